@@ -9,6 +9,10 @@ pairs (BASELINE.json configs[1]: batch 32 per GPU, 4 blocks x 32 features, depth
 inputs resident in HBM.  With N > 1 ranks (torchrun, one process per GPU) every rank owns
 its own 32-pair shard (weak scaling) and the step ends with ONE RCCL all-reduce of the flat
 gradient buffer.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times exactly K steps and prints the headline; `--full` adds the CPU baseline, the side entries
+(other inputs, precisions, sizes and configurations), the per-kernel roofline leg and 5 timed windows.  `--dump-outputs DIR`
+writes the last timed step's scores, loss and gradient as .npy files.
 """
 import argparse
 import json
@@ -216,6 +220,27 @@ def _count_collectives():
     return calls
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, outputs):
+    """(--dump-outputs) write each output as DIR/<name>.npy in float32 (float64 stays float64), so that two builds can be compared
+    output for output.  An array larger than its share of DUMP_LIMIT_BYTES is replaced by a fixed sample of its flattened elements
+    (numpy seed 0, sorted indices): the same elements in every run of the same arguments."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(outputs)
+    for name, t in outputs.items():
+        t = getattr(t, 'tensor', t).detach()                   # a MaskedTensor's padded data
+        if any(t.names):
+            t = t.rename(None)
+        a = t.cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(dirpath, name + '.npy'), a)
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
@@ -309,13 +334,20 @@ def parse_args():
                     help="block 1 on bit-packed inputs: 'structured' = csrc/block1_struct.hip (class tables + closed-form per-channel "
                          "product; constant-size and ragged batches, N <= 256, fp32 and bf16 engines), 'generic' = the kernels every block uses")
     ap.add_argument('--settle', type=int, default=64, help='untimed replays before the warm-up steps (clock / TLB settling)')
-    ap.add_argument('--windows', type=int, default=5,
+    ap.add_argument('--windows', type=int, default=None,
                     help='the K-step timed window is repeated this many times; ms_per_step / value are the MEDIAN window, '
-                         'ms_per_step_min / _max the spread')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+                         'ms_per_step_min / _max the spread (default: 1, so that a plain run times exactly K steps; 5 with --full)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure: the CPU baseline, the side entries of other inputs, precisions, sizes and '
+                         'configurations (dense_input, mfma_x3, precision16, batch256, wide64, module_surface, extra_configs), the '
+                         'per-kernel roofline leg, and 5 timed windows by default')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) leave out the CPU baseline')
     ap.add_argument('--no-extra-configs', action='store_true',
-                    help='do not append the cfg4 / cfg5 measurements (extra_configs) to the headline line')
-    ap.add_argument('--profile-steps', type=int, default=5, help='instrumented steps for the roofline leg')
+                    help='(--full) do not append the side entries and the cfg4 / cfg5 measurements (extra_configs) to the headline line')
+    ap.add_argument('--profile-steps', type=int, default=5, help='(--full) instrumented steps for the roofline leg')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help="after the timed steps, write what the headline's last step computed (rank 0: scores, loss, the flat "
+                         'parameter gradient) as DIR/<name>.npy, float32, at most 64 MB in all')
     ap.add_argument('--trace-steps', type=int, default=0,
                     help='(diagnostic) after the timed windows: synchronize, then this many steps with an event between every two; the '
                          'per-step GPU times go to step_trace_ms (how a window starts after an idle device)')
@@ -325,7 +357,10 @@ def parse_args():
                          'gradient, loss_sum, nodes, sizes} -- compared with a single-process run on the concatenated batch')
     ap.add_argument('--backend', default=None, help="torch.distributed backend (default: nccl = RCCL); 'gloo' lets "
                                                     'several ranks share one GPU for functional tests')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
+    return args
 
 
 def main():
@@ -342,8 +377,11 @@ def main():
     local_rank = local_rank % torch.cuda.device_count()     # (only differs in the shared-GPU functional test)
     torch.cuda.set_device(local_rank)
     dev = torch.device('cuda', local_rank)
-    out = run_config(args, args.config, rank, world, dev, cpu_leg=(world == 1 and not args.no_cpu_baseline))
-    if rank == 0 and world == 1 and out['config'].get('block1', 'generic') != 'generic' and not args.no_extra_configs:
+    # a plain run measures the headline alone; everything else it reports is measured with --full only
+    out = run_config(args, args.config, rank, world, dev, cpu_leg=(args.full and world == 1 and not args.no_cpu_baseline), profile=args.full,
+                     dump_dir=args.dump_outputs)
+    full = args.full and rank == 0 and world == 1
+    if full and out['config'].get('block1', 'generic') != 'generic' and not args.no_extra_configs:
         # the same step on the DENSE tensor representation through the generic block-1 kernels, reported beside the headline
         sub = run_config(args, args.config, rank, world, dev, cpu_leg=False, windows=min(args.windows, 3), block1='generic', input_form='dense')
         out['dense_input'] = {'value': sub['value'], 'unit': sub['unit'], 'ms_per_step': sub['ms_per_step'],
@@ -351,7 +389,7 @@ def main():
                               'input': sub['config']['input'], 'block1': sub['config']['block1'],
                               'roofline': {k: sub['roofline'][k] for k in ('kernel', 'bound', 'achieved', 'peak', 'unit', 'frac', 'traffic')
                                            if sub['roofline'] and k in sub['roofline']}}
-    if rank == 0 and world == 1 and args.config == 'cfg2' and args.path == 'engine' and args.mfma is None and args.precision is None \
+    if full and args.config == 'cfg2' and args.path == 'engine' and args.mfma is None and args.precision is None \
             and not args.no_extra_configs:
         # the same step with mlp1 / mlp2 on the bf16 matrix cores through the exact three-way operand split (--mfma x3; opt-in: it
         # draws more power, the part runs at its package power limit and clocks ~4 % lower under it, so its gain -- 0 ... 45 us per
@@ -359,7 +397,7 @@ def main():
         sub = run_config(args, args.config, rank, world, dev, cpu_leg=False, windows=min(args.windows, 3), mfma='x3', profile=False)
         out['mfma_x3'] = {'value': sub['value'], 'unit': sub['unit'], 'ms_per_step': sub['ms_per_step'], 'ms_per_step_min': sub['ms_per_step_min'],
                           'ms_per_step_max': sub['ms_per_step_max'], 'mlp_contraction': sub['config']['mlp_contraction']}
-    if rank == 0 and world == 1 and args.config == 'cfg2' and args.path == 'engine' and args.mfma is None and args.precision is None \
+    if full and args.config == 'cfg2' and args.path == 'engine' and args.mfma is None and args.precision is None \
             and args.batch is None and args.n is None and not args.no_extra_configs:
         # how the reference is actually run (side entries; the headline stays cfg2, fp32, 32 pairs per GPU):
         #   precision16 -- the cfg2 workload on the 16-bit engine (commander_explore.py:120-122 trains at precision=16; bf16 here)
@@ -374,10 +412,10 @@ def main():
                            'workload': sub['config']['workload'], 'block1': sub['config'].get('block1'), 'input': sub['config'].get('input')}
         #   wide64      -- the cfg2 workload on the 64-feature model (the reference takes any widths: models/layers.py:113-123)
         out['wide64'] = wide64_leg(args, dev)
-    if rank == 0 and world == 1 and args.path == 'engine' and not args.no_extra_configs and out['config'].get('block1', 'generic') != 'generic':
+    if full and args.path == 'engine' and not args.no_extra_configs and out['config'].get('block1', 'generic') != 'generic':
         # ... and through the module surface a user of the reference calls (dense loader batch in, fused_step)
         out['module_surface'] = module_surface_leg(args, args.config, rank, world, dev, out['ms_per_step'])
-    if rank == 0 and world == 1 and args.config == 'cfg2' and args.precision is None and args.path == 'engine' \
+    if full and args.config == 'cfg2' and args.precision is None and args.path == 'engine' \
             and not args.no_extra_configs and args.batch is None and args.n is None:
         # BASELINE configs 4 and 5 (per-GPU shard) under the same K / W protocol, outside the headline's timed region
         extra = {}
@@ -556,11 +594,11 @@ def module_surface_leg(args, config, rank, world, dev, engine_ms):
 
 
 def run_config(args, config, rank, world, dev, cpu_leg, windows=None, block1=None, input_form=None, path=None,
-               module_input_form=None, profile=True, mfma=None, precision_override=None, batch_override=None):
+               module_input_form=None, profile=True, mfma=None, precision_override=None, batch_override=None, dump_dir=None):
     """One measurement: build the workload of `config`, capture the step, settle, warm up, time `windows` windows of
     exactly K steps (barrier + synchronize on both sides, max over ranks), roofline leg.  Returns the JSON dict (rank 0).
     block1 / input_form: override --block1 / --input (the dense-input line reported beside the headline); path /
-    module_input_form: override --path / --module-input-form (module_surface_leg)."""
+    module_input_form: override --path / --module-input-form (module_surface_leg); dump_dir: --dump-outputs of the headline."""
     windows = args.windows if windows is None else windows
     mfma_arg = mfma
     precision = precision_override if precision_override is not None else (args.precision if config == args.config else None)
@@ -627,9 +665,8 @@ def run_config(args, config, rank, world, dev, cpu_leg, windows=None, block1=Non
 
     def model_work(eng=eng):
         if xbits is not None:
-            eng.step(params, grads, None, nvalid=nvalid, total_nodes=total_nodes, bits=xbits)
-        else:
-            eng.step(params, grads, None if dual else x, nvalid=None if dual else nvalid, total_nodes=total_nodes)
+            return eng.step(params, grads, None, nvalid=nvalid, total_nodes=total_nodes, bits=xbits)
+        return eng.step(params, grads, None if dual else x, nvalid=None if dual else nvalid, total_nodes=total_nodes)
     engine_work = model_work
 
     model = None
@@ -653,15 +690,17 @@ def run_config(args, config, rank, world, dev, cpu_leg, windows=None, block1=Non
 
         def model_work():                      # noqa: F811
             if path == 'fused_step':
-                model.fused_step({'input': xa}, {'input': xb})
-                return
+                loss, scores = model.fused_step({'input': xa}, {'input': xb})
+                return scores, loss
             for p in model.parameters():
                 p.grad = None
-            loss = model.loss(model({'input': xa}, {'input': xb})) * ((sum(sizes) if ragged else B * N) / total_nodes)
+            scores = model({'input': xa}, {'input': xb})
+            loss = model.loss(scores) * ((sum(sizes) if ragged else B * N) / total_nodes)
             loss.backward()
+            return scores, loss
 
     graph = None
-    model_work()                                  # allocates the backward workspace, sets kernel attributes
+    last = [model_work()]                         # allocates the backward workspace, sets kernel attributes
     torch.cuda.synchronize()
     # did the module surface put this batch on the structured block 1?  (fused_step's engine of this shape says so)
     surface_struct = bool(model is not None and path == 'fused_step' and any(
@@ -686,9 +725,10 @@ def run_config(args, config, rank, world, dev, cpu_leg, windows=None, block1=Non
             # with a collective in the capture the process group's watchdog thread is alive: its event queries must not be
             # counted against this thread's capture ('thread_local'; the default 'global' mode would invalidate the capture)
             with torch.cuda.graph(g, capture_error_mode='thread_local' if with_collective else 'global'):
-                model_work()
+                res = model_work()
                 if with_collective:
                     dp.allreduce_sum_(comm)
+            last[0] = res                         # the buffers every replay writes
             return g
         try:
             graph = capture(ar_in_graph)
@@ -716,7 +756,7 @@ def run_config(args, config, rank, world, dev, cpu_leg, windows=None, block1=Non
         if graph is not None:
             graph.replay()
         else:
-            model_work()
+            last[0] = model_work()
         if world > 1 and not ar_in_graph:
             dp.allreduce_sum_(comm)
         if calls is not None:
@@ -745,6 +785,9 @@ def run_config(args, config, rank, world, dev, cpu_leg, windows=None, block1=Non
         torch.cuda.synchronize()
         window_s.append(dp.max_over_ranks(time.perf_counter() - t0, dev))
     elapsed = sorted(window_s)[len(window_s) // 2]
+    if dump_dir is not None and rank == 0:
+        scores, loss = last[0]
+        dump_outputs(dump_dir, {'scores': scores, 'loss': loss, 'grads': comm})
     # the collective on its own (outside the timed windows: events inside them would cost the step two host calls each):
     # 20 back-to-back eager all-reduces of the same buffer on every rank, event-timed on rank 0's stream
     allreduce_ms = None

@@ -946,8 +946,51 @@ def main_round5b():
     np.savez_compressed(os.path.join(OUT, 'pinned_reference_errors.npz'), **out)
 
 
+def main_pins():
+    """tests/golden/oracle_pin_er_n17_b3_2blk.npz and pinned_pin_er_n19_b2_3blk.npz: the reference's own results on the two cases
+    tests/test_oracle_pinned.py and tests/test_oracle_pinned_decisions.py check the oracles against bit for bit.  ONE thread: ATen's
+    CPU gradients depend on the thread count, so the tests recompute the oracles with one thread too.  Both oracles are checked
+    torch.equal to the reference here (check_oracle_bit_equal, check_pinned_oracle) before anything is written."""
+    import_reference()
+    sys.path.insert(0, ROOT)
+    from graph_neural_net_amd import synthetic
+    from oracle import fgnn_oracle as O
+    from oracle import fgnn_oracle_pinned as OP
+    torch.set_num_threads(1)
+    model = build_reference_model(2, seed=5)
+    perturb_(model, 55)
+    x1, x2 = synthetic.make_batch(77, 3, 17, 'ErdosRenyi', 0.3, 0.1)
+    assert check_oracle_bit_equal(model, x1, x2, 'oracle pin') == 0.0
+    s, l, g = ref_step(model, x1, x2)
+    sd = {k: v.detach() for k, v in model.state_dict().items()}
+    keep = {}
+    O.node_embedding(x1, sd, keep)
+    inter = model.node_embedder({'input': x1})
+    out = {'x1': x1.numpy(), 'x2': x2.numpy(), 'scores': s.numpy(), 'loss': l.numpy()}
+    out.update({'sd/' + k[len('node_embedder.'):]: v.numpy() for k, v in sd.items()})
+    out.update({'grad/' + k: v.numpy() for k, v in g.items()})
+    out.update({'inter/' + k: inter[k].detach().numpy() for k in keep})
+    np.savez_compressed(os.path.join(OUT, 'oracle_pin_er_n17_b3_2blk.npz'), **out)
+
+    model = build_reference_model(3, seed=8)
+    perturb_(model, 88)
+    x1, x2 = synthetic.make_batch(78, 2, 19, 'ErdosRenyi', 0.3, 0.1)
+    out = {'x1': x1.numpy(), 'x2': x2.numpy()}
+    out.update({'sd/' + k[len('node_embedder.'):]: v.numpy() for k, v in model.state_dict().items()})
+    for tag, m in (('f32', model), ('f64', f64(model))):
+        (masks, idx), (s, l, g) = check_pinned_oracle(m, x1, x2, 'pinned pin ' + tag)
+        out.update({'%s/%s' % (tag, k): v for k, v in OP.pack_decisions(masks, idx).items()})
+        out[tag + '/scores'] = s.numpy()
+        out[tag + '/loss'] = l.numpy()
+        out.update({'%s/grad/%s' % (tag, k): v.numpy() for k, v in g.items()})
+    np.savez_compressed(os.path.join(OUT, 'pinned_pin_er_n19_b2_3blk.npz'), **out)
+    print('oracle_pin_er_n17_b3_2blk.npz, pinned_pin_er_n19_b2_3blk.npz written')
+
+
 if __name__ == '__main__':
-    if len(sys.argv) > 1 and sys.argv[1] == 'round5b':
+    if len(sys.argv) > 1 and sys.argv[1] == 'pins':
+        main_pins()
+    elif len(sys.argv) > 1 and sys.argv[1] == 'round5b':
         main_round5b()
     elif len(sys.argv) > 1 and sys.argv[1] == 'round5':
         main_round5()

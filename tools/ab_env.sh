@@ -4,7 +4,7 @@ VAR=$1; shift
 for rep in 1 2; do
 for v in 0 1; do
   for cfg in ${@:-cfg2}; do
-    env $VAR=$v python bench.py --config $cfg --no-cpu-baseline --no-extra-configs 2>/dev/null | python -c "
+    env $VAR=$v python bench.py --config $cfg --full --no-cpu-baseline --no-extra-configs 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$VAR=$v $cfg ms/step', round(d['ms_per_step'],4), 'module', (d.get('module_surface') or {}).get('ms_per_step'))

@@ -10,7 +10,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for spec in sys.argv[1:]:
     name, _, extra = spec.partition(':')
-    args = ['--no-cpu-baseline', '--no-extra-configs'] + (extra.split() if extra else ['--mfma', 'x3'])
+    args = ['--full', '--no-cpu-baseline', '--no-extra-configs'] + (extra.split() if extra else ['--mfma', 'x3'])
     if name == 'main':
         cmd = [sys.executable, os.path.join(ROOT, 'bench.py')] + args
     else:
