@@ -127,6 +127,14 @@ class PackJob(C.Structure):
                 ('out', C.c_void_p)]
 
 
+class PairgenArgs(C.Structure):       # fgnn_pairgen_args (csrc/pairgen.hip)
+    _fields_ = [('seed', C.c_ulonglong), ('first', C.c_longlong), ('B', C.c_int), ('N', C.c_int),
+                ('family', C.c_int), ('noise_model', C.c_int), ('edge_density', C.c_double),
+                ('thr_edge', C.c_ulonglong), ('thr_noise1', C.c_ulonglong), ('thr_noise2', C.c_ulonglong),
+                ('thr_vertex', C.c_ulonglong), ('swaps_per_edge', C.c_int),
+                ('bits1', C.c_void_p), ('bits2', C.c_void_p), ('nvalid', C.c_void_p)]
+
+
 MAX_GRAD_JOBS = 16
 MAX_PACK_JOBS = 24
 _VP, _LL, _I, _F = C.c_void_p, C.c_longlong, C.c_int, C.c_float
@@ -238,6 +246,8 @@ _SIGNATURES = {
     'fgnn_adjacency_degree': [_VP, _VP, _I, _I, _VP, _VP],
     'fgnn_accuracy_max': [_VP, _VP, _I, _I, _VP, _VP],
     'fgnn_lsap_accuracy': [_VP, _LL, _I, _VP, _I, _I, _VP, _VP, _VP],
+    'fgnn_pairgen_supported': [_I, _I, _I],
+    'fgnn_pairgen': [C.POINTER(PairgenArgs), _VP],
     # ---- bf16 path ----
     'fgnn_tiles_per_graph16': [_I, _I],
     'fgnn_to_bf16': [_VP, _VP, _I, _I, _I, _I, _VP, _LL, _LL, _VP],

@@ -1,0 +1,442 @@
+// QAP pair generation on the device (loaders/data_generator.py:38-125,175-219, QAP_Generator): one single-wave workgroup per
+// pair builds the parent graph and its noisy copy as bit rows in LDS and stores both in the engine's wire format.
+//
+// Randomness is counter-based: raw 32-bit draw t of stream s of pair k is word t & 7 (low half first) of Philox4x64-10 at
+// counter (t >> 3, k, s, 0) under key (seed, 0), so a pair never depends on the launch that made it.  Events are u32 < thr,
+// integers in [0, k) are (u32 * k) >> 32 (tests/pairgen_ref.py restates every step in numpy, bit for bit).
+//
+// The parallel parts (vertex count, Erdos-Renyi draws, noise, relabelling, stores) run across the 64 lanes; the serial chains
+// (Regular's double-edge swaps, Barabasi-Albert attachment, EdgeSwap noise) are wave-uniform code on LDS, with their draws
+// precomputed one per lane and read back by readlane.  Inside a chain LDS is written by single instructions of a few lanes
+// (atomics without return: nothing waits for them); a wave's LDS accesses complete in issue order, so the next step's reads see
+// those writes without a barrier.
+#include "fgnn_common.h"
+
+namespace {
+
+constexpr int PG_THREADS = 64;
+enum { ST_SIZE = 0, ST_PARENT, ST_NOISE1, ST_NOISE2, ST_RELABEL, ST_CHAIN };
+constexpr int MAX_SIZE_DRAWS = 64;       // n < 2 is redrawn at most this often, then n = 2 (tests/pairgen_ref.py)
+constexpr unsigned long long THR_ONE = 1ull << 32;
+
+struct P4 {
+    unsigned long long v0, v1, v2, v3;
+};
+
+// Random123 Philox4x64-10 (Salmon et al., SC'11) on counter (c0, c1, c2, 0), key (k0, 0)
+DEVI P4 philox(unsigned long long c0, unsigned long long c1, unsigned long long c2, unsigned long long k0) {
+    const unsigned long long M0 = 0xD2E7470EE14C6C93ull, M1 = 0xCA5A826395121157ull;
+    unsigned long long c3 = 0, k1 = 0;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        if (r) {
+            k0 += 0x9E3779B97F4A7C15ull;
+            k1 += 0xBB67AE8584CAA73Bull;
+        }
+        const unsigned long long hi0 = __umul64hi(M0, c0), lo0 = M0 * c0;
+        const unsigned long long hi1 = __umul64hi(M1, c2), lo1 = M1 * c2;
+        const unsigned long long n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+        c0 = n0;
+        c1 = lo1;
+        c2 = n2;
+        c3 = lo0;
+    }
+    return P4{c0, c1, c2, c3};
+}
+
+DEVI unsigned word_of(const P4 &r, int w) {
+    const unsigned long long x = w < 2 ? r.v0 : w < 4 ? r.v1 : w < 6 ? r.v2 : r.v3;
+    return (w & 1) ? (unsigned)(x >> 32) : (unsigned)x;
+}
+
+struct Pair {
+    unsigned long long seed, k;
+    DEVI unsigned draw(int stream, unsigned long long t) const { return word_of(philox(t >> 3, k, stream, seed), (int)(t & 7)); }
+    DEVI P4 block(int stream, unsigned long long q) const { return philox(q, k, stream, seed); }
+};
+
+DEVI int below(unsigned u, int k) { return (int)(((unsigned long long)u * (unsigned)k) >> 32); }
+DEVI int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
+DEVI int bit(const unsigned *rows, int W, int i, int j) { return uni((rows[i * W + (j >> 5)] >> (j & 31)) & 1); }
+DEVI void set_edge(unsigned *rows, int W, int i, int j) {           // any lane, both directions
+    atomicOr(&rows[i * W + (j >> 5)], 1u << (j & 31));
+    atomicOr(&rows[j * W + (i >> 5)], 1u << (i & 31));
+}
+DEVI void set_edge_one(unsigned *rows, int W, int i, int j) {      // one lane, both directions (LDS atomics without return)
+    atomicOr(&rows[i * W + (j >> 5)], 1u << (j & 31));
+    atomicOr(&rows[j * W + (i >> 5)], 1u << (i & 31));
+}
+// The double-edge swap (u, v), (s, t) -> (u, t), (s, v) on four distinct vertices: the 8 bits it changes toggled by lanes 0-7 in
+// ONE atomic xor (some may share a word), plus lanes 8 / 9 storing the two edge-list entries (wave-uniform call)
+DEVI void swap_edges(unsigned *rows, int W, int u, int v, int s, int t, unsigned short *edges, int A, int ea, int Bi, int eb) {
+    const int lane = threadIdx.x;
+    if (lane < 8) {
+        const int p = lane >> 1;                                 // (u, v), (s, t) go; (u, t), (s, v) come
+        const int a = (p & 1) ? s : u, b = (p == 0 || p == 3) ? v : t;
+        const int r = (lane & 1) ? b : a, c = (lane & 1) ? a : b;
+        atomicXor(&rows[r * W + (c >> 5)], 1u << (c & 31));
+    } else if (edges && lane < 10) {
+        edges[lane == 8 ? A : Bi] = (unsigned short)(lane == 8 ? ea : eb);
+    }
+}
+
+DEVI int regular_degree(int n, double p) {
+    int d = (int)(p * n);
+    if ((n * d) & 1) d++;
+    return d;
+}
+DEVI int ba_attachments(int n, double p) { return (int)(p * (n - 1) / 2.0); }
+
+// Independent Bernoulli draws (event u32 < thr) of one stream at positions i N + j, i < j < n, as symmetric bits
+DEVI void erdos_renyi(unsigned *rows, int W, int n, int N, const Pair &pr, int stream, unsigned long long thr) {
+    const int lane = threadIdx.x;
+    const int nq = (n * N + 7) >> 3;
+    for (int q = lane; q < nq; q += PG_THREADS) {
+        const P4 r = pr.block(stream, q);
+        int i = (8 * q) / N, j = 8 * q - i * N;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) {
+            if (j > i && j < n && word_of(r, w) < thr) set_edge(rows, W, i, j);
+            if (++j == N) {
+                j = 0;
+                ++i;
+            }
+        }
+    }
+}
+
+// W' = (W & ~Z1) | (~W & Z2) on the upper triangle, mirrored (data_generator.py:79-87)
+DEVI void noise_erdos_renyi(const unsigned *rp, unsigned *rq, int W, int n, int N, const Pair &pr, unsigned long long thr1,
+                            unsigned long long thr2) {
+    const int lane = threadIdx.x;
+    const int nq = (n * N + 7) >> 3;
+    for (int q = lane; q < nq; q += PG_THREADS) {
+        const P4 r1 = pr.block(ST_NOISE1, q), r2 = pr.block(ST_NOISE2, q);
+        int i = (8 * q) / N, j = 8 * q - i * N;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) {
+            if (j > i && j < n) {
+                const bool par = (rp[i * W + (j >> 5)] >> (j & 31)) & 1;
+                if (par ? word_of(r1, w) >= thr1 : word_of(r2, w) < thr2) set_edge(rq, W, i, j);
+            }
+            if (++j == N) {
+                j = 0;
+                ++i;
+            }
+        }
+    }
+}
+
+// The (u < v) edges of `rows` in row-major order -> edges[] (u | v << 8); returns their count (wave-uniform)
+DEVI int edge_list(const unsigned *rows, int W, int n, unsigned short *edges) {
+    const int lane = threadIdx.x;
+    int carry = 0;
+    for (int rb = 0; rb < n; rb += PG_THREADS) {
+        const int u = rb + lane;
+        int c = 0;
+        if (u < n)
+            for (int w = 0; w < W; ++w) c += __popc(rows[u * W + w] & (32 * w > u ? ~0u : 32 * w + 31 <= u ? 0u : ~0u << (u - 32 * w + 1)));
+        int x = c;
+#pragma unroll
+        for (int off = 1; off < PG_THREADS; off <<= 1) {
+            const int y = __shfl_up(x, off);
+            if (lane >= off) x += y;
+        }
+        int o = carry + x - c;
+        if (u < n)
+            for (int w = 0; w < W; ++w) {
+                unsigned b = rows[u * W + w] & (32 * w > u ? ~0u : 32 * w + 31 <= u ? 0u : ~0u << (u - 32 * w + 1));
+                while (b) {
+                    const int j = 32 * w + __ffs(b) - 1;
+                    b &= b - 1;
+                    edges[o++] = (unsigned short)(u | (j << 8));
+                }
+            }
+        carry += __shfl(x, PG_THREADS - 1);
+    }
+    return uni(carry);
+}
+
+// Random d-regular graph (synthetic.random_regular's scheme): circulant seed, `steps` double-edge swaps, random relabelling
+DEVI void random_regular(unsigned *rp, int W, int n, int d, int swaps_per_edge, const Pair &pr, unsigned short *edges,
+                         unsigned char *perm, unsigned char *inv) {
+    const int lane = threadIdx.x;
+    const int m = n * d / 2, half = (d / 2) * n;
+    for (int e = lane; e < m; e += PG_THREADS) {       // edge (s-1) n + i = {i, i+s}, then {i, i + n/2} for odd d
+        int i, v;
+        if (e < half) {
+            i = e % n;
+            v = (i + e / n + 1) % n;
+        } else {
+            i = e - half;
+            v = i + n / 2;
+        }
+        const int a = min(i, v), b = max(i, v);
+        edges[e] = (unsigned short)(a | (b << 8));
+        set_edge(rp, W, a, b);
+    }
+    __syncthreads();
+    const int steps = swaps_per_edge * m;
+    for (int base = 0; base < steps; base += PG_THREADS) {
+        const int s = base + lane;                       // swap s: draws 4 s .. 4 s + 2 = block s >> 1, words 4 (s & 1) ..
+        const P4 r = pr.block(ST_CHAIN, (unsigned long long)(s >> 1));
+        const unsigned long long x = (s & 1) ? r.v2 : r.v0, y = (s & 1) ? r.v3 : r.v1;
+        const int ra = below((unsigned)x, m), rb = below((unsigned)(x >> 32), m), rf = (int)((unsigned)y >> 31);
+        const int cnt = min(PG_THREADS, steps - base);
+        // the edges of swap l + 1 are read while swap l is decided (one LDS round trip per swap); if swap l rewrites one of
+        // them, the register copy is patched with the new value
+        int A = __builtin_amdgcn_readlane(ra, 0), Bi = __builtin_amdgcn_readlane(rb, 0);
+        int pe1 = edges[A], pe2 = edges[Bi];
+        for (int l = 0; l < cnt; ++l) {
+            const int e1 = uni(pe1), e2 = uni(pe2);
+            const int nA = l + 1 < cnt ? __builtin_amdgcn_readlane(ra, min(l + 1, PG_THREADS - 1)) : 0;
+            const int nB = l + 1 < cnt ? __builtin_amdgcn_readlane(rb, min(l + 1, PG_THREADS - 1)) : 0;
+            pe1 = edges[nA];
+            pe2 = edges[nB];
+            const int u = e1 & 255, v = e1 >> 8;
+            int s0 = e2 & 255, t0 = e2 >> 8;
+            if (__builtin_amdgcn_readlane(rf, l)) {
+                const int tmp = s0;
+                s0 = t0;
+                t0 = tmp;
+            }
+            const unsigned w1 = rp[u * W + (t0 >> 5)], w2 = rp[s0 * W + (v >> 5)];      // both reads in one round trip
+            const int hit = uni(((w1 >> (t0 & 31)) | (w2 >> (v & 31))) & 1);
+            if (A != Bi && u != t0 && s0 != v && u != s0 && v != t0 && !hit) {
+                const int ea = min(u, t0) | (max(u, t0) << 8), eb = min(s0, v) | (max(s0, v) << 8);
+                swap_edges(rp, W, u, v, s0, t0, edges, A, ea, Bi, eb);
+                pe1 = nA == A ? ea : nA == Bi ? eb : pe1;
+                pe2 = nB == A ? ea : nB == Bi ? eb : pe2;
+            }
+            A = nA;
+            Bi = nB;
+        }
+    }
+    // relabel: Fisher-Yates from the top (draw i of the relabel stream picks j in [0, i]), W'[a][b] = W[perm a][perm b]
+    for (int i = lane; i < n; i += PG_THREADS) perm[i] = (unsigned char)i;
+    __syncthreads();
+    for (int top = n - 1; top >= 1; top -= PG_THREADS) {
+        const int i = top - lane;
+        const int rj = i >= 1 ? below(pr.draw(ST_RELABEL, (unsigned long long)i), i + 1) : 0;
+        const int cnt = min(PG_THREADS, top);
+        for (int l = 0; l < cnt; ++l) {
+            const int ii = top - l, j = __builtin_amdgcn_readlane(rj, l);
+            const int pi = uni(perm[ii]), pj = uni(perm[j]);
+            if (lane == 0) {
+                perm[ii] = (unsigned char)pj;
+                perm[j] = (unsigned char)pi;
+            }
+        }
+    }
+    __syncthreads();
+    for (int a = lane; a < n; a += PG_THREADS) inv[perm[a]] = (unsigned char)a;
+    for (int i = lane; i < n * W; i += PG_THREADS) rp[i] = 0;
+    __syncthreads();
+    for (int e = lane; e < m; e += PG_THREADS) set_edge(rp, W, inv[edges[e] & 255], inv[edges[e] >> 8]);
+    __syncthreads();
+}
+
+// networkx 3.x barabasi_albert_graph: star on m + 1 nodes, then each new node takes m distinct targets drawn from the
+// repeated-nodes list (duplicates rejected); the list grows by the targets (in draw order) and m copies of the new node
+DEVI void barabasi_albert(unsigned *rp, int W, int n, int m, const Pair &pr, unsigned char *rep, unsigned char *mark) {
+    const int lane = threadIdx.x;
+    for (int i = lane; i < m; i += PG_THREADS) {
+        rep[i] = 0;
+        rep[m + i] = (unsigned char)(i + 1);
+        set_edge(rp, W, 0, i + 1);
+    }
+    for (int i = lane; i < n; i += PG_THREADS) mark[i] = 0;      // sources are >= 2
+    __syncthreads();
+    int len = 2 * m;
+    long long t = 0, t0 = -PG_THREADS;
+    unsigned rr = 0;
+    for (int source = m + 1; source < n; ++source) {
+        int cnt = 0;
+        while (cnt < m) {
+            if (t - t0 >= PG_THREADS) {
+                t0 = t;
+                rr = pr.draw(ST_CHAIN, (unsigned long long)(t0 + lane));
+            }
+            const unsigned u = __builtin_amdgcn_readlane(rr, (int)(t - t0));
+            ++t;
+            const int x = uni(rep[below(u, len)]);
+            if (uni(mark[x]) != source) {
+                if (lane == 0) {
+                    mark[x] = (unsigned char)source;
+                    rep[len + cnt] = (unsigned char)x;
+                    set_edge_one(rp, W, source, x);
+                }
+                ++cnt;
+            }
+        }
+        for (int i = lane; i < m; i += PG_THREADS) rep[len + m + i] = (unsigned char)source;
+        len += 2 * m;
+        __syncthreads();
+    }
+}
+
+DEVI void directed(const unsigned short *edges, int me, int i, int &s, int &t) {
+    const int e = uni(edges[i < me ? i : i - me]);
+    s = i < me ? (e & 255) : (e >> 8);
+    t = i < me ? (e >> 8) : (e & 255);
+}
+
+// data_generator.py:89-116 on rq (a copy of the parent), edge list of the parent (row-major u < v, then the reversals):
+// outer edge o fires on draw o of noise-1; inner edge i on draw o * 2m + i of noise-2; the first inner edge that fires and is
+// swappable on the current graph is swapped; (u, v) is gone after it, so no later inner edge of the same o can be
+DEVI void noise_edge_swap(unsigned *rq, int W, const unsigned short *edges, int me, const Pair &pr, unsigned long long thr) {
+    const int lane = threadIdx.x;
+    const int L = 2 * me;
+    for (int ob = 0; ob < L; ob += PG_THREADS) {
+        const int o = ob + lane;
+        unsigned long long fire = __ballot(o < L && pr.draw(ST_NOISE1, (unsigned long long)o) < thr);
+        while (fire) {
+            const int oo = ob + __ffsll((long long)fire) - 1;
+            fire &= fire - 1;
+            int u, v;
+            directed(edges, me, oo, u, v);
+            if (!bit(rq, W, u, v)) continue;
+            const long long pos0 = (long long)oo * L;
+            const long long q0 = pos0 >> 3, q1 = (pos0 + L + 7) >> 3;
+            for (long long qb = q0; qb < q1; qb += PG_THREADS) {
+                const long long q = qb + lane;
+                int best = -1;
+                if (q < q1) {
+                    const P4 r = pr.block(ST_NOISE2, (unsigned long long)q);
+#pragma unroll
+                    for (int w = 0; w < 8; ++w) {
+                        const long long i = 8 * q + w - pos0;
+                        if (best < 0 && i >= 0 && i < L && word_of(r, w) < thr) {
+                            const int ii = (int)i;
+                            const int e = edges[ii < me ? ii : ii - me];
+                            const int s = ii < me ? (e & 255) : (e >> 8), t = ii < me ? (e >> 8) : (e & 255);
+                            const bool has_st = (rq[s * W + (t >> 5)] >> (t & 31)) & 1;
+                            const bool has_ut = (rq[u * W + (t >> 5)] >> (t & 31)) & 1;
+                            const bool has_sv = (rq[s * W + (v >> 5)] >> (v & 31)) & 1;
+                            if (has_st && u != t && s != v && !has_ut && !has_sv) best = ii;
+                        }
+                    }
+                }
+                const unsigned long long found = __ballot(best >= 0);
+                if (found) {
+                    const int i = __builtin_amdgcn_readlane(best, __ffsll((long long)found) - 1);
+                    int s, t;
+                    directed(edges, me, i, s, t);
+                    swap_edges(rq, W, u, v, s, t, nullptr, 0, 0, 0, 0);
+                    break;
+                }
+            }
+        }
+    }
+}
+
+struct KArgs {
+    fgnn_pairgen_args a;
+    int emax;      // edge-list entries in LDS
+};
+
+__global__ __launch_bounds__(PG_THREADS) void pairgen_kernel(KArgs ka) {
+    extern __shared__ unsigned smem[];
+    const fgnn_pairgen_args &a = ka.a;
+    const int N = a.N, W = (N + 31) >> 5, lane = threadIdx.x;
+    const Pair pr{a.seed, (unsigned long long)(a.first + blockIdx.x)};
+    unsigned *rp = smem, *rq = smem + N * W;
+    unsigned char *perm = (unsigned char *)(rq + N * W), *inv = perm + 256;    // BA: mark = perm
+    unsigned short *edges = (unsigned short *)(inv + 256);
+    unsigned char *rep = (unsigned char *)(edges + ((ka.emax + 1) & ~1));
+    for (int i = lane; i < 2 * N * W; i += PG_THREADS) smem[i] = 0;
+
+    // vertex count: n ~ Binomial(N, vertex_proba) as N Bernoulli draws; n < 2 redrawn from the next N positions
+    int n = N;
+    if (a.thr_vertex < THR_ONE) {
+        n = 2;
+        for (int r = 0; r < MAX_SIZE_DRAWS; ++r) {
+            int c = 0;
+            for (int b = 0; b < N; b += PG_THREADS) {
+                const int i = b + lane;
+                c += __popcll(__ballot(i < N && pr.draw(ST_SIZE, (unsigned long long)(r * N + i)) < a.thr_vertex));
+            }
+            if (c >= 2) {
+                n = c;
+                break;
+            }
+        }
+    }
+    __syncthreads();
+
+    if (a.family == FGNN_PAIRGEN_REGULAR)
+        random_regular(rp, W, n, regular_degree(n, a.edge_density), a.swaps_per_edge, pr, edges, perm, inv);
+    else if (a.family == FGNN_PAIRGEN_BARABASI_ALBERT)
+        barabasi_albert(rp, W, n, ba_attachments(n, a.edge_density), pr, rep, perm);
+    else
+        erdos_renyi(rp, W, n, N, pr, ST_PARENT, a.thr_edge);
+    __syncthreads();
+
+    if (a.noise_model == FGNN_PAIRGEN_EDGE_SWAP) {
+        for (int i = lane; i < N * W; i += PG_THREADS) rq[i] = rp[i];
+        const int me = edge_list(rp, W, n, edges);
+        __syncthreads();
+        noise_edge_swap(rq, W, edges, me, pr, a.thr_noise1);
+    } else {
+        noise_erdos_renyi(rp, rq, W, n, N, pr, a.thr_noise1, a.thr_noise2);
+    }
+    __syncthreads();
+
+    const long long off = (long long)blockIdx.x * N * W;
+    for (int i = lane; i < N * W; i += PG_THREADS) {
+        a.bits1[off + i] = rp[i];
+        a.bits2[off + i] = rq[i];
+    }
+    if (a.nvalid && lane == 0) a.nvalid[blockIdx.x] = n;
+}
+
+int host_regular_degree(int n, double p) {
+    int d = (int)(p * n);
+    if ((n * d) & 1) d++;
+    return d;
+}
+
+LdsAttrCache g_pairgen_lds;
+
+}  // namespace
+
+extern "C" int fgnn_pairgen_supported(int N, int family, int noise_model) {
+    return N >= 1 && N <= FGNN_PAIRGEN_MAX_N && family >= 0 && family <= 2 && noise_model >= 0 && noise_model <= 1;
+}
+
+extern "C" int fgnn_pairgen(const fgnn_pairgen_args *args, void *stream) {
+    FGNN_CHECK(args, "fgnn_pairgen: NULL arguments");
+    const fgnn_pairgen_args &a = *args;
+    FGNN_CHECK(fgnn_pairgen_supported(a.N, a.family, a.noise_model), "fgnn_pairgen: unsupported N=%d family=%d noise_model=%d",
+               a.N, a.family, a.noise_model);
+    FGNN_CHECK(a.B >= 0 && a.first >= 0 && a.bits1 && a.bits2, "fgnn_pairgen: bad arguments (B=%d, first=%lld)", a.B, a.first);
+    FGNN_CHECK(a.edge_density >= 0.0 && a.edge_density < 1.0, "fgnn_pairgen: edge_density %g outside [0, 1)", a.edge_density);
+    FGNN_CHECK(a.swaps_per_edge >= 0 && a.swaps_per_edge <= 10000, "fgnn_pairgen: swaps_per_edge %d outside [0, 10000]",
+               a.swaps_per_edge);
+    FGNN_CHECK(a.thr_edge <= THR_ONE && a.thr_noise1 <= THR_ONE && a.thr_noise2 <= THR_ONE && a.thr_vertex <= THR_ONE &&
+                   a.thr_vertex > 0, "fgnn_pairgen: thresholds outside [0, 2^32] (vertex threshold > 0)");
+    FGNN_CHECK(a.thr_vertex == THR_ONE || a.N >= 2, "fgnn_pairgen: a binomial vertex count needs N >= 2");
+    const int N = a.N;
+    long long emax = 0, rep = 0;
+    if (a.family == FGNN_PAIRGEN_REGULAR) {
+        for (int n = (a.thr_vertex == THR_ONE ? N : 2); n <= N; ++n) emax = std::max(emax, (long long)n * host_regular_degree(n, a.edge_density) / 2);
+    } else if (a.family == FGNN_PAIRGEN_BARABASI_ALBERT) {
+        const int m = (int)(a.edge_density * (N - 1) / 2.0);
+        FGNN_CHECK(a.thr_vertex == THR_ONE, "fgnn_pairgen: BarabasiAlbert needs a constant vertex count");
+        FGNN_CHECK(m >= 1 && m < N, "fgnn_pairgen: BarabasiAlbert with m=%d attachments on N=%d vertices", m, N);
+        emax = (long long)m * (N - m);
+        rep = 2 * emax;
+    }
+    if (a.noise_model == FGNN_PAIRGEN_EDGE_SWAP && a.family == FGNN_PAIRGEN_ERDOS_RENYI) emax = (long long)N * (N - 1) / 2;
+    if (a.B == 0) return 0;
+    const int W = (N + 31) / 32;
+    const size_t lds = (size_t)2 * N * W * 4 + 512 + (size_t)((emax + 1) & ~1ll) * 2 + (size_t)rep;
+    FGNN_CHECK(lds <= 160 * 1024, "fgnn_pairgen: %zu bytes of LDS needed", lds);
+    FGNN_CHECK(fgnn_raise_lds(g_pairgen_lds, (const void *)pairgen_kernel, lds), "fgnn_pairgen: cannot raise LDS to %zu bytes", lds);
+    KArgs ka;
+    ka.a = a;
+    ka.emax = (int)emax;
+    hipLaunchKernelGGL(pairgen_kernel, dim3((unsigned)a.B), dim3(PG_THREADS), lds, (hipStream_t)stream, ka);
+    FGNN_LAUNCH_CHECK();
+    return 0;
+}

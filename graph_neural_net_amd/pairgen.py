@@ -1,0 +1,130 @@
+"""QAP graph pairs generated on the device (loaders/data_generator.py:38-125,175-219, ``QAP_Generator``).
+
+``PairGenerator`` writes (graph, noisy graph) pairs straight into the engine's wire format -- (B, N, ceil(N/32)) int32 words,
+bit j of word row i = W[i][j] (``synthetic.pack_adjacency``) -- with ``csrc/pairgen.hip``; ``.bits`` feeds
+``FgnnTrainer.train_step_bits`` and ``.dense`` builds the reference's collate structures from the same words.
+
+Semantics follow the reference:
+
+* vertex count: N, or n ~ Binomial(N, vertex_proba) as N Bernoulli draws, shared by both sides of a pair.  One deviation:
+  a draw with n < 2 is redrawn from the next N positions of the size stream (at most 64 times, then n = 2), where the
+  reference would build a graph on 0 or 1 vertices;
+* families: ``ErdosRenyi`` (one draw per unordered pair), ``Regular`` (degree d = int(p n), +1 if n d is odd; circulant seed,
+  ``swaps_per_edge`` * m degree-preserving double-edge swaps as in ``synthetic.random_regular``, random relabelling),
+  ``BarabasiAlbert`` (m = int(p (n - 1) / 2); networkx 3.x's star + repeated-nodes attachment, no relabelling; constant N);
+* noise models: ``ErdosRenyi`` (W' = W (1 - Z1) + (1 - W) Z2, Z1 ~ ER(noise), Z2 ~ ER(p noise / (1 - p))) and ``EdgeSwap``
+  (the reference's nested loop over the parent's directed edges: the (u < v) edges in row-major order, then their reversals);
+* the pair is not permuted: the ground truth is the identity (``triplet_loss``).
+
+Randomness is counter-based (Philox4x64-10 keyed by ``seed``): every draw is addressed by (pair index, stream, position), so
+pair k of a dataset is the same however a range is split into calls, devices or ranks -- data-parallel rank r of w takes
+pairs ``step * B * w + r * B ...`` with no communication.  Streams: 0 size, 1 parent, 2 noise-1, 3 noise-2, 4 relabel,
+5 swap chain / attachment.  Probabilities are integer thresholds ``min(2^32, floor(prob * 2^32))`` compared with raw 32-bit
+draws; integers in [0, k) are ``(u32 * k) >> 32`` (``tests/pairgen_ref.py`` restates it all in numpy, bit for bit).
+
+There is no CPU fallback (``_lib``).
+"""
+import ctypes as C
+import math
+
+import torch
+
+from . import _lib
+from .inputs import expand_adjacency
+from .masked import MaskedTensor
+
+FAMILIES = {'ErdosRenyi': 0, 'Regular': 1, 'BarabasiAlbert': 2}
+NOISE_MODELS = {'ErdosRenyi': 0, 'EdgeSwap': 1}
+MAX_N = 256                   # include/fgnn_hip.h: FGNN_PAIRGEN_MAX_N
+
+
+def threshold(prob):
+    """Integer threshold of an event of probability prob on a raw 32-bit draw (u32 < thr)."""
+    return min(1 << 32, int(math.floor(prob * 4294967296.0)))
+
+
+class PairGenerator:
+    """On-device twin of the reference's ``QAP_Generator`` (the ``data.train`` / ``data.test`` parameters)."""
+
+    def __init__(self, n_vertices, generative_model='Regular', noise_model='ErdosRenyi', edge_density=0.2, noise=0.1,
+                 vertex_proba=1.0, seed=0, swaps_per_edge=10, device=None):
+        N = int(n_vertices)
+        p, noise, vertex_proba = float(edge_density), float(noise), float(vertex_proba)
+        if not 1 <= N <= MAX_N:
+            raise ValueError('n_vertices must be in [1, %d], got %d' % (MAX_N, N))
+        if generative_model not in FAMILIES:
+            raise ValueError('unknown graph family %r' % (generative_model,))
+        if noise_model not in NOISE_MODELS:
+            raise ValueError('unknown noise model %r' % (noise_model,))
+        if not 0.0 <= p < 1.0:
+            raise ValueError('edge_density must be in [0, 1), got %r' % (edge_density,))
+        if not 0.0 <= noise <= 1.0:
+            raise ValueError('noise must be in [0, 1], got %r' % (noise,))
+        if not 0.0 < vertex_proba <= 1.0:
+            raise ValueError('vertex_proba must be in (0, 1], got %r' % (vertex_proba,))
+        if vertex_proba < 1.0 and N < 2:
+            raise ValueError('a binomial vertex count needs n_vertices >= 2, got %d' % N)
+        if not 0 <= int(swaps_per_edge) <= 10000:
+            raise ValueError('swaps_per_edge must be in [0, 10000], got %r' % (swaps_per_edge,))
+        if generative_model == 'BarabasiAlbert':
+            m = int(p * (N - 1) / 2)
+            if m < 1 or m >= N:
+                raise ValueError('no Barabasi-Albert graph with m = %d attachments on %d vertices '
+                                 '(m = int(edge_density * (n_vertices - 1) / 2) must be in [1, n_vertices))' % (m, N))
+            if vertex_proba < 1.0:
+                raise ValueError('BarabasiAlbert needs a constant vertex count (vertex_proba = 1), got vertex_proba %r'
+                                 % (vertex_proba,))
+        if not 0 <= int(seed) < 1 << 64:
+            raise ValueError('seed must be in [0, 2^64), got %r' % (seed,))
+        self.n_vertices, self.generative_model, self.noise_model = N, generative_model, noise_model
+        self.edge_density, self.noise, self.vertex_proba = p, noise, vertex_proba
+        self.seed, self.swaps_per_edge = int(seed), int(swaps_per_edge)
+        self.constant_n_vertices = vertex_proba == 1.0
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        self._thr = (threshold(p), threshold(noise), threshold(p * noise / (1 - p)), threshold(vertex_proba))
+
+    @classmethod
+    def from_config(cls, cfg, seed=0, **kw):
+        """The reference's ``data.train`` / ``data.test`` dict as is (keys it does not use, num_examples_* among them, are ignored)."""
+        return cls(cfg['n_vertices'], generative_model=cfg['generative_model'], noise_model=cfg['noise_model'],
+                   edge_density=cfg['edge_density'], noise=cfg['noise'], vertex_proba=cfg.get('vertex_proba', 1.0),
+                   seed=seed, **kw)
+
+    def bits(self, first, count):
+        """Pairs first .. first + count - 1 -> (bits1, bits2, nvalid): (count, N, ceil(N/32)) int32 device tensors and, when the
+        vertex count is binomial, the (count,) int32 vertex counts (else None).  Enqueued on the current stream."""
+        if self.device.type != 'cuda':
+            raise RuntimeError('PairGenerator: device %s; the generator runs on the GPU only (there is no CPU path)' % (self.device,))
+        first, count = int(first), int(count)
+        if first < 0 or count < 0:
+            raise ValueError('first and count must be >= 0, got %d, %d' % (first, count))
+        N = self.n_vertices
+        W = (N + 31) // 32
+        with torch.cuda.device(self.device):
+            b1 = torch.empty(count, N, W, dtype=torch.int32, device=self.device)
+            b2 = torch.empty(count, N, W, dtype=torch.int32, device=self.device)
+            nv = None if self.constant_n_vertices else torch.empty(count, dtype=torch.int32, device=self.device)
+            if count:
+                a = _lib.PairgenArgs()
+                a.seed, a.first, a.B, a.N = self.seed, first, count, N
+                a.family, a.noise_model = FAMILIES[self.generative_model], NOISE_MODELS[self.noise_model]
+                a.edge_density = self.edge_density
+                a.thr_edge, a.thr_noise1, a.thr_noise2, a.thr_vertex = self._thr
+                a.swaps_per_edge = self.swaps_per_edge
+                a.bits1, a.bits2 = b1.data_ptr(), b2.data_ptr()
+                a.nvalid = nv.data_ptr() if nv is not None else None
+                _lib.call('fgnn_pairgen', C.byref(a), _lib.stream_ptr())
+        return b1, b2, nv
+
+    def dense(self, first, count):
+        """The reference's collate structures for the same pairs: ({'input': x1}, {'input': x2}) with (count, 2, N, N) fp32
+        tensor representations (collate_fn_pair_explore) for a constant vertex count, else two MaskedTensors padded to the
+        largest n_i of the batch (collate_fn_pair; one host sync for that size)."""
+        b1, b2, nv = self.bits(first, count)
+        N = self.n_vertices
+        x1, x2 = expand_adjacency(b1, N, nv), expand_adjacency(b2, N, nv)
+        if nv is None:
+            return {'input': x1}, {'input': x2}
+        n = int(nv.max().item()) if count else 0
+        x1, x2 = x1[:, :, :n, :n].contiguous(), x2[:, :, :n, :n].contiguous()
+        return MaskedTensor(x1, nv, (2, 3), 'N'), MaskedTensor(x2, nv, (2, 3), 'M')

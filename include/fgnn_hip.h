@@ -734,6 +734,35 @@ int fgnn_mlp_bwd16(const fgnn_mlp_bwd16_args *args, void *stream);
  * R(R(old + dx1) + dx2), bit-identical to the two read-modify-write launches.  One slab of 2 or 32 channels, constant-size batches. */
 int fgnn_mlp_bwd16_pair(const fgnn_mlp_bwd16_args *m1, const fgnn_mlp_bwd16_args *m2, void *stream);
 
+/* ---- QAP pair generation (loaders/data_generator.py:38-125,175-219: QAP_Generator) ------------------------------------------
+ * B pairs (graph, noisy graph) written straight into the engine's wire format: bits1 / bits2 (B, N, ceil(N/32)) words, bit j of
+ * word row i = W[i][j] (the layout of fgnn_expand_adjacency), rows / columns >= n_k and padding bits zero; nvalid (optional,
+ * int32[B]) = n_k.  Pair k (= first + b) of dataset `seed` depends on (seed, k) only: every draw is addressed by (pair, stream,
+ * position) on Philox4x64-10, never by thread or launch.  Probabilities arrive as integer thresholds thr = min(2^32,
+ * floor(prob * 2^32)); an event is u32 < thr.  graph_neural_net_amd/pairgen.py documents the streams and algorithms. */
+#define FGNN_PAIRGEN_ERDOS_RENYI 0      /* family / noise model */
+#define FGNN_PAIRGEN_REGULAR 1          /* family */
+#define FGNN_PAIRGEN_BARABASI_ALBERT 2  /* family */
+#define FGNN_PAIRGEN_EDGE_SWAP 1        /* noise model */
+#define FGNN_PAIRGEN_MAX_N 256
+typedef struct {
+    unsigned long long seed;            /* Philox key */
+    long long first;                    /* index of the first pair of the launch */
+    int B, N;                           /* pairs, padded size (1 <= N <= FGNN_PAIRGEN_MAX_N) */
+    int family, noise_model;
+    double edge_density;                /* p: Regular degree int(p n) (+1 if n d is odd), BA attachments int(p (n-1) / 2) */
+    unsigned long long thr_edge;        /* ErdosRenyi parent: p */
+    unsigned long long thr_noise1;      /* ErdosRenyi noise: edge removal (noise); EdgeSwap: both loops (noise) */
+    unsigned long long thr_noise2;      /* ErdosRenyi noise: edge insertion (p noise / (1 - p)) */
+    unsigned long long thr_vertex;      /* vertex_proba; 2^32 = constant N, else n ~ Binomial(N, vertex_proba) */
+    int swaps_per_edge;                 /* Regular: double-edge swaps per edge of the circulant seed */
+    unsigned *bits1, *bits2;            /* out (B, N, ceil(N/32)) */
+    int *nvalid;                        /* optional out (B) */
+} fgnn_pairgen_args;
+/* 1 if (N, family, noise_model) is a shape fgnn_pairgen runs */
+int fgnn_pairgen_supported(int N, int family, int noise_model);
+int fgnn_pairgen(const fgnn_pairgen_args *args, void *stream);
+
 /* ---- test-only entry points (never on the product path; tests/ and tools/ call them) ---------------------------------------
  * fgnn_debug_mlp_fwd_masks / fgnn_debug_mlp_fwd_x3_masks: fgnn_mlp_fwd / fgnn_mlp_fwd_x3 once more -- the same tile code, the same
  * outputs, bit for bit -- that ALSO exports the ReLU decisions of the conv chain (models/layers.py:129-130), the input of the
