@@ -87,10 +87,6 @@ DEVI void sb_table_row(const TabArgs &A, const int N, float *tab, const int bf, 
         out[3 * FGNN_H + o] = sb_r(a, bf);
     }
 }
-__global__ __launch_bounds__(256) void sb_tables_kernel(const TabArgs A, const int N, float *tab, const int bf) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), NC = sb_classes(N);
-    if (row < 2 * NC) sb_table_row(A, N, tab, bf, row % NC, row / NC, threadIdx.x & 63);
-}
 
 // row t of graph g restricted to the valid corner (bits >= nv cleared, rows >= nv empty) as 2 NWD dwords in LDS
 template <int NWD>
@@ -146,8 +142,8 @@ static WsLayout sb_ws_layout(int G, int N) {
 }
 
 // ---- KG: code plane + vertex records (+ the input slabs the other kernels of block 1 read) -------------------------------------
-// grid ntab + G ny: the first ntab workgroups build the class tables of the step (four rows each: the graph-independent launch of
-// fgnn_block1_struct_tables folded in); workgroup ntab + g ny + y loads the bit rows of graph g and owns the band of SB_CW columns
+// grid ntab + G ny: the first ntab workgroups build the class tables of the step (four rows each: graph independent, but a launch
+// of their own would cost more than they do); workgroup ntab + g ny + y loads the bit rows of graph g and owns the band of SB_CW columns
 // y SB_CW ..: it transposes ONLY those columns (a workgroup that transposed the whole matrix spent 4.6 of its 9.5 us there at
 // N = 200), writes the vertex records of the vertices in the band and, thread <-> row, the band's codes of every row.
 constexpr int SB_CW = 16;                // columns per workgroup of the per-graph kernel
@@ -912,22 +908,6 @@ extern "C" int fgnn_block1_struct_rows(int G, int N) {          // rows of wpart
     return G * (wpg < 1 ? 1 : wpg);
 }
 
-extern "C" int fgnn_block1_struct_tables(const float *const *W1, const float *const *b1, const float *const *W2, const float *const *b2, int N,
-                                         int bf16_scheme, float *tables, void *stream) {
-    FGNN_CHECK(W1 && b1 && W2 && b2 && tables && N >= 1 && N <= SB_NMAX, "fgnn_block1_struct_tables: bad arguments (N=%d)", N);
-    TabArgs A;
-    for (int l = 0; l < 3; ++l) {
-        A.W[0][l] = W1[l];
-        A.b[0][l] = b1[l];
-        A.W[1][l] = W2[l];
-        A.b[1][l] = b2[l];
-        FGNN_CHECK(W1[l] && b1[l] && W2[l] && b2[l], "fgnn_block1_struct_tables: layer %d missing", l);
-    }
-    hipLaunchKernelGGL(sb_tables_kernel, dim3((2 * (2 + 2 * (N + 1)) + 3) / 4), dim3(256), 0, (hipStream_t)stream, A, N, tables, bf16_scheme ? 1 : 0);
-    FGNN_LAUNCH_CHECK();
-    return 0;
-}
-
 namespace {
 struct FwdCall {
     const unsigned *bits;
@@ -942,7 +922,7 @@ struct FwdCall {
     float *xdeg;
     void *x16;
     float *ws;
-    const float *const *tW1, *const *tb1, *const *tW2, *const *tb2;      // optional: build the tables in the same launch
+    const float *const *tW1, *const *tb1, *const *tW2, *const *tb2;      // weights the first launch builds the tables from
     hipStream_t st;
     const fgnn_pack_job *jobs;      // optional: the step's operand packing (fgnn_pack_operands) in the same launch
     int njobs;
@@ -955,17 +935,14 @@ int sb_fwd_launch(const FwdCall &c) {
     unsigned short *code = reinterpret_cast<unsigned short *>(c.ws + L.code);
     float4 *vinfo = reinterpret_cast<float4 *>(c.ws + L.vinfo);
     TabArgs TA = {};
-    int ntab = 0;
-    if (c.tW1) {
-        for (int l = 0; l < 3; ++l) {
-            FGNN_CHECK(c.tW1[l] && c.tb1[l] && c.tW2[l] && c.tb2[l], "fgnn_block1_struct_fwd: table weights of layer %d missing", l);
-            TA.W[0][l] = c.tW1[l];
-            TA.b[0][l] = c.tb1[l];
-            TA.W[1][l] = c.tW2[l];
-            TA.b[1][l] = c.tb2[l];
-        }
-        ntab = (2 * (2 + 2 * (c.N + 1)) + 3) / 4;
+    for (int l = 0; l < 3; ++l) {
+        FGNN_CHECK(c.tW1[l] && c.tb1[l] && c.tW2[l] && c.tb2[l], "fgnn_block1_struct_fwd: table weights of layer %d missing", l);
+        TA.W[0][l] = c.tW1[l];
+        TA.b[0][l] = c.tb1[l];
+        TA.W[1][l] = c.tW2[l];
+        TA.b[1][l] = c.tb2[l];
     }
+    const int ntab = (2 * (2 + 2 * (c.N + 1)) + 3) / 4;
     PackJobs PJ = {};
     FGNN_CHECK(c.njobs >= 0 && c.njobs <= FGNN_MAX_PACK_JOBS && (c.njobs == 0 || c.jobs), "fgnn_block1_struct_fwd_pack: 0 .. %d pack jobs", FGNN_MAX_PACK_JOBS);
     for (int i = 0; i < c.njobs; ++i) {
@@ -991,8 +968,7 @@ template <bool BF>
 int sb_fwd_dispatch(const FwdCall &c) {
     FGNN_CHECK(c.bits && c.tables && c.gnw1 && c.gnb1 && c.gnw2 && c.gnb2 && c.nrm1 && c.nrm2 && c.mult && c.ws && c.G > 0,
                "fgnn_block1_struct_fwd: bad arguments");
-    FGNN_CHECK((c.tW1 != nullptr) == (c.tb1 != nullptr) && (c.tW1 != nullptr) == (c.tW2 != nullptr) && (c.tW1 != nullptr) == (c.tb2 != nullptr),
-               "fgnn_block1_struct_fwd: the four table weight arrays come together");
+    FGNN_CHECK(c.tW1 && c.tb1 && c.tW2 && c.tb2, "fgnn_block1_struct_fwd: the four table weight arrays are required");
     FGNN_CHECK(c.N >= 1 && c.N <= SB_NMAX, "fgnn_block1_struct_fwd: N = %d (built for N <= %d)", c.N, SB_NMAX);
     FGNN_CHECK((reinterpret_cast<uintptr_t>(c.ws) & 15) == 0, "fgnn_block1_struct_fwd: workspace not 16-byte aligned");
     if (c.N <= 64) return sb_fwd_launch<1, BF>(c);

@@ -201,17 +201,6 @@ DEVI int next_live_tile(int t, int t_end, int step, int tpg, int N, const int *n
     return next_live_tile_p(t, t_end, step, tpg, FGNN_TILE, N, nvalid);
 }
 
-// Static priority for the younger half of a workgroup's waves (the loser of every arbitration for a SIMD's issue slots, MI355X_MICROARCH.md
-// "two waves per SIMD"): measurement switch FGNN_YP (bit mask per kernel family, see the call sites); 0 = off
-#ifndef FGNN_YP
-#define FGNN_YP 0
-#endif
-DEVI void young_prio(int bit, int wv, int nw) {
-    if ((FGNN_YP >> bit) & 1) {
-        if (wv >= nw / 2) __builtin_amdgcn_s_setprio(1);
-    }
-}
-
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel: what has been raised is remembered per
 // (launcher, device), so a process that drives a second GPU raises it there as well.
 struct LdsAttrCache {
@@ -246,3 +235,6 @@ void fgnn_set_error(const char *fmt, ...);
             return 2;                                                              \
         }                                                                          \
     } while (0)
+
+// the one input slab of a fused mlp1 + mlp2 backward (mlp_bwd_pair.hip, mlp_bwd_pair_x3.hip): depth 3, 2 or 32 channels
+inline bool mlp_bwd_pair_supported(int ca, int depth) { return depth == 3 && (ca == 2 || ca == 32); }

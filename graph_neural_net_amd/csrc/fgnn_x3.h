@@ -26,6 +26,13 @@
 #define X3_BWD_TERMS 6
 #endif
 
+// shapes the x3 MLP kernels are built for (mlp_fwd_x3.hip, mlp_bwd_x3.hip; nmlp: 1 or 2 forward, 1 backward)
+inline bool mlp_x3_supported(int ca, int cb, int depth, int nmlp) {
+    if (depth != 3) return false;
+    if (nmlp == 2) return cb == 0 && (ca == 2 || ca == 32);
+    return ((ca == 2 || ca == 32) && cb == 0) || (ca == 32 && (cb == 2 || cb == 32));
+}
+
 // ---- operand images: three bf16 part-images [part][step][lane][4 dwords] + the fp32 bias tail [layer][h][16] ------------
 // The step sequence of an image is the bf16 kernels' (pk16_layout / pk16_value in fgnn_bf16.h).
 struct PkX3 {

@@ -18,20 +18,6 @@
 #include "fgnn_bf16.h"
 #include "fgnn_norm.h"
 
-#ifndef MM_ABLATE
-#define MM_ABLATE 0          // debug builds (tools/gpu_mm16_ablate.py): 1 no stores, 2 no MFMA, 3 no LDS staging, 4 no global loads,
-#endif                       // 5 phase time stamps of the forward kernel (fgnn_debug_mm16_stamps)
-
-#if MM_ABLATE == 5
-__device__ unsigned long long mm_stamps[1024][16];
-#define MM_STAMP(k)                                                                    \
-    do {                                                                               \
-        if (threadIdx.x == 0 && blockIdx.x < 1024) mm_stamps[blockIdx.x][k] = __builtin_readcyclecounter(); \
-    } while (0)
-#else
-#define MM_STAMP(k) do {} while (0)
-#endif
-
 namespace {
 
 constexpr int MM_NW = 8, MM_THREADS = 64 * MM_NW, MM_KC = 64;
@@ -151,10 +137,6 @@ struct StageXK {
         const int base = kk < nv ? (x * ldr + kk) * 2 : OOB_OFF;
 #pragma unroll
         for (int i = 0; i < SW; ++i) {
-            if (MM_ABLATE == 4) {
-                r[i] = u32x4{(unsigned)tid, (unsigned)k0, 1u, 2u};
-                continue;
-            }
             r[i] = __builtin_amdgcn_raw_buffer_load_b128(s.v.r, (x + 64 * i) < nv ? base : OOB_OFF, s.off2 + 64 * i * ldr * 2, 0);
         }
     }
@@ -163,10 +145,6 @@ struct StageXK {
         char *dst = P + x * XK_LD + pc * 16;
 #pragma unroll
         for (int i = 0; i < SW; ++i) {
-            if (MM_ABLATE == 3) {
-                asm volatile("" ::"v"(r[i][0]), "v"(r[i][1]), "v"(r[i][2]), "v"(r[i][3]));
-                continue;
-            }
             const u32x4 o = s.norm ? norm8(r[i], s, nv, x + 64 * i, k0 + 8 * pc) : r[i];
             uint2 *d = reinterpret_cast<uint2 *>(dst + 64 * i * XK_LD);       // rows are 8-byte (not 16-byte) aligned
             d[0] = make_uint2(o[0], o[1]);
@@ -175,7 +153,6 @@ struct StageXK {
     }
     static DEVI u32x4 load_piece(int i, const Src16 &s, int ldr, int nv, int k0, int tid) {
         const int pc = tid & 7, x = tid >> 3, kk = k0 + 8 * pc;
-        if (MM_ABLATE == 4) return u32x4{(unsigned)tid, (unsigned)k0, 1u, 2u};
         return __builtin_amdgcn_raw_buffer_load_b128(s.v.r, (kk < nv && (x + 64 * i) < nv) ? (x * ldr + kk) * 2 : OOB_OFF,
                                                      s.off2 + 64 * i * ldr * 2, 0);
     }
@@ -201,10 +178,6 @@ struct StageKX {
         const int base = 8 * pc < nv ? 16 * pc + kr * ldr * 2 : OOB_OFF;
 #pragma unroll
         for (int i = 0; i < SW; ++i) {
-            if (MM_ABLATE == 4) {
-                r[i] = u32x4{(unsigned)tid, (unsigned)k0, 1u, 2u};
-                continue;
-            }
             const int kb = k0 + RPS * i;
             r[i] = __builtin_amdgcn_raw_buffer_load_b128(s.v.r, kb + kr < nv ? base : OOB_OFF, s.off2 + kb * ldr * 2, 0);
         }
@@ -214,17 +187,12 @@ struct StageKX {
         char *dst = P + kr * MMCfg<NT>::KX_LD + pc * 16;
 #pragma unroll
         for (int i = 0; i < SW; ++i) {
-            if (MM_ABLATE == 3) {
-                asm volatile("" ::"v"(r[i][0]), "v"(r[i][1]), "v"(r[i][2]), "v"(r[i][3]));
-                continue;
-            }
             const u32x4 o = s.norm ? norm8(r[i], s, nv, k0 + kr + RPS * i, 8 * pc) : r[i];
             *reinterpret_cast<u32x4 *>(dst + RPS * i * MMCfg<NT>::KX_LD) = o;
         }
     }
     static DEVI u32x4 load_piece(int i, const Src16 &s, int ldr, int nv, int k0, int tid) {
         const int pc = tid % PPR, kr = tid / PPR, kb = k0 + RPS * i;
-        if (MM_ABLATE == 4) return u32x4{(unsigned)tid, (unsigned)k0, 1u, 2u};
         return __builtin_amdgcn_raw_buffer_load_b128(s.v.r, (8 * pc < nv && kb + kr < nv) ? 16 * pc + kr * ldr * 2 : OOB_OFF,
                                                      s.off2 + kb * ldr * 2, 0);
     }
@@ -314,8 +282,8 @@ DEVI void strip_chunk(AccArray<NT, NCOL> &acc, const char *pa, const char *pb, c
         for (int tn = 0; tn < NCOL; ++tn) {
             const int it = s * NCOL + tn;
             if (it + 1 < TOT) bq[(it + 1) & 1] = read_operand<NT, B_XK>(pb, oa, (it + 1) % NCOL, (it + 1) / NCOL);
-            if (MM_ABLATE != 2) acc[tn] = mfma16(bq[it & 1], a, acc[tn]);
-            if (MM_ABLATE != 3 && !LAST) {
+            acc[tn] = mfma16(bq[it & 1], a, acc[tn]);
+            if (!LAST) {
                 if (tn < 4) {
                     if (!A_PLAIN) {
                         if (tn == 0) cx = sa.template ctx<WHOLE>(A, nv, k0n, s, tid);
@@ -332,7 +300,7 @@ DEVI void strip_chunk(AccArray<NT, NCOL> &acc, const char *pa, const char *pb, c
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (MM_ABLATE != 3 && !LAST) {
+        if (!LAST) {
             if (!B_PLAIN) {
 #pragma unroll
                 for (int q = NCOL - 4; q < 4; ++q) sb.r[s][q] = norm_dword<WHOLE>(sb.r[s][q], cx, q);
@@ -358,7 +326,6 @@ DEVI void mm_gemm_strip(AccArray<NT, NCOL> &acc, const Src16 &A, const Src16 &B,
     const int nkc = (nv + MM_KC - 1) / MM_KC;
     Stage<NT, A_XK> sa;
     Stage<NT, B_XK> sb;
-    MM_STAMP(0);
     if constexpr (PRELOADED) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -369,7 +336,6 @@ DEVI void mm_gemm_strip(AccArray<NT, NCOL> &acc, const Src16 &A, const Src16 &B,
         sa.load(A, ldr, nv, 0, tid);
         sb.load(B, ldr, nv, 0, tid);
     }
-    MM_STAMP(1);
 #pragma unroll
     for (int i = 0; i < MM_KC / 16; ++i) {                 // chunk 0: nothing to hide it under
         if (!A_PLAIN) {
@@ -388,24 +354,19 @@ DEVI void mm_gemm_strip(AccArray<NT, NCOL> &acc, const Src16 &A, const Src16 &B,
         sb.load_one(i, B, ldr, nv, MM_KC, tid);
     }
     __syncthreads();
-    MM_STAMP(2);
     for (int c = 0; c + 1 < nkc; ++c) {
         const char *pa = lds + (c & 1) * Cf::BUF_B, *pb = pa + Cf::PANEL_B;
         char *nx = lds + ((c & 1) ^ 1) * Cf::BUF_B;
         strip_chunk<NT, NCOL, A_XK, B_XK, A_PLAIN, B_PLAIN, WHOLE, false>(acc, pa, pb, oa, strip, sa, sb, nx, nx + Cf::PANEL_B, A, B,
                                                                         ldr, nv, (c + 1) * MM_KC, tid, next);
-        if (c < 4) MM_STAMP(3 + 2 * c);
         __syncthreads();
-        if (c < 4) MM_STAMP(4 + 2 * c);
     }
     if (nkc > 0) {
         const int c = nkc - 1;
         const char *pa = lds + (c & 1) * Cf::BUF_B, *pb = pa + Cf::PANEL_B;
         strip_chunk<NT, NCOL, A_XK, B_XK, A_PLAIN, B_PLAIN, WHOLE, true>(acc, pa, pb, oa, strip, sa, sb, nullptr, nullptr, A, B, ldr, nv,
                                                                        0, tid, next);
-        if (c < 4) MM_STAMP(3 + 2 * c);
         __syncthreads();
-        if (c < 4) MM_STAMP(4 + 2 * c);
     } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i) next(i, sa.r[i], sb.r[i]);
@@ -439,14 +400,11 @@ DEVI void mm_gemm(AccArray<NT, NCOL> &acc, const Src16 &A, const Src16 &B, char 
     const int nkc = (nv + MM_KC - 1) / MM_KC;
     Stage<NT, A_XK> sa;
     Stage<NT, B_XK> sb;
-    MM_STAMP(0);
     sa.load(A, ldr, nv, 0, tid);
     sb.load(B, ldr, nv, 0, tid);
-    MM_STAMP(1);
     sa.stage(lds, A, nv, 0, tid);
     sb.stage(lds + Cf::PANEL_B, B, nv, 0, tid);
     __syncthreads();
-    MM_STAMP(2);
     for (int c = 0; c < nkc; ++c) {
         const int cur = c & 1;
         const bool more = c + 1 < nkc;
@@ -455,28 +413,22 @@ DEVI void mm_gemm(AccArray<NT, NCOL> &acc, const Src16 &A, const Src16 &B, char 
             sb.load(B, ldr, nv, (c + 1) * MM_KC, tid);
         }
         const char *pa = lds + cur * Cf::BUF_B, *pb = pa + Cf::PANEL_B;
-        if (MM_ABLATE != 2) {
-            {
 #pragma unroll
-                for (int ti = 0; ti < Cf::MAXT; ++ti) {
-                    const int t = wv + MM_NW * ti;
-                    if (t < T) {
-                        const int tm = t / ntv, tn = t - tm * ntv;
+        for (int ti = 0; ti < Cf::MAXT; ++ti) {
+            const int t = wv + MM_NW * ti;
+            if (t < T) {
+                const int tm = t / ntv, tn = t - tm * ntv;
 #pragma unroll
-                        for (int s = 0; s < MM_KC / 16; ++s)
-                            acc[ti] = mfma16(read_operand<NT, B_XK>(pb, oa, tn, s), read_operand<NT, A_XK>(pa, oa, tm, s), acc[ti]);
-                    }
-                }
+                for (int s = 0; s < MM_KC / 16; ++s)
+                    acc[ti] = mfma16(read_operand<NT, B_XK>(pb, oa, tn, s), read_operand<NT, A_XK>(pa, oa, tm, s), acc[ti]);
             }
         }
-        if (c < 4) MM_STAMP(3 + 2 * c);
         if (more) {
             char *nx = lds + (cur ^ 1) * Cf::BUF_B;
             sa.stage(nx, A, nv, (c + 1) * MM_KC, tid);
             sb.stage(nx + Cf::PANEL_B, B, nv, (c + 1) * MM_KC, tid);
         }
         __syncthreads();
-        if (c < 4) MM_STAMP(4 + 2 * c);
     }
 }
 
@@ -510,7 +462,6 @@ DEVI void mm_store(const AccArray<NT, NCOL> &acc, char *lds, const View16 &ov, i
         }
     }
     __syncthreads();
-    MM_STAMP(11);
     // The next product's first chunk was requested during the last MFMA chunk.  Let it land BEFORE the stores below are
     // issued: vector memory operations of a wave retire in order, so waiting for those loads later (a runtime number of
     // stores in between) would mean waiting for every store to reach memory.
@@ -529,10 +480,9 @@ DEVI void mm_store(const AccArray<NT, NCOL> &acc, char *lds, const View16 &ov, i
             if (col_in && r < X) v = *reinterpret_cast<const u32x4 *>(lds + r * OP + cbase);
             u32x4 u;
             if (STATS == 1) u = __builtin_amdgcn_raw_buffer_load_b128(raw.v.r, r < nv ? rawc : OOB_OFF, raw.off2 + rb * ldr * 2, 0);
-            if (MM_ABLATE == 1) asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
             // soffset stays a literal 0: with an SGPR there the compiler assumes a VALU write to the data registers may follow
             // the 128-bit store immediately -- on gfx950 that corrupted dword 2 of some lanes (measured, tests/diag/gpu_mm16_check.py)
-            else __builtin_amdgcn_raw_buffer_store_b128(v, ov.r, r < N ? voff + o_off2 + rb * ldr * 2 : OOB_OFF, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(v, ov.r, r < N ? voff + o_off2 + rb * ldr * 2 : OOB_OFF, 0, 0);
             if (STATS == 2) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) s1 += bf_lo(v[q]) + bf_hi(v[q]);
@@ -555,9 +505,7 @@ DEVI void mm_store(const AccArray<NT, NCOL> &acc, char *lds, const View16 &ov, i
             }
         }
     }
-    MM_STAMP(12);
     __syncthreads();                      // the image is the next product's staging buffer
-    MM_STAMP(13);
 }
 
 // GraphNorm finalize of the two operands folded into the forward product's prologue (the work of fgnn_gn_finalize2_tpg
@@ -599,7 +547,6 @@ __global__ __launch_bounds__(MM_THREADS) void chan_matmul_fwd16_kernel(const fgn
     __shared__ float fin_red[MM_NW][4];
     constexpr bool STRIP = MMCfg<NT, NCOL>::STRIP;
     const int C = ya.C, gc = blockIdx.x, g = gc / C, c = gc - g * C, tid = threadIdx.x;
-    young_prio(5, tid >> 6, MM_NW);
     const int nv = nvalid_of(nvalid, g, N), ntv = (nv + 31) / 32;
     Src16 A, B;
     u32x4 pre_a[4], pre_b[4];
@@ -687,7 +634,6 @@ __global__ __launch_bounds__(MM_THREADS) void chan_matmul_bwd16_kernel(const fgn
     const int C = ya.C, gc = blockIdx.x, g = gc / C, c = gc - g * C, tid = threadIdx.x;
     const int lane = tid & 63, wv = tid >> 6;
     const int nv = nvalid_of(nvalid, g, N), ntv = (nv + 31) / 32;
-    young_prio(4, wv, MM_NW);
     const Src16 A = mm_src(ya, G, g, c), B = mm_src(yb, G, g, c);
     const Src16 D = mm_src_plain(dm, dmg, ldm, G, g, c);
     const View16 vOA = make_view16(da, ogstride, ldo, G), vOB = make_view16(db, ogstride, ldo, G);
@@ -818,11 +764,6 @@ int launch_bwd16(const fgnn_slab16 *ya, const fgnn_slab16 *yb, const void *dm, l
 
 }  // namespace
 
-#if MM_ABLATE == 5
-extern "C" int fgnn_debug_mm16_stamps(unsigned long long *host_dst) {
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(mm_stamps), sizeof(mm_stamps));
-}
-#endif
 
 static int matmul_fwd16_common(const fgnn_slab16 *ya, const fgnn_slab16 *yb, const int *nvalid, int G, int N, int ldr, void *out,
                                long long ogstride, long long ldo, const FinArgs16 *F, void *stream) {

@@ -454,10 +454,7 @@ __global__ __launch_bounds__(64 * NWB) void mlp64_bwd_kernel(const fgnn_mlp64_ar
     load_in<KG, KGA>(x, vx, c, q);
     load_in<OG>(dz, vdz, c, q);
 
-#ifndef M64_ABL
-#define M64_ABL 0           // measurement switch (tools/build_variant.sh): 1 no operand copy, 2 no parameter-gradient epilogue
-#endif
-    if (!(M64_ABL & 1)) {
+    {
         constexpr Packed64 PL{KG};
         copy4(smem + L::F0, A.packed + PL.f0(), ((HAS_DX ? PL.f2() : PL.b0()) - PL.f0()) / 4, threadIdx.x, 64 * NWB);   // F0, F1, B2, B1 (, B0)
         copy4(smem + L::BIAS, A.packed + PL.bias(), 2 * 64 / 4, threadIdx.x, 64 * NWB);
@@ -622,7 +619,6 @@ __global__ __launch_bounds__(64 * NWB) void mlp64_bwd_kernel(const fgnn_mlp64_ar
             o4[e] = v;
         }
     };
-    if (M64_ABL & 2) return;
     reduce_layer(dW0, db0, std::integral_constant<int, KG>{}, 0);
     reduce_layer(dW1, db1, std::integral_constant<int, OG>{}, 64 * K0P + 64);
     reduce_layer(dW2, db2, std::integral_constant<int, OG>{}, 64 * K0P + 64 + 64 * 64 + 64);

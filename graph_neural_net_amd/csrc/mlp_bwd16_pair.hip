@@ -236,14 +236,8 @@ __global__ __launch_bounds__(64 * NWB, NWB / 4) void mlp_bwd16_pair_kernel(const
     const int ld2 = va.ld2;
     auto roff = [&](int r) { return ((r & 3) + 8 * (r >> 2)) * ld2; };
 
-#ifndef FGNN_XEARLY
-#define FGNN_XEARLY 0     // measurement switch: x of the next tile requested in the middle of the tile (10 spilled registers: 75 -> 87 us)
-#endif
-#ifndef FGNN_PRIO16
-#define FGNN_PRIO16 1
-#endif
     // static priority for the mlp2 waves (the younger half of the workgroup AND the longer half of the pair): see mlp_bwd_pair_t16.hip
-    if (FGNN_PRIO16 > 0 && role == 1) __builtin_amdgcn_s_setprio(FGNN_PRIO16);
+    if (role == 1) __builtin_amdgcn_s_setprio(1);
     int tnext = 0;
     for (int tile = first; tile < T1; tile = tnext) {
         tnext = tile + NP;
@@ -337,10 +331,6 @@ __global__ __launch_bounds__(64 * NWB, NWB / 4) void mlp_bwd16_pair_kernel(const
                 yTb = transposed_input(yb, ident, false, 1.f, 0.f);
             }
 
-#if FGNN_XEARLY
-            // the next tile's x into the registers both groups have consumed by now: a tile's time instead of its last instants to arrive
-            if constexpr (GRP == 1 && CB == 0) load_slab16<CA>(xa, va, cn, h);
-#endif
             // ---- forward recompute: h_0 .. h_{d-2} ----
             F16 hs[DEPTH - 1];
             {
@@ -512,9 +502,7 @@ __global__ __launch_bounds__(64 * NWB, NWB / 4) void mlp_bwd16_pair_kernel(const
             es2 += __shfl_xor(es2, 32);
             if (h == 0) reinterpret_cast<float2 *>(P.m[1].s12part)[((long long)c.g * FGNN_H + j) * tpg + c.tt] = make_float2(es1, es2);
         }
-#if !FGNN_XEARLY
         load_slab16<CA>(xa, va, cn, h);     // the wave's next tile
-#endif
     }
 
     if constexpr (SKIP) {       // padding-only tiles of this wave's share: empty S1/S2 / trace-term records

@@ -224,11 +224,8 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_pair_kernel(const PairArgs
     if (threadIdx.x < 4 * NP) reinterpret_cast<int *>(smem + L::FLAG_OFF)[threadIdx.x] = -1;
     __syncthreads();
 
-#ifndef FGNN_PRIO32
-#define FGNN_PRIO32 1
-#endif
     // static priority for the mlp2 waves (the younger half of the workgroup AND the longer half of the pair): see mlp_bwd_pair_t16.hip
-    if (FGNN_PRIO32 > 0 && role == 1) __builtin_amdgcn_s_setprio(FGNN_PRIO32);
+    if (role == 1) __builtin_amdgcn_s_setprio(1);
     int tnext = 0, prev_tile = -1;
     for (int tile = first; tile < T1; tile = tnext) {
         tnext = tile + NP;
@@ -506,14 +503,12 @@ int launch_pair(const fgnn_mlp_bwd_args *a1, const fgnn_mlp_bwd_args *a2, int tp
 
 }  // namespace
 
-extern "C" int fgnn_mlp_bwd_pair_supported(int ca, int depth) { return (depth == 3 && (ca == 2 || ca == 32)) ? 1 : 0; }
-
 extern "C" int fgnn_mlp_bwd_pair(const fgnn_mlp_bwd_args *a1, const fgnn_mlp_bwd_args *a2, void *stream) {
     FGNN_CHECK(a1 && a2, "fgnn_mlp_bwd_pair: null args");
     FGNN_CHECK(BWD_WG == fgnn_mlp_bwd_num_workgroups(), "fgnn_mlp_bwd_pair: workgroup count differs from fgnn_mlp_bwd");
     FGNN_CHECK(a1->G > 0 && a1->N > 0 && a1->G == a2->G && a1->N == a2->N && a1->depth == a2->depth,
                "fgnn_mlp_bwd_pair: the two MLPs must share G, N and depth");
-    FGNN_CHECK(fgnn_mlp_bwd_pair_supported(a1->a.C, a1->depth) && a1->b.C == 0 && a2->b.C == 0,
+    FGNN_CHECK(mlp_bwd_pair_supported(a1->a.C, a1->depth) && a1->b.C == 0 && a2->b.C == 0,
                "fgnn_mlp_bwd_pair: built for depth 3 and ONE input slab of 2 or 32 channels (got depth %d, %d + %d); use fgnn_mlp_bwd",
                a1->depth, a1->a.C, a1->b.C);
     FGNN_CHECK(a1->a.ptr == a2->a.ptr && a1->a.C == a2->a.C && a1->a.gstride == a2->a.gstride && a1->a.ldp == a2->a.ldp &&

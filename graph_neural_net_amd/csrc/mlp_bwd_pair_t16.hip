@@ -32,10 +32,6 @@ __device__ unsigned long long *g_phase16_buf = nullptr;
 #define PH_FLUSH
 #endif
 
-#ifndef FGNN_PRIO
-#define FGNN_PRIO 1         // static priority of the mlp2 waves (0: none)
-#endif
-
 namespace {
 
 using namespace t16;
@@ -97,11 +93,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_pair_t16_kernel(const Pair
     extern __shared__ __attribute__((aligned(16))) float smem[];
     using L = PairLayout16;
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#ifdef FGNN_SWAP_ROLES      // measurement switch: the older waves (0..3) run mlp2
-    const int role = 1 - (wv >> 2), pair = wv & 3;
-#else
-    const int role = wv >> 2, pair = wv & 3;
-#endif            // role 0: mlp1 (starts the dx chain), role 1: mlp2 (finishes it, stores, emits)
+    const int role = wv >> 2, pair = wv & 3;        // role 0: mlp1 (starts the dx chain), role 1: mlp2 (finishes it, stores, emits)
     const int px = lane & 15, q = lane >> 4;
     const fgnn_mlp_bwd_args &A = P.m[role];
     const int P2 = A.N * A.N;
@@ -111,7 +103,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_pair_t16_kernel(const Pair
     const View vdx = make_view(P.m[1].dxa, P.m[1].dxa_gstride, P.m[1].dxa_ld, P.m[1].G);
 
     PH_DECL
-    if (FGNN_PRIO > 0 && role == 1) __builtin_amdgcn_s_setprio(FGNN_PRIO);
+    if (role == 1) __builtin_amdgcn_s_setprio(1);       // see the tile loop
     float *wl = smem + role * L::WEIGHT_F;              // this wave's MLP image
     float *my = smem + L::TILE_OFF + wv * (L::NSLOT * TILE_F);
     float *XA = my, *S0 = my + TILE_F, *S1 = my + 2 * TILE_F, *S2 = my + 3 * TILE_F;
@@ -225,9 +217,6 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_pair_t16_kernel(const Pair
     if (cached_g >= 0) read_records();
     PH(9)               // prologue
 
-#ifdef FGNN_STAGGER         // measurement switch: the mlp2 waves start late by FGNN_STAGGER x 64 cycles
-    if (role == 1) __builtin_amdgcn_s_sleep(FGNN_STAGGER);
-#endif
     // Static priority for the mlp2 waves: they are the younger half of the workgroup (waves 4..7) -- the loser of every arbitration for the
     // SIMD's matrix / vector issue -- AND carry the longer half (hand-over wait, dgrad at the very end, store, sums), so they set the
     // kernel's duration while the mlp1 waves idle ~ 15 % at the hand-over slots.  One s_setprio before the loop: 62.7 -> 59.3 us.
@@ -361,11 +350,8 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_pair_t16_kernel(const Pair
             if (role == 0) {
                 if (has_dx) {
                     // slot hk & 1 still holds fragment hk - 2: wait until the mlp2 wave has read it
-                    if (hk >= 2) {
-#if !(FGNN_ABL & 1)
+                    if (hk >= 2)
                         while (__hip_atomic_load(&flags[1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < hk - 1) __builtin_amdgcn_s_sleep(1);
-#endif
-                    }
                     PH(6)   // waiting for the partner wave
                     float *slot = XCH + (hk & 1) * 512;
 #pragma unroll
@@ -374,9 +360,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_pair_t16_kernel(const Pair
                 }
             } else {
                 if (has_dx) {
-#if !(FGNN_ABL & 1)
                     while (__hip_atomic_load(&flags[0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < hk + 1) __builtin_amdgcn_s_sleep(1);
-#endif
                     PH(6)   // waiting for the partner wave
                     const float *slot = XCH + (hk & 1) * 512;
 #pragma unroll
@@ -516,15 +500,13 @@ int launch_pair16(const fgnn_mlp_bwd_args *a1, const fgnn_mlp_bwd_args *a2, int 
 extern "C" int fgnn_debug_phase_buffer_t16(void *p) { return hipMemcpyToSymbol(HIP_SYMBOL(g_phase16_buf), &p, sizeof(p)) == hipSuccess ? 0 : 1; }
 #endif
 
-extern "C" int fgnn_mlp_bwd_pair_t16_supported(int ca, int depth) { return (depth == 3 && ca == 32) ? 1 : 0; }
-
 // Same contract as fgnn_mlp_bwd_pair (see there); `packed` of both argument blocks must be images of kind 5 (fgnn_pack_operands).
 extern "C" int fgnn_mlp_bwd_pair_t16(const fgnn_mlp_bwd_args *a1, const fgnn_mlp_bwd_args *a2, void *stream) {
     FGNN_CHECK(a1 && a2, "fgnn_mlp_bwd_pair_t16: null args");
     FGNN_CHECK(BWD_WG == fgnn_mlp_bwd_num_workgroups() && BWD_WG == FGNN_RANGE_WG, "fgnn_mlp_bwd_pair_t16: workgroup count differs from fgnn_mlp_bwd");
     FGNN_CHECK(a1->G > 0 && a1->N > 0 && a1->G == a2->G && a1->N == a2->N && a1->depth == a2->depth,
                "fgnn_mlp_bwd_pair_t16: the two MLPs must share G, N and depth");
-    FGNN_CHECK(fgnn_mlp_bwd_pair_t16_supported(a1->a.C, a1->depth) && a1->b.C == 0 && a2->b.C == 0 && !a1->xbits && !a2->xbits,
+    FGNN_CHECK(a1->depth == 3 && a1->a.C == 32 && a1->b.C == 0 && a2->b.C == 0 && !a1->xbits && !a2->xbits,
                "fgnn_mlp_bwd_pair_t16: built for depth 3 and ONE dense input slab of 32 channels (got depth %d, %d + %d); use fgnn_mlp_bwd_pair",
                a1->depth, a1->a.C, a1->b.C);
     FGNN_CHECK(a1->a.ptr && a1->a.ptr == a2->a.ptr && a1->a.C == a2->a.C && a1->a.gstride == a2->a.gstride && a1->a.ldp == a2->a.ldp &&

@@ -68,7 +68,6 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_t16_kernel(const fgnn_mlp_
     using L = Layout16<CB>;
     constexpr bool NB = CB == 32;
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    young_prio(3, wv, NW);
     const int px = lane & 15, q = lane >> 4;
     const int P2 = A.N * A.N, hpg = 2 * tpg;
     const View va = make_view(A.a.ptr, A.a.gstride, A.a.ldp, A.G);
@@ -289,9 +288,6 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_t16_kernel(const fgnn_mlp_
     load_dyz(h);                                     // (after the barrier, which drains every load: see mlp_bwd_pair_t16.hip)
     if (cached_g >= 0) read_records();
 
-#ifdef FGNN_PRIOB          // measurement switch: static priority for the younger waves (1) / the older waves (2)
-    if ((FGNN_PRIOB == 1) == (wv >= 4)) __builtin_amdgcn_s_setprio(1);
-#endif
     while (h < H1) {
         const int hn = next_half(SKIP ? h + 1 : h + NW);
         const int g = __builtin_amdgcn_readfirstlane(h / hpg), hh = h - g * hpg;
@@ -325,7 +321,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_t16_kernel(const fgnn_mlp_
             if constexpr (CB == 32) {
                 stage8(XB, lane_base, yb);
             } else {                                   // rows 0, 1 of the slab-b tile; rows 2..15 of its first block were zeroed once
-                if (q < 2) XB[(FGNN_ROWMAP ? 8 : 1) * q * TLD + px] = yb[0];     // channel q = chan(0, 2 q): row 4 * (2 q)
+                if (q < 2) XB[8 * q * TLD + px] = yb[0];     // channel q = chan(0, 2 q): row 4 * (2 q)
             }
             f32x4 acc[2];
             load_bias(acc, wl + L::BIAS_F, 0, q);

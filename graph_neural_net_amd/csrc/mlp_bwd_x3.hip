@@ -283,12 +283,7 @@ __global__ __launch_bounds__(64 * NWT, NWT / 4) void mlp_bwd_x3_kernel(const fgn
             cur_nv = __builtin_amdgcn_readfirstlane(nvalid_of(A.nvalid, c.g, A.N));
         }
         const bool c_valid = tile_valid(c, cur_nv);
-#ifndef X3_EARLY_RMW
-#define X3_EARLY_RMW 0
-#endif
-        constexpr bool EARLY_RMW = (CB == 0) && X3_EARLY_RMW;       // single-slab kernels prefetch the dx they accumulate into
-        float dyr[16], zr[16], old[16];
-        const bool rmw = EARLY_RMW && A.dxa != nullptr && A.accumulate_a;
+        float dyr[16], zr[16];
 
         // ---- forward recompute of the hidden activations ----
         f32x16 acc;
@@ -307,12 +302,9 @@ __global__ __launch_bounds__(64 * NWT, NWT / 4) void mlp_bwd_x3_kernel(const fgn
             split_slab<SB>(X, yb, h, negI);
             acc = gemm_x3<L::STEPS_B, X3_FWD_TERMS>(acc, wl, L::PD, L::OFF_W0B, X, lane);
         }
-        // this tile's dy / z and, when accumulating, the current dx values fly behind the recompute
+        // this tile's dy / z fly behind the recompute
         load_rows16(dyr, vdy, c, h);
         load_rows16(zr, vz, c, h);
-        if constexpr (EARLY_RMW) {
-            if (rmw) load_rows16(old, vdxa, c, h);
-        }
         float h1r[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) h1r[r] = relu1(acc[r]);
@@ -359,14 +351,6 @@ __global__ __launch_bounds__(64 * NWT, NWT / 4) void mlp_bwd_x3_kernel(const fgn
         stage16(SD1, dpre, j, h);
         if constexpr (TWO) stage16(SH1, h1r, j, h);          // h1 takes the slot h2 has just left
         // ---- layer 1 ----
-#ifndef X3_RELOAD_X
-#define X3_RELOAD_X 0
-#endif
-        // The 32-channel input slab is not held in registers across the tile: it is consumed by the first split and read
-        // again here (an L2 hit: this wave fetched it a few microseconds ago) for the layer-0 weight gradient and the
-        // S1/S2 sums -- 16 registers less during the phases where dy, z and the hidden activations are live.
-        constexpr bool RELOAD = (CA == 32) && X3_RELOAD_X;
-        if constexpr (RELOAD) load_raw<SA>(xa, va, c, h);
         {
             X3 D;
             split16m(D, dpre, negI);
@@ -454,16 +438,9 @@ __global__ __launch_bounds__(64 * NWT, NWT / 4) void mlp_bwd_x3_kernel(const fgn
                 float v[16];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) v[r] = dxa_acc[r];
-                if constexpr (EARLY_RMW) {
-                    if (rmw) {
+                if (A.accumulate_a) {
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) v[r] += old[r];
-                    }
-                } else {
-                    if (A.accumulate_a) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) v[r] += buf_load(vdxa, voff, s0 + ((r & 3) + 8 * (r >> 2)) * vdxa.ld4);
-                    }
+                    for (int r = 0; r < 16; ++r) v[r] += buf_load(vdxa, voff, s0 + ((r & 3) + 8 * (r >> 2)) * vdxa.ld4);
                 }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) buf_store(v[r], vdxa, voff, s0 + ((r & 3) + 8 * (r >> 2)) * vdxa.ld4);
@@ -594,7 +571,7 @@ int launch_bwd_x3(const fgnn_mlp_bwd_args *a, int tpg, int total, hipStream_t st
 extern "C" int fgnn_mlp_bwd_x3(const fgnn_mlp_bwd_args *a, void *stream) {
     FGNN_CHECK(a != nullptr, "fgnn_mlp_bwd_x3: null args");
     FGNN_CHECK(a->G > 0 && a->N > 0, "fgnn_mlp_bwd_x3: bad G=%d N=%d", a->G, a->N);
-    FGNN_CHECK(fgnn_mlp_x3_supported(a->a.C, a->b.C, a->depth, 1),
+    FGNN_CHECK(mlp_x3_supported(a->a.C, a->b.C, a->depth, 1),
                "fgnn_mlp_bwd_x3: built for depth 3 and 2, 32, 32+2, 32+32 input channels (got depth %d, %d + %d); use fgnn_mlp_bwd",
                a->depth, a->a.C, a->b.C);
     FGNN_CHECK(a->packed, "fgnn_mlp_bwd_x3: needs the operand image of fgnn_pack_x3_operands (kind 1)");

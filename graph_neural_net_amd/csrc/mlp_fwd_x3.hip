@@ -254,17 +254,11 @@ constexpr int FWD_X3_WAVES = 16;
 
 }  // namespace
 
-extern "C" int fgnn_mlp_x3_supported(int ca, int cb, int depth, int nmlp) {
-    if (depth != 3) return 0;
-    if (nmlp == 2) return (cb == 0 && (ca == 2 || ca == 32)) ? 1 : 0;
-    return ((ca == 2 || ca == 32) && cb == 0) || (ca == 32 && (cb == 2 || cb == 32)) ? 1 : 0;
-}
-
 static int mlp_fwd_x3_entry(const fgnn_mlp_fwd_args *a, void *stream, unsigned *const *dbg) {
     FGNN_CHECK(a != nullptr, "fgnn_mlp_fwd_x3: null args");
     FGNN_CHECK(a->G > 0 && a->N > 0, "fgnn_mlp_fwd_x3: bad G=%d N=%d", a->G, a->N);
     FGNN_CHECK(a->nmlp == 1 || a->nmlp == 2, "fgnn_mlp_fwd_x3: nmlp must be 1 or 2 (got %d)", a->nmlp);
-    FGNN_CHECK(fgnn_mlp_x3_supported(a->a.C, a->b.C, a->depth, a->nmlp),
+    FGNN_CHECK(mlp_x3_supported(a->a.C, a->b.C, a->depth, a->nmlp),
                "fgnn_mlp_fwd_x3: built for depth 3 and 2, 32, 32+2, 32+32 input channels (got depth %d, %d + %d, nmlp %d); use fgnn_mlp_fwd",
                a->depth, a->a.C, a->b.C, a->nmlp);
     FGNN_CHECK(a->packed, "fgnn_mlp_fwd_x3: needs the operand image of fgnn_pack_x3_operands");

@@ -410,8 +410,8 @@ extern "C" int fgnn_inv_node_count(const int *nvalid, int B, float *out, void *s
 }
 
 extern "C" int fgnn_pack_floats(int kind, int ca, int cb, int depth, int nmlp) {
-    if (kind >= 4)      // the *_t16 kernels' images: same layouts, each image padded to whole KiB (copied with global_load_lds, fgnn_pack.h)
-        return kind == 4 ? pk_pad_floats(pk_fwd(ca, cb, depth).floats * nmlp) : pk_pad_floats(pk_bwd(ca, cb, depth).floats);
+    if (kind == 5)      // the *_t16 kernels' backward image: same layout, padded to whole KiB (copied with global_load_lds, fgnn_pack.h)
+        return pk_pad_floats(pk_bwd(ca, cb, depth).floats);
     return kind == 0 ? pk_fwd(ca, cb, depth).floats * nmlp : pk_bwd(ca, cb, depth).floats;
 }
 
@@ -443,11 +443,6 @@ extern "C" int fgnn_gn_finalize_tpg(const float *part, const float *cnt, const f
                                     int G, int C, int N, int tpg, float eps, float *nrm, void *stream) {
     return gn_finalize_launch(part, cnt, gn_weight, nvalid, G, C, N, tpg, eps, nrm, 1, stream);
 }
-// _r: the tile statistics hold `recs` records per graph instead of fgnn_tiles_per_graph(N) (fgnn_mlp_fwd_t16: one per 16-pixel half)
-extern "C" int fgnn_gn_finalize_r(const float *part, const float *cnt, const float *gn_weight, const int *nvalid,
-                                  int G, int C, int N, int recs, float eps, float *nrm, void *stream) {
-    return gn_finalize_launch(part, cnt, gn_weight, nvalid, G, C, N, recs, eps, nrm, 0, stream);
-}
 extern "C" int fgnn_gn_finalize(const float *part, const float *cnt, const float *gn_weight, const int *nvalid,
                                 int G, int C, int N, float eps, float *nrm, void *stream) {
     return gn_finalize_launch(part, cnt, gn_weight, nvalid, G, C, N, fgnn_tiles_per_graph(N), eps, nrm, 0, stream);
@@ -468,11 +463,6 @@ extern "C" int fgnn_gn_finalize2_tpg(const float *part0, const float *part1, con
                                      const float *gn_weight1, const int *nvalid, int G, int C, int N, int tpg, float eps,
                                      float *nrm0, float *nrm1, void *stream) {
     return gn_finalize2_launch(part0, part1, cnt, gn_weight0, gn_weight1, nvalid, G, C, N, tpg, eps, nrm0, nrm1, 1, stream);
-}
-extern "C" int fgnn_gn_finalize2_r(const float *part0, const float *part1, const float *cnt, const float *gn_weight0,
-                                   const float *gn_weight1, const int *nvalid, int G, int C, int N, int recs, float eps,
-                                   float *nrm0, float *nrm1, void *stream) {
-    return gn_finalize2_launch(part0, part1, cnt, gn_weight0, gn_weight1, nvalid, G, C, N, recs, eps, nrm0, nrm1, 0, stream);
 }
 extern "C" int fgnn_gn_finalize2(const float *part0, const float *part1, const float *cnt, const float *gn_weight0,
                                  const float *gn_weight1, const int *nvalid, int G, int C, int N, float eps,
@@ -719,16 +709,6 @@ extern "C" int fgnn_grad_finalize(const fgnn_grad_job *jobs, int njobs, int num_
     }
     hipLaunchKernelGGL(grad_finalize_kernel, dim3((maxc + 63) / 64 + 1, njobs), dim3(256), 0, (hipStream_t)stream, J,
                        num_wg, G, C);
-    FGNN_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int fgnn_gn_bwd_coef2(const float *s12_0, const float *s12_1, const float *nrm0, const float *nrm1,
-                                 const int *nvalid, int G, int C, int N, float *coef0, float *coef1, void *stream) {
-    FGNN_CHECK(s12_0 && s12_1 && nrm0 && nrm1 && coef0 && coef1 && G > 0 && C > 0 && N > 0, "fgnn_gn_bwd_coef2: bad arguments");
-    const int tot = G * C;
-    CoefJobs J = {{s12_0, s12_1}, {nrm0, nrm1}, {coef0, coef1}};
-    hipLaunchKernelGGL(gn_bwd_coef_kernel, dim3((tot + 255) / 256, 2), dim3(256), 0, (hipStream_t)stream, J, nvalid, G, C, N);
     FGNN_LAUNCH_CHECK();
     return 0;
 }

@@ -471,98 +471,6 @@ __global__ __launch_bounds__(256) void score_bwd_kernel(const float *e1, const f
     }
 }
 
-// Scoring forward + triplet loss + their backward in ONE launch (a training step issues them back to back; N <= 64, 4 | C): grid
-// (B, CSPLIT_SMALL).  Every workgroup of pair b stages e1, e2, forms the full score matrix S in LDS (N^2 C fma: cheaper than a second
-// launch), the row log-sum-exps and dS = (exp(S - lse) - I) gscale, then produces de1 / de2 of ITS channels; workgroup y = 0 also
-// writes scores, lse and the pair-loss partials.  Arithmetic and summation orders are those of score_ce_fwd_kernel +
-// score_bwd_kernel<true, true>: results are bit-identical to the two launches (tests/test_gpu_kernels.py).
-constexpr int STEP_THREADS = 1024;       // 16 waves: the row pass (one wave per row, as in score_ce_fwd_kernel) is 4 rows deep at N = 50
-__global__ __launch_bounds__(STEP_THREADS) void score_ce_step_kernel(const float *e1, const float *e2, const int *nvalid,
-                                                                     const float *gscale, int C, int N, int row_blocks, float *scores,
-                                                                     float *lse, float *pair_loss, float *de1, float *de2) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float *s1 = sm, *s2 = sm + (size_t)C * N;
-    float *dS = s2 + (size_t)C * N;            // S, then dS: [i][j], row stride N + 1
-    const int ld = N + 1;
-    float *term = dS + (size_t)N * ld;         // per row: lse_i - S_ii (0 beyond nv)
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    constexpr int NT = STEP_THREADS, NWV = STEP_THREADS / 64;
-    const int nv = nvalid_of(nvalid, b, N);
-    const bool writer = blockIdx.y == 0;
-    {
-        const float *p1 = e1 + (long long)b * C * N, *p2 = e2 + (long long)b * C * N;
-        for (int e = tid; e < C * N; e += NT) {
-            s1[e] = p1[e];
-            s2[e] = p2[e];
-        }
-    }
-    const float gs = *gscale;
-    __syncthreads();
-    float *S = scores + (long long)b * N * N;
-    const float invN = 1.f / (float)N;
-    for (int e = tid; e < N * N; e += NT) {
-        const int i = (int)(((float)e + 0.5f) * invN), j = e - i * N;
-        float acc = 0.f;
-        if (i < nv && j < nv)
-            for (int c = 0; c < C; ++c) acc = fmaf(s1[c * N + i], s2[c * N + j], acc);
-        if (writer) S[e] = acc;
-        dS[i * ld + j] = acc;
-    }
-    __syncthreads();
-    for (int i = wave; i < N; i += NWV) {      // one wave per row, the arithmetic of score_ce_fwd_kernel
-        float l = 0.f, t = 0.f;
-        float *Sr = dS + (size_t)i * ld;
-        if (i < nv) {
-            float mx = -FLT_MAX;
-            for (int j = lane; j < nv; j += WAVE) mx = fmaxf(mx, Sr[j]);
-            mx = wave_max(mx);
-            float se = 0.f;
-            for (int j = lane; j < nv; j += WAVE) se += expf(Sr[j] - mx);
-            se = wave_sum(se);
-            l = mx + logf(se);
-            t = l - Sr[i];
-        }
-        // the row becomes dS in place (every lane has finished reading it: wave_sum is a full-wave exchange)
-        for (int j = lane; j < N; j += WAVE) {
-            float d = 0.f;
-            if (i < nv && j < nv) d = (expf(Sr[j] - l) - (i == j ? 1.f : 0.f)) * gs;
-            Sr[j] = d;
-        }
-        if (lane == 0) {
-            term[i] = t;
-            if (writer && lse) lse[(long long)b * N + i] = l;
-        }
-    }
-    __syncthreads();
-    if (writer && pair_loss && tid < row_blocks) {
-        // the partial sums of score_ce_fwd_kernel's workgroup (b, tid): wave w of it summed the rows i0 + w, i0 + w + 4, ...
-        const int rows = (N + row_blocks - 1) / row_blocks;
-        const int i0 = tid * rows, i1 = (i0 + rows < N) ? i0 + rows : N;
-        float wl[4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            wl[w] = 0.f;
-            for (int i = i0 + w; i < i1; i += 4) wl[w] += term[i];
-        }
-        pair_loss[b * row_blocks + tid] = (wl[0] + wl[1]) + (wl[2] + wl[3]);
-    }
-    // ---- de1, de2 of this workgroup's channels (score_bwd_kernel) ----
-    const int cper = (C + (int)gridDim.y - 1) / (int)gridDim.y;
-    const int c0 = blockIdx.y * cper;
-    const int cn = (c0 + cper <= C ? cper : (C > c0 ? C - c0 : 0));
-    for (int e = tid; e < 2 * cn * N; e += NT) {       // (the two gradients of an element on two threads)
-        const int which = e >= cn * N, ee = which ? e - cn * N : e;
-        const int c = ee / N, i = ee - c * N;
-        float a = 0.f;
-        if (i < nv) {
-            const float *r = (which ? s1 : s2) + (c0 + c) * N;
-            if (which) for (int jj = 0; jj < nv; ++jj) a = fmaf(r[jj], dS[jj * ld + i], a);
-            else for (int jj = 0; jj < nv; ++jj) a = fmaf(r[jj], dS[i * ld + jj], a);
-        }
-        (which ? de2 : de1)[((long long)b * C + c0) * N + ee] = a;
-    }
-}
-
 // Large N (dS does not fit LDS): grid (B, CSPLIT, ceil(N / SB_BLK)).  Workgroup (b, cs, rb) stages the row block
 // dS[i0:i1, :] and produces de1 for those rows, then stages the column block dS[:, i0:i1] and produces de2 for
 // those columns -- no cross-workgroup reduction, nothing recomputed inside the inner loops.
@@ -731,15 +639,9 @@ extern "C" int fgnn_colmax_fwd_fin_supported(int N) { return N <= 64 ? 1 : 0; }
 
 extern "C" int fgnn_colmax_fwd_fin(const fgnn_slab *y, const float *part, const float *cnt, const float *gn_weight, float eps,
                                    const int *nvalid, int G, int N, float *e, int *idx, void *stream) {
-    return fgnn_colmax_fwd_fin_r(y, part, cnt, gn_weight, eps, nvalid, G, N, fgnn_tiles_per_graph(N), e, idx, stream);
-}
-// _r: `recs` statistics records per graph (fgnn_mlp_fwd_t16: one per 16-pixel half)
-extern "C" int fgnn_colmax_fwd_fin_r(const fgnn_slab *y, const float *part, const float *cnt, const float *gn_weight, float eps,
-                                     const int *nvalid, int G, int N, int recs, float *e, int *idx, void *stream) {
     FGNN_CHECK(y && y->ptr && y->nrm && part && cnt && e && idx && G > 0 && N > 0 && y->C > 0, "fgnn_colmax_fwd_fin: bad arguments");
     FGNN_CHECK(N <= 64, "fgnn_colmax_fwd_fin: N=%d > 64 (use fgnn_gn_finalize + fgnn_colmax_fwd)", N);
-    FGNN_CHECK(recs > 0, "fgnn_colmax_fwd_fin: recs");
-    const ColmaxFin F = {part, cnt, gn_weight, eps, recs};
+    const ColmaxFin F = {part, cnt, gn_weight, eps, fgnn_tiles_per_graph(N)};
     hipLaunchKernelGGL(colmax_fwd_lds_kernel<true>, dim3((unsigned)((G * y->C + 3) / 4)), dim3(256), 0, (hipStream_t)stream, *y,
                        nvalid, G, N, e, idx, F);
     FGNN_LAUNCH_CHECK();
@@ -824,24 +726,6 @@ extern "C" int fgnn_score_ce_bwd(const float *e1, const float *e2, const float *
                                  void *stream) {
     FGNN_CHECK(e1 && e2 && scores && lse && gscale && de1 && de2 && B > 0, "fgnn_score_ce_bwd: bad arguments");
     return launch_score_bwd<true>(e1, e2, scores, lse, nullptr, nvalid, gscale, B, C, N, de1, de2, (hipStream_t)stream);
-}
-
-extern "C" int fgnn_score_ce_step_supported(int B, int C, int N) {
-    // the shapes where score_bwd_kernel stages the whole dS with CSPLIT_SMALL channel splits (small batches of small graphs)
-    return (N <= 64 && (long long)B * CSPLIT < 256 && C % CSPLIT_SMALL == 0) ? 1 : 0;
-}
-
-extern "C" int fgnn_score_ce_step(const float *e1, const float *e2, const int *nvalid, const float *gscale, int B, int C, int N,
-                                  int row_blocks, float *scores, float *lse, float *pair_loss, float *de1, float *de2, void *stream) {
-    FGNN_CHECK(e1 && e2 && gscale && scores && lse && pair_loss && de1 && de2 && B > 0 && row_blocks > 0 && row_blocks <= 256,
-               "fgnn_score_ce_step: bad arguments");
-    FGNN_CHECK(fgnn_score_ce_step_supported(B, C, N), "fgnn_score_ce_step: built for N <= 64, B < 64, C %% 8 == 0 (got B=%d C=%d N=%d); use "
-               "fgnn_score_ce_fwd_blocks + fgnn_score_ce_bwd", B, C, N);
-    const int lds = (2 * C * N + N * (N + 1) + N + 4) * (int)sizeof(float);
-    hipLaunchKernelGGL(score_ce_step_kernel, dim3(B, CSPLIT_SMALL), dim3(STEP_THREADS), lds, (hipStream_t)stream, e1, e2, nvalid, gscale, C, N,
-                       row_blocks, scores, lse, pair_loss, de1, de2);
-    FGNN_LAUNCH_CHECK();
-    return 0;
 }
 
 extern "C" int fgnn_score_bwd(const float *e1, const float *e2, const float *dscores, const int *nvalid, int B, int C,

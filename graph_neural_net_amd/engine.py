@@ -159,19 +159,10 @@ class FgnnEngine:
     SKIP_PADDING_TILES = True     # ragged engines: fgnn_ragged_tile_ranges + tile skipping in fgnn_mlp_fwd / fgnn_mlp_bwd
     MM_ORDER = True               # ragged engines: longest-job-first order of the whole-matrix per-channel products
     PAIR_BWD = os.environ.get('FGNN_PAIR_BWD', '1') != '0'      # mlp1 + mlp2 backward of a block as one launch (fgnn_mlp_bwd_pair)
-    # step(): scoring + loss + their backward as ONE launch (fgnn_score_ce_step, bit-identical to the two).  Off by default: measured in
-    # the replayed cfg2 step at 13.7 us against 5.8 + 7.0 us for the two launches it replaces (profiles/archive/r05_c_graph_timeline.txt) --
-    # every workgroup of a pair repeats the score matrix and the row log-sum-exps, and inside a graph a launch boundary costs nothing
-    SCORE_STEP = os.environ.get('FGNN_SCORE_STEP', '0') != '0'
     # the step's operand packing as extra workgroups of the structured block 1's first launch (FGNN_PACK_IN_STRUCT=0: its own launch)
     PACK_IN_STRUCT = os.environ.get('FGNN_PACK_IN_STRUCT', '1') != '0'
-    # round 6: the MLP kernels on 16-pixel tiles / v_mfma_f32_16x16x4_f32 (csrc/*_t16.hip) where they are built; FGNN_T16=0: the
-    # 32-pixel kernels everywhere.  A comma list selects kernels: 'pair' (mlp1 + mlp2 backward), 'bwd' (mlp3 backward) -- the default --
-    # and, opt-in, the forward: 'fwd3' (mlp3 forward: -1.2 us per launch; z bit-identical for the same inputs, but its statistics are
-    # per 16-pixel half, so the GraphNorm records -- and with them a few ReLU decisions of the following blocks -- round differently
-    # than in the 32-pixel forward: another, equally valid fp32 evaluation, which three batch-level golden gates tuned on the 32-pixel
-    # evaluation do not absorb; off by default), 'fwd12' (mlp1 + mlp2 forward: measured 0.3 us SLOWER per launch than the 32-pixel
-    # kernel, and its consumer -- the per-channel product that finalizes the statistics in its prologue -- 1.9 us slower)
+    # round 6: the MLP backward kernels on 16-pixel tiles / v_mfma_f32_16x16x4_f32 (csrc/*_t16.hip) where they are built; FGNN_T16=0:
+    # the 32-pixel kernels everywhere.  A comma list selects kernels: 'pair' (mlp1 + mlp2 backward), 'bwd' (mlp3 backward)
     T16 = os.environ.get('FGNN_T16', 'pair,bwd')
 
     # default contraction of the MLP kernels (FGNN_MFMA=x3 selects the split-bf16 kernels where they are built)
@@ -195,8 +186,6 @@ class FgnnEngine:
         if mfma not in ('f32', 'x3'):
             raise ValueError("mfma must be 'f32' or 'x3' (got %r)" % (mfma,))
         self.x3 = (mfma == 'x3' and not ragged and layout.depth == 3 and layout.c0 in (2, 32))
-        parts = os.environ.get('FGNN_X3_PARTS', 'fwd,pair').split(',')
-        self.x3_fwd, self.x3_pair = self.x3 and 'fwd' in parts, self.x3 and 'pair' in parts
         block1 = self.BLOCK1 if block1 is None else block1
         if block1 not in ('generic', 'structured'):
             raise ValueError("block1 must be 'generic' or 'structured' (got %r)" % (block1,))
@@ -217,8 +206,8 @@ class FgnnEngine:
         self.z = {(k, j): act() for k in range(1, K + 1) for j in (1, 2, 3)}
         self.mult = {k: act() for k in range(1, K + 1)}
         self.nrm = {(k, j): torch.empty(G * 32 * 4, **f32) for k in range(1, K + 1) for j in (1, 2, 3)}
-        # tile statistics of the forward MLP kernels: one record per 32-pixel tile, or per 16-pixel half with fgnn_mlp_fwd_t16
-        self.part = [torch.empty(G * 2 * self.tpg * 32 * 2, **f32) for _ in range(2)]
+        # tile statistics of the forward MLP kernels: one record per 32-pixel tile
+        self.part = [torch.empty(G * self.tpg * 32 * 2, **f32) for _ in range(2)]
         self.cnt = torch.empty(G * 2 * self.tpg, **f32)
         self.E = torch.empty(G, 32, N, **f32)
         self.idx = torch.empty(G, 32, N, dtype=torch.int32, device=device)
@@ -226,7 +215,6 @@ class FgnnEngine:
         self.scores = torch.empty(self.B, N, N, **f32)
         self.lse = torch.empty(self.B, N, **f32)
         self.score_blocks = _lib.load().fgnn_score_row_blocks(self.B, N)      # row blocks per pair of the scoring kernel
-        self._score_step_ok = bool(_lib.load().fgnn_score_ce_step_supported(self.B, 32, N)) and self.score_blocks <= 256
         self.pair_loss = torch.empty(self.B * self.score_blocks, **f32)
         self.loss = torch.empty(1, **f32)
         self.nvalid = torch.empty(G, dtype=torch.int32, device=device) if ragged else None
@@ -253,23 +241,14 @@ class FgnnEngine:
             # backward must recompute the hidden activations with the arithmetic of its forward (a ReLU mask that differs
             # from the forward's on a pre-activation within rounding distance of 0 is a gradient error of the flip class).
             fl = _lib.load().fgnn_pack_x3_floats if self.x3 else _lib.load().fgnn_pack_floats
+            # (kind 5: the backward image of the 16-pixel-tile kernels)
+            f12, b12 = 0, (5 if self._t16_pair(cin) else 1)
             f3 = 2 if self.x3 else 0
-            b3 = 3 if self.x3 else 1
-            # (measurement switch FGNN_X3_PARTS = 'fwd' / 'pair': only that half of the x3 kernel pair, the other on fp32 MFMAs)
-            f12 = 2 if (self.x3 and not self.x3_fwd) else 0
-            b12 = 3 if (self.x3 and not self.x3_pair) else 1
-            if self._t16_pair(cin):
-                b12 = 5
-            if self._t16_fwd(2):
-                f12 = 4
-            if self._t16_fwd(1):
-                f3 = 4
+            b3 = 5 if self._t16_bwd3(cin) else (3 if self.x3 else 1)
             self._packs[('f', k, 12)] = (f12, cin, 0, 2, torch.empty(fl(f12, cin, 0, layout.depth, 2), **f32))
             self._packs[('f', k, 3)] = (f3, 32, cin, 1, torch.empty(fl(f3, 32, cin, layout.depth, 1), **f32))
             for j in (1, 2):
                 self._packs[('b', k, j)] = (b12, cin, 0, 1, torch.empty(fl(b12, cin, 0, layout.depth, 1), **f32))
-            if self._t16_bwd3(cin):
-                b3 = 5
             self._packs[('b', k, 3)] = (b3, 32, cin, 1, torch.empty(fl(b3, 32, cin, layout.depth, 1), **f32))
 
     # ------------------------------------------------------------------ helpers
@@ -278,15 +257,7 @@ class FgnnEngine:
 
     def _t16_pair(self, cin):
         """mlp1 + mlp2 backward of a block on the 16-pixel-tile kernel (fgnn_mlp_bwd_pair_t16): dense 32-channel input slab, depth 3"""
-        return (self._t16('pair') and self.PAIR_BWD and not self.x3_pair and self.layout.depth == 3 and cin == 32 and self.N <= 256)
-
-    def _t16_fwd(self, nmlp):
-        """a forward MLP launch (nmlp = 2: mlp1 + mlp2, 1: mlp3) on the 16-pixel-tile kernel (fgnn_mlp_fwd_t16: statistics per 16-pixel half)"""
-        return self._t16('fwd3' if nmlp == 1 else 'fwd12') and not self.x3 and self.layout.depth == 3 and self.N <= 256
-
-    def _recs(self, nmlp):
-        """statistics records per graph of the forward launch with nmlp MLPs"""
-        return 2 * self.tpg if self._t16_fwd(nmlp) else self.tpg
+        return (self._t16('pair') and self.PAIR_BWD and not self.x3 and self.layout.depth == 3 and cin == 32 and self.N <= 256)
 
     def _t16_bwd3(self, cin):
         """mlp3 backward of a block on the 16-pixel-tile kernel (fgnn_mlp_bwd_t16): depth 3, input [mult ; 32 or 2 channels]"""
@@ -369,28 +340,13 @@ class FgnnEngine:
             args.ranges = self.ranges.data_ptr()
         args.cu_share = self.cu_share
         st = _lib.stream_ptr()
-        entry = 'fgnn_mlp_fwd_x3' if (self.x3_fwd and len(js) == 2) else 'fgnn_mlp_fwd'
-        recs = self._recs(len(js))
-        if self._t16_fwd(len(js)):
-            entry = 'fgnn_mlp_fwd_t16'
+        entry = 'fgnn_mlp_fwd_x3' if (self.x3 and len(js) == 2) else 'fgnn_mlp_fwd'
         _lib.call(entry, C.byref(args), st, tag='mlp_fwd[cin=%d,nmlp=%d]' % (a.C + (b.C if b is not None else 0), len(js)))
         if self.decisions is not None:
             # test-only (export_decisions): the decision-exporting twin of the launch above -- same tile code, same outputs written
             # once more -- leaves one bit per hidden pre-activation of these MLPs
             bufs = [torch.zeros(self.G * (L.depth - 1) * 32 * self.tpg, dtype=torch.int32, device=self.device) for _ in js]
-            if entry == 'fgnn_mlp_fwd_t16':
-                # the twin is the 32-pixel kernel: same inputs, same records, the same chain of fused multiply-adds -> the same decisions.
-                # Its outputs go to scratch (its statistics records have another granularity), its image it builds itself (kind 0)
-                scr = [torch.empty_like(self.z[(k, j)]) for j in js]
-                spart = [torch.empty(self.G * self.tpg * 32 * 2, dtype=torch.float32, device=self.device) for _ in js]
-                scnt = torch.empty(self.G * self.tpg, dtype=torch.float32, device=self.device)
-                for m in range(len(js)):
-                    args.z[m] = scr[m].data_ptr()
-                    args.part[m] = spart[m].data_ptr()
-                args.cnt = scnt.data_ptr()
-                args.packed = None
-                self._dbg_keep = (scr, spart, scnt)
-            _lib.call('fgnn_debug_mlp_fwd_x3_masks' if (self.x3_fwd and len(js) == 2) else 'fgnn_debug_mlp_fwd_masks', C.byref(args),
+            _lib.call('fgnn_debug_mlp_fwd_x3_masks' if (self.x3 and len(js) == 2) else 'fgnn_debug_mlp_fwd_masks', C.byref(args),
                       _lib.ptr(bufs[0]), _lib.ptr(bufs[1]) if len(js) == 2 else None, st)
             for j, buf in zip(js, bufs):
                 self.decisions[(k, j)] = buf
@@ -398,13 +354,13 @@ class FgnnEngine:
             return
         if len(js) == 2:
             r0, r1 = L.mlp[(k, js[0])], L.mlp[(k, js[1])]
-            _lib.call('fgnn_gn_finalize2_r', _lib.ptr(self.part[0]), _lib.ptr(self.part[1]), _lib.ptr(self.cnt),
+            _lib.call('fgnn_gn_finalize2', _lib.ptr(self.part[0]), _lib.ptr(self.part[1]), _lib.ptr(self.cnt),
                       C.c_void_p(self._w(params, r0['gn_w'])), C.c_void_p(self._w(params, r1['gn_w'])), self._nv(),
-                      self.G, 32, self.N, recs, EPS, _lib.ptr(self.nrm[(k, js[0])]), _lib.ptr(self.nrm[(k, js[1])]), st)
+                      self.G, 32, self.N, EPS, _lib.ptr(self.nrm[(k, js[0])]), _lib.ptr(self.nrm[(k, js[1])]), st)
         else:
             rec = L.mlp[(k, js[0])]
-            _lib.call('fgnn_gn_finalize_r', _lib.ptr(self.part[0]), _lib.ptr(self.cnt),
-                      C.c_void_p(self._w(params, rec['gn_w'])), self._nv(), self.G, 32, self.N, recs, EPS,
+            _lib.call('fgnn_gn_finalize', _lib.ptr(self.part[0]), _lib.ptr(self.cnt),
+                      C.c_void_p(self._w(params, rec['gn_w'])), self._nv(), self.G, 32, self.N, EPS,
                       _lib.ptr(self.nrm[(k, js[0])]), st)
 
     def _packed_input(self, args, k):
@@ -473,9 +429,9 @@ class FgnnEngine:
             ya, yb = self._slab_z(k, 1, params), self._slab_z(k, 2, params)
             if fin:     # the matmul finalizes the GraphNorm records of mlp1 / mlp2 itself (one launch less)
                 r1, r2 = L.mlp[(k, 1)], L.mlp[(k, 2)]
-                _lib.call('fgnn_chan_matmul_fwd_fin_ord_r', C.byref(ya), C.byref(yb), _lib.ptr(self.part[0]), _lib.ptr(self.part[1]),
+                _lib.call('fgnn_chan_matmul_fwd_fin_ord', C.byref(ya), C.byref(yb), _lib.ptr(self.part[0]), _lib.ptr(self.part[1]),
                           _lib.ptr(self.cnt), C.c_void_p(self._w(params, r1['gn_w'])), C.c_void_p(self._w(params, r2['gn_w'])),
-                          EPS, self._nv(), self.G, self.N, self._recs(2), _lib.ptr(self.mult[k]), 32 * self.ldp, self.ldp,
+                          EPS, self._nv(), self.G, self.N, _lib.ptr(self.mult[k]), 32 * self.ldp, self.ldp,
                           _lib.ptr(self.mm_order) if self.mm_order is not None else None, self._fill(), st, tag='fgnn_chan_matmul_fwd')
             else:
                 _lib.call('fgnn_chan_matmul_fwd_ord', C.byref(ya), C.byref(yb), self._nv(), self.G, self.N,
@@ -487,8 +443,8 @@ class FgnnEngine:
         out = self._slab_z(L.num_blocks, 3, params)
         if pool_fin:
             rec = L.mlp[(L.num_blocks, 3)]
-            _lib.call('fgnn_colmax_fwd_fin_r', C.byref(out), _lib.ptr(self.part[0]), _lib.ptr(self.cnt),
-                      C.c_void_p(self._w(params, rec['gn_w'])), EPS, self._nv(), self.G, self.N, self._recs(1), _lib.ptr(self.E),
+            _lib.call('fgnn_colmax_fwd_fin', C.byref(out), _lib.ptr(self.part[0]), _lib.ptr(self.cnt),
+                      C.c_void_p(self._w(params, rec['gn_w'])), EPS, self._nv(), self.G, self.N, _lib.ptr(self.E),
                       _lib.ptr(self.idx), st, tag='fgnn_colmax_fwd')
         else:
             _lib.call('fgnn_colmax_fwd', C.byref(out), self._nv(), self.G, self.N, _lib.ptr(self.E), _lib.ptr(self.idx), st)
@@ -546,14 +502,11 @@ class FgnnEngine:
                   _lib.ptr(W['wpart'][(1, 1)]), _lib.ptr(W['wpart'][(1, 2)]), _lib.ptr(W['s12'][(1, 1)]), _lib.ptr(W['s12'][(1, 2)]),
                   _lib.stream_ptr())
 
-    def forward(self, params, x, nvalid=None, total_nodes=None, defer_loss=False, loss_out=None, bits=None, pack=True,
-                with_score_bwd=False):
+    def forward(self, params, x, nvalid=None, total_nodes=None, defer_loss=False, loss_out=None, bits=None, pack=True):
         """Siamese forward on the stacked batch x = cat(x1, x2) (or its bit-packed adjacency, see embed): returns
         (scores, loss).
         defer_loss: leave the final sum of the per-pair losses to the gradient-finalize launch of the
-        following backward() (one launch less per training step); `loss` is valid after that.
-        with_score_bwd (step()): the backward of loss * 1 follows at once -- scoring, the loss and their backward run as ONE launch
-        where fgnn_score_ce_step is built for the shape (bit-identical to the two launches); backward() then starts at the pooling."""
+        following backward() (one launch less per training step); `loss` is valid after that."""
         self.embed(params, x, nvalid, bits=bits, pack=pack)
         B, N = self.B, self.N
         st = _lib.stream_ptr()
@@ -561,16 +514,8 @@ class FgnnEngine:
         if total_nodes is None:
             total_nodes = B * N if nvalid is None else int(nvalid[:B].sum().item())
         self.total_nodes = float(total_nodes)
-        self._dE_done = False
-        if with_score_bwd and self.SCORE_STEP and self._score_step_ok:
-            W = self._alloc_bwd()
-            self._set_gscale(1.0 / self.total_nodes)
-            _lib.call('fgnn_score_ce_step', _lib.ptr(e1), _lib.ptr(e2), self._nv(), _lib.ptr(W['gscale']), B, 32, N, self.score_blocks,
-                      _lib.ptr(self.scores), _lib.ptr(self.lse), _lib.ptr(self.pair_loss), _lib.ptr(W['dE'][:B]), _lib.ptr(W['dE'][B:]), st)
-            self._dE_done = True
-        else:
-            _lib.call('fgnn_score_ce_fwd_blocks', _lib.ptr(e1), _lib.ptr(e2), self._nv(), B, 32, N, self.score_blocks,
-                      _lib.ptr(self.scores), _lib.ptr(self.lse), _lib.ptr(self.pair_loss), st)
+        _lib.call('fgnn_score_ce_fwd_blocks', _lib.ptr(e1), _lib.ptr(e2), self._nv(), B, 32, N, self.score_blocks,
+                  _lib.ptr(self.scores), _lib.ptr(self.lse), _lib.ptr(self.pair_loss), st)
         self._loss_pending = bool(defer_loss)
         self._loss_target = self.loss if loss_out is None else loss_out     # 1-element fp32 device tensor
         if not defer_loss:
@@ -636,7 +581,7 @@ class FgnnEngine:
         W = self._bwd
         a1 = self._mlp_bwd_args(params, k, 1, sin, None, W['dy1'], None, None, None, False, False, False, None)
         a2 = self._mlp_bwd_args(params, k, 2, sin, None, W['dy2'], None, din, None, True, False, emit, None)
-        entry = 'fgnn_mlp_bwd_pair_x3' if self.x3_pair else ('fgnn_mlp_bwd_pair_t16' if self._t16_pair(sin.C) else 'fgnn_mlp_bwd_pair')
+        entry = 'fgnn_mlp_bwd_pair_x3' if self.x3 else ('fgnn_mlp_bwd_pair_t16' if self._t16_pair(sin.C) else 'fgnn_mlp_bwd_pair')
         _lib.call(entry, C.byref(a1), C.byref(a2), _lib.stream_ptr(),
                   tag='mlp_bwd_pair[cin=%d,dx=%d]' % (sin.C, sin.C if din is not None else 0))
 
@@ -690,10 +635,6 @@ class FgnnEngine:
         W = self._alloc_bwd()
         B, N = self.B, self.N
         st = _lib.stream_ptr()
-        if getattr(self, '_dE_done', False) and gscale_dev is None and grad_scale == 1.0:
-            self._dE_done = False              # forward(with_score_bwd=True) already left d loss / d E in W['dE']
-            return self.backward_from_dE(params, grads, W['dE'], finalize=finalize)
-        self._dE_done = False
         gs_t = W['gscale']
         if gscale_dev is not None:
             gs_t = gscale_dev                  # read in place (a 1-element fp32 device tensor; no copy launch)
@@ -813,7 +754,7 @@ class FgnnEngine:
     def step(self, params, grads, x, nvalid=None, total_nodes=None, loss_out=None, bits=None):
         """One training step's model work: forward + loss + backward.  (x / bits / an int32 device nvalid are read in place by both
         passes: see embed().)"""
-        scores, loss = self.forward(params, x, nvalid, total_nodes, defer_loss=True, loss_out=loss_out, bits=bits, with_score_bwd=True)
+        scores, loss = self.forward(params, x, nvalid, total_nodes, defer_loss=True, loss_out=loss_out, bits=bits)
         self.backward(params, grads)
         return scores, loss
 

@@ -59,7 +59,7 @@ int fgnn_mlp_bwd_num_workgroups(void);
  * Weights are constant within a step, so the images of all MLP launches can be packed ONCE
  * per step by one small launch and are then copied straight into LDS by every workgroup.
  * kind 0 = forward image (nmlp MLPs), kind 1 = backward image (one MLP; uses W[0], bias[0]);
- * kind 4 / 5 = the same two images in the layout of the 16-pixel-tile kernels (fgnn_*_t16; same sizes). */
+ * kind 5 = the backward image in the layout of the 16-pixel-tile kernels (fgnn_mlp_bwd_*t16; padded to whole KiB). */
 #define FGNN_MAX_PACK_JOBS 24
 typedef struct {
     int kind, ca, cb, depth, nmlp;
@@ -108,15 +108,6 @@ typedef struct {
                                                always runs FGNN_RANGE_WG workgroups */
 } fgnn_mlp_fwd_args;
 int fgnn_mlp_fwd(const fgnn_mlp_fwd_args *args, void *stream);
-/* Round 6: the same launch on 16-pixel tiles / v_mfma_f32_16x16x4_f32 (csrc/mlp_fwd_t16.hip, csrc/fgnn_t16.h).  z is BIT-IDENTICAL to
- * fgnn_mlp_fwd's (the conv chain runs through the same sequence of fused multiply-adds).  Differences: `packed` is mandatory and of
- * kind 4; the unit of work and of the tile statistics is a 16-pixel half tile -- part[m] is (G, R, 32, 2) and cnt (G, R) with R =
- * fgnn_mlp_fwd_t16_records(N) = 2 * fgnn_tiles_per_graph(N) -- so the statistics go to the *_r consumers below (fgnn_gn_finalize_r,
- * fgnn_gn_finalize2_r, fgnn_chan_matmul_fwd_fin_ord_r, fgnn_colmax_fwd_fin_r), which take the record count as an argument.
- * Built (fgnn_mlp_fwd_t16_supported) for depth 3, N <= 256, inputs of 32 or 2 channels (nmlp = 2) and 32 + 32 / 32 + 2 (nmlp = 1). */
-int fgnn_mlp_fwd_t16_records(int N);
-int fgnn_mlp_fwd_t16_supported(const fgnn_mlp_fwd_args *args);
-int fgnn_mlp_fwd_t16(const fgnn_mlp_fwd_args *args, void *stream);
 
 /* ---- the same two MLP entry points on the bf16 matrix cores ("x3": csrc/fgnn_x3.h) ------------------------------
  * replaces the same reference lines as fgnn_mlp_fwd / fgnn_mlp_bwd (models/layers.py:126-131 and its autograd).  Tensors,
@@ -126,7 +117,6 @@ int fgnn_mlp_fwd_t16(const fgnn_mlp_fwd_args *args, void *stream);
  * depth 3, slabs of 2 / 32 / 32+2 / 32+32 channels and constant-size batches (no `ranges`); `packed` is mandatory and
  * comes from fgnn_pack_x3_operands (same job struct as fgnn_pack_operands, fgnn_pack_x3_floats floats per image; jobs of
  * kind 2 / 3 produce the fp32 images of fgnn_pack_operands kind 0 / 1 in the same launch, for steps that mix both kernel sets). */
-int fgnn_mlp_x3_supported(int ca, int cb, int depth, int nmlp /* 1 or 2 forward; backward: 1 */);
 int fgnn_pack_x3_floats(int kind, int ca, int cb, int depth, int nmlp);
 int fgnn_pack_x3_operands(const fgnn_pack_job *jobs, int njobs, void *stream);
 int fgnn_mlp_fwd_x3(const fgnn_mlp_fwd_args *args, void *stream);
@@ -139,11 +129,6 @@ int fgnn_mlp_fwd_x3(const fgnn_mlp_fwd_args *args, void *stream);
 int fgnn_gn_finalize(const float *part, const float *cnt, const float *gn_weight /* (C) or NULL=1 */,
                      const int *nvalid, int G, int C, int N, float eps, float *nrm, void *stream);
 /* two MLPs (sharing cnt, e.g. mlp1 / mlp2 of one fgnn_mlp_fwd call) in one launch */
-/* the same two with `recs` statistics records per graph instead of fgnn_tiles_per_graph(N) (the output of fgnn_mlp_fwd_t16) */
-int fgnn_gn_finalize_r(const float *part, const float *cnt, const float *gn_weight, const int *nvalid, int G, int C, int N, int recs,
-                       float eps, float *nrm, void *stream);
-int fgnn_gn_finalize2_r(const float *part0, const float *part1, const float *cnt, const float *gn_weight0, const float *gn_weight1,
-                        const int *nvalid, int G, int C, int N, int recs, float eps, float *nrm0, float *nrm1, void *stream);
 int fgnn_gn_finalize2(const float *part0, const float *part1, const float *cnt, const float *gn_weight0,
                       const float *gn_weight1, const int *nvalid, int G, int C, int N, float eps,
                       float *nrm0, float *nrm1, void *stream);
@@ -304,11 +289,6 @@ int fgnn_chan_matmul_fwd_fin_ord(const fgnn_slab *ya, const fgnn_slab *yb, const
                                  const float *cnt, const float *gn_weight_a, const float *gn_weight_b, float eps,
                                  const int *nvalid, int G, int N, float *out, long long ogstride, long long ldo,
                                  const int *order /* as fgnn_chan_matmul_fwd_ord; used for 64 < N <= 256 */, int fill, void *stream);
-/* ... with `recs` statistics records per graph (the output of fgnn_mlp_fwd_t16) */
-int fgnn_chan_matmul_fwd_fin_ord_r(const fgnn_slab *ya, const fgnn_slab *yb, const float *part_a, const float *part_b,
-                                   const float *cnt, const float *gn_weight_a, const float *gn_weight_b, float eps,
-                                   const int *nvalid, int G, int N, int recs, float *out, long long ogstride, long long ldo,
-                                   const int *order, int fill, void *stream);
 
 /* ---- ColumnMaxPooling.forward (models/layers.py:202-203; masked: maskedtensor.py:213-228)
  * e[g,c,i] = max_j y[g,c,i,j] (first index on ties), idx int32; rows i >= nvalid -> 0.   */
@@ -319,9 +299,6 @@ int fgnn_colmax_fwd(const fgnn_slab *y, const int *nvalid, int G, int N, float *
 int fgnn_colmax_fwd_fin_supported(int N);
 int fgnn_colmax_fwd_fin(const fgnn_slab *y, const float *part, const float *cnt, const float *gn_weight, float eps,
                         const int *nvalid, int G, int N, float *e, int *idx, void *stream);
-int fgnn_colmax_fwd_fin_r(const fgnn_slab *y, const float *part, const float *cnt, const float *gn_weight, float eps,
-                          const int *nvalid, int G, int N, int recs /* statistics records per graph (fgnn_mlp_fwd_t16) */, float *e, int *idx,
-                          void *stream);
 
 /* ---- Siamese scoring + triplet_loss (models/trainers.py:67, toolbox/losses.py:20-34) ---
  * e1,e2: (B, C, N).  scores[b] = e1[b]^T e2[b] (B,N,N); lse (B,N) row log-sum-exp;
@@ -339,13 +316,6 @@ int fgnn_score_ce_fwd_blocks(const float *e1, const float *e2, const int *nvalid
 int fgnn_score_ce_bwd(const float *e1, const float *e2, const float *scores, const float *lse,
                       const int *nvalid, const float *gscale, int B, int C, int N,
                       float *de1, float *de2, void *stream);
-/* Scoring forward + triplet loss + their backward in ONE launch -- what a training step issues back to back (models/trainers.py:60-76:
- * `loss = self.loss(self(x1, x2))` followed at once by autograd's first two nodes): the outputs of fgnn_score_ce_fwd_blocks (scores,
- * lse, pair_loss with `row_blocks` partial sums per pair) AND of fgnn_score_ce_bwd (de1, de2; gscale as there), bit-identical to
- * the two launches.  Small batches of small graphs: fgnn_score_ce_step_supported(B, C, N) (N <= 64, B < 64, 8 | C). */
-int fgnn_score_ce_step_supported(int B, int C, int N);
-int fgnn_score_ce_step(const float *e1, const float *e2, const int *nvalid, const float *gscale, int B, int C, int N, int row_blocks,
-                       float *scores, float *lse, float *pair_loss, float *de1, float *de2, void *stream);
 
 /* triplet_loss on a given score tensor: lse (B,N), pair_loss (B) (toolbox/losses.py:27-34) */
 int fgnn_ce_fwd(const float *scores, const int *nvalid, int B, int N, float *lse, float *pair_loss, void *stream);
@@ -372,9 +342,6 @@ int fgnn_gn_bwd_stats(const float *dy, long long dgstride, long long ldd,
 int fgnn_gn_bwd_coef(const float *s12, const float *nrm, const int *nvalid, int G, int C, int N,
                      float *coef /* (G*C*4) */, float *dgn_w /* (C) or NULL */, float *dgn_b /* (C) or NULL */,
                      void *stream);
-/* coefficients of two MLPs in one launch (no affine gradients) */
-int fgnn_gn_bwd_coef2(const float *s12_0, const float *s12_1, const float *nrm0, const float *nrm1,
-                      const int *nvalid, int G, int C, int N, float *coef0, float *coef1, void *stream);
 /* same coefficients from per-tile partial sums (G, tpg, C, 2) as emitted by fgnn_mlp_bwd
  * (s12part); also writes the summed s12 (G*C*2) for the affine gradients.                  */
 int fgnn_gn_bwd_coef_tiles(const float *s12part, const float *nrm, const int *nvalid, int G, int C, int N,
@@ -427,7 +394,6 @@ int fgnn_mlp_bwd_x3(const fgnn_mlp_bwd_args *args, void *stream);   /* the x3 fo
  * `m1` / `m2` are the argument blocks of the two fgnn_mlp_bwd calls it replaces, describing the same input slab; the input
  * gradient (dxa, accumulate_a) and its tile sums (s12part) are given in m2 only and receive (old + dx1) + dx2, bit-identical to
  * the two accumulating launches.  Depth 3, one slab of 2 or 32 channels, constant-size batches, both operand images. */
-int fgnn_mlp_bwd_pair_supported(int ca, int depth);
 int fgnn_mlp_bwd_pair(const fgnn_mlp_bwd_args *m1, const fgnn_mlp_bwd_args *m2, void *stream);
 /* The same launch with every contraction on the bf16 matrix cores through the exact three-way operand split (the arithmetic of
  * fgnn_mlp_bwd_x3 / fgnn_mlp_fwd_x3: the recompute reproduces the x3 forward bit for bit): both images are of kind 1 from
@@ -436,7 +402,7 @@ int fgnn_mlp_bwd_pair(const fgnn_mlp_bwd_args *m1, const fgnn_mlp_bwd_args *m2, 
 int fgnn_mlp_bwd_pair_x3(const fgnn_mlp_bwd_args *m1, const fgnn_mlp_bwd_args *m2, void *stream);
 /* Round 6: the same launch on 16-pixel tiles / v_mfma_f32_16x16x4_f32 (csrc/mlp_bwd_pair_t16.hip, csrc/fgnn_t16.h) -- same arguments,
  * work unit (a 32-pixel tile, processed as two halves), S1/S2 records and partial rows as fgnn_mlp_bwd_pair, so it is a drop-in; the
- * operand images are of kind 5 (fgnn_pack_operands; kind 4 = the forward image for the *_t16 forward kernel).  The recomputed hidden
+ * operand images are of kind 5 (fgnn_pack_operands).  The recomputed hidden
  * activations follow the SAME fma sequence as the 32-pixel kernels (bit-identical ReLU masks); d_in is one fma chain over (the
  * gradient mlp3 left, mlp1's terms, mlp2's terms) instead of three separately rounded sums, the weight-gradient sums run in another
  * pixel order: equal to the 32-pixel kernel to fp32 rounding, not bit for bit.  Depth 3, one dense 32-channel slab, N <= 256,
@@ -448,7 +414,6 @@ int fgnn_mlp_bwd_pair_x3(const fgnn_mlp_bwd_args *m1, const fgnn_mlp_bwd_args *m
  * channels (dense or bit-packed) without dxb; no accumulation; N <= 256. */
 int fgnn_mlp_bwd_t16_supported(const fgnn_mlp_bwd_args *args);
 int fgnn_mlp_bwd_t16(const fgnn_mlp_bwd_args *args, void *stream);
-int fgnn_mlp_bwd_pair_t16_supported(int ca, int depth);
 int fgnn_mlp_bwd_pair_t16(const fgnn_mlp_bwd_args *m1, const fgnn_mlp_bwd_args *m2, void *stream);
 #define FGNN_BWD_COEF_GRAPHS 4
 int fgnn_mlp_bwd_coef_tiles_supported(int G, int N);   /* s12tiles usable: a workgroup spans <= FGNN_BWD_COEF_GRAPHS graphs */
@@ -517,21 +482,19 @@ int fgnn_lsap_accuracy(const float *cost, long long bstride, int ld, const int *
  * (models/layers.py:161-162) has a closed form in W, W^2, the degrees and the class values.  For bit-packed inputs of
  * batches (constant-size or ragged) with N <= 256, depth 3, these entry points replace fgnn_mlp_fwd (mlp1 + mlp2) + fgnn_chan_matmul_fwd
  * and fgnn_chan_matmul_bwd + fgnn_mlp_bwd_pair of block 1: same function, another evaluation order (equal to fp32 rounding).
- *   tables : (2 models, 2 + 2 (N + 1) classes, {h1, h2, z, z as stored}, 32) floats, graph independent: once per step.
- *            bf16_scheme != 0: the arithmetic of the 16-bit engine (matrix-core operands R(W), R(relu(.)), stored R(z))
+ *   tables : (2 models, 2 + 2 (N + 1) classes, {h1, h2, z, z as stored}, 32) floats, graph independent: built by the first launch
+ *            of fwd from tW1 / tb1 / tW2 / tb2
  *   fwd    : GraphNorm records nrm1 / nrm2 (G, 32, 4) of mlp1 / mlp2 and the raw slab mult (G, 32, ldp)
  *   bwd    : from d(mult): the first fgnn_block1_struct_rows(G, N) rows of wpart1 / wpart2 (the partial layout of fgnn_mlp_bwd; the
  *            other rows are not written: reduce exactly these, fgnn_grad_job.rows) and s12_1 / s12_2 (G, 32, 2), ready for
  *            fgnn_grad_finalize
- * The ...16 forms take the bf16 slabs of the 16-bit engine (row pitch ldr elements, channel stride ldp, tables built with
- * bf16_scheme = 1): mult is rounded to nearest even on store, the statistics stay fp32 and the class sums of the backward pass
+ * The ...16 forms take the bf16 slabs of the 16-bit engine (row pitch ldr elements, channel stride ldp, tables built with the
+ * arithmetic of the 16-bit engine: matrix-core operands R(W), R(relu(.)), stored R(z)): mult is rounded to nearest even on store, the statistics stay fp32 and the class sums of the backward pass
  * are formed in fp32 from the bf16 d(mult) (the generic 16-bit kernels round every pixel of dY1 / dY2 / dz instead).          */
 int fgnn_block1_struct_supported(int N, int depth, int original_features_num);      /* N <= 256, depth 3, 2 input channels */
 int fgnn_block1_struct_table_floats(int N);
 long long fgnn_block1_struct_ws_floats(int G, int N);       /* workspace shared by fwd and bwd of one step (16-byte aligned) */
 int fgnn_block1_struct_rows(int G, int N);                  /* bwd writes rows 0 .. rows-1 of wpart1 / wpart2 (<= fgnn_mlp_bwd_num_workgroups()) and no others; G > that many rows: row b sums the graphs b, b + rows, ... */
-int fgnn_block1_struct_tables(const float *const *W1, const float *const *b1, const float *const *W2, const float *const *b2, int N,
-                              int bf16_scheme, float *tables, void *stream);
 /* nvalid: optional per-graph vertex counts (ragged batches: the N x N planes are padded; mult is written as 0 outside the valid
  * corner, class counts and the GraphNorm n use nvalid[g]).  fwd fills ws (16-bit code plane (W^2)_ij | w_ij << 15, per-vertex
  * {row sum, column sum, w_ii, class}); bwd of the same step reads it. */
@@ -539,8 +502,8 @@ int fgnn_block1_struct_fwd(const unsigned *bits, const int *nvalid, int G, int N
                            const float *gnw2, const float *gnb2, float eps, float *nrm1, float *nrm2, float *mult, long long gstride,
                            long long ldp, float *xdeg /* optional: (G, N) row sums, as fgnn_adjacency_degree writes them */, float *ws,
                            const float *const *tW1, const float *const *tb1, const float *const *tW2, const float *const *tb2
-                           /* optional, all four or none: the arguments of fgnn_block1_struct_tables -- `tables` is then (re)built
-                              inside the first launch of this call instead of by a launch of its own */,
+                           /* required: the three weights / biases of mlp1 and mlp2 of block 1 -- `tables` is (re)built from them
+                              inside the first launch of this call */,
                            void *stream);
 int fgnn_block1_struct_bwd(const unsigned *bits, const int *nvalid, int G, int N, const float *tables, const float *const *W1,
                            const float *const *W2, const float *nrm1, const float *nrm2, const float *gnb1, const float *gnb2,
@@ -770,7 +733,8 @@ int fgnn_pairgen(const fgnn_pairgen_args *args, void *stream);
  * of word (g, layer, channel, t) = [hidden pre-activation of pixel 32 t + j > 0] as `relu` sees it (bit pattern > 0).  Depth 3;
  * words of tiles a ragged launch steps over are not written.  The x3 twin exists for the two-MLP launches (masks1 required).
  * fgnn_debug_matmul_variant: 0 selects the workgroup-per-matrix forward product (N <= 64) that fgnn_chan_matmul_fwd_w replaced, 1
- * (default) the wave-per-matrix kernel; process-global; for the bit-identity test of the two (tests/test_gpu_kernels.py). */
+ * (default) the wave-per-matrix kernel, 9 its four-byte-access form; process-global; for the bit-identity tests of the three
+ * (tests/test_gpu_kernels.py). */
 int fgnn_debug_mlp_fwd_masks(const fgnn_mlp_fwd_args *args, unsigned *masks0, unsigned *masks1 /* nmlp == 2 */, void *stream);
 int fgnn_debug_mlp_fwd_x3_masks(const fgnn_mlp_fwd_args *args, unsigned *masks0, unsigned *masks1, void *stream);
 int fgnn_debug_matmul_variant(int wave_per_matrix);

@@ -14,9 +14,9 @@ eng = FgnnEngine(lay, 64, 50, dev)
 eng.step(params, grads, x); torch.cuda.synchronize()
 W = eng._bwd; gs = 32 * eng.ldp; st = None
 
-def stage_fwd12():
+def stage_mlp12():
     eng._mlp_fwd(params, 2, (1, 2), eng._slab_in(2, params), None)          # mlp12 + finalize2
-def stage_fwd12_only():
+def stage_mlp12_only():
     a = eng._slab_in(2, params)
     args = _lib.MlpFwdArgs(); L = lay
     args.G, args.N, args.depth, args.nmlp = eng.G, eng.N, L.depth, 2
@@ -38,8 +38,9 @@ def stage_matmul_bwd():
     _lib.call('fgnn_chan_matmul_bwd', C.byref(ya), C.byref(yb), _lib.ptr(W['dmult']), gs, eng.ldp, None, eng.G, eng.N,
               _lib.ptr(W['dy1']), _lib.ptr(W['dy2']), gs, eng.ldp, _lib.ptr(W['s12'][(2, 1)]), _lib.ptr(W['s12'][(2, 2)]), _lib.stream_ptr())
 def stage_coef2():
-    _lib.call('fgnn_gn_bwd_coef2', _lib.ptr(W['s12'][(2, 1)]), _lib.ptr(W['s12'][(2, 2)]), _lib.ptr(eng.nrm[(2, 1)]), _lib.ptr(eng.nrm[(2, 2)]),
-              None, eng.G, 32, eng.N, _lib.ptr(W['coef'][0]), _lib.ptr(W['coef'][1]), _lib.stream_ptr())
+    for j in (1, 2):
+        _lib.call('fgnn_gn_bwd_coef', _lib.ptr(W['s12'][(2, j)]), _lib.ptr(eng.nrm[(2, j)]), None, eng.G, 32, eng.N,
+                  _lib.ptr(W['coef'][j - 1]), None, None, _lib.stream_ptr())
 
 def timeit(name, fn, copies=20, reps=20):
     fn(); torch.cuda.synchronize()
@@ -56,8 +57,8 @@ def timeit(name, fn, copies=20, reps=20):
     torch.cuda.synchronize()
     print('%-18s %7.2f us per call (graph replay, %d copies)' % (name, (time.perf_counter() - t) / reps / copies * 1e6, copies))
 
-timeit('mlp_fwd12+fin2', stage_fwd12)
-timeit('mlp_fwd12 only', stage_fwd12_only)
+timeit('mlp12 fwd+fin2', stage_mlp12)
+timeit('mlp12 fwd only', stage_mlp12_only)
 timeit('matmul_fwd', stage_matmul_fwd)
 timeit('mlp_bwd[32]', stage_bwd1)
 timeit('matmul_bwd', stage_matmul_bwd)

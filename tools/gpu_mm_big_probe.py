@@ -1,5 +1,5 @@
 """Isolated timing of the whole-matrix per-channel products (64 < N <= 128) on a ragged batch: plain launch order against the
-largest-graph-first order of fgnn_ragged_tile_ranges_order, with and without one workgroup per product in the backward.
+largest-graph-first order of fgnn_ragged_tile_ranges_order.
 usage: python tools/gpu_mm_big_probe.py [pairs]     (default 8: the cfg5 batch of bench.py)"""
 import ctypes as C, os, sys
 import torch
@@ -46,11 +46,7 @@ _lib.call('fgnn_ragged_tile_ranges_order', _lib.ptr(nv), G, N, _lib.ptr(ranges),
 flops = float((2 * nv.double() ** 3).sum() * Cc)
 print('G = %d graphs, N = %d, n = %s: %.2f GFLOP per product, %.1f MB per slab' % (G, N, n.tolist(), flops / 1e9, G * Cc * P * 4 / 1e6))
 it = [0]
-lib = _lib.load()
-for name, variant, o in (('plain order', 1, None), ('largest first, one workgroup per matrix', 3, order),
-                         ('largest first, backward: one workgroup per product', 1, order)):
-    lib.fgnn_debug_matmul_variant(variant)
-
+for name, o in (('plain order', None), ('largest first (backward: one workgroup per product)', order)):
     def fwd():
         s = sets[it[0] % K]; it[0] += 1
         _lib.call('fgnn_chan_matmul_fwd_ord', C.byref(s[0]), C.byref(s[1]), _lib.ptr(nv), G, N, _lib.ptr(s[3]), Cc * P, P, _lib.ptr(o), 0, st)
@@ -62,4 +58,3 @@ for name, variant, o in (('plain order', 1, None), ('largest first, one workgrou
 
     tf, tb = timeit(fwd), timeit(bwd)
     print('%-52s fwd %6.1f us (%5.1f TFLOP/s)   bwd %6.1f us (%5.1f TFLOP/s)' % (name, tf, flops / tf / 1e6, tb, 2 * flops / tb / 1e6))
-lib.fgnn_debug_matmul_variant(1)

@@ -1,5 +1,5 @@
 """16-pixel-tile MLP kernels (csrc/*_t16.hip) against the 32-pixel kernels: agreement of one step + per-launch and captured step time.
-usage: python tools/gpu_t16_probe.py [which ...]   which = comma lists for FGNN_T16, e.g. pair  pair,bwd  pair,bwd,fwd"""
+usage: python tools/gpu_t16_probe.py [which ...]   which = comma lists for FGNN_T16, e.g. pair  pair,bwd"""
 import os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
