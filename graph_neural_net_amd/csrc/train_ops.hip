@@ -62,7 +62,9 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float *p, const float *g,
     }
 }
 
-// one workgroup per pair: rows i < nv with argmax_j scores[i][j] (first maximum) == i
+// one workgroup per pair: rows i < nv with argmax_j scores[i][j] (first maximum) == i.
+// np.argmax order: NaN is the largest value (the first NaN wins), and a row of -inf still has its first column as
+// arg-max.  A lane without columns holds (-inf, INT_MAX), which loses every comparison with a real entry.
 __global__ __launch_bounds__(256) void accuracy_max_kernel(const float *scores, const int *nvalid, int N, int *correct) {
     __shared__ int red[4];
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -70,11 +72,11 @@ __global__ __launch_bounds__(256) void accuracy_max_kernel(const float *scores, 
     const float *S = scores + (long long)b * N * N;
     int cnt = 0;
     for (int i = wave; i < nv; i += 4) {
-        float best = -3.402823466e+38f;
+        float best = -INFINITY;
         int bj = 0x7fffffff;
-        for (int j = lane; j < nv; j += WAVE) {
+        for (int j = lane; j < nv; j += WAVE) {          // ascending j: an equal later value never replaces
             const float v = S[(long long)i * N + j];
-            if (v > best) {
+            if (bj == 0x7fffffff || (best == best && (v > best || v != v))) {
                 best = v;
                 bj = j;
             }
@@ -83,7 +85,8 @@ __global__ __launch_bounds__(256) void accuracy_max_kernel(const float *scores, 
         for (int o = 32; o > 0; o >>= 1) {
             const float ob = __shfl_xor(best, o);
             const int oj = __shfl_xor(bj, o);
-            if (ob > best || (ob == best && oj < bj)) {
+            const bool onan = ob != ob, bnan = best != best;
+            if (onan ? (!bnan || oj < bj) : (!bnan && (ob > best || (ob == best && oj < bj)))) {
                 best = ob;
                 bj = oj;
             }

@@ -20,10 +20,10 @@ def accuracy_max(weights, aggregate_score=True):
         s, nvalid = weights, None
         sizes = torch.full((s.shape[0],), s.shape[1], dtype=torch.int64, device=s.device)
     if not s.is_cuda:           # host scores: the reference's arg-max comparison (toolbox/metrics.py:127-137), per graph
-        n_ok = [int((s[b, :int(n), :int(n)].argmax(-1) == torch.arange(int(n))).sum()) for b, n in enumerate(sizes.tolist())]
+        n_ok = [int((s[b, :n, :n].argmax(-1) == torch.arange(n)).sum()) if n else 0 for b, n in enumerate(sizes.tolist())]
         if aggregate_score:
             return sum(n_ok), int(sizes.sum().item())
-        return [c / int(n) for c, n in zip(n_ok, sizes.tolist())]
+        return [c / n if n else float('nan') for c, n in zip(n_ok, sizes.tolist())]     # an empty graph: 0 / 0, as on the device
     s = s.contiguous()
     B, N, _ = s.shape
     correct = torch.empty(B, dtype=torch.int32, device=s.device)

@@ -463,7 +463,8 @@ int fgnn_adam_step(float *params, const float *grads, float *exp_avg, float *exp
 int fgnn_adam_step_dev(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int n,
                        const double *hp, int *state, void *stream);
 /* accuracy_max (toolbox/metrics.py:119-141): correct[b] = #{i < n_b : argmax_j scores[b,i,j] == i},
- * first maximum on ties (np.argmax); int32, bit-exact.                                              */
+ * with np.argmax's order: first maximum on ties, NaN above every number (the first NaN wins), a row of -inf
+ * has column 0 as arg-max; int32, bit-exact.                                                         */
 int fgnn_accuracy_max(const float *scores, const int *nvalid, int B, int N, int *correct, void *stream);
 /* accuracy_linear_assignment (toolbox/metrics.py:92-116): per graph b the minimum-cost perfect matching of the n_b x n_b corner
  * of cost[b] (= -log_softmax(scores[b]); row pitch ld, graphs bstride apart), correct[b] = #{i : matched column of row i == i};

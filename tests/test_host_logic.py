@@ -190,6 +190,22 @@ def test_metrics_on_host_scores_take_the_reference_route():
     assert accuracy_max(mt) == (sum(int((t.argmax(-1) == torch.arange(t.shape[0])).sum()) for t in lst), 10)
 
 
+def test_accuracy_max_host_route_follows_np_argmax():
+    """Host scores: an empty graph counts nothing (no arg-max of an empty row), a row of -inf has column 0 as arg-max, the first
+    NaN wins, ties go to the lower index -- np.argmax on each graph's valid block (toolbox/metrics.py:131)."""
+    from graph_neural_net_amd.metrics import accuracy_max
+    inf, nan = float('inf'), float('nan')
+    s = torch.zeros(3, 4, 4)
+    s[0] = torch.tensor([[-inf] * 4, [1., 2., 2., 0.], [0., nan, nan, 5.], [inf, 0., 0., inf]])
+    s[1] = torch.tensor([[2., 0., 2., 0.], [nan, nan, 0., 0.], [0., 0., nan, 0.], [0.] * 4])
+    nv = torch.tensor([4, 3, 0], dtype=torch.int32)
+    want = [int(np.sum(np.argmax(s[b, :n, :n].numpy(), 1) == np.arange(n))) if n else 0 for b, n in enumerate(nv.tolist())]
+    assert want == [2, 2, 0]
+    assert accuracy_max(MaskedTensor(s, nv, (1, 2))) == (4, 7)
+    per = accuracy_max(MaskedTensor(s, nv, (1, 2)), aggregate_score=False)
+    assert per[:2] == [2 / 4, 2 / 3] and np.isnan(per[2])
+
+
 def test_bench_algorithmic_model_matches_survey_figures():
     """bench.py's per-pair and per-launch algorithmic figures."""
     import importlib.util
