@@ -532,11 +532,13 @@ static int mlp_fwd_entry(const fgnn_mlp_fwd_args *a, void *stream, unsigned *con
     const long long total = (long long)a->G * tpg;
     FGNN_CHECK(total < (1ll << 30), "fgnn_mlp_fwd: too many tiles");
     hipStream_t st = (hipStream_t)stream;
-    if (dbg) {          // the decision-exporting twins exist for the fused engine's shapes: depth 3
-        FGNN_CHECK(a->depth == 3 && dbg[0] && (a->nmlp == 1 || dbg[1]), "fgnn_debug_mlp_fwd_masks: depth 3 and one mask buffer per MLP");
+    if (dbg) {          // the decision-exporting twins exist for every depth (depth 1 has no hidden layer: it writes no mask)
+        FGNN_CHECK(a->depth == 1 || (dbg[0] && (a->nmlp == 1 || dbg[1])), "fgnn_debug_mlp_fwd_masks: one mask buffer per MLP");
         const DbgOut d = {{dbg[0], a->nmlp == 2 ? dbg[1] : nullptr}};
-        if (a->nmlp == 1) return dispatch_c<1, 3, true>(a, tpg, (int)total, st, d);
-        return dispatch_c<2, 3, true>(a, tpg, (int)total, st, d);
+#define FGNN_ND(NM_, D_) \
+    if (a->nmlp == NM_ && a->depth == D_) return dispatch_c<NM_, D_, true>(a, tpg, (int)total, st, d);
+        FGNN_ND(1, 1) FGNN_ND(1, 2) FGNN_ND(1, 3) FGNN_ND(2, 1) FGNN_ND(2, 2) FGNN_ND(2, 3)
+#undef FGNN_ND
     }
 #define FGNN_ND(NM_, D_) \
     if (a->nmlp == NM_ && a->depth == D_) return dispatch_c<NM_, D_>(a, tpg, (int)total, st);
@@ -548,9 +550,9 @@ static int mlp_fwd_entry(const fgnn_mlp_fwd_args *a, void *stream, unsigned *con
 
 extern "C" int fgnn_mlp_fwd(const fgnn_mlp_fwd_args *a, void *stream) { return mlp_fwd_entry(a, stream, nullptr); }
 
-// Test-only (tests/test_gpu_grad_pinned.py): fgnn_mlp_fwd once more -- same tile code, same outputs -- that also writes the ReLU
-// decisions of the two hidden layers, masks[m]: (G, 2, 32, tiles per graph) words, bit j of word (g, layer, channel, t) = hidden
-// pre-activation of pixel 32 t + j > 0.  Words of tiles a ragged launch steps over are not written.
+// Test-only (tests/test_gpu_grad_pinned.py, tests/test_gpu_pinned_shapes.py): fgnn_mlp_fwd once more -- same tile code, same outputs --
+// that also writes the ReLU decisions of the depth - 1 hidden layers, masks[m]: (G, depth - 1, 32, tiles per graph) words, bit j of word
+// (g, layer, channel, t) = hidden pre-activation of pixel 32 t + j > 0.  Words of tiles a ragged launch steps over are not written.
 extern "C" int fgnn_debug_mlp_fwd_masks(const fgnn_mlp_fwd_args *a, unsigned *masks0, unsigned *masks1, void *stream) {
     unsigned *const dbg[2] = {masks0, masks1};
     return mlp_fwd_entry(a, stream, dbg);

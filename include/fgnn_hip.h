@@ -731,8 +731,8 @@ int fgnn_pairgen(const fgnn_pairgen_args *args, void *stream);
  * fgnn_debug_mlp_fwd_masks / fgnn_debug_mlp_fwd_x3_masks: fgnn_mlp_fwd / fgnn_mlp_fwd_x3 once more -- the same tile code, the same
  * outputs, bit for bit -- that ALSO exports the ReLU decisions of the conv chain (models/layers.py:129-130), the input of the
  * decision-pinned gradient test (tests/test_gpu_grad_pinned.py): masks[m] is (G, depth - 1, 32, fgnn_tiles_per_graph(N)) words, bit j
- * of word (g, layer, channel, t) = [hidden pre-activation of pixel 32 t + j > 0] as `relu` sees it (bit pattern > 0).  Depth 3;
- * words of tiles a ragged launch steps over are not written.  The x3 twin exists for the two-MLP launches (masks1 required).
+ * of word (g, layer, channel, t) = [hidden pre-activation of pixel 32 t + j > 0] as `relu` sees it (bit pattern > 0).  Every
+ * depth (depth 1 writes no mask, its buffers may be NULL); words of tiles a ragged launch steps over are not written.  The x3 twin exists for the two-MLP launches (masks1 required).
  * fgnn_debug_matmul_variant: 0 selects the workgroup-per-matrix forward product (N <= 64) that fgnn_chan_matmul_fwd_w replaced, 1
  * (default) the wave-per-matrix kernel, 9 its four-byte-access form; process-global; for the bit-identity tests of the three
  * (tests/test_gpu_kernels.py). */

@@ -78,6 +78,8 @@ def _loss_sum(scores):
     loss, total = 0, 0
     for out in scores:
         n = out.shape[0]
+        if n == 0:          # a size-0 filler pair (FgnnTrainer pads buckets with them) holds no vertex
+            continue
         loss = loss + F.cross_entropy(out, torch.arange(n, device=out.device), reduction='sum')
         total += n
     return loss, total
@@ -105,12 +107,16 @@ def step_fwd_bwd_pinned_ragged(x1, x2, sizes, sd, masks, idx, dtype=torch.float6
     """The ragged step (per-graph dense runs, the reference's own definition of a masked result:
     maskedtensors/test_maskedtensor.py:22-27, 141-150): x1, x2 (B, c0, Nmax, Nmax) zero-padded, sizes[b] vertices in pair b;
     decisions of the stacked padded batch, read on the valid corners.  loss = sum of the CE sums / sum(n) (toolbox/losses.py:27-34).
+    A pair with n = 0 (a filler) is skipped: its scores are (0, 0) and it adds nothing to the loss.
     Returns ([scores_b (n_b, n_b)], loss, grads)."""
     device = x1.device if device is None else device
     params = {k: v.detach().to(device=device, dtype=dtype).clone().requires_grad_(True) for k, v in O._strip(sd).items()}
     B = x1.shape[0]
     scores = []
     for b, n in enumerate(sizes):
+        if n == 0:
+            scores.append(torch.zeros(0, 0, dtype=dtype, device=device))
+            continue
         es = []
         for x, g in ((x1, b), (x2, B + b)):
             mk = {k: v[g:g + 1, :, :n, :n].to(device) for k, v in masks.items()}

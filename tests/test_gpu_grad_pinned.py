@@ -26,9 +26,9 @@ import numpy as np
 import pytest
 import torch
 
+import pinned
 from graph_neural_net_amd import synthetic
-from graph_neural_net_amd.engine import FgnnEngine, ParamLayout
-from oracle import fgnn_oracle_pinned as OP
+from pinned import pad_pairs
 from util import GOLDEN, is_zero_grad, load_golden, sub, unpack_pairs
 
 pytestmark = pytest.mark.gpu
@@ -37,10 +37,6 @@ PINNED_MEDIAN = {'f32': 1e-5, 'x3': 2e-5}        # median over the tensors of th
 PINNED_WORST = {'f32': 1.0, 'x3': 2.0}           # every tensor, in units of the reference's own worst tensor on the same batch
 ZERO_GRAD_ABS = 1e-4         # the analytically zero last-conv-bias gradients (GraphNorm removes the mean): absolute
 LOSS_TOL = 2e-6
-
-
-def _bits(x):
-    return torch.from_numpy(synthetic.pack_adjacency(x[:, 0].numpy()).view(np.int32)).to(DEV)
 
 
 def _case(name):
@@ -54,10 +50,8 @@ def _case(name):
         x1, x2 = synthetic.make_batch(4000, 8, 200, 'ErdosRenyi', 0.5, 0.1)
         return sd, x1, x2, None
     xs, ys = synthetic.make_ragged_batch(5000, 8, 30, 120, 'ErdosRenyi', 0.2, 0.1)
-    sizes = [int(t.shape[-1]) for t in xs]
-    N = max(sizes)
-    pad = lambda lst: torch.stack([torch.nn.functional.pad(t, (0, N - t.shape[-1], 0, N - t.shape[-1])) for t in lst])
-    return sd, pad(xs), pad(ys), sizes
+    x1, x2, sizes = pad_pairs(xs, ys)
+    return sd, x1, x2, sizes
 
 
 def run_pinned(case, mode):
@@ -65,46 +59,25 @@ def run_pinned(case, mode):
     evaluation of the branch the engine took."""
     sd, x1, x2, sizes = _case(case)
     struct = mode.endswith('s')
-    mfma = mode[:-1] if struct else mode
-    B, N = x1.shape[0], x1.shape[-1]
-    lay = ParamLayout(2, 4, 32, 32, 3)
-    params = lay.flatten(sd, DEV)
-    eng = FgnnEngine(lay, 2 * B, N, DEV, ragged=sizes is not None, mfma=mfma, block1='structured' if struct else 'generic')
-    nv = torch.tensor(sizes * 2, dtype=torch.int32, device=DEV) if sizes is not None else None
-    x = torch.cat([x1, x2]).contiguous()
-    kw = dict(bits=_bits(x)) if struct else {}
-    xin = None if struct else x.to(DEV)
-    # the product step, then the same step with the decision export on: the export must not change a bit of the results
-    g0 = torch.zeros_like(params)
-    s0, l0 = eng.step(params, g0, xin, nvalid=nv, **kw)
-    torch.cuda.synchronize()
-    s0, l0 = s0.clone(), l0.clone()
-    eng.export_decisions(True)
-    grads = torch.zeros_like(params)
-    scores, loss = eng.step(params, grads, xin, nvalid=nv, **kw)
-    torch.cuda.synchronize()
-    assert torch.equal(grads, g0) and torch.equal(scores, s0) and torch.equal(loss, l0)
-    masks = eng.relu_decisions()
-    assert len(masks) == 4 * 3 * 2
-    idx = eng.idx.to(torch.int64)
+    r = pinned.run_pinned(sd, x1, x2, sizes, mfma=mode[:-1] if struct else mode, block1='structured' if struct else 'generic',
+                          bits=struct)
+    assert len(r.masks) == 4 * 3 * 2
     # fp64 on the device, on that branch
+    s64, l64, g64 = pinned.pinned_oracle(r, sd, x1, x2, torch.float64, DEV)
     if sizes is None:
-        s64, l64, g64 = OP.step_fwd_bwd_pinned(x1, x2, sd, masks, idx, dtype=torch.float64, device=DEV)
-        assert ((scores.double() - s64).abs().max() / s64.abs().max()).item() < 3e-5
+        assert ((r.scores.double().cpu() - s64).abs().max() / s64.abs().max()).item() < 3e-5
     else:
-        s64, l64, g64 = OP.step_fwd_bwd_pinned_ragged(x1, x2, sizes, sd, masks, idx, dtype=torch.float64, device=DEV)
         for b, n in enumerate(sizes):
-            assert ((scores[b, :n, :n].double() - s64[b]).abs().max() / s64[b].abs().max()).item() < 3e-5
-    got = lay.unflatten(grads)
+            assert ((r.scores[b, :n, :n].double().cpu() - s64[b]).abs().max() / s64[b].abs().max()).item() < 3e-5
     errs = {}
     for name, g in g64.items():
-        a = got[name].double()
+        a = r.grads[name].double().cpu()
         if is_zero_grad(name):
             assert a.abs().max().item() < ZERO_GRAD_ABS, (name, a.abs().max().item())
             continue
         errs[name] = ((a - g.reshape(a.shape)).abs().max() / g.abs().max()).item()
-    ndec = sum(int(m.numel()) for m in masks.values()) + idx.numel()
-    return errs, abs(loss.item() - l64.item()) / abs(l64.item()), ndec
+    ndec = sum(int(m.numel()) for m in r.masks.values()) + r.idx.numel()
+    return errs, abs(r.loss - l64) / abs(l64), ndec
 
 
 # (ragged batches run the fp32-MFMA kernels in every mode -- FgnnEngine.x3 is False for ragged engines -- so cfg5 has two modes)
@@ -134,33 +107,15 @@ def test_bf16_gradients_on_the_engines_own_branch():
     on the neighbouring bf16 number).  Yard-stick: the reference's OWN bf16 run against fp64 on the N = 200 fixture
     (cfg4_er_n200_b1_4blk.npz, grad_refbf16 / grad64): every gradient tensor of the engine must lie closer to its pinned evaluation than
     the reference's worst tensor lies to the truth (gate: a fifth of it), the median tensor within a fiftieth of the reference's median."""
-    from graph_neural_net_amd.engine16 import FgnnEngineBF16
-    from oracle import fgnn_oracle_bf16 as OB
     from util import rel
     sd = sub(load_golden('cfg2_reg_n50_b2_4blk.npz'), 'sd/')
     x1, x2 = synthetic.make_batch(4000, 8, 200, 'ErdosRenyi', 0.5, 0.1)
-    B, N = x1.shape[0], x1.shape[-1]
-    lay = ParamLayout(2, 4, 32, 32, 3)
-    params = lay.flatten(sd, DEV)
-    eng = FgnnEngineBF16(lay, 2 * B, N, DEV, block1='generic')
-    x = torch.cat([x1, x2]).contiguous().to(DEV)
-    g0 = torch.zeros_like(params)
-    s0, l0 = eng.step(params, g0, x)
-    torch.cuda.synchronize()
-    s0, l0 = s0.clone(), l0.clone()
-    eng.export_decisions(True)
-    grads = torch.zeros_like(params)
-    scores, loss = eng.step(params, grads, x)
-    torch.cuda.synchronize()
-    assert torch.equal(grads, g0) and torch.equal(scores, s0) and torch.equal(loss, l0)      # the export does not change a bit
-    masks = eng.relu_decisions()
-    assert len(masks) == 4 * 3 * 2
-    idx = eng.idx.to(torch.int64)
-    s64, l64, g64 = OB.step_fwd_bwd(x1, x2, sd, decisions=(masks, idx), dtype=torch.float64, device=DEV)
-    got = lay.unflatten(grads)
+    r = pinned.run_pinned(sd, x1, x2, engine='bf16')      # (the export does not change a bit)
+    assert len(r.masks) == 4 * 3 * 2
+    s64, l64, g64 = pinned.pinned_oracle(r, sd, x1, x2, torch.float64, DEV)
     errs = {}
     for name, g in g64.items():
-        a = got[name].double()
+        a = r.grads[name].double().cpu()
         if is_zero_grad(name):
             continue
         errs[name] = ((a - g.reshape(a.shape)).abs().max() / g.abs().max()).item()
@@ -168,11 +123,11 @@ def test_bf16_gradients_on_the_engines_own_branch():
     yard = {k: rel(d['grad_refbf16/' + k], d['grad64/' + k]) for k in sub(d, 'grad/') if not is_zero_grad(k)}
     worst = max(errs, key=errs.get)
     med, ymed, ymax = float(np.median(list(errs.values()))), float(np.median(list(yard.values()))), max(yard.values())
-    ndec = sum(int(m.numel()) for m in masks.values()) + idx.numel()
+    ndec = sum(int(m.numel()) for m in r.masks.values()) + r.idx.numel()
     print('cfg4 bf16: %d decisions pinned; scores %.2e; worst tensor %s %.2e; median %.2e; loss %.1e | reference bf16 vs fp64: worst %.2e median %.2e'
-          % (ndec, ((scores.double() - s64).abs().max() / s64.abs().max()).item(), worst, errs[worst], med,
-             abs(loss.item() - l64.item()) / abs(l64.item()), ymax, ymed))
-    assert abs(loss.item() - l64.item()) <= 2e-3 * abs(l64.item())
+          % (ndec, ((r.scores.double().cpu() - s64).abs().max() / s64.abs().max()).item(), worst, errs[worst], med,
+             abs(r.loss - l64) / abs(l64), ymax, ymed))
+    assert abs(r.loss - l64) <= 2e-3 * abs(l64)
     # measured (round 6): worst tensor 7.8e-2 = 0.05 x the reference's worst (1.47), median 2.9e-3 = 0.0065 x its median (0.44)
     assert errs[worst] <= 0.2 * ymax, (worst, errs[worst], ymax)
     assert med <= 0.02 * ymed, (med, ymed)

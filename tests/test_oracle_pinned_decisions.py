@@ -1,6 +1,7 @@
 """CPU: oracle/fgnn_oracle_pinned.py (the op sequence of the reference with the ReLU / arg-max decisions as INPUTS) against the
 committed vectors of tests/golden/pinned_decisions.npz and pinned_pin_er_n19_b2_3blk.npz -- the reference's own fp32 and fp64 runs
 with the decisions its forward hooks saw (make_golden.py round5 / pins, where the comparison with the reference is torch.equal)."""
+import numpy as np
 import pytest
 import torch
 
@@ -111,3 +112,74 @@ def test_pinned_oracle_bit_equal_to_reference_live():
             assert torch.equal(i2, idx) and all(torch.equal(m2[k], masks[k]) for k in masks), tag + ': collect_decisions differs'
     finally:
         torch.set_num_threads(threads)
+
+
+def _perturbed_model(num_blocks, depth, seed):
+    torch.manual_seed(seed)
+    sd = O.init_state_dict(num_blocks=num_blocks, depth_of_mlp=depth)
+    g = torch.Generator().manual_seed(seed + 1)
+    return {k: (v + 0.1 * torch.randn(v.shape, generator=g) if (k.endswith('bias') or k.endswith('gn.weight')) else v)
+            for k, v in sd.items()}
+
+
+# the configurations tests/test_gpu_pinned_shapes.py relies on that the committed fixtures (4 and 3 blocks, depth 3, N >= 19) do not cover
+PLAIN_CASES = [(nb, depth, N) for nb, depth, N in ((2, 1, 17), (2, 2, 17), (1, 3, 33), (3, 3, 9), (2, 3, 1), (2, 3, 2), (2, 3, 65),
+                                                   (1, 1, 2), (3, 2, 65))]
+
+
+@pytest.mark.parametrize('tag,dtype,tol', [('f32', torch.float32, 1e-6), ('f64', torch.float64, 1e-13)])
+@pytest.mark.parametrize('nb,depth,N', PLAIN_CASES, ids=['%dblk-depth%d-N%d' % c for c in PLAIN_CASES])
+def test_pinned_oracle_on_the_plain_oracles_decisions(nb, depth, N, tag, dtype, tol):
+    """Fed the plain oracle's own decisions (collect_decisions), the pinned oracle IS the plain oracle -- at depth 1 and 2 (no / one
+    hidden ReLU per MLP), with 1 and 3 blocks, at N = 1, 2 (zero variance, gradients zero by symmetry) and 65, in both precisions."""
+    from graph_neural_net_amd import synthetic
+    sd = {k: v.to(dtype) for k, v in _perturbed_model(nb, depth, 10 * nb + depth).items()}
+    x1, x2 = synthetic.make_batch(300 + N, 2, N, 'ErdosRenyi', 0.3, 0.1)
+    x1, x2 = x1.to(dtype), x2.to(dtype)
+    masks, idx = OP.collect_decisions(torch.cat([x1, x2]), sd)
+    assert len(masks) == nb * 3 * (depth - 1)
+    s, l, g = OP.step_fwd_bwd_pinned(x1, x2, sd, masks, idx, dtype=dtype)
+    s0, l0, g0 = O.step_fwd_bwd(x1, x2, sd)
+    assert rel(s, s0) <= tol and abs(l.item() - l0.item()) <= tol * abs(l0.item()) + tol ** 2
+    assert sorted(g) == sorted(g0)
+    for k in g0:
+        assert rel(g[k], g0[k]) <= tol, (k, rel(g[k], g0[k]))
+
+
+@pytest.mark.parametrize('tag,dtype,tol', [('f32', torch.float32, 1e-6), ('f64', torch.float64, 1e-13)])
+@pytest.mark.parametrize('depth', [1, 2, 3])
+def test_ragged_pinned_oracle_with_single_vertex_graphs(depth, tag, dtype, tol):
+    """The ragged form on a batch with n = 1, n = Nmax and a size-0 filler pair (skipped: no scores, nothing in the loss), fed the
+    per-graph decisions of the plain oracle: equal to the plain oracle's ragged step on the live pairs."""
+    from graph_neural_net_amd import synthetic
+    sd = {k: v.to(dtype) for k, v in _perturbed_model(2, depth, 50 + depth).items()}
+    rng = np.random.default_rng(depth)
+    sizes = [1, 12, 0, 5, 1]
+    xs, ys = [], []
+    for n in sizes:
+        a, b = synthetic.make_pair(rng, max(n, 1), 'ErdosRenyi', 0.4, 0.1)
+        xs.append(torch.from_numpy(a).to(dtype)[:, :n, :n])
+        ys.append(torch.from_numpy(b).to(dtype)[:, :n, :n])
+    nmax, B = max(sizes), len(sizes)
+    pad = lambda lst: torch.stack([torch.nn.functional.pad(t, (0, nmax - t.shape[-1], 0, nmax - t.shape[-1])) for t in lst])
+    x1, x2 = pad(xs), pad(ys)
+    masks = {}
+    idx = torch.zeros(2 * B, 32, nmax, dtype=torch.int64)
+    for b, (a, c) in enumerate(zip(xs, ys)):
+        n = sizes[b]
+        if n == 0:
+            continue
+        for gi, t in ((b, a), (B + b, c)):
+            m, i = OP.collect_decisions(t.unsqueeze(0), sd)
+            for k, v in m.items():
+                masks.setdefault(k, torch.zeros(2 * B, 32, nmax, nmax, dtype=torch.bool))[gi, :, :n, :n] = v[0]
+            idx[gi, :, :n] = i[0]
+    s, l, g = OP.step_fwd_bwd_pinned_ragged(x1, x2, sizes, sd, masks, idx, dtype=dtype)
+    live = [b for b, n in enumerate(sizes) if n]
+    s0, l0, g0 = O.step_fwd_bwd_ragged([xs[b] for b in live], [ys[b] for b in live], sd)
+    assert s[2].shape == (0, 0)
+    assert abs(l.item() - l0.item()) <= tol * abs(l0.item())
+    for a, b in zip([s[b] for b in live], s0):
+        assert rel(a, b) <= tol
+    for k in g0:
+        assert rel(g[k], g0[k]) <= tol, (k, rel(g[k], g0[k]))
