@@ -18,6 +18,7 @@ FGNN_TILE = 32
 FGNN_MAX_DEPTH = 3
 FGNN_RANGE_WG = 256          # include/fgnn_hip.h
 FGNN_LSAP_MAX_N = 2048       # include/fgnn_hip.h: largest graph of fgnn_lsap_accuracy
+FGNN_QAP_MAX_N = 256         # include/fgnn_hip.h: largest graph of the fgnn_qap_* / fgnn_greedy_qap kernels
 FGNN_SCORE_SPLIT = 4
 
 c_float_p = C.c_void_p   # device pointers travel as integers
@@ -234,6 +235,10 @@ _SIGNATURES = {
     'fgnn_lsap_accuracy': [_VP, _LL, _I, _VP, _I, _I, _VP, _VP, _VP],
     'fgnn_pairgen_supported': [_I, _I, _I],
     'fgnn_pairgen': [C.POINTER(PairgenArgs), _VP],
+    'fgnn_qap_objective': [_VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP],
+    'fgnn_qap_improve_cost': [_VP, _VP, _VP, _VP, _I, _I, _VP, _LL, _I, _VP],
+    'fgnn_greedy_qap_ws_bytes': [_I, _I],
+    'fgnn_greedy_qap': [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
     # ---- bf16 path ----
     'fgnn_tiles_per_graph16': [_I, _I],
     'fgnn_to_bf16': [_VP, _VP, _I, _I, _I, _I, _VP, _LL, _LL, _VP],
@@ -259,7 +264,7 @@ _SIGNATURES = {
     'fgnn_mlp_bwd16': [C.POINTER(MlpBwd16Args), _VP],
     'fgnn_mlp_bwd16_pair': [C.POINTER(MlpBwd16Args), C.POINTER(MlpBwd16Args), _VP],
 }
-_RESTYPES = {'fgnn_last_error': C.c_char_p, 'fgnn_block1_struct_ws_floats': C.c_longlong}
+_RESTYPES = {'fgnn_last_error': C.c_char_p, 'fgnn_block1_struct_ws_floats': C.c_longlong, 'fgnn_greedy_qap_ws_bytes': C.c_longlong}
 EXPORTS = tuple(_SIGNATURES)
 
 _lib = None

@@ -48,17 +48,26 @@ def accuracy_linear_assignment(rawscores, aggregate_score=True):
     s = s.detach()
     if not s.is_cuda or s.shape[-1] > _lib.FGNN_LSAP_MAX_N:
         return _accuracy_lsap_host(s, sizes, aggregate_score)
+    correct, _ = lsap_device(s, nvalid)
+    if aggregate_score:
+        return int(correct.sum().item()), int(sizes.sum().item())
+    return (correct.to(torch.float64) / sizes.to(torch.float64).to(correct.device)).tolist()
+
+
+def lsap_device(s, nvalid=None, want_assign=False):
+    """The device route of accuracy_linear_assignment, shared with qap.all_acc_qap: s (B, N, N) raw scores on the GPU, nvalid the
+    vertex counts or None -> (correct (B,) int32, assign (B, N) int32 or None): -log_softmax over the valid columns, then SciPy's
+    assignment by fgnn_lsap_accuracy.  Nothing is copied to the host."""
     if nvalid is not None:          # padding columns must not take part in the row softmax
         col = torch.arange(s.shape[-1], device=s.device)[None, None, :] < nvalid.to(s.device)[:, None, None]
         s = s.masked_fill(~col, float('-inf'))
     cost = (-torch.log_softmax(s.float(), -1)).contiguous()
     B, N, _ = cost.shape
     correct = torch.empty(B, dtype=torch.int32, device=s.device)
+    assign = torch.empty(B, N, dtype=torch.int32, device=s.device) if want_assign else None
     nv32 = nvalid.to(device=s.device, dtype=torch.int32).contiguous() if nvalid is not None else None
-    _lib.call('fgnn_lsap_accuracy', _lib.ptr(cost), N * N, N, _lib.ptr(nv32), B, N, _lib.ptr(correct), None, _lib.stream_ptr())
-    if aggregate_score:
-        return int(correct.sum().item()), int(sizes.sum().item())
-    return (correct.to(torch.float64) / sizes.to(torch.float64).to(correct.device)).tolist()
+    _lib.call('fgnn_lsap_accuracy', _lib.ptr(cost), N * N, N, _lib.ptr(nv32), B, N, _lib.ptr(correct), _lib.ptr(assign), _lib.stream_ptr())
+    return correct, assign
 
 
 def _accuracy_lsap_host(s, sizes, aggregate_score):

@@ -1,0 +1,244 @@
+"""Decoding and scoring a matching (toolbox/metrics.py:168-193 ``all_acc_qap``; toolbox/utils.py:225-256 ``perm_matrix``, ``score``,
+``improve``, ``greedy_qap``) on the device, through ``csrc/qap.hip``.
+
+With pi(i) the column matched to row i and P[i, pi(i)] = 1:
+
+* ``qap_objective``: qap = sum_{i,k} A[i,k] B[pi(i),pi(k)] (``all_acc_qap``'s qap), planted = sum A * B, na = sum A, nb = sum B;
+* ``greedy_qap``: the reference's refinement loop.  One round solves the assignment problem with cost ``-A P B`` (``improve``) and
+  scores the new matching by ``trace(A P B P^T) / 2`` (``score``).  The reference's order of events is kept, its quirk included:
+  ``s_best`` starts as the score of the INITIAL matching; ``acc_best`` (fixed points) and ``T_best = 0`` start from a first
+  ``improve`` whose matching is never scored; rounds i = 0 .. T-1 then improve once more, score, and keep (s, acc, i) when strictly
+  better.  So where no round improves, ``s_best`` is the initial score while ``acc_best`` counts the fixed points of a matching
+  that was never scored.  ``perm`` (not in the reference, which returns no matching) is the matching whose score IS ``s_best``:
+  the initial one where no round improved -- ``acc_best`` then does NOT describe ``perm`` -- else the matching of round ``T_best``;
+* ``all_acc_qap``: the Hungarian matching of -log_softmax(scores) (the route of ``metrics.accuracy_linear_assignment``), its fixed
+  points, its qap and the planted objective, per pair.
+
+On 0/1 adjacency all of this is integer arithmetic ((A P B)[i, j] is a popcount of two bit rows), so the device results equal the
+reference's exactly.  ``adj1`` / ``adj2`` are bit words ((B, N, ceil(N/32)) int32, the layout of ``synthetic.pack_adjacency`` and
+``PairGenerator.bits``) or the dense (B, 2, N, N) float batches the loaders yield, which are bit-packed -- and verified to be
+tensor representations -- on the device.  Results stay on the device: with bit words nothing synchronises; with dense input the one
+read of the verdict flag, after the last launch is queued, is the only synchronisation.
+
+Host route (the split ``metrics.py`` makes): tensors that are not on the GPU, and graphs beyond FGNN_QAP_MAX_N = 256 vertices,
+run a numpy + SciPy loop over the pairs, the same arithmetic in integers.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from .metrics import lsap_device
+
+NOT_A_REPRESENTATION = ('the batch is NOT the tensor representation of a 0/1 adjacency (channel 0 in {0, 1}, channel 1 = '
+                        'diag(row sums), loaders/data_generator.py:118-125)')
+
+
+# ---------------------------------------------------------------------------------------------------------------- device route
+def to_bits(adj, nvalid=None, flag=None):
+    """adj -> (B, N, ceil(N/32)) int32 bit words on adj's device.  Bit words pass through; a dense (B, 2, N, N) batch is packed by
+    fgnn_pack_adjacency_ld, its verdict OR-ed into `flag` (1-element int32 device tensor; the caller reads it, see `raise_if_bad`)."""
+    if adj.dim() == 3 and adj.dtype == torch.int32:
+        if adj.shape[2] != (adj.shape[1] + 31) // 32:
+            raise RuntimeError('qap: expected (B, N, ceil(N/32)) bit words, got %s' % (tuple(adj.shape),))
+        return adj.contiguous()
+    if adj.dim() != 4 or adj.shape[1] != 2 or adj.shape[2] != adj.shape[3] or not adj.is_floating_point():
+        raise RuntimeError('qap: %s (got %s %s)' % (NOT_A_REPRESENTATION, tuple(adj.shape), adj.dtype))
+    x = adj.detach().float().contiguous()
+    G, n = x.shape[0], x.shape[-1]
+    bits = torch.empty(G, n, (n + 31) // 32, dtype=torch.int32, device=x.device)
+    _lib.call('fgnn_pack_adjacency_ld', _lib.ptr(x), _lib.ptr(nvalid), G, n, n, _lib.ptr(bits), _lib.ptr(flag), _lib.stream_ptr())
+    return bits
+
+
+def raise_if_bad(flag):
+    if int(flag.item()) != 0:               # (the one host synchronisation of a dense-input call)
+        raise RuntimeError('qap: ' + NOT_A_REPRESENTATION)
+
+
+def _nv32(nvalid, dev):
+    return nvalid.to(device=dev, dtype=torch.int32).contiguous() if nvalid is not None else None
+
+
+def _device_inputs(adj1, adj2, nvalid):
+    """-> (bits1, bits2, nv32, flag or None) with everything queued on the current stream."""
+    dev = adj1.device
+    nv = _nv32(nvalid, dev)
+    dense = adj1.dim() == 4 or adj2.dim() == 4
+    flag = torch.zeros(1, dtype=torch.int32, device=dev) if dense else None
+    b1, b2 = to_bits(adj1, nv, flag), to_bits(adj2, nv, flag)
+    if b1.shape != b2.shape:
+        raise RuntimeError('qap: the two sides differ in shape: %s / %s' % (tuple(b1.shape), tuple(b2.shape)))
+    return b1, b2, nv, flag
+
+
+def _on_host(adj1, n):
+    return not adj1.is_cuda or n > _lib.FGNN_QAP_MAX_N
+
+
+def objective_bits(b1, b2, assign, nv):
+    """fgnn_qap_objective on bit words -> dict of (B,) int64 device tensors; never synchronises."""
+    B, N, _ = b1.shape
+    a = assign.to(dtype=torch.int32).contiguous()
+    out = torch.empty(4, B, dtype=torch.int32, device=b1.device)
+    _lib.call('fgnn_qap_objective', _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(a), _lib.ptr(nv), B, N, _lib.ptr(out[0]), _lib.ptr(out[1]),
+              _lib.ptr(out[2]), _lib.ptr(out[3]), _lib.stream_ptr())
+    out = out.to(torch.int64)
+    return {'qap': out[0], 'planted': out[1], 'na': out[2], 'nb': out[3]}
+
+
+def greedy_bits(b1, b2, assign, T, nv):
+    """fgnn_greedy_qap on bit words -> the dict of `greedy_qap`; never synchronises."""
+    B, N, _ = b1.shape
+    dev = b1.device
+    a = assign.to(dtype=torch.int32).contiguous()
+    nbytes = _lib.load().fgnn_greedy_qap_ws_bytes(B, N)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(3, B, dtype=torch.int32, device=dev)
+    perm = torch.empty(B, N, dtype=torch.int32, device=dev)
+    sums = torch.empty(2, B, dtype=torch.int32, device=dev)
+    _lib.call('fgnn_greedy_qap', _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(a), _lib.ptr(nv), B, N, int(T), _lib.ptr(ws), nbytes,
+              _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.ptr(perm), _lib.stream_ptr())
+    _lib.call('fgnn_qap_objective', _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(a), _lib.ptr(nv), B, N, None, None, _lib.ptr(sums[0]),
+              _lib.ptr(sums[1]), _lib.stream_ptr())
+    return {'s_best': out[0].to(torch.float64) / 2, 'na': sums[0].to(torch.float64) / 2, 'nb': sums[1].to(torch.float64) / 2,
+            'acc_best': out[1].to(torch.int64), 'T_best': out[2].to(torch.int64), 'perm': perm}
+
+
+def qap_objective(adj1, adj2, assign, nvalid=None):
+    """Per pair: qap = sum_{i,k} A[i,k] B[pi(i),pi(k)] (-1 where `assign` holds no column inside the valid corner: the solver found
+    no finite matching), planted = sum A * B, na = sum A, nb = sum B -> dict of (B,) int64 tensors on the inputs' device."""
+    if _on_host(adj1, adj1.shape[-2]):
+        return _objective_host(adj1, adj2, assign, nvalid)
+    b1, b2, nv, flag = _device_inputs(adj1, adj2, nvalid)
+    out = objective_bits(b1, b2, assign, nv)
+    if flag is not None:
+        raise_if_bad(flag)
+    return out
+
+
+def greedy_qap(adj1, adj2, assign, T=10, nvalid=None):
+    """The reference's greedy_qap(A, B, perm_matrix(arange, assign), T) for every pair of the batch (see the module docstring for
+    the order of events and its quirk) -> dict of (B,) tensors: s_best, na, nb (float64; na / nb the halved sums, as score() returns
+    them), acc_best, T_best (int64), and perm (B, N) int32, the matching whose score is s_best (-1 in the padding).  Where no round
+    improved on the initial score, perm is `assign` and acc_best -- the fixed points of a matching that was never scored -- does NOT
+    describe it.  The device route is one chain of launches (4 per round) without a host round trip: it can be captured."""
+    if T < 0:
+        raise ValueError('T must be >= 0, got %r' % (T,))
+    if _on_host(adj1, adj1.shape[-2]):
+        return _greedy_host(adj1, adj2, assign, T, nvalid)
+    b1, b2, nv, flag = _device_inputs(adj1, adj2, nvalid)
+    out = greedy_bits(b1, b2, assign, T, nv)
+    if flag is not None:
+        raise_if_bad(flag)
+    return out
+
+
+def all_acc_qap(scores, adj1, adj2, nvalid=None):
+    """toolbox/metrics.py:168-193 per pair: (acc, qap, planted) as (B,) int64 tensors on the scores' device -- the fixed points of the
+    Hungarian matching of -log_softmax(scores), sum(g1 * g2[col][:, col]) and sum(g1 * g2)."""
+    scores = scores.detach()
+    if _on_host(scores, scores.shape[-1]) or not adj1.is_cuda:
+        return _all_acc_qap_host(scores, adj1, adj2, nvalid)
+    b1, b2, nv, flag = _device_inputs(adj1, adj2, nvalid)
+    correct, assign = lsap_device(scores, nv, want_assign=True)
+    out = objective_bits(b1, b2, assign, nv)
+    if flag is not None:
+        raise_if_bad(flag)
+    return correct.to(torch.int64), out['qap'], out['planted']
+
+
+# ------------------------------------------------------------------------------------------------------------------ host route
+def _adjacency_host(adj, sizes):
+    """-> list of (n_b, n_b) int64 0/1 numpy matrices, from bit words or from a dense tensor representation (verified here)."""
+    a = adj.detach().cpu()
+    if a.dim() == 3 and a.dtype == torch.int32:
+        words = a.numpy().view(np.uint32)
+        full = np.unpackbits(words.view(np.uint8), axis=-1, bitorder='little')          # (B, N, 32 W): bit j of row i
+        return [full[b, :n, :n].astype(np.int64) for b, n in enumerate(sizes)]
+    if a.dim() != 4 or a.shape[1] != 2 or a.shape[2] != a.shape[3] or not a.is_floating_point():
+        raise RuntimeError('qap: %s (got %s %s)' % (NOT_A_REPRESENTATION, tuple(a.shape), a.dtype))
+    x = a.double().numpy()
+    out = []
+    for b, n in enumerate(sizes):
+        w, d = x[b, 0, :n, :n], x[b, 1, :n, :n]
+        if not (np.isin(w, (0.0, 1.0)).all() and np.array_equal(d, np.diag(w.sum(1)))):
+            raise RuntimeError('qap: ' + NOT_A_REPRESENTATION)
+        out.append(w.astype(np.int64))
+    return out
+
+
+def _sizes(nvalid, B, N):
+    return [N] * B if nvalid is None else [min(max(int(n), 0), N) for n in nvalid.tolist()]
+
+
+def _qap_of(A, Bm, pi):
+    return int((A * Bm[np.ix_(pi, pi)]).sum())                     # sum_{i,k} A[i,k] B[pi(i),pi(k)]
+
+
+def _score2(A, Bm, pi):
+    return int((A * Bm[np.ix_(pi, pi)].T).sum())                   # trace(A P B P^T) = sum_{i,k} A[i,k] B[pi(k),pi(i)]
+
+
+def _improve(A, Bm, pi):
+    from scipy.optimize import linear_sum_assignment
+    _, cols = linear_sum_assignment(-(A @ Bm[pi, :]).astype(np.float64))      # (A P B)[i, j] = sum_k A[i,k] B[pi(k), j]
+    return cols, int((cols == np.arange(len(cols))).sum())
+
+
+def _objective_host(adj1, adj2, assign, nvalid):
+    B, N = adj1.shape[0], adj1.shape[-2]
+    sizes = _sizes(nvalid, B, N)
+    As, Bs = _adjacency_host(adj1, sizes), _adjacency_host(adj2, sizes)
+    pis = assign.detach().cpu().numpy()
+    out = np.zeros((4, B), dtype=np.int64)
+    for b, n in enumerate(sizes):
+        pi = pis[b, :n]
+        ok = bool(((pi >= 0) & (pi < n)).all())
+        out[:, b] = (_qap_of(As[b], Bs[b], pi) if ok else -1, int((As[b] * Bs[b]).sum()), int(As[b].sum()), int(Bs[b].sum()))
+    t = torch.from_numpy(out)
+    return {'qap': t[0], 'planted': t[1], 'na': t[2], 'nb': t[3]}
+
+
+def _greedy_host(adj1, adj2, assign, T, nvalid):
+    B, N = adj1.shape[0], adj1.shape[-2]
+    sizes = _sizes(nvalid, B, N)
+    As, Bs = _adjacency_host(adj1, sizes), _adjacency_host(adj2, sizes)
+    pis = assign.detach().cpu().numpy()
+    s2, acc_b, t_b = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
+    na, nb = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
+    perm = np.full((B, N), -1, dtype=np.int32)
+    for b, n in enumerate(sizes):
+        A, Bm, pi0 = As[b], Bs[b], pis[b, :n].astype(np.int64)
+        na[b], nb[b] = A.sum(), Bm.sum()
+        perm[b, :n] = pi0
+        if n == 0:
+            continue
+        if not ((pi0 >= 0) & (pi0 < n)).all():
+            raise RuntimeError('greedy_qap: pair %d starts from an incomplete matching' % b)
+        best = _score2(A, Bm, pi0)                                 # of the INITIAL matching
+        pi, acc_best = _improve(A, Bm, pi0)                        # ... while this one is never scored
+        t_best = 0
+        for i in range(T):
+            pi, acc = _improve(A, Bm, pi)
+            s = _score2(A, Bm, pi)
+            if s > best:
+                best, acc_best, t_best = s, acc, i
+                perm[b, :n] = pi
+        s2[b], acc_b[b], t_b[b] = best, acc_best, t_best
+    return {'s_best': torch.from_numpy(s2).to(torch.float64) / 2, 'na': torch.from_numpy(na).to(torch.float64) / 2,
+            'nb': torch.from_numpy(nb).to(torch.float64) / 2, 'acc_best': torch.from_numpy(acc_b), 'T_best': torch.from_numpy(t_b),
+            'perm': torch.from_numpy(perm)}
+
+
+def _all_acc_qap_host(scores, adj1, adj2, nvalid):
+    from scipy.optimize import linear_sum_assignment
+    B, N = scores.shape[0], scores.shape[-1]
+    sizes = _sizes(nvalid, B, N)
+    As, Bs = _adjacency_host(adj1, sizes), _adjacency_host(adj2, sizes)
+    out = np.zeros((3, B), dtype=np.int64)
+    for b, n in enumerate(sizes):
+        cost = -torch.log_softmax(scores[b, :n, :n].float(), -1).cpu().numpy()
+        _, cols = linear_sum_assignment(cost)
+        out[:, b] = (int((cols == np.arange(n)).sum()), _qap_of(As[b], Bs[b], cols), int((As[b] * Bs[b]).sum()))
+    t = torch.from_numpy(out)
+    return t[0], t[1], t[2]

@@ -11,10 +11,10 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, qap
 from .blocks import block, block_emb, node_embedding
 from .losses import triplet_loss
-from .metrics import accuracy_linear_assignment, accuracy_max
+from .metrics import accuracy_linear_assignment, accuracy_max, lsap_device
 from .masked import MaskedTensor
 from .network import Network
 
@@ -126,6 +126,33 @@ class Siamese_Node_Exp(nn.Module):
         if ragged:
             return MaskedTensor(scores, nvalid, (1, 2), x1.base_name)
         return scores
+
+    def match(self, x1, x2, refine=0):
+        """Decode a batch: the eager forward under no_grad (no `.grad` is touched), the Hungarian matching of -log_softmax(scores)
+        and the reference's evaluation of it (toolbox/metrics.py:168-193 all_acc_qap), all on the device (qap.py).  Takes what
+        `forward` takes.  Returns a dict: scores ((bs, n, n) tensor or MaskedTensor), assign ((bs, n) int32: the matched column of
+        every row, -1 in the padding), and per pair acc (fixed points of the matching), qap, planted (int64).  refine=T > 0 adds the
+        outputs of qap.greedy_qap(T) started from `assign`: s_best, na, nb, acc_best, T_best, perm (see its docstring for the
+        reference's quirk: acc_best need not describe perm).  The batch must be a tensor representation -- channel 0 the 0/1
+        adjacency -- whatever input_form the model was built with; it is verified on the device, and the one read of that verdict,
+        after everything is queued, is the only host synchronisation."""
+        a1, a2 = _unwrap_input(x1), _unwrap_input(x2)
+        with torch.no_grad():
+            scores = self(a1, a2)
+            ragged = isinstance(scores, MaskedTensor)
+            t1, t2 = (a1.tensor.rename(None), a2.tensor.rename(None)) if ragged else (a1, a2)
+            s = scores.tensor.rename(None) if ragged else scores
+            dev = s.device
+            nv = a1.nvalid.to(device=dev, dtype=torch.int32).contiguous() if ragged else None
+            flag = torch.zeros(1, dtype=torch.int32, device=dev)
+            b1, b2 = qap.to_bits(t1, nv, flag), qap.to_bits(t2, nv, flag)
+            correct, assign = lsap_device(s, nv, want_assign=True)
+            obj = qap.objective_bits(b1, b2, assign, nv)
+            out = {'scores': scores, 'assign': assign, 'acc': correct.to(torch.int64), 'qap': obj['qap'], 'planted': obj['planted']}
+            if refine:
+                out.update(qap.greedy_bits(b1, b2, assign, int(refine), nv))
+        self._raise_if_not_representation({'flag': flag})
+        return out
 
     def fused_step(self, x1, x2, capture=True, metric=False):
         """Forward of both branches + scoring + `triplet_loss` + the full backward (+ the step's metric, models/trainers.py:70-76)

@@ -727,6 +727,38 @@ typedef struct {
 int fgnn_pairgen_supported(int N, int family, int noise_model);
 int fgnn_pairgen(const fgnn_pairgen_args *args, void *stream);
 
+/* ---- decoding a matching: QAP objective and greedy refinement (csrc/qap.hip; toolbox/metrics.py:168-193 all_acc_qap,
+ * toolbox/utils.py:225-256 perm_matrix / score / improve / greedy_qap) --------------------------------------------------------
+ * bits1 / bits2: (B, N, ceil(N/32)) words, bit j of word row i = A[i][j] resp. B[i][j] (the layout of fgnn_expand_adjacency).
+ * nvalid (optional, int32[B]): pair b is the n_b x n_b corner (n_b clamped to [0, N]); bits outside it are ignored, they need not
+ * be zero.  assign: (B, N) int32, the matched column pi(i) of row i, as fgnn_lsap_accuracy writes it; entries outside [0, n_b) (the
+ * -1 of an infeasible pair) contribute nothing; the entries inside the corner must be distinct.  On 0/1 matrices everything here is
+ * integer arithmetic, so every output is exact.  N <= FGNN_QAP_MAX_N; no entry point copies to the host or synchronises.
+ *
+ * fgnn_qap_objective, per pair, int32, every output optional:
+ *   qap[b]     = sum_{i,k} A[i,k] B[pi(i),pi(k)]  (all_acc_qap's qap; = trace(A P B P^T) = 2 x the first value of score() whenever
+ *                A or B is symmetric); -1 if an assign entry of the corner is outside [0, n_b)
+ *   planted[b] = sum_{i,k} A[i,k] B[i,k],  na[b] = sum A,  nb[b] = sum B  (score() returns na / 2 and nb / 2)
+ * fgnn_qap_improve_cost: cost[b][i][j] = -(sum_k A[i,k] B[pi(k),j]) = (-A P B)[i][j] of improve() with P[i,pi(i)] = 1, fp32 (exact:
+ *   |value| <= 256), for ANY 0/1 matrices (no symmetry assumed), written to the n_b x n_b corner of the layout fgnn_lsap_accuracy
+ *   reads: row pitch ld >= N, pairs bstride >= N ld apart; nothing outside the corner is written.
+ * fgnn_greedy_qap: greedy_qap(A, B, P(assign0), T) for every pair as a chain of launches on `stream` (per round: improve cost ->
+ *   the solver of fgnn_lsap_accuracy -> objective -> keep if strictly better), scratch from ws (fgnn_greedy_qap_ws_bytes bytes,
+ *   16-byte aligned): no allocation, capturable.  The reference's order of events is kept, its quirk included: s_best starts as the
+ *   score of the INITIAL matching, acc_best / T_best = 0 start from the first improve() whose matching is never scored, rounds
+ *   i = 0 .. T-1 score improve()'s next matching (as trace(A P B P^T)) and keep it when strictly better.  Outputs, int32: s_best2 =
+ *   2 s_best, acc_best, t_best, and perm_best (B, N; optional; not in the reference) = the matching whose score is s_best: assign0
+ *   where no round improved -- acc_best then does NOT describe perm_best -- else the matching of round t_best; -1 in the padding.
+ *   A pair with n_b = 0 yields zeros. */
+#define FGNN_QAP_MAX_N 256
+int fgnn_qap_objective(const unsigned *bits1, const unsigned *bits2, const int *assign, const int *nvalid, int B, int N, int *qap,
+                       int *planted, int *na, int *nb, void *stream);
+int fgnn_qap_improve_cost(const unsigned *bits1, const unsigned *bits2, const int *assign, const int *nvalid, int B, int N, float *cost,
+                          long long bstride, int ld, void *stream);
+long long fgnn_greedy_qap_ws_bytes(int B, int N);
+int fgnn_greedy_qap(const unsigned *bits1, const unsigned *bits2, const int *assign0, const int *nvalid, int B, int N, int T, void *ws,
+                    long long ws_bytes, int *s_best2, int *acc_best, int *t_best, int *perm_best /* optional */, void *stream);
+
 /* ---- test-only entry points (never on the product path; tests/ and tools/ call them) ---------------------------------------
  * fgnn_debug_mlp_fwd_masks / fgnn_debug_mlp_fwd_x3_masks: fgnn_mlp_fwd / fgnn_mlp_fwd_x3 once more -- the same tile code, the same
  * outputs, bit for bit -- that ALSO exports the ReLU decisions of the conv chain (models/layers.py:129-130), the input of the
