@@ -19,6 +19,7 @@ import os
 import torch
 
 from . import _lib
+from .engine_base import EngineBase
 
 EPS = 1e-05
 
@@ -154,7 +155,7 @@ class EngineCache:
         return [e for e, _ in self._items.values()]
 
 
-class FgnnEngine:
+class FgnnEngine(EngineBase):
     """Workspace + launch sequence for a fixed (G, N) problem on the current device."""
     SKIP_PADDING_TILES = True     # ragged engines: fgnn_ragged_tile_ranges + tile skipping in fgnn_mlp_fwd / fgnn_mlp_bwd
     MM_ORDER = True               # ragged engines: longest-job-first order of the whole-matrix per-channel products
@@ -172,6 +173,7 @@ class FgnnEngine:
     # dense-input step); 'structured' = csrc/block1_struct.hip (class tables, closed-form product, class sums in the backward:
     # same function, results equal to fp32 rounding).  FGNN_BLOCK1 overrides the default.
     BLOCK1 = os.environ.get('FGNN_BLOCK1', 'generic')
+    GN_FINALIZE = ('fgnn_gn_finalize', 'fgnn_gn_finalize2')      # EngineBase._gn_finalize: one MLP / two MLPs
 
     def __init__(self, layout, G, N, device, ragged=False, cu_share=0, mfma=None, block1=None):
         """cu_share=2: the persistent MLP kernels take half of the CUs (fgnn_mlp_fwd_args.cu_share), for engines that run
@@ -192,47 +194,28 @@ class FgnnEngine:
         # the structured block 1 applies to bit-packed inputs (embed(bits=...)), constant-size or ragged, N <= 256; anything else runs generic
         self.struct1 = (block1 == 'structured' and cu_share == 0
                         and bool(_lib.load().fgnn_block1_struct_supported(N, layout.depth, layout.c0)))
-        self._struct = None
-        self.decisions = None       # test-only, see export_decisions()
-        self.layout = layout
-        self.G, self.N = G, N
+        super().__init__(layout, G, N, device, ragged)
         self.P = N * N
         self.ldp = _round_up(self.P, 32)
         self.tpg = _lib.tiles_per_graph(N)
-        self.device = device
+        self._gn_args = (EPS,)      # EngineBase._gn_finalize: what its entry points take between N and the records
         K = layout.num_blocks
         f32 = dict(dtype=torch.float32, device=device)
-        act = lambda: torch.empty(G * 32 * self.ldp, **f32)
+        self._act = act = lambda: torch.empty(G * 32 * self.ldp, **f32)
         self.z = {(k, j): act() for k in range(1, K + 1) for j in (1, 2, 3)}
         self.mult = {k: act() for k in range(1, K + 1)}
-        self.nrm = {(k, j): torch.empty(G * 32 * 4, **f32) for k in range(1, K + 1) for j in (1, 2, 3)}
         # tile statistics of the forward MLP kernels: one record per 32-pixel tile
         self.part = [torch.empty(G * self.tpg * 32 * 2, **f32) for _ in range(2)]
         self.cnt = torch.empty(G * 2 * self.tpg, **f32)
-        self.E = torch.empty(G, 32, N, **f32)
-        self.idx = torch.empty(G, 32, N, dtype=torch.int32, device=device)
-        self.B = G // 2
-        self.scores = torch.empty(self.B, N, N, **f32)
-        self.lse = torch.empty(self.B, N, **f32)
-        self.score_blocks = _lib.load().fgnn_score_row_blocks(self.B, N)      # row blocks per pair of the scoring kernel
-        self.pair_loss = torch.empty(self.B * self.score_blocks, **f32)
-        self.loss = torch.empty(1, **f32)
-        self.nvalid = torch.empty(G, dtype=torch.int32, device=device) if ragged else None
-        self._nvalid_own = self.nvalid      # the engine's own buffer; an int32 device tensor handed in is used in place (no copy launch)
-        # ragged batches: work-balanced tile ranges of the MLP kernels (padding-only tiles are stepped over)
-        self.ranges = (torch.empty(_lib.FGNN_RANGE_WG + 1, dtype=torch.int32, device=device)
-                       if ragged and self.SKIP_PADDING_TILES else None)
-        # ... and the largest-graph-first workgroup order of the whole-matrix per-channel products (64 < N <= 256), written
-        # by the same launch
+        # ragged batches: the largest-graph-first workgroup order of the whole-matrix per-channel products (64 < N <= 256), written
+        # by the launch that writes the tile ranges
         self.mm_order = (torch.empty(G, dtype=torch.int32, device=device)
                          if self.ranges is not None and self.MM_ORDER and 64 < N <= 256 else None)
-        # backward workspace (allocated lazily)
-        self._bwd = None
         self.x = None
-        self.xbits = None         # bit-packed adjacency input (embed(..., bits=...)) and its row sums
-        self.xdeg = None
+        self.xdeg = None          # row sums of a bit-packed adjacency input (embed(..., bits=...))
         # LDS operand images of every MLP launch, re-packed once per step (fgnn_pack_operands)
         self._packs = {}
+        self._pack_entry = 'fgnn_pack_x3_operands' if self.x3 else 'fgnn_pack_operands'      # EngineBase.pack_operands
         for k in range(1, K + 1):
             cin = layout.c0 if k == 1 else 32
             # image kinds: 0 / 1 = forward / backward image of the kernel set in use; with x3, kind + 2 = an fp32-MFMA image
@@ -263,12 +246,6 @@ class FgnnEngine:
         """mlp3 backward of a block on the 16-pixel-tile kernel (fgnn_mlp_bwd_t16): depth 3, input [mult ; 32 or 2 channels]"""
         return self._t16('bwd') and not self.x3 and self.layout.depth == 3 and cin in (2, 32) and self.N <= 256
 
-    def _nv(self):
-        return _lib.ptr(self.nvalid) if self.nvalid is not None else None
-
-    def _w(self, params, off):
-        return params.data_ptr() + 4 * off
-
     def _slab_in(self, k, params):
         """Input slab of block k: raw x for k == 1, else block k-1's mlp3 output (normalise on load)."""
         if k == 1:
@@ -290,30 +267,6 @@ class FgnnEngine:
 
     def _slab_raw(self, t):
         return _lib.make_slab(t, 32 * self.ldp, self.ldp, 32)
-
-    def pack_operands(self, params):
-        """Pack the LDS operand images of all MLP launches of one step (one small launch)."""
-        L = self.layout
-        self._pack_launch(params, list(self._packs.items()), 'fgnn_pack_x3_operands' if self.x3 else 'fgnn_pack_operands')
-
-    def _pack_jobs(self, params, chunk):
-        L = self.layout
-        jobs = (_lib.PackJob * len(chunk))()
-        for i, ((kind, k, which), (knd, ca, cb, nmlp, buf)) in enumerate(chunk):
-            jobs[i].kind, jobs[i].ca, jobs[i].cb, jobs[i].depth, jobs[i].nmlp = knd, ca, cb, L.depth, nmlp
-            js = (1, 2) if which == 12 else (which,)
-            for m, j in enumerate(js):
-                rec = L.mlp[(k, j)]
-                for l in range(L.depth):
-                    jobs[i].W[m][l] = self._w(params, rec['w'][l])
-                    jobs[i].bias[m][l] = self._w(params, rec['b'][l])
-            jobs[i].out = buf.data_ptr()
-        return jobs
-
-    def _pack_launch(self, params, items, entry):
-        for lo in range(0, len(items), _lib.MAX_PACK_JOBS):
-            chunk = items[lo:lo + _lib.MAX_PACK_JOBS]
-            _lib.call(entry, self._pack_jobs(params, chunk), len(chunk), _lib.stream_ptr())
 
     def _mlp_fwd(self, params, k, js, a, b, finalize=True):
         """finalize=False: leave the tile statistics of the two MLPs un-finalized (the matmul that consumes them
@@ -350,18 +303,8 @@ class FgnnEngine:
                       _lib.ptr(bufs[0]), _lib.ptr(bufs[1]) if len(js) == 2 else None, st)
             for j, buf in zip(js, bufs):
                 self.decisions[(k, j)] = buf
-        if not finalize:
-            return
-        if len(js) == 2:
-            r0, r1 = L.mlp[(k, js[0])], L.mlp[(k, js[1])]
-            _lib.call('fgnn_gn_finalize2', _lib.ptr(self.part[0]), _lib.ptr(self.part[1]), _lib.ptr(self.cnt),
-                      C.c_void_p(self._w(params, r0['gn_w'])), C.c_void_p(self._w(params, r1['gn_w'])), self._nv(),
-                      self.G, 32, self.N, EPS, _lib.ptr(self.nrm[(k, js[0])]), _lib.ptr(self.nrm[(k, js[1])]), st)
-        else:
-            rec = L.mlp[(k, js[0])]
-            _lib.call('fgnn_gn_finalize', _lib.ptr(self.part[0]), _lib.ptr(self.cnt),
-                      C.c_void_p(self._w(params, rec['gn_w'])), self._nv(), self.G, 32, self.N, EPS,
-                      _lib.ptr(self.nrm[(k, js[0])]), st)
+        if finalize:
+            self._gn_finalize(params, k, js)
 
     def _packed_input(self, args, k):
         """Block 1 with a bit-packed input: its 2-channel slab is expanded inside the kernel."""
@@ -380,26 +323,15 @@ class FgnnEngine:
         caller must leave them untouched until backward() has been issued (stream order is enough).  Any other nvalid (host list,
         int64, another device) is copied into the engine's own buffer.  A HIP graph captured around step() keeps those addresses."""
         L = self.layout
-        if (nvalid is None) != (self.nvalid is None):
-            raise RuntimeError('FgnnEngine: ragged flag and nvalid argument disagree')
-        if nvalid is not None:
-            if nvalid.dtype == torch.int32 and nvalid.is_cuda and nvalid.is_contiguous() and nvalid.numel() == self.G:
-                self.nvalid = nvalid            # read in place by every kernel of the step (a copy node costs 4.6 + 8.6 us of gap in a replayed graph)
-            else:
-                self._nvalid_own.copy_(nvalid.to(torch.int32))
-                self.nvalid = self._nvalid_own
+        self._adopt_nvalid(nvalid)
         st = _lib.stream_ptr()
         if self.ranges is not None:
             _lib.call('fgnn_ragged_tile_ranges_order', _lib.ptr(self.nvalid), self.G, self.N, _lib.ptr(self.ranges),
                       _lib.ptr(self.mm_order) if self.mm_order is not None else None, st, tag='fgnn_ragged_tile_ranges')
         if bits is not None:
-            words = (self.N + 31) // 32
             if x is not None or L.c0 != 2 or L.depth != 3:
                 raise RuntimeError('FgnnEngine.embed: bits= replaces x and needs original_features_num = 2, depth_of_mlp = 3')
-            if tuple(bits.shape) != (self.G, self.N, words) or bits.dtype not in (torch.int32, torch.uint32) \
-                    or not bits.is_contiguous() or bits.device.type != 'cuda':
-                raise RuntimeError('FgnnEngine.embed: expected contiguous 32-bit words %s on the GPU, got %s %s'
-                                   % ((self.G, self.N, words), tuple(bits.shape), bits.dtype))
+            self._check_bits(bits)
             if self.xdeg is None:
                 self.xdeg = torch.empty(self.G * self.N, dtype=torch.float32, device=self.device)
             self.x, self.xbits = None, bits
@@ -456,18 +388,6 @@ class FgnnEngine:
         return 1 if self.ranges is not None else 0
 
     # ------------------------------------------------------------------ block 1 on its structured input (csrc/block1_struct.hip)
-    def _struct_ws(self):
-        if self._struct is None:
-            lib = _lib.load()
-            f32 = dict(dtype=torch.float32, device=self.device)
-            self._struct = {'tab': torch.empty(lib.fgnn_block1_struct_table_floats(self.N), **f32),
-                            'ws': torch.empty(lib.fgnn_block1_struct_ws_floats(self.G, self.N), **f32)}
-        return self._struct
-
-    def _w3(self, params, j):
-        rec = self.layout.mlp[(1, j)]
-        return ((C.c_void_p * 3)(*[self._w(params, o) for o in rec['w']]), (C.c_void_p * 3)(*[self._w(params, o) for o in rec['b']]))
-
     def _struct_fwd(self, params, with_pack=False):
         """mlp1 + mlp2 + mult of block 1 from the class tables: two small launches instead of fgnn_mlp_fwd + fgnn_chan_matmul_fwd.
         with_pack: the first of them also packs the operand images of the step's MLP launches (pack_operands, without its launch)."""
@@ -502,56 +422,14 @@ class FgnnEngine:
                   _lib.ptr(W['wpart'][(1, 1)]), _lib.ptr(W['wpart'][(1, 2)]), _lib.ptr(W['s12'][(1, 1)]), _lib.ptr(W['s12'][(1, 2)]),
                   _lib.stream_ptr())
 
-    def forward(self, params, x, nvalid=None, total_nodes=None, defer_loss=False, loss_out=None, bits=None, pack=True):
-        """Siamese forward on the stacked batch x = cat(x1, x2) (or its bit-packed adjacency, see embed): returns
-        (scores, loss).
-        defer_loss: leave the final sum of the per-pair losses to the gradient-finalize launch of the
-        following backward() (one launch less per training step); `loss` is valid after that."""
-        self.embed(params, x, nvalid, bits=bits, pack=pack)
-        B, N = self.B, self.N
-        st = _lib.stream_ptr()
-        e1, e2 = self.E[:B], self.E[B:]
-        if total_nodes is None:
-            total_nodes = B * N if nvalid is None else int(nvalid[:B].sum().item())
-        self.total_nodes = float(total_nodes)
-        _lib.call('fgnn_score_ce_fwd_blocks', _lib.ptr(e1), _lib.ptr(e2), self._nv(), B, 32, N, self.score_blocks,
-                  _lib.ptr(self.scores), _lib.ptr(self.lse), _lib.ptr(self.pair_loss), st)
-        self._loss_pending = bool(defer_loss)
-        self._loss_target = self.loss if loss_out is None else loss_out     # 1-element fp32 device tensor
-        if not defer_loss:
-            _lib.call('fgnn_sum_scale', _lib.ptr(self.pair_loss), B * self.score_blocks, 1, 1.0 / self.total_nodes,
-                      _lib.ptr(self._loss_target), st)
-        return self.scores, self._loss_target
-
     # ------------------------------------------------------------------ backward
-    def _alloc_bwd(self):
-        if self._bwd is not None:
-            return self._bwd
-        f32 = dict(dtype=torch.float32, device=self.device)
-        act = lambda: torch.empty(self.G * 32 * self.ldp, **f32)
-        nwg = _lib.load().fgnn_mlp_bwd_num_workgroups()
+    def _partial_rows(self):
+        nwg = super()._partial_rows()
         # cu_share = 2: half of the CUs = half the workgroups = half the partial rows -- but only for constant-size batches:
         # with `ranges` (ragged engines) the kernels ignore cu_share and run the full grid, one row of wpart per workgroup
         if self.cu_share == 2 and self.ranges is None:
             nwg //= 2
-        L = self.layout
-        keys = [(k, j) for k in range(1, L.num_blocks + 1) for j in (1, 2, 3)]
-        self._bwd = {
-            'dE': torch.empty(self.G, 32, self.N, **f32),
-            'dy': [act(), act()],
-            'dmult': act(), 'dy1': act(), 'dy2': act(),
-            # per-MLP GraphNorm-backward sums and workgroup partials live until the final
-            # fgnn_grad_finalize launch
-            's12': {kj: torch.empty(self.G * 32 * 2, **f32) for kj in keys},
-            # (the structured block 1 writes one row per graph: the other rows of its two buffers stay zero)
-            'wpart': {kj: torch.empty(nwg * L.mlp[kj]['count'], **f32)
-                      for kj in keys},
-            's12part': torch.empty(self.G * self.tpg * 32 * 2, **f32),
-            'coef': [torch.empty(self.G * 32 * 4, **f32) for _ in range(3)],
-            'nwg': nwg,
-            'gscale': torch.empty(1, **f32),
-        }
-        return self._bwd
+        return nwg
 
     def _coef(self, kj, slot):
         """coef[slot] <- dz coefficients of MLP kj from its summed s12."""
@@ -627,30 +505,6 @@ class FgnnEngine:
             args.s12part = W['s12part'].data_ptr()
         return args
 
-    def backward(self, params, grads, grad_scale=1.0, finalize=True, gscale_dev=None):
-        """Backward of loss*grad_scale after forward(); fills the flat `grads` buffer (finalize=False: everything but the
-        last launch, see backward_from_dE).
-        gscale_dev: a 1-element fp32 DEVICE tensor that holds grad_scale / total_nodes (replaces both): the normaliser of a ragged
-        batch then never visits the host, and a captured step stays valid when the next batch has another node count."""
-        W = self._alloc_bwd()
-        B, N = self.B, self.N
-        st = _lib.stream_ptr()
-        gs_t = W['gscale']
-        if gscale_dev is not None:
-            gs_t = gscale_dev                  # read in place (a 1-element fp32 device tensor; no copy launch)
-        else:
-            self._set_gscale(grad_scale / self.total_nodes)
-        e1, e2 = self.E[:B], self.E[B:]
-        _lib.call('fgnn_score_ce_bwd', _lib.ptr(e1), _lib.ptr(e2), _lib.ptr(self.scores), _lib.ptr(self.lse),
-                  self._nv(), _lib.ptr(gs_t), B, 32, N, _lib.ptr(W['dE'][:B]), _lib.ptr(W['dE'][B:]), st)
-        return self.backward_from_dE(params, grads, W['dE'], finalize=finalize)
-
-    def _set_gscale(self, gs):
-        W = self._bwd
-        if W.get('gscale_value') != gs:        # a 1-element fill kernel per step otherwise
-            W['gscale'].fill_(gs)
-            W['gscale_value'] = gs
-
     def backward_from_dE(self, params, grads, dE, finalize=True, dx=None):
         """Backward of the node embedder given d loss / d E  (G, 32, N).
         dx: optional zero-initialised (G, c0, N, N) fp32 tensor that receives the gradient with respect to the input x (the
@@ -712,59 +566,7 @@ class FgnnEngine:
             self.grad_finalize(grads)
         return grads
 
-    def grad_finalize(self, grads, rows=None, graphs=None, pair_rows=None):
-        """ONE launch: reduce the workgroup partials + GraphNorm affine gradients of all MLPs (and the deferred loss sum).
-        rows / graphs / pair_rows: FgnnEngineDual reduces the partials of both of its engines at once -- their wpart, s12,
-        nrm and pair_loss buffers are consecutive halves of one allocation, this engine holding the first."""
-        L = self.layout
-        W = self._bwd
-        K = L.num_blocks
-        st = _lib.stream_ptr()
-        keys = [(k, j) for k in range(1, K + 1) for j in (1, 2, 3)]
-        if getattr(self, '_loss_pending', False):
-            keys.append('loss')
-            self._loss_pending = False
-        for lo in range(0, len(keys), _lib.MAX_GRAD_JOBS):
-            chunk = keys[lo:lo + _lib.MAX_GRAD_JOBS]
-            jobs = (_lib.GradJob * len(chunk))()
-            for i, kj in enumerate(chunk):
-                if kj == 'loss':        # loss = sum(pair_loss) / nodes rides along as one more reduction job
-                    jobs[i].wpart = self.pair_loss.data_ptr()
-                    jobs[i].count = 1
-                    jobs[i].out = self._loss_target.data_ptr()
-                    jobs[i].rows = self.B * self.score_blocks if pair_rows is None else pair_rows
-                    jobs[i].scale = 1.0 / self.total_nodes
-                    if getattr(self, '_loss_scale_dev', None) is not None:       # 1 / sum(n) as a device scalar (forward(inv_nodes_dev=...))
-                        jobs[i].scale_dev = self._loss_scale_dev.data_ptr()
-                    continue
-                rec = L.mlp[kj]
-                jobs[i].wpart = W['wpart'][kj].data_ptr()
-                jobs[i].count = rec['count']
-                if kj in ((1, 1), (1, 2)) and W.get('struct_rows', 0):
-                    jobs[i].rows = W['struct_rows']         # block 1 on its structured input: the rows its backward wrote
-                jobs[i].out = grads.data_ptr() + 4 * rec['off']
-                jobs[i].s12 = W['s12'][kj].data_ptr()
-                jobs[i].nrm = self.nrm[kj].data_ptr()
-                jobs[i].dgn_w = grads.data_ptr() + 4 * rec['gn_w']
-                jobs[i].dgn_b = grads.data_ptr() + 4 * rec['gn_b']
-            _lib.call('fgnn_grad_finalize', jobs, len(chunk), W['nwg'] if rows is None else rows,
-                      self.G if graphs is None else graphs, 32, st)
-        return grads
-
-    def step(self, params, grads, x, nvalid=None, total_nodes=None, loss_out=None, bits=None):
-        """One training step's model work: forward + loss + backward.  (x / bits / an int32 device nvalid are read in place by both
-        passes: see embed().)"""
-        scores, loss = self.forward(params, x, nvalid, total_nodes, defer_loss=True, loss_out=loss_out, bits=bits)
-        self.backward(params, grads)
-        return scores, loss
-
     # ------------------------------------------------------------------ inspection (tests / module API)
-    def export_decisions(self, on=True):
-        """Test-only (tests/test_gpu_grad_pinned.py): from the next forward on, every fgnn_mlp_fwd launch is followed by its
-        decision-exporting twin (fgnn_debug_mlp_fwd_masks) and `relu_decisions()` returns the ReLU masks the step took; together with
-        self.idx (the arg-max of the pooling) these are ALL the discrete decisions of a step."""
-        self.decisions = {} if on else None
-
     def relu_decisions(self, params=None):
         """{(block, mlp, hidden layer): bool (G, 32, N, N)}: [pre-activation > 0] as the kernels' ReLU saw it.  MLPs that ran on the
         class tables of the structured block 1 take theirs from the table (a class's hidden value > 0), expanded over the pixels."""

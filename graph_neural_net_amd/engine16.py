@@ -17,14 +17,17 @@ import torch
 
 from . import _lib
 from .engine import EPS, ParamLayout, _round_up  # noqa: F401
+from .engine_base import EngineBase
 
 
-class FgnnEngineBF16:
+class FgnnEngineBF16(EngineBase):
     """Workspace + launch sequence for a fixed (G, N) problem on the current device, bf16 storage."""
     SKIP_PADDING_TILES = True     # ragged engines: fgnn_ragged_tile_ranges16 + tile skipping in fgnn_mlp_fwd16 / fgnn_mlp_bwd16
     PAIR_BWD = True               # mlp1 + mlp2 backward of a block as one launch (fgnn_mlp_bwd16_pair), constant-size batches
     BLOCK1 = os.environ.get('FGNN_BLOCK1', 'generic')      # 'structured': csrc/block1_struct.hip for bit-packed inputs
     PACK_IN_STRUCT = os.environ.get('FGNN_PACK_IN_STRUCT', '1') != '0'      # as FgnnEngine.PACK_IN_STRUCT
+    GN_FINALIZE = ('fgnn_gn_finalize_tpg', 'fgnn_gn_finalize2_tpg')      # EngineBase._gn_finalize: one MLP / two MLPs
+    _pack_entry = 'fgnn_pack16_operands'                                 # EngineBase.pack_operands
 
     def __init__(self, layout, G, N, device, ragged=False, block1=None):
         lib = _lib.load()
@@ -33,44 +36,26 @@ class FgnnEngineBF16:
             raise ValueError("block1 must be 'generic' or 'structured' (got %r)" % (block1,))
         # the structured block 1 applies to bit-packed inputs (embed(bits=...)), constant-size or ragged; dense inputs run generic
         self.struct1 = block1 == 'structured' and bool(lib.fgnn_block1_struct_supported(N, layout.depth, layout.c0))
-        self._struct = None
-        self.xbits = None
         if layout.depth != 3:
             raise RuntimeError('the bf16 kernels are built for depth_of_mlp = 3 (got %d)' % layout.depth)
         if layout.c0 != 2:
             raise RuntimeError('the bf16 kernels are built for original_features_num = 2 (got %d)' % layout.c0)
         if N > 256:
             raise RuntimeError('the bf16 per-channel matmul handles N <= 256 (got %d)' % N)
-        self.layout = layout
-        self.G, self.N = G, N
-        self.B = G // 2
+        super().__init__(layout, G, N, device, ragged)
         self.ldr = _round_up(N, 8)                       # row pitch of an N x N matrix inside a channel
         self.ldp = _round_up(N * self.ldr, 64)           # channel stride
         self.tpg = lib.fgnn_tiles_per_graph16(N, self.ldr)
-        self.device = device
+        self._gn_args = (self.tpg, EPS)                  # EngineBase._gn_finalize: what its entry points take between N and the records
         K = layout.num_blocks
         f32 = dict(dtype=torch.float32, device=device)
         bf = dict(dtype=torch.bfloat16, device=device)
-        act = lambda: torch.empty(G * 32 * self.ldp, **bf)
+        self._act = act = lambda: torch.empty(G * 32 * self.ldp, **bf)
         self.x16 = torch.empty(G * 2 * self.ldp, **bf)
         self.z = {(k, j): act() for k in range(1, K + 1) for j in (1, 2, 3)}
         self.mult = {k: act() for k in range(1, K + 1)}
-        self.nrm = {(k, j): torch.empty(G * 32 * 4, **f32) for k in range(1, K + 1) for j in (1, 2, 3)}
         self.part = [torch.empty(G * self.tpg * 32 * 2, **f32) for _ in range(2)]
         self.cnt = torch.empty(G * self.tpg, **f32)
-        self.E = torch.empty(G, 32, N, **f32)
-        self.idx = torch.empty(G, 32, N, dtype=torch.int32, device=device)
-        self.scores = torch.empty(self.B, N, N, **f32)
-        self.lse = torch.empty(self.B, N, **f32)
-        self.score_blocks = lib.fgnn_score_row_blocks(self.B, N)      # row blocks per pair of the scoring kernel
-        self.pair_loss = torch.empty(self.B * self.score_blocks, **f32)
-        self.loss = torch.empty(1, **f32)
-        self.nvalid = torch.empty(G, dtype=torch.int32, device=device) if ragged else None
-        self._nvalid_own = self.nvalid      # the engine's own buffer; an int32 device tensor handed in is used in place (no copy launch)
-        # ragged batches: work-balanced tile ranges of the MLP kernels (padding-only tiles are stepped over)
-        self.ranges = (torch.empty(_lib.FGNN_RANGE_WG + 1, dtype=torch.int32, device=device)
-                       if ragged and self.SKIP_PADDING_TILES else None)
-        self._bwd = None
         self._packs = {}
         for k in range(1, K + 1):
             cin = layout.c0 if k == 1 else 32
@@ -81,12 +66,6 @@ class FgnnEngineBF16:
             self._packs[('b', k, 3)] = (1, 32, cin, 1, torch.empty(lib.fgnn_pack16_floats(1, 32, cin, 3, 1), **f32))
 
     # ------------------------------------------------------------------ helpers
-    def _nv(self):
-        return _lib.ptr(self.nvalid) if self.nvalid is not None else None
-
-    def _w(self, params, off):
-        return params.data_ptr() + 4 * off
-
     def _slab_in(self, k, params):
         if k == 1:
             return _lib.make_slab16(self.x16, 2 * self.ldp, self.ldp, 2)
@@ -101,26 +80,6 @@ class FgnnEngineBF16:
 
     def _slab_raw(self, t):
         return _lib.make_slab16(t, 32 * self.ldp, self.ldp, 32)
-
-    def _pack_jobs(self, params, chunk):
-        L = self.layout
-        jobs = (_lib.PackJob * len(chunk))()
-        for i, ((kind, k, which), (knd, ca, cb, nmlp, buf)) in enumerate(chunk):
-            jobs[i].kind, jobs[i].ca, jobs[i].cb, jobs[i].depth, jobs[i].nmlp = knd, ca, cb, L.depth, nmlp
-            js = (1, 2) if which == 12 else (which,)
-            for m, j in enumerate(js):
-                rec = L.mlp[(k, j)]
-                for l in range(L.depth):
-                    jobs[i].W[m][l] = self._w(params, rec['w'][l])
-                    jobs[i].bias[m][l] = self._w(params, rec['b'][l])
-            jobs[i].out = buf.data_ptr()
-        return jobs
-
-    def pack_operands(self, params):
-        items = list(self._packs.items())
-        for lo in range(0, len(items), _lib.MAX_PACK_JOBS):
-            chunk = items[lo:lo + _lib.MAX_PACK_JOBS]
-            _lib.call('fgnn_pack16_operands', self._pack_jobs(params, chunk), len(chunk), _lib.stream_ptr())
 
     def _mlp_fwd(self, params, k, js, a, b, finalize=True):
         """finalize=False: leave the tile statistics un-finalized (the matmul that consumes the two outputs finalizes them in
@@ -143,25 +102,15 @@ class FgnnEngineBF16:
         st = _lib.stream_ptr()
         _lib.call('fgnn_mlp_fwd16', C.byref(args), st,
                   tag='mlp_fwd16[cin=%d,nmlp=%d]' % (a.C + (b.C if b is not None else 0), len(js)))
-        if getattr(self, 'decisions', None) is not None:
+        if self.decisions is not None:
             # test-only (export_decisions): the decision-exporting twin of the launch above -- same tile code, same outputs written once
             # more -- leaves one bit per hidden pre-activation of these MLPs
             bufs = [torch.zeros(self.G * (L.depth - 1) * 32 * self.tpg * 2, dtype=torch.int32, device=self.device) for _ in js]
             _lib.call('fgnn_debug_mlp_fwd16_masks', C.byref(args), _lib.ptr(bufs[0]), _lib.ptr(bufs[1]) if len(js) == 2 else None, st)
             for j, buf in zip(js, bufs):
                 self.decisions[(k, j)] = buf
-        if not finalize:
-            return
-        if len(js) == 2:
-            r0, r1 = L.mlp[(k, js[0])], L.mlp[(k, js[1])]
-            _lib.call('fgnn_gn_finalize2_tpg', _lib.ptr(self.part[0]), _lib.ptr(self.part[1]), _lib.ptr(self.cnt),
-                      C.c_void_p(self._w(params, r0['gn_w'])), C.c_void_p(self._w(params, r1['gn_w'])), self._nv(),
-                      self.G, 32, self.N, self.tpg, EPS, _lib.ptr(self.nrm[(k, js[0])]), _lib.ptr(self.nrm[(k, js[1])]), st)
-        else:
-            rec = L.mlp[(k, js[0])]
-            _lib.call('fgnn_gn_finalize_tpg', _lib.ptr(self.part[0]), _lib.ptr(self.cnt),
-                      C.c_void_p(self._w(params, rec['gn_w'])), self._nv(), self.G, 32, self.N, self.tpg, EPS,
-                      _lib.ptr(self.nrm[(k, js[0])]), st)
+        if finalize:
+            self._gn_finalize(params, k, js)
 
     # ------------------------------------------------------------------ forward
     def embed(self, params, x, nvalid=None, bits=None):
@@ -171,28 +120,17 @@ class FgnnEngineBF16:
         LIFETIME: as FgnnEngine.embed -- bits and an int32 device nvalid of G entries are read in place by this forward and by the
         backward after it; leave them untouched until backward() has been issued."""
         L = self.layout
-        if (nvalid is None) != (self.nvalid is None):
-            raise RuntimeError('FgnnEngineBF16: ragged flag and nvalid argument disagree')
+        self._adopt_nvalid(nvalid)
         if bits is not None:
-            words = (self.N + 31) // 32
             if x is not None:
                 raise RuntimeError('FgnnEngineBF16.embed: pass x or bits, not both')
-            if tuple(bits.shape) != (self.G, self.N, words) or bits.dtype not in (torch.int32, torch.uint32) \
-                    or not bits.is_contiguous() or bits.device.type != 'cuda':
-                raise RuntimeError('FgnnEngineBF16.embed: expected contiguous int32 device bits %s, got %s %s'
-                                   % ((self.G, self.N, words), tuple(bits.shape), bits.dtype))
+            self._check_bits(bits)
             if not self.struct1:
                 raise RuntimeError("FgnnEngineBF16.embed: bits= needs block1='structured' (N <= 256, depth 3, 2 input channels)")
         elif x.shape != (self.G, L.c0, self.N, self.N) or not x.is_contiguous() or x.dtype != torch.float32:
             raise RuntimeError('FgnnEngineBF16.embed: expected contiguous fp32 %s, got %s %s'
                                % ((self.G, L.c0, self.N, self.N), tuple(x.shape), x.dtype))
         self.xbits = bits
-        if nvalid is not None:
-            if nvalid.dtype == torch.int32 and nvalid.is_cuda and nvalid.is_contiguous() and nvalid.numel() == self.G:
-                self.nvalid = nvalid            # read in place by every kernel of the step (a copy node costs 4.6 + 8.6 us of gap in a replayed graph)
-            else:
-                self._nvalid_own.copy_(nvalid.to(torch.int32))
-                self.nvalid = self._nvalid_own
         st = _lib.stream_ptr()
         if self.ranges is not None:
             _lib.call('fgnn_ragged_tile_ranges16', _lib.ptr(self.nvalid), self.G, self.N, self.ldr, _lib.ptr(self.ranges), st)
@@ -225,18 +163,6 @@ class FgnnEngineBF16:
         return self.E
 
     # ------------------------------------------------------------------ block 1 on its structured input (csrc/block1_struct.hip)
-    def _struct_ws(self):
-        if self._struct is None:
-            lib = _lib.load()
-            f32 = dict(dtype=torch.float32, device=self.device)
-            self._struct = {'tab': torch.empty(lib.fgnn_block1_struct_table_floats(self.N), **f32),
-                            'ws': torch.empty(lib.fgnn_block1_struct_ws_floats(self.G, self.N), **f32)}
-        return self._struct
-
-    def _w3(self, params, j):
-        rec = self.layout.mlp[(1, j)]
-        return ((C.c_void_p * 3)(*[self._w(params, o) for o in rec['w']]), (C.c_void_p * 3)(*[self._w(params, o) for o in rec['b']]))
-
     def _struct_fwd(self, params, with_pack=False):
         S = self._struct_ws()
         st = _lib.stream_ptr()
@@ -265,46 +191,7 @@ class FgnnEngineBF16:
                   _lib.ptr(W['wpart'][(1, 1)]), _lib.ptr(W['wpart'][(1, 2)]), _lib.ptr(W['s12'][(1, 1)]), _lib.ptr(W['s12'][(1, 2)]),
                   _lib.stream_ptr())
 
-    def forward(self, params, x, nvalid=None, total_nodes=None, defer_loss=False, loss_out=None, bits=None):
-        self.embed(params, x, nvalid, bits=bits)
-        B, N = self.B, self.N
-        st = _lib.stream_ptr()
-        e1, e2 = self.E[:B], self.E[B:]
-        _lib.call('fgnn_score_ce_fwd_blocks', _lib.ptr(e1), _lib.ptr(e2), self._nv(), B, 32, N, self.score_blocks,
-                  _lib.ptr(self.scores), _lib.ptr(self.lse), _lib.ptr(self.pair_loss), st)
-        if total_nodes is None:
-            total_nodes = B * N if nvalid is None else int(nvalid[:B].sum().item())
-        self.total_nodes = float(total_nodes)
-        self._loss_pending = bool(defer_loss)
-        self._loss_target = self.loss if loss_out is None else loss_out     # 1-element fp32 device tensor
-        if not defer_loss:
-            _lib.call('fgnn_sum_scale', _lib.ptr(self.pair_loss), B * self.score_blocks, 1, 1.0 / self.total_nodes,
-                      _lib.ptr(self._loss_target), st)
-        return self.scores, self._loss_target
-
     # ------------------------------------------------------------------ backward
-    def _alloc_bwd(self):
-        if self._bwd is not None:
-            return self._bwd
-        f32 = dict(dtype=torch.float32, device=self.device)
-        bf = dict(dtype=torch.bfloat16, device=self.device)
-        act = lambda: torch.empty(self.G * 32 * self.ldp, **bf)
-        nwg = _lib.load().fgnn_mlp_bwd_num_workgroups()
-        L = self.layout
-        keys = [(k, j) for k in range(1, L.num_blocks + 1) for j in (1, 2, 3)]
-        self._bwd = {
-            'dE': torch.empty(self.G, 32, self.N, **f32),
-            'dy': [act(), act()],
-            'dmult': act(), 'dy1': act(), 'dy2': act(),
-            's12': {kj: torch.empty(self.G * 32 * 2, **f32) for kj in keys},
-            'wpart': {kj: torch.empty(nwg * L.mlp[kj]['count'], **f32) for kj in keys},
-            's12part': torch.empty(self.G * self.tpg * 32 * 2, **f32),
-            'coef': [torch.empty(self.G * 32 * 4, **f32) for _ in range(3)],
-            'nwg': nwg,
-            'gscale': torch.empty(1, **f32),
-        }
-        return self._bwd
-
     def _mlp_bwd(self, params, k, j, a, b, dy, coef, dxa, dxb, acc_a, acc_b, emit=False):
         args = self._mlp_bwd_args(params, k, j, a, b, dy, coef, dxa, dxb, acc_a, acc_b, emit)
         _lib.call('fgnn_mlp_bwd16', C.byref(args), _lib.stream_ptr(),
@@ -345,25 +232,6 @@ class FgnnEngineBF16:
         if emit:
             args.s12part = W['s12part'].data_ptr()
         return args
-
-    def backward(self, params, grads, grad_scale=1.0, hook=None, gscale_dev=None):
-        """gscale_dev: a 1-element fp32 DEVICE tensor holding grad_scale / total_nodes (replaces both), as in FgnnEngine.backward:
-        the normaliser of a ragged batch never visits the host and a captured step survives another node count."""
-        W = self._alloc_bwd()
-        B, N = self.B, self.N
-        st = _lib.stream_ptr()
-        gs_t = W['gscale']
-        if gscale_dev is not None:
-            gs_t = gscale_dev                  # read in place (a 1-element fp32 device tensor; no copy launch)
-        else:
-            gs = grad_scale / self.total_nodes
-            if W.get('gscale_value') != gs:
-                W['gscale'].fill_(gs)
-                W['gscale_value'] = gs
-        e1, e2 = self.E[:B], self.E[B:]
-        _lib.call('fgnn_score_ce_bwd', _lib.ptr(e1), _lib.ptr(e2), _lib.ptr(self.scores), _lib.ptr(self.lse),
-                  self._nv(), _lib.ptr(gs_t), B, 32, N, _lib.ptr(W['dE'][:B]), _lib.ptr(W['dE'][B:]), st)
-        return self.backward_from_dE(params, grads, W['dE'], hook=hook)
 
     def backward_from_dE(self, params, grads, dE, hook=None):
         """hook(stage, k): optional inspection callback, called after every kernel of the block backward ('colmax_bwd',
@@ -419,41 +287,7 @@ class FgnnEngineBF16:
                           self.G, 32, self.N, self.tpg, _lib.ptr(W['s12'][(k - 1, 3)]), _lib.ptr(W['coef'][2]), st)
                 coef3 = W['coef'][2]
             dy = din
-        keys = [(k, j) for k in range(1, K + 1) for j in (1, 2, 3)]
-        if getattr(self, '_loss_pending', False):
-            keys.append('loss')
-            self._loss_pending = False
-        for lo in range(0, len(keys), _lib.MAX_GRAD_JOBS):
-            chunk = keys[lo:lo + _lib.MAX_GRAD_JOBS]
-            jobs = (_lib.GradJob * len(chunk))()
-            for i, kj in enumerate(chunk):
-                if kj == 'loss':
-                    jobs[i].wpart = self.pair_loss.data_ptr()
-                    jobs[i].count = 1
-                    jobs[i].out = self._loss_target.data_ptr()
-                    jobs[i].rows = self.B * self.score_blocks
-                    jobs[i].scale = 1.0 / self.total_nodes
-                    if getattr(self, '_loss_scale_dev', None) is not None:       # 1 / sum(n) as a device scalar (forward(inv_nodes_dev=...))
-                        jobs[i].scale_dev = self._loss_scale_dev.data_ptr()
-                    continue
-                rec = L.mlp[kj]
-                jobs[i].wpart = W['wpart'][kj].data_ptr()
-                jobs[i].count = rec['count']
-                if kj in ((1, 1), (1, 2)) and W.get('struct_rows', 0):
-                    jobs[i].rows = W['struct_rows']
-                jobs[i].out = grads.data_ptr() + 4 * rec['off']
-                jobs[i].s12 = W['s12'][kj].data_ptr()
-                jobs[i].nrm = self.nrm[kj].data_ptr()
-                jobs[i].dgn_w = grads.data_ptr() + 4 * rec['gn_w']
-                jobs[i].dgn_b = grads.data_ptr() + 4 * rec['gn_b']
-            _lib.call('fgnn_grad_finalize', jobs, len(chunk), W['nwg'], self.G, 32, st)
-        return grads
-
-    def export_decisions(self, on=True):
-        """Test-only (tests/test_gpu_grad_pinned.py): from the next forward on, every fgnn_mlp_fwd16 launch is followed by its
-        decision-exporting twin (fgnn_debug_mlp_fwd16_masks); relu_decisions() + self.idx are then all the discrete ReLU / arg-max
-        decisions of a step (constant-size batches, generic block 1)."""
-        self.decisions = {} if on else None
+        return self.grad_finalize(grads)
 
     def relu_decisions(self):
         """{(block, mlp, hidden layer): bool (G, 32, N, N)}: [pre-activation > 0] as the kernels' ReLU saw it."""
@@ -468,11 +302,6 @@ class FgnnEngineBF16:
             for l in range(L.depth - 1):
                 out[(k, j, l)] = m[:, l].bool()
         return out
-
-    def step(self, params, grads, x, nvalid=None, total_nodes=None, loss_out=None, bits=None):
-        scores, loss = self.forward(params, x, nvalid, total_nodes, defer_loss=True, loss_out=loss_out, bits=bits)
-        self.backward(params, grads)
-        return scores, loss
 
     # ------------------------------------------------------------------ inspection (tests)
     def load_dense(self, buf, t):
