@@ -19,6 +19,8 @@ FGNN_MAX_DEPTH = 3
 FGNN_RANGE_WG = 256          # include/fgnn_hip.h
 FGNN_LSAP_MAX_N = 2048       # include/fgnn_hip.h: largest graph of fgnn_lsap_accuracy
 FGNN_QAP_MAX_N = 256         # include/fgnn_hip.h: largest graph of the fgnn_qap_* / fgnn_greedy_qap kernels
+FGNN_SPECTRAL_MAX_N = 256    # include/fgnn_hip.h: largest graph of fgnn_spectral_features
+FGNN_SPECTRAL_MAX_POWERS = 8
 FGNN_SCORE_SPLIT = 4
 
 c_float_p = C.c_void_p   # device pointers travel as integers
@@ -239,6 +241,7 @@ _SIGNATURES = {
     'fgnn_qap_improve_cost': [_VP, _VP, _VP, _VP, _I, _I, _VP, _LL, _I, _VP],
     'fgnn_greedy_qap_ws_bytes': [_I, _I],
     'fgnn_greedy_qap': [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
+    'fgnn_spectral_features': [_VP, _VP, _I, _I, _I, _VP, _I, _VP],
     # ---- bf16 path ----
     'fgnn_tiles_per_graph16': [_I, _I],
     'fgnn_to_bf16': [_VP, _VP, _I, _I, _I, _I, _VP, _LL, _LL, _VP],

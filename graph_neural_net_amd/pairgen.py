@@ -2,7 +2,8 @@
 
 ``PairGenerator`` writes (graph, noisy graph) pairs straight into the engine's wire format -- (B, N, ceil(N/32)) int32 words,
 bit j of word row i = W[i][j] (``synthetic.pack_adjacency``) -- with ``csrc/pairgen.hip``; ``.bits`` feeds
-``FgnnTrainer.train_step_bits`` and ``.dense`` builds the reference's collate structures from the same words.
+``FgnnTrainer.train_step_bits``, ``.dense`` builds the reference's collate structures from the same words and ``.spectral`` those
+of ``QAP_spectralGenerator`` (loaders/data_generator.py:221-277: the channels L, L^2, ... of ``spectral.py``).
 
 Semantics follow the reference:
 
@@ -32,6 +33,7 @@ import torch
 from . import _lib
 from .inputs import expand_adjacency
 from .masked import MaskedTensor
+from .spectral import spectral_features
 
 FAMILIES = {'ErdosRenyi': 0, 'Regular': 1, 'BarabasiAlbert': 2}
 NOISE_MODELS = {'ErdosRenyi': 0, 'EdgeSwap': 1}
@@ -128,3 +130,16 @@ class PairGenerator:
         n = int(nv.max().item()) if count else 0
         x1, x2 = x1[:, :, :n, :n].contiguous(), x2[:, :, :n, :n].contiguous()
         return MaskedTensor(x1, nv, (2, 3), 'N'), MaskedTensor(x2, nv, (2, 3), 'M')
+
+    def spectral(self, first, count, n_powers=4):
+        """The twin of `dense` for the reference's ``QAP_spectralGenerator`` (loaders/data_generator.py:221-277): the same pairs as
+        `bits`, each side as the n_powers channels L, L^2, ... of ``spectral.spectral_features`` (one launch per side, straight from
+        the bit rows; an isolated vertex gives a zero row and column where the reference gives NaN).  ({'input': F1}, {'input': F2})
+        with (count, n_powers, N, N) fp32 tensors for a constant vertex count, else two MaskedTensors written directly at the
+        largest n_i of the batch (one host sync for that size), with the names and masked dims of `dense`."""
+        b1, b2, nv = self.bits(first, count)
+        if nv is None:
+            return {'input': spectral_features(b1, None, n_powers)}, {'input': spectral_features(b2, None, n_powers)}
+        n = max(int(nv.max().item()), 1) if count else 1
+        f1, f2 = spectral_features(b1, nv, n_powers, n_out=n), spectral_features(b2, nv, n_powers, n_out=n)
+        return MaskedTensor(f1, nv, (2, 3), 'N'), MaskedTensor(f2, nv, (2, 3), 'M')

@@ -759,6 +759,21 @@ long long fgnn_greedy_qap_ws_bytes(int B, int N);
 int fgnn_greedy_qap(const unsigned *bits1, const unsigned *bits2, const int *assign0, const int *nvalid, int B, int N, int T, void *ws,
                     long long ws_bytes, int *s_best2, int *acc_best, int *t_best, int *perm_best /* optional */, void *stream);
 
+/* ---- spectral input features (csrc/spectral.hip; loaders/data_generator.py:221-232 make_laplacian / make_spectral_feature, the
+ * input of QAP_spectralGenerator) ---------------------------------------------------------------------------------------------
+ * bits: (G, N, ceil(N/32)) words, bit j of word row i = W[i][j] (the layout of fgnn_expand_adjacency); nvalid (optional, int32[G]):
+ * graph g is the n_g x n_g corner (n_g clamped to [0, N]); bits outside it are ignored, they need not be zero.  W need not be
+ * symmetric.  out: (G, n_powers, Nout, Nout) fp32, channel p - 1 = L^p with L = D^-1/2 W D^-1/2:
+ *   d_i = sum_j W[i][j] over the corner, s_i = 1 / sqrt(d_i) in fp32 (IEEE), s_i = 0 where d_i = 0;
+ *   F_1[i][j] = (s_i W[i][j]) s_j (bit-exact against the reference), F_{p+1} = F_p @ L as s_j sum_k (F_p[i][k] s_k) W[k][j] in fp32.
+ * Deviation: for a vertex of degree 0 the reference computes inf * 0 = NaN, and every later power is NaN in every entry; here the
+ * row and column of an isolated vertex are zeros.  Nout <= N is the row pitch and plane size of out: the top-left Nout x Nout corner
+ * of every N x N plane is written (a ragged batch goes out at its largest n_g), with exact zeros outside the n_g x n_g corner.
+ * One launch on `stream`, no workspace, no copy to the host, no synchronisation: capturable. */
+#define FGNN_SPECTRAL_MAX_N 256
+#define FGNN_SPECTRAL_MAX_POWERS 8
+int fgnn_spectral_features(const unsigned *bits, const int *nvalid, int G, int N, int n_powers, float *out, int Nout, void *stream);
+
 /* ---- test-only entry points (never on the product path; tests/ and tools/ call them) ---------------------------------------
  * fgnn_debug_mlp_fwd_masks / fgnn_debug_mlp_fwd_x3_masks: fgnn_mlp_fwd / fgnn_mlp_fwd_x3 once more -- the same tile code, the same
  * outputs, bit for bit -- that ALSO exports the ReLU decisions of the conv chain (models/layers.py:129-130), the input of the
