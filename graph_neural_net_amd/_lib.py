@@ -19,6 +19,7 @@ FGNN_MAX_DEPTH = 3
 FGNN_RANGE_WG = 256          # include/fgnn_hip.h
 FGNN_LSAP_MAX_N = 2048       # include/fgnn_hip.h: largest graph of fgnn_lsap_accuracy
 FGNN_QAP_MAX_N = 256         # include/fgnn_hip.h: largest graph of the fgnn_qap_* / fgnn_greedy_qap kernels
+FGNN_QAPW_MAX_N = 256        # include/fgnn_hip.h: largest graph of the fgnn_qapw_* / fgnn_greedy_qapw kernels (fp32 weights)
 FGNN_SPECTRAL_MAX_N = 256    # include/fgnn_hip.h: largest graph of fgnn_spectral_features
 FGNN_SPECTRAL_MAX_POWERS = 8
 FGNN_SCORE_SPLIT = 4
@@ -241,6 +242,10 @@ _SIGNATURES = {
     'fgnn_qap_improve_cost': [_VP, _VP, _VP, _VP, _I, _I, _VP, _LL, _I, _VP],
     'fgnn_greedy_qap_ws_bytes': [_I, _I],
     'fgnn_greedy_qap': [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
+    'fgnn_qapw_objective': [_VP, _VP, _LL, _I, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP],
+    'fgnn_qapw_improve_cost': [_VP, _VP, _LL, _I, _VP, _VP, _I, _I, _VP, _LL, _I, _VP],
+    'fgnn_greedy_qapw_ws_bytes': [_I, _I],
+    'fgnn_greedy_qapw': [_VP, _VP, _LL, _I, _VP, _VP, _I, _I, _I, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
     'fgnn_spectral_features': [_VP, _VP, _I, _I, _I, _VP, _I, _VP],
     # ---- bf16 path ----
     'fgnn_tiles_per_graph16': [_I, _I],
@@ -267,7 +272,8 @@ _SIGNATURES = {
     'fgnn_mlp_bwd16': [C.POINTER(MlpBwd16Args), _VP],
     'fgnn_mlp_bwd16_pair': [C.POINTER(MlpBwd16Args), C.POINTER(MlpBwd16Args), _VP],
 }
-_RESTYPES = {'fgnn_last_error': C.c_char_p, 'fgnn_block1_struct_ws_floats': C.c_longlong, 'fgnn_greedy_qap_ws_bytes': C.c_longlong}
+_RESTYPES = {'fgnn_last_error': C.c_char_p, 'fgnn_block1_struct_ws_floats': C.c_longlong, 'fgnn_greedy_qap_ws_bytes': C.c_longlong,
+             'fgnn_greedy_qapw_ws_bytes': C.c_longlong}
 EXPORTS = tuple(_SIGNATURES)
 
 _lib = None

@@ -22,6 +22,16 @@ read of the verdict flag, after the last launch is queued, is the only synchroni
 
 Host route (the split ``metrics.py`` makes): tensors that are not on the GPU, and graphs beyond FGNN_QAP_MAX_N = 256 vertices,
 run a numpy + SciPy loop over the pairs, the same arithmetic in integers.
+
+``weighted=True`` (``csrc/qap_weighted.hip``) lifts the 0/1 limit, as the reference has none: ``adj1`` / ``adj2`` are (B, N, N) float
+matrices or (B, C, N, N) batches whose channel 0 is used AS IS (``data['input'][:, 0, :]`` of ``all_acc_qap``) -- a spectral
+``L = D^-1/2 W D^-1/2`` of ``PairGenerator.spectral``, any weighted graph.  No representation check is made and no flag is read: the
+device route never synchronises.  (A P B) is then an fp32 GEMM with a row-gathered right operand on the fp32 matrix cores, the sums
+are fp32 in a fixed order: qap, planted, na, nb and s_best come back as float32 device tensors (acc, acc_best, T_best, perm as
+without the keyword), exact where every product and partial sum is representable (integer or dyadic weights), else within
+gamma_m sum |a||b| of the float64 value, gamma_m = m u / (1 - m u), u = 2^-24, m = n_b^2.  qap = -1 still marks an `assign` without
+a column inside the corner; with weights that may be negative -1 is then not a value.  Its host route is the reference's own float64
+matrix arithmetic (``trace(A @ P @ B @ P.T) / 2``, ``linear_sum_assignment(-A @ P @ B)``) and returns float64.
 """
 import numpy as np
 import torch
@@ -104,9 +114,76 @@ def greedy_bits(b1, b2, assign, T, nv):
             'acc_best': out[1].to(torch.int64), 'T_best': out[2].to(torch.int64), 'perm': perm}
 
 
-def qap_objective(adj1, adj2, assign, nvalid=None):
+def _chan0_ok(x):
+    n = x.shape[-1]
+    return (x.stride(-1) == 1 and x.stride(-2) >= n and (x.shape[0] == 1 or x.stride(0) >= n * x.stride(-2))
+            and x.data_ptr() % 4 == 0)
+
+
+def weighted_views(adj1, adj2):
+    """-> (x1, x2, gstride, ld): fp32 device tensors whose data_ptr() is channel 0 of pair 0 (row pitch ld, pairs gstride floats apart,
+    the same on both sides).  A contiguous fp32 (B, N, N) or (B, C, N, N) batch passes in place; anything else has its channel 0 copied."""
+    xs = []
+    for a in (adj1, adj2):
+        if a.dim() not in (3, 4) or a.shape[-1] != a.shape[-2] or not a.is_floating_point():
+            raise RuntimeError('qap: weighted input is (B, N, N) or (B, C, N, N) float, got %s %s' % (tuple(a.shape), a.dtype))
+        x = a.detach().float()
+        xs.append(x[:, 0] if x.dim() == 4 else x)
+    if xs[0].shape != xs[1].shape:
+        raise RuntimeError('qap: the two sides differ in shape: %s / %s' % (tuple(xs[0].shape), tuple(xs[1].shape)))
+    n = xs[0].shape[-1]
+    strides = [(x.stride(0) if x.shape[0] > 1 else n * x.stride(-2), x.stride(-2)) for x in xs]
+    if not (_chan0_ok(xs[0]) and _chan0_ok(xs[1]) and strides[0] == strides[1]):
+        xs = [x.contiguous() for x in xs]
+        strides = [(n * n, n)] * 2
+    return xs[0], xs[1], strides[0][0], strides[0][1]
+
+
+def objective_weighted(adj1, adj2, assign, nv):
+    """fgnn_qapw_objective -> dict of (B,) float32 device tensors (qap, trace, planted, na, nb); never synchronises."""
+    x1, x2, gs, ld = weighted_views(adj1, adj2)
+    B, N = x1.shape[0], x1.shape[-1]
+    a = assign.to(device=x1.device, dtype=torch.int32).contiguous()
+    out = torch.empty(5, B, dtype=torch.float32, device=x1.device)
+    _lib.call('fgnn_qapw_objective', _lib.ptr(x1), _lib.ptr(x2), gs, ld, _lib.ptr(a), _lib.ptr(nv), B, N, _lib.ptr(out[0]),
+              _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.ptr(out[3]), _lib.ptr(out[4]), _lib.stream_ptr())
+    return {'qap': out[0], 'trace': out[1], 'planted': out[2], 'na': out[3], 'nb': out[4]}
+
+
+def greedy_weighted(adj1, adj2, assign, T, nv):
+    """fgnn_greedy_qapw -> the dict of `greedy_qap(weighted=True)`; never synchronises."""
+    x1, x2, gs, ld = weighted_views(adj1, adj2)
+    B, N = x1.shape[0], x1.shape[-1]
+    dev = x1.device
+    a = assign.to(device=dev, dtype=torch.int32).contiguous()
+    nbytes = _lib.load().fgnn_greedy_qapw_ws_bytes(B, N)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    s_best = torch.empty(B, dtype=torch.float32, device=dev)
+    out = torch.empty(2, B, dtype=torch.int32, device=dev)
+    perm = torch.empty(B, N, dtype=torch.int32, device=dev)
+    sums = torch.empty(2, B, dtype=torch.float32, device=dev)
+    _lib.call('fgnn_greedy_qapw', _lib.ptr(x1), _lib.ptr(x2), gs, ld, _lib.ptr(a), _lib.ptr(nv), B, N, int(T), _lib.ptr(ws), nbytes,
+              _lib.ptr(s_best), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(perm), _lib.stream_ptr())
+    _lib.call('fgnn_qapw_objective', _lib.ptr(x1), _lib.ptr(x2), gs, ld, _lib.ptr(a), _lib.ptr(nv), B, N, None, None, None,
+              _lib.ptr(sums[0]), _lib.ptr(sums[1]), _lib.stream_ptr())
+    return {'s_best': s_best, 'na': sums[0] / 2, 'nb': sums[1] / 2, 'acc_best': out[0].to(torch.int64), 'T_best': out[1].to(torch.int64),
+            'perm': perm}
+
+
+def _on_host_weighted(adj1, n):
+    return not adj1.is_cuda or n > _lib.FGNN_QAPW_MAX_N
+
+
+def qap_objective(adj1, adj2, assign, nvalid=None, weighted=False):
     """Per pair: qap = sum_{i,k} A[i,k] B[pi(i),pi(k)] (-1 where `assign` holds no column inside the valid corner: the solver found
-    no finite matching), planted = sum A * B, na = sum A, nb = sum B -> dict of (B,) int64 tensors on the inputs' device."""
+    no finite matching), planted = sum A * B, na = sum A, nb = sum B -> dict of (B,) int64 tensors on the inputs' device.  weighted=True: real matrices (see the module docstring), float32
+    results (float64 from the host route)."""
+    if weighted:
+        if _on_host_weighted(adj1, adj1.shape[-1]):
+            return _objective_host_w(adj1, adj2, assign, nvalid)
+        out = objective_weighted(adj1, adj2, assign, _nv32(nvalid, adj1.device))
+        del out['trace']
+        return out
     if _on_host(adj1, adj1.shape[-2]):
         return _objective_host(adj1, adj2, assign, nvalid)
     b1, b2, nv, flag = _device_inputs(adj1, adj2, nvalid)
@@ -116,14 +193,19 @@ def qap_objective(adj1, adj2, assign, nvalid=None):
     return out
 
 
-def greedy_qap(adj1, adj2, assign, T=10, nvalid=None):
+def greedy_qap(adj1, adj2, assign, T=10, nvalid=None, weighted=False):
     """The reference's greedy_qap(A, B, perm_matrix(arange, assign), T) for every pair of the batch (see the module docstring for
     the order of events and its quirk) -> dict of (B,) tensors: s_best, na, nb (float64; na / nb the halved sums, as score() returns
     them), acc_best, T_best (int64), and perm (B, N) int32, the matching whose score is s_best (-1 in the padding).  Where no round
     improved on the initial score, perm is `assign` and acc_best -- the fixed points of a matching that was never scored -- does NOT
-    describe it.  The device route is one chain of launches (4 per round) without a host round trip: it can be captured."""
+    describe it.  The device route is one chain of launches (4 per round) without a host round trip: it can be captured.
+    weighted=True: real matrices (see the module docstring); s_best, na, nb are float32 (float64 from the host route)."""
     if T < 0:
         raise ValueError('T must be >= 0, got %r' % (T,))
+    if weighted:
+        if _on_host_weighted(adj1, adj1.shape[-1]):
+            return _greedy_host_w(adj1, adj2, assign, T, nvalid)
+        return greedy_weighted(adj1, adj2, assign, T, _nv32(nvalid, adj1.device))
     if _on_host(adj1, adj1.shape[-2]):
         return _greedy_host(adj1, adj2, assign, T, nvalid)
     b1, b2, nv, flag = _device_inputs(adj1, adj2, nvalid)
@@ -133,10 +215,18 @@ def greedy_qap(adj1, adj2, assign, T=10, nvalid=None):
     return out
 
 
-def all_acc_qap(scores, adj1, adj2, nvalid=None):
+def all_acc_qap(scores, adj1, adj2, nvalid=None, weighted=False):
     """toolbox/metrics.py:168-193 per pair: (acc, qap, planted) as (B,) int64 tensors on the scores' device -- the fixed points of the
-    Hungarian matching of -log_softmax(scores), sum(g1 * g2[col][:, col]) and sum(g1 * g2)."""
+    Hungarian matching of -log_softmax(scores), sum(g1 * g2[col][:, col]) and sum(g1 * g2).  weighted=True: g1 / g2 are channel 0 of real batches (see the module docstring); qap
+    and planted are float32 (float64 from the host route)."""
     scores = scores.detach()
+    if weighted:
+        if _on_host_weighted(scores, scores.shape[-1]) or not adj1.is_cuda:
+            return _all_acc_qap_host_w(scores, adj1, adj2, nvalid)
+        nv = _nv32(nvalid, scores.device)
+        correct, assign = lsap_device(scores, nv, want_assign=True)
+        out = objective_weighted(adj1, adj2, assign, nv)
+        return correct.to(torch.int64), out['qap'], out['planted']
     if _on_host(scores, scores.shape[-1]) or not adj1.is_cuda:
         return _all_acc_qap_host(scores, adj1, adj2, nvalid)
     b1, b2, nv, flag = _device_inputs(adj1, adj2, nvalid)
@@ -242,3 +332,90 @@ def _all_acc_qap_host(scores, adj1, adj2, nvalid):
         out[:, b] = (int((cols == np.arange(n)).sum()), _qap_of(As[b], Bs[b], cols), int((As[b] * Bs[b]).sum()))
     t = torch.from_numpy(out)
     return t[0], t[1], t[2]
+
+
+# ------------------------------------------------------------------------------------- host route, real weights (weighted=True)
+def _matrices_host_w(adj, sizes):
+    """-> list of (n_b, n_b) float64 numpy matrices: channel 0 of a (B, C, N, N) batch, or the (B, N, N) matrices themselves"""
+    a = adj.detach().cpu()
+    if a.dim() not in (3, 4) or a.shape[-1] != a.shape[-2] or not a.is_floating_point():
+        raise RuntimeError('qap: weighted input is (B, N, N) or (B, C, N, N) float, got %s %s' % (tuple(a.shape), a.dtype))
+    x = (a[:, 0] if a.dim() == 4 else a).double().numpy()
+    return [x[b, :n, :n] for b, n in enumerate(sizes)]
+
+
+def _perm_matrix(pi):
+    n = len(pi)
+    P = np.zeros((n, n))
+    P[np.arange(n), pi] = 1
+    return P
+
+
+def _score_w(A, Bm, P):                                            # toolbox/utils.py:231-232
+    return np.trace(A @ P @ Bm @ P.T) / 2
+
+
+def _improve_w(A, Bm, P):                                          # toolbox/utils.py:234-239
+    from scipy.optimize import linear_sum_assignment
+    _, cols = linear_sum_assignment(-A @ P @ Bm)
+    return cols, int((cols == np.arange(len(cols))).sum())
+
+
+def _objective_host_w(adj1, adj2, assign, nvalid):
+    B, N = adj1.shape[0], adj1.shape[-1]
+    sizes = _sizes(nvalid, B, N)
+    As, Bs = _matrices_host_w(adj1, sizes), _matrices_host_w(adj2, sizes)
+    pis = assign.detach().cpu().numpy()
+    out = np.zeros((4, B), dtype=np.float64)
+    for b, n in enumerate(sizes):
+        pi = pis[b, :n]
+        ok = bool(((pi >= 0) & (pi < n)).all())
+        out[:, b] = ((As[b] * Bs[b][pi, :][:, pi]).sum() if ok else -1.0, (As[b] * Bs[b]).sum(), As[b].sum(), Bs[b].sum())
+    t = torch.from_numpy(out)
+    return {'qap': t[0], 'planted': t[1], 'na': t[2], 'nb': t[3]}
+
+
+def _greedy_host_w(adj1, adj2, assign, T, nvalid):
+    B, N = adj1.shape[0], adj1.shape[-1]
+    sizes = _sizes(nvalid, B, N)
+    As, Bs = _matrices_host_w(adj1, sizes), _matrices_host_w(adj2, sizes)
+    pis = assign.detach().cpu().numpy()
+    s_b, na, nb = np.zeros(B), np.zeros(B), np.zeros(B)
+    acc_b, t_b = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
+    perm = np.full((B, N), -1, dtype=np.int32)
+    for b, n in enumerate(sizes):
+        A, Bm, pi0 = As[b], Bs[b], pis[b, :n].astype(np.int64)
+        na[b], nb[b] = A.sum() / 2, Bm.sum() / 2
+        perm[b, :n] = pi0
+        if n == 0:
+            continue
+        if not ((pi0 >= 0) & (pi0 < n)).all():
+            raise RuntimeError('greedy_qap: pair %d starts from an incomplete matching' % b)
+        best = _score_w(A, Bm, _perm_matrix(pi0))                  # of the INITIAL matching
+        pi, acc_best = _improve_w(A, Bm, _perm_matrix(pi0))        # ... while this one is never scored
+        t_best = 0
+        for i in range(T):
+            pi, acc = _improve_w(A, Bm, _perm_matrix(pi))
+            s = _score_w(A, Bm, _perm_matrix(pi))
+            if s > best:
+                best, acc_best, t_best = s, acc, i
+                perm[b, :n] = pi
+        s_b[b], acc_b[b], t_b[b] = best, acc_best, t_best
+    return {'s_best': torch.from_numpy(s_b), 'na': torch.from_numpy(na), 'nb': torch.from_numpy(nb), 'acc_best': torch.from_numpy(acc_b),
+            'T_best': torch.from_numpy(t_b), 'perm': torch.from_numpy(perm)}
+
+
+def _all_acc_qap_host_w(scores, adj1, adj2, nvalid):
+    from scipy.optimize import linear_sum_assignment
+    B, N = scores.shape[0], scores.shape[-1]
+    sizes = _sizes(nvalid, B, N)
+    As, Bs = _matrices_host_w(adj1, sizes), _matrices_host_w(adj2, sizes)
+    acc, out = np.zeros(B, dtype=np.int64), np.zeros((2, B), dtype=np.float64)
+    for b, n in enumerate(sizes):
+        if n == 0:
+            continue
+        cost = -torch.log_softmax(scores[b, :n, :n].float(), -1).cpu().numpy()
+        _, cols = linear_sum_assignment(cost)
+        acc[b] = int((cols == np.arange(n)).sum())
+        out[:, b] = ((As[b] * Bs[b][cols, :][:, cols]).sum(), (As[b] * Bs[b]).sum())
+    return torch.from_numpy(acc), torch.from_numpy(out[0]), torch.from_numpy(out[1])

@@ -127,7 +127,7 @@ class Siamese_Node_Exp(nn.Module):
             return MaskedTensor(scores, nvalid, (1, 2), x1.base_name)
         return scores
 
-    def match(self, x1, x2, refine=0):
+    def match(self, x1, x2, refine=0, weighted=False):
         """Decode a batch: the eager forward under no_grad (no `.grad` is touched), the Hungarian matching of -log_softmax(scores)
         and the reference's evaluation of it (toolbox/metrics.py:168-193 all_acc_qap), all on the device (qap.py).  Takes what
         `forward` takes.  Returns a dict: scores ((bs, n, n) tensor or MaskedTensor), assign ((bs, n) int32: the matched column of
@@ -135,7 +135,11 @@ class Siamese_Node_Exp(nn.Module):
         outputs of qap.greedy_qap(T) started from `assign`: s_best, na, nb, acc_best, T_best, perm (see its docstring for the
         reference's quirk: acc_best need not describe perm).  The batch must be a tensor representation -- channel 0 the 0/1
         adjacency -- whatever input_form the model was built with; it is verified on the device, and the one read of that verdict,
-        after everything is queued, is the only host synchronisation."""
+        after everything is queued, is the only host synchronisation.
+
+        weighted=True decodes real-weighted batches -- the output of PairGenerator.spectral goes straight in: channel 0 of the batch
+        is used as the matrices, as the reference's all_acc_qap does (qap.py, csrc/qap_weighted.hip).  No verdict is taken and nothing
+        synchronises; the keys are the same, with qap, planted, s_best, na, nb as float32."""
         a1, a2 = _unwrap_input(x1), _unwrap_input(x2)
         with torch.no_grad():
             scores = self(a1, a2)
@@ -144,6 +148,13 @@ class Siamese_Node_Exp(nn.Module):
             s = scores.tensor.rename(None) if ragged else scores
             dev = s.device
             nv = a1.nvalid.to(device=dev, dtype=torch.int32).contiguous() if ragged else None
+            if weighted:
+                correct, assign = lsap_device(s, nv, want_assign=True)
+                obj = qap.objective_weighted(t1, t2, assign, nv)
+                out = {'scores': scores, 'assign': assign, 'acc': correct.to(torch.int64), 'qap': obj['qap'], 'planted': obj['planted']}
+                if refine:
+                    out.update(qap.greedy_weighted(t1, t2, assign, int(refine), nv))
+                return out
             flag = torch.zeros(1, dtype=torch.int32, device=dev)
             b1, b2 = qap.to_bits(t1, nv, flag), qap.to_bits(t2, nv, flag)
             correct, assign = lsap_device(s, nv, want_assign=True)

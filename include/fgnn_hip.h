@@ -759,6 +759,42 @@ long long fgnn_greedy_qap_ws_bytes(int B, int N);
 int fgnn_greedy_qap(const unsigned *bits1, const unsigned *bits2, const int *assign0, const int *nvalid, int B, int N, int T, void *ws,
                     long long ws_bytes, int *s_best2, int *acc_best, int *t_best, int *perm_best /* optional */, void *stream);
 
+/* ---- decoding a matching on real-weighted pairs (csrc/qap_weighted.hip): the fp32 twin of the section above, for what the
+ * reference's all_acc_qap / greedy_qap take besides 0/1 adjacency -- a spectral L = D^-1/2 W D^-1/2, any weighted graph ---------
+ * a1 / a2: B pairs of fp32 matrices A resp. B, row pitch ld >= N, pairs gstride >= N ld floats apart (both sides share ld and
+ * gstride; a (B, C, N, N) batch passes its channel 0 in place with gstride = C N N).  nvalid, assign and the -1 conventions are
+ * those of the bit-word entry points: pair b is the n_b x n_b corner (n_b clamped to [0, N]); NOTHING outside it is read (it may
+ * hold NaN); assign entries outside [0, n_b) contribute nothing; the entries inside the corner must be distinct.  No symmetry is
+ * assumed.  N <= FGNN_QAPW_MAX_N, B <= 65535; no entry point copies to the host, allocates or synchronises.  Every reduction has a
+ * fixed order (no float atomics): a result is bit-identical from run to run.  Where every product and partial sum is exactly
+ * representable (integer or dyadic weights with all sums below 2^24 units) every output is exact; otherwise each sum of m terms
+ * lies within gamma_m sum |terms| of its exact value, gamma_m = m u / (1 - m u), u = 2^-24 (m = n_b^2; a cost entry: m = n_b).
+ *
+ * fgnn_qapw_objective, per pair, fp32, every output optional:
+ *   qap[b]     = sum_{i,k} A[i,k] B[pi(i),pi(k)]  (all_acc_qap's qap)
+ *   trace[b]   = sum_{i,k} A[i,k] B[pi(k),pi(i)] = trace(A P B P^T) = 2 x the first value of score(); != qap when neither matrix is
+ *                symmetric
+ *   qap / trace are the sentinel -1 if an assign entry of the corner is outside [0, n_b): -1 is then NOT a value (weights may be
+ *                negative, so a caller that cannot rule such entries out must look at assign itself)
+ *   planted[b] = sum A o B,  na[b] = sum A,  nb[b] = sum B  (score() returns na / 2 and nb / 2)
+ * fgnn_qapw_improve_cost: cost[b][i][j] = -(sum_k A[i,k] B[pi(k),j]) = (-A P B)[i][j] of improve(), written to the n_b x n_b corner of
+ *   the layout fgnn_lsap_accuracy reads (row pitch cost_ld >= N, pairs bstride >= N cost_ld apart); nothing outside the corner is
+ *   written.  A GEMM with a row-gathered right operand on v_mfma_f32_32x32x2_f32 (fp32 in, fp32 accumulate: an fmaf chain over k
+ *   upwards), gathered rows staged through LDS; grid (ceil(N/32), ceil(N/128), B).
+ * fgnn_greedy_qapw: greedy_qap(A, B, P(assign0), T) for every pair as a chain of launches on `stream` (per round: improve cost ->
+ *   the solver of fgnn_lsap_accuracy -> trace -> keep if strictly better), scratch from ws (fgnn_greedy_qapw_ws_bytes bytes, 16-byte
+ *   aligned): capturable.  Order of events and quirk as fgnn_greedy_qap.  Outputs: s_best fp32 = trace / 2 (the halving is exact),
+ *   acc_best, t_best int32, perm_best (B, N; optional) with the semantics of fgnn_greedy_qap.  A pair with n_b = 0 yields zeros. */
+#define FGNN_QAPW_MAX_N 256
+int fgnn_qapw_objective(const float *a1, const float *a2, long long gstride, int ld, const int *assign, const int *nvalid, int B, int N,
+                        float *qap, float *trace, float *planted, float *na, float *nb, void *stream);
+int fgnn_qapw_improve_cost(const float *a1, const float *a2, long long gstride, int ld, const int *assign, const int *nvalid, int B, int N,
+                           float *cost, long long bstride, int cost_ld, void *stream);
+long long fgnn_greedy_qapw_ws_bytes(int B, int N);
+int fgnn_greedy_qapw(const float *a1, const float *a2, long long gstride, int ld, const int *assign0, const int *nvalid, int B, int N, int T,
+                     void *ws, long long ws_bytes, float *s_best, int *acc_best, int *t_best, int *perm_best /* optional */,
+                     void *stream);
+
 /* ---- spectral input features (csrc/spectral.hip; loaders/data_generator.py:221-232 make_laplacian / make_spectral_feature, the
  * input of QAP_spectralGenerator) ---------------------------------------------------------------------------------------------
  * bits: (G, N, ceil(N/32)) words, bit j of word row i = W[i][j] (the layout of fgnn_expand_adjacency); nvalid (optional, int32[G]):
