@@ -238,6 +238,8 @@ _SIGNATURES = {
     'fgnn_lsap_accuracy': [_VP, _LL, _I, _VP, _I, _I, _VP, _VP, _VP],
     'fgnn_pairgen_supported': [_I, _I, _I],
     'fgnn_pairgen': [C.POINTER(PairgenArgs), _VP],
+    'fgnn_pairgen_indexed': [C.POINTER(PairgenArgs), _VP, _VP],
+    'fgnn_epoch_index': [C.c_ulonglong, C.c_ulonglong, _LL, _LL, _LL, _VP, _VP],
     'fgnn_qap_objective': [_VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP],
     'fgnn_qap_improve_cost': [_VP, _VP, _VP, _VP, _I, _I, _VP, _LL, _I, _VP],
     'fgnn_greedy_qap_ws_bytes': [_I, _I],

@@ -10,6 +10,9 @@
 // precomputed one per lane and read back by readlane.  Inside a chain LDS is written by single instructions of a few lanes
 // (atomics without return: nothing waits for them); a wave's LDS accesses complete in issue order, so the next step's reads see
 // those writes without a barrier.
+//
+// Which pair a workgroup builds is first + b (fgnn_pairgen) or index[b] (fgnn_pairgen_indexed); fgnn_epoch_index, at the end of the
+// file, writes such an index list: a window of the shuffled order of an epoch.
 #include "fgnn_common.h"
 
 namespace {
@@ -23,10 +26,10 @@ struct P4 {
     unsigned long long v0, v1, v2, v3;
 };
 
-// Random123 Philox4x64-10 (Salmon et al., SC'11) on counter (c0, c1, c2, 0), key (k0, 0)
-DEVI P4 philox(unsigned long long c0, unsigned long long c1, unsigned long long c2, unsigned long long k0) {
+// Random123 Philox4x64-10 (Salmon et al., SC'11) on counter (c0, c1, c2, c3), key (k0, 0); c3 = 0 for every pair stream
+DEVI P4 philox(unsigned long long c0, unsigned long long c1, unsigned long long c2, unsigned long long k0, unsigned long long c3 = 0) {
     const unsigned long long M0 = 0xD2E7470EE14C6C93ull, M1 = 0xCA5A826395121157ull;
-    unsigned long long c3 = 0, k1 = 0;
+    unsigned long long k1 = 0;
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         if (r) {
@@ -332,14 +335,24 @@ DEVI void noise_edge_swap(unsigned *rq, int W, const unsigned short *edges, int 
 
 struct KArgs {
     fgnn_pairgen_args a;
-    int emax;      // edge-list entries in LDS
+    int emax;                    // edge-list entries in LDS
+    const long long *index;      // INDEXED: the pair of workgroup b is index[b]
 };
 
+// INDEXED: the pair of workgroup b is index[b] (fgnn_pairgen_indexed), else first + b (fgnn_pairgen: the kernel as it always was)
+template <bool INDEXED>
 __global__ __launch_bounds__(PG_THREADS) void pairgen_kernel(KArgs ka) {
     extern __shared__ unsigned smem[];
     const fgnn_pairgen_args &a = ka.a;
     const int N = a.N, W = (N + 31) >> 5, lane = threadIdx.x;
-    const Pair pr{a.seed, (unsigned long long)(a.first + blockIdx.x)};
+    const long long k = INDEXED ? ka.index[blockIdx.x] : a.first + blockIdx.x;
+    if (INDEXED && k < 0) {      // a caller error (fgnn_pairgen_indexed): the empty graph, wave-uniform exit before any barrier
+        const long long off = (long long)blockIdx.x * N * W;
+        for (int i = lane; i < N * W; i += PG_THREADS) a.bits1[off + i] = a.bits2[off + i] = 0;
+        if (a.nvalid && lane == 0) a.nvalid[blockIdx.x] = 0;
+        return;
+    }
+    const Pair pr{a.seed, (unsigned long long)k};
     unsigned *rp = smem, *rq = smem + N * W;
     unsigned char *perm = (unsigned char *)(rq + N * W), *inv = perm + 256;    // BA: mark = perm
     unsigned short *edges = (unsigned short *)(inv + 256);
@@ -396,7 +409,7 @@ int host_regular_degree(int n, double p) {
     return d;
 }
 
-LdsAttrCache g_pairgen_lds;
+LdsAttrCache g_pairgen_lds, g_pairgen_indexed_lds;
 
 }  // namespace
 
@@ -404,12 +417,15 @@ extern "C" int fgnn_pairgen_supported(int N, int family, int noise_model) {
     return N >= 1 && N <= FGNN_PAIRGEN_MAX_N && family >= 0 && family <= 2 && noise_model >= 0 && noise_model <= 1;
 }
 
-extern "C" int fgnn_pairgen(const fgnn_pairgen_args *args, void *stream) {
+// the checks and the launch shared by fgnn_pairgen (index = NULL) and fgnn_pairgen_indexed
+static int launch_pairgen(const fgnn_pairgen_args *args, const long long *index, bool indexed, void *stream) {
     FGNN_CHECK(args, "fgnn_pairgen: NULL arguments");
     const fgnn_pairgen_args &a = *args;
     FGNN_CHECK(fgnn_pairgen_supported(a.N, a.family, a.noise_model), "fgnn_pairgen: unsupported N=%d family=%d noise_model=%d",
                a.N, a.family, a.noise_model);
-    FGNN_CHECK(a.B >= 0 && a.first >= 0 && a.bits1 && a.bits2, "fgnn_pairgen: bad arguments (B=%d, first=%lld)", a.B, a.first);
+    FGNN_CHECK(a.B >= 0 && (indexed || a.first >= 0) && a.bits1 && a.bits2, "fgnn_pairgen: bad arguments (B=%d, first=%lld)", a.B,
+               a.first);
+    FGNN_CHECK(!indexed || index || a.B == 0, "fgnn_pairgen_indexed: NULL index for B=%d pairs", a.B);
     FGNN_CHECK(a.edge_density >= 0.0 && a.edge_density < 1.0, "fgnn_pairgen: edge_density %g outside [0, 1)", a.edge_density);
     FGNN_CHECK(a.swaps_per_edge >= 0 && a.swaps_per_edge <= 10000, "fgnn_pairgen: swaps_per_edge %d outside [0, 10000]",
                a.swaps_per_edge);
@@ -432,11 +448,71 @@ extern "C" int fgnn_pairgen(const fgnn_pairgen_args *args, void *stream) {
     const int W = (N + 31) / 32;
     const size_t lds = (size_t)2 * N * W * 4 + 512 + (size_t)((emax + 1) & ~1ll) * 2 + (size_t)rep;
     FGNN_CHECK(lds <= 160 * 1024, "fgnn_pairgen: %zu bytes of LDS needed", lds);
-    FGNN_CHECK(fgnn_raise_lds(g_pairgen_lds, (const void *)pairgen_kernel, lds), "fgnn_pairgen: cannot raise LDS to %zu bytes", lds);
+    FGNN_CHECK(fgnn_raise_lds(indexed ? g_pairgen_indexed_lds : g_pairgen_lds,
+                              indexed ? (const void *)pairgen_kernel<true> : (const void *)pairgen_kernel<false>, lds),
+               "fgnn_pairgen: cannot raise LDS to %zu bytes", lds);
     KArgs ka;
     ka.a = a;
     ka.emax = (int)emax;
-    hipLaunchKernelGGL(pairgen_kernel, dim3((unsigned)a.B), dim3(PG_THREADS), lds, (hipStream_t)stream, ka);
+    ka.index = indexed ? index : nullptr;
+    if (indexed)
+        hipLaunchKernelGGL(pairgen_kernel<true>, dim3((unsigned)a.B), dim3(PG_THREADS), lds, (hipStream_t)stream, ka);
+    else
+        hipLaunchKernelGGL(pairgen_kernel<false>, dim3((unsigned)a.B), dim3(PG_THREADS), lds, (hipStream_t)stream, ka);
+    FGNN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int fgnn_pairgen(const fgnn_pairgen_args *args, void *stream) { return launch_pairgen(args, nullptr, false, stream); }
+
+extern "C" int fgnn_pairgen_indexed(const fgnn_pairgen_args *args, const long long *index, void *stream) {
+    return launch_pairgen(args, index, true, stream);
+}
+
+// ---- the order of a shuffled epoch (include/fgnn_hip.h; tests/epoch_ref.py restates it in numpy, bit for bit) -----------------
+namespace {
+
+constexpr int EP_THREADS = 256;
+
+// one pass of the balanced Feistel network on 2 h bits: a bijection of [0, 4^h) whatever the round function returns
+DEVI unsigned long long feistel(unsigned long long x, int h, unsigned long long seed, unsigned long long epoch) {
+    const unsigned long long mask = (1ull << h) - 1;
+    unsigned long long L = x >> h, R = x & mask;
+#pragma unroll
+    for (int r = 0; r < FGNN_EPOCH_ROUNDS; ++r) {
+        const unsigned long long f = philox(epoch, (unsigned long long)r, R, seed, FGNN_EPOCH_STREAM).v0 & mask;
+        const unsigned long long t = L ^ f;
+        L = R;
+        R = t;
+    }
+    return (L << h) | R;
+}
+
+__global__ __launch_bounds__(EP_THREADS) void epoch_index_kernel(unsigned long long seed, unsigned long long epoch,
+                                                                unsigned long long M, unsigned long long first_pos, int count, int h,
+                                                                long long *out) {
+    const int i = blockIdx.x * EP_THREADS + threadIdx.x;
+    if (i >= count) return;
+    unsigned long long x = (first_pos + (unsigned long long)i) % M;
+    do x = feistel(x, h, seed, epoch);      // x < M lies on a cycle of the bijection that comes back below M: the walk ends
+    while (x >= M);
+    out[i] = (long long)x;
+}
+
+}  // namespace
+
+extern "C" int fgnn_epoch_index(unsigned long long seed, unsigned long long epoch, long long M, long long first_pos, long long count,
+                                long long *out, void *stream) {
+    FGNN_CHECK(M >= 1 && M <= (1ll << FGNN_EPOCH_MAX_LOG2_M), "fgnn_epoch_index: M=%lld outside [1, 2^%d]", M, FGNN_EPOCH_MAX_LOG2_M);
+    FGNN_CHECK(count >= 0 && count < (1ll << 31), "fgnn_epoch_index: count=%lld outside [0, 2^31)", count);
+    FGNN_CHECK(first_pos >= 0 && first_pos <= (1ll << 62), "fgnn_epoch_index: first_pos=%lld outside [0, 2^62]", first_pos);
+    if (count == 0) return 0;
+    FGNN_CHECK(out, "fgnn_epoch_index: NULL output");
+    int bits = 0;
+    while ((1ll << bits) < M) ++bits;
+    const int h = std::max(1, (bits + 1) / 2);
+    hipLaunchKernelGGL(epoch_index_kernel, dim3((unsigned)((count + EP_THREADS - 1) / EP_THREADS)), dim3(EP_THREADS), 0,
+                       (hipStream_t)stream, seed, epoch, (unsigned long long)M, (unsigned long long)first_pos, (int)count, h, out);
     FGNN_LAUNCH_CHECK();
     return 0;
 }

@@ -18,10 +18,16 @@ Semantics follow the reference:
 * the pair is not permuted: the ground truth is the identity (``triplet_loss``).
 
 Randomness is counter-based (Philox4x64-10 keyed by ``seed``): every draw is addressed by (pair index, stream, position), so
-pair k of a dataset is the same however a range is split into calls, devices or ranks -- data-parallel rank r of w takes
-pairs ``step * B * w + r * B ...`` with no communication.  Streams: 0 size, 1 parent, 2 noise-1, 3 noise-2, 4 relabel,
-5 swap chain / attachment.  Probabilities are integer thresholds ``min(2^32, floor(prob * 2^32))`` compared with raw 32-bit
+pair k of a dataset is the same however a range is split into calls, devices or ranks.  Streams: 0 size, 1 parent, 2 noise-1,
+3 noise-2, 4 relabel, 5 swap chain / attachment, all with 0 in the fourth counter word; number 6 in that word belongs to the
+epoch permutation (``sampler.py``).  Probabilities are integer thresholds ``min(2^32, floor(prob * 2^32))`` compared with raw 32-bit
 draws; integers in [0, k) are ``(u32 * k) >> 32`` (``tests/pairgen_ref.py`` restates it all in numpy, bit for bit).
+
+Which pairs: a contiguous range ``(first, count)``, or any pairs by ``index=`` (an int64 tensor of dataset indices in any order,
+duplicates allowed; one launch, ``fgnn_pairgen_indexed``).  The rank split: global step s of batch size B on w ranks covers positions
+``[s * B * w, (s + 1) * B * w)`` of the epoch order and rank r takes ``r * B ... r * B + B - 1`` of them, with no communication.
+For an endless dataset the order is the identity (``bits(step * B * w + r * B, B)``); for the reference's fixed dataset reshuffled
+every epoch ``sampler.EpochSampler.batch_index`` gives the indices of those positions (``FgnnTrainer.train_epoch``).
 
 There is no CPU fallback (``_lib``).
 """
@@ -92,14 +98,31 @@ class PairGenerator:
                    edge_density=cfg['edge_density'], noise=cfg['noise'], vertex_proba=cfg.get('vertex_proba', 1.0),
                    seed=seed, **kw)
 
-    def bits(self, first, count):
-        """Pairs first .. first + count - 1 -> (bits1, bits2, nvalid): (count, N, ceil(N/32)) int32 device tensors and, when the
-        vertex count is binomial, the (count,) int32 vertex counts (else None).  Enqueued on the current stream."""
+    def _selection(self, first, count, index):
+        """(first, count, None) of a contiguous range, or (0, len(index), index as a contiguous int64 tensor on the device)."""
+        if index is None:
+            if first is None or count is None:
+                raise ValueError('give either (first, count) or index=')
+            first, count = int(first), int(count)
+            if first < 0 or count < 0:
+                raise ValueError('first and count must be >= 0, got %d, %d' % (first, count))
+            return first, count, None
+        if first is not None or count is not None:
+            raise ValueError('give either (first, count) or index=, not both')
+        if not torch.is_tensor(index):
+            index = torch.tensor(index, dtype=torch.int64)
+        if index.dim() != 1 or index.dtype != torch.int64:
+            raise ValueError('index must be a 1-D int64 tensor, got shape %s, %s' % (tuple(index.shape), index.dtype))
+        return 0, index.numel(), index.to(self.device).contiguous()
+
+    def bits(self, first=None, count=None, index=None):
+        """Pairs first .. first + count - 1, or the pairs index[0], index[1], ... (a 1-D int64 tensor, or a list; moved to the device
+        if it is not there; any order, duplicates allowed) -> (bits1, bits2, nvalid): (count, N, ceil(N/32)) int32 device tensors
+        and, when the vertex count is binomial, the (count,) int32 vertex counts (else None).  Enqueued on the current stream; the
+        index is not read on the host: a negative entry (a caller error) gives the empty graph, all words zero and nvalid = 0."""
         if self.device.type != 'cuda':
             raise RuntimeError('PairGenerator: device %s; the generator runs on the GPU only (there is no CPU path)' % (self.device,))
-        first, count = int(first), int(count)
-        if first < 0 or count < 0:
-            raise ValueError('first and count must be >= 0, got %d, %d' % (first, count))
+        first, count, index = self._selection(first, count, index)
         N = self.n_vertices
         W = (N + 31) // 32
         with torch.cuda.device(self.device):
@@ -115,14 +138,18 @@ class PairGenerator:
                 a.swaps_per_edge = self.swaps_per_edge
                 a.bits1, a.bits2 = b1.data_ptr(), b2.data_ptr()
                 a.nvalid = nv.data_ptr() if nv is not None else None
-                _lib.call('fgnn_pairgen', C.byref(a), _lib.stream_ptr())
+                if index is None:
+                    _lib.call('fgnn_pairgen', C.byref(a), _lib.stream_ptr())
+                else:
+                    _lib.call('fgnn_pairgen_indexed', C.byref(a), _lib.ptr(index), _lib.stream_ptr())
         return b1, b2, nv
 
-    def dense(self, first, count):
+    def dense(self, first=None, count=None, index=None):
         """The reference's collate structures for the same pairs: ({'input': x1}, {'input': x2}) with (count, 2, N, N) fp32
         tensor representations (collate_fn_pair_explore) for a constant vertex count, else two MaskedTensors padded to the
         largest n_i of the batch (collate_fn_pair; one host sync for that size)."""
-        b1, b2, nv = self.bits(first, count)
+        b1, b2, nv = self.bits(first, count, index)
+        count = b1.shape[0]
         N = self.n_vertices
         x1, x2 = expand_adjacency(b1, N, nv), expand_adjacency(b2, N, nv)
         if nv is None:
@@ -131,13 +158,14 @@ class PairGenerator:
         x1, x2 = x1[:, :, :n, :n].contiguous(), x2[:, :, :n, :n].contiguous()
         return MaskedTensor(x1, nv, (2, 3), 'N'), MaskedTensor(x2, nv, (2, 3), 'M')
 
-    def spectral(self, first, count, n_powers=4):
+    def spectral(self, first=None, count=None, n_powers=4, index=None):
         """The twin of `dense` for the reference's ``QAP_spectralGenerator`` (loaders/data_generator.py:221-277): the same pairs as
         `bits`, each side as the n_powers channels L, L^2, ... of ``spectral.spectral_features`` (one launch per side, straight from
         the bit rows; an isolated vertex gives a zero row and column where the reference gives NaN).  ({'input': F1}, {'input': F2})
         with (count, n_powers, N, N) fp32 tensors for a constant vertex count, else two MaskedTensors written directly at the
         largest n_i of the batch (one host sync for that size), with the names and masked dims of `dense`."""
-        b1, b2, nv = self.bits(first, count)
+        b1, b2, nv = self.bits(first, count, index)
+        count = b1.shape[0]
         if nv is None:
             return {'input': spectral_features(b1, None, n_powers)}, {'input': spectral_features(b2, None, n_powers)}
         n = max(int(nv.max().item()), 1) if count else 1

@@ -321,6 +321,19 @@ class FgnnTrainer:
         scores, _ = eng.step(self.params, self.grads, None, nvalid=nv, total_nodes=1.0, loss_out=self._loss_sum, bits=b)
         return self._reduce_and_update(), scores
 
+    def train_epoch(self, generator, sampler, epoch, batch_size):
+        """One epoch over a fixed dataset of on-device pairs, in the sampler's order (the reference's shuffled DataLoader over
+        num_examples_train pairs): per step ``train_step_bits(*generator.bits(index=sampler.batch_index(epoch, step, batch_size)))``.
+        generator: pairgen.PairGenerator; sampler: sampler.EpochSampler (its rank and world size are this process's).  The loop reads
+        nothing back (a ragged generator's vertex counts stay on the device as well).  Returns the (steps,) device tensor of the
+        per-step losses of the global batch."""
+        steps = sampler.steps_per_epoch(batch_size)
+        losses = torch.empty(steps, dtype=torch.float32, device=self.params.device)
+        for step in range(steps):
+            loss, _ = self.train_step_bits(*generator.bits(index=sampler.batch_index(epoch, step, batch_size)))
+            losses[step].copy_(loss)
+        return losses
+
     def train_step(self, x1, x2, nvalid=None):
         """x1, x2: (B, c0, N, N) local shard on the GPU.  Returns (loss of the global batch as a device
         scalar, scores of the local shard)."""

@@ -726,6 +726,23 @@ typedef struct {
 /* 1 if (N, family, noise_model) is a shape fgnn_pairgen runs */
 int fgnn_pairgen_supported(int N, int family, int noise_model);
 int fgnn_pairgen(const fgnn_pairgen_args *args, void *stream);
+/* The same launch with pair b = dataset pair index[b] (int64[B] on the device; any order, duplicates allowed): args->first is
+ * ignored, every stream, draw and output is that of the contiguous launch for the same pair.  A negative index is a caller error:
+ * its pair is written as the empty graph (all words zero, nvalid = 0) and nothing outside index[0..B) is read. */
+int fgnn_pairgen_indexed(const fgnn_pairgen_args *args, const long long *index, void *stream);
+
+/* ---- the order of a shuffled epoch (csrc/pairgen.hip; graph_neural_net_amd/sampler.py) ---------------------------------------
+ * out[i] = pi((first_pos + i) mod M) for i < count, with pi the permutation of [0, M) that (seed, epoch) select: a balanced Feistel
+ * network on 2 h bits (h = max(1, ceil(ceil(log2 M) / 2))), FGNN_EPOCH_ROUNDS rounds, walked along its cycle until the value is
+ * < M.  The round function of round r on right half R is the low h bits of word 0 of Philox4x64-10 at counter
+ * (epoch, r, R, FGNN_EPOCH_STREAM) under key (seed, 0) -- the fourth counter word of every pair stream is 0, so the two never
+ * meet.  O(1) per position, no M-sized temporary: position p of epoch e is the same however the epoch is cut into launches or
+ * ranks.  1 <= M <= 2^40, first_pos >= 0, 0 <= count < 2^31; out is int64[count] on the device. */
+#define FGNN_EPOCH_ROUNDS 8
+#define FGNN_EPOCH_STREAM 6
+#define FGNN_EPOCH_MAX_LOG2_M 40
+int fgnn_epoch_index(unsigned long long seed, unsigned long long epoch, long long M, long long first_pos, long long count,
+                     long long *out, void *stream);
 
 /* ---- decoding a matching: QAP objective and greedy refinement (csrc/qap.hip; toolbox/metrics.py:168-193 all_acc_qap,
  * toolbox/utils.py:225-256 perm_matrix / score / improve / greedy_qap) --------------------------------------------------------
