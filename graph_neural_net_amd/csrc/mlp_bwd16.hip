@@ -1,133 +1,14 @@
-// bf16 variant of the fused MlpBlock_Real backward (autograd of models/layers.py:126-131 with the GraphNorm backward of
-// :68-80 folded into the load of dz) for gfx950.  Storage bf16, matrix work on v_mfma_f32_32x32x16_bf16, fp32 accumulation of
-// every parameter gradient.  See mlp_fwd16.hip for the tile / fragment conventions (64-element tiles = 32 pixel pairs, two
-// 32-column problems E / O per tile).
-//
-// Per tile and per pixel group:
-//   1. recompute the hidden activations h_0 .. h_{d-2} with the forward's in-register chain (bf16 operands);
-//   2. dz = R(ca*dy + cb*(z - mean) + cc)                                  (coef from fgnn_gn_bwd_coef*)
-//   3. for l = d-1 .. 0:  dW_l += dpre_l (x) in_l,  db_l += dpre_l,  d in_l = R(W_l)^T dpre_l,
-//                         dpre_{l-1} = R(d in_l * [h_{l-1} > 0])
-//   4. dx = R(d in_0 (+ old dx)), optionally the per-tile sums {sum dx, sum dx (z_in - mean_in)} of the rounded values.
-// The weight-gradient products contract over pixels and need lane = channel operands.  They are NOT staged through LDS:
-// a fragment is transposed by multiplying it with an identity matrix on the (otherwise idle) matrix pipe
-// (fgnn_bf16.h: transpose16, exact), which also yields the bias gradients as register sums.
-// dW/db accumulate in registers over the wave's statically assigned tiles; the eight waves of a workgroup are summed through
-// LDS in a fixed order and one partial per workgroup is written for fgnn_grad_finalize: bit-reproducible run to run.
+// bf16 variant of the fused MlpBlock_Real backward for gfx950, one MLP per launch.  The per-tile algorithm and its rounding
+// points are described in fgnn_bwd16.h, which also holds what this kernel shares with its mlp1 + mlp2 pair twin
+// (mlp_bwd16_pair.hip): the LDS layout, the parked accumulator tiles, the per-graph record fetch and the phases of a pixel group
+// that are plain functions of their operands.  This kernel's own: a second input slab (CB), ragged batches (SKIP), the slab-b
+// gradient and the two forms of per-tile sums it emits with the slab-a gradient.
 #include <type_traits>
-#include "fgnn_bf16.h"
+#include "fgnn_bwd16.h"
+
+using namespace bwd16;
 
 namespace {
-
-#ifndef FGNN_NWB
-#define FGNN_NWB 8
-#endif
-constexpr int NWB = FGNN_NWB;    // waves per workgroup (2 per SIMD)
-constexpr int BWD16_WG = 256;   // persistent workgroups (partials layout shared with the fp32 path)
-
-template <int CA, int CB, int DEPTH>
-struct Bwd16Layout {
-    static constexpr Pk16 PK = pk16_layout(1, CA, CB, DEPTH);
-    static constexpr int WEIGHT_F = PK.floats;
-    static constexpr int REC_F = 64 + 64 + 128;                     // per wave: {a, b'} slab a, slab b, {mean, ca, cb, cc}
-    static constexpr int PCOUNT = 32 * (CA + CB) + 32 + (DEPTH - 1) * (32 * 32 + 32);
-    static constexpr int MAIN_F = WEIGHT_F + NWB * REC_F;
-    // Weight-gradient accumulator tiles kept in LDS between the tiles of the loop ("parked") instead of in registers: the
-    // variants that would otherwise spill them to scratch (the 64-input-channel kernel needs four 32x32 fp32 accumulators on
-    // top of everything else).  A scratch reload retires in order with the prefetch loads in flight and stalls behind them;
-    // LDS does not, and ~130 KB of it are idle here.  Slots in order of use: dW_2, dW_1, dW_0 (slab a), dW_0 (slab b).
-    static constexpr int NPARK = (CA >= 32 && CB >= 32) ? 4 : (CA >= 32 && CB > 0) ? 2 : (CA >= 32 ? 1 : 0);
-    static constexpr int PARK_OFF = (MAIN_F + 3) & ~3;
-    static constexpr int PARK_F = NWB * NPARK * 1024;
-    static constexpr int RED_F = NWB * PCOUNT;
-    static constexpr int LDS_F = PARK_OFF + PARK_F > RED_F ? PARK_OFF + PARK_F : RED_F;
-};
-
-// a parked accumulator tile: [4][64 lanes][4 floats] -> conflict-free 16-byte accesses
-DEVI f32x16 park_get(const float *slot, int lane) {
-    f32x16 v;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 t = reinterpret_cast<const float4 *>(slot)[q * 64 + lane];
-        v[4 * q] = t.x;
-        v[4 * q + 1] = t.y;
-        v[4 * q + 2] = t.z;
-        v[4 * q + 3] = t.w;
-    }
-    return v;
-}
-DEVI void park_put(float *slot, int lane, const f32x16 &v) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        reinterpret_cast<float4 *>(slot)[q * 64 + lane] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-}
-
-// (the base pointers pass through an empty asm: the per-lane 64-bit addresses of these once-per-graph loads are then formed here, in
-// the rarely taken branch, instead of being hoisted out of the tile loop -- where they were the kernel's only spilled registers)
-template <typename T>
-DEVI const T *opaque_ptr(const T *p) {
-    asm volatile("" : "+s"(p));
-    return p;
-}
-DEVI void fetch_rec2(float *rec, const fgnn_slab16 &s, int g, int lane) {
-    if (lane < 32) {
-        float2 o = make_float2(1.f, 0.f);
-        if (s.nrm && lane < s.C) {
-            const float4 n = reinterpret_cast<const float4 *>(opaque_ptr(s.nrm))[(long long)g * s.C + lane];
-            const float be = s.beta ? opaque_ptr(s.beta)[lane] : 0.f;
-            o.x = n.y;
-            o.y = be - n.x * n.y;
-        }
-        reinterpret_cast<float2 *>(rec)[lane] = o;
-    }
-}
-
-// normal fragments (even / odd pixel) of a 32-channel slab, normalised; `raw*` = the un-normalised fragments
-DEVI void operands32b(F16 &e, F16 &o, F16 &rawE, F16 &rawO, const unsigned (&x)[16], const float *rec, bool norm, int h) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        rawE.d[q] = pack_lo(x[2 * q], x[2 * q + 1]);
-        rawO.d[q] = pack_hi(x[2 * q], x[2 * q + 1]);
-    }
-    if (norm) {
-        const float2 *r2 = reinterpret_cast<const float2 *>(rec);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const float2 n0 = r2[ch_of(2 * q, h)], n1 = r2[ch_of(2 * q + 1, h)];
-            e.d[q] = cvt_pk(fmaf(bf_lo(x[2 * q]), n0.x, n0.y), fmaf(bf_lo(x[2 * q + 1]), n1.x, n1.y));
-            o.d[q] = cvt_pk(fmaf(bf_hi(x[2 * q]), n0.x, n0.y), fmaf(bf_hi(x[2 * q + 1]), n1.x, n1.y));
-        }
-    } else {
-        e = rawE;
-        o = rawO;
-    }
-}
-DEVI void operands2b(F16 &e, F16 &o, const unsigned (&x)[2]) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) e.d[q] = o.d[q] = 0u;
-    e.d[0] = pack_lo(x[0], x[1]);
-    o.d[0] = pack_hi(x[0], x[1]);
-}
-
-// transposed, normalised operand of one pixel group: lane = channel, y^T = R(x^T * a_lane + b_lane)
-DEVI F16 transposed_input(const F16 &raw, const F16 &ident, bool norm, float la, float lb) {
-    const f32x16 t = transpose16(raw, ident);
-    F16 f;
-    if (norm) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) f.d[q] = cvt_pk(fmaf(t[2 * q], la, lb), fmaf(t[2 * q + 1], la, lb));
-    } else {
-        pack_acc(f, t);
-    }
-    return f;
-}
-
-DEVI float sum16(const f32x16 &t) {
-    float s = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s += t[r];
-    return s;
-}
 
 // SKIP (ragged batches with A.ranges): work-balanced tile range from fgnn_ragged_tile_ranges16; the waves step over tiles
 // without a valid element (no contribution to the parameter gradients, dx not written there); such a tile only gets an empty
@@ -139,7 +20,7 @@ __global__ __launch_bounds__(64 * NWB, NWB / 4) void mlp_bwd16_kernel(const fgnn
     extern __shared__ __attribute__((aligned(16))) float smem[];
     using L = Bwd16Layout<CA, CB, DEPTH>;
     constexpr Pk16 PK = L::PK;
-    constexpr int CIN = CA + CB, SA = pk16_steps(CA), SB = pk16_steps(CB);
+    constexpr int CIN = CA + CB;
     constexpr int XA = CA >= 32 ? 16 : 2, XB = CB >= 32 ? 16 : 2;
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int j = lane & 31, h = lane >> 5;
@@ -204,8 +85,8 @@ __global__ __launch_bounds__(64 * NWB, NWB / 4) void mlp_bwd16_kernel(const fgnn
     int cached_g = -1, cur_nv = A.N;
     float la_a = 1.f, la_b = 0.f, lb_a = 1.f, lb_b = 0.f, la_mean = 0.f;      // lane-channel constants (transposed layout)
     auto graph_change = [&](int g) {
-        fetch_rec2(recA, A.a, g, lane);
-        if constexpr (CB > 0) fetch_rec2(recB, A.b, g, lane);
+        fetch_rec2<true>(recA, A.a, g, lane);
+        if constexpr (CB > 0) fetch_rec2<true>(recB, A.b, g, lane);
         if (lane < 32) reinterpret_cast<float4 *>(recK)[lane] = reinterpret_cast<const float4 *>(opaque_ptr(A.coef))[(long long)g * FGNN_H + lane];
         cached_g = g;
         cur_nv = __builtin_amdgcn_readfirstlane(nvalid_of(A.nvalid, g, A.N));
@@ -277,85 +158,50 @@ __global__ __launch_bounds__(64 * NWB, NWB / 4) void mlp_bwd16_kernel(const fgnn
         // scheduling barrier: interleaving them doubles the live fragments and spills.
         auto group = [&](auto tag) {
             constexpr int GRP = decltype(tag)::value;
-            auto half = [](unsigned d) { return GRP ? bf_hi(d) : bf_lo(d); };
-            auto pack2 = [](unsigned a, unsigned b) { return GRP ? pack_hi(a, b) : pack_lo(a, b); };
             const float fv = GRP ? (v1 ? 1.f : 0.f) : (v0 ? 1.f : 0.f);
             // ---- input operands: normal (recompute) and transposed (layer-0 weight gradient) ----
             F16 ya, yb, raw_a, yTa, yTb;
             if constexpr (CA >= 32) {
-#pragma unroll
-                for (int q = 0; q < 8; ++q) raw_a.d[q] = pack2(xa[2 * q], xa[2 * q + 1]);
+                raw_fragment<GRP>(raw_a, xa);
                 if (normA) {
                     const float2 *r2 = reinterpret_cast<const float2 *>(recA);
 #pragma unroll
                     for (int q = 0; q < 8; ++q) {
                         const float2 n0 = r2[ch_of(2 * q, h)], n1 = r2[ch_of(2 * q + 1, h)];
-                        ya.d[q] = cvt_pk(fmaf(half(xa[2 * q]), n0.x, n0.y), fmaf(half(xa[2 * q + 1]), n1.x, n1.y));
+                        ya.d[q] = cvt_pk(fmaf(half_of<GRP>(xa[2 * q]), n0.x, n0.y), fmaf(half_of<GRP>(xa[2 * q + 1]), n1.x, n1.y));
                     }
                 } else {
                     ya = raw_a;
                 }
                 yTa = transposed_input(raw_a, ident, normA, la_a, la_b);
             } else {
-#pragma unroll
-                for (int q = 0; q < 8; ++q) ya.d[q] = 0u;
-                ya.d[0] = pack2(xa[0], xa[1]);
+                narrow_fragment<GRP>(ya, xa);
                 yTa = transposed_input(ya, ident, false, 1.f, 0.f);
             }
             if constexpr (CB >= 32) {
                 F16 raw_b;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) raw_b.d[q] = pack2(xb[2 * q], xb[2 * q + 1]);
+                raw_fragment<GRP>(raw_b, xb);
                 if (normB) {
                     const float2 *r2 = reinterpret_cast<const float2 *>(recB);
 #pragma unroll
                     for (int q = 0; q < 8; ++q) {
                         const float2 n0 = r2[ch_of(2 * q, h)], n1 = r2[ch_of(2 * q + 1, h)];
-                        yb.d[q] = cvt_pk(fmaf(half(xb[2 * q]), n0.x, n0.y), fmaf(half(xb[2 * q + 1]), n1.x, n1.y));
+                        yb.d[q] = cvt_pk(fmaf(half_of<GRP>(xb[2 * q]), n0.x, n0.y), fmaf(half_of<GRP>(xb[2 * q + 1]), n1.x, n1.y));
                     }
                 } else {
                     yb = raw_b;
                 }
                 yTb = transposed_input(raw_b, ident, normB, lb_a, lb_b);
             } else if constexpr (CB > 0) {
-#pragma unroll
-                for (int q = 0; q < 8; ++q) yb.d[q] = 0u;
-                yb.d[0] = pack2(xb[0], xb[1]);
+                narrow_fragment<GRP>(yb, xb);
                 yTb = transposed_input(yb, ident, false, 1.f, 0.f);
             }
 
-            // ---- forward recompute: h_0 .. h_{d-2} ----
             F16 hs[DEPTH - 1];
-            {
-                f32x16 acc;
-                load_bias16(acc, tail, 0, h);
-#pragma unroll
-                for (int t = 0; t < SA; ++t) acc = mfma16(lds_step(wl, PK.off_w0a + t, lane), step_of(ya, t), acc);
-#pragma unroll
-                for (int t = 0; t < SB; ++t) acc = mfma16(lds_step(wl, PK.off_w0b + t, lane), step_of(yb, t), acc);
-                pack_acc_relu(hs[0], acc);
-#pragma unroll
-                for (int l = 1; l + 1 < DEPTH; ++l) {
-                    load_bias16(acc, tail, l, h);
-#pragma unroll
-                    for (int t = 0; t < 2; ++t)
-                        acc = mfma16(lds_step(wl, PK.off_wh + 2 * (l - 1) + t, lane), step_of(hs[l - 1], t), acc);
-                    pack_acc_relu(hs[l], acc);
-                }
-            }
+            recompute_hidden<CA, CB, DEPTH>(hs, ya, yb, wl, tail, lane, h);
 
-            // ---- dz from (dy, z, coef), rounded to bf16, zero in the padding ----
-            F16 d;
-            {
-                const float4 *kp = reinterpret_cast<const float4 *>(recK);
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const float4 k0 = kp[ch_of(2 * q, h)], k1 = kp[ch_of(2 * q + 1, h)];
-                    const float e0 = fmaf(k0.y, half(dyr[2 * q]), fmaf(k0.z, half(zr[2 * q]) - k0.x, k0.w));
-                    const float e1 = fmaf(k1.y, half(dyr[2 * q + 1]), fmaf(k1.z, half(zr[2 * q + 1]) - k1.x, k1.w));
-                    d.d[q] = cvt_pk(e0 * fv, e1 * fv);
-                }
-            }
+            F16 d;       // dz, zero in the padding
+            dz_of<GRP>(d, dyr, zr, recK, fv, h);
 
             // ---- hidden layers, l = DEPTH-1 .. 1 ----
 #pragma unroll
@@ -376,9 +222,7 @@ __global__ __launch_bounds__(64 * NWB, NWB / 4) void mlp_bwd16_kernel(const fgnn
                     else accum(std::integral_constant<int, 1>(), dWh[l - 1], upd);
                 }
                 {
-                    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                    f32x16 acc = mfma16(lds_step(wl, PK.off_wt + 2 * (DEPTH - 1 - l), lane), step_of(d, 0), zero);
-                    acc = mfma16(lds_step(wl, PK.off_wt + 2 * (DEPTH - 1 - l) + 1, lane), step_of(d, 1), acc);
+                    const f32x16 acc = input_grad(wl, PK.off_wt + 2 * (DEPTH - 1 - l), d, lane);
 #pragma unroll
                     for (int q = 0; q < 8; ++q) d.d[q] = cvt_pk(acc[2 * q], acc[2 * q + 1]) & pos_mask_pk(in.d[q]);
                 }
@@ -405,12 +249,10 @@ __global__ __launch_bounds__(64 * NWB, NWB / 4) void mlp_bwd16_kernel(const fgnn
             // ---- dx of slab a ----
             if constexpr (CA >= 32) {
                 if (A.dxa) {
-                    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                    f32x16 acc = mfma16(lds_step(wl, PK.off_wt0a, lane), step_of(d, 0), zero);
-                    acc = mfma16(lds_step(wl, PK.off_wt0a + 1, lane), step_of(d, 1), acc);
+                    f32x16 acc = input_grad(wl, PK.off_wt0a, d, lane);
                     if (rmw_a) {
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[r] += half(olda[r]);
+                        for (int r = 0; r < 16; ++r) acc[r] += half_of<GRP>(olda[r]);
                     }
                     F16 v;
                     pack_acc(v, acc);
@@ -452,12 +294,10 @@ __global__ __launch_bounds__(64 * NWB, NWB / 4) void mlp_bwd16_kernel(const fgnn
             // ---- dx of slab b ----
             if constexpr (CB >= 32) {
                 if (A.dxb) {
-                    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                    f32x16 acc = mfma16(lds_step(wl, PK.off_wt0b, lane), step_of(d, 0), zero);
-                    acc = mfma16(lds_step(wl, PK.off_wt0b + 1, lane), step_of(d, 1), acc);
+                    f32x16 acc = input_grad(wl, PK.off_wt0b, d, lane);
                     if (rmw_b) {
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[r] += half(oldb[r]);
+                        for (int r = 0; r < 16; ++r) acc[r] += half_of<GRP>(oldb[r]);
                     }
                     F16 v;
                     pack_acc(v, acc);
@@ -584,15 +424,9 @@ extern "C" int fgnn_mlp_bwd16(const fgnn_mlp_bwd16_args *a, void *stream) {
     FGNN_CHECK(a->depth == 3, "fgnn_mlp_bwd16: built for depth_of_mlp = 3 (got %d)", a->depth);
     FGNN_CHECK(a->a.ptr && a->a.C > 0 && a->packed, "fgnn_mlp_bwd16: slab a / operand image missing");
     FGNN_CHECK(a->b.C == 0 || a->b.ptr, "fgnn_mlp_bwd16: slab b has channels but no pointer");
-    FGNN_CHECK(a->dy && a->z && a->wpart && a->coef, "fgnn_mlp_bwd16: missing dy/z/wpart/coef");
+    if (check_mlp_args(a, "fgnn_mlp_bwd16", true)) return 1;
     FGNN_CHECK(!a->s12part || (a->a.C == 32 && a->dxa && ((a->b.C == 0 && a->a.nrm) || (a->b.C > 0 && !a->a.nrm))),
                "fgnn_mlp_bwd16: s12part needs dxa and either a single normalised 32-channel slab or a raw first slab of a two-slab MLP");
-    {
-        const long long lim = 0x7fffffffll / 2, G = a->G;
-        FGNN_CHECK(G * a->a.gstride < lim && G * a->b.gstride < lim && G * a->dgstride < lim && G * a->zgstride < lim &&
-                   G * a->dxa_gstride < lim && G * a->dxb_gstride < lim,
-                   "fgnn_mlp_bwd16: a tensor exceeds 2 GiB (32-bit buffer addressing); split the batch");
-    }
     const int tpg = fgnn_tiles_per_graph16(a->N, a->ldr);
     const long long total = (long long)a->G * tpg;
     FGNN_CHECK(total < (1ll << 30), "fgnn_mlp_bwd16: too many tiles");

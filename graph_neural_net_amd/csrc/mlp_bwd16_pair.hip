@@ -1,6 +1,7 @@
 // mlp1 + mlp2 of one FGNN block (models/blocks_emb.py:16-27: two MlpBlock_Real on the SAME input), bf16 backward in ONE
 // launch -- the bf16 twin of mlp_bwd_pair.hip.  Per MLP and per tile the algorithm, rounding points and fragment conventions
-// are mlp_bwd16.hip's; what changes is who does it and what travels through HBM:
+// are those of fgnn_bwd16.h, which holds what this kernel shares with mlp_bwd16.hip; what changes is who does it and what
+// travels through HBM:
 //   * the two waves that share a SIMD form a PAIR on the same tile: wave p (p = 0..3) runs mlp1, wave p + 4 runs mlp2, each with
 //     only its own weight-gradient accumulators (registers + the same parked LDS tiles as the single-MLP kernel);
 //   * the gradient of the shared input is summed in the pair: the mlp1 wave leaves its fp32 dx fragments (even / odd pixel
@@ -12,118 +13,23 @@
 // Depth 3, one input slab of 32 channels (blocks > 1) or 2 channels (block 1: no input gradient, the pair only shares the
 // launch), constant-size batches.
 #include <type_traits>
-#include "fgnn_bf16.h"
+#include "fgnn_bwd16.h"
+
+using namespace bwd16;
 
 namespace {
 
-constexpr int NWB = 8;           // waves per workgroup: 4 pairs
-constexpr int NP = 4;
-constexpr int BWD16_WG = 256;   // persistent workgroups (partials layout shared with the fp32 path)
-
-template <int CA, int CB, int DEPTH>
-struct Bwd16Layout {
-    static constexpr Pk16 PK = pk16_layout(1, CA, CB, DEPTH);
-    static constexpr int WEIGHT_F = PK.floats;
-    static constexpr int REC_F = 64 + 64 + 128;                     // per wave: {a, b'} slab a, slab b, {mean, ca, cb, cc}
-    static constexpr int PCOUNT = 32 * (CA + CB) + 32 + (DEPTH - 1) * (32 * 32 + 32);
-    static constexpr int MAIN_F = 2 * WEIGHT_F + NWB * REC_F;       // two operand images
-    // Weight-gradient accumulator tiles kept in LDS between the tiles of the loop ("parked") instead of in registers: the
-    // variants that would otherwise spill them to scratch (the 64-input-channel kernel needs four 32x32 fp32 accumulators on
-    // top of everything else).  A scratch reload retires in order with the prefetch loads in flight and stalls behind them;
-    // LDS does not, and ~130 KB of it are idle here.  Slots in order of use: dW_2, dW_1, dW_0 (slab a), dW_0 (slab b).
-    static constexpr int NPARK = (CA >= 32 && CB >= 32) ? 4 : (CA >= 32 && CB > 0) ? 2 : (CA >= 32 ? 1 : 0);
-    static constexpr int PARK_OFF = (MAIN_F + 3) & ~3;
-    static constexpr int PARK_F = NWB * NPARK * 1024;
-    // hand-over of the mlp1 wave's fp32 dx fragments: per pair 2 buffers x 2 pixel groups x [4][64 lanes][4 floats]
-    static constexpr int XCH_OFF = PARK_OFF + PARK_F;
+// the single kernel's layout with two operand images, then the hand-over of the mlp1 wave's fp32 dx fragments: per pair
+// 2 buffers x 2 pixel groups x [4][64 lanes][4 floats], and 4 flag words per pair
+template <int CA>
+struct Pair16Layout : Bwd16Layout<CA, 0, 3, 2> {
+    using B = Bwd16Layout<CA, 0, 3, 2>;
+    static constexpr int XCH_OFF = B::PARK_OFF + B::PARK_F;
     static constexpr int XCH_F = (CA >= 32) ? NP * 2 * 2 * 1024 : 0;
     static constexpr int FLAG_OFF = XCH_OFF + XCH_F;
-    static constexpr int RED_F = NWB * PCOUNT;
-    static constexpr int LDS_F = FLAG_OFF + 4 * NP > RED_F ? FLAG_OFF + 4 * NP : RED_F;
+    static constexpr int LDS_F = FLAG_OFF + 4 * NP > B::RED_F ? FLAG_OFF + 4 * NP : B::RED_F;
 };
 
-// a parked accumulator tile: [4][64 lanes][4 floats] -> conflict-free 16-byte accesses
-DEVI f32x16 park_get(const float *slot, int lane) {
-    f32x16 v;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 t = reinterpret_cast<const float4 *>(slot)[q * 64 + lane];
-        v[4 * q] = t.x;
-        v[4 * q + 1] = t.y;
-        v[4 * q + 2] = t.z;
-        v[4 * q + 3] = t.w;
-    }
-    return v;
-}
-DEVI void park_put(float *slot, int lane, const f32x16 &v) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        reinterpret_cast<float4 *>(slot)[q * 64 + lane] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-}
-
-DEVI void fetch_rec2(float *rec, const fgnn_slab16 &s, int g, int lane) {
-    if (lane < 32) {
-        float2 o = make_float2(1.f, 0.f);
-        if (s.nrm && lane < s.C) {
-            const float4 n = reinterpret_cast<const float4 *>(s.nrm)[(long long)g * s.C + lane];
-            const float be = s.beta ? s.beta[lane] : 0.f;
-            o.x = n.y;
-            o.y = be - n.x * n.y;
-        }
-        reinterpret_cast<float2 *>(rec)[lane] = o;
-    }
-}
-
-// normal fragments (even / odd pixel) of a 32-channel slab, normalised; `raw*` = the un-normalised fragments
-DEVI void operands32b(F16 &e, F16 &o, F16 &rawE, F16 &rawO, const unsigned (&x)[16], const float *rec, bool norm, int h) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        rawE.d[q] = pack_lo(x[2 * q], x[2 * q + 1]);
-        rawO.d[q] = pack_hi(x[2 * q], x[2 * q + 1]);
-    }
-    if (norm) {
-        const float2 *r2 = reinterpret_cast<const float2 *>(rec);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const float2 n0 = r2[ch_of(2 * q, h)], n1 = r2[ch_of(2 * q + 1, h)];
-            e.d[q] = cvt_pk(fmaf(bf_lo(x[2 * q]), n0.x, n0.y), fmaf(bf_lo(x[2 * q + 1]), n1.x, n1.y));
-            o.d[q] = cvt_pk(fmaf(bf_hi(x[2 * q]), n0.x, n0.y), fmaf(bf_hi(x[2 * q + 1]), n1.x, n1.y));
-        }
-    } else {
-        e = rawE;
-        o = rawO;
-    }
-}
-DEVI void operands2b(F16 &e, F16 &o, const unsigned (&x)[2]) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) e.d[q] = o.d[q] = 0u;
-    e.d[0] = pack_lo(x[0], x[1]);
-    o.d[0] = pack_hi(x[0], x[1]);
-}
-
-// transposed, normalised operand of one pixel group: lane = channel, y^T = R(x^T * a_lane + b_lane)
-DEVI F16 transposed_input(const F16 &raw, const F16 &ident, bool norm, float la, float lb) {
-    const f32x16 t = transpose16(raw, ident);
-    F16 f;
-    if (norm) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) f.d[q] = cvt_pk(fmaf(t[2 * q], la, lb), fmaf(t[2 * q + 1], la, lb));
-    } else {
-        pack_acc(f, t);
-    }
-    return f;
-}
-
-DEVI float sum16(const f32x16 &t) {
-    float s = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s += t[r];
-    return s;
-}
-
-// SKIP (ragged batches with A.ranges): work-balanced tile range from fgnn_ragged_tile_ranges16; the waves step over tiles
-// without a valid element (no contribution to the parameter gradients, dx not written there); such a tile only gets an empty
-// S1/S2 (or trace-term) record.
 struct Pair16Args {
     fgnn_mlp_bwd16_args m[2];
 };
@@ -133,9 +39,9 @@ __global__ __launch_bounds__(64 * NWB, NWB / 4) void mlp_bwd16_pair_kernel(const
     constexpr int CB = 0, DEPTH = 3;
     constexpr bool SKIP = false;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    using L = Bwd16Layout<CA, CB, DEPTH>;
+    using L = Pair16Layout<CA>;
     constexpr Pk16 PK = L::PK;
-    constexpr int CIN = CA + CB, SA = pk16_steps(CA), SB = pk16_steps(CB);
+    constexpr int CIN = CA + CB;
     constexpr int XA = CA >= 32 ? 16 : 2, XB = CB >= 32 ? 16 : 2;
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int role = wv >> 2, pair = wv & 3;        // role 0: mlp1 (hands its dx over), role 1: mlp2 (sums, stores, emits)
@@ -207,8 +113,8 @@ __global__ __launch_bounds__(64 * NWB, NWB / 4) void mlp_bwd16_pair_kernel(const
     int cached_g = -1, cur_nv = A.N;
     float la_a = 1.f, la_b = 0.f, lb_a = 1.f, lb_b = 0.f, la_mean = 0.f;      // lane-channel constants (transposed layout)
     auto graph_change = [&](int g) {
-        fetch_rec2(recA, A.a, g, lane);
-        if constexpr (CB > 0) fetch_rec2(recB, A.b, g, lane);
+        fetch_rec2<false>(recA, A.a, g, lane);
+        if constexpr (CB > 0) fetch_rec2<false>(recB, A.b, g, lane);
         if (lane < 32) reinterpret_cast<float4 *>(recK)[lane] = reinterpret_cast<const float4 *>(A.coef)[(long long)g * FGNN_H + lane];
         cached_g = g;
         cur_nv = __builtin_amdgcn_readfirstlane(nvalid_of(A.nvalid, g, A.N));
@@ -284,85 +190,49 @@ __global__ __launch_bounds__(64 * NWB, NWB / 4) void mlp_bwd16_pair_kernel(const
         // scheduling barrier: interleaving them doubles the live fragments and spills.
         auto group = [&](auto tag) {
             constexpr int GRP = decltype(tag)::value;
-            auto half = [](unsigned d) { return GRP ? bf_hi(d) : bf_lo(d); };
-            auto pack2 = [](unsigned a, unsigned b) { return GRP ? pack_hi(a, b) : pack_lo(a, b); };
             const float fv = GRP ? (v1 ? 1.f : 0.f) : (v0 ? 1.f : 0.f);
             // ---- input operands: normal (recompute) and transposed (layer-0 weight gradient) ----
             F16 ya, yb, raw_a, yTa, yTb;
             if constexpr (CA >= 32) {
-#pragma unroll
-                for (int q = 0; q < 8; ++q) raw_a.d[q] = pack2(xa[2 * q], xa[2 * q + 1]);
+                raw_fragment<GRP>(raw_a, xa);
                 if (normA) {
                     const float2 *r2 = reinterpret_cast<const float2 *>(recA);
 #pragma unroll
                     for (int q = 0; q < 8; ++q) {
                         const float2 n0 = r2[ch_of(2 * q, h)], n1 = r2[ch_of(2 * q + 1, h)];
-                        ya.d[q] = cvt_pk(fmaf(half(xa[2 * q]), n0.x, n0.y), fmaf(half(xa[2 * q + 1]), n1.x, n1.y));
+                        ya.d[q] = cvt_pk(fmaf(half_of<GRP>(xa[2 * q]), n0.x, n0.y), fmaf(half_of<GRP>(xa[2 * q + 1]), n1.x, n1.y));
                     }
                 } else {
                     ya = raw_a;
                 }
                 yTa = transposed_input(raw_a, ident, normA, la_a, la_b);
             } else {
-#pragma unroll
-                for (int q = 0; q < 8; ++q) ya.d[q] = 0u;
-                ya.d[0] = pack2(xa[0], xa[1]);
+                narrow_fragment<GRP>(ya, xa);
                 yTa = transposed_input(ya, ident, false, 1.f, 0.f);
             }
             if constexpr (CB >= 32) {
                 F16 raw_b;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) raw_b.d[q] = pack2(xb[2 * q], xb[2 * q + 1]);
+                raw_fragment<GRP>(raw_b, xb);
                 if (normB) {
                     const float2 *r2 = reinterpret_cast<const float2 *>(recB);
 #pragma unroll
                     for (int q = 0; q < 8; ++q) {
                         const float2 n0 = r2[ch_of(2 * q, h)], n1 = r2[ch_of(2 * q + 1, h)];
-                        yb.d[q] = cvt_pk(fmaf(half(xb[2 * q]), n0.x, n0.y), fmaf(half(xb[2 * q + 1]), n1.x, n1.y));
+                        yb.d[q] = cvt_pk(fmaf(half_of<GRP>(xb[2 * q]), n0.x, n0.y), fmaf(half_of<GRP>(xb[2 * q + 1]), n1.x, n1.y));
                     }
                 } else {
                     yb = raw_b;
                 }
                 yTb = transposed_input(raw_b, ident, normB, lb_a, lb_b);
             } else if constexpr (CB > 0) {
-#pragma unroll
-                for (int q = 0; q < 8; ++q) yb.d[q] = 0u;
-                yb.d[0] = pack2(xb[0], xb[1]);
+                narrow_fragment<GRP>(yb, xb);
                 yTb = transposed_input(yb, ident, false, 1.f, 0.f);
             }
 
-            // ---- forward recompute: h_0 .. h_{d-2} ----
             F16 hs[DEPTH - 1];
-            {
-                f32x16 acc;
-                load_bias16(acc, tail, 0, h);
-#pragma unroll
-                for (int t = 0; t < SA; ++t) acc = mfma16(lds_step(wl, PK.off_w0a + t, lane), step_of(ya, t), acc);
-#pragma unroll
-                for (int t = 0; t < SB; ++t) acc = mfma16(lds_step(wl, PK.off_w0b + t, lane), step_of(yb, t), acc);
-                pack_acc_relu(hs[0], acc);
-#pragma unroll
-                for (int l = 1; l + 1 < DEPTH; ++l) {
-                    load_bias16(acc, tail, l, h);
-#pragma unroll
-                    for (int t = 0; t < 2; ++t)
-                        acc = mfma16(lds_step(wl, PK.off_wh + 2 * (l - 1) + t, lane), step_of(hs[l - 1], t), acc);
-                    pack_acc_relu(hs[l], acc);
-                }
-            }
-
-            // ---- dz from (dy, z, coef), rounded to bf16, zero in the padding ----
-            F16 d;
-            {
-                const float4 *kp = reinterpret_cast<const float4 *>(recK);
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const float4 k0 = kp[ch_of(2 * q, h)], k1 = kp[ch_of(2 * q + 1, h)];
-                    const float e0 = fmaf(k0.y, half(dyr[2 * q]), fmaf(k0.z, half(zr[2 * q]) - k0.x, k0.w));
-                    const float e1 = fmaf(k1.y, half(dyr[2 * q + 1]), fmaf(k1.z, half(zr[2 * q + 1]) - k1.x, k1.w));
-                    d.d[q] = cvt_pk(e0 * fv, e1 * fv);
-                }
-            }
+            recompute_hidden<CA, CB, DEPTH>(hs, ya, yb, wl, tail, lane, h);
+            F16 d;       // dz, zero in the padding
+            dz_of<GRP>(d, dyr, zr, recK, fv, h);
 
             // ---- hidden layers, l = DEPTH-1 .. 1 ----
 #pragma unroll
@@ -383,9 +253,7 @@ __global__ __launch_bounds__(64 * NWB, NWB / 4) void mlp_bwd16_pair_kernel(const
                     else accum(std::integral_constant<int, 1>(), dWh[l - 1], upd);
                 }
                 {
-                    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                    f32x16 acc = mfma16(lds_step(wl, PK.off_wt + 2 * (DEPTH - 1 - l), lane), step_of(d, 0), zero);
-                    acc = mfma16(lds_step(wl, PK.off_wt + 2 * (DEPTH - 1 - l) + 1, lane), step_of(d, 1), acc);
+                    const f32x16 acc = input_grad(wl, PK.off_wt + 2 * (DEPTH - 1 - l), d, lane);
 #pragma unroll
                     for (int q = 0; q < 8; ++q) d.d[q] = cvt_pk(acc[2 * q], acc[2 * q + 1]) & pos_mask_pk(in.d[q]);
                 }
@@ -412,9 +280,7 @@ __global__ __launch_bounds__(64 * NWB, NWB / 4) void mlp_bwd16_pair_kernel(const
             // ---- dx of the shared input slab ----
             if constexpr (CA >= 32) {
                 if (has_dx) {
-                    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                    f32x16 acc = mfma16(lds_step(wl, PK.off_wt0a, lane), step_of(d, 0), zero);
-                    acc = mfma16(lds_step(wl, PK.off_wt0a + 1, lane), step_of(d, 1), acc);
+                    f32x16 acc = input_grad(wl, PK.off_wt0a, d, lane);
                     if (role == 0) {
                         // hand the fp32 fragment over ([4][lane][4] like a parked tile).  The buffer was last used two tiles ago:
                         // wait until that tile has been consumed
@@ -434,7 +300,7 @@ __global__ __launch_bounds__(64 * NWB, NWB / 4) void mlp_bwd16_pair_kernel(const
                         if constexpr (GRP == 1) __hip_atomic_store(&flags[1], tile, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                         if (rmw_a) {
 #pragma unroll
-                            for (int r = 0; r < 16; ++r) t[r] += half(olda[r]);
+                            for (int r = 0; r < 16; ++r) t[r] += half_of<GRP>(olda[r]);
                         }
                         F16 v1;
                         pack_acc(v1, t);
@@ -471,12 +337,10 @@ __global__ __launch_bounds__(64 * NWB, NWB / 4) void mlp_bwd16_pair_kernel(const
             // ---- dx of slab b ----
             if constexpr (CB >= 32) {
                 if (A.dxb) {
-                    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                    f32x16 acc = mfma16(lds_step(wl, PK.off_wt0b, lane), step_of(d, 0), zero);
-                    acc = mfma16(lds_step(wl, PK.off_wt0b + 1, lane), step_of(d, 1), acc);
+                    f32x16 acc = input_grad(wl, PK.off_wt0b, d, lane);
                     if (rmw_b) {
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[r] += half(oldb[r]);
+                        for (int r = 0; r < 16; ++r) acc[r] += half_of<GRP>(oldb[r]);
                     }
                     F16 v;
                     pack_acc(v, acc);
@@ -569,7 +433,7 @@ __global__ __launch_bounds__(64 * NWB, NWB / 4) void mlp_bwd16_pair_kernel(const
 
 template <int CA>
 int launch_pair16(const fgnn_mlp_bwd16_args *a1, const fgnn_mlp_bwd16_args *a2, int tpg, int total, hipStream_t st) {
-    constexpr int LDS = Bwd16Layout<CA, 0, 3>::LDS_F * 4;
+    constexpr int LDS = Pair16Layout<CA>::LDS_F * 4;
     static_assert(LDS <= 160 * 1024, "LDS budget");
     static LdsAttrCache attr_cache;
     (void)fgnn_raise_lds(attr_cache, (const void *)mlp_bwd16_pair_kernel<CA>, LDS);
@@ -599,12 +463,8 @@ extern "C" int fgnn_mlp_bwd16_pair(const fgnn_mlp_bwd16_args *a1, const fgnn_mlp
     FGNN_CHECK(!a1->dxa && !a1->s12part, "fgnn_mlp_bwd16_pair: the input gradient and its tile sums belong to the SECOND argument block");
     FGNN_CHECK(!(a2->dxa && a2->a.C != 32), "fgnn_mlp_bwd16_pair: the input gradient exists for the 32-channel slab only");
     FGNN_CHECK(!a2->s12part || (a2->a.C == 32 && a2->dxa && a2->a.nrm), "fgnn_mlp_bwd16_pair: s12part needs dxa and a normalised 32-channel slab");
-    for (const fgnn_mlp_bwd16_args *a : {a1, a2}) {
-        FGNN_CHECK(a->dy && a->z && a->wpart && a->coef, "fgnn_mlp_bwd16_pair: missing dy/z/wpart/coef");
-        const long long lim = 0x7fffffffll / 2, G = a->G;
-        FGNN_CHECK(G * a->a.gstride < lim && G * a->dgstride < lim && G * a->zgstride < lim && G * a->dxa_gstride < lim,
-                   "fgnn_mlp_bwd16_pair: a tensor exceeds 2 GiB (32-bit buffer addressing); split the batch");
-    }
+    for (const fgnn_mlp_bwd16_args *a : {a1, a2})
+        if (check_mlp_args(a, "fgnn_mlp_bwd16_pair", false)) return 1;
     const int tpg = fgnn_tiles_per_graph16(a1->N, a1->ldr);
     const long long total = (long long)a1->G * tpg;
     FGNN_CHECK(total < (1ll << 30), "fgnn_mlp_bwd16_pair: too many tiles");
