@@ -22,6 +22,7 @@ FGNN_QAP_MAX_N = 256         # include/fgnn_hip.h: largest graph of the fgnn_qap
 FGNN_QAPW_MAX_N = 256        # include/fgnn_hip.h: largest graph of the fgnn_qapw_* / fgnn_greedy_qapw kernels (fp32 weights)
 FGNN_SPECTRAL_MAX_N = 256    # include/fgnn_hip.h: largest graph of fgnn_spectral_features
 FGNN_SPECTRAL_MAX_POWERS = 8
+FGNN_PLANTED_MAX_N = 256      # include/fgnn_hip.h: largest graph of the fgnn_planted_perm / fgnn_relabel_* kernels
 FGNN_SCORE_SPLIT = 4
 
 c_float_p = C.c_void_p   # device pointers travel as integers
@@ -244,10 +245,17 @@ _SIGNATURES = {
     'fgnn_qap_improve_cost': [_VP, _VP, _VP, _VP, _I, _I, _VP, _LL, _I, _VP],
     'fgnn_greedy_qap_ws_bytes': [_I, _I],
     'fgnn_greedy_qap': [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
+    'fgnn_greedy_qap_labels': [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
     'fgnn_qapw_objective': [_VP, _VP, _LL, _I, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP],
     'fgnn_qapw_improve_cost': [_VP, _VP, _LL, _I, _VP, _VP, _I, _I, _VP, _LL, _I, _VP],
     'fgnn_greedy_qapw_ws_bytes': [_I, _I],
     'fgnn_greedy_qapw': [_VP, _VP, _LL, _I, _VP, _VP, _I, _I, _I, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
+    'fgnn_greedy_qapw_labels': [_VP, _VP, _LL, _I, _VP, _VP, _VP, _I, _I, _I, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
+    'fgnn_planted_perm': [C.c_ulonglong, _LL, _VP, _VP, _I, _I, _VP, _VP],
+    'fgnn_relabel_bits': [_VP, _VP, _VP, _I, _I, _VP, _VP],
+    'fgnn_relabel_dense': [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP],
+    'fgnn_count_matches': [_VP, _VP, _VP, _I, _I, _VP, _VP],
+    'fgnn_accuracy_max_labels': [_VP, _VP, _VP, _I, _I, _VP, _VP],
     'fgnn_spectral_features': [_VP, _VP, _I, _I, _I, _VP, _I, _VP],
     # ---- bf16 path ----
     'fgnn_tiles_per_graph16': [_I, _I],

@@ -1,8 +1,8 @@
 // QAP pair generation on the device (loaders/data_generator.py:38-125,175-219, QAP_Generator): one single-wave workgroup per
 // pair builds the parent graph and its noisy copy as bit rows in LDS and stores both in the engine's wire format.
 //
-// Randomness is counter-based: raw 32-bit draw t of stream s of pair k is word t & 7 (low half first) of Philox4x64-10 at
-// counter (t >> 3, k, s, 0) under key (seed, 0), so a pair never depends on the launch that made it.  Events are u32 < thr,
+// Randomness is counter-based (fgnn_philox.h): raw 32-bit draw t of stream s of pair k is word t & 7 (low half first) of Philox4x64-10
+// at counter (t >> 3, k, s, 0) under key (seed, 0), so a pair never depends on the launch that made it.  Events are u32 < thr,
 // integers in [0, k) are (u32 * k) >> 32 (tests/pairgen_ref.py restates every step in numpy, bit for bit).
 //
 // The parallel parts (vertex count, Erdos-Renyi draws, noise, relabelling, stores) run across the 64 lanes; the serial chains
@@ -14,6 +14,7 @@
 // Which pair a workgroup builds is first + b (fgnn_pairgen) or index[b] (fgnn_pairgen_indexed); fgnn_epoch_index, at the end of the
 // file, writes such an index list: a window of the shuffled order of an epoch.
 #include "fgnn_common.h"
+#include "fgnn_philox.h"
 
 namespace {
 
@@ -22,44 +23,6 @@ enum { ST_SIZE = 0, ST_PARENT, ST_NOISE1, ST_NOISE2, ST_RELABEL, ST_CHAIN };
 constexpr int MAX_SIZE_DRAWS = 64;       // n < 2 is redrawn at most this often, then n = 2 (tests/pairgen_ref.py)
 constexpr unsigned long long THR_ONE = 1ull << 32;
 
-struct P4 {
-    unsigned long long v0, v1, v2, v3;
-};
-
-// Random123 Philox4x64-10 (Salmon et al., SC'11) on counter (c0, c1, c2, c3), key (k0, 0); c3 = 0 for every pair stream
-DEVI P4 philox(unsigned long long c0, unsigned long long c1, unsigned long long c2, unsigned long long k0, unsigned long long c3 = 0) {
-    const unsigned long long M0 = 0xD2E7470EE14C6C93ull, M1 = 0xCA5A826395121157ull;
-    unsigned long long k1 = 0;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        if (r) {
-            k0 += 0x9E3779B97F4A7C15ull;
-            k1 += 0xBB67AE8584CAA73Bull;
-        }
-        const unsigned long long hi0 = __umul64hi(M0, c0), lo0 = M0 * c0;
-        const unsigned long long hi1 = __umul64hi(M1, c2), lo1 = M1 * c2;
-        const unsigned long long n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0;
-        c1 = lo1;
-        c2 = n2;
-        c3 = lo0;
-    }
-    return P4{c0, c1, c2, c3};
-}
-
-DEVI unsigned word_of(const P4 &r, int w) {
-    const unsigned long long x = w < 2 ? r.v0 : w < 4 ? r.v1 : w < 6 ? r.v2 : r.v3;
-    return (w & 1) ? (unsigned)(x >> 32) : (unsigned)x;
-}
-
-struct Pair {
-    unsigned long long seed, k;
-    DEVI unsigned draw(int stream, unsigned long long t) const { return word_of(philox(t >> 3, k, stream, seed), (int)(t & 7)); }
-    DEVI P4 block(int stream, unsigned long long q) const { return philox(q, k, stream, seed); }
-};
-
-DEVI int below(unsigned u, int k) { return (int)(((unsigned long long)u * (unsigned)k) >> 32); }
-DEVI int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
 DEVI int bit(const unsigned *rows, int W, int i, int j) { return uni((rows[i * W + (j >> 5)] >> (j & 31)) & 1); }
 DEVI void set_edge(unsigned *rows, int W, int i, int j) {           // any lane, both directions
     atomicOr(&rows[i * W + (j >> 5)], 1u << (j & 31));

@@ -249,8 +249,10 @@ extern "C" long long fgnn_greedy_qap_ws_bytes(int B, int N) {
     return ws_round((long long)B * N * N * 4) + ws_round((long long)B * N * 4) + 2 * ws_round((long long)B * 4);
 }
 
-extern "C" int fgnn_greedy_qap(const unsigned *bits1, const unsigned *bits2, const int *assign0, const int *nvalid, int B, int N, int T,
-                               void *ws, long long ws_bytes, int *s_best2, int *acc_best, int *t_best, int *perm_best, void *stream) {
+// fgnn_greedy_qap (labels = NULL) and fgnn_greedy_qap_labels: one launch sequence; with labels a fgnn_count_matches launch overwrites
+// `correct` after every solver call, so acc_best counts the matches with the labels instead of the fixed points
+static int greedy(const unsigned *bits1, const unsigned *bits2, const int *assign0, const int *labels, const int *nvalid, int B, int N, int T,
+                  void *ws, long long ws_bytes, int *s_best2, int *acc_best, int *t_best, int *perm_best, void *stream) {
     FGNN_CHECK(bits1 && bits2 && assign0 && ws && s_best2 && acc_best && t_best && B > 0 && N > 0 && T >= 0, "fgnn_greedy_qap: bad arguments");
     FGNN_CHECK(N <= FGNN_QAP_MAX_N, "fgnn_greedy_qap: at most %d vertices per graph (got %d)", FGNN_QAP_MAX_N, N);
     FGNN_CHECK(ws_bytes >= fgnn_greedy_qap_ws_bytes(B, N) && ((uintptr_t)ws & 15) == 0,
@@ -270,14 +272,28 @@ extern "C" int fgnn_greedy_qap(const unsigned *bits1, const unsigned *bits2, con
     if ((rc = objective<true>(bits1, bits2, assign0, nvalid, B, N, s_best2, nullptr, nullptr, nullptr, st))) return rc;
     if ((rc = improve_cost(bits1, bits2, assign0, nvalid, B, N, cost, bs, N, st))) return rc;
     if ((rc = fgnn_lsap_accuracy(cost, bs, N, nvalid, B, N, correct, cur, stream))) return rc;
+    if (labels && (rc = fgnn_count_matches(cur, labels, nvalid, B, N, correct, stream))) return rc;
     hipLaunchKernelGGL(qap_keep_kernel, dim3(B), dim3(64), 0, st, -1, cur_q, correct, assign0, nvalid, N, s_best2, acc_best, t_best, perm_best);
     FGNN_LAUNCH_CHECK();
     for (int i = 0; i < T; ++i) {
         if ((rc = improve_cost(bits1, bits2, cur, nvalid, B, N, cost, bs, N, st))) return rc;
         if ((rc = fgnn_lsap_accuracy(cost, bs, N, nvalid, B, N, correct, cur, stream))) return rc;
+        if (labels && (rc = fgnn_count_matches(cur, labels, nvalid, B, N, correct, stream))) return rc;
         if ((rc = objective<true>(bits1, bits2, cur, nvalid, B, N, cur_q, nullptr, nullptr, nullptr, st))) return rc;
         hipLaunchKernelGGL(qap_keep_kernel, dim3(B), dim3(64), 0, st, i, cur_q, correct, cur, nvalid, N, s_best2, acc_best, t_best, perm_best);
         FGNN_LAUNCH_CHECK();
     }
     return 0;
+}
+
+extern "C" int fgnn_greedy_qap(const unsigned *bits1, const unsigned *bits2, const int *assign0, const int *nvalid, int B, int N, int T,
+                               void *ws, long long ws_bytes, int *s_best2, int *acc_best, int *t_best, int *perm_best, void *stream) {
+    return greedy(bits1, bits2, assign0, nullptr, nvalid, B, N, T, ws, ws_bytes, s_best2, acc_best, t_best, perm_best, stream);
+}
+
+extern "C" int fgnn_greedy_qap_labels(const unsigned *bits1, const unsigned *bits2, const int *assign0, const int *labels, const int *nvalid,
+                                      int B, int N, int T, void *ws, long long ws_bytes, int *s_best2, int *acc_best, int *t_best,
+                                      int *perm_best, void *stream) {
+    FGNN_CHECK(labels, "fgnn_greedy_qap_labels: NULL labels");
+    return greedy(bits1, bits2, assign0, labels, nvalid, B, N, T, ws, ws_bytes, s_best2, acc_best, t_best, perm_best, stream);
 }

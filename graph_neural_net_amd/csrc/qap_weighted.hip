@@ -197,9 +197,11 @@ extern "C" long long fgnn_greedy_qapw_ws_bytes(int B, int N) {
     return ws_round((long long)B * N * N * 4) + ws_round((long long)B * N * 4) + 2 * ws_round((long long)B * 4);
 }
 
-extern "C" int fgnn_greedy_qapw(const float *a1, const float *a2, long long gstride, int ld, const int *assign0, const int *nvalid, int B,
-                                int N, int T, void *ws, long long ws_bytes, float *s_best, int *acc_best, int *t_best, int *perm_best,
-                                void *stream) {
+// fgnn_greedy_qapw (labels = NULL) and fgnn_greedy_qapw_labels: one launch sequence; with labels a fgnn_count_matches launch overwrites
+// `correct` after every solver call (qap.hip)
+static int greedy(const float *a1, const float *a2, long long gstride, int ld, const int *assign0, const int *labels, const int *nvalid,
+                  int B, int N, int T, void *ws, long long ws_bytes, float *s_best, int *acc_best, int *t_best, int *perm_best,
+                  void *stream) {
     FGNN_CHECK(a1 && a2 && assign0 && ws && s_best && acc_best && t_best && B > 0 && N > 0 && T >= 0, "fgnn_greedy_qapw: bad arguments");
     QAPW_CHECK_SHAPE("fgnn_greedy_qapw");
     FGNN_CHECK(ws_bytes >= fgnn_greedy_qapw_ws_bytes(B, N) && ((uintptr_t)ws & 15) == 0,
@@ -219,14 +221,29 @@ extern "C" int fgnn_greedy_qapw(const float *a1, const float *a2, long long gstr
     if ((rc = objective(a1, a2, gstride, ld, assign0, nvalid, B, N, nullptr, s_best, nullptr, nullptr, nullptr, st))) return rc;
     if ((rc = improve_cost(a1, a2, gstride, ld, assign0, nvalid, B, N, cost, bs, N, st))) return rc;
     if ((rc = fgnn_lsap_accuracy(cost, bs, N, nvalid, B, N, correct, cur, stream))) return rc;
+    if (labels && (rc = fgnn_count_matches(cur, labels, nvalid, B, N, correct, stream))) return rc;
     hipLaunchKernelGGL(qapw_keep_kernel, dim3(B), dim3(64), 0, st, -1, cur_trace, correct, assign0, nvalid, N, s_best, acc_best, t_best, perm_best);
     FGNN_LAUNCH_CHECK();
     for (int i = 0; i < T; ++i) {
         if ((rc = improve_cost(a1, a2, gstride, ld, cur, nvalid, B, N, cost, bs, N, st))) return rc;
         if ((rc = fgnn_lsap_accuracy(cost, bs, N, nvalid, B, N, correct, cur, stream))) return rc;
+        if (labels && (rc = fgnn_count_matches(cur, labels, nvalid, B, N, correct, stream))) return rc;
         if ((rc = objective(a1, a2, gstride, ld, cur, nvalid, B, N, nullptr, cur_trace, nullptr, nullptr, nullptr, st))) return rc;
         hipLaunchKernelGGL(qapw_keep_kernel, dim3(B), dim3(64), 0, st, i, cur_trace, correct, cur, nvalid, N, s_best, acc_best, t_best, perm_best);
         FGNN_LAUNCH_CHECK();
     }
     return 0;
+}
+
+extern "C" int fgnn_greedy_qapw(const float *a1, const float *a2, long long gstride, int ld, const int *assign0, const int *nvalid, int B,
+                                int N, int T, void *ws, long long ws_bytes, float *s_best, int *acc_best, int *t_best, int *perm_best,
+                                void *stream) {
+    return greedy(a1, a2, gstride, ld, assign0, nullptr, nvalid, B, N, T, ws, ws_bytes, s_best, acc_best, t_best, perm_best, stream);
+}
+
+extern "C" int fgnn_greedy_qapw_labels(const float *a1, const float *a2, long long gstride, int ld, const int *assign0, const int *labels,
+                                       const int *nvalid, int B, int N, int T, void *ws, long long ws_bytes, float *s_best,
+                                       int *acc_best, int *t_best, int *perm_best, void *stream) {
+    FGNN_CHECK(labels, "fgnn_greedy_qapw_labels: NULL labels");
+    return greedy(a1, a2, gstride, ld, assign0, labels, nvalid, B, N, T, ws, ws_bytes, s_best, acc_best, t_best, perm_best, stream);
 }

@@ -15,12 +15,16 @@ Semantics follow the reference:
   ``BarabasiAlbert`` (m = int(p (n - 1) / 2); networkx 3.x's star + repeated-nodes attachment, no relabelling; constant N);
 * noise models: ``ErdosRenyi`` (W' = W (1 - Z1) + (1 - W) Z2, Z1 ~ ER(noise), Z2 ~ ER(p noise / (1 - p))) and ``EdgeSwap``
   (the reference's nested loop over the parent's directed edges: the (u < v) edges in row-major order, then their reversals);
-* the pair is not permuted: the ground truth is the identity (``triplet_loss``).
+* by default the pair is not permuted: the ground truth is the identity, as ``triplet_loss`` and the reference's loaders have
+  it.  ``permute=True`` on ``bits`` / ``dense`` / ``spectral`` relabels side 2 by the pair's planted permutation (``planted.py``:
+  ``out[pi(i)][pi(j)] = in[i][j]``) and appends ``labels`` ((count, N) int32, ``labels[b, i] = pi_b(i)``, -1 past n_b) to the return
+  value: the ground truth that ``metrics``, ``qap`` and ``Siamese_Node_Exp.match`` take as ``labels=``.  Training does not take it:
+  the model is permutation-equivariant and the reference's loss has no label.
 
 Randomness is counter-based (Philox4x64-10 keyed by ``seed``): every draw is addressed by (pair index, stream, position), so
 pair k of a dataset is the same however a range is split into calls, devices or ranks.  Streams: 0 size, 1 parent, 2 noise-1,
-3 noise-2, 4 relabel, 5 swap chain / attachment, all with 0 in the fourth counter word; number 6 in that word belongs to the
-epoch permutation (``sampler.py``).  Probabilities are integer thresholds ``min(2^32, floor(prob * 2^32))`` compared with raw 32-bit
+3 noise-2, 4 relabel, 5 swap chain / attachment, 7 planted permutation (``planted.py``), all with 0 in the fourth counter word;
+number 6 in that word belongs to the epoch permutation (``sampler.py``).  Probabilities are integer thresholds ``min(2^32, floor(prob * 2^32))`` compared with raw 32-bit
 draws; integers in [0, k) are ``(u32 * k) >> 32`` (``tests/pairgen_ref.py`` restates it all in numpy, bit for bit).
 
 Which pairs: a contiguous range ``(first, count)``, or any pairs by ``index=`` (an int64 tensor of dataset indices in any order,
@@ -39,6 +43,7 @@ import torch
 from . import _lib
 from .inputs import expand_adjacency
 from .masked import MaskedTensor
+from .planted import planted_permutation, relabel_bits
 from .spectral import spectral_features
 
 FAMILIES = {'ErdosRenyi': 0, 'Regular': 1, 'BarabasiAlbert': 2}
@@ -115,11 +120,12 @@ class PairGenerator:
             raise ValueError('index must be a 1-D int64 tensor, got shape %s, %s' % (tuple(index.shape), index.dtype))
         return 0, index.numel(), index.to(self.device).contiguous()
 
-    def bits(self, first=None, count=None, index=None):
+    def bits(self, first=None, count=None, index=None, permute=False):
         """Pairs first .. first + count - 1, or the pairs index[0], index[1], ... (a 1-D int64 tensor, or a list; moved to the device
         if it is not there; any order, duplicates allowed) -> (bits1, bits2, nvalid): (count, N, ceil(N/32)) int32 device tensors
         and, when the vertex count is binomial, the (count,) int32 vertex counts (else None).  Enqueued on the current stream; the
-        index is not read on the host: a negative entry (a caller error) gives the empty graph, all words zero and nvalid = 0."""
+        index is not read on the host: a negative entry (a caller error) gives the empty graph, all words zero and nvalid = 0.
+        permute=True: bits2 is relabelled by the planted permutation of each pair and (bits1, bits2, nvalid, labels) is returned."""
         if self.device.type != 'cuda':
             raise RuntimeError('PairGenerator: device %s; the generator runs on the GPU only (there is no CPU path)' % (self.device,))
         first, count, index = self._selection(first, count, index)
@@ -142,32 +148,40 @@ class PairGenerator:
                     _lib.call('fgnn_pairgen', C.byref(a), _lib.stream_ptr())
                 else:
                     _lib.call('fgnn_pairgen_indexed', C.byref(a), _lib.ptr(index), _lib.stream_ptr())
+            if permute:
+                if index is None:
+                    labels = planted_permutation(self.seed, N, first, count, nvalid=nv, device=self.device)
+                else:
+                    labels = planted_permutation(self.seed, N, index=index, nvalid=nv, device=self.device)
+                return b1, relabel_bits(b2, labels, nv), nv, labels
         return b1, b2, nv
 
-    def dense(self, first=None, count=None, index=None):
+    def dense(self, first=None, count=None, index=None, permute=False):
         """The reference's collate structures for the same pairs: ({'input': x1}, {'input': x2}) with (count, 2, N, N) fp32
         tensor representations (collate_fn_pair_explore) for a constant vertex count, else two MaskedTensors padded to the
-        largest n_i of the batch (collate_fn_pair; one host sync for that size)."""
-        b1, b2, nv = self.bits(first, count, index)
+        largest n_i of the batch (collate_fn_pair; one host sync for that size).  permute=True: side 2 is the representation of
+        the relabelled graph and the (count, N) labels are appended to the return value."""
+        b1, b2, nv, *labels = self.bits(first, count, index, permute)
         count = b1.shape[0]
         N = self.n_vertices
         x1, x2 = expand_adjacency(b1, N, nv), expand_adjacency(b2, N, nv)
         if nv is None:
-            return {'input': x1}, {'input': x2}
+            return ({'input': x1}, {'input': x2}, *labels)
         n = int(nv.max().item()) if count else 0
         x1, x2 = x1[:, :, :n, :n].contiguous(), x2[:, :, :n, :n].contiguous()
-        return MaskedTensor(x1, nv, (2, 3), 'N'), MaskedTensor(x2, nv, (2, 3), 'M')
+        return (MaskedTensor(x1, nv, (2, 3), 'N'), MaskedTensor(x2, nv, (2, 3), 'M'), *labels)
 
-    def spectral(self, first=None, count=None, n_powers=4, index=None):
+    def spectral(self, first=None, count=None, n_powers=4, index=None, permute=False):
         """The twin of `dense` for the reference's ``QAP_spectralGenerator`` (loaders/data_generator.py:221-277): the same pairs as
         `bits`, each side as the n_powers channels L, L^2, ... of ``spectral.spectral_features`` (one launch per side, straight from
         the bit rows; an isolated vertex gives a zero row and column where the reference gives NaN).  ({'input': F1}, {'input': F2})
         with (count, n_powers, N, N) fp32 tensors for a constant vertex count, else two MaskedTensors written directly at the
-        largest n_i of the batch (one host sync for that size), with the names and masked dims of `dense`."""
-        b1, b2, nv = self.bits(first, count, index)
+        largest n_i of the batch (one host sync for that size), with the names and masked dims of `dense`.  permute=True: side 2 is
+        computed from the relabelled bit rows and the (count, N) labels are appended to the return value."""
+        b1, b2, nv, *labels = self.bits(first, count, index, permute)
         count = b1.shape[0]
         if nv is None:
-            return {'input': spectral_features(b1, None, n_powers)}, {'input': spectral_features(b2, None, n_powers)}
+            return ({'input': spectral_features(b1, None, n_powers)}, {'input': spectral_features(b2, None, n_powers)}, *labels)
         n = max(int(nv.max().item()), 1) if count else 1
         f1, f2 = spectral_features(b1, nv, n_powers, n_out=n), spectral_features(b2, nv, n_powers, n_out=n)
-        return MaskedTensor(f1, nv, (2, 3), 'N'), MaskedTensor(f2, nv, (2, 3), 'M')
+        return (MaskedTensor(f1, nv, (2, 3), 'N'), MaskedTensor(f2, nv, (2, 3), 'M'), *labels)

@@ -32,12 +32,18 @@ without the keyword), exact where every product and partial sum is representable
 gamma_m sum |a||b| of the float64 value, gamma_m = m u / (1 - m u), u = 2^-24, m = n_b^2.  qap = -1 still marks an `assign` without
 a column inside the corner; with weights that may be negative -1 is then not a value.  Its host route is the reference's own float64
 matrix arithmetic (``trace(A @ P @ B @ P.T) / 2``, ``linear_sum_assignment(-A @ P @ B)``) and returns float64.
+
+``labels=`` on ``all_acc_qap`` and ``greedy_qap`` (both routes, with and without ``weighted``) scores against a planted permutation
+instead of the identity (``planted.py``; a (B, N) integer tensor with labels[b, i] = the column of row i, or the reference's list
+of per-graph arrays): ``acc`` and ``acc_best`` count ``assign[i] == labels[i]`` and ``planted`` is the objective of the labels'
+matching, ``qap_objective(adj1, adj2, labels)['qap']`` -- for the identity that is ``sum A * B``.  On ``greedy_qap`` this is an
+extension: the reference's has no such parameter, its label is ``arange``.  ``labels=None`` changes nothing.
 """
 import numpy as np
 import torch
 
 from . import _lib
-from .metrics import lsap_device
+from .metrics import count_matches, labels_tensor, lsap_device
 
 NOT_A_REPRESENTATION = ('the batch is NOT the tensor representation of a 0/1 adjacency (channel 0 in {0, 1}, channel 1 = '
                         'diag(row sums), loaders/data_generator.py:118-125)')
@@ -96,8 +102,9 @@ def objective_bits(b1, b2, assign, nv):
     return {'qap': out[0], 'planted': out[1], 'na': out[2], 'nb': out[3]}
 
 
-def greedy_bits(b1, b2, assign, T, nv):
-    """fgnn_greedy_qap on bit words -> the dict of `greedy_qap`; never synchronises."""
+def greedy_bits(b1, b2, assign, T, nv, labels=None):
+    """fgnn_greedy_qap (fgnn_greedy_qap_labels with (B, N) int32 device labels) on bit words -> the dict of `greedy_qap`; never
+    synchronises."""
     B, N, _ = b1.shape
     dev = b1.device
     a = assign.to(dtype=torch.int32).contiguous()
@@ -106,8 +113,12 @@ def greedy_bits(b1, b2, assign, T, nv):
     out = torch.empty(3, B, dtype=torch.int32, device=dev)
     perm = torch.empty(B, N, dtype=torch.int32, device=dev)
     sums = torch.empty(2, B, dtype=torch.int32, device=dev)
-    _lib.call('fgnn_greedy_qap', _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(a), _lib.ptr(nv), B, N, int(T), _lib.ptr(ws), nbytes,
-              _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.ptr(perm), _lib.stream_ptr())
+    if labels is None:
+        _lib.call('fgnn_greedy_qap', _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(a), _lib.ptr(nv), B, N, int(T), _lib.ptr(ws), nbytes,
+                  _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.ptr(perm), _lib.stream_ptr())
+    else:
+        _lib.call('fgnn_greedy_qap_labels', _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(a), _lib.ptr(labels), _lib.ptr(nv), B, N, int(T),
+                  _lib.ptr(ws), nbytes, _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.ptr(perm), _lib.stream_ptr())
     _lib.call('fgnn_qap_objective', _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(a), _lib.ptr(nv), B, N, None, None, _lib.ptr(sums[0]),
               _lib.ptr(sums[1]), _lib.stream_ptr())
     return {'s_best': out[0].to(torch.float64) / 2, 'na': sums[0].to(torch.float64) / 2, 'nb': sums[1].to(torch.float64) / 2,
@@ -150,8 +161,9 @@ def objective_weighted(adj1, adj2, assign, nv):
     return {'qap': out[0], 'trace': out[1], 'planted': out[2], 'na': out[3], 'nb': out[4]}
 
 
-def greedy_weighted(adj1, adj2, assign, T, nv):
-    """fgnn_greedy_qapw -> the dict of `greedy_qap(weighted=True)`; never synchronises."""
+def greedy_weighted(adj1, adj2, assign, T, nv, labels=None):
+    """fgnn_greedy_qapw (fgnn_greedy_qapw_labels with (B, N) int32 device labels) -> the dict of `greedy_qap(weighted=True)`; never
+    synchronises."""
     x1, x2, gs, ld = weighted_views(adj1, adj2)
     B, N = x1.shape[0], x1.shape[-1]
     dev = x1.device
@@ -162,8 +174,12 @@ def greedy_weighted(adj1, adj2, assign, T, nv):
     out = torch.empty(2, B, dtype=torch.int32, device=dev)
     perm = torch.empty(B, N, dtype=torch.int32, device=dev)
     sums = torch.empty(2, B, dtype=torch.float32, device=dev)
-    _lib.call('fgnn_greedy_qapw', _lib.ptr(x1), _lib.ptr(x2), gs, ld, _lib.ptr(a), _lib.ptr(nv), B, N, int(T), _lib.ptr(ws), nbytes,
-              _lib.ptr(s_best), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(perm), _lib.stream_ptr())
+    if labels is None:
+        _lib.call('fgnn_greedy_qapw', _lib.ptr(x1), _lib.ptr(x2), gs, ld, _lib.ptr(a), _lib.ptr(nv), B, N, int(T), _lib.ptr(ws), nbytes,
+                  _lib.ptr(s_best), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(perm), _lib.stream_ptr())
+    else:
+        _lib.call('fgnn_greedy_qapw_labels', _lib.ptr(x1), _lib.ptr(x2), gs, ld, _lib.ptr(a), _lib.ptr(labels), _lib.ptr(nv), B, N,
+                  int(T), _lib.ptr(ws), nbytes, _lib.ptr(s_best), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(perm), _lib.stream_ptr())
     _lib.call('fgnn_qapw_objective', _lib.ptr(x1), _lib.ptr(x2), gs, ld, _lib.ptr(a), _lib.ptr(nv), B, N, None, None, None,
               _lib.ptr(sums[0]), _lib.ptr(sums[1]), _lib.stream_ptr())
     return {'s_best': s_best, 'na': sums[0] / 2, 'nb': sums[1] / 2, 'acc_best': out[0].to(torch.int64), 'T_best': out[1].to(torch.int64),
@@ -193,45 +209,53 @@ def qap_objective(adj1, adj2, assign, nvalid=None, weighted=False):
     return out
 
 
-def greedy_qap(adj1, adj2, assign, T=10, nvalid=None, weighted=False):
+def greedy_qap(adj1, adj2, assign, T=10, nvalid=None, weighted=False, labels=None):
     """The reference's greedy_qap(A, B, perm_matrix(arange, assign), T) for every pair of the batch (see the module docstring for
     the order of events and its quirk) -> dict of (B,) tensors: s_best, na, nb (float64; na / nb the halved sums, as score() returns
     them), acc_best, T_best (int64), and perm (B, N) int32, the matching whose score is s_best (-1 in the padding).  Where no round
     improved on the initial score, perm is `assign` and acc_best -- the fixed points of a matching that was never scored -- does NOT
     describe it.  The device route is one chain of launches (4 per round) without a host round trip: it can be captured.
-    weighted=True: real matrices (see the module docstring); s_best, na, nb are float32 (float64 from the host route)."""
+    weighted=True: real matrices (see the module docstring); s_best, na, nb are float32 (float64 from the host route).
+    labels (an extension, see the module docstring): acc_best counts the matches with the labels instead of the fixed points."""
     if T < 0:
         raise ValueError('T must be >= 0, got %r' % (T,))
+    labels = labels_tensor(labels, assign.shape[0], assign.shape[1], adj1.device)
     if weighted:
         if _on_host_weighted(adj1, adj1.shape[-1]):
-            return _greedy_host_w(adj1, adj2, assign, T, nvalid)
-        return greedy_weighted(adj1, adj2, assign, T, _nv32(nvalid, adj1.device))
+            return _greedy_host_w(adj1, adj2, assign, T, nvalid, labels)
+        return greedy_weighted(adj1, adj2, assign, T, _nv32(nvalid, adj1.device), labels)
     if _on_host(adj1, adj1.shape[-2]):
-        return _greedy_host(adj1, adj2, assign, T, nvalid)
+        return _greedy_host(adj1, adj2, assign, T, nvalid, labels)
     b1, b2, nv, flag = _device_inputs(adj1, adj2, nvalid)
-    out = greedy_bits(b1, b2, assign, T, nv)
+    out = greedy_bits(b1, b2, assign, T, nv, labels)
     if flag is not None:
         raise_if_bad(flag)
     return out
 
 
-def all_acc_qap(scores, adj1, adj2, nvalid=None, weighted=False):
+def all_acc_qap(scores, adj1, adj2, nvalid=None, weighted=False, labels=None):
     """toolbox/metrics.py:168-193 per pair: (acc, qap, planted) as (B,) int64 tensors on the scores' device -- the fixed points of the
     Hungarian matching of -log_softmax(scores), sum(g1 * g2[col][:, col]) and sum(g1 * g2).  weighted=True: g1 / g2 are channel 0 of real batches (see the module docstring); qap
-    and planted are float32 (float64 from the host route)."""
+    and planted are float32 (float64 from the host route).  labels (see the module docstring): acc counts the matches with the labels
+    and planted is the objective of the labels' matching (one more count and one more objective launch)."""
     scores = scores.detach()
+    labels = labels_tensor(labels, scores.shape[0], scores.shape[-1], scores.device)
     if weighted:
         if _on_host_weighted(scores, scores.shape[-1]) or not adj1.is_cuda:
-            return _all_acc_qap_host_w(scores, adj1, adj2, nvalid)
+            return _all_acc_qap_host_w(scores, adj1, adj2, nvalid, labels)
         nv = _nv32(nvalid, scores.device)
         correct, assign = lsap_device(scores, nv, want_assign=True)
         out = objective_weighted(adj1, adj2, assign, nv)
+        if labels is not None:
+            correct, out['planted'] = count_matches(assign, labels, nv), objective_weighted(adj1, adj2, labels, nv)['qap']
         return correct.to(torch.int64), out['qap'], out['planted']
     if _on_host(scores, scores.shape[-1]) or not adj1.is_cuda:
-        return _all_acc_qap_host(scores, adj1, adj2, nvalid)
+        return _all_acc_qap_host(scores, adj1, adj2, nvalid, labels)
     b1, b2, nv, flag = _device_inputs(adj1, adj2, nvalid)
     correct, assign = lsap_device(scores, nv, want_assign=True)
     out = objective_bits(b1, b2, assign, nv)
+    if labels is not None:
+        correct, out['planted'] = count_matches(assign, labels, nv), objective_bits(b1, b2, labels, nv)['qap']
     if flag is not None:
         raise_if_bad(flag)
     return correct.to(torch.int64), out['qap'], out['planted']
@@ -269,10 +293,18 @@ def _score2(A, Bm, pi):
     return int((A * Bm[np.ix_(pi, pi)].T).sum())                   # trace(A P B P^T) = sum_{i,k} A[i,k] B[pi(k),pi(i)]
 
 
-def _improve(A, Bm, pi):
+def _label_rows(labels, sizes):
+    """-> per pair the n_b label entries as int64 numpy (arange(n_b) without labels)"""
+    if labels is None:
+        return [np.arange(n) for n in sizes]
+    lab = labels.detach().cpu().numpy().astype(np.int64)
+    return [lab[b, :n] for b, n in enumerate(sizes)]
+
+
+def _improve(A, Bm, pi, label):
     from scipy.optimize import linear_sum_assignment
     _, cols = linear_sum_assignment(-(A @ Bm[pi, :]).astype(np.float64))      # (A P B)[i, j] = sum_k A[i,k] B[pi(k), j]
-    return cols, int((cols == np.arange(len(cols))).sum())
+    return cols, int((cols == label).sum())
 
 
 def _objective_host(adj1, adj2, assign, nvalid):
@@ -289,9 +321,10 @@ def _objective_host(adj1, adj2, assign, nvalid):
     return {'qap': t[0], 'planted': t[1], 'na': t[2], 'nb': t[3]}
 
 
-def _greedy_host(adj1, adj2, assign, T, nvalid):
+def _greedy_host(adj1, adj2, assign, T, nvalid, labels=None):
     B, N = adj1.shape[0], adj1.shape[-2]
     sizes = _sizes(nvalid, B, N)
+    lab = _label_rows(labels, sizes)
     As, Bs = _adjacency_host(adj1, sizes), _adjacency_host(adj2, sizes)
     pis = assign.detach().cpu().numpy()
     s2, acc_b, t_b = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
@@ -306,10 +339,10 @@ def _greedy_host(adj1, adj2, assign, T, nvalid):
         if not ((pi0 >= 0) & (pi0 < n)).all():
             raise RuntimeError('greedy_qap: pair %d starts from an incomplete matching' % b)
         best = _score2(A, Bm, pi0)                                 # of the INITIAL matching
-        pi, acc_best = _improve(A, Bm, pi0)                        # ... while this one is never scored
+        pi, acc_best = _improve(A, Bm, pi0, lab[b])                # ... while this one is never scored
         t_best = 0
         for i in range(T):
-            pi, acc = _improve(A, Bm, pi)
+            pi, acc = _improve(A, Bm, pi, lab[b])
             s = _score2(A, Bm, pi)
             if s > best:
                 best, acc_best, t_best = s, acc, i
@@ -320,16 +353,17 @@ def _greedy_host(adj1, adj2, assign, T, nvalid):
             'perm': torch.from_numpy(perm)}
 
 
-def _all_acc_qap_host(scores, adj1, adj2, nvalid):
+def _all_acc_qap_host(scores, adj1, adj2, nvalid, labels=None):
     from scipy.optimize import linear_sum_assignment
     B, N = scores.shape[0], scores.shape[-1]
     sizes = _sizes(nvalid, B, N)
+    lab = _label_rows(labels, sizes)
     As, Bs = _adjacency_host(adj1, sizes), _adjacency_host(adj2, sizes)
     out = np.zeros((3, B), dtype=np.int64)
     for b, n in enumerate(sizes):
         cost = -torch.log_softmax(scores[b, :n, :n].float(), -1).cpu().numpy()
         _, cols = linear_sum_assignment(cost)
-        out[:, b] = (int((cols == np.arange(n)).sum()), _qap_of(As[b], Bs[b], cols), int((As[b] * Bs[b]).sum()))
+        out[:, b] = (int((cols == lab[b]).sum()), _qap_of(As[b], Bs[b], cols), _qap_of(As[b], Bs[b], lab[b]))
     t = torch.from_numpy(out)
     return t[0], t[1], t[2]
 
@@ -355,10 +389,10 @@ def _score_w(A, Bm, P):                                            # toolbox/uti
     return np.trace(A @ P @ Bm @ P.T) / 2
 
 
-def _improve_w(A, Bm, P):                                          # toolbox/utils.py:234-239
+def _improve_w(A, Bm, P, label):                                   # toolbox/utils.py:234-239
     from scipy.optimize import linear_sum_assignment
     _, cols = linear_sum_assignment(-A @ P @ Bm)
-    return cols, int((cols == np.arange(len(cols))).sum())
+    return cols, int((cols == label).sum())
 
 
 def _objective_host_w(adj1, adj2, assign, nvalid):
@@ -375,9 +409,10 @@ def _objective_host_w(adj1, adj2, assign, nvalid):
     return {'qap': t[0], 'planted': t[1], 'na': t[2], 'nb': t[3]}
 
 
-def _greedy_host_w(adj1, adj2, assign, T, nvalid):
+def _greedy_host_w(adj1, adj2, assign, T, nvalid, labels=None):
     B, N = adj1.shape[0], adj1.shape[-1]
     sizes = _sizes(nvalid, B, N)
+    lab = _label_rows(labels, sizes)
     As, Bs = _matrices_host_w(adj1, sizes), _matrices_host_w(adj2, sizes)
     pis = assign.detach().cpu().numpy()
     s_b, na, nb = np.zeros(B), np.zeros(B), np.zeros(B)
@@ -392,10 +427,10 @@ def _greedy_host_w(adj1, adj2, assign, T, nvalid):
         if not ((pi0 >= 0) & (pi0 < n)).all():
             raise RuntimeError('greedy_qap: pair %d starts from an incomplete matching' % b)
         best = _score_w(A, Bm, _perm_matrix(pi0))                  # of the INITIAL matching
-        pi, acc_best = _improve_w(A, Bm, _perm_matrix(pi0))        # ... while this one is never scored
+        pi, acc_best = _improve_w(A, Bm, _perm_matrix(pi0), lab[b])    # ... while this one is never scored
         t_best = 0
         for i in range(T):
-            pi, acc = _improve_w(A, Bm, _perm_matrix(pi))
+            pi, acc = _improve_w(A, Bm, _perm_matrix(pi), lab[b])
             s = _score_w(A, Bm, _perm_matrix(pi))
             if s > best:
                 best, acc_best, t_best = s, acc, i
@@ -405,10 +440,11 @@ def _greedy_host_w(adj1, adj2, assign, T, nvalid):
             'T_best': torch.from_numpy(t_b), 'perm': torch.from_numpy(perm)}
 
 
-def _all_acc_qap_host_w(scores, adj1, adj2, nvalid):
+def _all_acc_qap_host_w(scores, adj1, adj2, nvalid, labels=None):
     from scipy.optimize import linear_sum_assignment
     B, N = scores.shape[0], scores.shape[-1]
     sizes = _sizes(nvalid, B, N)
+    lab = _label_rows(labels, sizes)
     As, Bs = _matrices_host_w(adj1, sizes), _matrices_host_w(adj2, sizes)
     acc, out = np.zeros(B, dtype=np.int64), np.zeros((2, B), dtype=np.float64)
     for b, n in enumerate(sizes):
@@ -416,6 +452,6 @@ def _all_acc_qap_host_w(scores, adj1, adj2, nvalid):
             continue
         cost = -torch.log_softmax(scores[b, :n, :n].float(), -1).cpu().numpy()
         _, cols = linear_sum_assignment(cost)
-        acc[b] = int((cols == np.arange(n)).sum())
-        out[:, b] = ((As[b] * Bs[b][cols, :][:, cols]).sum(), (As[b] * Bs[b]).sum())
+        acc[b] = int((cols == lab[b]).sum())
+        out[:, b] = ((As[b] * Bs[b][cols, :][:, cols]).sum(), (As[b] * Bs[b][lab[b], :][:, lab[b]]).sum())
     return torch.from_numpy(acc), torch.from_numpy(out[0]), torch.from_numpy(out[1])

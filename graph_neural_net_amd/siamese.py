@@ -14,7 +14,7 @@ import torch.nn as nn
 from . import _lib, qap
 from .blocks import block, block_emb, node_embedding
 from .losses import triplet_loss
-from .metrics import accuracy_linear_assignment, accuracy_max, lsap_device
+from .metrics import accuracy_linear_assignment, accuracy_max, count_matches, labels_tensor, lsap_device
 from .masked import MaskedTensor
 from .network import Network
 
@@ -127,7 +127,7 @@ class Siamese_Node_Exp(nn.Module):
             return MaskedTensor(scores, nvalid, (1, 2), x1.base_name)
         return scores
 
-    def match(self, x1, x2, refine=0, weighted=False):
+    def match(self, x1, x2, refine=0, weighted=False, labels=None):
         """Decode a batch: the eager forward under no_grad (no `.grad` is touched), the Hungarian matching of -log_softmax(scores)
         and the reference's evaluation of it (toolbox/metrics.py:168-193 all_acc_qap), all on the device (qap.py).  Takes what
         `forward` takes.  Returns a dict: scores ((bs, n, n) tensor or MaskedTensor), assign ((bs, n) int32: the matched column of
@@ -139,7 +139,12 @@ class Siamese_Node_Exp(nn.Module):
 
         weighted=True decodes real-weighted batches -- the output of PairGenerator.spectral goes straight in: channel 0 of the batch
         is used as the matrices, as the reference's all_acc_qap does (qap.py, csrc/qap_weighted.hip).  No verdict is taken and nothing
-        synchronises; the keys are the same, with qap, planted, s_best, na, nb as float32."""
+        synchronises; the keys are the same, with qap, planted, s_best, na, nb as float32.
+
+        labels (planted.py; a (bs, n) integer tensor, labels[b, i] = the vertex of x2 that vertex i of x1 is, or the reference's list
+        of per-graph arrays; wider rows, such as a generator's (bs, N) labels beside a ragged batch cropped to its largest graph, are
+        cut to n): acc and acc_best count the matches with the labels instead of the fixed points, and planted is the objective of
+        the labels' matching.  None: the identity, as before."""
         a1, a2 = _unwrap_input(x1), _unwrap_input(x2)
         with torch.no_grad():
             scores = self(a1, a2)
@@ -148,20 +153,27 @@ class Siamese_Node_Exp(nn.Module):
             s = scores.tensor.rename(None) if ragged else scores
             dev = s.device
             nv = a1.nvalid.to(device=dev, dtype=torch.int32).contiguous() if ragged else None
+            if torch.is_tensor(labels) and labels.dim() == 2 and labels.shape[1] > s.shape[-1]:
+                labels = labels[:, :s.shape[-1]]
+            labels = labels_tensor(labels, s.shape[0], s.shape[-1], dev)
             if weighted:
                 correct, assign = lsap_device(s, nv, want_assign=True)
                 obj = qap.objective_weighted(t1, t2, assign, nv)
+                if labels is not None:
+                    correct, obj['planted'] = count_matches(assign, labels, nv), qap.objective_weighted(t1, t2, labels, nv)['qap']
                 out = {'scores': scores, 'assign': assign, 'acc': correct.to(torch.int64), 'qap': obj['qap'], 'planted': obj['planted']}
                 if refine:
-                    out.update(qap.greedy_weighted(t1, t2, assign, int(refine), nv))
+                    out.update(qap.greedy_weighted(t1, t2, assign, int(refine), nv, labels))
                 return out
             flag = torch.zeros(1, dtype=torch.int32, device=dev)
             b1, b2 = qap.to_bits(t1, nv, flag), qap.to_bits(t2, nv, flag)
             correct, assign = lsap_device(s, nv, want_assign=True)
             obj = qap.objective_bits(b1, b2, assign, nv)
+            if labels is not None:
+                correct, obj['planted'] = count_matches(assign, labels, nv), qap.objective_bits(b1, b2, labels, nv)['qap']
             out = {'scores': scores, 'assign': assign, 'acc': correct.to(torch.int64), 'qap': obj['qap'], 'planted': obj['planted']}
             if refine:
-                out.update(qap.greedy_bits(b1, b2, assign, int(refine), nv))
+                out.update(qap.greedy_bits(b1, b2, assign, int(refine), nv, labels))
         self._raise_if_not_representation({'flag': flag})
         return out
 

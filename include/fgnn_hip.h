@@ -744,6 +744,33 @@ int fgnn_pairgen_indexed(const fgnn_pairgen_args *args, const long long *index, 
 int fgnn_epoch_index(unsigned long long seed, unsigned long long epoch, long long M, long long first_pos, long long count,
                      long long *out, void *stream);
 
+/* ---- planted permutations (csrc/planted.hip; graph_neural_net_amd/planted.py) -------------------------------------------------
+ * labels: (B, N) int32, labels[b][i] = pi_b(i): vertex i of the first graph of pair b is vertex pi_b(i) of the second; entries
+ * i >= n_b are -1, like assign.  nvalid (optional, int32[B]) = n_b, clamped to [0, N]; N <= FGNN_PLANTED_MAX_N.  No entry point copies
+ * to the host, allocates or synchronises: all are capturable.
+ *
+ * fgnn_planted_perm: a uniform permutation of [0, n_b) per pair, a function of (seed, pair index) only: pair b is first + b, or
+ *   index[b] when index (int64[B] on the device) is given (first is then ignored; a negative index, a caller error, gives the empty
+ *   permutation: all -1).  Fisher-Yates from the top on the identity: for k = n_b - 1 .. 1, j = (u32_k (k + 1)) >> 32, swap p[k], p[j],
+ *   with u32_k raw draw k of pair stream FGNN_PLANTED_STREAM (third counter word, fourth word 0, as every pair stream).
+ * fgnn_relabel_bits: out[pi(i)][pi(j)] = in[i][j] on (B, N, ceil(N/32)) bit words; no symmetry assumed; rows, columns and padding bits
+ *   >= n_b of out are zero whatever in holds there.  out may be in.
+ * fgnn_relabel_dense: the same movement on (B, C, ld, ld) fp32 planes (out != in), any C >= 1, ld <= FGNN_PLANTED_MAX_N; labels has
+ *   row pitch NL and n_b is clamped to [0, min(ld, NL)].  Pure data movement: bit-exact; everything outside the n_b x n_b corner of
+ *   out is an exact zero, and nothing outside the corner of in is read.  The batch must be smaller than 2 GiB, B <= 65535.
+ * A labels row that is no permutation of [0, n_b) is a caller error; rows and columns no entry maps to come out zero.
+ * fgnn_count_matches: correct[b] = #{i < n_b : assign[b][i] == labels[b][i]} (both (B, N) int32).
+ * fgnn_accuracy_max_labels: fgnn_accuracy_max against labels: correct[b] = #{i < n_b : argmax_j scores[b,i,j] == labels[b][i]}, the
+ *   same arg-max (first maximum on ties, NaN above every number). */
+#define FGNN_PLANTED_STREAM 7
+#define FGNN_PLANTED_MAX_N 256
+int fgnn_planted_perm(unsigned long long seed, long long first, const long long *index /* optional */, const int *nvalid /* optional */,
+                      int B, int N, int *labels, void *stream);
+int fgnn_relabel_bits(const unsigned *in, const int *labels, const int *nvalid, int B, int N, unsigned *out, void *stream);
+int fgnn_relabel_dense(const float *in, const int *labels, const int *nvalid, int B, int C, int ld, int NL, float *out, void *stream);
+int fgnn_count_matches(const int *assign, const int *labels, const int *nvalid, int B, int N, int *correct, void *stream);
+int fgnn_accuracy_max_labels(const float *scores, const int *labels, const int *nvalid, int B, int N, int *correct, void *stream);
+
 /* ---- decoding a matching: QAP objective and greedy refinement (csrc/qap.hip; toolbox/metrics.py:168-193 all_acc_qap,
  * toolbox/utils.py:225-256 perm_matrix / score / improve / greedy_qap) --------------------------------------------------------
  * bits1 / bits2: (B, N, ceil(N/32)) words, bit j of word row i = A[i][j] resp. B[i][j] (the layout of fgnn_expand_adjacency).
@@ -775,6 +802,12 @@ int fgnn_qap_improve_cost(const unsigned *bits1, const unsigned *bits2, const in
 long long fgnn_greedy_qap_ws_bytes(int B, int N);
 int fgnn_greedy_qap(const unsigned *bits1, const unsigned *bits2, const int *assign0, const int *nvalid, int B, int N, int T, void *ws,
                     long long ws_bytes, int *s_best2, int *acc_best, int *t_best, int *perm_best /* optional */, void *stream);
+/* fgnn_greedy_qap scored against labels (B, N; the section on planted permutations): the same launch sequence and workspace, with a
+ * fgnn_count_matches launch after every solver call, so that acc_best counts assign[i] == labels[i] instead of fixed points.  An
+ * extension: the reference's greedy_qap has no such parameter (its label is arange).  Every other output is that of fgnn_greedy_qap. */
+int fgnn_greedy_qap_labels(const unsigned *bits1, const unsigned *bits2, const int *assign0, const int *labels, const int *nvalid, int B,
+                           int N, int T, void *ws, long long ws_bytes, int *s_best2, int *acc_best, int *t_best,
+                           int *perm_best /* optional */, void *stream);
 
 /* ---- decoding a matching on real-weighted pairs (csrc/qap_weighted.hip): the fp32 twin of the section above, for what the
  * reference's all_acc_qap / greedy_qap take besides 0/1 adjacency -- a spectral L = D^-1/2 W D^-1/2, any weighted graph ---------
@@ -811,6 +844,10 @@ long long fgnn_greedy_qapw_ws_bytes(int B, int N);
 int fgnn_greedy_qapw(const float *a1, const float *a2, long long gstride, int ld, const int *assign0, const int *nvalid, int B, int N, int T,
                      void *ws, long long ws_bytes, float *s_best, int *acc_best, int *t_best, int *perm_best /* optional */,
                      void *stream);
+/* the weighted twin of fgnn_greedy_qap_labels: fgnn_greedy_qapw with acc_best counted against labels */
+int fgnn_greedy_qapw_labels(const float *a1, const float *a2, long long gstride, int ld, const int *assign0, const int *labels,
+                            const int *nvalid, int B, int N, int T, void *ws, long long ws_bytes, float *s_best, int *acc_best,
+                            int *t_best, int *perm_best /* optional */, void *stream);
 
 /* ---- spectral input features (csrc/spectral.hip; loaders/data_generator.py:221-232 make_laplacian / make_spectral_feature, the
  * input of QAP_spectralGenerator) ---------------------------------------------------------------------------------------------
