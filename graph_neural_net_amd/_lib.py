@@ -140,6 +140,17 @@ class PairgenArgs(C.Structure):       # fgnn_pairgen_args (csrc/pairgen.hip)
                 ('bits1', C.c_void_p), ('bits2', C.c_void_p), ('nvalid', C.c_void_p)]
 
 
+FGNN_GUARD_MAX_PARTS = 64         # include/fgnn_hip.h
+FGNN_GUARD_SKIP_NONFINITE = 1     # mode bit
+FGNN_GUARD_NONFINITE = 1          # flags bit
+
+
+class GuardRecord(C.Structure):       # fgnn_guard_record (csrc/grad_guard.hip); lives in device memory, this mirror gives the offsets
+    _fields_ = [('max_norm', C.c_double), ('norm', C.c_double), ('coef', C.c_double),
+                ('flags', C.c_int), ('skipped', C.c_int), ('arrivals', C.c_int), ('mode', C.c_int),
+                ('partial', C.c_double * FGNN_GUARD_MAX_PARTS)]
+
+
 MAX_GRAD_JOBS = 16
 MAX_PACK_JOBS = 24
 _VP, _LL, _I, _F = C.c_void_p, C.c_longlong, C.c_int, C.c_float
@@ -230,6 +241,8 @@ _SIGNATURES = {
     'fgnn_sum_scale': [_VP, _I, _I, _F, _VP, _VP],
     'fgnn_adam_step': [_VP, _VP, _VP, _VP, _I, C.c_double, C.c_double, C.c_double, C.c_double, _I, C.c_double, _VP],
     'fgnn_adam_step_dev': [_VP, _VP, _VP, _VP, _I, _VP, _VP, _VP],
+    'fgnn_grad_guard': [_VP, _I, _VP, _VP, _VP],
+    'fgnn_adam_step_guarded': [_VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP],
     'fgnn_expand_adjacency': [_VP, _VP, _I, _I, _VP, _VP],
     'fgnn_pack_adjacency': [_VP, _VP, _I, _I, _VP, _VP, _VP],
     'fgnn_pack_adjacency_ld': [_VP, _VP, _I, _I, _I, _VP, _VP, _VP],

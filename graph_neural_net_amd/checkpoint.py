@@ -71,12 +71,14 @@ def save_checkpoint(path, layout, flat, extra=None, epoch=0, global_step=0, opti
     'epoch', 'global_step', 'pytorch-lightning_version'} (the keys Lightning's load_from_checkpoint migration looks at;
     models/__init__.py:19-24), plus -- optionally -- the fused Adam state so that a resumed run continues the optimizer
     ('fgnn_adam': exp_avg, exp_avg_sq, step, lr).  Only tensors and plain scalars are written, so the file loads with
-    weights_only=True."""
+    weights_only=True.  For an optimizer that skips non-finite steps (FlatAdam(skip_nonfinite=True)) 'step' is the count in device
+    memory, which skipped steps did not advance (one host read); restore_optimizer puts it back there."""
     sd = {'node_embedder.' + k: v.detach().cpu().clone() for k, v in layout.unflatten(flat).items()}
     obj = {'state_dict': sd, 'epoch': int(epoch), 'global_step': int(global_step), 'pytorch-lightning_version': '1.9.0'}
     if optimizer is not None:
+        step = optimizer.step_count() if getattr(optimizer, 'skip_nonfinite', False) else optimizer.t
         obj['fgnn_adam'] = {'exp_avg': optimizer.exp_avg.detach().cpu().clone(), 'exp_avg_sq': optimizer.exp_avg_sq.detach().cpu().clone(),
-                            'step': int(optimizer.t), 'lr': float(optimizer.lr)}
+                            'step': int(step), 'lr': float(optimizer.lr)}
     if extra:
         obj.update(extra)
     torch.save(obj, path)

@@ -18,7 +18,7 @@ class FgnnTrainer:
     INPUT_CHECK_EVERY = 128     # input_form='tensor_representation': the device verdict is read back on every k-th train_step (0: never)
 
     def __init__(self, layout, params_flat, lr=1e-3, capture=False, precision='fp32', collective='auto', block1=None,
-                 input_form='dense'):
+                 input_form='dense', max_grad_norm=None, skip_nonfinite=False):
         """capture=True: constant-shape steps are captured in a HIP graph and replayed -- the launch overhead of ~40 kernels
         per step disappears.  With more than one rank the gradient all-reduce is recorded INSIDE that graph when the backend
         can be captured (RCCL: model work -> all-reduce -> fused Adam is one replay, no host launch on the critical path;
@@ -33,7 +33,14 @@ class FgnnTrainer:
         reference's loaders yield (loaders/data_generator.py:118-125); train_step then bit-packs them on the device
         (fgnn_pack_adjacency, which also verifies the statement: the verdict is read on the first step of a shape and on every
         INPUT_CHECK_EVERY-th step, and a batch that is not a tensor representation raises) and runs train_step_bits with the structured
-        block 1.  'dense' (default): dense batches run the generic kernels, whatever block1 says."""
+        block 1.  'dense' (default): dense batches run the generic kernels, whatever block1 says.
+        max_grad_norm / skip_nonfinite: the guarded optimizer step (optim.FlatAdam) -- clip the global L2 norm of the normalised
+        gradient with clip_grad_norm_ semantics (Lightning's gradient_clip_val), and drop the whole update when the gradient holds
+        an inf or a NaN (what the AMP GradScaler behind pl.Trainer(precision=16) does).  The guard is part of every optimizer
+        step: the eager one, the one-graph captured step and the optimizer graph of the gloo fallback; `grad_norm` and
+        `skipped_steps` stay on the device and no step reads them.  It runs AFTER the all-reduce, on a buffer that is bit-identical
+        on every rank, and its sums have a fixed order, so every rank takes the same clip and skip decision without another
+        collective.  The defaults (None, False) leave every launch sequence and captured graph as it was."""
         if input_form not in ('dense', 'tensor_representation'):
             raise ValueError('input_form must be "dense" or "tensor_representation" (got %r)' % (input_form,))
         self.input_form = input_form
@@ -54,7 +61,7 @@ class FgnnTrainer:
         self.grads = self.comm[:n]
         self._loss_sum = self.comm[n:n + 1]
         self._nodes = self.comm[n + 1:n + 2]
-        self.opt = FlatAdam(params_flat, lr=lr)
+        self.opt = FlatAdam(params_flat, lr=lr, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
         self.capture = capture
         self._engines = EngineCache(self.ENGINE_CACHE_BYTES)
         self._graphs = {}
@@ -71,7 +78,7 @@ class FgnnTrainer:
             self.allreduce_in_graph = bool(capture) and dp.collective_captures()
 
     @classmethod
-    def from_module(cls, model, lr=None, capture=True):
+    def from_module(cls, model, lr=None, capture=True, max_grad_norm=None, skip_nonfinite=False):
         """The fused training step for a `Siamese_Node_Exp` built through the reference's own surface
         (models/trainers.py:20-58): the trainer works IN PLACE on the module's flat parameter buffer, so the module
         (its `state_dict`, its eager forward) always sees the trained weights, and `capture=True` gives a reference user the
@@ -83,7 +90,17 @@ class FgnnTrainer:
                                '(original_features_num 2 or 32, in_features = out_features = 32)')
         net._bind_flat()
         return cls(lay, net._flat, lr=model.lr if lr is None else lr, capture=capture, precision=getattr(net, 'precision', 'fp32'),
-                   input_form=getattr(net, 'input_form', 'dense'))
+                   input_form=getattr(net, 'input_form', 'dense'), max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+
+    @property
+    def grad_norm(self):
+        """0-dim fp64 device tensor: global L2 norm of the last step's normalised gradient, before clipping (guarded trainers)"""
+        return self.opt.grad_norm
+
+    @property
+    def skipped_steps(self):
+        """0-dim int32 device tensor: updates dropped so far because their gradient was not finite (guarded trainers)"""
+        return self.opt.skipped_steps
 
     # ------------------------------------------------------------------ engines: bounded cache keyed on padded shapes
     def _engine(self, G, N, ragged):

@@ -462,6 +462,33 @@ int fgnn_adam_step(float *params, const float *grads, float *exp_avg, float *exp
  * state (device, 2 ints, zero-initialised) = {steps taken, internal arrival counter}; the kernel advances state[0] */
 int fgnn_adam_step_dev(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int n,
                        const double *hp, int *state, void *stream);
+/* ---- guarded optimizer step (csrc/grad_guard.hip): what the reference gets from pl.Trainer(precision=16) -- the AMP GradScaler
+ * skips optimizer.step() on a non-finite gradient -- and from Lightning's gradient_clip_val, on the device and capturable.
+ * The record lives in device memory, zero-initialised by its owner, who then writes max_norm and mode; the kernels write the rest. */
+#define FGNN_GUARD_MAX_PARTS 64
+#define FGNN_GUARD_SKIP_NONFINITE 1 /* mode bit 0: a non-finite gradient skips the whole update */
+#define FGNN_GUARD_NONFINITE 1      /* flags bit 0: the last guarded gradient held an inf or a NaN */
+typedef struct {
+    double max_norm; /* in: clip the global L2 norm to this; <= 0: no clipping */
+    double norm;     /* out: L2 norm of the scaled gradient, before clipping (what clip_grad_norm_ returns) */
+    double coef;     /* out: min(1, max_norm / (norm + 1e-6)); 1 without clipping; NaN when the norm is NaN (torch.clamp) */
+    int flags;       /* out: FGNN_GUARD_NONFINITE or 0, rewritten by every launch */
+    int skipped;     /* out: updates skipped so far (counts only in skip mode) */
+    int arrivals;    /* internal arrival counter, 0 between launches */
+    int mode;        /* in: FGNN_GUARD_SKIP_NONFINITE or 0 */
+    double partial[FGNN_GUARD_MAX_PARTS]; /* internal: the workgroups' sums of squares */
+} fgnn_guard_record;
+/* norm, coef and flags of gi = grads[i] * (float)hp[4], i < n (the fp32 product the Adam kernels form); sum of gi^2 in fp64.
+ * The order of every addition is a function of n alone (a fixed number of workgroups with one contiguous chunk each, fixed-order
+ * wave / LDS / partial sums, no floating-point atomics): the same buffer gives the same bits on every launch and every rank.
+ * In skip mode a non-finite gradient also advances guard->skipped.                                                           */
+int fgnn_grad_guard(const float *grads, int n, const double *hp, fgnn_guard_record *guard, void *stream);
+/* fgnn_adam_step_dev with grad_scale = (float)(hp[4] * guard->coef), after fgnn_grad_guard on the same grads / hp / guard.  In
+ * skip mode with the non-finite flag set nothing is written: parameters, both moments and state[0] keep their values (a skipped
+ * step does not count towards the bias correction, as under GradScaler).  Without skip mode a non-finite gradient propagates
+ * as in torch (clip_grad_norm_(error_if_nonfinite=False) + Adam).                                                            */
+int fgnn_adam_step_guarded(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int n, const double *hp,
+                           int *state, const fgnn_guard_record *guard, void *stream);
 /* accuracy_max (toolbox/metrics.py:119-141): correct[b] = #{i < n_b : argmax_j scores[b,i,j] == i},
  * with np.argmax's order: first maximum on ties, NaN above every number (the first NaN wins), a row of -inf
  * has column 0 as arg-max; int32, bit-exact.                                                         */
