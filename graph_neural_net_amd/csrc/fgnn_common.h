@@ -110,6 +110,14 @@ DEVI float relu1(float x) {
 }
 
 DEVI int nvalid_of(const int *nvalid, int g, int N) { return nvalid ? nvalid[g] : N; }
+// The same through a buffer descriptor (an empty one without nvalid: returns 0, no access), for the 16-pixel tile loops:
+//   const rsrc_t rnv = __builtin_amdgcn_make_buffer_rsrc(const_cast<int *>(nvalid), 0, ragged ? G * 4 : 0, 0x00020000);
+// `nvalid ? nvalid[g] : N` compiles to ONE load through a select of the two addresses -- a FLAT load, which makes every later
+// s_waitcnt of the tile loop a full drain (flat operations complete out of order with respect to buffer loads)
+DEVI int graph_nv(const rsrc_t &rnv, bool ragged, int g, int N) {
+    const int v = __builtin_amdgcn_raw_buffer_load_b32(rnv, g * 4, 0, 0);
+    return __builtin_amdgcn_readfirstlane(ragged ? v : N);
+}
 
 // Workgroups are dispatched round-robin over the 8 XCDs, each with its own L2.  Kernels whose consecutive logical
 // workgroups share per-graph data (the 32 channel matrices of one graph read the same rows of tile statistics) remap

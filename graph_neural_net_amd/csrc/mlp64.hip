@@ -27,11 +27,6 @@ constexpr int SUB = 1024;              // floats per 32 x 32 operand set
 constexpr int NWF = M64_NWF, NWB = 4;  // waves per workgroup: forward (2 per SIMD), backward (1 per SIMD)
 constexpr int WG64 = 256;              // persistent workgroups = rows of wpart
 
-DEVI int graph_nv(const rsrc_t &rnv, bool ragged, int g, int N) {
-    const int v = __builtin_amdgcn_raw_buffer_load_b32(rnv, g * 4, 0, 0);
-    return __builtin_amdgcn_readfirstlane(ragged ? v : N);
-}
-
 // element f of an operand set: k-step s, row block b, MFMA lane (m, kq)  (fgnn_t16.h gemm32: image element (t, lane), t = 2 s + b,
 // stored [t / 4][lane][4])
 struct SetElem {

@@ -20,8 +20,9 @@
 // are bit-reproducible run to run.
 // Execution shape: one 512-thread workgroup per CU (2 waves per SIMD, <= 256 VGPRs), all
 // MFMA A-operands in workgroup-shared LDS, three aliased 32x36 LDS tiles per wave.
-#include "fgnn_common.h"
+#include "fgnn_tile.h"
 #include "fgnn_pack.h"
+#include "fgnn_bwd32.h"
 
 #ifdef FGNN_PHASES
 // Debug build only (make phases): per-wave cycle stamps of the tile phases, summed over the wave's
@@ -38,140 +39,6 @@ __device__ int g_phase_sel = 0;       // CA * 100 + CB of the variant that recor
 #endif
 
 namespace {
-
-constexpr int TLD = 36;              // LDS tile row stride (floats): 144 B rows, 16-B aligned
-constexpr int TILE_F = 32 * TLD;     // floats per 32-row tile
-constexpr int BWD_WG = 256;          // persistent workgroups (one per CU)
-
-struct TileCtx {
-    int g, tt, p, i, jj;
-    bool inb;
-};
-
-// The valid-vertex count of the graph is NOT read here: a global load at the top of every tile makes
-// the compiler drain the whole memory pipeline (s_waitcnt vmcnt(0): next-tile prefetch AND the previous
-// tile's stores).  It is fetched once per graph change, next to the per-graph records.
-DEVI TileCtx decode_tile(int tile, bool active, int tpg, int N, int P, int j) {
-    TileCtx c;
-    c.g = __builtin_amdgcn_readfirstlane(active ? tile / tpg : 0);
-    c.tt = active ? tile - c.g * tpg : 0;
-    c.p = c.tt * FGNN_TILE + j;
-    c.inb = active && c.p < P;
-    c.i = c.p / N;
-    c.jj = c.p - c.i * N;
-    return c;
-}
-DEVI bool tile_valid(const TileCtx &c, int nv) { return c.inb && c.i < nv && c.jj < nv; }
-
-// channel contracted by k-step k in half-wave h (same convention as mlp_fwd.hip)
-template <int S>
-DEVI constexpr int slab_ch(int k, int h) { return S == 16 ? ch_of(k, h) : 2 * k + h; }
-
-// h-independent part of slab_ch, and the row multiplier of the h part
-template <int S>
-DEVI constexpr int slab_kbase(int k) { return S == 16 ? (k & 3) + 8 * (k >> 2) : 2 * k; }
-template <int S>
-DEVI constexpr int slab_hmul() { return S == 16 ? 4 : 1; }
-
-// per-lane byte offset of pixel c.p in the half-wave's first row (OOB_OFF when out of range)
-template <int HMUL>
-DEVI int lane_off(const View &v, const TileCtx &c, int h) {
-    return c.inb ? HMUL * h * v.ld4 + 4 * c.p : OOB_OFF;
-}
-
-template <int S>
-DEVI void load_raw(float (&x)[S > 0 ? S : 1], const View &v, const TileCtx &c, int h) {
-    if constexpr (S > 0) {
-        const int voff = lane_off<slab_hmul<S>()>(v, c, h);
-        const int s0 = c.g * v.gs4;
-#pragma unroll
-        for (int k = 0; k < S; ++k) x[k] = buf_load(v, voff, s0 + slab_kbase<S>(k) * v.ld4);
-    }
-}
-
-// slab load: from memory, or (PK, 2-channel slabs only) from the packed adjacency
-template <int S, bool PK>
-DEVI void load_slab(float (&x)[S > 0 ? S : 1], const View &v, const PackedSrc &ps, const TileCtx &c, int h) {
-    if constexpr (PK && S == 1) load_packed(x, ps, c, h);
-    else load_raw<S>(x, v, c, h);
-}
-
-// rows ch_of(r,h) of a (G,32,ld) tensor
-DEVI void load_rows16(float (&x)[16], const View &v, const TileCtx &c, int h) {
-    const int voff = lane_off<4>(v, c, h);
-    const int s0 = c.g * v.gs4;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) x[r] = buf_load(v, voff, s0 + ((r & 3) + 8 * (r >> 2)) * v.ld4);
-}
-
-// y = (x - mean) * a + beta with the per-graph records {mean, a, beta, -} read from LDS
-template <int S>
-DEVI void norm_from_lds(float (&y)[S > 0 ? S : 1], const float (&x)[S > 0 ? S : 1], const float *rec, bool on,
-                        bool valid, int h) {
-    if constexpr (S > 0) {
-        const float4 *r4 = reinterpret_cast<const float4 *>(rec);
-        if (on) {                       // wave-uniform: ONE branch, not one per element
-            // multiply by a 0/1 mask instead of `valid ? .. : 0`: the ternary is turned into divergent
-            // control flow around the LDS reads, with a full-array phi copy per element
-            const float vf = valid ? 1.f : 0.f;
-#pragma unroll
-            for (int k = 0; k < S; ++k) {
-                const float4 n = r4[slab_ch<S>(k, h)];
-                y[k] = ((x[k] - n.x) * n.y + n.z) * vf;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < S; ++k) y[k] = x[k];
-        }
-    }
-}
-
-// dz coefficients {mean, ca, cb, cc} of channel `ch` of graph g: precomputed (A.coef) or derived here
-// from the GraphNorm-backward sums S1,S2 and the output's GraphNorm record:
-//   dz = a*dy - a*S2*r2/m * (z - mean) - a*S1/m
-DEVI float4 coef_from_sums(const float4 n, const float2 sv, float nv) {
-    const float m = nv * nv;
-    float4 k;
-    k.x = n.x;
-    k.y = n.y;
-    k.z = m > 0.f ? -n.y * sv.y * n.w / m : 0.f;
-    k.w = m > 0.f ? -n.y * sv.x / m : 0.f;
-    return k;
-}
-DEVI float4 coef_record(const fgnn_mlp_bwd_args &A, int g, int ch) {
-    if (A.coef) return reinterpret_cast<const float4 *>(A.coef)[(long long)g * FGNN_H + ch];
-    const float4 n = reinterpret_cast<const float4 *>(A.znrm)[(long long)g * FGNN_H + ch];
-    const float2 sv = reinterpret_cast<const float2 *>(A.s12)[(long long)g * FGNN_H + ch];
-    return coef_from_sums(n, sv, (float)nvalid_of(A.nvalid, g, A.N));
-}
-
-// dW += Dt (rows = out channel) x In (rows = in channel), contraction over the 32 pixels.
-// The Dt fragments of lane (o, h) are 16 pixels of channel o, so the bias gradient
-// db[o] = sum_px Dt[o][px] falls out of the same LDS reads (WITH_DB).
-template <bool WITH_DB>
-DEVI f32x16 wgrad_tile(const float *Dt, const float *In, f32x16 acc, float &db, int lane) {
-    const int i = lane & 31, h = lane >> 5;
-    const float4 *dp = reinterpret_cast<const float4 *>(Dt + i * TLD + 4 * h);
-    const float4 *ip = reinterpret_cast<const float4 *>(In + i * TLD + 4 * h);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 a = dp[2 * q];
-        const float4 b = ip[2 * q];
-        if (WITH_DB) db += (a.x + a.y) + (a.z + a.w);
-        acc = mfma32(a.x, b.x, acc);
-        acc = mfma32(a.y, b.y, acc);
-        acc = mfma32(a.z, b.z, acc);
-        acc = mfma32(a.w, b.w, acc);
-    }
-    return acc;
-}
-
-DEVI void zero16(f32x16 &a) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = 0.f;
-}
-
-constexpr int NW = 8;                // waves per workgroup (2 per SIMD)
 
 // Operand sets kept in workgroup-shared LDS (one float per lane per k-step, stored as
 // [step/4][lane][4] so a ds_read_b128 returns four consecutive k-steps of a lane), the
@@ -201,33 +68,6 @@ struct BwdLayout {
     static constexpr int MAIN_F = WEIGHT_F + NW * REC_F + TILE_F_ALL + WGK_F;
     static constexpr int LDS_F = MAIN_F > RED_F ? MAIN_F : RED_F;
 };
-
-template <int OFF, int CNT>
-DEVI void load_ops(float (&dst)[CNT > 0 ? CNT : 1], const float *wl, int lane) {
-    static_assert(OFF % 4 == 0, "operand sets are float4 aligned");
-    const float4 *p = reinterpret_cast<const float4 *>(wl) + (OFF / 4) * 64 + lane;
-#pragma unroll
-    for (int q = 0; q < (CNT + 3) / 4; ++q) {
-        const float4 v = p[q * 64];
-        if (4 * q + 0 < CNT) dst[4 * q + 0] = v.x;
-        if (4 * q + 1 < CNT) dst[4 * q + 1] = v.y;
-        if (4 * q + 2 < CNT) dst[4 * q + 2] = v.z;
-        if (4 * q + 3 < CNT) dst[4 * q + 3] = v.w;
-    }
-}
-
-// bias[ch_of(r, h)], r = 0..15, of one layer from the compact tail (broadcast reads)
-DEVI void load_bias(float (&dst)[16], const float *tail, int layer, int h) {
-    const float4 *p = reinterpret_cast<const float4 *>(tail + layer * 32 + h * 16);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 v = p[q];
-        dst[4 * q + 0] = v.x;
-        dst[4 * q + 1] = v.y;
-        dst[4 * q + 2] = v.z;
-        dst[4 * q + 3] = v.w;
-    }
-}
 
 // SKIP (ragged batches with A.ranges): the workgroup's tile range comes from fgnn_ragged_tile_ranges (equal work), the
 // waves step over tiles without a single valid pixel (they contribute nothing to the parameter gradients); the only thing
@@ -282,16 +122,8 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_kernel(const fgnn_mlp_bwd_
 #pragma unroll
     for (int l = 0; l < DEPTH; ++l) db[l] = 0.f;
 
-    // static, strided tile assignment inside the workgroup's contiguous range: the order in
-    // which a wave accumulates its weight gradients is fixed -> bit-reproducible results
-    const int nwg = gridDim.x;
-    const int q = total_tiles / nwg, rem = total_tiles % nwg;
-    int T0 = blockIdx.x * q + ((int)blockIdx.x < rem ? (int)blockIdx.x : rem);
-    int T1 = T0 + q + ((int)blockIdx.x < rem ? 1 : 0);
-    if constexpr (SKIP) {
-        T0 = A.ranges[blockIdx.x];
-        T1 = A.ranges[blockIdx.x + 1];
-    }
+    int T0, T1;
+    wg_tile_range<SKIP>(A.ranges, total_tiles, T0, T1);
     const bool normA = A.a.nrm != nullptr, normB = (CB > 0) && A.b.nrm != nullptr;
     const bool emit = (CA == 32) && (CB == 0) && normA && A.dxa != nullptr && A.s12part != nullptr;
     // dz coefficients from the per-tile sums its consumer left behind (the work of fgnn_gn_bwd_coef_tiles,
@@ -439,8 +271,8 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_kernel(const fgnn_mlp_bwd_
             f32x16 acc;
             {
                 float ya[SA > 0 ? SA : 1], yb[SB > 0 ? SB : 1];
-                norm_from_lds<SA>(ya, xa, recA, normA, c_valid, h);
-                norm_from_lds<SB>(yb, xb, recB, normB, c_valid, h);
+                norm_slab<SA>(ya, xa, recA, normA, c_valid, h);
+                norm_slab<SB>(yb, xb, recB, normB, c_valid, h);
                 PH(0)   // tile decode, records, x arrived + normalised
                 float b0[16];
                 load_bias(b0, wl + L::BIAS_F, 0, h);
@@ -498,7 +330,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_kernel(const fgnn_mlp_bwd_
         float dpre[16];
         {
             const float4 *kp = reinterpret_cast<const float4 *>(recK) + 4 * h;
-            const float vf = c_valid ? 1.f : 0.f;      // mask multiply, see norm_from_lds
+            const float vf = c_valid ? 1.f : 0.f;      // mask multiply, see norm_slab
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float4 k = kp[(r & 3) + 8 * (r >> 2)];
@@ -539,7 +371,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_kernel(const fgnn_mlp_bwd_
             float *Dt = (DEPTH == 2 && CB == 0) ? S1 : S2;
             if constexpr (VW0) {
                 float ya[1];
-                norm_from_lds<SA>(ya, xa, recA, normA, c_valid, h);      // channel h of this lane's pixel
+                norm_slab<SA>(ya, xa, recA, normA, c_valid, h);      // channel h of this lane's pixel
                 const float other = __shfl_xor(ya[0], 32);
                 const float x0 = h ? other : ya[0], x1 = h ? ya[0] : other;
 #pragma unroll
@@ -554,7 +386,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_kernel(const fgnn_mlp_bwd_
             }
             if constexpr (!VW0) {
                 float ya[SA > 0 ? SA : 1];
-                norm_from_lds<SA>(ya, xa, recA, normA, c_valid, h);
+                norm_slab<SA>(ya, xa, recA, normA, c_valid, h);
                 if constexpr (CA < 32) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) XA[ch_of(r, h) * TLD + j] = 0.f;
@@ -564,7 +396,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_kernel(const fgnn_mlp_bwd_
             }
             if constexpr (CB > 0) {
                 float yb[SB > 0 ? SB : 1];
-                norm_from_lds<SB>(yb, xb, recB, normB, c_valid, h);
+                norm_slab<SB>(yb, xb, recB, normB, c_valid, h);
                 if constexpr (CB < 32) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) XB[ch_of(r, h) * TLD + j] = 0.f;
@@ -742,21 +574,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_kernel(const fgnn_mlp_bwd_
     PH(10)              // waiting for the slowest wave of the workgroup
     put_partials(smem + wv * PCOUNT);      // the whole LDS allocation is free now
     __syncthreads();
-    static_assert(PCOUNT % 4 == 0, "partials are summed four at a time");
-    float4 *out = reinterpret_cast<float4 *>(A.wpart + (long long)blockIdx.x * PCOUNT);
-    const float4 *part4 = reinterpret_cast<const float4 *>(smem);
-    for (int e = threadIdx.x; e < PCOUNT / 4; e += 64 * NW) {
-        float4 a = part4[e];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) {                                  // fixed order
-            const float4 b = part4[w * (PCOUNT / 4) + e];
-            a.x += b.x;
-            a.y += b.y;
-            a.z += b.z;
-            a.w += b.w;
-        }
-        out[e] = a;
-    }
+    sum_wave_partials<PCOUNT, NW>(smem, A.wpart);
     PH(11)              // workgroup reduction + partial store
     PH_FLUSH
 }
@@ -775,7 +593,6 @@ int launch_bwd_impl(const fgnn_mlp_bwd_args *a, int tpg, int total, hipStream_t 
 }
 template <int CA, int CB, int DEPTH, bool PK = false>
 int launch_bwd(const fgnn_mlp_bwd_args *a, int tpg, int total, hipStream_t st) {
-    static_assert(BWD_WG == FGNN_RANGE_WG, "fgnn_ragged_tile_ranges splits for the backward grid");
     if (a->ranges) return launch_bwd_impl<CA, CB, DEPTH, PK, true>(a, tpg, total, st);
     return launch_bwd_impl<CA, CB, DEPTH, PK, false>(a, tpg, total, st);
 }
@@ -834,18 +651,10 @@ extern "C" int fgnn_mlp_bwd(const fgnn_mlp_bwd_args *a, void *stream) {
     FGNN_CHECK(a->b.C == 0 || a->b.ptr || pk_b, "fgnn_mlp_bwd: slab b has channels but no pointer");
     FGNN_CHECK(!a->xbits || a->xdeg, "fgnn_mlp_bwd: xbits without xdeg (fgnn_adjacency_degree)");
     FGNN_CHECK(!(pk_a && a->dxa) && !(pk_b && a->dxb), "fgnn_mlp_bwd: no gradient with respect to the packed adjacency");
-    FGNN_CHECK(a->dy && a->z && a->wpart, "fgnn_mlp_bwd: missing dy/z/wpart");
-    FGNN_CHECK(a->coef || (a->s12 && a->znrm) || (a->s12tiles && a->znrm), "fgnn_mlp_bwd: need coef, or s12 + znrm, or s12tiles + znrm");
-    {
-        const long long lim = 0x7fffffffll / 4, G = a->G;
-        FGNN_CHECK(G * a->a.gstride < lim && G * a->b.gstride < lim && G * a->dgstride < lim && G * a->zgstride < lim &&
-                   G * a->dxa_gstride < lim && G * a->dxb_gstride < lim,
-                   "fgnn_mlp_bwd: a tensor exceeds 2 GiB (32-bit buffer addressing); split the batch");
-    }
+    if (check_mlp_bwd_common(a, "fgnn_mlp_bwd", 30)) return 1;
     for (int l = 0; l < a->depth; ++l) FGNN_CHECK(a->W[l] && a->bias[l], "fgnn_mlp_bwd: missing weights layer %d", l);
     const int tpg = fgnn_tiles_per_graph(a->N);
     const long long total = (long long)a->G * tpg;
-    FGNN_CHECK(total < (1ll << 30), "fgnn_mlp_bwd: too many tiles");
     FGNN_CHECK(!a->ranges || (a->nvalid && !a->s12tiles), "fgnn_mlp_bwd: ranges need nvalid and exclude s12tiles");
     FGNN_CHECK(!a->s12tiles || a->b.C > 0, "fgnn_mlp_bwd: s12tiles is built into the two-slab kernels only; use fgnn_gn_bwd_coef_tiles");
     FGNN_CHECK(!a->s12tiles || fgnn_mlp_bwd_coef_tiles_supported(a->G, a->N),

@@ -19,77 +19,9 @@
 // fgnn_ragged_tile_ranges).
 #include "fgnn_tile.h"
 #include "fgnn_pack.h"
+#include "fgnn_bwd32.h"
 
 namespace {
-
-constexpr int BWD_WG = 256;          // persistent workgroups (one per CU) = rows of each wpart
-constexpr int NW = 8;                // waves per workgroup: 4 pairs
-constexpr int NP = 4;
-
-DEVI float4 coef_from_sums(const float4 n, const float2 sv, float nv) {
-    const float m = nv * nv;
-    float4 k;
-    k.x = n.x;
-    k.y = n.y;
-    k.z = m > 0.f ? -n.y * sv.y * n.w / m : 0.f;
-    k.w = m > 0.f ? -n.y * sv.x / m : 0.f;
-    return k;
-}
-DEVI float4 coef_record(const fgnn_mlp_bwd_args &A, int g, int ch) {
-    if (A.coef) return reinterpret_cast<const float4 *>(A.coef)[(long long)g * FGNN_H + ch];
-    const float4 n = reinterpret_cast<const float4 *>(A.znrm)[(long long)g * FGNN_H + ch];
-    const float2 sv = reinterpret_cast<const float2 *>(A.s12)[(long long)g * FGNN_H + ch];
-    return coef_from_sums(n, sv, (float)nvalid_of(A.nvalid, g, A.N));
-}
-
-// dW += Dt (rows = out channel) x In (rows = in channel), contraction over the 32 pixels; db from the same LDS reads
-template <bool WITH_DB>
-DEVI f32x16 wgrad_tile(const float *Dt, const float *In, f32x16 acc, float &db, int lane) {
-    const int i = lane & 31, h = lane >> 5;
-    const float4 *dp = reinterpret_cast<const float4 *>(Dt + i * TLD + 4 * h);
-    const float4 *ip = reinterpret_cast<const float4 *>(In + i * TLD + 4 * h);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 a = dp[2 * q];
-        const float4 b = ip[2 * q];
-        if (WITH_DB) db += (a.x + a.y) + (a.z + a.w);
-        acc = mfma32(a.x, b.x, acc);
-        acc = mfma32(a.y, b.y, acc);
-        acc = mfma32(a.z, b.z, acc);
-        acc = mfma32(a.w, b.w, acc);
-    }
-    return acc;
-}
-
-DEVI void zero16(f32x16 &a) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = 0.f;
-}
-
-template <int OFF, int CNT>
-DEVI void load_ops(float (&dst)[CNT > 0 ? CNT : 1], const float *wl, int lane) {
-    static_assert(OFF % 4 == 0, "operand sets are float4 aligned");
-    const float4 *p = reinterpret_cast<const float4 *>(wl) + (OFF / 4) * 64 + lane;
-#pragma unroll
-    for (int q = 0; q < (CNT + 3) / 4; ++q) {
-        const float4 v = p[q * 64];
-        if (4 * q + 0 < CNT) dst[4 * q + 0] = v.x;
-        if (4 * q + 1 < CNT) dst[4 * q + 1] = v.y;
-        if (4 * q + 2 < CNT) dst[4 * q + 2] = v.z;
-        if (4 * q + 3 < CNT) dst[4 * q + 3] = v.w;
-    }
-}
-DEVI void load_bias(float (&dst)[16], const float *tail, int layer, int h) {
-    const float4 *p = reinterpret_cast<const float4 *>(tail + layer * 32 + h * 16);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 v = p[q];
-        dst[4 * q + 0] = v.x;
-        dst[4 * q + 1] = v.y;
-        dst[4 * q + 2] = v.z;
-        dst[4 * q + 3] = v.w;
-    }
-}
 
 template <int CA>
 struct PairLayout {
@@ -106,10 +38,6 @@ struct PairLayout {
     static constexpr int MAIN_F = FLAG_OFF + FLAG_F;
     static constexpr int RED_F = NW * PCOUNT;
     static constexpr int LDS_F = MAIN_F > RED_F ? MAIN_F : RED_F;
-};
-
-struct PairArgs {
-    fgnn_mlp_bwd_args m[2];
 };
 
 // SKIP (ragged batches with ranges): work-balanced tile range from fgnn_ragged_tile_ranges, padding-only tiles are stepped over
@@ -156,14 +84,8 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_pair_kernel(const PairArgs
 #pragma unroll
     for (int l = 0; l < DEPTH; ++l) db[l] = 0.f;
 
-    const int nwg = gridDim.x;
-    const int q = total_tiles / nwg, rem = total_tiles % nwg;
-    int T0 = blockIdx.x * q + ((int)blockIdx.x < rem ? (int)blockIdx.x : rem);
-    int T1 = T0 + q + ((int)blockIdx.x < rem ? 1 : 0);
-    if constexpr (SKIP) {
-        T0 = A.ranges[blockIdx.x];
-        T1 = A.ranges[blockIdx.x + 1];
-    }
+    int T0, T1;
+    wg_tile_range<SKIP>(A.ranges, total_tiles, T0, T1);
     const bool normA = A.a.nrm != nullptr;
     const bool has_dx = (CA == 32) && P.m[1].dxa != nullptr;
     const bool emit = (CA == 32) && role == 1 && normA && has_dx && P.m[1].s12part != nullptr;
@@ -496,7 +418,6 @@ int launch_pair_impl(const fgnn_mlp_bwd_args *a1, const fgnn_mlp_bwd_args *a2, i
 }
 template <int CA, bool PK>
 int launch_pair(const fgnn_mlp_bwd_args *a1, const fgnn_mlp_bwd_args *a2, int tpg, int total, hipStream_t st) {
-    static_assert(BWD_WG == FGNN_RANGE_WG, "fgnn_ragged_tile_ranges splits for the backward grid");
     if (a1->ranges) return launch_pair_impl<CA, PK, true>(a1, a2, tpg, total, st);
     return launch_pair_impl<CA, PK, false>(a1, a2, tpg, total, st);
 }
@@ -504,34 +425,18 @@ int launch_pair(const fgnn_mlp_bwd_args *a1, const fgnn_mlp_bwd_args *a2, int tp
 }  // namespace
 
 extern "C" int fgnn_mlp_bwd_pair(const fgnn_mlp_bwd_args *a1, const fgnn_mlp_bwd_args *a2, void *stream) {
-    FGNN_CHECK(a1 && a2, "fgnn_mlp_bwd_pair: null args");
-    FGNN_CHECK(BWD_WG == fgnn_mlp_bwd_num_workgroups(), "fgnn_mlp_bwd_pair: workgroup count differs from fgnn_mlp_bwd");
-    FGNN_CHECK(a1->G > 0 && a1->N > 0 && a1->G == a2->G && a1->N == a2->N && a1->depth == a2->depth,
-               "fgnn_mlp_bwd_pair: the two MLPs must share G, N and depth");
+    if (check_pair_common(a1, a2, "fgnn_mlp_bwd_pair", 30, false)) return 1;
     FGNN_CHECK(mlp_bwd_pair_supported(a1->a.C, a1->depth) && a1->b.C == 0 && a2->b.C == 0,
                "fgnn_mlp_bwd_pair: built for depth 3 and ONE input slab of 2 or 32 channels (got depth %d, %d + %d); use fgnn_mlp_bwd",
                a1->depth, a1->a.C, a1->b.C);
-    FGNN_CHECK(a1->a.ptr == a2->a.ptr && a1->a.C == a2->a.C && a1->a.gstride == a2->a.gstride && a1->a.ldp == a2->a.ldp &&
-               a1->a.nrm == a2->a.nrm && a1->a.beta == a2->a.beta && a1->xbits == a2->xbits && a1->xdeg == a2->xdeg &&
-               a1->nvalid == a2->nvalid, "fgnn_mlp_bwd_pair: the two MLPs must read the same input slab");
     FGNN_CHECK(a1->ranges == a2->ranges && (!a1->ranges || a1->nvalid), "fgnn_mlp_bwd_pair: both MLPs take the same ranges (with nvalid)");
     FGNN_CHECK(a1->packed && a2->packed, "fgnn_mlp_bwd_pair: needs both operand images (fgnn_pack_operands, kind 1)");
-    FGNN_CHECK(!a1->dxa && !a1->s12part, "fgnn_mlp_bwd_pair: the input gradient and its tile sums belong to the SECOND argument block");
-    FGNN_CHECK(!a1->s12tiles && !a2->s12tiles, "fgnn_mlp_bwd_pair: s12tiles is an mlp3 feature");
     const bool pk_a = a1->xbits && a1->a.C == 2;
     FGNN_CHECK((a1->a.ptr || pk_a), "fgnn_mlp_bwd_pair: slab a missing");
     FGNN_CHECK(!a1->xbits || a1->xdeg, "fgnn_mlp_bwd_pair: xbits without xdeg (fgnn_adjacency_degree)");
     FGNN_CHECK(!(a2->dxa && a2->a.C != 32), "fgnn_mlp_bwd_pair: the input gradient exists for the 32-channel slab only; use fgnn_mlp_bwd");
-    for (const fgnn_mlp_bwd_args *a : {a1, a2}) {
-        FGNN_CHECK(a->dy && a->z && a->wpart, "fgnn_mlp_bwd_pair: missing dy/z/wpart");
-        FGNN_CHECK(a->coef || (a->s12 && a->znrm), "fgnn_mlp_bwd_pair: need coef, or s12 + znrm");
-        const long long lim = 0x7fffffffll / 4, G = a->G;
-        FGNN_CHECK(G * a->a.gstride < lim && G * a->dgstride < lim && G * a->zgstride < lim && G * a->dxa_gstride < lim,
-                   "fgnn_mlp_bwd_pair: a tensor exceeds 2 GiB (32-bit buffer addressing); split the batch");
-    }
     const int tpg = fgnn_tiles_per_graph(a1->N);
     const long long total = (long long)a1->G * tpg;
-    FGNN_CHECK(total < (1ll << 30), "fgnn_mlp_bwd_pair: too many tiles");
     hipStream_t st = (hipStream_t)stream;
     if (a1->xbits) return launch_pair<2, true>(a1, a2, tpg, (int)total, st);
     if (a1->a.C == 2) return launch_pair<2, false>(a1, a2, tpg, (int)total, st);

@@ -17,8 +17,7 @@
 //     every dx of a padding pixel is then 0 whatever its column of the recomputed chain holds.
 // The recomputed hidden activations are bit-identical to the forward's (fgnn_t16.h), so the ReLU masks are the forward's.
 // Constant-size and ragged batches (nvalid, optionally with fgnn_ragged_tile_ranges); depth 3, 32-channel input slab.
-#include "fgnn_t16.h"
-#include "fgnn_pack.h"
+#include "fgnn_bwd_t16.h"
 
 #ifdef FGNN_PHASES
 // Debug build only (-DFGNN_PHASES): per-wave cycle stamps of the half-tile phases, summed over the wave's halves (tools/gpu_phases_t16.py)
@@ -34,55 +33,14 @@ __device__ unsigned long long *g_phase16_buf = nullptr;
 
 namespace {
 
-using namespace t16;
-
-constexpr int BWD_WG = 256;          // persistent workgroups (one per CU) = rows of each wpart
-constexpr int NW = 8;                // waves per workgroup: 4 pairs
-constexpr int NP = 4;
-
-DEVI float4 coef_from_sums(const float4 n, const float2 sv, float nv) {
-    const float m = nv * nv;
-    float4 k;
-    k.x = n.x;
-    k.y = n.y;
-    k.z = m > 0.f ? -n.y * sv.y * n.w / m : 0.f;
-    k.w = m > 0.f ? -n.y * sv.x / m : 0.f;
-    return k;
-}
-DEVI float4 coef_record(const fgnn_mlp_bwd_args &A, int g, int ch, int nv) {
-    if (A.coef) return reinterpret_cast<const float4 *>(A.coef)[(long long)g * FGNN_H + ch];
-    const float4 n = reinterpret_cast<const float4 *>(A.znrm)[(long long)g * FGNN_H + ch];
-    const float2 sv = reinterpret_cast<const float2 *>(A.s12)[(long long)g * FGNN_H + ch];
-    return coef_from_sums(n, sv, (float)nv);
-}
-// vertex count of graph g through a buffer descriptor (an empty one without nvalid: returns 0, no access).  `nvalid ? nvalid[g] : N`
-// compiles to ONE load through a select of the two addresses -- a FLAT load, which makes every later s_waitcnt of the tile loop
-// a full drain (flat operations complete out of order with respect to buffer loads)
-DEVI int graph_nv(const rsrc_t &rnv, bool ragged, int g, int N) {
-    const int v = __builtin_amdgcn_raw_buffer_load_b32(rnv, g * 4, 0, 0);
-    return __builtin_amdgcn_readfirstlane(ragged ? v : N);
-}
-
-struct PairLayout16 {
-    static constexpr int DEPTH = 3;
-    static constexpr PkBwd PK = pk_bwd(32, 0, DEPTH);                      // one image per MLP: fgnn_pack.h (kind 5)
-    static constexpr int OFF_W0 = PK.off_w1a, OFF_W1 = PK.off_wh, OFF_WT1 = PK.off_wt, OFF_WT2 = PK.off_wt + 16, OFF_WT0 = PK.off_wt0a;
-    static constexpr int BIAS_F = PK.bias_f;
-    static constexpr int WEIGHT_F = pk_pad_floats(PK.floats);             // floats per image (whole KiB: global_load_lds)
-    static constexpr int NSLOT = 4;                                       // per wave: x_a, h1, h2 / dpre_1, dz / dpre_0
-    static constexpr int PCOUNT = 32 * 32 + 32 + (DEPTH - 1) * (32 * 32 + 32);
-    static constexpr int TILE_OFF = 2 * WEIGHT_F;
-    static constexpr int XCH_OFF = TILE_OFF + NW * NSLOT * TILE_F;        // per pair: the handed-over dx fragment [s][lane]
+struct PairLayout16 : BwdT16Layout<0, 2, 4> {                             // one image per MLP; per wave: x_a, h1, h2 / dpre_1, dz / dpre_0
+    static constexpr int OFF_W0 = PK.off_w1a, OFF_WT0 = PK.off_wt0a;
+    static constexpr int XCH_OFF = TILE_END;                              // per pair: the handed-over dx fragment [s][lane]
     static constexpr int FLAG_OFF = XCH_OFF + NP * 1024;                  // (two slots per pair); per pair: ready, consumed counters (+ padding)
     static constexpr int REC_OFF = FLAG_OFF + 4 * NP;                     // per wave: {coef[32], nrm[32]} float4 (graph changes only)
     static constexpr int LIVE_OFF = REC_OFF + NW * 256;                   // SKIP: the range's live tiles (build_live_list) + NW counters
     static constexpr int MAIN_F = LIVE_OFF + LIVE_LIST_CAP + NW;
-    static constexpr int RED_F = NW * PCOUNT;
     static constexpr int LDS_F = MAIN_F > RED_F ? MAIN_F : RED_F;
-};
-
-struct PairArgs {
-    fgnn_mlp_bwd_args m[2];
 };
 
 // SKIP (ragged batches with ranges): work-balanced tile range from fgnn_ragged_tile_ranges, padding-only tiles are stepped over
@@ -116,14 +74,8 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_pair_t16_kernel(const Pair
 #pragma unroll
     for (int k = 0; k < 4; ++k) dW0[k] = dW1[k] = dW2[k] = zero4();
 
-    const int nwg = gridDim.x;
-    const int qq = total_tiles / nwg, rem = total_tiles % nwg;
-    int T0 = blockIdx.x * qq + ((int)blockIdx.x < rem ? (int)blockIdx.x : rem);
-    int T1 = T0 + qq + ((int)blockIdx.x < rem ? 1 : 0);
-    if constexpr (SKIP) {
-        T0 = A.ranges[blockIdx.x];
-        T1 = A.ranges[blockIdx.x + 1];
-    }
+    int T0, T1;
+    wg_tile_range<SKIP>(A.ranges, total_tiles, T0, T1);
     const bool normA = A.a.nrm != nullptr;
     constexpr bool has_dx = HAS_DX;
     const bool emit = role == 1 && normA && has_dx && P.m[1].s12part != nullptr;
@@ -156,21 +108,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_pair_t16_kernel(const Pair
             if (normA) rec[32 + lane] = reinterpret_cast<const float4 *>(A.a.nrm)[(long long)g * A.a.C + lane];
         }
     };
-    auto read_records = [&]() {
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const float4 k4 = rec[chan_s(s) + chan_q(q)];
-            kx[s] = k4.x;
-            ky[s] = k4.y;
-            kz[s] = k4.z;
-            kw[s] = k4.w;
-            if (normA) {
-                const float4 n = rec[32 + chan_s(s) + chan_q(q)];
-                mean[s] = n.x;
-                av[s] = n.y;
-            }
-        }
-    };
+    auto read_records = [&]() { FGNN_T16_READ_RECORDS(normA) };
 
     // loop-carried loads: every slab of a half is requested while the PREVIOUS half computes (x after its layer-1 stage, dy / z as
     // soon as dz has consumed their registers, the old d_in after the hand-over), so no wave waits for HBM inside a half
@@ -286,50 +224,24 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_pair_t16_kernel(const Pair
                 f32x4 acc[2];
                 load_bias(acc, wl + L::BIAS_F, 0, q);
                 gemm32<L::OFF_W0>(acc, wl, ya, lane);
-#pragma unroll
-                for (int s = 0; s < 8; ++s) h1[s] = relu1(acc[s >> 2][s & 3]);
-                stage8(S0, lane_base, h1);
-                load_bias(acc, wl + L::BIAS_F, 1, q);
-                gemm32<L::OFF_W1>(acc, wl, h1, lane);
-#pragma unroll
-                for (int s = 0; s < 8; ++s) h2[s] = relu1(acc[s >> 2][s & 3]);
-                stage8(S1, lane_base, h2);
+                FGNN_T16_RECOMPUTE_HIDDEN(acc, h1, h2)
             }
             PH(1)       // x arrived, normalised, two layers recomputed and staged
             // ---- dz from (dy, z, coef); the ONLY place the padding mask is applied ----
             float dpre[8];
-#pragma unroll
-            for (int s = 0; s < 8; ++s) dpre[s] = fmaf(kz[s], zr[s] - kx[s], fmaf(ky[s], dyr[s], kw[s]));
-            if (!full) {
-#pragma unroll
-                for (int s = 0; s < 8; ++s) dpre[s] = valid ? dpre[s] : 0.f;
-            }
+            FGNN_T16_DZ(dpre)
             stage8(S2, lane_base, dpre);
             load8(dyr, vdy, lane_voff(vdy, q, np, ninb), ng * vdy.gs4);      // the next half's dy / z into the registers just consumed
             load8(zr, vz, lane_voff(vz, q, np, ninb), ng * vz.gs4);
             PH(2)       // dz (waits for dy, z)
             __builtin_amdgcn_sched_barrier(0);
             // ---- layer 2: dgrad, weight gradient (dz x h2), ReLU mask of h2 ----
-            {
-                f32x4 a2[2];
-                a2[0] = a2[1] = zero4();
-                gemm32<L::OFF_WT2>(a2, wl, dpre, lane);
-                wgrad16(dW2, db2, S2, S1, lane);
-#pragma unroll
-                for (int s = 0; s < 8; ++s) dpre[s] = h2[s] > 0.f ? a2[s >> 2][s & 3] : 0.f;
-            }
+            FGNN_T16_HIDDEN_BWD(L::OFF_WT2, dpre, dW2, db2, S2, S1, h2)
             PH(3)       // layer 2 dgrad + wgrad + mask
             __builtin_amdgcn_sched_barrier(0);
             stage8(S1, lane_base, dpre);         // h2's tile is dead: its reads were issued above (LDS is in order within a wave)
             // ---- layer 1 ----
-            {
-                f32x4 a2[2];
-                a2[0] = a2[1] = zero4();
-                gemm32<L::OFF_WT1>(a2, wl, dpre, lane);
-                wgrad16(dW1, db1, S1, S0, lane);
-#pragma unroll
-                for (int s = 0; s < 8; ++s) dpre[s] = h1[s] > 0.f ? a2[s >> 2][s & 3] : 0.f;
-            }
+            FGNN_T16_HIDDEN_BWD(L::OFF_WT1, dpre, dW1, db1, S1, S0, h1)
             PH(4)       // layer 1
             __builtin_amdgcn_sched_barrier(0);
             stage8(S2, lane_base, dpre);         // dz's tile is dead
@@ -430,15 +342,8 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_pair_t16_kernel(const Pair
     // ---- workgroup reduction: each MLP's partial = fixed-order sum of its four waves ----
     // layout per MLP: [W0 (32*32) | b0 (32) | W1 (1024) | b1 (32) | W2 (1024) | b2 (32)]
     constexpr int PCOUNT = L::PCOUNT;
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        db0[b] += __shfl_xor(db0[b], 16);
-        db0[b] += __shfl_xor(db0[b], 32);
-        db1[b] += __shfl_xor(db1[b], 16);
-        db1[b] += __shfl_xor(db1[b], 32);
-        db2[b] += __shfl_xor(db2[b], 16);
-        db2[b] += __shfl_xor(db2[b], 32);
-    }
+    static_assert(PCOUNT == 3 * 1056, "put() below: three layers of 32 x 32 + 32");
+    FGNN_T16_DB_BUTTERFLY(db0, db1, db2)
     __syncthreads();                       // everyone done with the operand images and the tile buffers
     PH(10)              // waiting for the slowest wave of the workgroup
     {
@@ -460,21 +365,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_pair_t16_kernel(const Pair
         put(2112, dW2, db2);
     }
     __syncthreads();
-    static_assert(PCOUNT % 4 == 0 && PCOUNT == 3 * 1056, "partials are summed four at a time");
-    const float4 *part4 = reinterpret_cast<const float4 *>(smem);
-    for (int e = threadIdx.x; e < 2 * (PCOUNT / 4); e += 64 * NW) {
-        const int m = e >= PCOUNT / 4 ? 1 : 0, ee = e - m * (PCOUNT / 4);
-        float4 a = part4[(4 * m) * (PCOUNT / 4) + ee];
-#pragma unroll
-        for (int w = 1; w < NP; ++w) {                                  // fixed order over the MLP's four waves
-            const float4 b = part4[(4 * m + w) * (PCOUNT / 4) + ee];
-            a.x += b.x;
-            a.y += b.y;
-            a.z += b.z;
-            a.w += b.w;
-        }
-        reinterpret_cast<float4 *>(P.m[m].wpart + (long long)blockIdx.x * PCOUNT)[ee] = a;
-    }
+    sum_pair_partials<PCOUNT>(smem, P);
     PH(11)              // workgroup reduction + partial store
     PH_FLUSH
 }
@@ -502,31 +393,15 @@ extern "C" int fgnn_debug_phase_buffer_t16(void *p) { return hipMemcpyToSymbol(H
 
 // Same contract as fgnn_mlp_bwd_pair (see there); `packed` of both argument blocks must be images of kind 5 (fgnn_pack_operands).
 extern "C" int fgnn_mlp_bwd_pair_t16(const fgnn_mlp_bwd_args *a1, const fgnn_mlp_bwd_args *a2, void *stream) {
-    FGNN_CHECK(a1 && a2, "fgnn_mlp_bwd_pair_t16: null args");
-    FGNN_CHECK(BWD_WG == fgnn_mlp_bwd_num_workgroups() && BWD_WG == FGNN_RANGE_WG, "fgnn_mlp_bwd_pair_t16: workgroup count differs from fgnn_mlp_bwd");
-    FGNN_CHECK(a1->G > 0 && a1->N > 0 && a1->G == a2->G && a1->N == a2->N && a1->depth == a2->depth,
-               "fgnn_mlp_bwd_pair_t16: the two MLPs must share G, N and depth");
+    if (check_pair_common(a1, a2, "fgnn_mlp_bwd_pair_t16", 29, true)) return 1;
     FGNN_CHECK(a1->depth == 3 && a1->a.C == 32 && a1->b.C == 0 && a2->b.C == 0 && !a1->xbits && !a2->xbits,
                "fgnn_mlp_bwd_pair_t16: built for depth 3 and ONE dense input slab of 32 channels (got depth %d, %d + %d); use fgnn_mlp_bwd_pair",
                a1->depth, a1->a.C, a1->b.C);
-    FGNN_CHECK(a1->a.ptr && a1->a.ptr == a2->a.ptr && a1->a.C == a2->a.C && a1->a.gstride == a2->a.gstride && a1->a.ldp == a2->a.ldp &&
-               a1->a.nrm == a2->a.nrm && a1->a.beta == a2->a.beta && a1->nvalid == a2->nvalid,
-               "fgnn_mlp_bwd_pair_t16: the two MLPs must read the same input slab");
     FGNN_CHECK(a1->ranges == a2->ranges && (!a1->ranges || a1->nvalid), "fgnn_mlp_bwd_pair_t16: both MLPs take the same ranges (with nvalid)");
     FGNN_CHECK(a1->packed && a2->packed, "fgnn_mlp_bwd_pair_t16: needs both operand images (fgnn_pack_operands, kind 5)");
-    FGNN_CHECK(!a1->dxa && !a1->s12part, "fgnn_mlp_bwd_pair_t16: the input gradient and its tile sums belong to the SECOND argument block");
-    FGNN_CHECK(!a1->s12tiles && !a2->s12tiles, "fgnn_mlp_bwd_pair_t16: s12tiles is an mlp3 feature");
     FGNN_CHECK(a1->N <= 256, "fgnn_mlp_bwd_pair_t16: N <= 256 (division-free pixel decode)");
-    for (const fgnn_mlp_bwd_args *a : {a1, a2}) {
-        FGNN_CHECK(a->dy && a->z && a->wpart, "fgnn_mlp_bwd_pair_t16: missing dy/z/wpart");
-        FGNN_CHECK(a->coef || (a->s12 && a->znrm), "fgnn_mlp_bwd_pair_t16: need coef, or s12 + znrm");
-        const long long lim = 0x7fffffffll / 4, G = a->G;
-        FGNN_CHECK(G * a->a.gstride < lim && G * a->dgstride < lim && G * a->zgstride < lim && G * a->dxa_gstride < lim,
-                   "fgnn_mlp_bwd_pair_t16: a tensor exceeds 2 GiB (32-bit buffer addressing); split the batch");
-    }
     const int tpg = fgnn_tiles_per_graph(a1->N);
     const long long total = (long long)a1->G * tpg;
-    FGNN_CHECK(total < (1ll << 29), "fgnn_mlp_bwd_pair_t16: too many tiles");
     hipStream_t st = (hipStream_t)stream;
     if (a2->dxa) return a1->ranges ? launch_pair16<true, true>(a1, a2, tpg, (int)total, st) : launch_pair16<false, true>(a1, a2, tpg, (int)total, st);
     return a1->ranges ? launch_pair16<true, false>(a1, a2, tpg, (int)total, st) : launch_pair16<false, false>(a1, a2, tpg, (int)total, st);

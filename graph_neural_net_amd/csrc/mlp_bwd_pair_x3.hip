@@ -19,6 +19,7 @@
 #include "fgnn_tile.h"
 #include "fgnn_pack.h"
 #include "fgnn_x3.h"
+#include "fgnn_bwd32.h"
 
 namespace {
 
@@ -33,26 +34,6 @@ __device__ unsigned long long *g_px3_phase_buf = nullptr;
 #define PH(k)
 #define PH_FLUSH
 #endif
-
-constexpr int BWD_WG = 256;          // persistent workgroups (one per CU) = rows of each wpart
-constexpr int NW = 8;                // waves per workgroup: 4 pairs
-constexpr int NP = 4;
-
-DEVI float4 coef_from_sums(const float4 n, const float2 sv, float nv) {
-    const float m = nv * nv;
-    float4 k;
-    k.x = n.x;
-    k.y = n.y;
-    k.z = m > 0.f ? -n.y * sv.y * n.w / m : 0.f;
-    k.w = m > 0.f ? -n.y * sv.x / m : 0.f;
-    return k;
-}
-DEVI float4 coef_record(const fgnn_mlp_bwd_args &A, int g, int ch) {
-    if (A.coef) return reinterpret_cast<const float4 *>(A.coef)[(long long)g * FGNN_H + ch];
-    const float4 n = reinterpret_cast<const float4 *>(A.znrm)[(long long)g * FGNN_H + ch];
-    const float2 sv = reinterpret_cast<const float2 *>(A.s12)[(long long)g * FGNN_H + ch];
-    return coef_from_sums(n, sv, (float)nvalid_of(A.nvalid, g, A.N));
-}
 
 template <int CA>
 struct PairX3Layout {
@@ -75,10 +56,6 @@ struct PairX3Layout {
     static constexpr int MAIN_F = FLAG_OFF + 4 * NP;
     static constexpr int RED_F = NW * PCOUNT;
     static constexpr int LDS_F = MAIN_F > RED_F ? MAIN_F : RED_F;
-};
-
-struct PairArgs {
-    fgnn_mlp_bwd_args m[2];
 };
 
 // the three bf16 parts of an input slab as B operand (mlp_fwd_x3.hip)
@@ -156,10 +133,8 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_pair_x3_kernel(const PairA
 #pragma unroll
     for (int l = 0; l < DEPTH; ++l) ndb[l] = 0.f;
 
-    const int nwg = gridDim.x;
-    const int q = total_tiles / nwg, rem = total_tiles % nwg;
-    const int T0 = blockIdx.x * q + ((int)blockIdx.x < rem ? (int)blockIdx.x : rem);
-    const int T1 = T0 + q + ((int)blockIdx.x < rem ? 1 : 0);
+    int T0, T1;
+    wg_tile_range<false>(nullptr, total_tiles, T0, T1);
     const bool normA = A.a.nrm != nullptr;
     const bool has_dx = (CA == 32) && P.m[1].dxa != nullptr;
     const bool emit = (CA == 32) && role == 1 && normA && has_dx && P.m[1].s12part != nullptr;
@@ -513,20 +488,12 @@ extern "C" int fgnn_debug_phase_buffer_px3(void *p) {
 #endif
 
 extern "C" int fgnn_mlp_bwd_pair_x3(const fgnn_mlp_bwd_args *a1, const fgnn_mlp_bwd_args *a2, void *stream) {
-    FGNN_CHECK(a1 && a2, "fgnn_mlp_bwd_pair_x3: null args");
-    FGNN_CHECK(BWD_WG == fgnn_mlp_bwd_num_workgroups(), "fgnn_mlp_bwd_pair_x3: workgroup count differs from fgnn_mlp_bwd");
-    FGNN_CHECK(a1->G > 0 && a1->N > 0 && a1->G == a2->G && a1->N == a2->N && a1->depth == a2->depth,
-               "fgnn_mlp_bwd_pair_x3: the two MLPs must share G, N and depth");
+    if (check_pair_common(a1, a2, "fgnn_mlp_bwd_pair_x3", 30, false)) return 1;
     FGNN_CHECK(mlp_bwd_pair_supported(a1->a.C, a1->depth) && a1->b.C == 0 && a2->b.C == 0,
                "fgnn_mlp_bwd_pair_x3: built for depth 3 and ONE input slab of 2 or 32 channels (got depth %d, %d + %d); use fgnn_mlp_bwd",
                a1->depth, a1->a.C, a1->b.C);
-    FGNN_CHECK(a1->a.ptr == a2->a.ptr && a1->a.C == a2->a.C && a1->a.gstride == a2->a.gstride && a1->a.ldp == a2->a.ldp &&
-               a1->a.nrm == a2->a.nrm && a1->a.beta == a2->a.beta && a1->xbits == a2->xbits && a1->xdeg == a2->xdeg &&
-               a1->nvalid == a2->nvalid, "fgnn_mlp_bwd_pair_x3: the two MLPs must read the same input slab");
     FGNN_CHECK(!a1->ranges && !a2->ranges, "fgnn_mlp_bwd_pair_x3: no padding-tile skipping (ranges); use fgnn_mlp_bwd_pair for ragged batches");
     FGNN_CHECK(a1->packed && a2->packed, "fgnn_mlp_bwd_pair_x3: needs both operand images (fgnn_pack_x3_operands, kind 1)");
-    FGNN_CHECK(!a1->dxa && !a1->s12part, "fgnn_mlp_bwd_pair_x3: the input gradient and its tile sums belong to the SECOND argument block");
-    FGNN_CHECK(!a1->s12tiles && !a2->s12tiles, "fgnn_mlp_bwd_pair_x3: s12tiles is an mlp3 feature");
     const bool pk_a = a1->xbits && a1->a.C == 2;
     FGNN_CHECK((a1->a.ptr || pk_a), "fgnn_mlp_bwd_pair_x3: slab a missing");
     FGNN_CHECK(!a1->xbits || a1->xdeg, "fgnn_mlp_bwd_pair_x3: xbits without xdeg (fgnn_adjacency_degree)");
@@ -534,16 +501,8 @@ extern "C" int fgnn_mlp_bwd_pair_x3(const fgnn_mlp_bwd_args *a1, const fgnn_mlp_
     FGNN_CHECK(a1->ldd == a1->ldz && a2->ldd == a1->ldd && a2->ldz == a1->ldd && (!a2->dxa || a2->dxa_ld == a1->ldd) &&
                (a1->a.C != 32 || a1->a.ldp == a1->ldd),
                "fgnn_mlp_bwd_pair_x3: dy, z, d_in (and a 32-channel input slab) must share one channel stride");
-    for (const fgnn_mlp_bwd_args *a : {a1, a2}) {
-        FGNN_CHECK(a->dy && a->z && a->wpart, "fgnn_mlp_bwd_pair_x3: missing dy/z/wpart");
-        FGNN_CHECK(a->coef || (a->s12 && a->znrm), "fgnn_mlp_bwd_pair_x3: need coef, or s12 + znrm");
-        const long long lim = 0x7fffffffll / 4, G = a->G;
-        FGNN_CHECK(G * a->a.gstride < lim && G * a->dgstride < lim && G * a->zgstride < lim && G * a->dxa_gstride < lim,
-                   "fgnn_mlp_bwd_pair_x3: a tensor exceeds 2 GiB (32-bit buffer addressing); split the batch");
-    }
     const int tpg = fgnn_tiles_per_graph(a1->N);
     const long long total = (long long)a1->G * tpg;
-    FGNN_CHECK(total < (1ll << 30), "fgnn_mlp_bwd_pair_x3: too many tiles");
     hipStream_t st = (hipStream_t)stream;
     if (a1->xbits) return launch_pair_x3<2, true>(a1, a2, tpg, (int)total, st);
     if (a1->a.C == 2) return launch_pair_x3<2, false>(a1, a2, tpg, (int)total, st);

@@ -14,49 +14,19 @@
 // Built for depth 3, slab a = 32 raw channels (mult), slab b = 32 channels (a block's input, normalised on load) or 2 raw channels
 // (block 1: the model input, dense or bit-packed); dx for both slabs (stored, not accumulated) or for slab a only.  Anything else:
 // fgnn_mlp_bwd.
-#include "fgnn_t16.h"
-#include "fgnn_pack.h"
+#include "fgnn_bwd_t16.h"
 
 namespace {
 
-using namespace t16;
-
-constexpr int BWD_WG = 256;          // persistent workgroups (one per CU) = rows of wpart
-constexpr int NW = 8;                // waves per workgroup (2 per SIMD)
-
-DEVI float4 coef_from_sums(const float4 n, const float2 sv, float nv) {
-    const float m = nv * nv;
-    float4 k;
-    k.x = n.x;
-    k.y = n.y;
-    k.z = m > 0.f ? -n.y * sv.y * n.w / m : 0.f;
-    k.w = m > 0.f ? -n.y * sv.x / m : 0.f;
-    return k;
-}
-// vertex count of graph g through a buffer descriptor (see mlp_bwd_pair_t16.hip: a select of two addresses would be a FLAT load)
-DEVI int graph_nv(const rsrc_t &rnv, bool ragged, int g, int N) {
-    const int v = __builtin_amdgcn_raw_buffer_load_b32(rnv, g * 4, 0, 0);
-    return __builtin_amdgcn_readfirstlane(ragged ? v : N);
-}
-
 template <int CB>
-struct Layout16 {
-    static constexpr int DEPTH = 3;
-    static constexpr PkBwd PK = pk_bwd(32, CB, DEPTH);                    // fgnn_pack.h, image kind 5
-    static constexpr int OFF_W0A = PK.off_w1a, OFF_W0B = PK.off_w1b, OFF_W1 = PK.off_wh, OFF_WT1 = PK.off_wt, OFF_WT2 = PK.off_wt + 16;
-    static constexpr int OFF_WT0A = PK.off_wt0a, OFF_WT0B = PK.off_wt0b;
-    static constexpr int BIAS_F = PK.bias_f;
-    static constexpr int WEIGHT_F = pk_pad_floats(PK.floats);
-    static constexpr int NSLOT = 5;                                       // per wave: x_a, x_b, h1, h2 / dpre_1, dz / dpre_0
-    static constexpr int CIN = 32 + CB;
-    static constexpr int PCOUNT = 32 * CIN + 32 + (DEPTH - 1) * (32 * 32 + 32);
-    static constexpr int TILE_OFF = WEIGHT_F;
-    static constexpr int REC_OFF = TILE_OFF + NW * NSLOT * TILE_F;        // per wave: {coef[32], nrm_b[32]} float4 (graph changes only)
+struct Layout16 : BwdT16Layout<CB, 1, 5> {                                // per wave: x_a, x_b, h1, h2 / dpre_1, dz / dpre_0
+    using B = BwdT16Layout<CB, 1, 5>;
+    static constexpr int OFF_W0A = B::PK.off_w1a, OFF_W0B = B::PK.off_w1b, OFF_WT0A = B::PK.off_wt0a, OFF_WT0B = B::PK.off_wt0b;
+    static constexpr int REC_OFF = B::TILE_END;                           // per wave: {coef[32], nrm_b[32]} float4 (graph changes only)
     static constexpr int WGK_OFF = REC_OFF + NW * 256;                    // workgroup cache of dz coefficient records (s12tiles)
     static constexpr int LIVE_OFF = WGK_OFF + FGNN_BWD_COEF_GRAPHS * 128;  // SKIP: the range's live tiles (build_live_list) + NW counters
     static constexpr int MAIN_F = LIVE_OFF + LIVE_LIST_CAP + NW;
-    static constexpr int RED_F = NW * PCOUNT;
-    static constexpr int LDS_F = MAIN_F > RED_F ? MAIN_F : RED_F;
+    static constexpr int LDS_F = MAIN_F > B::RED_F ? MAIN_F : B::RED_F;
 };
 
 // SKIP (ragged batches with ranges): the workgroup's tile range comes from fgnn_ragged_tile_ranges, 32-pixel tiles without a valid
@@ -89,14 +59,8 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_t16_kernel(const fgnn_mlp_
 #pragma unroll
     for (int k = 0; k < 4; ++k) dW0a[k] = dW0b[k] = dW1[k] = dW2[k] = zero4();
 
-    const int nwg = gridDim.x;
-    const int qq = total_tiles / nwg, rem = total_tiles % nwg;
-    int T0 = blockIdx.x * qq + ((int)blockIdx.x < rem ? (int)blockIdx.x : rem);
-    int T1 = T0 + qq + ((int)blockIdx.x < rem ? 1 : 0);
-    if constexpr (SKIP) {
-        T0 = A.ranges[blockIdx.x];
-        T1 = A.ranges[blockIdx.x + 1];
-    }
+    int T0, T1;
+    wg_tile_range<SKIP>(A.ranges, total_tiles, T0, T1);
     const int H0 = 2 * T0, H1 = 2 * T1;                 // this workgroup's halves
     const bool ragged = A.nvalid != nullptr;
     const rsrc_t rnv = __builtin_amdgcn_make_buffer_rsrc(const_cast<int *>(A.nvalid), 0, ragged ? A.G * 4 : 0, 0x00020000);
@@ -182,21 +146,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_t16_kernel(const fgnn_mlp_
             if (NB && A.b.nrm) rec[32 + lane] = reinterpret_cast<const float4 *>(A.b.nrm)[(long long)g * A.b.C + lane];
         }
     };
-    auto read_records = [&]() {
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const float4 k4 = rec[chan_s(s) + chan_q(q)];
-            kx[s] = k4.x;
-            ky[s] = k4.y;
-            kz[s] = k4.z;
-            kw[s] = k4.w;
-            if (NB && A.b.nrm) {
-                const float4 n = rec[32 + chan_s(s) + chan_q(q)];
-                mean[s] = n.x;
-                av[s] = n.y;
-            }
-        }
-    };
+    auto read_records = [&]() { FGNN_T16_READ_RECORDS(NB && A.b.nrm) };
 
     // slab loads of half h: xa[8] (32 raw channels), xb (CB = 32: 8 registers; CB = 2: one -- channel q for q < 2)
     constexpr int NXB = CB == 32 ? 8 : 1;
@@ -329,46 +279,20 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_t16_kernel(const fgnn_mlp_
             if constexpr (CB == 32) gemm32<L::OFF_W0B>(acc, wl, yb, lane);
             else gemm2<L::OFF_W0B>(acc, wl, q < 2 ? yb[0] : 0.f, lane);
             load_x(hn);                               // the next half's input slabs into the registers just consumed
-#pragma unroll
-            for (int s = 0; s < 8; ++s) h1[s] = relu1(acc[s >> 2][s & 3]);
-            stage8(S0, lane_base, h1);
-            load_bias(acc, wl + L::BIAS_F, 1, q);
-            gemm32<L::OFF_W1>(acc, wl, h1, lane);
-#pragma unroll
-            for (int s = 0; s < 8; ++s) h2[s] = relu1(acc[s >> 2][s & 3]);
-            stage8(S1, lane_base, h2);
+            FGNN_T16_RECOMPUTE_HIDDEN(acc, h1, h2)
         }
         // ---- dz from (dy, z, coef); the ONLY place the padding mask is applied ----
         float dpre[8];
-#pragma unroll
-        for (int s = 0; s < 8; ++s) dpre[s] = fmaf(kz[s], zr[s] - kx[s], fmaf(ky[s], dyr[s], kw[s]));
-        if (!full) {
-#pragma unroll
-            for (int s = 0; s < 8; ++s) dpre[s] = valid ? dpre[s] : 0.f;
-        }
+        FGNN_T16_DZ(dpre)
         stage8(S2, lane_base, dpre);
         load_dyz(hn);                                 // the next half's dy / z into the registers just consumed
         __builtin_amdgcn_sched_barrier(0);
         // ---- layer 2 ----
-        {
-            f32x4 a2[2];
-            a2[0] = a2[1] = zero4();
-            gemm32<L::OFF_WT2>(a2, wl, dpre, lane);
-            wgrad16(dW2, db2, S2, S1, lane);
-#pragma unroll
-            for (int s = 0; s < 8; ++s) dpre[s] = h2[s] > 0.f ? a2[s >> 2][s & 3] : 0.f;
-        }
+        FGNN_T16_HIDDEN_BWD(L::OFF_WT2, dpre, dW2, db2, S2, S1, h2)
         __builtin_amdgcn_sched_barrier(0);
         stage8(S1, lane_base, dpre);                  // h2's tile is dead (LDS is in order within a wave)
         // ---- layer 1 ----
-        {
-            f32x4 a2[2];
-            a2[0] = a2[1] = zero4();
-            gemm32<L::OFF_WT1>(a2, wl, dpre, lane);
-            wgrad16(dW1, db1, S1, S0, lane);
-#pragma unroll
-            for (int s = 0; s < 8; ++s) dpre[s] = h1[s] > 0.f ? a2[s >> 2][s & 3] : 0.f;
-        }
+        FGNN_T16_HIDDEN_BWD(L::OFF_WT1, dpre, dW1, db1, S1, S0, h1)
         __builtin_amdgcn_sched_barrier(0);
         stage8(S2, lane_base, dpre);                  // dz's tile is dead
         __builtin_amdgcn_sched_barrier(0);
@@ -414,15 +338,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_t16_kernel(const fgnn_mlp_
     // ---- workgroup reduction of the parameter gradients (fixed order over the waves) ----
     // layout: [W0 (32*CIN) | b0 (32) | W1 (1024) | b1 (32) | W2 (1024) | b2 (32)]
     constexpr int PCOUNT = L::PCOUNT, CIN = L::CIN;
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        db0[b] += __shfl_xor(db0[b], 16);
-        db0[b] += __shfl_xor(db0[b], 32);
-        db1[b] += __shfl_xor(db1[b], 16);
-        db1[b] += __shfl_xor(db1[b], 32);
-        db2[b] += __shfl_xor(db2[b], 16);
-        db2[b] += __shfl_xor(db2[b], 32);
-    }
+    FGNN_T16_DB_BUTTERFLY(db0, db1, db2)
     (void)dbx;
     __syncthreads();                       // everyone done with the operand image and the tile buffers
     {
@@ -450,21 +366,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_bwd_t16_kernel(const fgnn_mlp_
         }
     }
     __syncthreads();
-    static_assert(PCOUNT % 4 == 0, "partials are summed four at a time");
-    float4 *out = reinterpret_cast<float4 *>(A.wpart + (long long)blockIdx.x * PCOUNT);
-    const float4 *part4 = reinterpret_cast<const float4 *>(smem);
-    for (int e = threadIdx.x; e < PCOUNT / 4; e += 64 * NW) {
-        float4 a = part4[e];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) {                                  // fixed order
-            const float4 b = part4[w * (PCOUNT / 4) + e];
-            a.x += b.x;
-            a.y += b.y;
-            a.z += b.z;
-            a.w += b.w;
-        }
-        out[e] = a;
-    }
+    sum_wave_partials<PCOUNT, NW>(smem, A.wpart);
 }
 
 template <int CB, bool PKD, bool SKIP, bool DXB>
@@ -500,19 +402,10 @@ extern "C" int fgnn_mlp_bwd_t16(const fgnn_mlp_bwd_args *a, void *stream) {
                "channels with dx stored or 2 raw channels without dx, an operand image of kind 5, N <= 256; use fgnn_mlp_bwd");
     FGNN_CHECK(a->G > 0 && a->N > 0 && a->a.ptr && (a->b.ptr || (a->xbits && a->b.C == 2)), "fgnn_mlp_bwd_t16: bad G / N / slabs");
     FGNN_CHECK(!a->xbits || a->xdeg, "fgnn_mlp_bwd_t16: xbits without xdeg (fgnn_adjacency_degree)");
-    FGNN_CHECK(a->dy && a->z && a->wpart, "fgnn_mlp_bwd_t16: missing dy/z/wpart");
-    FGNN_CHECK(a->coef || (a->s12 && a->znrm) || (a->s12tiles && a->znrm), "fgnn_mlp_bwd_t16: need coef, or s12 + znrm, or s12tiles + znrm");
-    FGNN_CHECK(BWD_WG == fgnn_mlp_bwd_num_workgroups() && BWD_WG == FGNN_RANGE_WG, "fgnn_mlp_bwd_t16: workgroup count differs from fgnn_mlp_bwd");
-    {
-        const long long lim = 0x7fffffffll / 4, G = a->G;
-        FGNN_CHECK(G * a->a.gstride < lim && G * a->b.gstride < lim && G * a->dgstride < lim && G * a->zgstride < lim &&
-                   G * a->dxa_gstride < lim && G * a->dxb_gstride < lim,
-                   "fgnn_mlp_bwd_t16: a tensor exceeds 2 GiB (32-bit buffer addressing); split the batch");
-    }
+    if (check_mlp_bwd_common(a, "fgnn_mlp_bwd_t16", 29)) return 1;
     for (int l = 0; l < a->depth; ++l) FGNN_CHECK(a->W[l] && a->bias[l], "fgnn_mlp_bwd_t16: missing weights layer %d", l);
     const int tpg = fgnn_tiles_per_graph(a->N);
     const long long total = (long long)a->G * tpg;
-    FGNN_CHECK(total < (1ll << 29), "fgnn_mlp_bwd_t16: too many tiles");
     FGNN_CHECK(!a->ranges || (a->nvalid && !a->s12tiles), "fgnn_mlp_bwd_t16: ranges need nvalid and exclude s12tiles");
     FGNN_CHECK(!a->s12tiles || fgnn_mlp_bwd_coef_tiles_supported(a->G, a->N), "fgnn_mlp_bwd_t16: s12tiles needs a workgroup's tile range to span <= %d graphs",
                FGNN_BWD_COEF_GRAPHS);

@@ -15,29 +15,12 @@
 #include "fgnn_tile.h"
 #include "fgnn_pack.h"
 #include "fgnn_x3.h"
+#include "fgnn_bwd32.h"
 
 namespace {
 
-constexpr int BWD_WG = 256;          // persistent workgroups (one per CU), = rows of wpart
-// waves per workgroup (template parameter NWT): 8 = 2 per SIMD with <= 256 registers each; 4 = one per SIMD with up to 512
-// (256 VGPRs + 256 AGPRs: the weight-gradient accumulators live in AGPRs, nothing spills)
-
-// dz coefficients {mean, ca, cb, cc} of one channel: dz = ca*dy + cb*(z - mean) + cc   
-DEVI float4 coef_from_sums(const float4 n, const float2 sv, float nv) {
-    const float m = nv * nv;
-    float4 k;
-    k.x = n.x;
-    k.y = n.y;
-    k.z = m > 0.f ? -n.y * sv.y * n.w / m : 0.f;
-    k.w = m > 0.f ? -n.y * sv.x / m : 0.f;
-    return k;
-}
-DEVI float4 coef_record(const fgnn_mlp_bwd_args &A, int g, int ch) {
-    if (A.coef) return reinterpret_cast<const float4 *>(A.coef)[(long long)g * FGNN_H + ch];
-    const float4 n = reinterpret_cast<const float4 *>(A.znrm)[(long long)g * FGNN_H + ch];
-    const float2 sv = reinterpret_cast<const float2 *>(A.s12)[(long long)g * FGNN_H + ch];
-    return coef_from_sums(n, sv, (float)nvalid_of(A.nvalid, g, A.N));
-}
+// waves per workgroup (template parameter NWT, shadowing fgnn_bwd32.h's NW): 8 = 2 per SIMD with <= 256 registers each; 4 = one per
+// SIMD with up to 512 (256 VGPRs + 256 AGPRs: the weight-gradient accumulators live in AGPRs, nothing spills)
 
 template <int CA, int CB, int NWT>
 struct BwdX3Layout {
@@ -167,11 +150,8 @@ __global__ __launch_bounds__(64 * NWT, NWT / 4) void mlp_bwd_x3_kernel(const fgn
 #pragma unroll
     for (int l = 0; l < DEPTH; ++l) db[l] = 0.f;
 
-    // static, strided tile assignment inside the workgroup's contiguous range (fixed accumulation order)
-    const int nwg = gridDim.x;
-    const int q = total_tiles / nwg, rem = total_tiles % nwg;
-    const int T0 = blockIdx.x * q + ((int)blockIdx.x < rem ? (int)blockIdx.x : rem);
-    const int T1 = T0 + q + ((int)blockIdx.x < rem ? 1 : 0);
+    int T0, T1;
+    wg_tile_range<false>(nullptr, total_tiles, T0, T1);
     const bool normA = A.a.nrm != nullptr, normB = (CB > 0) && A.b.nrm != nullptr;
     const bool emit = (CA == 32) && (CB == 0) && normA && A.dxa != nullptr && A.s12part != nullptr;
     const bool from_tiles = (CB > 0) && A.s12tiles != nullptr;
@@ -576,23 +556,14 @@ extern "C" int fgnn_mlp_bwd_x3(const fgnn_mlp_bwd_args *a, void *stream) {
                a->depth, a->a.C, a->b.C);
     FGNN_CHECK(a->packed, "fgnn_mlp_bwd_x3: needs the operand image of fgnn_pack_x3_operands (kind 1)");
     FGNN_CHECK(!a->ranges, "fgnn_mlp_bwd_x3: no padding-tile skipping (ranges); use fgnn_mlp_bwd for ragged batches");
-    FGNN_CHECK(BWD_WG == fgnn_mlp_bwd_num_workgroups(), "fgnn_mlp_bwd_x3: workgroup count differs from fgnn_mlp_bwd");
     const bool pk_a = a->xbits && a->a.C == 2, pk_b = a->xbits && a->b.C == 2;
     FGNN_CHECK((a->a.ptr || pk_a) && (a->b.C == 0 || a->b.ptr || pk_b), "fgnn_mlp_bwd_x3: slab pointer missing");
     FGNN_CHECK(!a->xbits || a->xdeg, "fgnn_mlp_bwd_x3: xbits without xdeg (fgnn_adjacency_degree)");
     FGNN_CHECK(!(a->a.C != 32 && a->dxa) && !(a->b.C != 32 && a->b.C != 0 && a->dxb),
                "fgnn_mlp_bwd_x3: input gradients exist for 32-channel slabs only; use fgnn_mlp_bwd");
-    FGNN_CHECK(a->dy && a->z && a->wpart, "fgnn_mlp_bwd_x3: missing dy/z/wpart");
-    FGNN_CHECK(a->coef || (a->s12 && a->znrm) || (a->s12tiles && a->znrm), "fgnn_mlp_bwd_x3: need coef, or s12 + znrm, or s12tiles + znrm");
-    {
-        const long long lim = 0x7fffffffll / 4, G = a->G;
-        FGNN_CHECK(G * a->a.gstride < lim && G * a->b.gstride < lim && G * a->dgstride < lim && G * a->zgstride < lim &&
-                   G * a->dxa_gstride < lim && G * a->dxb_gstride < lim,
-                   "fgnn_mlp_bwd_x3: a tensor exceeds 2 GiB (32-bit buffer addressing); split the batch");
-    }
+    if (check_mlp_bwd_common(a, "fgnn_mlp_bwd_x3", 30)) return 1;
     const int tpg = fgnn_tiles_per_graph(a->N);
     const long long total = (long long)a->G * tpg;
-    FGNN_CHECK(total < (1ll << 30), "fgnn_mlp_bwd_x3: too many tiles");
     FGNN_CHECK(!a->s12tiles || a->b.C > 0, "fgnn_mlp_bwd_x3: s12tiles is built into the two-slab kernels only");
     FGNN_CHECK(!a->s12tiles || fgnn_mlp_bwd_coef_tiles_supported(a->G, a->N),
                "fgnn_mlp_bwd_x3: s12tiles needs a workgroup's tile range to span <= %d graphs (G=%d N=%d)", FGNN_BWD_COEF_GRAPHS, a->G, a->N);
