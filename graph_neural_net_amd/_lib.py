@@ -151,6 +151,11 @@ class GuardRecord(C.Structure):       # fgnn_guard_record (csrc/grad_guard.hip);
                 ('partial', C.c_double * FGNN_GUARD_MAX_PARTS)]
 
 
+class EvalRecord(C.Structure):        # fgnn_eval_record (csrc/eval.hip); lives in device memory, this mirror gives the offsets
+    _fields_ = [('ce_sum', C.c_double), ('nodes', C.c_longlong), ('correct_lsap', C.c_longlong), ('correct_max', C.c_longlong),
+                ('pairs', C.c_longlong), ('steps', C.c_longlong)]
+
+
 MAX_GRAD_JOBS = 16
 MAX_PACK_JOBS = 24
 _VP, _LL, _I, _F = C.c_void_p, C.c_longlong, C.c_int, C.c_float
@@ -270,6 +275,8 @@ _SIGNATURES = {
     'fgnn_count_matches': [_VP, _VP, _VP, _I, _I, _VP, _VP],
     'fgnn_accuracy_max_labels': [_VP, _VP, _VP, _I, _I, _VP, _VP],
     'fgnn_spectral_features': [_VP, _VP, _I, _I, _I, _VP, _I, _VP],
+    'fgnn_eval_pairs': [_VP, _VP, _VP, _I, _I, _VP, _LL, _I, _VP, _VP, _VP],
+    'fgnn_eval_fold': [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP],
     # ---- bf16 path ----
     'fgnn_tiles_per_graph16': [_I, _I],
     'fgnn_to_bf16': [_VP, _VP, _I, _I, _I, _I, _VP, _LL, _LL, _VP],

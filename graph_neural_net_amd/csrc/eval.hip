@@ -1,0 +1,160 @@
+// Validation on the device (include/fgnn_hip.h, "evaluation"): what the reference's all_losses_acc (toolbox/metrics.py:144-166)
+// and the val_loss of its ReduceLROnPlateau (models/trainers.py:78-104) need from a batch of raw scores, without the eager
+// prologue of the Hungarian accuracy (masked_fill, log_softmax, negation, contiguous: five passes over B N^2 floats) and without
+// a read-back per batch.
+//   fgnn_eval_pairs : ONE pass over the scores: per valid row the log-sum-exp, the cost row -log_softmax for fgnn_lsap_accuracy,
+//                     the cross-entropy against the identity and the arg-max hit.
+//   fgnn_eval_fold  : per-pair sums of those rows and the add into the epoch record, by one workgroup in a fixed order.
+// Both are plain launches on the caller's stream: capturable, no allocation, no copy, no synchronisation.
+#include "fgnn_common.h"
+
+namespace {
+
+constexpr int EVAL_THREADS = 256;
+
+DEVI int clamp_nv(const int *nvalid, int b, int N) {
+    const int n = nvalid ? nvalid[b] : N;
+    return n < 0 ? 0 : (n > N ? N : n);
+}
+
+// W lanes per row (64: one wave per row; 16: four rows per wave, for rows of at most 16 columns).  Lane `sub` of a row's group
+// takes the columns sub, sub + W, ... in ascending order and the group meets by xor butterflies below W (a + b == b + a: every
+// lane of the group ends with the same bits), so the order of every addition is a function of (N, lane) alone -- W is chosen from
+// N -- and a row has the same lse in any batch, at any position.
+// The arg-max is the rule of fgnn_accuracy_max: first maximum on ties, NaN above every number (the first NaN wins), column 0 for
+// a row of -inf.  Its value doubles as the row maximum m of the lse: a NaN there makes the lse NaN, which exp(NaN - m) would as well.
+template <int W>
+__global__ __launch_bounds__(EVAL_THREADS) void eval_pairs_kernel(const float *scores, const int *nvalid, const int *labels, int B, int N,
+                                                                  float *cost, long long cost_bstride, int cost_ld, float *row_ce,
+                                                                  int *row_hit) {
+    const int sub = threadIdx.x & (W - 1);
+    const long long t = (long long)blockIdx.x * (EVAL_THREADS / W) + threadIdx.x / W;      // row index over (b, i)
+    const bool inside = t < (long long)B * N;
+    const long long tc = inside ? t : 0;
+    const int b = (int)(tc / N), i = (int)(tc - (long long)b * N);
+    const int nb = clamp_nv(nvalid, b, N);
+    const bool live = inside && i < nb;                  // (uniform inside a row's group)
+    const int n = live ? nb : 0;                         // dead groups run the butterflies on empty rows and store nothing
+    const float *row = scores + ((long long)b * N + i) * N;
+
+    float best = -INFINITY;
+    int bj = 0x7fffffff;
+    for (int j = sub; j < n; j += W) {                   // ascending j: an equal later value never replaces
+        const float v = row[j];
+        if (bj == 0x7fffffff || (best == best && (v > best || v != v))) {
+            best = v;
+            bj = j;
+        }
+    }
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) {                // ties towards the smaller index
+        const float ob = __shfl_xor(best, o);
+        const int oj = __shfl_xor(bj, o);
+        const bool onan = ob != ob, bnan = best != best;
+        if (onan ? (!bnan || oj < bj) : (!bnan && (ob > best || (ob == best && oj < bj)))) {
+            best = ob;
+            bj = oj;
+        }
+    }
+    const float m = best;
+    float sum = 0.f;
+    for (int j = sub; j < n; j += W) sum += expf(row[j] - m);
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    const float lse = m + logf(sum);
+    float *crow = cost + (long long)b * cost_bstride + (long long)i * cost_ld;
+    for (int j = sub; j < n; j += W) crow[j] = lse - row[j];
+    if (live && sub == 0) {
+        row_ce[t] = lse - row[i];
+        row_hit[t] = bj == (labels ? labels[t] : i) ? 1 : 0;
+    }
+}
+
+// One workgroup of four waves.  Wave w takes the pairs 4 c + w of chunk c: lane l adds the rows l, l + 64, ... of the pair in
+// ascending order (fp64 for the cross-entropy), the wave meets by a butterfly; thread 0 then adds the chunk's pairs below `live`
+// to its running record in pair order, one pair at a time.  Every addition has its place fixed by (B, N, live) and the record it
+// started from, so an epoch's record has the same bits on every run, however its examples were cut into calls.
+__global__ __launch_bounds__(EVAL_THREADS) void eval_fold_kernel(const float *row_ce, const int *row_hit, const int *correct_lsap,
+                                                                 const int *nvalid, int B, int N, int live, double *pair_ce, int *pair_max,
+                                                                 fgnn_eval_record *meter) {
+    __shared__ double s_ce[EVAL_THREADS / WAVE];
+    __shared__ int s_hit[EVAL_THREADS / WAVE];
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+    double ce_sum = 0.0;
+    long long nodes = 0, c_lsap = 0, c_max = 0, pairs = 0;
+    if (threadIdx.x == 0) ce_sum = meter->ce_sum;
+    for (int b0 = 0; b0 < live; b0 += EVAL_THREADS / WAVE) {         // (uniform bounds: every thread meets every barrier)
+        const int b = b0 + wave;
+        if (b < live) {
+            const int n = clamp_nv(nvalid, b, N);
+            double ce = 0.0;
+            int hit = 0;
+            for (int i = lane; i < n; i += WAVE) {
+                ce += (double)row_ce[(long long)b * N + i];
+                hit += row_hit[(long long)b * N + i];
+            }
+            for (int o = 32; o > 0; o >>= 1) {
+                ce += __shfl_xor(ce, o);
+                hit += __shfl_xor(hit, o);
+            }
+            if (lane == 0) {
+                s_ce[wave] = ce;
+                s_hit[wave] = hit;
+                if (pair_ce) pair_ce[b] = ce;
+                if (pair_max) pair_max[b] = hit;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int w = 0; w < EVAL_THREADS / WAVE && b0 + w < live; ++w) {
+                ce_sum += s_ce[w];
+                c_max += s_hit[w];
+                nodes += clamp_nv(nvalid, b0 + w, N);
+                if (correct_lsap) c_lsap += correct_lsap[b0 + w];
+                pairs += 1;
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && live > 0) {
+        meter->ce_sum = ce_sum;
+        meter->nodes += nodes;
+        meter->correct_lsap += c_lsap;
+        meter->correct_max += c_max;
+        meter->pairs += pairs;
+        meter->steps += 1;
+    }
+}
+
+}  // namespace
+
+extern "C" int fgnn_eval_pairs(const float *scores, const int *nvalid, const int *labels, int B, int N, float *cost,
+                               long long cost_bstride, int cost_ld, float *row_ce, int *row_hit, void *stream) {
+    FGNN_CHECK(scores && cost && row_ce && row_hit && B > 0 && N > 0, "fgnn_eval_pairs: bad arguments");
+    FGNN_CHECK(N <= FGNN_LSAP_MAX_N, "fgnn_eval_pairs: at most %d vertices per graph (got %d)", FGNN_LSAP_MAX_N, N);
+    FGNN_CHECK(cost_ld >= N && cost_bstride >= (long long)N * cost_ld, "fgnn_eval_pairs: cost strides smaller than the matrices");
+    const long long rows = (long long)B * N;
+    if (N <= 16) {
+        const long long wgs = (rows + EVAL_THREADS / 16 - 1) / (EVAL_THREADS / 16);
+        FGNN_CHECK(wgs <= 0x7fffffffll, "fgnn_eval_pairs: %lld rows are more than one launch takes", rows);
+        hipLaunchKernelGGL(eval_pairs_kernel<16>, dim3((unsigned)wgs), dim3(EVAL_THREADS), 0, (hipStream_t)stream, scores, nvalid, labels,
+                           B, N, cost, cost_bstride, cost_ld, row_ce, row_hit);
+    } else {
+        const long long wgs = (rows + EVAL_THREADS / WAVE - 1) / (EVAL_THREADS / WAVE);
+        FGNN_CHECK(wgs <= 0x7fffffffll, "fgnn_eval_pairs: %lld rows are more than one launch takes", rows);
+        hipLaunchKernelGGL(eval_pairs_kernel<WAVE>, dim3((unsigned)wgs), dim3(EVAL_THREADS), 0, (hipStream_t)stream, scores, nvalid,
+                           labels, B, N, cost, cost_bstride, cost_ld, row_ce, row_hit);
+    }
+    FGNN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int fgnn_eval_fold(const float *row_ce, const int *row_hit, const int *correct_lsap, const int *nvalid, int B, int N,
+                              int live, double *pair_ce, int *pair_max, fgnn_eval_record *meter, void *stream) {
+    FGNN_CHECK(row_ce && row_hit && meter && B > 0 && N > 0, "fgnn_eval_fold: bad arguments");
+    FGNN_CHECK(live >= 0 && live <= B, "fgnn_eval_fold: live = %d outside [0, %d]", live, B);
+    hipLaunchKernelGGL(eval_fold_kernel, dim3(1), dim3(EVAL_THREADS), 0, (hipStream_t)stream, row_ce, row_hit, correct_lsap, nvalid, B, N,
+                       live, pair_ce, pair_max, meter);
+    FGNN_LAUNCH_CHECK();
+    return 0;
+}

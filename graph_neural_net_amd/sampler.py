@@ -83,6 +83,13 @@ class EpochSampler:
         device = self.device if self.device is not None else torch.device('cuda', torch.cuda.current_device())
         return torch.arange(first, first + count, dtype=torch.int64, device=device) % self.num_examples
 
+    def live_count(self, step, batch_size):
+        """How many of this rank's batch_size positions at `step` are examples of their own (positions below num_examples): the
+        others wrap around and repeat examples the epoch has already shown, which an evaluation must not count twice.  batch_size
+        everywhere but in the last global step of a drop_last=False epoch (host arithmetic only)."""
+        first, count = self.window(step, batch_size)
+        return max(0, min(count, self.num_examples - first))
+
     @staticmethod
     def _batch(batch_size):
         B = int(batch_size)

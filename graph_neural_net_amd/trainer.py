@@ -351,6 +351,81 @@ class FgnnTrainer:
             losses[step].copy_(loss)
         return losses
 
+    # ------------------------------------------------------------------ validation / test epochs (evaluation.py)
+    def _eval_forward(self, B, N, nvalid, x=None, bits=None):
+        """EngineBase.forward of the training engine for (B, N) on the stacked batch: raw scores only.  Its loss sum goes to a buffer
+        of this method's own; gradients, the collective's buffer, the optimizer and the captured graphs are not touched."""
+        if getattr(self, '_eval_loss', None) is None:
+            self._eval_loss = torch.zeros(1, dtype=torch.float32, device=self.params.device)
+        eng = self._engine(2 * B, N, nvalid is not None)
+        nv = None if nvalid is None else torch.cat([nvalid, nvalid]).to(torch.int32)
+        scores, _ = eng.forward(self.params, x, nvalid=nv, total_nodes=1.0, defer_loss=False, loss_out=self._eval_loss, bits=bits)
+        return scores
+
+    def eval_step_bits(self, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, hungarian=True):
+        """Forward-only evaluation of a batch handed over as train_step_bits takes it: the training engine's forward pass (a third of
+        a step's work), then evaluation.evaluate_scores on its scores -- see there for labels, meter, live, hungarian and the
+        returned per-pair device tensors.  Nothing is read back; parameters, gradients and optimizer state keep their bits."""
+        if bits1.dim() != 3 or bits1.shape != bits2.shape or bits1.dtype not in (torch.int32, torch.uint32) or not bits1.is_cuda:
+            raise RuntimeError('FgnnTrainer.eval_step_bits: expected two (B, N, ceil(N/32)) int32 device tensors, got %s %s / %s %s'
+                               % (tuple(bits1.shape), bits1.dtype, tuple(bits2.shape), bits2.dtype))
+        B, N = bits1.shape[0], bits1.shape[1]
+        if bits1.shape[2] != (N + 31) // 32:
+            raise RuntimeError('FgnnTrainer.eval_step_bits: %d words per row for N = %d (expected %d)' % (bits1.shape[2], N, (N + 31) // 32))
+        from .evaluation import evaluate_scores
+        scores = self._eval_forward(B, N, nvalid, bits=torch.cat([bits1, bits2]).contiguous())
+        return evaluate_scores(scores, nvalid=nvalid, labels=labels, meter=meter, live=live, hungarian=hungarian)
+
+    def eval_step(self, x1, x2, nvalid=None, labels=None, meter=None, live=None, hungarian=True):
+        """eval_step_bits for dense batches: x1, x2 (B, c0, N, N) fp32 on the GPU, through the generic kernels."""
+        if x1.dim() != 4 or x1.shape != x2.shape or not x1.is_cuda:
+            raise RuntimeError('FgnnTrainer.eval_step: expected two (B, c0, N, N) device tensors, got %s / %s'
+                               % (tuple(x1.shape), tuple(x2.shape)))
+        from .evaluation import evaluate_scores
+        scores = self._eval_forward(x1.shape[0], x1.shape[-1], nvalid, x=torch.cat([x1, x2]).contiguous())
+        return evaluate_scores(scores, nvalid=nvalid, labels=labels, meter=meter, live=live, hungarian=hungarian)
+
+    def evaluate(self, generator, sampler, batch_size, epoch=0, hungarian=True, meter=None, permute=False):
+        """One pass over this rank's examples of `sampler` (sampler.EpochSampler; shuffle=False is the reference's validation
+        loader): per step ``eval_step_bits(*generator.bits(index=sampler.batch_index(epoch, step, batch_size)))`` with the generator's
+        vertex counts and, with permute=True, its planted labels.  Every example counts exactly once: the positions with which a
+        short last step is filled are masked out (live=sampler.live_count(...)).  With more than one rank the record is summed
+        over the ranks at the end (one all-reduce of 6 values).  Reads nothing back; returns the meter (EvalMeter)."""
+        from .evaluation import EvalMeter
+        B = int(batch_size)
+        if meter is None:
+            meter = EvalMeter(self.params.device)
+        elif not isinstance(meter, EvalMeter):
+            raise ValueError('FgnnTrainer.evaluate: meter must be an EvalMeter or None (got %s)' % type(meter).__name__)
+        for step in range(sampler.steps_per_epoch(B)):
+            live = sampler.live_count(step, B)
+            if live == 0:       # (a rank past the end of the data in the last global step)
+                continue
+            kw = {'permute': True} if permute else {}
+            b1, b2, nv, *labels = generator.bits(index=sampler.batch_index(epoch, step, B), **kw)
+            self.eval_step_bits(b1, b2, nvalid=nv, labels=labels[0] if labels else None, meter=meter, live=live, hungarian=hungarian)
+        if dp.world_size() > 1:
+            meter.allreduce_()
+        return meter
+
+    def fit(self, train_gen, train_sampler, val_gen, val_sampler, epochs, batch_size, scheduler=None):
+        """The reference's training loop around its scheduler (models/trainers.py:92-104): per epoch train_epoch, evaluate, ONE host
+        read (the validation record), scheduler.step(val_loss).  scheduler=None: optim.ReduceLROnPlateau with the reference's
+        settings, driving self.opt.lr (the next step pushes a changed rate to the device).  Returns the per-epoch history: dicts
+        with 'epoch', 'train_losses' (the (steps,) device tensor of train_epoch), 'val_loss', 'val_acc', 'val_acc_max', 'lr' (the
+        rate the NEXT epoch runs with)."""
+        if scheduler is None:
+            from .optim import ReduceLROnPlateau
+            scheduler = ReduceLROnPlateau(self.opt)
+        history = []
+        for epoch in range(int(epochs)):
+            losses = self.train_epoch(train_gen, train_sampler, epoch, batch_size)
+            res = self.evaluate(val_gen, val_sampler, batch_size, epoch=epoch).result()
+            scheduler.step(res['loss'])
+            history.append({'epoch': epoch, 'train_losses': losses, 'val_loss': res['loss'], 'val_acc': res['acc'],
+                            'val_acc_max': res['acc_max'], 'lr': self.opt.lr})
+        return history
+
     def train_step(self, x1, x2, nvalid=None):
         """x1, x2: (B, c0, N, N) local shard on the GPU.  Returns (loss of the global batch as a device
         scalar, scores of the local shard)."""

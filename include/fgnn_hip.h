@@ -891,6 +891,43 @@ int fgnn_greedy_qapw_labels(const float *a1, const float *a2, long long gstride,
 #define FGNN_SPECTRAL_MAX_POWERS 8
 int fgnn_spectral_features(const unsigned *bits, const int *nvalid, int G, int N, int n_powers, float *out, int Nout, void *stream);
 
+/* ---- evaluation (csrc/eval.hip): what the reference's all_losses_acc (toolbox/metrics.py:144-166) and the val_loss behind its
+ * ReduceLROnPlateau (models/trainers.py:78-104) take from a batch of raw scores, kept on the device ---------------------------
+ * scores: (B, N, N) fp32 raw scores.  nvalid (optional, int32[B]): pair b is the n_b x n_b corner (n_b clamped to [0, N]; NULL:
+ * n_b = N); NOTHING outside the corner of scores is read (it may hold NaN).  1 <= N <= FGNN_LSAP_MAX_N.
+ *
+ * fgnn_eval_pairs, one pass, for every row i < n_b of pair b over the columns j < n_b:
+ *   lse           = m + log(sum_j exp(s_ij - m)), m = max_j s_ij, in fp32; the order of the additions is fixed by (N, lane) alone: a
+ *                   row has the same bits in any batch, at any position
+ *   cost[b][i][j] = lse - s_ij (= -log_softmax), written to the n_b x n_b corner of the layout fgnn_lsap_accuracy reads (row pitch
+ *                   cost_ld >= N, pairs cost_bstride >= N cost_ld apart); nothing outside the corner is written
+ *   row_ce[b][i]  = lse - s_ii: the reference loss (toolbox/losses.py:20-34), whose target is the identity; labels never enter it
+ *   row_hit[b][i] = [argmax_j s_ij == (labels ? labels[b][i] : i)] with the arg-max of fgnn_accuracy_max / fgnn_accuracy_max_labels:
+ *                   first maximum on ties, NaN above every number, column 0 for a row of -inf
+ *   row_ce (fp32) and row_hit (int32) are (B, N); entries of rows >= n_b are not written.  Non-finite scores propagate by IEEE
+ *   rules (a NaN or +inf in a row, or a row of -inf, gives a NaN lse); nothing is special-cased beyond the arg-max rule.
+ * fgnn_eval_fold, for the pairs b < live (0 <= live <= B; pairs >= live are ignored entirely -- the surplus of a short last step):
+ *   pair_ce[b] (optional, fp64) = sum_i row_ce[b][i] in fp64, pair_max[b] (optional, int32) = sum_i row_hit[b][i]; then ONE
+ *   workgroup adds the pairs to the epoch record in pair order, one pair at a time: ce_sum += pair_ce[b], nodes += n_b,
+ *   correct_max += pair_max[b], correct_lsap += correct_lsap[b] (optional: the correct[] of fgnn_lsap_accuracy / fgnn_count_matches),
+ *   pairs += 1; steps += 1 per call with live > 0.  No floating-point atomics, a fixed order: the record of an epoch is
+ *   bit-identical from run to run and does not depend on how its examples were cut into calls.  The record lives in device
+ *   memory, zero-initialised (and reset) by its owner.
+ * Both are single launches on `stream`: capturable, no allocation, no host copy, no synchronisation. */
+typedef struct {
+    double ce_sum;          /* sum of the row cross-entropies of every live pair */
+    long long nodes;        /* sum of n_b */
+    long long correct_lsap; /* matches of the Hungarian matching */
+    long long correct_max;  /* arg-max hits */
+    long long pairs;        /* live pairs folded */
+    long long steps;        /* fgnn_eval_fold calls with live > 0 */
+} fgnn_eval_record;
+int fgnn_eval_pairs(const float *scores, const int *nvalid /* optional */, const int *labels /* optional */, int B, int N, float *cost,
+                    long long cost_bstride, int cost_ld, float *row_ce, int *row_hit, void *stream);
+int fgnn_eval_fold(const float *row_ce, const int *row_hit, const int *correct_lsap /* optional */, const int *nvalid /* optional */,
+                   int B, int N, int live, double *pair_ce /* optional */, int *pair_max /* optional */, fgnn_eval_record *meter,
+                   void *stream);
+
 /* ---- test-only entry points (never on the product path; tests/ and tools/ call them) ---------------------------------------
  * fgnn_debug_mlp_fwd_masks / fgnn_debug_mlp_fwd_x3_masks: fgnn_mlp_fwd / fgnn_mlp_fwd_x3 once more -- the same tile code, the same
  * outputs, bit for bit -- that ALSO exports the ReLU decisions of the conv chain (models/layers.py:129-130), the input of the
