@@ -1,5 +1,5 @@
 // What the six fp32 MLP backward files share (mlp_bwd.hip, mlp_bwd_pair.hip, mlp_bwd_x3.hip, mlp_bwd_pair_x3.hip, mlp_bwd_t16.hip,
-// mlp_bwd_pair_t16.hip): the launch geometry, the dz coefficient records, a workgroup's tile range, the
+// mlp_bwd_pair_t16.hip): the launch geometry, the dz coefficient records, the
 // fixed-order sum of the waves' partials and the entry points' argument checks.  Tile geometry is NOT here: the 32-pixel kernels
 // take theirs from fgnn_tile.h, the 16-pixel ones from fgnn_t16.h.
 #pragma once
@@ -40,22 +40,7 @@ DEVI float4 coef_record(const fgnn_mlp_bwd_args &A, int g, int ch) {
     return coef_from_sums(n, sv, (float)nvalid_of(A.nvalid, g, A.N));
 }
 
-// The workgroup's contiguous tile range [T0, T1): an even split, or (SKIP: ragged batches with ranges) the equal-work split of
-// fgnn_ragged_tile_ranges.  Inside it the waves (pairs) take tiles in a static order: the order in which a wave accumulates its
-// weight gradients is fixed -> bit-reproducible results.
-template <bool SKIP>
-DEVI void wg_tile_range(const int *ranges, int total_tiles, int &T0, int &T1) {
-    if constexpr (SKIP) {
-        T0 = ranges[blockIdx.x];
-        T1 = ranges[blockIdx.x + 1];
-    } else {
-        const int nwg = gridDim.x;
-        const int q = total_tiles / nwg, rem = total_tiles % nwg;
-        const int b = blockIdx.x;
-        T0 = b * q + (b < rem ? b : rem);
-        T1 = T0 + q + (b < rem ? 1 : 0);
-    }
-}
+// (a workgroup's tile range, wg_tile_range<SKIP>, is in fgnn_common.h: the forward kernels use it too)
 
 // the two argument blocks of a fused mlp1 + mlp2 launch
 struct PairArgs {

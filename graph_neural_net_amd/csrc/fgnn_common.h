@@ -129,6 +129,23 @@ DEVI int xcd_swizzle(int b, int n) {
     return b < n8 ? (b & 7) * (n8 >> 3) + (b >> 3) : b;
 }
 
+// The workgroup's contiguous tile range [T0, T1) in the fused MLP kernels, forward and backward: an even split, or (SKIP: ragged
+// batches with ranges) the equal-work split of fgnn_ragged_tile_ranges.  Inside it the waves (pairs) take tiles in a static order:
+// the order in which a wave accumulates its weight gradients is fixed -> bit-reproducible results.
+template <bool SKIP>
+DEVI void wg_tile_range(const int *ranges, int total_tiles, int &T0, int &T1) {
+    if constexpr (SKIP) {
+        T0 = ranges[blockIdx.x];
+        T1 = ranges[blockIdx.x + 1];
+    } else {
+        const int nwg = gridDim.x;
+        const int q = total_tiles / nwg, rem = total_tiles % nwg;
+        const int b = blockIdx.x;
+        T0 = b * q + (b < rem ? b : rem);
+        T1 = T0 + q + (b < rem ? 1 : 0);
+    }
+}
+
 // ---- ragged batches: tiles inside the padding ------------------------------------------------------------------------
 // A tile = T consecutive elements of a plane stored with row pitch `pitch` (fp32 slabs: T = FGNN_TILE, pitch = N; bf16
 // slabs: T = 64, pitch = ldr).  Does tile tt hold an element of the valid nv x nv corner?

@@ -1,5 +1,5 @@
-// Tile geometry, slab loads and operand reads shared by the 32-pixel MLP backward kernels and the x3 MLP kernels (the same
-// conventions as mlp_fwd.hip):
+// Tile geometry, slab loads and operand reads shared by the 32-pixel MLP kernels (mlp_fwd.hip, the backward kernels and the x3
+// kernels):
 // a tile = 32 consecutive pixels of one graph; lane (j, h) = pixel j of the tile, half-wave h; a 32-channel slab gives
 // the lane its 16 channels ch_of(r, h), a 2-channel slab gives half-wave h channel h.
 #pragma once

@@ -22,7 +22,7 @@
 //     BEFORE the prefetch is issued (vmcnt is in-order);
 //   * tile statistics: the z tile is transposed through a wave-private LDS tile so that a
 //     lane owns one channel and sums its 16 pixels in registers (two-pass mean / M2).
-#include "fgnn_common.h"
+#include "fgnn_fwd32.h"
 #include "fgnn_pack.h"
 
 #ifdef FGNN_PHASES
@@ -33,61 +33,8 @@ __device__ int g_fwd_sel = 0;
 
 namespace {
 
-constexpr int TLD = 36;              // LDS tile row stride (floats)
-constexpr int TILE_F = 32 * TLD;
-
-struct TileCtx {
-    int g, tt, p, i, jj;
-    bool inb;
-};
-
-// The valid-vertex count of the graph is NOT read here: a global load at the top of every tile makes
-// the compiler drain the whole memory pipeline (s_waitcnt vmcnt(0): next-tile prefetch AND the previous
-// tile's stores).  It is fetched once per graph change, next to the per-graph records.
-DEVI TileCtx decode_tile(int tile, bool active, int tpg, int N, int P, int j) {
-    TileCtx c;
-    c.g = __builtin_amdgcn_readfirstlane(active ? tile / tpg : 0);
-    c.tt = active ? tile - c.g * tpg : 0;
-    c.p = c.tt * FGNN_TILE + j;
-    c.inb = active && c.p < P;
-    c.i = c.p / N;
-    c.jj = c.p - c.i * N;
-    return c;
-}
-DEVI bool tile_valid(const TileCtx &c, int nv) { return c.inb && c.i < nv && c.jj < nv; }
-
-// channel contracted by k-step k in half-wave h for a slab with S = C/2 steps: 32-channel
-// slabs use the accumulator-fragment pairing (same as the hidden layers), narrower ones (2k, 2k+1)
-template <int S>
-DEVI constexpr int slab_ch(int k, int h) { return S == 16 ? ch_of(k, h) : 2 * k + h; }
-template <int S>
-DEVI constexpr int slab_kbase(int k) { return S == 16 ? (k & 3) + 8 * (k >> 2) : 2 * k; }
-template <int S>
-DEVI constexpr int slab_hmul() { return S == 16 ? 4 : 1; }
-
-template <int HMUL>
-DEVI int lane_off(const View &v, const TileCtx &c, int h) {
-    return c.inb ? HMUL * h * v.ld4 + 4 * c.p : OOB_OFF;
-}
-
-template <int S>
-DEVI void load_raw(float (&x)[S > 0 ? S : 1], const View &v, const TileCtx &c, int h) {
-    if constexpr (S > 0) {
-        const int voff = lane_off<slab_hmul<S>()>(v, c, h);
-        const int s0 = c.g * v.gs4;
-#pragma unroll
-        for (int k = 0; k < S; ++k) x[k] = buf_load(v, voff, s0 + slab_kbase<S>(k) * v.ld4);
-    }
-}
-
-// slab load: from memory, or (PK, 2-channel slabs only) from the packed adjacency
-template <int S, bool PK>
-DEVI void load_slab(float (&x)[S > 0 ? S : 1], const View &v, const PackedSrc &ps, const TileCtx &c, int h) {
-    if constexpr (PK && S == 1) load_packed(x, ps, c, h);
-    else load_raw<S>(x, v, c, h);
-}
-
 // y = (x - mean) * a + beta with the per-graph records {mean, a, beta, -} read from wave-private LDS
+// (in place; fgnn_tile.h's out-of-place norm_slab, called with y = x, changes the branches of 56 of the 96 kernels)
 template <int S>
 DEVI void apply_norm(float (&x)[S > 0 ? S : 1], const float *rec, bool on, bool valid, int h) {
     if constexpr (S > 0) {
@@ -127,6 +74,7 @@ struct FwdLayout {
     static constexpr int LDS_F = WEIGHT_F + NW * (TILE_F + REC_F);
 };
 
+// fgnn_tile.h's load_ops<OFF, CNT> with the offset at run time (the hidden layers' offset is a loop variable)
 template <int CNT>
 DEVI void load_ops(float (&dst)[CNT > 0 ? CNT : 1], const float *wl, int off_steps, int lane) {
     const float4 *p = reinterpret_cast<const float4 *>(wl) + (off_steps / 4) * 64 + lane;
@@ -137,19 +85,6 @@ DEVI void load_ops(float (&dst)[CNT > 0 ? CNT : 1], const float *wl, int off_ste
         if (4 * q + 1 < CNT) dst[4 * q + 1] = v.y;
         if (4 * q + 2 < CNT) dst[4 * q + 2] = v.z;
         if (4 * q + 3 < CNT) dst[4 * q + 3] = v.w;
-    }
-}
-
-// bias[ch_of(r, h)], r = 0..15, of one layer from the compact tail (broadcast reads)
-DEVI void load_bias(float (&dst)[16], const float *tail, int layer, int h) {
-    const float4 *p = reinterpret_cast<const float4 *>(tail + layer * 32 + h * 16);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 v = p[q];
-        dst[4 * q + 0] = v.x;
-        dst[4 * q + 1] = v.y;
-        dst[4 * q + 2] = v.z;
-        dst[4 * q + 3] = v.w;
     }
 }
 
@@ -171,26 +106,12 @@ DEVI void mlp_fwd_body(const fgnn_mlp_fwd_args A, const int tpg, const int total
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int j = lane & 31, h = lane >> 5;
     const int P = A.N * A.N;
-    float *wl = smem;
-    float *tl = smem + L::WEIGHT_F + wv * TILE_F;
-    float *recA = smem + L::WEIGHT_F + NW * TILE_F + wv * L::REC_F, *recB = recA + 128;
-    const View va = make_view(A.a.ptr, A.a.gstride, A.a.ldp, A.G);
-    const View vb = make_view(A.b.ptr, A.b.gstride, A.b.ldp, A.G);
-    PackedSrc ps = {};
-    if constexpr (PK) ps = make_packed_src(A.xbits, A.xdeg, A.G, A.N);
-    View vz[NMLP];
-#pragma unroll
-    for (int m = 0; m < NMLP; ++m) vz[m] = make_view(A.z[m], FGNN_H * A.ldz, A.ldz, A.G);
+    float *wl = smem, *tl = fwd_lds_tile<L>(smem, wv), *recA = fwd_lds_records<L>(smem, wv), *recB = recA + 128;
+    FGNN_FWD32_VIEWS
 
     // contiguous tile range of this workgroup; wave w takes tiles T0 + w, T0 + w + NW, ... (static)
-    const int nwg = gridDim.x;
-    const int q = total_tiles / nwg, rem = total_tiles % nwg;
-    int T0 = blockIdx.x * q + ((int)blockIdx.x < rem ? (int)blockIdx.x : rem);
-    int T1 = T0 + q + ((int)blockIdx.x < rem ? 1 : 0);
-    if constexpr (SKIP) {
-        T0 = A.ranges[blockIdx.x];
-        T1 = A.ranges[blockIdx.x + 1];
-    }
+    int T0, T1;
+    wg_tile_range<SKIP>(A.ranges, total_tiles, T0, T1);
 
     // The first tile's input slabs and per-graph records are requested BEFORE the operand image
     // is copied, so the three dependent round trips of the prologue overlap into one.
@@ -229,14 +150,8 @@ DEVI void mlp_fwd_body(const fgnn_mlp_fwd_args A, const int tpg, const int total
         load_slab<SA, PK>(xa, va, ps, c, h);
         load_slab<SB, PK>(xb, vb, ps, c, h);
         if (tile < T1 && lane < 32) {
-            if (normA && lane < CA) {
-                ra = reinterpret_cast<const float4 *>(A.a.nrm)[(long long)c.g * A.a.C + lane];
-                ra.z = A.a.beta ? A.a.beta[lane] : 0.f;
-            }
-            if (normB && lane < CB) {
-                rb = reinterpret_cast<const float4 *>(A.b.nrm)[(long long)c.g * A.b.C + lane];
-                rb.z = A.b.beta ? A.b.beta[lane] : 0.f;
-            }
+            if (normA && lane < CA) fetch_record(ra, A.a.nrm, A.a.beta, A.a.C, c.g, lane);
+            if (normB && lane < CB) fetch_record(rb, A.b.nrm, A.b.beta, A.b.C, c.g, lane);
         }
         if (tile < T1) {
             cached_g = c.g;
@@ -279,13 +194,13 @@ DEVI void mlp_fwd_body(const fgnn_mlp_fwd_args A, const int tpg, const int total
         if (c.g != cached_g) {        // wave-uniform; issued before the prefetch (vmcnt is in-order)
             if (lane < 32) {
                 if (normA && lane < CA) {
-                    float4 n = reinterpret_cast<const float4 *>(A.a.nrm)[(long long)c.g * A.a.C + lane];
-                    n.z = A.a.beta ? A.a.beta[lane] : 0.f;
+                    float4 n;
+                    fetch_record(n, A.a.nrm, A.a.beta, A.a.C, c.g, lane);
                     reinterpret_cast<float4 *>(recA)[lane] = n;
                 }
                 if (normB && lane < CB) {
-                    float4 n = reinterpret_cast<const float4 *>(A.b.nrm)[(long long)c.g * A.b.C + lane];
-                    n.z = A.b.beta ? A.b.beta[lane] : 0.f;
+                    float4 n;
+                    fetch_record(n, A.b.nrm, A.b.beta, A.b.C, c.g, lane);
                     reinterpret_cast<float4 *>(recB)[lane] = n;
                 }
             }
@@ -332,16 +247,8 @@ DEVI void mlp_fwd_body(const fgnn_mlp_fwd_args A, const int tpg, const int total
                 float hid[16], bl[16], wh[16];
                 load_bias(bl, wm + L::BIAS_F, l, h);
                 load_ops<16>(wh, wm, L::OFF_WH + 16 * (l - 1), lane);
-                if constexpr (DBG) {      // the decision relu1 takes: bit pattern > 0 as a signed integer
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const unsigned long long mk = __ballot(__float_as_int(acc[r]) > 0);
-                        if (lane == 0) {
-                            unsigned *o = (m == 0 ? dbg0 : dbg1) + (((long long)c.g * (DEPTH - 1) + (l - 1)) * 32 + ch_of(r, 0)) * tpg + c.tt;
-                            o[0] = (unsigned)mk;
-                            o[4ll * tpg] = (unsigned)(mk >> 32);       // channel ch_of(r, 1) = ch_of(r, 0) + 4
-                        }
-                    }
+                if constexpr (DBG) {
+                    FGNN_FWD32_EXPORT_RELU(acc, m == 0 ? dbg0 : dbg1, DEPTH - 1, l - 1)
                 }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
@@ -351,43 +258,7 @@ DEVI void mlp_fwd_body(const fgnn_mlp_fwd_args A, const int tpg, const int total
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc = mfma32(wh[r], hid[r], acc);
             }
-            // epilogue: mask, store z, transpose through LDS, per-tile {mean, M2} with lane = channel
-            const int zoff = lane_off<4>(vz[m], c, h);
-            const int zs0 = c.g * vz[m].gs4;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int chl = (r & 3) + 8 * (r >> 2);   // channel minus 4*h
-                const float v = c_valid ? acc[r] : 0.f;
-                buf_store(v, vz[m], zoff, zs0 + chl * vz[m].ld4);
-                tl[(chl + 4 * h) * TLD + j] = v;
-            }
-            // lane (ch = j, h) owns pixels 16h .. 16h+15 of channel ch
-            const float4 *rp = reinterpret_cast<const float4 *>(tl + j * TLD + 16 * h);
-            float4 qv[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) qv[k] = rp[k];
-            float s = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) s += (qv[k].x + qv[k].y) + (qv[k].z + qv[k].w);
-            s += __shfl_xor(s, 32);
-            const float mean = s * inv;
-            const unsigned mh = vmask >> (16 * h);
-            float m2 = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float d0 = ((mh >> (4 * k + 0)) & 1u) ? qv[k].x - mean : 0.f;
-                const float d1 = ((mh >> (4 * k + 1)) & 1u) ? qv[k].y - mean : 0.f;
-                const float d2 = ((mh >> (4 * k + 2)) & 1u) ? qv[k].z - mean : 0.f;
-                const float d3 = ((mh >> (4 * k + 3)) & 1u) ? qv[k].w - mean : 0.f;
-                m2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-            }
-            m2 += __shfl_xor(m2, 32);
-            if (h == 0) {
-                float2 o;
-                o.x = mean;
-                o.y = m2;
-                reinterpret_cast<float2 *>(A.part[m])[((long long)c.g * tpg + c.tt) * FGNN_H + j] = o;
-            }
+            FGNN_FWD32_STATS(acc, vz[m], A.part[m])
         }
         if (lane == 0) A.cnt[(long long)c.g * tpg + c.tt] = cnt;
 
@@ -437,27 +308,16 @@ struct DbgOut {
     unsigned *m[2];
 };
 
+template <int CA, int CB, int NMLP, int DEPTH, bool PK, bool SKIP>
+struct FwdKernels {
+    static auto product() { return mlp_fwd_kernel<CA, CB, NMLP, DEPTH, PK, SKIP>; }
+    static auto dbg() { return mlp_fwd_dbg_kernel<CA, CB, NMLP, DEPTH, PK, SKIP>; }
+};
 template <int CA, int CB, int NMLP, int DEPTH, bool PK = false, bool SKIP = false, bool DBG = false>
 int launch_fwd_impl(const fgnn_mlp_fwd_args *a, int tpg, int total, hipStream_t st, const DbgOut &d) {
     using L = FwdLayout<CA, CB, NMLP, DEPTH>;
-    constexpr int NW = L::NW;
-    constexpr int LDS = (L::LDS_F + (SKIP ? LIVE_LIST_CAP + NW : 0)) * 4;
-    static_assert(LDS <= 160 * 1024, "LDS budget");
-    static LdsAttrCache attr_cache;
-    int grid = (total + NW - 1) / NW;
-    const int cap = a->cu_share == 2 ? 128 : 256;      // 2: half of the CUs (two launches on two streams side by side)
-    if (grid > cap) grid = cap;
-    if (SKIP) grid = FGNN_RANGE_WG;
-    if constexpr (DBG) {
-        (void)fgnn_raise_lds(attr_cache, (const void *)mlp_fwd_dbg_kernel<CA, CB, NMLP, DEPTH, PK, SKIP>, LDS);
-        hipLaunchKernelGGL((mlp_fwd_dbg_kernel<CA, CB, NMLP, DEPTH, PK, SKIP>), dim3(grid), dim3(64 * NW), LDS, st, *a, tpg, total, d.m[0],
-                           d.m[1]);
-    } else {
-        (void)fgnn_raise_lds(attr_cache, (const void *)mlp_fwd_kernel<CA, CB, NMLP, DEPTH, PK, SKIP>, LDS);
-        hipLaunchKernelGGL((mlp_fwd_kernel<CA, CB, NMLP, DEPTH, PK, SKIP>), dim3(grid), dim3(64 * NW), LDS, st, *a, tpg, total);
-    }
-    FGNN_LAUNCH_CHECK();
-    return 0;
+    constexpr int LDS = (L::LDS_F + (SKIP ? LIVE_LIST_CAP + L::NW : 0)) * 4;
+    return launch_fwd32<FwdKernels<CA, CB, NMLP, DEPTH, PK, SKIP>, DBG, L::NW, LDS>(a, tpg, total, SKIP ? FGNN_RANGE_WG : 0, st, d.m[0], d.m[1]);
 }
 template <int CA, int CB, int NMLP, int DEPTH, bool PK = false, bool DBG = false>
 int launch_fwd(const fgnn_mlp_fwd_args *a, int tpg, int total, hipStream_t st, const DbgOut &d) {
@@ -508,29 +368,16 @@ extern "C" int fgnn_debug_fwd_stamps(void *p, int ca, int cb, int nmlp) {
 extern "C" int fgnn_tiles_per_graph(int N) { return (N * N + FGNN_TILE - 1) / FGNN_TILE; }
 
 static int mlp_fwd_entry(const fgnn_mlp_fwd_args *a, void *stream, unsigned *const *dbg) {
-    FGNN_CHECK(a != nullptr, "fgnn_mlp_fwd: null args");
-    FGNN_CHECK(a->G > 0 && a->N > 0, "fgnn_mlp_fwd: bad G=%d N=%d", a->G, a->N);
-    FGNN_CHECK(a->nmlp == 1 || a->nmlp == 2, "fgnn_mlp_fwd: nmlp must be 1 or 2 (got %d)", a->nmlp);
+    if (check_mlp_fwd_common(a, "fgnn_mlp_fwd")) return 1;
     FGNN_CHECK(a->depth >= 1 && a->depth <= FGNN_MAX_DEPTH, "fgnn_mlp_fwd: depth %d not in 1..%d", a->depth, FGNN_MAX_DEPTH);
     const bool pk_a = a->xbits && a->a.C == 2, pk_b = a->xbits && a->b.C == 2;     // that slab's memory is never touched
     FGNN_CHECK((a->a.ptr || pk_a) && a->a.C > 0, "fgnn_mlp_fwd: slab a missing");
     FGNN_CHECK(a->b.C == 0 || a->b.ptr || pk_b, "fgnn_mlp_fwd: slab b has channels but no pointer");
-    FGNN_CHECK(!a->xbits || a->xdeg, "fgnn_mlp_fwd: xbits without xdeg (fgnn_adjacency_degree)");
-    FGNN_CHECK((long long)a->N * a->N <= a->ldz && (pk_a || (long long)a->N * a->N <= a->a.ldp), "fgnn_mlp_fwd: channel stride < N*N");
-    for (int m = 0; m < a->nmlp; ++m) {
-        FGNN_CHECK(a->z[m] && a->part[m], "fgnn_mlp_fwd: missing output %d", m);
+    for (int m = 0; m < a->nmlp; ++m)
         for (int l = 0; l < a->depth; ++l) FGNN_CHECK(a->W[m][l] && a->bias[m][l], "fgnn_mlp_fwd: missing weights mlp %d layer %d", m, l);
-    }
-    FGNN_CHECK(a->cnt, "fgnn_mlp_fwd: missing cnt");
     FGNN_CHECK(!a->ranges || a->nvalid, "fgnn_mlp_fwd: ranges (fgnn_ragged_tile_ranges) only make sense with nvalid");
-    {
-        const long long lim = 0x7fffffffll / 4, G = a->G;
-        FGNN_CHECK(G * a->a.gstride < lim && G * a->b.gstride < lim && G * FGNN_H * a->ldz < lim,
-                   "fgnn_mlp_fwd: a tensor exceeds 2 GiB (32-bit buffer addressing); split the batch");
-    }
     const int tpg = fgnn_tiles_per_graph(a->N);
     const long long total = (long long)a->G * tpg;
-    FGNN_CHECK(total < (1ll << 30), "fgnn_mlp_fwd: too many tiles");
     hipStream_t st = (hipStream_t)stream;
     if (dbg) {          // the decision-exporting twins exist for every depth (depth 1 has no hidden layer: it writes no mask)
         FGNN_CHECK(a->depth == 1 || (dbg[0] && (a->nmlp == 1 || dbg[1])), "fgnn_debug_mlp_fwd_masks: one mask buffer per MLP");

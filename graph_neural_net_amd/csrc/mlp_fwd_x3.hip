@@ -7,7 +7,7 @@
 // layer's v_mfma_f32_32x32x16_bf16, fgnn_bf16.h) and multiplied with the pre-split weight images from LDS: 12 bf16 MFMAs
 // (384 matrix-pipe cycles, running beside the VALU) replace 16 fp32 MFMAs (1024 cycles that block the SIMD's fp32 VALU).
 // Built for the reference's depth 3 and input slabs of 2 / 32 / 32+2 / 32+32 channels; constant-size batches.
-#include "fgnn_tile.h"
+#include "fgnn_fwd32.h"
 #include "fgnn_pack.h"
 #include "fgnn_x3.h"
 
@@ -55,22 +55,12 @@ DEVI void mlp_fwd_x3_body(const fgnn_mlp_fwd_args A, const int tpg, const int to
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int j = lane & 31, h = lane >> 5;
     const int P = A.N * A.N;
-    float *wl = smem;
-    float *tl = smem + L::WEIGHT_F + wv * TILE_F;
-    float *recA = smem + L::WEIGHT_F + NW * TILE_F + wv * L::REC_F, *recB = recA + 128;
-    const View va = make_view(A.a.ptr, A.a.gstride, A.a.ldp, A.G);
-    const View vb = make_view(A.b.ptr, A.b.gstride, A.b.ldp, A.G);
-    PackedSrc ps = {};
-    if constexpr (PK) ps = make_packed_src(A.xbits, A.xdeg, A.G, A.N);
-    View vz[NMLP];
-#pragma unroll
-    for (int m = 0; m < NMLP; ++m) vz[m] = make_view(A.z[m], FGNN_H * A.ldz, A.ldz, A.G);
+    float *wl = smem, *tl = fwd_lds_tile<L>(smem, wv), *recA = fwd_lds_records<L>(smem, wv), *recB = recA + 128;
+    FGNN_FWD32_VIEWS
 
     // contiguous tile range of this workgroup; wave w takes tiles T0 + w, T0 + w + NW, ... (static)
-    const int nwg = gridDim.x;
-    const int q = total_tiles / nwg, rem = total_tiles % nwg;
-    const int T0 = blockIdx.x * q + ((int)blockIdx.x < rem ? (int)blockIdx.x : rem);
-    const int T1 = T0 + q + ((int)blockIdx.x < rem ? 1 : 0);
+    int T0, T1;
+    wg_tile_range<false>(nullptr, total_tiles, T0, T1);
 
     const bool normA = A.a.nrm != nullptr, normB = (CB > 0) && A.b.nrm != nullptr;
     // one memory round trip: the operand image is requested first (into registers), then the first tile and its records
@@ -86,14 +76,8 @@ DEVI void mlp_fwd_x3_body(const fgnn_mlp_fwd_args A, const int tpg, const int to
         load_slab<SA, PK>(xa, va, ps, c, h);
         load_slab<SB, PK>(xb, vb, ps, c, h);
         if (tile < T1 && lane < 32) {
-            if (normA && lane < CA) {
-                ra = reinterpret_cast<const float4 *>(A.a.nrm)[(long long)c.g * A.a.C + lane];
-                ra.z = A.a.beta ? A.a.beta[lane] : 0.f;
-            }
-            if (normB && lane < CB) {
-                rb = reinterpret_cast<const float4 *>(A.b.nrm)[(long long)c.g * A.b.C + lane];
-                rb.z = A.b.beta ? A.b.beta[lane] : 0.f;
-            }
+            if (normA && lane < CA) fetch_record(ra, A.a.nrm, A.a.beta, A.a.C, c.g, lane);
+            if (normB && lane < CB) fetch_record(rb, A.b.nrm, A.b.beta, A.b.C, c.g, lane);
         }
         if (tile < T1) {
             cached_g = c.g;
@@ -113,13 +97,13 @@ DEVI void mlp_fwd_x3_body(const fgnn_mlp_fwd_args A, const int tpg, const int to
         if (c.g != cached_g) {        // wave-uniform; issued before the prefetch (vmcnt is in-order)
             if (lane < 32) {
                 if (normA && lane < CA) {
-                    float4 n = reinterpret_cast<const float4 *>(A.a.nrm)[(long long)c.g * A.a.C + lane];
-                    n.z = A.a.beta ? A.a.beta[lane] : 0.f;
+                    float4 n;
+                    fetch_record(n, A.a.nrm, A.a.beta, A.a.C, c.g, lane);
                     reinterpret_cast<float4 *>(recA)[lane] = n;
                 }
                 if (normB && lane < CB) {
-                    float4 n = reinterpret_cast<const float4 *>(A.b.nrm)[(long long)c.g * A.b.C + lane];
-                    n.z = A.b.beta ? A.b.beta[lane] : 0.f;
+                    float4 n;
+                    fetch_record(n, A.b.nrm, A.b.beta, A.b.C, c.g, lane);
                     reinterpret_cast<float4 *>(recB)[lane] = n;
                 }
             }
@@ -161,58 +145,14 @@ DEVI void mlp_fwd_x3_body(const fgnn_mlp_fwd_args A, const int tpg, const int to
 #pragma unroll
                     for (int r = 0; r < 16; ++r) hid[r] = relu1(acc[r]);
                     if constexpr (DBG) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const unsigned long long mk = __ballot(__float_as_int(acc[r]) > 0);
-                            if (lane == 0) {
-                                unsigned *o = (m == 0 ? dbg0 : dbg1) + (((long long)c.g * (DEPTH - 1) + (l - 1)) * 32 + ch_of(r, 0)) * tpg + c.tt;
-                                o[0] = (unsigned)mk;
-                                o[4ll * tpg] = (unsigned)(mk >> 32);
-                            }
-                        }
+                        FGNN_FWD32_EXPORT_RELU(acc, m == 0 ? dbg0 : dbg1, DEPTH - 1, l - 1)
                     }
                     split16m(H, hid, negI);
                 }
                 load_bias16(acc, wm + L::BIAS_F, l, h);
                 acc = gemm_x3<2, X3_FWD_TERMS>(acc, wm, L::PD, L::OFF_WH + 2 * (l - 1), H, lane);
             }
-            // epilogue: mask, store z, transpose through LDS, per-tile {mean, M2} with lane = channel
-            const int zoff = lane_off<4>(vz[m], c, h);
-            const int zs0 = c.g * vz[m].gs4;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int chl = (r & 3) + 8 * (r >> 2);   // channel minus 4*h
-                const float v = c_valid ? acc[r] : 0.f;
-                buf_store(v, vz[m], zoff, zs0 + chl * vz[m].ld4);
-                tl[(chl + 4 * h) * TLD + j] = v;
-            }
-            // lane (ch = j, h) owns pixels 16h .. 16h+15 of channel ch
-            const float4 *rp = reinterpret_cast<const float4 *>(tl + j * TLD + 16 * h);
-            float4 qv[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) qv[k] = rp[k];
-            float s = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) s += (qv[k].x + qv[k].y) + (qv[k].z + qv[k].w);
-            s += __shfl_xor(s, 32);
-            const float mean = s * inv;
-            const unsigned mh = vmask >> (16 * h);
-            float m2 = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float d0 = ((mh >> (4 * k + 0)) & 1u) ? qv[k].x - mean : 0.f;
-                const float d1 = ((mh >> (4 * k + 1)) & 1u) ? qv[k].y - mean : 0.f;
-                const float d2 = ((mh >> (4 * k + 2)) & 1u) ? qv[k].z - mean : 0.f;
-                const float d3 = ((mh >> (4 * k + 3)) & 1u) ? qv[k].w - mean : 0.f;
-                m2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-            }
-            m2 += __shfl_xor(m2, 32);
-            if (h == 0) {
-                float2 o;
-                o.x = mean;
-                o.y = m2;
-                reinterpret_cast<float2 *>(A.part[m])[((long long)c.g * tpg + c.tt) * FGNN_H + j] = o;
-            }
+            FGNN_FWD32_STATS(acc, vz[m], A.part[m])
         }
         if (lane == 0) A.cnt[(long long)c.g * tpg + c.tt] = cnt;
         tile = next;
@@ -230,24 +170,15 @@ __global__ __launch_bounds__(64 * NWT, NWT / 4) void mlp_fwd_x3_dbg_kernel(const
     mlp_fwd_x3_body<CA, CB, NMLP, PK, NWT, true>(A, tpg, total_tiles, d0, d1);
 }
 
+template <int CA, int CB, int NMLP, bool PK, int NWT>
+struct FwdX3Kernels {
+    static auto product() { return mlp_fwd_x3_kernel<CA, CB, NMLP, PK, NWT>; }
+    static auto dbg() { return mlp_fwd_x3_dbg_kernel<CA, CB, NMLP, PK, NWT>; }
+};
 template <int CA, int CB, int NMLP, bool PK, int NWT, bool DBG = false>
 int launch_fwd_x3(const fgnn_mlp_fwd_args *a, int tpg, int total, hipStream_t st, unsigned *d0 = nullptr, unsigned *d1 = nullptr) {
-    using L = FwdX3Layout<CA, CB, NMLP, NWT>;
-    constexpr int LDS = L::LDS_F * 4;
-    static_assert(LDS <= 160 * 1024, "LDS budget");
-    static LdsAttrCache attr_cache;
-    int grid = (total + NWT - 1) / NWT;
-    const int cap = a->cu_share == 2 ? 128 : 256;
-    if (grid > cap) grid = cap;
-    if constexpr (DBG) {
-        (void)fgnn_raise_lds(attr_cache, (const void *)mlp_fwd_x3_dbg_kernel<CA, CB, NMLP, PK, NWT>, LDS);
-        hipLaunchKernelGGL((mlp_fwd_x3_dbg_kernel<CA, CB, NMLP, PK, NWT>), dim3(grid), dim3(64 * NWT), LDS, st, *a, tpg, total, d0, d1);
-    } else {
-        (void)fgnn_raise_lds(attr_cache, (const void *)mlp_fwd_x3_kernel<CA, CB, NMLP, PK, NWT>, LDS);
-        hipLaunchKernelGGL((mlp_fwd_x3_kernel<CA, CB, NMLP, PK, NWT>), dim3(grid), dim3(64 * NWT), LDS, st, *a, tpg, total);
-    }
-    FGNN_LAUNCH_CHECK();
-    return 0;
+    constexpr int LDS = FwdX3Layout<CA, CB, NMLP, NWT>::LDS_F * 4;
+    return launch_fwd32<FwdX3Kernels<CA, CB, NMLP, PK, NWT>, DBG, NWT, LDS>(a, tpg, total, 0, st, d0, d1);
 }
 
 constexpr int FWD_X3_WAVES = 16;
@@ -255,9 +186,7 @@ constexpr int FWD_X3_WAVES = 16;
 }  // namespace
 
 static int mlp_fwd_x3_entry(const fgnn_mlp_fwd_args *a, void *stream, unsigned *const *dbg) {
-    FGNN_CHECK(a != nullptr, "fgnn_mlp_fwd_x3: null args");
-    FGNN_CHECK(a->G > 0 && a->N > 0, "fgnn_mlp_fwd_x3: bad G=%d N=%d", a->G, a->N);
-    FGNN_CHECK(a->nmlp == 1 || a->nmlp == 2, "fgnn_mlp_fwd_x3: nmlp must be 1 or 2 (got %d)", a->nmlp);
+    if (check_mlp_fwd_common(a, "fgnn_mlp_fwd_x3")) return 1;
     FGNN_CHECK(mlp_x3_supported(a->a.C, a->b.C, a->depth, a->nmlp),
                "fgnn_mlp_fwd_x3: built for depth 3 and 2, 32, 32+2, 32+32 input channels (got depth %d, %d + %d, nmlp %d); use fgnn_mlp_fwd",
                a->depth, a->a.C, a->b.C, a->nmlp);
@@ -265,18 +194,8 @@ static int mlp_fwd_x3_entry(const fgnn_mlp_fwd_args *a, void *stream, unsigned *
     FGNN_CHECK(!a->ranges, "fgnn_mlp_fwd_x3: no padding-tile skipping (ranges); use fgnn_mlp_fwd for ragged batches");
     const bool pk_a = a->xbits && a->a.C == 2, pk_b = a->xbits && a->b.C == 2;
     FGNN_CHECK((a->a.ptr || pk_a) && (a->b.C == 0 || a->b.ptr || pk_b), "fgnn_mlp_fwd_x3: slab pointer missing");
-    FGNN_CHECK(!a->xbits || a->xdeg, "fgnn_mlp_fwd_x3: xbits without xdeg (fgnn_adjacency_degree)");
-    FGNN_CHECK((long long)a->N * a->N <= a->ldz && (pk_a || (long long)a->N * a->N <= a->a.ldp), "fgnn_mlp_fwd_x3: channel stride < N*N");
-    for (int m = 0; m < a->nmlp; ++m) FGNN_CHECK(a->z[m] && a->part[m], "fgnn_mlp_fwd_x3: missing output %d", m);
-    FGNN_CHECK(a->cnt, "fgnn_mlp_fwd_x3: missing cnt");
-    {
-        const long long lim = 0x7fffffffll / 4, G = a->G;
-        FGNN_CHECK(G * a->a.gstride < lim && G * a->b.gstride < lim && G * FGNN_H * a->ldz < lim,
-                   "fgnn_mlp_fwd_x3: a tensor exceeds 2 GiB (32-bit buffer addressing); split the batch");
-    }
     const int tpg = fgnn_tiles_per_graph(a->N);
     const long long total = (long long)a->G * tpg;
-    FGNN_CHECK(total < (1ll << 30), "fgnn_mlp_fwd_x3: too many tiles");
     hipStream_t st = (hipStream_t)stream;
     const int ca = a->a.C, cb = a->b.C;
     constexpr int W = FWD_X3_WAVES;
