@@ -281,6 +281,7 @@ _SIGNATURES = {
     'fgnn_tiles_per_graph16': [_I, _I],
     'fgnn_to_bf16': [_VP, _VP, _I, _I, _I, _I, _VP, _LL, _LL, _VP],
     'fgnn_from_bf16': [_VP, _LL, _LL, _I, _I, _I, _I, _VP, _VP],
+    'fgnn_to_bf16_pad': [_VP, _VP, _I, _I, _I, _I, _I, _VP, _LL, _VP],
     'fgnn_pack16_floats': [_I, _I, _I, _I, _I],
     'fgnn_pack16_operands': [_VP, _I, _VP],
     'fgnn_mlp_fwd16': [C.POINTER(MlpFwd16Args), _VP],
@@ -309,8 +310,10 @@ EXPORTS = tuple(_SIGNATURES)
 _lib = None
 
 
-def load():
-    """Load the HIP library (once).  Raises RuntimeError if it has not been built."""
+def load(allow_missing=False):
+    """Load the HIP library (once).  Raises RuntimeError if it has not been built.
+    allow_missing=True (A/B tools that load an OLDER build through FGNN_LIB; must be the process's first load): entry points the
+    library lacks are left unbound -- calling one raises AttributeError -- instead of failing the load."""
     global _lib
     if _lib is not None:
         return _lib
@@ -321,6 +324,8 @@ def load():
             'There is no CPU fallback.' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in _SIGNATURES.items():
+        if allow_missing and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, C.c_int)

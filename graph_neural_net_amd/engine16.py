@@ -38,8 +38,9 @@ class FgnnEngineBF16(EngineBase):
         self.struct1 = block1 == 'structured' and bool(lib.fgnn_block1_struct_supported(N, layout.depth, layout.c0))
         if layout.depth != 3:
             raise RuntimeError('the bf16 kernels are built for depth_of_mlp = 3 (got %d)' % layout.depth)
-        if layout.c0 != 2:
-            raise RuntimeError('the bf16 kernels are built for original_features_num = 2 (got %d)' % layout.c0)
+        if layout.c0 not in (2, 32):
+            raise RuntimeError('the bf16 kernels are built for an input slab of 2 or 32 channels (got %d): inputs of 3..31 channels '
+                               'run zero-padded on a 32-channel layout (Network._padded_layout)' % layout.c0)
         if N > 256:
             raise RuntimeError('the bf16 per-channel matmul handles N <= 256 (got %d)' % N)
         super().__init__(layout, G, N, device, ragged)
@@ -51,7 +52,7 @@ class FgnnEngineBF16(EngineBase):
         f32 = dict(dtype=torch.float32, device=device)
         bf = dict(dtype=torch.bfloat16, device=device)
         self._act = act = lambda: torch.empty(G * 32 * self.ldp, **bf)
-        self.x16 = torch.empty(G * 2 * self.ldp, **bf)
+        self.x16 = torch.empty(G * layout.c0 * self.ldp, **bf)      # block 1's raw input slab: 2 or 32 channels
         self.z = {(k, j): act() for k in range(1, K + 1) for j in (1, 2, 3)}
         self.mult = {k: act() for k in range(1, K + 1)}
         self.part = [torch.empty(G * self.tpg * 32 * 2, **f32) for _ in range(2)]
@@ -68,7 +69,8 @@ class FgnnEngineBF16(EngineBase):
     # ------------------------------------------------------------------ helpers
     def _slab_in(self, k, params):
         if k == 1:
-            return _lib.make_slab16(self.x16, 2 * self.ldp, self.ldp, 2)
+            c0 = self.layout.c0
+            return _lib.make_slab16(self.x16, c0 * self.ldp, self.ldp, c0)
         rec = self.layout.mlp[(k - 1, 3)]
         return _lib.make_slab16(self.z[(k - 1, 3)], 32 * self.ldp, self.ldp, 32, nrm=self.nrm[(k - 1, 3)],
                                 beta=self._w(params, rec['gn_b']))
@@ -114,7 +116,9 @@ class FgnnEngineBF16(EngineBase):
 
     # ------------------------------------------------------------------ forward
     def embed(self, params, x, nvalid=None, bits=None):
-        """x: (G, 2, N, N) contiguous fp32 device tensor (0/1 adjacency + degrees: exact in bf16 for N <= 256) -- or bits:
+        """x: (G, c, N, N) contiguous fp32 device tensor with c <= layout.c0 (2: 0/1 adjacency + degrees, exact in bf16 for N <= 256;
+        32-channel layouts take any 1..32 channels, e.g. the four spectral ones: one launch, fgnn_to_bf16_pad, rounds them into the
+        32-channel slab and writes the missing channels as zeros -- no fp32 staging buffer) -- or bits:
         (G, N, ceil(N/32)) int32 words of the bit-packed adjacency (the input form of FgnnEngine.embed(bits=...)); with
         block1='structured' block 1 then runs on the class tables (csrc/block1_struct.hip).
         LIFETIME: as FgnnEngine.embed -- bits and an int32 device nvalid of G entries are read in place by this forward and by the
@@ -127,16 +131,20 @@ class FgnnEngineBF16(EngineBase):
             self._check_bits(bits)
             if not self.struct1:
                 raise RuntimeError("FgnnEngineBF16.embed: bits= needs block1='structured' (N <= 256, depth 3, 2 input channels)")
-        elif x.shape != (self.G, L.c0, self.N, self.N) or not x.is_contiguous() or x.dtype != torch.float32:
-            raise RuntimeError('FgnnEngineBF16.embed: expected contiguous fp32 %s, got %s %s'
-                               % ((self.G, L.c0, self.N, self.N), tuple(x.shape), x.dtype))
+        elif x.dim() != 4 or (x.shape[0], x.shape[2], x.shape[3]) != (self.G, self.N, self.N) or not 1 <= x.shape[1] <= L.c0 \
+                or not x.is_contiguous() or x.dtype != torch.float32:
+            raise RuntimeError('FgnnEngineBF16.embed: expected contiguous fp32 %s with 1 <= c <= %d, got %s %s'
+                               % ((self.G, 'c', self.N, self.N), L.c0, tuple(x.shape), x.dtype))
         self.xbits = bits
         st = _lib.stream_ptr()
         if self.ranges is not None:
             _lib.call('fgnn_ragged_tile_ranges16', _lib.ptr(self.nvalid), self.G, self.N, self.ldr, _lib.ptr(self.ranges), st)
-        if bits is None:
+        if bits is None and x.shape[1] == L.c0 == 2:
             _lib.call('fgnn_to_bf16', _lib.ptr(x), self._nv(), self.G, 2, self.N, self.ldr, _lib.ptr(self.x16),
                       2 * self.ldp, self.ldp, st)
+        elif bits is None:      # fewer channels than the slab, or the 32-channel slab: convert and zero-fill in one pass
+            _lib.call('fgnn_to_bf16_pad', _lib.ptr(x), self._nv(), self.G, x.shape[1], L.c0, self.N, self.ldr, _lib.ptr(self.x16),
+                      self.ldp, st)
         # the structured block 1's first launch carries the packing as extra workgroups (fgnn_block1_struct_fwd16_pack: one launch less)
         pack_in_struct = bits is not None and self.PACK_IN_STRUCT and len(self._packs) <= _lib.MAX_PACK_JOBS
         if not pack_in_struct:

@@ -336,6 +336,9 @@ class Network(nn.Module):
         P = self._pad
         if P is None or P['c0p'] == P['c0']:
             return x
+        if getattr(self, 'precision', 'fp32') == 'bf16':
+            self._check_channels(x)
+            return x        # the bf16 engine rounds the c0 channels into its own 32-channel slab and zero-fills the rest (fgnn_to_bf16_pad)
         shape = (x.shape[0], P['c0p'], x.shape[2], x.shape[3])
         eng = self._engine_for_shape(x.shape[0], x.shape[-1], nvalid is not None, x.device, grad)
         buf = getattr(eng, '_xpad', None)
@@ -343,6 +346,13 @@ class Network(nn.Module):
             buf = eng._xpad = torch.zeros(shape, dtype=torch.float32, device=x.device)
         buf[:, :P['c0']].copy_(x)
         return buf
+
+    def _check_channels(self, x):
+        """The bf16 engine takes any channel count up to its slab's: the module still insists on its own original_features_num."""
+        want = self._pad['c0'] if self._pad is not None else self._layout.c0
+        if x.shape[1] != want:
+            raise RuntimeError('Network: the input has %d channels, the model was built with original_features_num = %d'
+                               % (x.shape[1], want))
 
     def _crop_embedding(self, E):
         if self._pad is None or self._pad['cout'] == E.shape[1]:
@@ -430,15 +440,19 @@ class Network(nn.Module):
     def fused_embedding(self, x):
         """x: (G, c0, N, N) tensor or MaskedTensor -> node embeddings (G, C, N)."""
         lay = self._standard_layout()
-        if lay is None:
-            if getattr(self, 'precision', 'fp32') == 'bf16':
-                raise RuntimeError('Network: the bf16 path is the fused engine (original_features_num = 2, in_features = '
-                                   'out_features = 32); this graph runs through the per-layer fp32 modules')
+        bf16 = getattr(self, 'precision', 'fp32') == 'bf16'
+        if lay is None or (bf16 and lay.depth != 3):
+            if bf16:
+                raise RuntimeError('Network: the bf16 path is the fused engine (original_features_num, in_features and out_features '
+                                   'up to 32, depth_of_mlp = 3); a graph with a width above 32 or another depth runs through the '
+                                   'per-layer fp32 modules only')
             return self.forward({'input': x})['ne/suffix']
         t, nvalid = (x.tensor, x.nvalid) if isinstance(x, MaskedTensor) else (x, None)
         if not t.is_cuda:
             raise RuntimeError('graph_neural_net_amd only runs on the GPU (input is on %s)' % (t.device,))
         self._bind_flat()
+        if bf16:
+            self._check_channels(t)
         if torch.is_grad_enabled() and (any(p.requires_grad for p in self._param_list) or t.requires_grad):
             if self._params_as_inputs():
                 e = _EmbedFnParams.apply(self, t.contiguous(), nvalid, *self._param_list)

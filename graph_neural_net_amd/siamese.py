@@ -107,6 +107,12 @@ class Siamese_Node_Exp(nn.Module):
         self.node_embedder.input_form = input_form
         self.lr, self.scheduler_decay, self.scheduler_step, self.lr_stop = lr, scheduler_decay, scheduler_step, lr_stop
 
+    def half(self):
+        """The reference's 16-bit switch on the whole model (pl.Trainer(precision=16), commander_explore.py:120-122): selects the bf16
+        engine of the node embedder (Network.half) and returns self.  The parameters stay fp32 masters; nothing is cast."""
+        self.node_embedder.half()
+        return self
+
     def forward(self, x1, x2):
         """x1, x2: (bs, features, n, n) (or MaskedTensors of ragged graphs, both sides sharing the
         per-pair vertex counts) -> raw scores (bs, n, n)."""
@@ -223,7 +229,8 @@ class Siamese_Node_Exp(nn.Module):
         gran = max(1, int(self.RAGGED_GRANULE))
         N = -(-nmax // gran) * gran if ragged else nmax
         pad = net._pad
-        c0e = pad['c0p'] if pad is not None else t1.shape[1]
+        # (the bf16 engine takes the batch's own channels: its input conversion writes the padded slab, fgnn_to_bf16_pad)
+        c0e = pad['c0p'] if pad is not None and getattr(net, 'precision', 'fp32') != 'bf16' else t1.shape[1]
         if tuple(t1.shape) != tuple(t2.shape):
             raise RuntimeError('fused_step: the two sides of the batch have different (padded) shapes %s / %s; use the module path '
                                '`loss = model.loss(model(x1, x2)); loss.backward()`' % (tuple(t1.shape), tuple(t2.shape)))
@@ -243,6 +250,8 @@ class Siamese_Node_Exp(nn.Module):
                 st['bits'] = torch.zeros(2 * B, N, (N + 31) // 32, dtype=torch.int32, device=dev)
                 st['flag'] = self.__dict__.setdefault('_tr_flags', {}).setdefault(dev, torch.zeros(1, dtype=torch.int32, device=dev))
         c0 = t1.shape[1]
+        if getattr(net, 'precision', 'fp32') == 'bf16':
+            net._check_channels(t1)
         first_of_shape = st['calls'] == 0
         st['calls'] += 1
         if ragged:

@@ -80,17 +80,38 @@ class FgnnTrainer:
     @classmethod
     def from_module(cls, model, lr=None, capture=True, max_grad_norm=None, skip_nonfinite=False):
         """The fused training step for a `Siamese_Node_Exp` built through the reference's own surface
-        (models/trainers.py:20-58): the trainer works IN PLACE on the module's flat parameter buffer, so the module
-        (its `state_dict`, its eager forward) always sees the trained weights, and `capture=True` gives a reference user the
-        replayed-graph step instead of ~40 host launches per step.  Standard node_embedding graphs only."""
+        (models/trainers.py:20-58): the trainer works IN PLACE on the module's flat parameter buffer (a padded 16-bit module: on its
+        padded image, see below), so the module (its `state_dict`, its eager forward) always sees the trained weights, and `capture=True` gives a reference user the
+        replayed-graph step instead of ~40 host launches per step.  Standard node_embedding graphs only.
+        A 16-bit module narrower than the engine (`model.half()` with original_features_num 1 or 3..31, widths below 32) trains on its
+        zero-padded image (Network._padded_layout): layout, parameters, Adam moments and checkpoints of the trainer are the padded
+        ones -- the padded entries get exact zero gradients and stay zero -- and every step ends with one gather of the trained
+        values back into the module's flat buffer (one eager launch after the step, outside a captured graph).  `tr.params` then IS
+        the module's padded image (Network._pad['pflat']), which every forward of the module rewrites from the module's own
+        parameters: the two agree after every train_step, but a value written into `tr.params` by anything else than a step is lost
+        at the module's next forward (load a checkpoint into the MODULE, not into such a trainer).  train_step / eval_step take the
+        module's own (B, c, N, N) batches."""
         net = model.node_embedder
         lay = net._standard_layout()
-        if lay is None or net._pad is not None:
-            raise RuntimeError('FgnnTrainer.from_module: the module is not the standard node_embedding graph '
-                               '(original_features_num 2 or 32, in_features = out_features = 32)')
+        precision = getattr(net, 'precision', 'fp32')
+        pad = net._pad
+        if lay is None or (pad is not None and precision != 'bf16'):
+            raise RuntimeError('FgnnTrainer.from_module: the module is not a node_embedding graph the fused trainer runs: fp32 needs '
+                               'original_features_num 2 or 32 and in_features = out_features = 32; 16-bit (model.half()) takes '
+                               'original_features_num, in_features and out_features up to 32; depth_of_mlp = 3 in 16-bit')
         net._bind_flat()
-        return cls(lay, net._flat, lr=model.lr if lr is None else lr, capture=capture, precision=getattr(net, 'precision', 'fp32'),
-                   input_form=getattr(net, 'input_form', 'dense'), max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+        tr = cls(lay, net._flat if pad is None else net._engine_params(), lr=model.lr if lr is None else lr, capture=capture,
+                 precision=precision, input_form=getattr(net, 'input_form', 'dense'), max_grad_norm=max_grad_norm,
+                 skip_nonfinite=skip_nonfinite)
+        if pad is not None:
+            tr._module = net
+        return tr
+
+    def _sync_module(self):
+        """from_module on a padded module: the trained values back into the module's own flat buffer (one gather launch)."""
+        net = getattr(self, '_module', None)
+        if net is not None:
+            torch.index_select(self.params, 0, net._pad['idx'], out=net._flat)
 
     @property
     def grad_norm(self):
@@ -131,6 +152,7 @@ class FgnnTrainer:
             self.opt.t += 1
         else:
             self.opt.step_dev(self.grads)
+        self._sync_module()
         return (self._loss_sum / self._nodes).reshape(())
 
     # ------------------------------------------------------------------ ragged batches, bucketed by size
@@ -280,6 +302,10 @@ class FgnnTrainer:
             self.opt.t = t0                               # a capture does not execute an update
             st = self._graphs[key] = (xs, g_model, g_opt, scores, B)
         xs, g_model, g_opt, scores, B = st
+        if tuple(x1.shape[1:]) != tuple(xs.shape[1:]) or tuple(x2.shape) != tuple(x1.shape):
+            raise RuntimeError('FgnnTrainer: the captured step of (B, N) = (%d, %d) was recorded for batches of shape %s per side, got %s / '
+                               '%s; a trainer captures one channel count per (B, N)' % (B, N, (B,) + tuple(xs.shape[1:]),
+                                                                                         tuple(x1.shape), tuple(x2.shape)))
         if x1.data_ptr() != xs.data_ptr():              # (train_step(input_form='tensor_representation') packs straight into xs)
             xs[:B].copy_(x1)
             xs[B:].copy_(x2)
@@ -288,6 +314,7 @@ class FgnnTrainer:
             self.opt.sync_hyper_parameters(grad_scale=None)
             g_model.replay()
             self.opt.t += 1
+            self._sync_module()
             return (self._loss_sum / self._nodes).reshape(()), scores
         g_model.replay()
         return self._reduce_and_update(opt_graph=g_opt), scores
@@ -377,7 +404,8 @@ class FgnnTrainer:
         return evaluate_scores(scores, nvalid=nvalid, labels=labels, meter=meter, live=live, hungarian=hungarian)
 
     def eval_step(self, x1, x2, nvalid=None, labels=None, meter=None, live=None, hungarian=True):
-        """eval_step_bits for dense batches: x1, x2 (B, c0, N, N) fp32 on the GPU, through the generic kernels."""
+        """eval_step_bits for dense batches: x1, x2 (B, c0, N, N) fp32 on the GPU, through the generic kernels (precision='bf16' with
+        a 32-channel layout: any 1..32 channels, as train_step)."""
         if x1.dim() != 4 or x1.shape != x2.shape or not x1.is_cuda:
             raise RuntimeError('FgnnTrainer.eval_step: expected two (B, c0, N, N) device tensors, got %s / %s'
                                % (tuple(x1.shape), tuple(x2.shape)))
@@ -427,7 +455,8 @@ class FgnnTrainer:
         return history
 
     def train_step(self, x1, x2, nvalid=None):
-        """x1, x2: (B, c0, N, N) local shard on the GPU.  Returns (loss of the global batch as a device
+        """x1, x2: (B, c0, N, N) local shard on the GPU (precision='bf16' with a 32-channel layout: any 1..32 channels, e.g. the four
+        spectral ones; the engine's input conversion zero-fills the rest).  Returns (loss of the global batch as a device
         scalar, scores of the local shard)."""
         if self.input_form == 'tensor_representation' and x1.dim() == 4 and x1.shape[1] == 2 and self.layout.c0 == 2 \
                 and x1.dtype == torch.float32 and x1.shape == x2.shape:

@@ -624,6 +624,11 @@ int fgnn_tiles_per_graph16(int N, int ldr);
 int fgnn_to_bf16(const float *x, const int *nvalid, int G, int C, int N, int ldr, void *y, long long gstride, long long ldp,
                  void *stream);
 int fgnn_from_bf16(const void *y, long long gstride, long long ldp, int G, int C, int N, int ldr, float *x, void *stream);
+/* fp32 (G, c, N, N) contiguous  ->  the bf16 input slab of block 1 in one pass: CP = 2 or 32 channels (the slab's width, stated
+ * by the caller), 1 <= c <= CP, (G, CP, ldp) with gstride = CP * ldp.  Channels < c: round-to-nearest-even inside the graph's n_g x n_g corner (nvalid, or N);
+ * channels >= c, the ragged padding, the pitch columns and the tail of every channel up to ldp: exact +0.  Nothing outside the
+ * corner of x is read.  ldr: multiple of 8, ldp: multiple of 64 (the engine's pitches); y 16-byte aligned. */
+int fgnn_to_bf16_pad(const float *x, const int *nvalid, int G, int c, int CP, int N, int ldr, void *y, long long ldp, void *stream);
 
 /* operand images of the bf16 MLP kernels (weights rounded to bf16, biases fp32), packed once per step.
  * kind 0 = forward image (nmlp MLPs back to back), kind 1 = backward image (one MLP, W[0] / bias[0]). */
