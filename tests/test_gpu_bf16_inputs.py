@@ -378,13 +378,16 @@ def _digest(*tensors):
     return h.hexdigest()
 
 
-def c2_digests():
-    """{case: sha256 of (scores, loss, flat gradient)} of the 2-channel bf16 engine: tests/golden/make_bf16_c2_digest.py records them."""
+def c2_digests(pair_bwd=True):
+    """{case: sha256 of (scores, loss, flat gradient)} of the 2-channel bf16 engine: tests/golden/make_bf16_c2_digest.py records them.
+    pair_bwd=False: the dense cases with PAIR_BWD off on the engine, i.e. mlp1 and mlp2 of a block as two fgnn_mlp_bwd16 launches --
+    the only way to the kernels mlp_bwd16<2,0,3> and <32,0,3> without tile ranges (a ragged batch runs their SKIP twins)."""
     from graph_neural_net_amd import synthetic
     out = {}
     lay = ParamLayout(2, 2, 32, 32, 3)
     params = lay.init_flat(3, DEV)
-    for name, N, B, nvalid in (('dense_n33_b2', 33, 2, None), ('dense_n8_b1', 8, 1, None), ('ragged_n24_b3', 24, 3, [24, 7, 15])):
+    cases = (('dense_n33_b2', 33, 2, None), ('dense_n8_b1', 8, 1, None), ('ragged_n24_b3', 24, 3, [24, 7, 15]))
+    for name, N, B, nvalid in cases if pair_bwd else cases[:2]:
         x1, x2 = synthetic.make_batch(500 + N, B, N, 'ErdosRenyi', 0.3, 0.05)
         x = torch.cat([x1, x2]).contiguous().to(DEV)
         nv = None
@@ -395,6 +398,7 @@ def c2_digests():
             nv = torch.tensor(nvalid * 2, dtype=torch.int32, device=DEV)
         grads = torch.zeros_like(params)
         eng = FgnnEngineBF16(lay, 2 * B, N, DEV, ragged=nvalid is not None)
+        eng.PAIR_BWD = pair_bwd
         scores, loss = eng.step(params, grads, x, nvalid=nv)
         torch.cuda.synchronize()
         out[name] = _digest(scores, loss, grads)
@@ -405,6 +409,16 @@ def test_two_channel_engine_keeps_its_bits():
     """Recorded with the library of the commit before the 32-channel input slab existed."""
     want = json.load(open(os.path.join(GOLDEN, 'bf16_c2_digest.json')))
     assert c2_digests() == want
+
+
+def test_two_channel_engine_keeps_its_bits_without_the_pair_launch():
+    """The two dense cases with the single-MLP backward launches (mlp_bwd16<2,0,3>, <32,0,3> without tile ranges).  Recorded with the
+    library of commit 0ebc75b, the last one before these two kernels and their pair twin took their common tile body from
+    fgnn_bwd16.h as macros: tests/golden/make_bf16_c2_digest.py nopair.  (With 84 and 2 tiles for 256 workgroups no workgroup sums
+    two tiles, so the order of the fp32 sums is the pair launch's and the recorded digests equal those of the test above.)"""
+    want = json.load(open(os.path.join(GOLDEN, 'bf16_c2_nopair_digest.json')))
+    assert sorted(want) == ['dense_n33_b2', 'dense_n8_b1']
+    assert c2_digests(pair_bwd=False) == want
 
 
 def test_refusals_keep_their_ground():
