@@ -211,6 +211,10 @@ _SIGNATURES = {
     'fgnn_score_row_blocks': [_I, _I],
     'fgnn_score_ce_fwd_blocks': [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP],
     'fgnn_score_ce_bwd': [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP],
+    'fgnn_score_ce_fwd_blocks_labels': [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP],
+    'fgnn_score_ce_bwd_labels': [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP],
+    'fgnn_ce_fwd_labels': [_VP, _VP, _VP, _I, _I, _VP, _VP, _VP],
+    'fgnn_ce_bwd_labels': [_VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP],
     'fgnn_inv_node_count': [_VP, _I, _VP, _VP],
     'fgnn_score_bwd': [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP],
     'fgnn_ce_fwd': [_VP, _VP, _I, _I, _VP, _VP, _VP],
@@ -276,6 +280,7 @@ _SIGNATURES = {
     'fgnn_accuracy_max_labels': [_VP, _VP, _VP, _I, _I, _VP, _VP],
     'fgnn_spectral_features': [_VP, _VP, _I, _I, _I, _VP, _I, _VP],
     'fgnn_eval_pairs': [_VP, _VP, _VP, _I, _I, _VP, _LL, _I, _VP, _VP, _VP],
+    'fgnn_eval_pairs_labels': [_VP, _VP, _VP, _I, _I, _VP, _LL, _I, _VP, _VP, _VP],
     'fgnn_eval_fold': [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP],
     # ---- bf16 path ----
     'fgnn_tiles_per_graph16': [_I, _I],

@@ -23,10 +23,11 @@ DEVI int clamp_nv(const int *nvalid, int b, int N) {
 // N -- and a row has the same lse in any batch, at any position.
 // The arg-max is the rule of fgnn_accuracy_max: first maximum on ties, NaN above every number (the first NaN wins), column 0 for
 // a row of -inf.  Its value doubles as the row maximum m of the lse: a NaN there makes the lse NaN, which exp(NaN - m) would as well.
-template <int W>
-__global__ __launch_bounds__(EVAL_THREADS) void eval_pairs_kernel(const float *scores, const int *nvalid, const int *labels, int B, int N,
-                                                                  float *cost, long long cost_bstride, int cost_ld, float *row_ce,
-                                                                  int *row_hit) {
+// LCE (fgnn_eval_pairs_labels): the target of the cross-entropy is the row's label as well: row_ce = lse - s[i, t_i], and 0 for a
+// row whose label lies outside [0, n_b) (no target); row_hit and the cost corner are those of the plain kernel.
+template <int W, bool LCE>
+DEVI void eval_pairs_body(const float *scores, const int *nvalid, const int *labels, int B, int N, float *cost, long long cost_bstride,
+                          int cost_ld, float *row_ce, int *row_hit) {
     const int sub = threadIdx.x & (W - 1);
     const long long t = (long long)blockIdx.x * (EVAL_THREADS / W) + threadIdx.x / W;      // row index over (b, i)
     const bool inside = t < (long long)B * N;
@@ -65,9 +66,29 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_pairs_kernel(const float *s
     float *crow = cost + (long long)b * cost_bstride + (long long)i * cost_ld;
     for (int j = sub; j < n; j += W) crow[j] = lse - row[j];
     if (live && sub == 0) {
-        row_ce[t] = lse - row[i];
-        row_hit[t] = bj == (labels ? labels[t] : i) ? 1 : 0;
+        if (LCE) {
+            const int ti = labels[t];
+            row_ce[t] = ti >= 0 && ti < nb ? lse - row[ti] : 0.f;
+            row_hit[t] = bj == ti ? 1 : 0;
+        } else {
+            row_ce[t] = lse - row[i];
+            row_hit[t] = bj == (labels ? labels[t] : i) ? 1 : 0;
+        }
     }
+}
+
+template <int W>
+__global__ __launch_bounds__(EVAL_THREADS) void eval_pairs_kernel(const float *scores, const int *nvalid, const int *labels, int B, int N,
+                                                                  float *cost, long long cost_bstride, int cost_ld, float *row_ce,
+                                                                  int *row_hit) {
+    eval_pairs_body<W, false>(scores, nvalid, labels, B, N, cost, cost_bstride, cost_ld, row_ce, row_hit);
+}
+
+template <int W>
+__global__ __launch_bounds__(EVAL_THREADS) void eval_pairs_labels_kernel(const float *scores, const int *nvalid, const int *labels, int B,
+                                                                         int N, float *cost, long long cost_bstride, int cost_ld,
+                                                                         float *row_ce, int *row_hit) {
+    eval_pairs_body<W, true>(scores, nvalid, labels, B, N, cost, cost_bstride, cost_ld, row_ce, row_hit);
 }
 
 // One workgroup of four waves.  Wave w takes the pairs 4 c + w of chunk c: lane l adds the rows l, l + 64, ... of the pair in
@@ -145,6 +166,25 @@ extern "C" int fgnn_eval_pairs(const float *scores, const int *nvalid, const int
         hipLaunchKernelGGL(eval_pairs_kernel<WAVE>, dim3((unsigned)wgs), dim3(EVAL_THREADS), 0, (hipStream_t)stream, scores, nvalid,
                            labels, B, N, cost, cost_bstride, cost_ld, row_ce, row_hit);
     }
+    FGNN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int fgnn_eval_pairs_labels(const float *scores, const int *nvalid, const int *labels, int B, int N, float *cost,
+                                      long long cost_bstride, int cost_ld, float *row_ce, int *row_hit, void *stream) {
+    FGNN_CHECK(scores && labels && cost && row_ce && row_hit && B > 0 && N > 0, "fgnn_eval_pairs_labels: bad arguments");
+    FGNN_CHECK(N <= FGNN_LSAP_MAX_N, "fgnn_eval_pairs_labels: at most %d vertices per graph (got %d)", FGNN_LSAP_MAX_N, N);
+    FGNN_CHECK(cost_ld >= N && cost_bstride >= (long long)N * cost_ld, "fgnn_eval_pairs_labels: cost strides smaller than the matrices");
+    const long long rows = (long long)B * N;
+    const int per = N <= 16 ? EVAL_THREADS / 16 : EVAL_THREADS / WAVE;
+    const long long wgs = (rows + per - 1) / per;
+    FGNN_CHECK(wgs <= 0x7fffffffll, "fgnn_eval_pairs_labels: %lld rows are more than one launch takes", rows);
+    if (N <= 16)
+        hipLaunchKernelGGL(eval_pairs_labels_kernel<16>, dim3((unsigned)wgs), dim3(EVAL_THREADS), 0, (hipStream_t)stream, scores, nvalid,
+                           labels, B, N, cost, cost_bstride, cost_ld, row_ce, row_hit);
+    else
+        hipLaunchKernelGGL(eval_pairs_labels_kernel<WAVE>, dim3((unsigned)wgs), dim3(EVAL_THREADS), 0, (hipStream_t)stream, scores, nvalid,
+                           labels, B, N, cost, cost_bstride, cost_ld, row_ce, row_hit);
     FGNN_LAUNCH_CHECK();
     return 0;
 }

@@ -346,9 +346,15 @@ DEVI void copy_to_lds256(float *dst, const float *src, int n, int tid) {
 // grid (B, row_blocks): workgroup (b, rp) owns a contiguous block of rows of pair b.
 // e1,e2: (C, N) each.  scores[i][j] = sum_c e1[c][i] e2[c][j]; lse_i; partial loss of its rows.
 // LDS: e2 whole (C x N) and the workgroup's own rows of e1 (C x rows).
-__global__ __launch_bounds__(256) void score_ce_fwd_kernel(const float *e1, const float *e2, const int *nvalid,
-                                                           int C, int N, int rows, float *scores, float *lse,
-                                                           float *pair_loss) {
+// LAB: the target of row i is labels[b][i] instead of i (a row whose label lies outside [0, n_b) has none: no loss); a wave reads
+// the label of its own row, the target score comes from the LDS copy of the row like Sr[i].  With labels[b][i] = i every output
+// has the bits of the label-less kernel: the two differ by that index alone.
+// A live row's target must be a live column: t in [0, n_b) (and below N, whatever n_b claims)
+DEVI bool label_ok(int t, int nv, int N) { return t >= 0 && t < nv && t < N; }
+
+template <bool LAB>
+DEVI void score_ce_fwd_body(const float *e1, const float *e2, const int *nvalid, const int *labels, int C, int N, int rows,
+                            float *scores, float *lse, float *pair_loss) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float *s2 = sm, *s1 = sm + (size_t)C * N;
     float *sS = s1 + (size_t)C * rows;   // the workgroup's score rows, [r][j]
@@ -381,6 +387,7 @@ __global__ __launch_bounds__(256) void score_ce_fwd_kernel(const float *e1, cons
         float l = 0.f;
         const float *Sr = sS + (size_t)(i - i0) * N;      // the row pass reads the LDS copy, not the global one
         if (i < nv) {
+            const int t = LAB ? labels[(long long)b * N + i] : i;      // (requested before the row pass, used after it)
             float mx = -FLT_MAX;
             for (int j = lane; j < nv; j += WAVE) mx = fmaxf(mx, Sr[j]);
             mx = wave_max(mx);
@@ -388,7 +395,7 @@ __global__ __launch_bounds__(256) void score_ce_fwd_kernel(const float *e1, cons
             for (int j = lane; j < nv; j += WAVE) se += expf(Sr[j] - mx);
             se = wave_sum(se);
             l = mx + logf(se);
-            wl += l - Sr[i];
+            if (!LAB || label_ok(t, nv, N)) wl += l - Sr[t];
         }
         if (lane == 0 && lse) lse[(long long)b * N + i] = l;
     }
@@ -397,21 +404,35 @@ __global__ __launch_bounds__(256) void score_ce_fwd_kernel(const float *e1, cons
     if (tid == 0 && pair_loss) pair_loss[b * gridDim.y + blockIdx.y] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+__global__ __launch_bounds__(256) void score_ce_fwd_kernel(const float *e1, const float *e2, const int *nvalid,
+                                                           int C, int N, int rows, float *scores, float *lse,
+                                                           float *pair_loss) {
+    score_ce_fwd_body<false>(e1, e2, nvalid, nullptr, C, N, rows, scores, lse, pair_loss);
+}
+
+__global__ __launch_bounds__(256) void score_ce_fwd_labels_kernel(const float *e1, const float *e2, const int *nvalid,
+                                                                  const int *labels, int C, int N, int rows, float *scores,
+                                                                  float *lse, float *pair_loss) {
+    score_ce_fwd_body<true>(e1, e2, nvalid, labels, C, N, rows, scores, lse, pair_loss);
+}
+
 // dS[i][j] = (exp(S-lse_i) - [i==j]) * gscale (CE mode) or the given dscores (plain mode);
 // de1[c][i] = sum_j e2[c][j] dS[i][j];  de2[c][j] = sum_i e1[c][i] dS[i][j].
 // grid (B, splits): every workgroup stages dS (N x N) once in LDS and handles C / gridDim.y channels.
 constexpr int CSPLIT = 4;          // channel splits of the blocked kernel and of large batches
 constexpr int CSPLIT_SMALL = 8;    // whole-dS staging at small batch (B * 4 < 256 workgroups)
-template <bool CE, bool STAGE>
-__global__ __launch_bounds__(256) void score_bwd_kernel(const float *e1, const float *e2, const float *scores,
-                                                        const float *lse, const float *dscores, const int *nvalid,
-                                                        const float *gscale, int C, int N, float *de1, float *de2) {
+// LAB (CE mode): dS[i][j] = (exp(S - lse_i) - [j == t_i]) * gscale with t_i = labels[b][i]; a row without a target (t_i outside
+// [0, n_b)) is zero.  The pair's labels are staged once per workgroup in N ints of LDS between s2 and dS (no-target rows as -1).
+template <bool CE, bool STAGE, bool LAB>
+DEVI void score_bwd_body(const float *e1, const float *e2, const float *scores, const float *lse, const float *dscores,
+                         const int *nvalid, const int *labels, const float *gscale, int C, int N, float *de1, float *de2) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int cper = (C + (int)gridDim.y - 1) / (int)gridDim.y;
     const int c0 = blockIdx.y * cper;
     const int cn = (c0 + cper <= C ? cper : (C > c0 ? C - c0 : 0));
     float *s1 = sm, *s2 = sm + (size_t)cper * N;
-    float *dS = s2 + (size_t)cper * N;         // [i][j], row stride N + 1
+    int *lab = reinterpret_cast<int *>(s2 + (size_t)cper * N);
+    float *dS = s2 + (size_t)cper * N + (LAB ? N : 0);         // [i][j], row stride N + 1
     const int ld = N + 1;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int nv = nvalid_of(nvalid, b, N);
@@ -420,13 +441,24 @@ __global__ __launch_bounds__(256) void score_bwd_kernel(const float *e1, const f
         s1[e] = p1[e];
         s2[e] = p2[e];
     }
+    if (LAB) {
+        for (int i = tid; i < N; i += 256) {
+            const int t = i < nv ? labels[(long long)b * N + i] : -1;
+            lab[i] = label_ok(t, nv, N) ? t : -1;
+        }
+        __syncthreads();
+    }
     const float gs = CE ? *gscale : 1.f;
     const float *S = (CE ? scores : dscores) + (long long)b * N * N;
     const float *Lr = CE ? lse + (long long)b * N : nullptr;
     const float invN = 1.f / (float)N;
     auto ds_at = [&](int i, int jj) -> float {     // valid i, jj only
         float d = S[(long long)i * N + jj];
-        if (CE) d = (expf(d - Lr[i]) - (i == jj ? 1.f : 0.f)) * gs;
+        if (CE) {
+            const int t = LAB ? lab[i] : i;
+            d = (expf(d - Lr[i]) - (t == jj ? 1.f : 0.f)) * gs;
+            if (LAB && t < 0) d = 0.f;
+        }
         return d;
     };
     if (STAGE) {
@@ -448,7 +480,11 @@ __global__ __launch_bounds__(256) void score_bwd_kernel(const float *e1, const f
                     float d = 0.f;
                     if (i < nv && jj < nv) {
                         d = v[k];
-                        if (CE) d = (expf(d - Lr[i]) - (i == jj ? 1.f : 0.f)) * gs;
+                        if (CE) {
+                            const int t = LAB ? lab[i] : i;
+                            d = (expf(d - Lr[i]) - (t == jj ? 1.f : 0.f)) * gs;
+                            if (LAB && t < 0) d = 0.f;
+                        }
                     }
                     dS[i * ld + jj] = d;
                 }
@@ -471,20 +507,34 @@ __global__ __launch_bounds__(256) void score_bwd_kernel(const float *e1, const f
     }
 }
 
+template <bool CE, bool STAGE>
+__global__ __launch_bounds__(256) void score_bwd_kernel(const float *e1, const float *e2, const float *scores,
+                                                        const float *lse, const float *dscores, const int *nvalid,
+                                                        const float *gscale, int C, int N, float *de1, float *de2) {
+    score_bwd_body<CE, STAGE, false>(e1, e2, scores, lse, dscores, nvalid, nullptr, gscale, C, N, de1, de2);
+}
+
+__global__ __launch_bounds__(256) void score_bwd_labels_kernel(const float *e1, const float *e2, const float *scores,
+                                                               const float *lse, const int *nvalid, const int *labels,
+                                                               const float *gscale, int C, int N, float *de1, float *de2) {
+    score_bwd_body<true, true, true>(e1, e2, scores, lse, nullptr, nvalid, labels, gscale, C, N, de1, de2);
+}
+
 // Large N (dS does not fit LDS): grid (B, CSPLIT, ceil(N / SB_BLK)).  Workgroup (b, cs, rb) stages the row block
 // dS[i0:i1, :] and produces de1 for those rows, then stages the column block dS[:, i0:i1] and produces de2 for
 // those columns -- no cross-workgroup reduction, nothing recomputed inside the inner loops.
-template <bool CE>
-__global__ __launch_bounds__(256) void score_bwd_blocked_kernel(const float *e1, const float *e2, const float *scores,
-                                                                const float *lse, const float *dscores,
-                                                                const int *nvalid, const float *gscale, int C, int N,
-                                                                int SB_BLK, float *de1, float *de2) {
+// LAB: as in score_bwd_body (the labels of the pair in N ints of LDS between s2 and dS).
+template <bool CE, bool LAB>
+DEVI void score_bwd_blocked_body(const float *e1, const float *e2, const float *scores, const float *lse, const float *dscores,
+                                 const int *nvalid, const int *labels, const float *gscale, int C, int N, int SB_BLK, float *de1,
+                                 float *de2) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int cper = (C + CSPLIT - 1) / CSPLIT;
     const int c0 = blockIdx.y * cper;
     const int cn = (c0 + cper <= C ? cper : (C > c0 ? C - c0 : 0));
     float *s1 = sm, *s2 = sm + (size_t)cper * N;
-    float *dS = s2 + (size_t)cper * N;         // phase 1: [SB_BLK][N + 1], phase 2: [N][SB_BLK + 1]
+    int *lab = reinterpret_cast<int *>(s2 + (size_t)cper * N);
+    float *dS = s2 + (size_t)cper * N + (LAB ? N : 0);         // phase 1: [SB_BLK][N + 1], phase 2: [N][SB_BLK + 1]
     const int b = blockIdx.x, tid = threadIdx.x;
     const int nv = nvalid_of(nvalid, b, N);
     const int x0 = blockIdx.z * SB_BLK, x1 = (x0 + SB_BLK < N) ? x0 + SB_BLK : N, w = x1 - x0;
@@ -494,13 +544,23 @@ __global__ __launch_bounds__(256) void score_bwd_blocked_kernel(const float *e1,
     constexpr int U = 8;
     copy_to_lds256(s1, p1, cn * N, tid);
     copy_to_lds256(s2, p2, cn * N, tid);
+    if (LAB) {
+        for (int i = tid; i < N; i += 256) {
+            const int t = i < nv ? labels[(long long)b * N + i] : -1;
+            lab[i] = label_ok(t, nv, N) ? t : -1;
+        }
+        __syncthreads();
+    }
     const float gs = CE ? *gscale : 1.f;
     const float *S = (CE ? scores : dscores) + (long long)b * N * N;
     const float *Lr = CE ? lse + (long long)b * N : nullptr;
     // dS[i][jj] from the loaded score (and the row's lse); i, jj < N
     auto ds_of = [&](float sv, float lv, int i, int jj) -> float {
         if (i >= nv || jj >= nv) return 0.f;
-        return CE ? (expf(sv - lv) - (i == jj ? 1.f : 0.f)) * gs : sv;
+        if (!CE) return sv;
+        const int t = LAB ? lab[i] : i;
+        if (LAB && t < 0) return 0.f;
+        return (expf(sv - lv) - (t == jj ? 1.f : 0.f)) * gs;
     };
     // ---- phase 1: rows x0..x1 ----
     {
@@ -565,6 +625,21 @@ __global__ __launch_bounds__(256) void score_bwd_blocked_kernel(const float *e1,
     }
 }
 
+template <bool CE>
+__global__ __launch_bounds__(256) void score_bwd_blocked_kernel(const float *e1, const float *e2, const float *scores,
+                                                                const float *lse, const float *dscores,
+                                                                const int *nvalid, const float *gscale, int C, int N,
+                                                                int SB_BLK, float *de1, float *de2) {
+    score_bwd_blocked_body<CE, false>(e1, e2, scores, lse, dscores, nvalid, nullptr, gscale, C, N, SB_BLK, de1, de2);
+}
+
+__global__ __launch_bounds__(256) void score_bwd_blocked_labels_kernel(const float *e1, const float *e2, const float *scores,
+                                                                       const float *lse, const int *nvalid, const int *labels,
+                                                                       const float *gscale, int C, int N, int SB_BLK, float *de1,
+                                                                       float *de2) {
+    score_bwd_blocked_body<true, true>(e1, e2, scores, lse, nullptr, nvalid, labels, gscale, C, N, SB_BLK, de1, de2);
+}
+
 // triplet_loss pieces on a given score tensor (module-level API): one workgroup per pair.
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const float *scores, const int *nvalid, int N, float *lse,
                                                      float *pair_loss) {
@@ -592,6 +667,36 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float *scores, const 
     if (tid == 0 && pair_loss) pair_loss[b] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// its labelled sibling: the target of row i is labels[b][i] (see score_ce_fwd_body); every wave reads the label of its own row.
+// (A sibling, not an instantiation of a shared body: the compiler allots the label-less kernel other registers when its code
+// comes out of an inlined template.)
+__global__ __launch_bounds__(256) void ce_fwd_labels_kernel(const float *scores, const int *nvalid, const int *labels, int N,
+                                                            float *lse, float *pair_loss) {
+    __shared__ float red[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nv = nvalid_of(nvalid, b, N);
+    const float *S = scores + (long long)b * N * N;
+    float wl = 0.f;
+    for (int i = wave; i < N; i += 4) {
+        float l = 0.f;
+        if (i < nv) {
+            const int t = labels[(long long)b * N + i];
+            float mx = -FLT_MAX;
+            for (int j = lane; j < nv; j += WAVE) mx = fmaxf(mx, S[(long long)i * N + j]);
+            mx = wave_max(mx);
+            float se = 0.f;
+            for (int j = lane; j < nv; j += WAVE) se += expf(S[(long long)i * N + j] - mx);
+            se = wave_sum(se);
+            l = mx + logf(se);
+            if (label_ok(t, nv, N)) wl += l - S[(long long)i * N + t];
+        }
+        if (lane == 0 && lse) lse[(long long)b * N + i] = l;
+    }
+    if (lane == 0) red[wave] = wl;
+    __syncthreads();
+    if (tid == 0 && pair_loss) pair_loss[b] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 __global__ void ce_bwd_kernel(const float *scores, const float *lse, const int *nvalid, const float *gscale, int N,
                               float *dscores) {
     const int b = blockIdx.y;
@@ -602,6 +707,31 @@ __global__ void ce_bwd_kernel(const float *scores, const float *lse, const int *
     float d = 0.f;
     if (i < nv && j < nv)
         d = (expf(scores[(long long)b * N * N + e] - lse[(long long)b * N + i]) - (i == j ? 1.f : 0.f)) * (*gscale);
+    dscores[(long long)b * N * N + e] = d;
+}
+
+// its labelled sibling: one thread per element; the 256 elements of a workgroup lie in at most 256 rows (N = 1), whose labels it
+// reads once into LDS (no-target rows as -1: their dS is zero)
+__global__ __launch_bounds__(256) void ce_bwd_labels_kernel(const float *scores, const float *lse, const int *nvalid,
+                                                            const int *labels, const float *gscale, int N, float *dscores) {
+    __shared__ int lab[256];
+    const int b = blockIdx.y;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    const int nv = nvalid_of(nvalid, b, N);
+    const int r0 = (int)(blockIdx.x * 256) / N;       // the row of the workgroup's first element
+    {
+        const int r = r0 + (int)threadIdx.x;
+        const int t = r < nv && r < N ? labels[(long long)b * N + r] : -1;
+        lab[threadIdx.x] = label_ok(t, nv, N) ? t : -1;
+    }
+    __syncthreads();
+    if (e >= N * N) return;
+    const int i = e / N, j = e - i * N;
+    float d = 0.f;
+    if (i < nv && j < nv) {
+        const int t = lab[i - r0];
+        if (t >= 0) d = (expf(scores[(long long)b * N * N + e] - lse[(long long)b * N + i]) - (t == j ? 1.f : 0.f)) * (*gscale);
+    }
     dscores[(long long)b * N * N + e] = d;
 }
 
@@ -666,15 +796,39 @@ static int score_bwd_lds_bytes(int C, int N, bool stage, int csplit = CSPLIT) {
     const int cper = (C + csplit - 1) / csplit;
     return (2 * cper * N + (stage ? N * (N + 1) : 0)) * (int)sizeof(float);
 }
+// labels (CE mode only; NULL: the identity): the labelled twins of the same forms, chosen by the same rules -- the form is decided
+// on the label-less LDS sizes, the labelled launch then asks for N ints more (the pair's labels)
 template <bool CE>
 static int launch_score_bwd(const float *e1, const float *e2, const float *scores, const float *lse,
                             const float *dscores, const int *nvalid, const float *gscale, int B, int C, int N,
-                            float *de1, float *de2, hipStream_t st) {
+                            float *de1, float *de2, hipStream_t st, const int *labels = nullptr) {
     // whole-dS staging gives only B x CSPLIT workgroups: with few large pairs (N > 64) the blocked kernel fills the chip better
     const bool stage = score_bwd_lds_bytes(C, N, true) <= 160 * 1024 && (N <= 64 || (long long)B * CSPLIT >= 256);
     const int csplit = (long long)B * CSPLIT < 256 ? CSPLIT_SMALL : CSPLIT;
     const int lds = score_bwd_lds_bytes(C, N, stage, stage ? csplit : CSPLIT);
     FGNN_CHECK(lds <= 160 * 1024, "score backward: C*N=%d too large for LDS staging", C * N);
+    const int lab_bytes = N * (int)sizeof(int);
+    if (CE && labels) {
+        if (stage) {
+            FGNN_CHECK(lds + lab_bytes <= 160 * 1024, "score backward: C*N=%d too large for LDS staging with labels", C * N);
+            if (lds + lab_bytes > 64 * 1024)
+                (void)hipFuncSetAttribute((const void *)score_bwd_labels_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds + lab_bytes);
+            hipLaunchKernelGGL(score_bwd_labels_kernel, dim3(B, csplit), dim3(256), lds + lab_bytes, st, e1, e2, scores, lse, nvalid,
+                               labels, gscale, C, N, de1, de2);
+        } else {
+            const int cper = (C + CSPLIT - 1) / CSPLIT;
+            const int SB_BLK = (long long)B * CSPLIT * ((N + 63) / 64) >= 512 ? 64 : 16;
+            const int big = (N + 1) * SB_BLK > N * (SB_BLK + 1) ? (N + 1) * SB_BLK : N * (SB_BLK + 1);
+            const int lds2 = (2 * cper * N + big) * (int)sizeof(float) + lab_bytes;
+            FGNN_CHECK(lds2 <= 160 * 1024, "score backward: N=%d too large for the blocked LDS staging with labels", N);
+            if (lds2 > 64 * 1024)
+                (void)hipFuncSetAttribute((const void *)score_bwd_blocked_labels_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
+            hipLaunchKernelGGL(score_bwd_blocked_labels_kernel, dim3(B, CSPLIT, (N + SB_BLK - 1) / SB_BLK), dim3(256), lds2, st, e1, e2,
+                               scores, lse, nvalid, labels, gscale, C, N, SB_BLK, de1, de2);
+        }
+        FGNN_LAUNCH_CHECK();
+        return 0;
+    }
     if (stage) {
         if (lds > 64 * 1024)
             (void)hipFuncSetAttribute((const void *)score_bwd_kernel<CE, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -716,6 +870,20 @@ extern "C" int fgnn_score_ce_fwd_blocks(const float *e1, const float *e2, const 
     return 0;
 }
 
+extern "C" int fgnn_score_ce_fwd_blocks_labels(const float *e1, const float *e2, const int *nvalid, const int *labels, int B, int C,
+                                               int N, int row_blocks, float *scores, float *lse, float *pair_loss, void *stream) {
+    FGNN_CHECK(e1 && e2 && labels && scores && B > 0 && C > 0 && N > 0 && row_blocks > 0, "fgnn_score_ce_fwd_blocks_labels: bad arguments");
+    const int rows = (N + row_blocks - 1) / row_blocks;
+    const int lds = (C * N + C * rows + rows * N + 4) * (int)sizeof(float);      // the geometry and LDS of fgnn_score_ce_fwd_blocks
+    FGNN_CHECK(lds <= 160 * 1024, "fgnn_score_ce_fwd_blocks_labels: C*N=%d too large for LDS staging", C * N);
+    if (lds > 64 * 1024)
+        (void)hipFuncSetAttribute((const void *)score_ce_fwd_labels_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipLaunchKernelGGL(score_ce_fwd_labels_kernel, dim3(B, row_blocks), dim3(256), lds, (hipStream_t)stream, e1, e2, nvalid, labels, C,
+                       N, rows, scores, lse, pair_loss);
+    FGNN_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int fgnn_score_ce_fwd(const float *e1, const float *e2, const int *nvalid, int B, int C, int N,
                                  float *scores, float *lse, float *pair_loss, void *stream) {
     return fgnn_score_ce_fwd_blocks(e1, e2, nvalid, B, C, N, FGNN_SCORE_SPLIT, scores, lse, pair_loss, stream);
@@ -726,6 +894,13 @@ extern "C" int fgnn_score_ce_bwd(const float *e1, const float *e2, const float *
                                  void *stream) {
     FGNN_CHECK(e1 && e2 && scores && lse && gscale && de1 && de2 && B > 0, "fgnn_score_ce_bwd: bad arguments");
     return launch_score_bwd<true>(e1, e2, scores, lse, nullptr, nvalid, gscale, B, C, N, de1, de2, (hipStream_t)stream);
+}
+
+extern "C" int fgnn_score_ce_bwd_labels(const float *e1, const float *e2, const float *scores, const float *lse, const int *nvalid,
+                                        const int *labels, const float *gscale, int B, int C, int N, float *de1, float *de2,
+                                        void *stream) {
+    FGNN_CHECK(e1 && e2 && scores && lse && labels && gscale && de1 && de2 && B > 0, "fgnn_score_ce_bwd_labels: bad arguments");
+    return launch_score_bwd<true>(e1, e2, scores, lse, nullptr, nvalid, gscale, B, C, N, de1, de2, (hipStream_t)stream, labels);
 }
 
 extern "C" int fgnn_score_bwd(const float *e1, const float *e2, const float *dscores, const int *nvalid, int B, int C,
@@ -747,6 +922,23 @@ extern "C" int fgnn_ce_bwd(const float *scores, const float *lse, const int *nva
     FGNN_CHECK(scores && lse && gscale && dscores && B > 0 && N > 0, "fgnn_ce_bwd: bad arguments");
     hipLaunchKernelGGL(ce_bwd_kernel, dim3((N * N + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, scores, lse,
                        nvalid, gscale, N, dscores);
+    FGNN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int fgnn_ce_fwd_labels(const float *scores, const int *nvalid, const int *labels, int B, int N, float *lse,
+                                  float *pair_loss, void *stream) {
+    FGNN_CHECK(scores && labels && lse && pair_loss && B > 0 && N > 0, "fgnn_ce_fwd_labels: bad arguments");
+    hipLaunchKernelGGL(ce_fwd_labels_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, scores, nvalid, labels, N, lse, pair_loss);
+    FGNN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int fgnn_ce_bwd_labels(const float *scores, const float *lse, const int *nvalid, const int *labels, const float *gscale,
+                                  int B, int N, float *dscores, void *stream) {
+    FGNN_CHECK(scores && lse && labels && gscale && dscores && B > 0 && N > 0, "fgnn_ce_bwd_labels: bad arguments");
+    hipLaunchKernelGGL(ce_bwd_labels_kernel, dim3((N * N + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, scores, lse, nvalid,
+                       labels, gscale, N, dscores);
     FGNN_LAUNCH_CHECK();
     return 0;
 }

@@ -49,6 +49,7 @@ class EngineBase:
         self._loss_pending = False
         self._loss_target = None
         self._loss_scale_dev = None      # 1 / sum(n) as a device scalar: assigned by the caller that keeps the normaliser on the device
+        self.labels = None               # (B, N) int32 targets of the cross-entropy (forward(labels=...)); None: the identity
 
     # ------------------------------------------------------------------ helpers
     def _nv(self):
@@ -104,6 +105,14 @@ class EngineBase:
                 self._nvalid_own.copy_(nvalid.to(torch.int32))
                 self.nvalid = self._nvalid_own
 
+    def _adopt_labels(self, labels):
+        """labels= of forward / step: None (the identity: the label-less launches), or what metrics.labels_tensor takes.  A (B, N)
+        int32 contiguous tensor on the engine's device is read in place by the two score launches, like nvalid."""
+        if labels is not None:
+            from .metrics import labels_tensor
+            labels = labels_tensor(labels, self.B, self.N, self.device)
+        self.labels = labels
+
     def _check_bits(self, bits):
         """bits: (G, N, ceil(N/32)) contiguous 32-bit words of the bit-packed adjacency on the GPU."""
         words = (self.N + 31) // 32
@@ -126,12 +135,17 @@ class EngineBase:
         return ((C.c_void_p * 3)(*[self._w(params, o) for o in rec['w']]), (C.c_void_p * 3)(*[self._w(params, o) for o in rec['b']]))
 
     # ------------------------------------------------------------------ forward
-    def forward(self, params, x, nvalid=None, total_nodes=None, defer_loss=False, loss_out=None, bits=None, **embed_kw):
+    def forward(self, params, x, nvalid=None, total_nodes=None, defer_loss=False, loss_out=None, bits=None, labels=None, **embed_kw):
         """Siamese forward on the stacked batch x = cat(x1, x2) (or its bit-packed adjacency, see embed): returns
         (scores, loss).
+        labels: (B, N) integer tensor, labels[b, i] = the column row i of pair b should match (planted.py; -1 in the padding):
+        the cross-entropy is taken against them instead of the identity, and the following backward()
+        differentiates that loss.  A live row whose label lies outside [0, n_b) has no target: no loss, no gradient.  The
+        normaliser stays the node count.  None: the label-less launches, as before.
         defer_loss: leave the final sum of the per-pair losses to the gradient-finalize launch of the
         following backward() (one launch less per training step); `loss` is valid after that.
         embed_kw: keywords of the engine's own embed()."""
+        self._adopt_labels(labels)
         self.embed(params, x, nvalid, bits=bits, **embed_kw)
         B, N = self.B, self.N
         st = _lib.stream_ptr()
@@ -139,8 +153,12 @@ class EngineBase:
         if total_nodes is None:
             total_nodes = B * N if nvalid is None else int(nvalid[:B].sum().item())
         self.total_nodes = float(total_nodes)
-        _lib.call('fgnn_score_ce_fwd_blocks', _lib.ptr(e1), _lib.ptr(e2), self._nv(), B, 32, N, self.score_blocks,
-                  _lib.ptr(self.scores), _lib.ptr(self.lse), _lib.ptr(self.pair_loss), st)
+        if self.labels is None:
+            _lib.call('fgnn_score_ce_fwd_blocks', _lib.ptr(e1), _lib.ptr(e2), self._nv(), B, 32, N, self.score_blocks,
+                      _lib.ptr(self.scores), _lib.ptr(self.lse), _lib.ptr(self.pair_loss), st)
+        else:
+            _lib.call('fgnn_score_ce_fwd_blocks_labels', _lib.ptr(e1), _lib.ptr(e2), self._nv(), _lib.ptr(self.labels), B, 32, N,
+                      self.score_blocks, _lib.ptr(self.scores), _lib.ptr(self.lse), _lib.ptr(self.pair_loss), st)
         self._loss_pending = bool(defer_loss)
         self._loss_target = self.loss if loss_out is None else loss_out     # 1-element fp32 device tensor
         if not defer_loss:
@@ -180,6 +198,7 @@ class EngineBase:
     def backward(self, params, grads, grad_scale=1.0, gscale_dev=None, **kw):
         """Backward of loss*grad_scale after forward(); fills the flat `grads` buffer (the fp32 engine's finalize=False: everything
         but the last launch, see its backward_from_dE).
+        After forward(labels=...) the gradient is that of the labelled loss (the labels are read again, in place).
         gscale_dev: a 1-element fp32 DEVICE tensor that holds grad_scale / total_nodes (replaces both): the normaliser of a ragged
         batch then never visits the host, and a captured step stays valid when the next batch has another node count.
         kw: keywords of the engine's own backward_from_dE() (finalize=, hook=)."""
@@ -192,8 +211,12 @@ class EngineBase:
         else:
             self._set_gscale(grad_scale / self.total_nodes)
         e1, e2 = self.E[:B], self.E[B:]
-        _lib.call('fgnn_score_ce_bwd', _lib.ptr(e1), _lib.ptr(e2), _lib.ptr(self.scores), _lib.ptr(self.lse),
-                  self._nv(), _lib.ptr(gs_t), B, 32, N, _lib.ptr(W['dE'][:B]), _lib.ptr(W['dE'][B:]), st)
+        if self.labels is None:
+            _lib.call('fgnn_score_ce_bwd', _lib.ptr(e1), _lib.ptr(e2), _lib.ptr(self.scores), _lib.ptr(self.lse),
+                      self._nv(), _lib.ptr(gs_t), B, 32, N, _lib.ptr(W['dE'][:B]), _lib.ptr(W['dE'][B:]), st)
+        else:
+            _lib.call('fgnn_score_ce_bwd_labels', _lib.ptr(e1), _lib.ptr(e2), _lib.ptr(self.scores), _lib.ptr(self.lse),
+                      self._nv(), _lib.ptr(self.labels), _lib.ptr(gs_t), B, 32, N, _lib.ptr(W['dE'][:B]), _lib.ptr(W['dE'][B:]), st)
         return self.backward_from_dE(params, grads, W['dE'], **kw)
 
     def _set_gscale(self, gs):
@@ -241,10 +264,10 @@ class EngineBase:
                       self.G if graphs is None else graphs, 32, st)
         return grads
 
-    def step(self, params, grads, x, nvalid=None, total_nodes=None, loss_out=None, bits=None):
-        """One training step's model work: forward + loss + backward.  (x / bits / an int32 device nvalid are read in place by both
-        passes: see embed().)"""
-        scores, loss = self.forward(params, x, nvalid, total_nodes, defer_loss=True, loss_out=loss_out, bits=bits)
+    def step(self, params, grads, x, nvalid=None, total_nodes=None, loss_out=None, bits=None, labels=None):
+        """One training step's model work: forward + loss + backward.  (x / bits / an int32 device nvalid / int32 device labels are
+        read in place by both passes: see embed() and forward().)"""
+        scores, loss = self.forward(params, x, nvalid, total_nodes, defer_loss=True, loss_out=loss_out, bits=bits, labels=labels)
         self.backward(params, grads)
         return scores, loss
 

@@ -80,10 +80,13 @@ def record_result(rec):
             'nodes': nodes, 'pairs': rec['pairs']}
 
 
-def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hungarian=True):
+def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False):
     """scores: (B, N, N) fp32 raw scores on the GPU, or a MaskedTensor of them (its vertex counts are used unless nvalid is given).
     nvalid: (B,) vertex counts in [0, N]; labels: see metrics.py (None: the identity; they enter the accuracies, never the loss).
     live: the first `live` pairs count (None: all B) -- the others, the filling of a short last step, are ignored entirely.
+    loss_on_labels=True: the labels enter the loss as well -- 'ce' and the meter's ce_sum are the cross-entropy against labels[b, i]
+    (fgnn_eval_pairs_labels; a row whose label lies outside [0, n_b) adds nothing; the node count still counts it), the loss of a
+    model trained with train_step(labels=...).  Without labels it changes nothing.
     hungarian=False leaves the solver out (correct_lsap stays 0, assign is None).
     Adds the live pairs to `meter` (an EvalMeter; None: a fresh one, returned under 'meter') and returns the per-pair device
     tensors {'ce': (B,) fp64 CE sums, 'n': (B,) int32 vertex counts, 'correct_max', 'correct_lsap': (B,) int32, 'assign': (B, N) int32
@@ -127,7 +130,7 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
         correct = torch.zeros(B, **i32)
         assign = None
         st = _lib.stream_ptr()
-        _lib.call('fgnn_eval_pairs', _lib.ptr(s), _lib.ptr(nvalid), _lib.ptr(labels), B, N, _lib.ptr(cost), N * N, N,
+        _lib.call('fgnn_eval_pairs_labels' if loss_on_labels and labels is not None else 'fgnn_eval_pairs', _lib.ptr(s), _lib.ptr(nvalid), _lib.ptr(labels), B, N, _lib.ptr(cost), N * N, N,
                   _lib.ptr(row_ce), _lib.ptr(row_hit), st)
         if hungarian:
             assign = torch.empty(B, N, **i32)

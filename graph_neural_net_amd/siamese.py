@@ -183,7 +183,7 @@ class Siamese_Node_Exp(nn.Module):
         self._raise_if_not_representation({'flag': flag})
         return out
 
-    def fused_step(self, x1, x2, capture=True, metric=False):
+    def fused_step(self, x1, x2, capture=True, metric=False, labels=None):
         """Forward of both branches + scoring + `triplet_loss` + the full backward (+ the step's metric, models/trainers.py:70-76)
         as the fused launch sequence of engine.FgnnEngine -- with capture=True ONE replayed HIP graph per (padded) batch shape,
         the step `bench.py` measures (the eager module path `loss = model.loss(model(x1, x2)); loss.backward()` of
@@ -203,7 +203,13 @@ class Siamese_Node_Exp(nn.Module):
         metric=True appends the model's matching accuracy (the default Hungarian accuracy or 'max', both device kernels) to the
         step: returns (loss, scores, (n_correct, n_vertices)) with the counts as DEVICE tensors -- no host synchronisation
         unless the caller reads them.  Returns (loss, raw scores) otherwise; scores are (bs, n, n) or a MaskedTensor; all outputs
-        are device tensors that the NEXT call of the same shape overwrites."""
+        are device tensors that the NEXT call of the same shape overwrites.
+
+        labels (an extension: the reference's target is always the identity): what metrics.labels_tensor takes, (bs, n) with
+        labels[b, i] = the vertex of x2[b] that vertex i of x1[b] matches, -1 for none (wider rows are cut to n).  Loss and gradient
+        are those of the cross-entropy against them and the metric counts matches with them; a labelled step
+        is a captured graph of its own whose labels live in a static buffer each call overwrites.  On the module path's own launch
+        sequence (non-standard widths) a labelled step runs eagerly."""
         x1, x2 = _unwrap_input(x1), _unwrap_input(x2)
         net = self.node_embedder
         lay = net._standard_layout()
@@ -212,15 +218,20 @@ class Siamese_Node_Exp(nn.Module):
         if not t1.is_cuda:
             raise RuntimeError('graph_neural_net_amd only runs on the GPU (input is on %s)' % (t1.device,))
         builtin_metric = self.metric is accuracy_linear_assignment or self.metric is accuracy_max
+        if labels is not None:
+            if torch.is_tensor(labels) and labels.dim() == 2 and labels.shape[1] > t1.shape[-1]:
+                labels = labels[:, :t1.shape[-1]]
+            labels = labels_tensor(labels, t1.shape[0], t1.shape[-1], t1.device)
+        mkw = {} if labels is None else {'labels': labels}
         if lay is None or (ragged and self.loss.loss_reduction != 'mean'):
             # widths / depths the fused engine is not built for (or a per-graph loss weighting the engine's scoring kernel does not
             # have): the module path's own launch sequence, captured once per batch shape and replayed (constant-size batches)
             if ragged:
                 raise RuntimeError('fused_step: MaskedTensor batches need the standard node_embedding graph and loss_reduction="mean"; '
                                    'use the module path `loss = model.loss(model(x1, x2)); loss.backward()`')
-            out = self._captured_module_step(t1, t2, capture)
+            out = self._captured_module_step(t1, t2, capture and labels is None, labels)
             if metric:
-                acc, n = self.metric(out[1])
+                acc, n = self.metric(out[1], **mkw)
                 return out + ((acc, n),)
             return out
         net._bind_flat()
@@ -250,6 +261,14 @@ class Siamese_Node_Exp(nn.Module):
                 st['bits'] = torch.zeros(2 * B, N, (N + 31) // 32, dtype=torch.int32, device=dev)
                 st['flag'] = self.__dict__.setdefault('_tr_flags', {}).setdefault(dev, torch.zeros(1, dtype=torch.int32, device=dev))
         c0 = t1.shape[1]
+        lkw = {}
+        if labels is not None:
+            if st.get('labels') is None:
+                st['labels'] = torch.full((B, N), -1, dtype=torch.int32, device=dev)
+            st['labels'][:, :nmax].copy_(labels)
+            if nmax < N:
+                st['labels'][:, nmax:].fill_(-1)
+            lkw = mkw = {'labels': st['labels']}        # (the metric sees the padded scores: it takes the padded labels)
         if getattr(net, 'precision', 'fp32') == 'bf16':
             net._check_channels(t1)
         first_of_shape = st['calls'] == 0
@@ -303,13 +322,13 @@ class Siamese_Node_Exp(nn.Module):
                 if not tr:      # (input_form='tensor_representation': the packing launch in front of the graph has written st['inv'])
                     _lib.call('fgnn_inv_node_count', _lib.ptr(st['nv']), B, _lib.ptr(st['inv']), _lib.stream_ptr())
                 eng._loss_scale_dev = st['inv']
-                scores, loss = eng.forward(params, xin, nvalid=st['nv'], total_nodes=1.0, defer_loss=True, bits=bits)
+                scores, loss = eng.forward(params, xin, nvalid=st['nv'], total_nodes=1.0, defer_loss=True, bits=bits, **lkw)
                 eng.backward(params, grads, gscale_dev=st['inv'])
             else:
-                scores, loss = eng.step(params, grads, xin, bits=bits)
+                scores, loss = eng.step(params, grads, xin, bits=bits, **lkw)
             if pad is not None:
                 torch.index_select(pad['pgrad'], 0, pad['idx'], out=net._flat_grad)
-            if metric and builtin_metric:
+            if metric and in_graph_metric:
                 nvp = _lib.ptr(st['nv']) if ragged else None
                 if self.metric is accuracy_max:
                     _lib.call('fgnn_accuracy_max', _lib.ptr(scores), nvp, B, N, _lib.ptr(st['correct']), _lib.stream_ptr())
@@ -322,7 +341,10 @@ class Siamese_Node_Exp(nn.Module):
                     _lib.call('fgnn_lsap_accuracy', _lib.ptr(cost), N * N, N, nvp, B, N, _lib.ptr(st['correct']), None, _lib.stream_ptr())
             return scores, loss
 
-        key = bool(metric and builtin_metric)
+        in_graph_metric = builtin_metric and labels is None       # (with labels the metric is the module's own call after the step)
+        key = bool(metric and in_graph_metric)                    # (the label-less graphs keep their keys: False / True)
+        if labels is not None:
+            key = (key, 'labels')
         if capture and st['graph'].get(key) is None:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
@@ -347,10 +369,10 @@ class Siamese_Node_Exp(nn.Module):
             scores = MaskedTensor(scores, x1.nvalid, (1, 2), x1.base_name)
         if not metric:
             return loss.reshape(()), scores
-        if builtin_metric:
+        if in_graph_metric:
             total = st['nv'][:B].sum() if ragged else torch.tensor(B * N, device=dev)
             return loss.reshape(()), scores, (st['correct'].sum(), total)
-        acc, n = self.metric(scores)
+        acc, n = self.metric(scores, **mkw)
         return loss.reshape(()), scores, (acc, n)
 
     @staticmethod
@@ -370,7 +392,7 @@ class Siamese_Node_Exp(nn.Module):
             self._raise_if_not_representation({'flag': flag})
         return bool(flags)
 
-    def _captured_module_step(self, x1, x2, capture):
+    def _captured_module_step(self, x1, x2, capture, labels=None):
         """forward + loss + backward of the eager module path (models/trainers.py:60-76) as ONE replayed HIP graph per batch
         shape: the ~400 launches of a non-standard model cost the host nothing on replay.  Same contract as fused_step:
         every p.grad is overwritten per call, the returned tensors are overwritten by the next call of the same shape."""
@@ -384,7 +406,7 @@ class Siamese_Node_Exp(nn.Module):
             # which is not allowed inside a capture (the capture then dies in hipStreamEndCapture).
             leaves = {n: p.detach().requires_grad_(True) for n, p in named}
             scores = torch.func.functional_call(self, leaves, (a, b))
-            loss = self.loss(scores)
+            loss = self.loss(scores) if labels is None else self.loss(scores, labels=labels)
             grads = torch.autograd.grad(loss, list(leaves.values()), allow_unused=True)
             return loss.detach().reshape(()), scores.detach(), grads
 
@@ -430,10 +452,17 @@ class Siamese_Node_Exp(nn.Module):
         pass
 
     def _shared_step(self, batch, prefix):
+        """batch: (data1, data2) as the reference's loaders yield it, or (data1, data2, labels) -- an extension: loss and metric
+        are then taken against the labels (PairGenerator.dense(permute=True) yields such batches)."""
         raw_scores = self(batch[0], batch[1])
-        loss = self.loss(raw_scores)
+        lkw = {'labels': batch[2]} if len(batch) > 2 and batch[2] is not None else {}
+        if lkw:
+            n = (raw_scores.tensor if isinstance(raw_scores, MaskedTensor) else raw_scores).shape[-1]
+            if torch.is_tensor(batch[2]) and batch[2].dim() == 2 and batch[2].shape[1] > n:
+                lkw = {'labels': batch[2][:, :n]}
+        loss = self.loss(raw_scores, **lkw)
         self.log(prefix + '_loss', loss)
-        acc, n = self.metric(raw_scores)
+        acc, n = self.metric(raw_scores, **lkw)
         self.log(prefix + '_acc', acc / n)
         return loss
 

@@ -166,16 +166,20 @@ class FgnnTrainer:
             buckets.setdefault(-(-int(n) // granule) * granule, []).append(i)
         return sorted(buckets.items())
 
-    def prepare_ragged(self, xs, ys, granule=None):
+    def prepare_ragged(self, xs, ys, granule=None, labels=None):
         """Stage a ragged list of pairs (xs[i], ys[i]: (c0, n_i, n_i) tensors): one stacked, zero-padded
         (2 * pairs, c0, npad, npad) device tensor + vertex counts per size bucket.  This is loader work (pad / stack / copy):
         done once per batch, off the step's critical path.  -> dict for model_step_prepared.
         granule=None: ONE batch padded to its largest graph (rounded up to a multiple of 16) -- since the MLP kernels step over padding tiles this is the
         fastest schedule up to a size spread of about 4x (measured, 8 and 64 pairs with n in [30, 120]: 1.13 / 5.96 ms against
         1.77 / 6.09 ms with buckets of 32); granule=g: one engine pass per size class ceil(n / g) * g (bounded workspace for
-        very mixed batches)."""
+        very mixed batches).
+        labels: None, or one integer array per pair (labels[i][r] = the vertex of ys[i] that vertex r of xs[i] matches, at most n_i
+        entries): they follow their pairs into the buckets as (pairs, npad) int32 tensors, -1 in the padding."""
         dev = self.params.device
         sizes = [int(x.shape[-1]) for x in xs]
+        if labels is not None and len(labels) != len(xs):
+            raise ValueError('FgnnTrainer.prepare_ragged: %d label arrays for %d pairs' % (len(labels), len(xs)))
         if granule is None:
             granule = -(-max(sizes) // 16) * 16        # one bucket; rounded up so that engines are shared between batches
         buckets = []
@@ -189,6 +193,10 @@ class FgnnTrainer:
             ns = [sizes[i] for i in idx] + [0] * (cnt - len(idx))
             nv = torch.tensor(ns * 2, dtype=torch.int32, device=dev)
             buckets.append({'npad': npad, 'idx': idx, 'pairs': cnt, 'x': x, 'nvalid': nv})
+            if labels is not None:
+                import numpy as np
+                from .metrics import labels_tensor
+                buckets[-1]['labels'] = labels_tensor([labels[i] for i in idx] + [np.zeros(0, dtype=np.int64)] * (cnt - len(idx)), cnt, npad, dev)
         return {'sizes': sizes, 'buckets': buckets}
 
     def model_step_prepared(self, batch, total_nodes=None, want_scores=True):
@@ -206,7 +214,8 @@ class FgnnTrainer:
             eng = self._engine(2 * b['pairs'], b['npad'], True)
             # the first bucket writes self.grads, the others go through the scratch vector and are added
             dst = self.grads if first else self._grad_tmp()
-            sc, l = eng.step(self.params, dst, b['x'], nvalid=b['nvalid'], total_nodes=total)
+            kw = {'labels': b['labels']} if b.get('labels') is not None else {}
+            sc, l = eng.step(self.params, dst, b['x'], nvalid=b['nvalid'], total_nodes=total, **kw)
             if not first:
                 self.grads += dst
             first = False
@@ -221,28 +230,35 @@ class FgnnTrainer:
             self._gtmp = torch.empty_like(self.grads)
         return self._gtmp
 
-    def model_step_ragged(self, xs, ys, granule=None, total_nodes=None):
+    def model_step_ragged(self, xs, ys, granule=None, total_nodes=None, labels=None):
         """prepare_ragged + model_step_prepared in one call.  Returns (loss, [scores_i of shape (n_i, n_i)])."""
-        return self.model_step_prepared(self.prepare_ragged(xs, ys, granule), total_nodes)
+        return self.model_step_prepared(self.prepare_ragged(xs, ys, granule, labels), total_nodes)
 
-    def train_step_ragged(self, xs, ys, granule=None):
-        loss, scores = self.model_step_ragged(xs, ys, granule, total_nodes=1.0)
+    def train_step_ragged(self, xs, ys, granule=None, labels=None):
+        """labels: per-pair integer arrays (prepare_ragged): the loss is the cross-entropy against them (train_step)."""
+        loss, scores = self.model_step_ragged(xs, ys, granule, total_nodes=1.0, labels=labels)
         self._loss_sum.copy_(loss.reshape(1))
         self._nodes.fill_(float(sum(int(x.shape[-1]) for x in xs)))
         return self._reduce_and_update(), scores
 
     # ------------------------------------------------------------------ captured constant-shape step
-    def _captured_step(self, x1, x2, bits=False):
-        """bits: x1, x2 are (B, N, ceil(N / 32)) int32 words of bit-packed adjacency instead of (B, c0, N, N) tensors."""
+    def _captured_step(self, x1, x2, bits=False, labels=None):
+        """bits: x1, x2 are (B, N, ceil(N / 32)) int32 words of bit-packed adjacency instead of (B, c0, N, N) tensors.
+        labels: (B, N) int32 device tensor or None.  A labelled step is a graph of its own (the key says which): its labels live in
+        a static buffer that every call copies into, like xs, so one trainer can hold and alternate both."""
         B, N = x1.shape[0], x1.shape[-2 if bits else -1]
         world = dp.world_size()
         key = (B, N, 'bits') if bits else (B, N)
+        if labels is not None:
+            key = key + ('labels',)
         st = self._graphs.get(key)
         if st is None:
             eng = self._engine(2 * B, N, False)
             xs = torch.cat([x1, x2]).contiguous().clone()
-            step = ((lambda: eng.step(self.params, self.grads, None, total_nodes=1.0, loss_out=self._loss_sum, bits=xs)) if bits else
-                    (lambda: eng.step(self.params, self.grads, xs, total_nodes=1.0, loss_out=self._loss_sum)))
+            lab = None if labels is None else labels.clone()
+            lkw = {} if lab is None else {'labels': lab}
+            step = ((lambda: eng.step(self.params, self.grads, None, total_nodes=1.0, loss_out=self._loss_sum, bits=xs, **lkw)) if bits else
+                    (lambda: eng.step(self.params, self.grads, xs, total_nodes=1.0, loss_out=self._loss_sum, **lkw)))
             self.opt.sync_hyper_parameters(grad_scale=None)
             # two eager steps on a side stream (allocations, kernel attributes); they do not touch the optimizer
             side = torch.cuda.Stream()
@@ -300,8 +316,8 @@ class FgnnTrainer:
                 with torch.cuda.graph(g_opt):
                     self.opt.step_dev(self.grads)
             self.opt.t = t0                               # a capture does not execute an update
-            st = self._graphs[key] = (xs, g_model, g_opt, scores, B)
-        xs, g_model, g_opt, scores, B = st
+            st = self._graphs[key] = (xs, g_model, g_opt, scores, B, lab)
+        xs, g_model, g_opt, scores, B, lab = st
         if tuple(x1.shape[1:]) != tuple(xs.shape[1:]) or tuple(x2.shape) != tuple(x1.shape):
             raise RuntimeError('FgnnTrainer: the captured step of (B, N) = (%d, %d) was recorded for batches of shape %s per side, got %s / '
                                '%s; a trainer captures one channel count per (B, N)' % (B, N, (B,) + tuple(xs.shape[1:]),
@@ -309,6 +325,8 @@ class FgnnTrainer:
         if x1.data_ptr() != xs.data_ptr():              # (train_step(input_form='tensor_representation') packs straight into xs)
             xs[:B].copy_(x1)
             xs[B:].copy_(x2)
+        if lab is not None and labels.data_ptr() != lab.data_ptr():
+            lab.copy_(labels)
         self._nodes.fill_(float(B * N))
         if g_opt is None:
             self.opt.sync_hyper_parameters(grad_scale=None)
@@ -342,19 +360,28 @@ class FgnnTrainer:
         self.check_input_form()
         return save_checkpoint(path, self.layout, self.params, optimizer=self.opt, **kw)
 
-    def train_step_bits(self, bits1, bits2, nvalid=None):
+    def _labels(self, labels, B, N):
+        """labels= of the train steps -> None or a (B, N) int32 device tensor (metrics.labels_tensor does the checking)"""
+        if labels is None:
+            return None
+        from .metrics import labels_tensor
+        return labels_tensor(labels, B, N, self.params.device)
+
+    def train_step_bits(self, bits1, bits2, nvalid=None, labels=None):
         """The same step with the local shard handed over as bit-packed adjacency: bits1, bits2
         (B, N, ceil(N / 32)) int32 device tensors, bit j of row i = W[i][j] (synthetic.pack_adjacency / the loader's packing); the
         tensor representation of loaders/data_generator.py:118-125 is built inside block 1's kernels, and with block1='structured'
-        block 1 runs on the class tables of csrc/block1_struct.hip.  nvalid: (B,) int32 for ragged batches (padded to N)."""
+        block 1 runs on the class tables of csrc/block1_struct.hip.  nvalid: (B,) int32 for ragged batches (padded to N).
+        labels: see train_step."""
         if bits1.dim() != 3 or bits1.shape != bits2.shape or bits1.dtype not in (torch.int32, torch.uint32) or not bits1.is_cuda:
             raise RuntimeError('FgnnTrainer.train_step_bits: expected two (B, N, ceil(N/32)) int32 device tensors, got %s %s / %s %s'
                                % (tuple(bits1.shape), bits1.dtype, tuple(bits2.shape), bits2.dtype))
         B, N = bits1.shape[0], bits1.shape[1]
         if bits1.shape[2] != (N + 31) // 32:
             raise RuntimeError('FgnnTrainer.train_step_bits: %d words per row for N = %d (expected %d)' % (bits1.shape[2], N, (N + 31) // 32))
+        labels = self._labels(labels, B, N)
         if self.capture and nvalid is None:
-            return self._captured_step(bits1, bits2, bits=True)
+            return self._captured_step(bits1, bits2, bits=True, labels=labels)
         eng = self._engine(2 * B, N, nvalid is not None)
         b = torch.cat([bits1, bits2]).contiguous()
         nv = None if nvalid is None else torch.cat([nvalid, nvalid]).to(torch.int32)
@@ -362,19 +389,26 @@ class FgnnTrainer:
             self._nodes.fill_(float(B * N))
         else:
             self._nodes.copy_(nvalid.sum().to(torch.float32).reshape(1))
-        scores, _ = eng.step(self.params, self.grads, None, nvalid=nv, total_nodes=1.0, loss_out=self._loss_sum, bits=b)
+        lkw = {} if labels is None else {'labels': labels}
+        scores, _ = eng.step(self.params, self.grads, None, nvalid=nv, total_nodes=1.0, loss_out=self._loss_sum, bits=b, **lkw)
         return self._reduce_and_update(), scores
 
-    def train_epoch(self, generator, sampler, epoch, batch_size):
+    def train_epoch(self, generator, sampler, epoch, batch_size, permute=False):
         """One epoch over a fixed dataset of on-device pairs, in the sampler's order (the reference's shuffled DataLoader over
         num_examples_train pairs): per step ``train_step_bits(*generator.bits(index=sampler.batch_index(epoch, step, batch_size)))``.
         generator: pairgen.PairGenerator; sampler: sampler.EpochSampler (its rank and world size are this process's).  The loop reads
         nothing back (a ragged generator's vertex counts stay on the device as well).  Returns the (steps,) device tensor of the
-        per-step losses of the global batch."""
+        per-step losses of the global batch.
+        permute=True: the pairs come relabelled (``generator.bits(index=..., permute=True)``) and the step trains on the
+        cross-entropy against their planted labels (train_step_bits(labels=...))."""
         steps = sampler.steps_per_epoch(batch_size)
         losses = torch.empty(steps, dtype=torch.float32, device=self.params.device)
         for step in range(steps):
-            loss, _ = self.train_step_bits(*generator.bits(index=sampler.batch_index(epoch, step, batch_size)))
+            if permute:
+                b1, b2, nv, lab = generator.bits(index=sampler.batch_index(epoch, step, batch_size), permute=True)
+                loss, _ = self.train_step_bits(b1, b2, nv, labels=lab)
+            else:
+                loss, _ = self.train_step_bits(*generator.bits(index=sampler.batch_index(epoch, step, batch_size)))
             losses[step].copy_(loss)
         return losses
 
@@ -389,10 +423,10 @@ class FgnnTrainer:
         scores, _ = eng.forward(self.params, x, nvalid=nv, total_nodes=1.0, defer_loss=False, loss_out=self._eval_loss, bits=bits)
         return scores
 
-    def eval_step_bits(self, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, hungarian=True):
+    def eval_step_bits(self, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False):
         """Forward-only evaluation of a batch handed over as train_step_bits takes it: the training engine's forward pass (a third of
-        a step's work), then evaluation.evaluate_scores on its scores -- see there for labels, meter, live, hungarian and the
-        returned per-pair device tensors.  Nothing is read back; parameters, gradients and optimizer state keep their bits."""
+        a step's work), then evaluation.evaluate_scores on its scores -- see there for labels, meter, live, hungarian,
+        loss_on_labels and the returned per-pair device tensors.  Nothing is read back; parameters, gradients and optimizer state keep their bits."""
         if bits1.dim() != 3 or bits1.shape != bits2.shape or bits1.dtype not in (torch.int32, torch.uint32) or not bits1.is_cuda:
             raise RuntimeError('FgnnTrainer.eval_step_bits: expected two (B, N, ceil(N/32)) int32 device tensors, got %s %s / %s %s'
                                % (tuple(bits1.shape), bits1.dtype, tuple(bits2.shape), bits2.dtype))
@@ -401,9 +435,10 @@ class FgnnTrainer:
             raise RuntimeError('FgnnTrainer.eval_step_bits: %d words per row for N = %d (expected %d)' % (bits1.shape[2], N, (N + 31) // 32))
         from .evaluation import evaluate_scores
         scores = self._eval_forward(B, N, nvalid, bits=torch.cat([bits1, bits2]).contiguous())
-        return evaluate_scores(scores, nvalid=nvalid, labels=labels, meter=meter, live=live, hungarian=hungarian)
+        return evaluate_scores(scores, nvalid=nvalid, labels=labels, meter=meter, live=live, hungarian=hungarian,
+                               **({'loss_on_labels': True} if loss_on_labels else {}))
 
-    def eval_step(self, x1, x2, nvalid=None, labels=None, meter=None, live=None, hungarian=True):
+    def eval_step(self, x1, x2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False):
         """eval_step_bits for dense batches: x1, x2 (B, c0, N, N) fp32 on the GPU, through the generic kernels (precision='bf16' with
         a 32-channel layout: any 1..32 channels, as train_step)."""
         if x1.dim() != 4 or x1.shape != x2.shape or not x1.is_cuda:
@@ -411,14 +446,17 @@ class FgnnTrainer:
                                % (tuple(x1.shape), tuple(x2.shape)))
         from .evaluation import evaluate_scores
         scores = self._eval_forward(x1.shape[0], x1.shape[-1], nvalid, x=torch.cat([x1, x2]).contiguous())
-        return evaluate_scores(scores, nvalid=nvalid, labels=labels, meter=meter, live=live, hungarian=hungarian)
+        return evaluate_scores(scores, nvalid=nvalid, labels=labels, meter=meter, live=live, hungarian=hungarian,
+                               **({'loss_on_labels': True} if loss_on_labels else {}))
 
-    def evaluate(self, generator, sampler, batch_size, epoch=0, hungarian=True, meter=None, permute=False):
+    def evaluate(self, generator, sampler, batch_size, epoch=0, hungarian=True, meter=None, permute=False, loss_on_labels=False):
         """One pass over this rank's examples of `sampler` (sampler.EpochSampler; shuffle=False is the reference's validation
         loader): per step ``eval_step_bits(*generator.bits(index=sampler.batch_index(epoch, step, batch_size)))`` with the generator's
         vertex counts and, with permute=True, its planted labels.  Every example counts exactly once: the positions with which a
         short last step is filled are masked out (live=sampler.live_count(...)).  With more than one rank the record is summed
-        over the ranks at the end (one all-reduce of 6 values).  Reads nothing back; returns the meter (EvalMeter)."""
+        over the ranks at the end (one all-reduce of 6 values).  Reads nothing back; returns the meter (EvalMeter).
+        loss_on_labels=True (with permute=True): the record's loss is the cross-entropy against the planted labels -- the model's
+        loss on those pairs, the one ReduceLROnPlateau should watch -- instead of the one against the identity."""
         from .evaluation import EvalMeter
         B = int(batch_size)
         if meter is None:
@@ -431,33 +469,48 @@ class FgnnTrainer:
                 continue
             kw = {'permute': True} if permute else {}
             b1, b2, nv, *labels = generator.bits(index=sampler.batch_index(epoch, step, B), **kw)
-            self.eval_step_bits(b1, b2, nvalid=nv, labels=labels[0] if labels else None, meter=meter, live=live, hungarian=hungarian)
+            if loss_on_labels:
+                kw = {'loss_on_labels': True}
+            else:
+                kw = {}
+            self.eval_step_bits(b1, b2, nvalid=nv, labels=labels[0] if labels else None, meter=meter, live=live, hungarian=hungarian, **kw)
         if dp.world_size() > 1:
             meter.allreduce_()
         return meter
 
-    def fit(self, train_gen, train_sampler, val_gen, val_sampler, epochs, batch_size, scheduler=None):
+    def fit(self, train_gen, train_sampler, val_gen, val_sampler, epochs, batch_size, scheduler=None, permute=False):
         """The reference's training loop around its scheduler (models/trainers.py:92-104): per epoch train_epoch, evaluate, ONE host
         read (the validation record), scheduler.step(val_loss).  scheduler=None: optim.ReduceLROnPlateau with the reference's
         settings, driving self.opt.lr (the next step pushes a changed rate to the device).  Returns the per-epoch history: dicts
         with 'epoch', 'train_losses' (the (steps,) device tensor of train_epoch), 'val_loss', 'val_acc', 'val_acc_max', 'lr' (the
-        rate the NEXT epoch runs with)."""
+        rate the NEXT epoch runs with).
+        permute=True: training and validation run on planted pairs (train_epoch(permute=True), evaluate(permute=True,
+        loss_on_labels=True)): 'val_loss' (what the scheduler sees), 'val_acc' and 'val_acc_max' all refer to the labels, and the
+        Hungarian accuracy is free of the identity tie bias."""
         if scheduler is None:
             from .optim import ReduceLROnPlateau
             scheduler = ReduceLROnPlateau(self.opt)
         history = []
         for epoch in range(int(epochs)):
-            losses = self.train_epoch(train_gen, train_sampler, epoch, batch_size)
-            res = self.evaluate(val_gen, val_sampler, batch_size, epoch=epoch).result()
+            if permute:
+                losses = self.train_epoch(train_gen, train_sampler, epoch, batch_size, permute=True)
+                res = self.evaluate(val_gen, val_sampler, batch_size, epoch=epoch, permute=True, loss_on_labels=True).result()
+            else:
+                losses = self.train_epoch(train_gen, train_sampler, epoch, batch_size)
+                res = self.evaluate(val_gen, val_sampler, batch_size, epoch=epoch).result()
             scheduler.step(res['loss'])
             history.append({'epoch': epoch, 'train_losses': losses, 'val_loss': res['loss'], 'val_acc': res['acc'],
                             'val_acc_max': res['acc_max'], 'lr': self.opt.lr})
         return history
 
-    def train_step(self, x1, x2, nvalid=None):
+    def train_step(self, x1, x2, nvalid=None, labels=None):
         """x1, x2: (B, c0, N, N) local shard on the GPU (precision='bf16' with a 32-channel layout: any 1..32 channels, e.g. the four
         spectral ones; the engine's input conversion zero-fills the rest).  Returns (loss of the global batch as a device
-        scalar, scores of the local shard)."""
+        scalar, scores of the local shard).
+        labels: None (the identity, the reference's target), or what metrics.labels_tensor takes -- a (B, N) integer tensor with
+        labels[b, i] = the vertex of x2[b] that vertex i of x1[b] matches (-1: no target), or a list of B integer arrays: the loss is
+        the cross-entropy against them (normalised by the node count as before).  An int32 device tensor is
+        read in place by the eager step and copied into the captured step's static buffer."""
         if self.input_form == 'tensor_representation' and x1.dim() == 4 and x1.shape[1] == 2 and self.layout.c0 == 2 \
                 and x1.dtype == torch.float32 and x1.shape == x2.shape:
             from . import _lib
@@ -476,12 +529,13 @@ class FgnnTrainer:
                 self._tr_calls += 1
                 if first or (self.INPUT_CHECK_EVERY and self._tr_calls % self.INPUT_CHECK_EVERY == 0):
                     self.check_input_form()
-                out = self.train_step_bits(w[:B], w[B:], nvalid=nv)
+                out = self.train_step_bits(w[:B], w[B:], nvalid=nv, **({} if labels is None else {'labels': labels}))
                 if first and (B, N, 'bits') in self._graphs:        # from now on pack straight into the captured step's input words
                     self._tr[(B, N)] = self._graphs[(B, N, 'bits')][0]
                 return out
+        labels = self._labels(labels, x1.shape[0], x1.shape[-1])
         if self.capture and nvalid is None:
-            return self._captured_step(x1, x2)
+            return self._captured_step(x1, x2, labels=labels)
         B, _, N, _ = x1.shape
         eng = self._engine(2 * B, N, nvalid is not None)
         x = torch.cat([x1, x2]).contiguous()
@@ -490,5 +544,6 @@ class FgnnTrainer:
             self._nodes.fill_(float(B * N))
         else:
             self._nodes.copy_(nvalid.sum().to(torch.float32).reshape(1))     # device-side, no host sync
-        scores, _ = eng.step(self.params, self.grads, x, nvalid=nv, total_nodes=1.0, loss_out=self._loss_sum)
+        lkw = {} if labels is None else {'labels': labels}
+        scores, _ = eng.step(self.params, self.grads, x, nvalid=nv, total_nodes=1.0, loss_out=self._loss_sum, **lkw)
         return self._reduce_and_update(), scores

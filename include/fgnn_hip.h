@@ -317,6 +317,24 @@ int fgnn_score_ce_bwd(const float *e1, const float *e2, const float *scores, con
                       const int *nvalid, const float *gscale, int B, int C, int N,
                       float *de1, float *de2, void *stream);
 
+/* ---- cross-entropy against labels: the four launches above with the target of row i of pair b taken from
+ * labels[b][i] (int32 (B, N), read in place; -1 in the padding, as planted.py / metrics.labels_tensor write it) instead of i:
+ *   loss_b = sum over i < n_b with 0 <= t_i < n_b of (lse_i - S[i][t_i]),    dS[i][j] = (exp(S_ij - lse_i) - [j == t_i]) * gscale.
+ * A live row whose label lies outside [0, n_b) has NO target (torch's ignore_index): it adds nothing to the loss, its row of dS is
+ * zero and nothing is indexed with it; lse is written for every live row as before.  The normaliser of the loss stays sum n_b (the
+ * reference divides by the node count, toolbox/losses.py:27-34), rows without a target included.  With labels[b][i] = i every
+ * output is bit-identical to the label-less entry point: the additions keep their order, the only differences are the index of
+ * the target score and the comparison j == t_i.  Geometry, form selection and LDS are those of the label-less launches (the
+ * backward stages the pair's labels in N more ints of LDS).  No scratch, no atomics; single capturable launches. */
+int fgnn_score_ce_fwd_blocks_labels(const float *e1, const float *e2, const int *nvalid, const int *labels, int B, int C, int N,
+                                    int row_blocks, float *scores, float *lse, float *pair_loss, void *stream);
+int fgnn_score_ce_bwd_labels(const float *e1, const float *e2, const float *scores, const float *lse, const int *nvalid,
+                             const int *labels, const float *gscale, int B, int C, int N, float *de1, float *de2, void *stream);
+int fgnn_ce_fwd_labels(const float *scores, const int *nvalid, const int *labels, int B, int N, float *lse, float *pair_loss,
+                       void *stream);
+int fgnn_ce_bwd_labels(const float *scores, const float *lse, const int *nvalid, const int *labels, const float *gscale, int B, int N,
+                       float *dscores, void *stream);
+
 /* triplet_loss on a given score tensor: lse (B,N), pair_loss (B) (toolbox/losses.py:27-34) */
 int fgnn_ce_fwd(const float *scores, const int *nvalid, int B, int N, float *lse, float *pair_loss, void *stream);
 /* dscores = (softmax_row(scores) - I) * (*gscale) on valid entries, 0 on padding */
@@ -929,6 +947,11 @@ typedef struct {
 } fgnn_eval_record;
 int fgnn_eval_pairs(const float *scores, const int *nvalid /* optional */, const int *labels /* optional */, int B, int N, float *cost,
                     long long cost_bstride, int cost_ld, float *row_ce, int *row_hit, void *stream);
+/* fgnn_eval_pairs with the cross-entropy against the labels as well (labels required): row_ce[b][i] = lse - s[i][t_i], t_i =
+ * labels[b][i], and 0 for a row whose label lies outside [0, n_b) (no target, see "cross-entropy against labels"); lse, the cost
+ * corner and row_hit are those of fgnn_eval_pairs with the same labels, bit for bit. */
+int fgnn_eval_pairs_labels(const float *scores, const int *nvalid /* optional */, const int *labels, int B, int N, float *cost,
+                           long long cost_bstride, int cost_ld, float *row_ce, int *row_hit, void *stream);
 int fgnn_eval_fold(const float *row_ce, const int *row_hit, const int *correct_lsap /* optional */, const int *nvalid /* optional */,
                    int B, int N, int live, double *pair_ce /* optional */, int *pair_max /* optional */, fgnn_eval_record *meter,
                    void *stream);
