@@ -18,6 +18,7 @@ FGNN_TILE = 32
 FGNN_MAX_DEPTH = 3
 FGNN_RANGE_WG = 256          # include/fgnn_hip.h
 FGNN_LSAP_MAX_N = 2048       # include/fgnn_hip.h: largest graph of fgnn_lsap_accuracy
+FGNN_MAX_LEVELS = 64         # include/fgnn_hip.h: noise levels of fgnn_pairgen_levels, records of fgnn_eval_fold_bins
 FGNN_QAP_MAX_N = 256         # include/fgnn_hip.h: largest graph of the fgnn_qap_* / fgnn_greedy_qap kernels
 FGNN_QAPW_MAX_N = 256        # include/fgnn_hip.h: largest graph of the fgnn_qapw_* / fgnn_greedy_qapw kernels (fp32 weights)
 FGNN_SPECTRAL_MAX_N = 256    # include/fgnn_hip.h: largest graph of fgnn_spectral_features
@@ -262,6 +263,7 @@ _SIGNATURES = {
     'fgnn_pairgen_supported': [_I, _I, _I],
     'fgnn_pairgen': [C.POINTER(PairgenArgs), _VP],
     'fgnn_pairgen_indexed': [C.POINTER(PairgenArgs), _VP, _VP],
+    'fgnn_pairgen_levels': [C.POINTER(PairgenArgs), _VP, _VP, _I, _VP, _VP],
     'fgnn_epoch_index': [C.c_ulonglong, C.c_ulonglong, _LL, _LL, _LL, _VP, _VP],
     'fgnn_qap_objective': [_VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP],
     'fgnn_qap_improve_cost': [_VP, _VP, _VP, _VP, _I, _I, _VP, _LL, _I, _VP],
@@ -282,6 +284,7 @@ _SIGNATURES = {
     'fgnn_eval_pairs': [_VP, _VP, _VP, _I, _I, _VP, _LL, _I, _VP, _VP, _VP],
     'fgnn_eval_pairs_labels': [_VP, _VP, _VP, _I, _I, _VP, _LL, _I, _VP, _VP, _VP],
     'fgnn_eval_fold': [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP],
+    'fgnn_eval_fold_bins': [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP],
     # ---- bf16 path ----
     'fgnn_tiles_per_graph16': [_I, _I],
     'fgnn_to_bf16': [_VP, _VP, _I, _I, _I, _I, _VP, _LL, _LL, _VP],

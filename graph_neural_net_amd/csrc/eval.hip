@@ -5,6 +5,7 @@
 //   fgnn_eval_pairs : ONE pass over the scores: per valid row the log-sum-exp, the cost row -log_softmax for fgnn_lsap_accuracy,
 //                     the cross-entropy against the identity and the arg-max hit.
 //   fgnn_eval_fold  : per-pair sums of those rows and the add into the epoch record, by one workgroup in a fixed order.
+//   fgnn_eval_fold_bins : the same fold into one record per bin (the noise levels of FgnnTrainer.noise_curve).
 // Both are plain launches on the caller's stream: capturable, no allocation, no copy, no synchronisation.
 #include "fgnn_common.h"
 
@@ -147,6 +148,63 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_fold_kernel(const float *ro
     }
 }
 
+// eval_fold_kernel with one record per bin: the per-pair sums are its code as it stands; thread k < K then owns record k and walks
+// the chunk's pairs in order, taking those of its bin.  A record that took no pair is not written, so its bytes stay.
+__global__ __launch_bounds__(EVAL_THREADS) void eval_fold_bins_kernel(const float *row_ce, const int *row_hit, const int *correct_lsap,
+                                                                      const int *nvalid, int B, int N, int live, const int *bin, int K,
+                                                                      double *pair_ce, int *pair_max, fgnn_eval_record *records) {
+    __shared__ double s_ce[EVAL_THREADS / WAVE];
+    __shared__ int s_hit[EVAL_THREADS / WAVE];
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+    const bool owner = (int)threadIdx.x < K;
+    double ce_sum = 0.0;
+    long long nodes = 0, c_lsap = 0, c_max = 0, pairs = 0;
+    if (owner) ce_sum = records[threadIdx.x].ce_sum;
+    for (int b0 = 0; b0 < live; b0 += EVAL_THREADS / WAVE) {         // (uniform bounds: every thread meets every barrier)
+        const int b = b0 + wave;
+        if (b < live) {
+            const int n = clamp_nv(nvalid, b, N);
+            double ce = 0.0;
+            int hit = 0;
+            for (int i = lane; i < n; i += WAVE) {
+                ce += (double)row_ce[(long long)b * N + i];
+                hit += row_hit[(long long)b * N + i];
+            }
+            for (int o = 32; o > 0; o >>= 1) {
+                ce += __shfl_xor(ce, o);
+                hit += __shfl_xor(hit, o);
+            }
+            if (lane == 0) {
+                s_ce[wave] = ce;
+                s_hit[wave] = hit;
+                if (pair_ce) pair_ce[b] = ce;
+                if (pair_max) pair_max[b] = hit;
+            }
+        }
+        __syncthreads();
+        if (owner) {
+            for (int w = 0; w < EVAL_THREADS / WAVE && b0 + w < live; ++w) {
+                if (bin[b0 + w] != (int)threadIdx.x) continue;
+                ce_sum += s_ce[w];
+                c_max += s_hit[w];
+                nodes += clamp_nv(nvalid, b0 + w, N);
+                if (correct_lsap) c_lsap += correct_lsap[b0 + w];
+                pairs += 1;
+            }
+        }
+        __syncthreads();
+    }
+    if (owner && pairs > 0) {
+        fgnn_eval_record *meter = records + threadIdx.x;
+        meter->ce_sum = ce_sum;
+        meter->nodes += nodes;
+        meter->correct_lsap += c_lsap;
+        meter->correct_max += c_max;
+        meter->pairs += pairs;
+        meter->steps += 1;
+    }
+}
+
 }  // namespace
 
 extern "C" int fgnn_eval_pairs(const float *scores, const int *nvalid, const int *labels, int B, int N, float *cost,
@@ -195,6 +253,18 @@ extern "C" int fgnn_eval_fold(const float *row_ce, const int *row_hit, const int
     FGNN_CHECK(live >= 0 && live <= B, "fgnn_eval_fold: live = %d outside [0, %d]", live, B);
     hipLaunchKernelGGL(eval_fold_kernel, dim3(1), dim3(EVAL_THREADS), 0, (hipStream_t)stream, row_ce, row_hit, correct_lsap, nvalid, B, N,
                        live, pair_ce, pair_max, meter);
+    FGNN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int fgnn_eval_fold_bins(const float *row_ce, const int *row_hit, const int *correct_lsap, const int *nvalid, int B, int N,
+                                   int live, const int *bin, int K, double *pair_ce, int *pair_max, fgnn_eval_record *records,
+                                   void *stream) {
+    FGNN_CHECK(row_ce && row_hit && bin && records && B > 0 && N > 0, "fgnn_eval_fold_bins: bad arguments");
+    FGNN_CHECK(live >= 0 && live <= B, "fgnn_eval_fold_bins: live = %d outside [0, %d]", live, B);
+    FGNN_CHECK(K >= 1 && K <= FGNN_MAX_LEVELS, "fgnn_eval_fold_bins: K = %d records outside [1, %d]", K, FGNN_MAX_LEVELS);
+    hipLaunchKernelGGL(eval_fold_bins_kernel, dim3(1), dim3(EVAL_THREADS), 0, (hipStream_t)stream, row_ce, row_hit, correct_lsap, nvalid,
+                       B, N, live, bin, K, pair_ce, pair_max, records);
     FGNN_LAUNCH_CHECK();
     return 0;
 }

@@ -12,7 +12,11 @@
 // those writes without a barrier.
 //
 // Which pair a workgroup builds is first + b (fgnn_pairgen) or index[b] (fgnn_pairgen_indexed); fgnn_epoch_index, at the end of the
-// file, writes such an index list: a window of the shuffled order of an epoch.
+// file, writes such an index list: a window of the shuffled order of an epoch.  fgnn_pairgen_levels
+// takes the two noise thresholds of workgroup b from a table row level[b] instead of the launch arguments: the draws of a pair
+// do not depend on the thresholds they are compared with, so one launch holds pairs of several noise levels (section 10.3).
+#include <type_traits>
+
 #include "fgnn_common.h"
 #include "fgnn_philox.h"
 
@@ -301,15 +305,36 @@ struct KArgs {
     int emax;                    // edge-list entries in LDS
     const long long *index;      // INDEXED: the pair of workgroup b is index[b]
 };
+struct KArgsLevels : KArgs {     // LEVELS (index may be NULL: first + b)
+    const unsigned long long *level_thr;      // (K, 2): thr_noise1, thr_noise2 of each level
+    const int *level;                         // (B): the level of workgroup b
+    int K;
+};
 
 // INDEXED: the pair of workgroup b is index[b] (fgnn_pairgen_indexed), else first + b (fgnn_pairgen: the kernel as it always was)
-template <bool INDEXED>
-__global__ __launch_bounds__(PG_THREADS) void pairgen_kernel(KArgs ka) {
+// LEVELS (fgnn_pairgen_levels; a kernel of its own, so that the other two keep their code and its placement): index[b] when there
+// is an index, and the noise thresholds are row level[b] of the table, read once per workgroup (wave-uniform values)
+template <bool INDEXED, bool LEVELS = false>
+__global__ __launch_bounds__(PG_THREADS) void pairgen_kernel(std::conditional_t<LEVELS, KArgsLevels, KArgs> ka) {
     extern __shared__ unsigned smem[];
     const fgnn_pairgen_args &a = ka.a;
     const int N = a.N, W = (N + 31) >> 5, lane = threadIdx.x;
-    const long long k = INDEXED ? ka.index[blockIdx.x] : a.first + blockIdx.x;
-    if (INDEXED && k < 0) {      // a caller error (fgnn_pairgen_indexed): the empty graph, wave-uniform exit before any barrier
+    long long k;
+    unsigned long long thr_noise1 = a.thr_noise1, thr_noise2 = a.thr_noise2;
+    if constexpr (LEVELS) {
+        k = ka.index ? ka.index[blockIdx.x] : a.first + blockIdx.x;
+        const int lv = ka.level[blockIdx.x];
+        if (lv < 0 || lv >= ka.K) {
+            k = -1;              // a level outside the table is a caller error like a negative index
+        } else {
+            thr_noise1 = ka.level_thr[2 * lv];
+            thr_noise2 = ka.level_thr[2 * lv + 1];
+        }
+    } else {
+        k = INDEXED ? ka.index[blockIdx.x] : a.first + blockIdx.x;
+    }
+    // a caller error (a negative index, or a level outside the table): the empty graph, wave-uniform exit before any barrier
+    if ((INDEXED || LEVELS) && k < 0) {
         const long long off = (long long)blockIdx.x * N * W;
         for (int i = lane; i < N * W; i += PG_THREADS) a.bits1[off + i] = a.bits2[off + i] = 0;
         if (a.nvalid && lane == 0) a.nvalid[blockIdx.x] = 0;
@@ -352,9 +377,9 @@ __global__ __launch_bounds__(PG_THREADS) void pairgen_kernel(KArgs ka) {
         for (int i = lane; i < N * W; i += PG_THREADS) rq[i] = rp[i];
         const int me = edge_list(rp, W, n, edges);
         __syncthreads();
-        noise_edge_swap(rq, W, edges, me, pr, a.thr_noise1);
+        noise_edge_swap(rq, W, edges, me, pr, thr_noise1);
     } else {
-        noise_erdos_renyi(rp, rq, W, n, N, pr, a.thr_noise1, a.thr_noise2);
+        noise_erdos_renyi(rp, rq, W, n, N, pr, thr_noise1, thr_noise2);
     }
     __syncthreads();
 
@@ -372,7 +397,7 @@ int host_regular_degree(int n, double p) {
     return d;
 }
 
-LdsAttrCache g_pairgen_lds, g_pairgen_indexed_lds;
+LdsAttrCache g_pairgen_lds, g_pairgen_indexed_lds, g_pairgen_levels_lds;
 
 }  // namespace
 
@@ -380,19 +405,34 @@ extern "C" int fgnn_pairgen_supported(int N, int family, int noise_model) {
     return N >= 1 && N <= FGNN_PAIRGEN_MAX_N && family >= 0 && family <= 2 && noise_model >= 0 && noise_model <= 1;
 }
 
-// the checks and the launch shared by fgnn_pairgen (index = NULL) and fgnn_pairgen_indexed
-static int launch_pairgen(const fgnn_pairgen_args *args, const long long *index, bool indexed, void *stream) {
+// which entry point a launch serves: it selects the kernel instance and what the launch reads beside the arguments
+enum class PairgenForm {
+    CONTIGUOUS,      // fgnn_pairgen: pair first + b
+    INDEXED,         // fgnn_pairgen_indexed: pair index[b]
+    LEVELS           // fgnn_pairgen_levels: pair index[b], or first + b without an index; noise thresholds from the level table
+};
+struct LevelTable {
+    const unsigned long long *thr;      // (K, 2)
+    int K;
+    const int *level;                   // (B)
+};
+
+// the checks and the launch shared by the three entry points (levels: the table of PairgenForm::LEVELS, else NULL)
+static int launch_pairgen(PairgenForm form, const fgnn_pairgen_args *args, const long long *index, const LevelTable *levels,
+                          void *stream) {
     FGNN_CHECK(args, "fgnn_pairgen: NULL arguments");
     const fgnn_pairgen_args &a = *args;
+    const bool by_index = form == PairgenForm::INDEXED || (form == PairgenForm::LEVELS && index);
+    const bool own_noise = form != PairgenForm::LEVELS;      // the noise thresholds of the arguments are used
     FGNN_CHECK(fgnn_pairgen_supported(a.N, a.family, a.noise_model), "fgnn_pairgen: unsupported N=%d family=%d noise_model=%d",
                a.N, a.family, a.noise_model);
-    FGNN_CHECK(a.B >= 0 && (indexed || a.first >= 0) && a.bits1 && a.bits2, "fgnn_pairgen: bad arguments (B=%d, first=%lld)", a.B,
+    FGNN_CHECK(a.B >= 0 && (by_index || a.first >= 0) && a.bits1 && a.bits2, "fgnn_pairgen: bad arguments (B=%d, first=%lld)", a.B,
                a.first);
-    FGNN_CHECK(!indexed || index || a.B == 0, "fgnn_pairgen_indexed: NULL index for B=%d pairs", a.B);
+    FGNN_CHECK(form != PairgenForm::INDEXED || index || a.B == 0, "fgnn_pairgen_indexed: NULL index for B=%d pairs", a.B);
     FGNN_CHECK(a.edge_density >= 0.0 && a.edge_density < 1.0, "fgnn_pairgen: edge_density %g outside [0, 1)", a.edge_density);
     FGNN_CHECK(a.swaps_per_edge >= 0 && a.swaps_per_edge <= 10000, "fgnn_pairgen: swaps_per_edge %d outside [0, 10000]",
                a.swaps_per_edge);
-    FGNN_CHECK(a.thr_edge <= THR_ONE && a.thr_noise1 <= THR_ONE && a.thr_noise2 <= THR_ONE && a.thr_vertex <= THR_ONE &&
+    FGNN_CHECK(a.thr_edge <= THR_ONE && (!own_noise || (a.thr_noise1 <= THR_ONE && a.thr_noise2 <= THR_ONE)) && a.thr_vertex <= THR_ONE &&
                    a.thr_vertex > 0, "fgnn_pairgen: thresholds outside [0, 2^32] (vertex threshold > 0)");
     FGNN_CHECK(a.thr_vertex == THR_ONE || a.N >= 2, "fgnn_pairgen: a binomial vertex count needs N >= 2");
     const int N = a.N;
@@ -411,25 +451,48 @@ static int launch_pairgen(const fgnn_pairgen_args *args, const long long *index,
     const int W = (N + 31) / 32;
     const size_t lds = (size_t)2 * N * W * 4 + 512 + (size_t)((emax + 1) & ~1ll) * 2 + (size_t)rep;
     FGNN_CHECK(lds <= 160 * 1024, "fgnn_pairgen: %zu bytes of LDS needed", lds);
-    FGNN_CHECK(fgnn_raise_lds(indexed ? g_pairgen_indexed_lds : g_pairgen_lds,
-                              indexed ? (const void *)pairgen_kernel<true> : (const void *)pairgen_kernel<false>, lds),
-               "fgnn_pairgen: cannot raise LDS to %zu bytes", lds);
-    KArgs ka;
+    const dim3 grid((unsigned)a.B), block(PG_THREADS);
+    KArgsLevels ka;      // (the first two forms pass its KArgs part)
     ka.a = a;
     ka.emax = (int)emax;
-    ka.index = indexed ? index : nullptr;
-    if (indexed)
-        hipLaunchKernelGGL(pairgen_kernel<true>, dim3((unsigned)a.B), dim3(PG_THREADS), lds, (hipStream_t)stream, ka);
-    else
-        hipLaunchKernelGGL(pairgen_kernel<false>, dim3((unsigned)a.B), dim3(PG_THREADS), lds, (hipStream_t)stream, ka);
+    ka.index = by_index ? index : nullptr;
+    switch (form) {
+    case PairgenForm::CONTIGUOUS:
+        FGNN_CHECK(fgnn_raise_lds(g_pairgen_lds, (const void *)pairgen_kernel<false>, lds), "fgnn_pairgen: cannot raise LDS to %zu bytes", lds);
+        hipLaunchKernelGGL(pairgen_kernel<false>, grid, block, lds, (hipStream_t)stream, (KArgs)ka);
+        break;
+    case PairgenForm::INDEXED:
+        FGNN_CHECK(fgnn_raise_lds(g_pairgen_indexed_lds, (const void *)pairgen_kernel<true>, lds), "fgnn_pairgen: cannot raise LDS to %zu bytes",
+                   lds);
+        hipLaunchKernelGGL(pairgen_kernel<true>, grid, block, lds, (hipStream_t)stream, (KArgs)ka);
+        break;
+    case PairgenForm::LEVELS:
+        FGNN_CHECK(fgnn_raise_lds(g_pairgen_levels_lds, (const void *)pairgen_kernel<true, true>, lds),
+                   "fgnn_pairgen_levels: cannot raise LDS to %zu bytes", lds);
+        ka.level_thr = levels->thr;
+        ka.level = levels->level;
+        ka.K = levels->K;
+        hipLaunchKernelGGL((pairgen_kernel<true, true>), grid, block, lds, (hipStream_t)stream, ka);
+        break;
+    }
     FGNN_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int fgnn_pairgen(const fgnn_pairgen_args *args, void *stream) { return launch_pairgen(args, nullptr, false, stream); }
+extern "C" int fgnn_pairgen(const fgnn_pairgen_args *args, void *stream) {
+    return launch_pairgen(PairgenForm::CONTIGUOUS, args, nullptr, nullptr, stream);
+}
 
 extern "C" int fgnn_pairgen_indexed(const fgnn_pairgen_args *args, const long long *index, void *stream) {
-    return launch_pairgen(args, index, true, stream);
+    return launch_pairgen(PairgenForm::INDEXED, args, index, nullptr, stream);
+}
+
+extern "C" int fgnn_pairgen_levels(const fgnn_pairgen_args *args, const long long *index, const unsigned long long *level_thr, int K,
+                                   const int *level, void *stream) {
+    FGNN_CHECK(K >= 1 && K <= FGNN_MAX_LEVELS, "fgnn_pairgen_levels: K=%d levels outside [1, %d]", K, FGNN_MAX_LEVELS);
+    FGNN_CHECK(level_thr && (level || !args || args->B == 0), "fgnn_pairgen_levels: NULL threshold table or level list");
+    const LevelTable levels{level_thr, K, level};
+    return launch_pairgen(PairgenForm::LEVELS, args, index, &levels, stream);
 }
 
 // ---- the order of a shuffled epoch (include/fgnn_hip.h; tests/epoch_ref.py restates it in numpy, bit for bit) -----------------

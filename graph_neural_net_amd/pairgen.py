@@ -33,6 +33,11 @@ duplicates allowed; one launch, ``fgnn_pairgen_indexed``).  The rank split: glob
 For an endless dataset the order is the identity (``bits(step * B * w + r * B, B)``); for the reference's fixed dataset reshuffled
 every epoch ``sampler.EpochSampler.batch_index`` gives the indices of those positions (``FgnnTrainer.train_epoch``).
 
+Several noise levels in one launch: ``levels = generator.levels(noises)`` builds the threshold table of up to 64 noise values and
+``bits`` / ``dense`` / ``spectral`` take ``levels=levels, level=`` (one level number per pair): pair b is the pair the same generator
+with ``noise=noises[level[b]]`` makes for that index, bit for bit, because a draw does not depend on the threshold it is compared
+with (``fgnn_pairgen_levels``; ``FgnnTrainer.noise_curve`` evaluates a model across noise levels with it).
+
 There is no CPU fallback (``_lib``).
 """
 import ctypes as C
@@ -54,6 +59,39 @@ MAX_N = 256                   # include/fgnn_hip.h: FGNN_PAIRGEN_MAX_N
 def threshold(prob):
     """Integer threshold of an event of probability prob on a raw 32-bit draw (u32 < thr)."""
     return min(1 << 32, int(math.floor(prob * 4294967296.0)))
+
+
+def same_device(a, b):
+    """Do two torch devices name the same device?  A CUDA device without an index ('cuda') is the current one, as torch places
+    tensors and as the launches here run; torch.device('cuda') == torch.device('cuda:0') is False even when 0 is current."""
+    a, b = torch.device(a), torch.device(b)
+    if a.type != b.type:
+        return False
+    if a.type != 'cuda' or a.index == b.index:
+        return True
+    cur = torch.cuda.current_device()
+    return (cur if a.index is None else a.index) == (cur if b.index is None else b.index)
+
+
+class NoiseLevels:
+    """The noise levels of a mixed launch (``PairGenerator.levels``): `noises`, the validated values as a tuple of floats; `table`,
+    the (K, 2) int64 device tensor of their thresholds (thr_noise1, thr_noise2 per level, as ``PairGenerator`` computes them for a
+    single noise value), built on the host."""
+
+    def __init__(self, noises, edge_density, device):
+        noises = tuple(float(v) for v in noises)
+        if not 1 <= len(noises) <= _lib.FGNN_MAX_LEVELS:
+            raise ValueError('between 1 and %d noise levels, got %d' % (_lib.FGNN_MAX_LEVELS, len(noises)))
+        for v in noises:
+            if not 0.0 <= v <= 1.0:
+                raise ValueError('noise must be in [0, 1], got %r' % (v,))
+        p = float(edge_density)
+        self.noises, self.edge_density = noises, p
+        self.thresholds = [(threshold(v), threshold(p * v / (1 - p))) for v in noises]
+        self.table = torch.tensor(self.thresholds, dtype=torch.int64).to(device)
+
+    def __len__(self):
+        return len(self.noises)
 
 
 class PairGenerator:
@@ -120,15 +158,45 @@ class PairGenerator:
             raise ValueError('index must be a 1-D int64 tensor, got shape %s, %s' % (tuple(index.shape), index.dtype))
         return 0, index.numel(), index.to(self.device).contiguous()
 
-    def bits(self, first=None, count=None, index=None, permute=False):
+    def levels(self, noises):
+        """The NoiseLevels of this generator's edge density for `noises` (1 to 64 values in [0, 1]): the `levels=` of bits / dense /
+        spectral.  `self.noise` does not enter it."""
+        return NoiseLevels(noises, self.edge_density, self.device)
+
+    def _need_gpu(self):
+        if self.device.type != 'cuda':
+            raise RuntimeError('PairGenerator: device %s; the generator runs on the GPU only (there is no CPU path)' % (self.device,))
+
+    def _level(self, levels, level, count):
+        """level= as a contiguous (count,) int32 tensor on the device (never read on the host), or None without levels"""
+        if levels is None and level is None:
+            return None
+        if levels is None or level is None:
+            raise ValueError('levels= (PairGenerator.levels) and level= (one level number per pair) go together')
+        if not isinstance(levels, NoiseLevels) or levels.edge_density != self.edge_density or not same_device(levels.table.device, self.device):
+            raise ValueError('levels must come from the levels() of this generator (edge density %r, device %s)'
+                             % (self.edge_density, self.device))
+        if not torch.is_tensor(level):
+            level = torch.tensor(level, dtype=torch.int32)
+        if level.dim() != 1 or level.numel() != count or level.is_floating_point() or level.dtype == torch.bool:
+            raise ValueError('level must be a (%d,) integer tensor, got shape %s, %s' % (count, tuple(level.shape), level.dtype))
+        return level.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def bits(self, first=None, count=None, index=None, permute=False, levels=None, level=None):
         """Pairs first .. first + count - 1, or the pairs index[0], index[1], ... (a 1-D int64 tensor, or a list; moved to the device
         if it is not there; any order, duplicates allowed) -> (bits1, bits2, nvalid): (count, N, ceil(N/32)) int32 device tensors
         and, when the vertex count is binomial, the (count,) int32 vertex counts (else None).  Enqueued on the current stream; the
         index is not read on the host: a negative entry (a caller error) gives the empty graph, all words zero and nvalid = 0.
-        permute=True: bits2 is relabelled by the planted permutation of each pair and (bits1, bits2, nvalid, labels) is returned."""
-        if self.device.type != 'cuda':
-            raise RuntimeError('PairGenerator: device %s; the generator runs on the GPU only (there is no CPU path)' % (self.device,))
+        permute=True: bits2 is relabelled by the planted permutation of each pair and (bits1, bits2, nvalid, labels) is returned.
+        levels, level: the NoiseLevels of `levels()` and one level number per pair ((count,) integer device tensor, or a list; not
+        read on the host): pair b gets the noise levels.noises[level[b]] instead of self.noise and is otherwise the same pair (the
+        planted permutation depends on (seed, index) only).  A level outside [0, K) is a caller error like a negative index."""
+        mixed = levels is not None or level is not None
+        if not mixed:       # (with levels every argument is checked before the device, so that the checks run anywhere)
+            self._need_gpu()
         first, count, index = self._selection(first, count, index)
+        level = self._level(levels, level, count)
+        self._need_gpu()
         N = self.n_vertices
         W = (N + 31) // 32
         with torch.cuda.device(self.device):
@@ -144,7 +212,10 @@ class PairGenerator:
                 a.swaps_per_edge = self.swaps_per_edge
                 a.bits1, a.bits2 = b1.data_ptr(), b2.data_ptr()
                 a.nvalid = nv.data_ptr() if nv is not None else None
-                if index is None:
+                if level is not None:
+                    _lib.call('fgnn_pairgen_levels', C.byref(a), _lib.ptr(index), _lib.ptr(levels.table), len(levels), _lib.ptr(level),
+                              _lib.stream_ptr())
+                elif index is None:
                     _lib.call('fgnn_pairgen', C.byref(a), _lib.stream_ptr())
                 else:
                     _lib.call('fgnn_pairgen_indexed', C.byref(a), _lib.ptr(index), _lib.stream_ptr())
@@ -156,12 +227,16 @@ class PairGenerator:
                 return b1, relabel_bits(b2, labels, nv), nv, labels
         return b1, b2, nv
 
-    def dense(self, first=None, count=None, index=None, permute=False):
+    @staticmethod
+    def _levels_kw(levels, level):
+        return {} if levels is None and level is None else {'levels': levels, 'level': level}
+
+    def dense(self, first=None, count=None, index=None, permute=False, levels=None, level=None):
         """The reference's collate structures for the same pairs: ({'input': x1}, {'input': x2}) with (count, 2, N, N) fp32
         tensor representations (collate_fn_pair_explore) for a constant vertex count, else two MaskedTensors padded to the
         largest n_i of the batch (collate_fn_pair; one host sync for that size).  permute=True: side 2 is the representation of
-        the relabelled graph and the (count, N) labels are appended to the return value."""
-        b1, b2, nv, *labels = self.bits(first, count, index, permute)
+        the relabelled graph and the (count, N) labels are appended to the return value.  levels, level: as in `bits`."""
+        b1, b2, nv, *labels = self.bits(first, count, index, permute, **self._levels_kw(levels, level))
         count = b1.shape[0]
         N = self.n_vertices
         x1, x2 = expand_adjacency(b1, N, nv), expand_adjacency(b2, N, nv)
@@ -171,14 +246,15 @@ class PairGenerator:
         x1, x2 = x1[:, :, :n, :n].contiguous(), x2[:, :, :n, :n].contiguous()
         return (MaskedTensor(x1, nv, (2, 3), 'N'), MaskedTensor(x2, nv, (2, 3), 'M'), *labels)
 
-    def spectral(self, first=None, count=None, n_powers=4, index=None, permute=False):
+    def spectral(self, first=None, count=None, n_powers=4, index=None, permute=False, levels=None, level=None):
         """The twin of `dense` for the reference's ``QAP_spectralGenerator`` (loaders/data_generator.py:221-277): the same pairs as
         `bits`, each side as the n_powers channels L, L^2, ... of ``spectral.spectral_features`` (one launch per side, straight from
         the bit rows; an isolated vertex gives a zero row and column where the reference gives NaN).  ({'input': F1}, {'input': F2})
         with (count, n_powers, N, N) fp32 tensors for a constant vertex count, else two MaskedTensors written directly at the
         largest n_i of the batch (one host sync for that size), with the names and masked dims of `dense`.  permute=True: side 2 is
-        computed from the relabelled bit rows and the (count, N) labels are appended to the return value."""
-        b1, b2, nv, *labels = self.bits(first, count, index, permute)
+        computed from the relabelled bit rows and the (count, N) labels are appended to the return value.  levels, level: as in
+        `bits`."""
+        b1, b2, nv, *labels = self.bits(first, count, index, permute, **self._levels_kw(levels, level))
         count = b1.shape[0]
         if nv is None:
             return ({'input': spectral_features(b1, None, n_powers)}, {'input': spectral_features(b2, None, n_powers)}, *labels)

@@ -423,10 +423,11 @@ class FgnnTrainer:
         scores, _ = eng.forward(self.params, x, nvalid=nv, total_nodes=1.0, defer_loss=False, loss_out=self._eval_loss, bits=bits)
         return scores
 
-    def eval_step_bits(self, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False):
+    def eval_step_bits(self, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False,
+                       bins=None):
         """Forward-only evaluation of a batch handed over as train_step_bits takes it: the training engine's forward pass (a third of
         a step's work), then evaluation.evaluate_scores on its scores -- see there for labels, meter, live, hungarian,
-        loss_on_labels and the returned per-pair device tensors.  Nothing is read back; parameters, gradients and optimizer state keep their bits."""
+        loss_on_labels, bins and the returned per-pair device tensors.  Nothing is read back; parameters, gradients and optimizer state keep their bits."""
         if bits1.dim() != 3 or bits1.shape != bits2.shape or bits1.dtype not in (torch.int32, torch.uint32) or not bits1.is_cuda:
             raise RuntimeError('FgnnTrainer.eval_step_bits: expected two (B, N, ceil(N/32)) int32 device tensors, got %s %s / %s %s'
                                % (tuple(bits1.shape), bits1.dtype, tuple(bits2.shape), bits2.dtype))
@@ -436,9 +437,9 @@ class FgnnTrainer:
         from .evaluation import evaluate_scores
         scores = self._eval_forward(B, N, nvalid, bits=torch.cat([bits1, bits2]).contiguous())
         return evaluate_scores(scores, nvalid=nvalid, labels=labels, meter=meter, live=live, hungarian=hungarian,
-                               **({'loss_on_labels': True} if loss_on_labels else {}))
+                               **({'loss_on_labels': True} if loss_on_labels else {}), **({} if bins is None else {'bins': bins}))
 
-    def eval_step(self, x1, x2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False):
+    def eval_step(self, x1, x2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False, bins=None):
         """eval_step_bits for dense batches: x1, x2 (B, c0, N, N) fp32 on the GPU, through the generic kernels (precision='bf16' with
         a 32-channel layout: any 1..32 channels, as train_step)."""
         if x1.dim() != 4 or x1.shape != x2.shape or not x1.is_cuda:
@@ -447,7 +448,7 @@ class FgnnTrainer:
         from .evaluation import evaluate_scores
         scores = self._eval_forward(x1.shape[0], x1.shape[-1], nvalid, x=torch.cat([x1, x2]).contiguous())
         return evaluate_scores(scores, nvalid=nvalid, labels=labels, meter=meter, live=live, hungarian=hungarian,
-                               **({'loss_on_labels': True} if loss_on_labels else {}))
+                               **({'loss_on_labels': True} if loss_on_labels else {}), **({} if bins is None else {'bins': bins}))
 
     def evaluate(self, generator, sampler, batch_size, epoch=0, hungarian=True, meter=None, permute=False, loss_on_labels=False):
         """One pass over this rank's examples of `sampler` (sampler.EpochSampler; shuffle=False is the reference's validation
@@ -475,6 +476,59 @@ class FgnnTrainer:
                 kw = {}
             self.eval_step_bits(b1, b2, nvalid=nv, labels=labels[0] if labels else None, meter=meter, live=live, hungarian=hungarian, **kw)
         if dp.world_size() > 1:
+            meter.allreduce_()
+        return meter
+
+    @staticmethod
+    def noise_curve_batch(sampler, step, batch_size, num_examples):
+        """This rank's batch at `step` of a noise curve over num_examples pairs per level: (pair, level, live).  The K * M examples
+        lie level-major -- example e is dataset pair e % M at level e // M -- and `sampler` is the unshuffled EpochSampler over
+        them; pair and level are (batch_size,) int64 tensors on the sampler's device (two integer ops, nothing is read), live the
+        number of leading positions that are examples of their own (the filling of a short last step wraps to example 0)."""
+        M = int(num_examples)
+        e = sampler.batch_index(0, step, batch_size)
+        return e % M, e // M, sampler.live_count(step, batch_size)
+
+    def noise_curve(self, generator, noises, num_examples, batch_size, hungarian=True, permute=False, loss_on_labels=False,
+                    rank=None, world_size=None, meter=None):
+        """The reference's result figure (README.md, "Results": a trained model evaluated across noise levels; per level
+        toolbox/metrics.py:144-166) in one pass: the first num_examples pairs of `generator` at each of the K = len(noises) noise
+        levels -- the SAME parent graphs at every level, a paired design -- through full batches of mixed levels
+        (``generator.bits(index=pair, levels=generator.levels(noises), level=level)``) and ``eval_step_bits(..., bins=level)`` into
+        a BinnedEvalMeter with one record per level.  `generator.noise` is ignored here: every pair takes the noise of its level.
+        The K * num_examples examples are cut by an unshuffled EpochSampler (rank, world_size: None is this process's rank and
+        the number of ranks of torch.distributed); every example counts once, a step with no live pair on this rank is skipped.
+        When the split is the one of torch.distributed (world_size left at None, or equal to its number of ranks, above 1) the
+        records are summed over the ranks at the end (one all-reduce of K x 6 values); with any other world_size -- 1 on every
+        rank for a whole curve each, or the parts of a split walked in one process -- the records stay this call's own.
+        hungarian, permute, loss_on_labels: as in `evaluate`.  meter: a BinnedEvalMeter of K records to accumulate into (None: a
+        fresh one whose values are the noises).  Reads nothing back: ``meter.result()``, K dicts with 'noise', 'loss', 'acc',
+        'acc_max', is the one host read.  Returns the meter."""
+        from .evaluation import BinnedEvalMeter
+        from .sampler import EpochSampler
+        levels = generator.levels(noises)
+        K, M, B = len(levels), int(num_examples), int(batch_size)
+        if M < 1:
+            raise ValueError('FgnnTrainer.noise_curve: num_examples must be >= 1, got %d' % M)
+        if meter is None:
+            meter = BinnedEvalMeter(self.params.device, K, values=levels.noises)
+        elif not isinstance(meter, BinnedEvalMeter) or meter.K != K:
+            raise ValueError('FgnnTrainer.noise_curve: meter must be a BinnedEvalMeter of %d records or None' % K)
+        if world_size is None:
+            world_size = dp.world_size()
+        if rank is None:        # (this process's rank in the split of torch.distributed; any other split has to name it)
+            rank = torch.distributed.get_rank() if world_size == dp.world_size() > 1 else 0
+        sampler = EpochSampler(K * M, shuffle=False, rank=rank, world_size=world_size, drop_last=False, device=generator.device)
+        kw = {'permute': True} if permute else {}
+        ekw = {'loss_on_labels': True} if loss_on_labels else {}
+        for step in range(sampler.steps_per_epoch(B)):
+            pair, level, live = self.noise_curve_batch(sampler, step, B, M)
+            if live == 0:       # (a rank past the end of the examples in the last global step)
+                continue
+            b1, b2, nv, *labels = generator.bits(index=pair, levels=levels, level=level, **kw)
+            self.eval_step_bits(b1, b2, nvalid=nv, labels=labels[0] if labels else None, meter=meter, live=live, hungarian=hungarian,
+                                bins=level, **ekw)
+        if dp.world_size() > 1 and sampler.world_size == dp.world_size():
             meter.allreduce_()
         return meter
 

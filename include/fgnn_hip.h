@@ -780,6 +780,15 @@ int fgnn_pairgen(const fgnn_pairgen_args *args, void *stream);
  * ignored, every stream, draw and output is that of the contiguous launch for the same pair.  A negative index is a caller error:
  * its pair is written as the empty graph (all words zero, nvalid = 0) and nothing outside index[0..B) is read. */
 int fgnn_pairgen_indexed(const fgnn_pairgen_args *args, const long long *index, void *stream);
+/* Pairs of several noise levels in one launch: pair b takes its two noise thresholds from row level[b] (int32[B] on the device) of
+ * level_thr ((K, 2) 64-bit words on the device: thr_noise1, thr_noise2 of each level; 1 <= K <= FGNN_MAX_LEVELS; 2^32 is noise 1);
+ * args->thr_noise1 / thr_noise2 are ignored.  Pair b is index[b], or args->first + b when index is NULL, and is what
+ * fgnn_pairgen_indexed writes for that dataset index with the thresholds of its level -- the same streams, draws and words: a draw
+ * does not depend on the threshold it is compared with.  EdgeSwap reads the first threshold only.  A level outside [0, K) is a
+ * caller error treated like a negative index: the empty graph, nvalid = 0. */
+#define FGNN_MAX_LEVELS 64
+int fgnn_pairgen_levels(const fgnn_pairgen_args *args, const long long *index /* NULL: args->first + b */,
+                        const unsigned long long *level_thr /* (K, 2) */, int K, const int *level /* (B) */, void *stream);
 
 /* ---- the order of a shuffled epoch (csrc/pairgen.hip; graph_neural_net_amd/sampler.py) ---------------------------------------
  * out[i] = pi((first_pos + i) mod M) for i < count, with pi the permutation of [0, M) that (seed, epoch) select: a balanced Feistel
@@ -955,6 +964,14 @@ int fgnn_eval_pairs_labels(const float *scores, const int *nvalid /* optional */
 int fgnn_eval_fold(const float *row_ce, const int *row_hit, const int *correct_lsap /* optional */, const int *nvalid /* optional */,
                    int B, int N, int live, double *pair_ce /* optional */, int *pair_max /* optional */, fgnn_eval_record *meter,
                    void *stream);
+/* fgnn_eval_fold with one record per bin (1 <= K <= FGNN_MAX_LEVELS records, contiguous): pair_ce / pair_max are those of
+ * fgnn_eval_fold, bit for bit; record k then receives the pairs b < live with bin[b] == k (int32[B] on the device) in ascending
+ * b, one pair at a time, and its `steps` advances only in a call that added a pair to it.  A pair whose bin lies outside [0, K) is
+ * ignored like a pair >= live.  Record k ends with the bytes fgnn_eval_fold leaves after folding just those pairs, in that order,
+ * into the same starting record; a record that received no pair is not written.  One workgroup, no floating-point atomics. */
+int fgnn_eval_fold_bins(const float *row_ce, const int *row_hit, const int *correct_lsap /* optional */, const int *nvalid /* optional */,
+                        int B, int N, int live, const int *bin /* (B) */, int K, double *pair_ce /* optional */,
+                        int *pair_max /* optional */, fgnn_eval_record *records /* K records */, void *stream);
 
 /* ---- test-only entry points (never on the product path; tests/ and tools/ call them) ---------------------------------------
  * fgnn_debug_mlp_fwd_masks / fgnn_debug_mlp_fwd_x3_masks: fgnn_mlp_fwd / fgnn_mlp_fwd_x3 once more -- the same tile code, the same
