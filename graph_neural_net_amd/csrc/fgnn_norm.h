@@ -1,5 +1,6 @@
-// GraphNorm record arithmetic shared by the finalize kernels (norm.hip) and by kernels that finalize a
-// producer's tile statistics in their own prologue (matmul.hip).
+// GraphNorm record arithmetic shared by the finalize kernels (norm.hip, block1_struct.hip, matmul16.hip) and by kernels that
+// finalize a producer's tile statistics in their own prologue (matmul.hip, pool_score.hip), and the record as a consumer
+// applies it (NormRec, norm_of, norm_from: matmul.hip).
 #pragma once
 #include "fgnn_common.h"
 
@@ -61,6 +62,37 @@ DEVI float4 finalize_reduce(const TilePartials &p, float nv, float w, float eps)
     m2 = wave_sum(m2);
     return nrm_record(mean, m2, sn, nv, w, eps);
 }
+
+// The record of channel c of graph g as a consumer applies it: y = (z - mean) * a + beta (`on` false: the slab is used raw).
+struct NormRec {
+    float mean, a, beta;
+    bool on;
+};
+DEVI NormRec norm_of(const fgnn_slab &s, int g, int c) {
+    NormRec r;
+    r.on = s.nrm != nullptr;
+    if (r.on) {
+        const float4 n = reinterpret_cast<const float4 *>(s.nrm)[(long long)g * s.C + c];
+        r.mean = n.x;
+        r.a = n.y;
+        r.beta = s.beta ? s.beta[c] : 0.f;
+    } else {
+        r.mean = 0.f;
+        r.a = 1.f;
+        r.beta = 0.f;
+    }
+    return r;
+}
+// the same from a record that the kernel has just finalized itself (FIN prologues): always on, beta from the slab
+DEVI NormRec norm_from(const float4 &n, const fgnn_slab &s, int c) {
+    NormRec r;
+    r.on = true;
+    r.mean = n.x;
+    r.a = n.y;
+    r.beta = s.beta ? s.beta[c] : 0.f;
+    return r;
+}
+
 DEVI float4 finalize_wave(const float *part, const float *cnt, int g, int c, int C, int tpg, float nv, float w, float eps,
                           int lane, bool tr = false) {
     return finalize_reduce(finalize_load(part, cnt, g, c, C, tpg, lane, tr), nv, w, eps);

@@ -14,27 +14,6 @@ namespace {
 constexpr int TM = 64;        // output tile edge
 constexpr int LDS_LD = 65;    // LDS row stride (floats)
 
-struct NormRec {
-    float mean, a, beta;
-    bool on;
-};
-
-DEVI NormRec norm_of(const fgnn_slab &s, int g, int c) {
-    NormRec r;
-    r.on = s.nrm != nullptr;
-    if (r.on) {
-        const float4 n = reinterpret_cast<const float4 *>(s.nrm)[(long long)g * s.C + c];
-        r.mean = n.x;
-        r.a = n.y;
-        r.beta = s.beta ? s.beta[c] : 0.f;
-    } else {
-        r.mean = 0.f;
-        r.a = 1.f;
-        r.beta = 0.f;
-    }
-    return r;
-}
-
 // Stage the [row0,row0+64) x [col0,col0+64) window of an N x N matrix into LDS (zero fill
 // outside the valid nv x nv region), optionally normalising.
 DEVI void stage_tile(float *lds, const float *mat, int N, int nv, int row0, int col0, const NormRec &nr, int tid) {
@@ -72,6 +51,29 @@ DEVI void store_quadrant(float *out, int N, int row0, int col0, const f32x16 &ac
     for (int r = 0; r < 16; ++r) {
         const int row = row0 + ch_of(r, h);
         if (row < N && col < N) out[(long long)row * N + col] = acc[r];
+    }
+}
+
+// S1 / S2 epilogue of the backward kernels that hold a whole matrix in one four-wave workgroup: the waves' sums of
+// {sa1, sa2, sb1, sb2} meet in `red` and are added in the fixed order (w0 + w1) + (w2 + w3); threads 0..3 write
+// s12a[gc] = {sa1, sa2} and s12b[gc] = {sb1, sb2}.
+DEVI void s12_epilogue(float (&red)[4][4], float sa1, float sa2, float sb1, float sb2, float *s12a, float *s12b, int gc, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    sa1 = wave_sum(sa1);
+    sa2 = wave_sum(sa2);
+    sb1 = wave_sum(sb1);
+    sb2 = wave_sum(sb2);
+    if (lane == 0) {
+        red[wave][0] = sa1;
+        red[wave][1] = sa2;
+        red[wave][2] = sb1;
+        red[wave][3] = sb2;
+    }
+    __syncthreads();
+    if (tid < 4) {
+        const float v = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+        float *dst = (tid < 2 ? s12a : s12b) + (long long)gc * 2 + (tid & 1);
+        *dst = v;
     }
 }
 
@@ -206,22 +208,7 @@ __global__ __launch_bounds__(256) void chan_matmul_bwd_kernel(const fgnn_slab ya
                 }
             }
         }
-        sa1 = wave_sum(sa1);
-        sa2 = wave_sum(sa2);
-        sb1 = wave_sum(sb1);
-        sb2 = wave_sum(sb2);
-        if (lane == 0) {
-            red[wave][0] = sa1;
-            red[wave][1] = sa2;
-            red[wave][2] = sb1;
-            red[wave][3] = sb2;
-        }
-        __syncthreads();
-        if (tid < 4) {
-            const float v = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-            float *dst = (tid < 2 ? s12a : s12b) + (long long)gc * 2 + (tid & 1);
-            *dst = v;
-        }
+        s12_epilogue(red, sa1, sa2, sb1, sb2, s12a, s12b, gc, tid);
     }
 }
 
@@ -351,8 +338,8 @@ __global__ __launch_bounds__(256, 4) void chan_matmul_fwd1_kernel(const fgnn_sla
             }
             __syncthreads();
             const float4 ra = fin_rec[0], rb = fin_rec[1];
-            na.on = true; na.mean = ra.x; na.a = ra.y; na.beta = ya.beta ? ya.beta[c] : 0.f;
-            nb.on = true; nb.mean = rb.x; nb.a = rb.y; nb.beta = yb.beta ? yb.beta[c] : 0.f;
+            na = norm_from(ra, ya, c);
+            nb = norm_from(rb, yb, c);
         } else {
             na = norm_of(ya, g, c);
             nb = norm_of(yb, g, c);
@@ -452,22 +439,7 @@ __global__ __launch_bounds__(256, 4) void chan_matmul_bwd1_kernel(const fgnn_sla
         if (s12a) {
             tile_to_global<true>(vOA, o_off, Ds, N, ua, sa1, sa2, tid);
             tile_to_global<true>(vOB, o_off, Bs, N, ub, sb1, sb2, tid);
-            sa1 = wave_sum(sa1);
-            sa2 = wave_sum(sa2);
-            sb1 = wave_sum(sb1);
-            sb2 = wave_sum(sb2);
-            if (lane == 0) {
-                red[wave][0] = sa1;
-                red[wave][1] = sa2;
-                red[wave][2] = sb1;
-                red[wave][3] = sb2;
-            }
-            __syncthreads();
-            if (tid < 4) {
-                const float v = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-                float *dst = (tid < 2 ? s12a : s12b) + (long long)gc * 2 + (tid & 1);
-                *dst = v;
-            }
+            s12_epilogue(red, sa1, sa2, sb1, sb2, s12a, s12b, gc, tid);
         } else {
             tile_to_global<false>(vOA, o_off, Ds, N, dummy, sa1, sa2, tid);
             tile_to_global<false>(vOB, o_off, Bs, N, dummy, sb1, sb2, tid);
@@ -505,6 +477,82 @@ DEVI float rsrc_load(rsrc_t r, int voff, int soff) {
 DEVI void rsrc_store(float x, rsrc_t r, int voff, int soff) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, x), r, voff, soff, 0);
 }
+DEVI float2 rsrc_load2(rsrc_t r, int voff, int soff) {
+    typedef unsigned u2 __attribute__((ext_vector_type(2)));
+    const u2 v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
+    const unsigned a = v.x, b = v.y;            // (copy the elements to scalars first: see the note on vector elements in DESIGN.md)
+    return make_float2(__builtin_bit_cast(float, a), __builtin_bit_cast(float, b));
+}
+DEVI void rsrc_store2(float x, float y, rsrc_t r, int voff, int soff) {
+    typedef unsigned u2 __attribute__((ext_vector_type(2)));
+    u2 v;
+    v.x = __builtin_bit_cast(unsigned, x);
+    v.y = __builtin_bit_cast(unsigned, y);
+    __builtin_amdgcn_raw_buffer_store_b64(v, r, voff, soff, 0);
+}
+
+// ---- what the two wave-per-matrix kernels (four-byte and eight-byte accesses) share ----
+// Pasted into both bodies: as functions (the context returned as a struct, the product loop taking the B value as a lambda) each
+// changed the instructions of every kernel of the pair ("What the per-channel product kernels share").
+// The wave's matrix pair: gc = (g, c), its vertex count, the wave's LDS tile `As` of LDS_FLOATS floats and the buffer descriptors --
+// the operands' end after row nv - 1, the output's after row N - 1.
+#define FGNN_W_CONTEXT(LDS_FLOATS)                                                                                       \
+    __shared__ __attribute__((aligned(16))) float lds[W_WAVES * (LDS_FLOATS)];                                           \
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                            \
+    const int gc = xcd_swizzle(blockIdx.x, gridDim.x) * W_WAVES + wv;                                                    \
+    if (gc >= M) return;                                                                                                 \
+    const int C = ya.C;                                                                                                  \
+    const int g = gc / C, c = gc - g * C;                                                                                \
+    const int nv = __builtin_amdgcn_readfirstlane(nvalid_of(nvalid, g, N));                                              \
+    const int j = lane & 31, h = lane >> 5;                                                                              \
+    float *As = lds + wv * (LDS_FLOATS);                                                                                 \
+    const rsrc_t rA = mat_rsrc(ya.ptr + (long long)g * ya.gstride + (long long)c * ya.ldp, nv * N * 4);                  \
+    const rsrc_t rB = mat_rsrc(yb.ptr + (long long)g * yb.gstride + (long long)c * yb.ldp, nv * N * 4);                  \
+    const rsrc_t rO = mat_rsrc(out + (long long)g * ogstride + (long long)c * ldo, N * N * 4);
+// acc[NB][NB] = the NB x NB independent accumulator chains over the 4 KQ k-steps: A from the wave's LDS tile (four k-steps per
+// ds_read_b128); BVAL fills bv[0 .. NB - 1], the normalised B values of k-step s.  k-steps past the matrix (k = 2 s >= N: up to
+// three of the last quartet) would add 0 * 0: skipped (uniform).
+#define FGNN_W_PRODUCTS(NB_, BVAL)                                                                                       \
+    f32x16 acc[NB_][NB_];                                                                                                \
+    _Pragma("unroll") for (int rb = 0; rb < NB_; ++rb)                                                                   \
+        _Pragma("unroll") for (int cb = 0; cb < NB_; ++cb)                                                               \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[rb][cb][r] = 0.f;                                         \
+    _Pragma("unroll") for (int q = 0; q < KQ; ++q) {                                                                     \
+        float4 af[NB_];                                                                                                  \
+        _Pragma("unroll") for (int rb = 0; rb < NB_; ++rb)                                                               \
+            af[rb] = *reinterpret_cast<const float4 *>(As + (32 * rb + j) * WLD + h * 32 + 4 * q);                       \
+        _Pragma("unroll") for (int t = 0; t < 4; ++t) {                                                                  \
+            const int s = 4 * q + t;                                                                                     \
+            if (q == KQ - 1 && 2 * s >= N) break;                                                                        \
+            float bv[NB_];                                                                                               \
+            BVAL                                                                                                         \
+            _Pragma("unroll") for (int rb = 0; rb < NB_; ++rb) {                                                         \
+                const float a = t == 0 ? af[rb].x : (t == 1 ? af[rb].y : (t == 2 ? af[rb].z : af[rb].w));               \
+                _Pragma("unroll") for (int cb = 0; cb < NB_; ++cb) acc[rb][cb] = mfma32(a, bv[cb], acc[rb][cb]);         \
+            }                                                                                                            \
+        }                                                                                                                \
+    }
+// The GraphNorm records of the two operands: read from the slabs, or (FIN) finalized from the partials ta, tb loaded earlier and
+// published by lane 0.  Both records first, then both beta values: norm_rec (fgnn_norm.h), which takes one operand at a time,
+// changed the instructions of every kernel of the pair.
+#define FGNN_W_RECORDS                                                                                                   \
+    float meanA, aA, meanB, aB;                                                                                          \
+    if (FIN) {                                                                                                           \
+        const float4 ra = finalize_reduce(ta, (float)nv, F.gw_a ? F.gw_a[c] : 1.f, F.eps);                               \
+        const float4 rb = finalize_reduce(tb, (float)nv, F.gw_b ? F.gw_b[c] : 1.f, F.eps);                               \
+        if (lane == 0) {                                                                                                 \
+            reinterpret_cast<float4 *>(F.nrm_a)[gc] = ra;                                                                \
+            reinterpret_cast<float4 *>(F.nrm_b)[gc] = rb;                                                                \
+        }                                                                                                                \
+        meanA = ra.x; aA = ra.y; meanB = rb.x; aB = rb.y;                                                                \
+    } else {                                                                                                             \
+        const NormRec na = norm_of(ya, g, c), nb = norm_of(yb, g, c);                                                    \
+        meanA = na.mean; aA = na.a; meanB = nb.mean; aB = nb.a;                                                          \
+    }                                                                                                                    \
+    const bool onA = FIN || ya.nrm != nullptr, onB = FIN || yb.nrm != nullptr;                                           \
+    const float betaA = (onA && ya.beta) ? ya.beta[c] : 0.f, betaB = (onB && yb.beta) ? yb.beta[c] : 0.f;
+// byte offset of the row of D-fragment register r of row block rb, less the half-wave's 4 h rows
+DEVI constexpr int wave_row_off(int rb, int r, int N) { return (32 * rb + (r & 3) + 8 * (r >> 2)) * N * 4; }
 
 // rows 0 .. 8*KQ-1 of one matrix, lane = column; rows >= N re-read row 0 (never used)
 template <int KQ>
@@ -535,18 +583,7 @@ __global__ __launch_bounds__(64 * W_WAVES, 2) void chan_matmul_fwd_w_kernel(cons
     constexpr int KH = 4 * KQ;
     constexpr bool TWO = KQ > 4;                       // N > 32: two row blocks x two column blocks
     constexpr int NB = TWO ? 2 : 1;
-    __shared__ __attribute__((aligned(16))) float lds[W_WAVES * 32 * NB * WLD];
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int gc = xcd_swizzle(blockIdx.x, gridDim.x) * W_WAVES + wv;
-    if (gc >= M) return;
-    const int C = ya.C;
-    const int g = gc / C, c = gc - g * C;
-    const int nv = __builtin_amdgcn_readfirstlane(nvalid_of(nvalid, g, N));
-    const int j = lane & 31, h = lane >> 5;
-    float *As = lds + wv * (32 * NB * WLD);
-    const rsrc_t rA = mat_rsrc(ya.ptr + (long long)g * ya.gstride + (long long)c * ya.ldp, nv * N * 4);
-    const rsrc_t rB = mat_rsrc(yb.ptr + (long long)g * yb.gstride + (long long)c * yb.ldp, nv * N * 4);
-    const rsrc_t rO = mat_rsrc(out + (long long)g * ogstride + (long long)c * ldo, N * N * 4);
+    FGNN_W_CONTEXT(32 * NB * WLD)
 
     TilePartials ta, tb;
     if (FIN) {
@@ -567,21 +604,7 @@ __global__ __launch_bounds__(64 * W_WAVES, 2) void chan_matmul_fwd_w_kernel(cons
 #pragma unroll
         for (int cb = 0; cb < NB; ++cb) xb[cb][s] = rsrc_load(rB, voffB[cb] + s * 2 * N * 4, 0);
     // ---- GraphNorm records ----
-    float meanA, aA, meanB, aB;
-    if (FIN) {
-        const float4 ra = finalize_reduce(ta, (float)nv, F.gw_a ? F.gw_a[c] : 1.f, F.eps);
-        const float4 rb = finalize_reduce(tb, (float)nv, F.gw_b ? F.gw_b[c] : 1.f, F.eps);
-        if (lane == 0) {
-            reinterpret_cast<float4 *>(F.nrm_a)[gc] = ra;
-            reinterpret_cast<float4 *>(F.nrm_b)[gc] = rb;
-        }
-        meanA = ra.x; aA = ra.y; meanB = rb.x; aB = rb.y;
-    } else {
-        const NormRec na = norm_of(ya, g, c), nb = norm_of(yb, g, c);
-        meanA = na.mean; aA = na.a; meanB = nb.mean; aB = nb.a;
-    }
-    const bool onA = FIN || ya.nrm != nullptr, onB = FIN || yb.nrm != nullptr;
-    const float betaA = (onA && ya.beta) ? ya.beta[c] : 0.f, betaB = (onB && yb.beta) ? yb.beta[c] : 0.f;
+    FGNN_W_RECORDS
     // ---- A: normalise, stage ----
     {
         const bool okc = lane < nv;
@@ -595,37 +618,7 @@ __global__ __launch_bounds__(64 * W_WAVES, 2) void chan_matmul_fwd_w_kernel(cons
         aeB[cb] = okc ? aB : 0.f;
         beB[cb] = okc ? betaB : 0.f;
     }
-    // ---- products: NB x NB independent accumulator chains ----
-    f32x16 acc[NB][NB];
-#pragma unroll
-    for (int rb = 0; rb < NB; ++rb)
-#pragma unroll
-        for (int cb = 0; cb < NB; ++cb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[rb][cb][r] = 0.f;
-#pragma unroll
-    for (int q = 0; q < KQ; ++q) {
-        float4 af[NB];
-#pragma unroll
-        for (int rb = 0; rb < NB; ++rb)
-            af[rb] = *reinterpret_cast<const float4 *>(As + (32 * rb + j) * WLD + h * 32 + 4 * q);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            // k-steps past the matrix (k = 2 (4 q + t) >= N: up to three of the last quartet) would add 0 * 0: skipped (uniform)
-            if (q == KQ - 1 && 2 * (4 * q + t) >= N) break;
-            float bv[NB];
-#pragma unroll
-            for (int cb = 0; cb < NB; ++cb) bv[cb] = (xb[cb][4 * q + t] - meanB) * aeB[cb] + beB[cb];
-#pragma unroll
-            for (int rb = 0; rb < NB; ++rb) {
-                const float a = t == 0 ? af[rb].x : (t == 1 ? af[rb].y : (t == 2 ? af[rb].z : af[rb].w));
-#pragma unroll
-                for (int cb = 0; cb < NB; ++cb) {
-                    acc[rb][cb] = mfma32(a, bv[cb], acc[rb][cb]);
-                }
-            }
-        }
-    }
+    FGNN_W_PRODUCTS(NB, _Pragma("unroll") for (int cb = 0; cb < NB; ++cb) bv[cb] = (xb[cb][s] - meanB) * aeB[cb] + beB[cb];)
     // ---- output: row 32 rb + ch_of(r, h), column 32 cb + j; rows >= N are out of range of the descriptor ----
 #pragma unroll
     for (int cb = 0; cb < NB; ++cb) {
@@ -634,7 +627,7 @@ __global__ __launch_bounds__(64 * W_WAVES, 2) void chan_matmul_fwd_w_kernel(cons
 #pragma unroll
         for (int rb = 0; rb < NB; ++rb)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) rsrc_store(acc[rb][cb][r], rO, voffO + (32 * rb + (r & 3) + 8 * (r >> 2)) * N * 4, 0);
+            for (int r = 0; r < 16; ++r) rsrc_store(acc[rb][cb][r], rO, voffO + wave_row_off(rb, r, N), 0);
     }
 }
 
@@ -649,20 +642,6 @@ __global__ __launch_bounds__(64 * W_WAVES, 2) void chan_matmul_fwd_w_kernel(cons
 // 56 loads in flight: one round trip.  Which lane computes which element changes, the arithmetic of an element does not (k order,
 // normalisation expression): bit-identical to the kernel above (tests/test_gpu_kernels.py).  An odd column that is padding is
 // selected to 0 after the load (its partner may be valid), an odd column beyond N is never stored.
-DEVI float2 rsrc_load2(rsrc_t r, int voff, int soff) {
-    typedef unsigned u2 __attribute__((ext_vector_type(2)));
-    const u2 v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
-    const unsigned a = v.x, b = v.y;            // (copy the elements to scalars first: see the note on vector elements in DESIGN.md)
-    return make_float2(__builtin_bit_cast(float, a), __builtin_bit_cast(float, b));
-}
-DEVI void rsrc_store2(float x, float y, rsrc_t r, int voff, int soff) {
-    typedef unsigned u2 __attribute__((ext_vector_type(2)));
-    u2 v;
-    v.x = __builtin_bit_cast(unsigned, x);
-    v.y = __builtin_bit_cast(unsigned, y);
-    __builtin_amdgcn_raw_buffer_store_b64(v, r, voff, soff, 0);
-}
-
 template <int KQ, bool FIN>
 __global__ __launch_bounds__(64 * W_WAVES, 2) void chan_matmul_fwd_w2_kernel(const fgnn_slab ya, const fgnn_slab yb,
                                                                             const int *nvalid, int N, int M, float *out,
@@ -670,18 +649,7 @@ __global__ __launch_bounds__(64 * W_WAVES, 2) void chan_matmul_fwd_w2_kernel(con
                                                                             const FinArgs F) {
     static_assert(KQ > 4, "two column blocks: 32 < N <= 64");
     constexpr int KH = 4 * KQ;                         // k-steps; also: row PAIRS of A
-    __shared__ __attribute__((aligned(16))) float lds[W_WAVES * 64 * WLD];
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int gc = xcd_swizzle(blockIdx.x, gridDim.x) * W_WAVES + wv;
-    if (gc >= M) return;
-    const int C = ya.C;
-    const int g = gc / C, c = gc - g * C;
-    const int nv = __builtin_amdgcn_readfirstlane(nvalid_of(nvalid, g, N));
-    const int j = lane & 31, h = lane >> 5;
-    float *As = lds + wv * (64 * WLD);
-    const rsrc_t rA = mat_rsrc(ya.ptr + (long long)g * ya.gstride + (long long)c * ya.ldp, nv * N * 4);
-    const rsrc_t rB = mat_rsrc(yb.ptr + (long long)g * yb.gstride + (long long)c * yb.ldp, nv * N * 4);
-    const rsrc_t rO = mat_rsrc(out + (long long)g * ogstride + (long long)c * ldo, N * N * 4);
+    FGNN_W_CONTEXT(64 * WLD)
 
     TilePartials ta, tb;
     if (FIN) {
@@ -700,21 +668,7 @@ __global__ __launch_bounds__(64 * W_WAVES, 2) void chan_matmul_fwd_w2_kernel(con
         for (int s = 0; s < KH; ++s) xb[s] = rsrc_load2(rB, voffB, 2 * s < N ? 2 * s * N * 4 : 0);
     }
     // ---- GraphNorm records ----
-    float meanA, aA, meanB, aB;
-    if (FIN) {
-        const float4 ra = finalize_reduce(ta, (float)nv, F.gw_a ? F.gw_a[c] : 1.f, F.eps);
-        const float4 rb = finalize_reduce(tb, (float)nv, F.gw_b ? F.gw_b[c] : 1.f, F.eps);
-        if (lane == 0) {
-            reinterpret_cast<float4 *>(F.nrm_a)[gc] = ra;
-            reinterpret_cast<float4 *>(F.nrm_b)[gc] = rb;
-        }
-        meanA = ra.x; aA = ra.y; meanB = rb.x; aB = rb.y;
-    } else {
-        const NormRec na = norm_of(ya, g, c), nb = norm_of(yb, g, c);
-        meanA = na.mean; aA = na.a; meanB = nb.mean; aB = nb.a;
-    }
-    const bool onA = FIN || ya.nrm != nullptr, onB = FIN || yb.nrm != nullptr;
-    const float betaA = (onA && ya.beta) ? ya.beta[c] : 0.f, betaB = (onB && yb.beta) ? yb.beta[c] : 0.f;
+    FGNN_W_RECORDS
     // ---- A: normalise, stage rows 2 p + h: even column -> position j, odd column -> position 32 + j ----
     {
         const float a0 = ok0 ? aA : 0.f, b0 = ok0 ? betaA : 0.f, a1 = ok1 ? aA : 0.f, b1 = ok1 ? betaA : 0.f;
@@ -728,35 +682,10 @@ __global__ __launch_bounds__(64 * W_WAVES, 2) void chan_matmul_fwd_w2_kernel(con
             As[row * WLD + 32 + j] = rok ? v1 : 0.f;
         }
     }
+    // ---- products: column block q = columns 2 j + q ----
     const float aeB[2] = {ok0 ? aB : 0.f, ok1 ? aB : 0.f}, beB[2] = {ok0 ? betaB : 0.f, ok1 ? betaB : 0.f};
-    // ---- products: 2 x 2 independent accumulator chains; column block q = columns 2 j + q ----
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[rb][cb][r] = 0.f;
-#pragma unroll
-    for (int q = 0; q < KQ; ++q) {
-        float4 af[2];
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-            af[rb] = *reinterpret_cast<const float4 *>(As + (32 * rb + j) * WLD + h * 32 + 4 * q);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            if (q == KQ - 1 && 2 * (4 * q + t) >= N) break;      // k-steps past the matrix: skipped (uniform), as above
-            float bv[2];
-            bv[0] = (xb[4 * q + t].x - meanB) * aeB[0] + beB[0];
-            bv[1] = ((ok1 ? xb[4 * q + t].y : 0.f) - meanB) * aeB[1] + beB[1];
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb) {
-                const float a = t == 0 ? af[rb].x : (t == 1 ? af[rb].y : (t == 2 ? af[rb].z : af[rb].w));
-#pragma unroll
-                for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mfma32(a, bv[cb], acc[rb][cb]);
-            }
-        }
-    }
+    FGNN_W_PRODUCTS(2, bv[0] = (xb[s].x - meanB) * aeB[0] + beB[0];
+                       bv[1] = ((ok1 ? xb[s].y : 0.f) - meanB) * aeB[1] + beB[1];)
     // ---- output: row 32 rb + ch_of(r, h), columns (2 j, 2 j + 1); rows >= N are out of range of the descriptor ----
     {
         const bool two = 2 * j + 1 < N;
@@ -765,9 +694,8 @@ __global__ __launch_bounds__(64 * W_WAVES, 2) void chan_matmul_fwd_w2_kernel(con
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int soff = (32 * rb + (r & 3) + 8 * (r >> 2)) * N * 4;
-                if (two) rsrc_store2(acc[rb][0][r], acc[rb][1][r], rO, voffO, soff);
-                else rsrc_store(acc[rb][0][r], rO, voffO, soff);
+                if (two) rsrc_store2(acc[rb][0][r], acc[rb][1][r], rO, voffO, wave_row_off(rb, r, N));
+                else rsrc_store(acc[rb][0][r], rO, voffO, wave_row_off(rb, r, N));
             }
     }
 }
@@ -781,15 +709,8 @@ int launch_fwd_w(const fgnn_slab *ya, const fgnn_slab *yb, const int *nvalid, in
     // the instruction count is not what limits the kernel below N ~ 58 (it moves its 61 MB at the ~4 TB/s this part reads at), so
     // the eight-byte form runs where it wins: KQ = 8, even N (an odd N would let a column pair straddle two rows).
     if (KQ == 8 && !mm_narrow() && (N & 1) == 0) {
-#define FGNN_W2(K_)                                                                                                       \
-    case K_:                                                                                                             \
-        hipLaunchKernelGGL((chan_matmul_fwd_w2_kernel<K_, FIN>), dim3(grid), dim3(64 * W_WAVES), 0, st, *ya, *yb, nvalid, N, \
-                           M, out, ogstride, ldo, F);                                                                    \
-        break;
-        switch (KQ) {
-            FGNN_W2(8)
-        }
-#undef FGNN_W2
+        hipLaunchKernelGGL((chan_matmul_fwd_w2_kernel<8, FIN>), dim3(grid), dim3(64 * W_WAVES), 0, st, *ya, *yb, nvalid, N, M, out,
+                           ogstride, ldo, F);
         return 0;
     }
 #define FGNN_W(K_)                                                                                                       \
@@ -1106,8 +1027,8 @@ __global__ __launch_bounds__(BIG_THREADS) void chan_matmul_fwd_big_kernel(const 
         }
         __syncthreads();
         const float4 ra = fin_rec[0], rb = fin_rec[1];
-        A.nr.on = true; A.nr.mean = ra.x; A.nr.a = ra.y; A.nr.beta = ya.beta ? ya.beta[c] : 0.f;
-        B.nr.on = true; B.nr.mean = rb.x; B.nr.a = rb.y; B.nr.beta = yb.beta ? yb.beta[c] : 0.f;
+        A.nr = norm_from(ra, ya, c);
+        B.nr = norm_from(rb, yb, c);
     }
     const View vO = make_view(out, ogstride, ldo, G);
     const int o_off = g * vO.gs4 + c * vO.ld4;
@@ -1191,6 +1112,41 @@ static void launch_fwd_big(const fgnn_slab *ya, const fgnn_slab *yb, const int *
                        ogstride, ldo, order, F, fill);
 }
 
+// 32-bit buffer addressing: G graphs of every stride given (in floats; 0: not used) stay below 2 GiB
+static int check_2gib(const char *name, int G, long long s0, long long s1, long long s2 = 0, long long s3 = 0) {
+    FGNN_CHECK((long long)G * s0 < 0x7fffffffll / 4 && (long long)G * s1 < 0x7fffffffll / 4 && (long long)G * s2 < 0x7fffffffll / 4 &&
+               (long long)G * s3 < 0x7fffffffll / 4,
+               "%s: a tensor exceeds 2 GiB (32-bit buffer addressing); split the batch", name);
+    return 0;
+}
+
+// The form of the forward product for a shape, once for the four entry points: one wave or one workgroup per matrix (N <= 64), the
+// whole matrix in one workgroup (64 < N <= 256, at most 4 or 8 tiles per side), generic tiles beyond (records must exist: no FIN form).
+template <bool FIN>
+static int chan_matmul_fwd_dispatch(const char *name, const fgnn_slab *ya, const fgnn_slab *yb, const int *nvalid, int G, int N,
+                                    float *out, long long ogstride, long long ldo, const int *order, int fill, const FinArgs &F,
+                                    hipStream_t st) {
+    const int M = G * ya->C;
+    if (FIN || big_path(N)) {
+        if (check_2gib(name, G, ya->gstride, yb->gstride, ogstride)) return 1;
+    } else if (N <= TM) {
+        if (check_2gib(name, G, ya->gstride, yb->gstride)) return 1;
+        FGNN_CHECK((long long)G * ogstride < 0x7fffffffll / 4, "%s: output exceeds 2 GiB", name);
+    }
+    if (N <= TM) {
+        if (mm_wave_variant()) launch_fwd_w<FIN>(ya, yb, nvalid, N, M, out, ogstride, ldo, F, st);
+        else hipLaunchKernelGGL(chan_matmul_fwd1_kernel<FIN>, dim3(M), dim3(256), 0, st, *ya, *yb, nvalid, N, M, out, ogstride, ldo, F);
+    } else if (big_path(N)) {
+        if (N <= 128) launch_fwd_big<4, FIN>(ya, yb, nvalid, N, G, out, ogstride, ldo, order, F, fill, st);
+        else launch_fwd_big<8, FIN>(ya, yb, nvalid, N, G, out, ogstride, ldo, order, F, fill, st);
+    } else if constexpr (!FIN) {
+        const int t = (N + TM - 1) / TM;
+        hipLaunchKernelGGL(chan_matmul_fwd_kernel, dim3(t, t, M), dim3(256), 0, st, *ya, *yb, nvalid, N, out, ogstride, ldo);
+    }
+    FGNN_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int fgnn_chan_matmul_fwd(const fgnn_slab *ya, const fgnn_slab *yb, const int *nvalid, int G, int N,
                                     float *out, long long ogstride, long long ldo, void *stream) {
     return fgnn_chan_matmul_fwd_ord(ya, yb, nvalid, G, N, out, ogstride, ldo, nullptr, 0, stream);
@@ -1202,41 +1158,15 @@ extern "C" int fgnn_chan_matmul_fwd_ord(const fgnn_slab *ya, const fgnn_slab *yb
     FGNN_CHECK(ya && yb && out && ya->ptr && yb->ptr, "fgnn_chan_matmul_fwd: null argument");
     FGNN_CHECK(ya->C == yb->C && ya->C > 0 && G > 0 && N > 0, "fgnn_chan_matmul_fwd: bad shapes");
     FGNN_CHECK((long long)G * ya->C <= 65535 * 1024ll, "fgnn_chan_matmul_fwd: G*C too large");
-    const int t = (N + TM - 1) / TM;
-    if (t == 1) {
-        FGNN_CHECK((long long)G * ya->gstride < 0x7fffffffll / 4 && (long long)G * yb->gstride < 0x7fffffffll / 4,
-                   "fgnn_chan_matmul_fwd: a tensor exceeds 2 GiB (32-bit buffer addressing); split the batch");
-        FGNN_CHECK((long long)G * ogstride < 0x7fffffffll / 4, "fgnn_chan_matmul_fwd: output exceeds 2 GiB");
-        const int M = G * ya->C;
-        if (mm_wave_variant()) {
-            launch_fwd_w<false>(ya, yb, nvalid, N, M, out, ogstride, ldo, FinArgs{}, (hipStream_t)stream);
-            FGNN_LAUNCH_CHECK();
-            return 0;
-        }
-        hipLaunchKernelGGL(chan_matmul_fwd1_kernel<false>, dim3(M), dim3(256), 0, (hipStream_t)stream, *ya, *yb, nvalid,
-                           N, M, out, ogstride, ldo, FinArgs{});
-        FGNN_LAUNCH_CHECK();
-        return 0;
-    }
-    if (big_path(N)) {
-        FGNN_CHECK((long long)G * ya->gstride < 0x7fffffffll / 4 && (long long)G * yb->gstride < 0x7fffffffll / 4 &&
-                   (long long)G * ogstride < 0x7fffffffll / 4,
-                   "fgnn_chan_matmul_fwd: a tensor exceeds 2 GiB (32-bit buffer addressing); split the batch");
-        if (N <= 128) launch_fwd_big<4, false>(ya, yb, nvalid, N, G, out, ogstride, ldo, order, FinArgs{}, fill, (hipStream_t)stream);
-        else launch_fwd_big<8, false>(ya, yb, nvalid, N, G, out, ogstride, ldo, order, FinArgs{}, fill, (hipStream_t)stream);
-        FGNN_LAUNCH_CHECK();
-        return 0;
-    }
-    hipLaunchKernelGGL(chan_matmul_fwd_kernel, dim3(t, t, G * ya->C), dim3(256), 0, (hipStream_t)stream, *ya, *yb,
-                       nvalid, N, out, ogstride, ldo);
-    FGNN_LAUNCH_CHECK();
-    return 0;
+    return chan_matmul_fwd_dispatch<false>("fgnn_chan_matmul_fwd", ya, yb, nvalid, G, N, out, ogstride, ldo, order, fill, FinArgs{},
+                                           (hipStream_t)stream);
 }
 
 extern "C" int fgnn_chan_matmul_fwd_fin_supported(int N) { return (N <= TM || big_path(N)) ? 1 : 0; }
 
-// debug only (tests/test_gpu_kernels.py, tests/diag/gpu_mm_variants_equal.py): bit 0 clear selects the workgroup-per-matrix forward
-// kernel for N <= 64, bit 3 the four-byte-access form of the wave-per-matrix kernel; both reproduce the default bit for bit
+// debug only (tests/test_gpu_kernels.py, tests/diag/gpu_mm_variants_equal.py), N <= 64: 1 (the default) the wave-per-matrix forward
+// kernel, with eight-byte accesses where that form runs; 9 its four-byte form at every N; 0 the workgroup-per-matrix kernel.  All
+// three give the same bits.
 extern "C" int fgnn_debug_matmul_variant(int wave_per_matrix) {
     FGNN_CHECK((wave_per_matrix & ~9) == 0, "fgnn_debug_matmul_variant: bits 0 and 3 only (got %d)", wave_per_matrix);
     g_mm_wave_variant = wave_per_matrix;
@@ -1259,27 +1189,10 @@ extern "C" int fgnn_chan_matmul_fwd_fin_ord(const fgnn_slab *ya, const fgnn_slab
     FGNN_CHECK(ya->nrm && yb->nrm, "fgnn_chan_matmul_fwd_fin: the slabs must carry the record buffers to fill");
     FGNN_CHECK(ya->C == yb->C && ya->C > 0 && G > 0 && N > 0, "fgnn_chan_matmul_fwd_fin: bad shapes");
     FGNN_CHECK(N <= TM || big_path(N), "fgnn_chan_matmul_fwd_fin: N=%d > 256 (use fgnn_gn_finalize2 + fgnn_chan_matmul_fwd)", N);
-    FGNN_CHECK((long long)G * ya->gstride < 0x7fffffffll / 4 && (long long)G * yb->gstride < 0x7fffffffll / 4 &&
-               (long long)G * ogstride < 0x7fffffffll / 4,
-               "fgnn_chan_matmul_fwd_fin: a tensor exceeds 2 GiB (32-bit buffer addressing); split the batch");
-    const int M = G * ya->C;
-    FinArgs F = {part_a, part_b, cnt, gn_weight_a, gn_weight_b, const_cast<float *>(ya->nrm), const_cast<float *>(yb->nrm), eps,
-                 fgnn_tiles_per_graph(N)};
-    if (big_path(N)) {
-        if (N <= 128) launch_fwd_big<4, true>(ya, yb, nvalid, N, G, out, ogstride, ldo, order, F, fill, (hipStream_t)stream);
-        else launch_fwd_big<8, true>(ya, yb, nvalid, N, G, out, ogstride, ldo, order, F, fill, (hipStream_t)stream);
-        FGNN_LAUNCH_CHECK();
-        return 0;
-    }
-    if (mm_wave_variant()) {
-        launch_fwd_w<true>(ya, yb, nvalid, N, M, out, ogstride, ldo, F, (hipStream_t)stream);
-        FGNN_LAUNCH_CHECK();
-        return 0;
-    }
-    hipLaunchKernelGGL(chan_matmul_fwd1_kernel<true>, dim3(M), dim3(256), 0, (hipStream_t)stream, *ya, *yb, nvalid, N, M, out,
-                       ogstride, ldo, F);
-    FGNN_LAUNCH_CHECK();
-    return 0;
+    const FinArgs F = {part_a, part_b, cnt, gn_weight_a, gn_weight_b, const_cast<float *>(ya->nrm), const_cast<float *>(yb->nrm), eps,
+                       fgnn_tiles_per_graph(N)};
+    return chan_matmul_fwd_dispatch<true>("fgnn_chan_matmul_fwd_fin", ya, yb, nvalid, G, N, out, ogstride, ldo, order, fill, F,
+                                          (hipStream_t)stream);
 }
 
 extern "C" int fgnn_chan_matmul_bwd(const fgnn_slab *ya, const fgnn_slab *yb, const float *dm, long long dmgstride,
@@ -1301,9 +1214,7 @@ extern "C" int fgnn_chan_matmul_bwd_ord(const fgnn_slab *ya, const fgnn_slab *yb
     const int t = (N + TM - 1) / TM;
     const bool fused = s12a && t == 1;
     if (t == 1) {
-        FGNN_CHECK((long long)G * ya->gstride < 0x7fffffffll / 4 && (long long)G * yb->gstride < 0x7fffffffll / 4 &&
-                   (long long)G * dmgstride < 0x7fffffffll / 4,
-                   "fgnn_chan_matmul_bwd: a tensor exceeds 2 GiB (32-bit buffer addressing); split the batch");
+        if (check_2gib("fgnn_chan_matmul_bwd", G, ya->gstride, yb->gstride, dmgstride)) return 1;
         FGNN_CHECK((long long)G * ogstride < 0x7fffffffll / 4, "fgnn_chan_matmul_bwd: output exceeds 2 GiB");
         const int M = G * ya->C;
         hipLaunchKernelGGL(chan_matmul_bwd1_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, *ya, *yb, dm,
@@ -1312,9 +1223,7 @@ extern "C" int fgnn_chan_matmul_bwd_ord(const fgnn_slab *ya, const fgnn_slab *yb
         return 0;
     }
     if (big_path(N)) {
-        FGNN_CHECK((long long)G * ya->gstride < 0x7fffffffll / 4 && (long long)G * yb->gstride < 0x7fffffffll / 4 &&
-                   (long long)G * dmgstride < 0x7fffffffll / 4 && (long long)G * ogstride < 0x7fffffffll / 4,
-                   "fgnn_chan_matmul_bwd: a tensor exceeds 2 GiB (32-bit buffer addressing); split the batch");
+        if (check_2gib("fgnn_chan_matmul_bwd", G, ya->gstride, yb->gstride, dmgstride, ogstride)) return 1;
 #define FGNN_BIG_BWD(MT)                                                                                              \
     {                                                                                                                 \
         static LdsAttrCache attr_cache;                                                                           \

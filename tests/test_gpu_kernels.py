@@ -356,7 +356,7 @@ def test_wave_per_matrix_forward_matmul_is_bit_identical_to_the_workgroup_kernel
     """The shipped N <= 64 forward (one wave per matrix; for even N > 32 with 8-byte accesses and the even / odd column blocks of
     chan_matmul_fwd_w2_kernel) keeps the k-step order and the normalisation expression of the workgroup-per-matrix kernel it
     replaced: outputs must be equal bit for bit (dense and ragged with odd and even vertex counts, normalised operands; the
-    untouched output is poisoned with NaN first).  Variants: 1 = shipped, 9 = the four-byte wave kernel, 0 = the workgroup kernel, 17 = two matrices per wave (a measurement build, N = 49 ... 56)."""
+    untouched output is poisoned with NaN first).  Variants: 1 = shipped, 9 = the four-byte wave kernel, 0 = the workgroup kernel."""
     lib = _lib.load()
     G, Cc = 3, 5
     g = torch.Generator().manual_seed(N)
@@ -391,6 +391,60 @@ def test_wave_per_matrix_forward_matmul_is_bit_identical_to_the_workgroup_kernel
     for gi, n in enumerate(nv.tolist()):
         assert float(res[0][gi, :, n:, :].abs().max()) == 0.0 if n < N else True
         assert float(res[0][gi, :, :, n:].abs().max()) == 0.0 if n < N else True
+
+
+@pytest.mark.parametrize('N', [1, 32, 33, 50, 58, 64])
+def test_forward_matmul_fin_prologue_is_bit_identical_across_the_variants(N):
+    """fgnn_chan_matmul_fwd_fin at N <= 64: the shipped wave-per-matrix kernel (1; 8-byte accesses at N = 58 and 64, where the
+    ragged counts put an odd vertex count inside an even N), its four-byte form (9) and the workgroup-per-matrix kernel (0) finalize
+    the operands' GraphNorm records from the same tile partials in their prologue.  The products and both published record
+    buffers must be equal bit for bit (everything poisoned with NaN before each call), the padding of the ragged graphs exact
+    zeros.  One and two column blocks: N = 1, 32 against 33 ... 64."""
+    lib = _lib.load()
+    G, Cc = 3, 5
+    g = torch.Generator().manual_seed(1000 + N)
+    a = torch.randn(G, Cc, N, N, generator=g)
+    b = torch.randn(G, Cc, N, N, generator=g)
+    beta = torch.randn(Cc, generator=g).to(DEV)
+    gw_a = (torch.rand(Cc, generator=g) + 0.5).to(DEV)
+    gw_b = (torch.rand(Cc, generator=g) + 0.5).to(DEV)
+    nvl = [N, max(1, N // 2), max(0, N - 1)]
+    nv = torch.tensor(nvl, dtype=torch.int32, device=DEV)
+    for gi, n in enumerate(nvl):                       # the kernels mask the padding themselves; keep it finite for variant 0
+        for t in (a, b):
+            t[gi, :, n:, :] = 0.0
+            t[gi, :, :, n:] = 0.0
+    a, b = a.to(DEV), b.to(DEV)
+    tpg = lib.fgnn_tiles_per_graph(N)
+    part_a = torch.stack([torch.randn(G, tpg, Cc, generator=g), torch.rand(G, tpg, Cc, generator=g) + 0.1], dim=-1).contiguous().to(DEV)
+    part_b = torch.stack([torch.randn(G, tpg, Cc, generator=g), torch.rand(G, tpg, Cc, generator=g) + 0.1], dim=-1).contiguous().to(DEV)
+    w = torch.rand(G, tpg, generator=g) + 0.1          # positive counts that sum to n^2 per graph
+    cnt = (w / w.sum(dim=1, keepdim=True) * torch.tensor([float(n * n) for n in nvl]).view(G, 1)).contiguous().to(DEV)
+    res = []
+    try:
+        for variant in (1, 0, 9):
+            lib.fgnn_debug_matmul_variant(variant)
+            out = torch.full((G, Cc, N, N), float('nan'), device=DEV)
+            nrm_a = torch.full((G, Cc, 4), float('nan'), device=DEV)
+            nrm_b = torch.full((G, Cc, 4), float('nan'), device=DEV)
+            sa, sb = _slab(a, nrm=nrm_a, beta=beta), _slab(b, nrm=nrm_b, beta=beta)
+            _lib.call('fgnn_chan_matmul_fwd_fin', C.byref(sa), C.byref(sb), _lib.ptr(part_a), _lib.ptr(part_b), _lib.ptr(cnt),
+                      _lib.ptr(gw_a), _lib.ptr(gw_b), 1e-5, _lib.ptr(nv), G, N, _lib.ptr(out), Cc * N * N, N * N, _lib.stream_ptr())
+            torch.cuda.synchronize()
+            res.append((out.cpu(), nrm_a.cpu(), nrm_b.cpu()))
+    finally:
+        lib.fgnn_debug_matmul_variant(1)
+    for other in res[1:]:
+        for x, y in zip(res[0], other):
+            assert torch.equal(x.view(torch.int32), y.view(torch.int32))
+    assert not torch.isnan(res[0][1]).any() and not torch.isnan(res[0][2]).any()
+    for gi, n in enumerate(nvl):
+        if n < N:
+            assert float(res[0][0][gi, :, n:, :].abs().max()) == 0.0
+            assert float(res[0][0][gi, :, :, n:].abs().max()) == 0.0
+        if n > 0:
+            assert not torch.isnan(res[0][0][gi, :, :n, :n]).any()
+
 
 @pytest.mark.parametrize('N', [1, 31, 32, 33, 50, 64, 65, 97, 200])
 def test_pack_tensor_representation_round_trip_and_check(N):
