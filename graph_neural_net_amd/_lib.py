@@ -214,6 +214,9 @@ _SIGNATURES = {
     'fgnn_score_ce_bwd': [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP],
     'fgnn_score_ce_fwd_blocks_labels': [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP],
     'fgnn_score_ce_bwd_labels': [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP],
+    'fgnn_score_ce_bwd_w': [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP],
+    'fgnn_pair_weights': [_VP, _VP, _I, _VP, _I, _I, _VP, _VP, _VP],
+    'fgnn_pair_loss_w': [_VP, _I, _VP, _I, _VP, _VP],
     'fgnn_ce_fwd_labels': [_VP, _VP, _VP, _I, _I, _VP, _VP, _VP],
     'fgnn_ce_bwd_labels': [_VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP],
     'fgnn_inv_node_count': [_VP, _I, _VP, _VP],

@@ -423,9 +423,13 @@ constexpr int CSPLIT = 4;          // channel splits of the blocked kernel and o
 constexpr int CSPLIT_SMALL = 8;    // whole-dS staging at small batch (B * 4 < 256 workgroups)
 // LAB (CE mode): dS[i][j] = (exp(S - lse_i) - [j == t_i]) * gscale with t_i = labels[b][i]; a row without a target (t_i outside
 // [0, n_b)) is zero.  The pair's labels are staged once per workgroup in N ints of LDS between s2 and dS (no-target rows as -1).
-template <bool CE, bool STAGE, bool LAB>
+// WGT (CE mode): pair b carries the weight w = pair_weight[b] >= 0.  w != 0: gs = *gscale * w, the one new
+// operation per workgroup (w = 1: the bits of the unweighted kernel).  w == 0 is a select: the pair is treated as n_b = 0, so its
+// scores and lse are never used and its de rows are +0 whatever they hold.
+template <bool CE, bool STAGE, bool LAB, bool WGT = false>
 DEVI void score_bwd_body(const float *e1, const float *e2, const float *scores, const float *lse, const float *dscores,
-                         const int *nvalid, const int *labels, const float *gscale, int C, int N, float *de1, float *de2) {
+                         const int *nvalid, const int *labels, const float *gscale, int C, int N, float *de1, float *de2,
+                         const float *pair_weight = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int cper = (C + (int)gridDim.y - 1) / (int)gridDim.y;
     const int c0 = blockIdx.y * cper;
@@ -435,7 +439,8 @@ DEVI void score_bwd_body(const float *e1, const float *e2, const float *scores, 
     float *dS = s2 + (size_t)cper * N + (LAB ? N : 0);         // [i][j], row stride N + 1
     const int ld = N + 1;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int nv = nvalid_of(nvalid, b, N);
+    const float wb = WGT ? pair_weight[b] : 1.f;
+    const int nv = (WGT && wb == 0.f) ? 0 : nvalid_of(nvalid, b, N);
     const float *p1 = e1 + ((long long)b * C + c0) * N, *p2 = e2 + ((long long)b * C + c0) * N;
     for (int e = tid; e < cn * N; e += 256) {
         s1[e] = p1[e];
@@ -448,7 +453,7 @@ DEVI void score_bwd_body(const float *e1, const float *e2, const float *scores, 
         }
         __syncthreads();
     }
-    const float gs = CE ? *gscale : 1.f;
+    const float gs = CE ? (WGT ? *gscale * wb : *gscale) : 1.f;
     const float *S = (CE ? scores : dscores) + (long long)b * N * N;
     const float *Lr = CE ? lse + (long long)b * N : nullptr;
     const float invN = 1.f / (float)N;
@@ -524,10 +529,11 @@ __global__ __launch_bounds__(256) void score_bwd_labels_kernel(const float *e1, 
 // dS[i0:i1, :] and produces de1 for those rows, then stages the column block dS[:, i0:i1] and produces de2 for
 // those columns -- no cross-workgroup reduction, nothing recomputed inside the inner loops.
 // LAB: as in score_bwd_body (the labels of the pair in N ints of LDS between s2 and dS).
-template <bool CE, bool LAB>
+// WGT: as in score_bwd_body.
+template <bool CE, bool LAB, bool WGT = false>
 DEVI void score_bwd_blocked_body(const float *e1, const float *e2, const float *scores, const float *lse, const float *dscores,
                                  const int *nvalid, const int *labels, const float *gscale, int C, int N, int SB_BLK, float *de1,
-                                 float *de2) {
+                                 float *de2, const float *pair_weight = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int cper = (C + CSPLIT - 1) / CSPLIT;
     const int c0 = blockIdx.y * cper;
@@ -536,7 +542,8 @@ DEVI void score_bwd_blocked_body(const float *e1, const float *e2, const float *
     int *lab = reinterpret_cast<int *>(s2 + (size_t)cper * N);
     float *dS = s2 + (size_t)cper * N + (LAB ? N : 0);         // phase 1: [SB_BLK][N + 1], phase 2: [N][SB_BLK + 1]
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int nv = nvalid_of(nvalid, b, N);
+    const float wb = WGT ? pair_weight[b] : 1.f;
+    const int nv = (WGT && wb == 0.f) ? 0 : nvalid_of(nvalid, b, N);
     const int x0 = blockIdx.z * SB_BLK, x1 = (x0 + SB_BLK < N) ? x0 + SB_BLK : N, w = x1 - x0;
     const float *p1 = e1 + ((long long)b * C + c0) * N, *p2 = e2 + ((long long)b * C + c0) * N;
     // every staging loop below keeps U loads in flight per thread: rolled, each element pays its own memory round trip
@@ -551,7 +558,7 @@ DEVI void score_bwd_blocked_body(const float *e1, const float *e2, const float *
         }
         __syncthreads();
     }
-    const float gs = CE ? *gscale : 1.f;
+    const float gs = CE ? (WGT ? *gscale * wb : *gscale) : 1.f;
     const float *S = (CE ? scores : dscores) + (long long)b * N * N;
     const float *Lr = CE ? lse + (long long)b * N : nullptr;
     // dS[i][jj] from the loaded score (and the row's lse); i, jj < N
@@ -638,6 +645,22 @@ __global__ __launch_bounds__(256) void score_bwd_blocked_labels_kernel(const flo
                                                                        const float *gscale, int C, int N, int SB_BLK, float *de1,
                                                                        float *de2) {
     score_bwd_blocked_body<true, true>(e1, e2, scores, lse, nullptr, nvalid, labels, gscale, C, N, SB_BLK, de1, de2);
+}
+
+// the weighted step (fgnn_score_ce_bwd_w): the same two bodies with WGT, labelled or not
+template <bool LAB>
+__global__ __launch_bounds__(256) void score_bwd_w_kernel(const float *e1, const float *e2, const float *scores, const float *lse,
+                                                          const int *nvalid, const int *labels, const float *pair_weight,
+                                                          const float *gscale, int C, int N, float *de1, float *de2) {
+    score_bwd_body<true, true, LAB, true>(e1, e2, scores, lse, nullptr, nvalid, labels, gscale, C, N, de1, de2, pair_weight);
+}
+
+template <bool LAB>
+__global__ __launch_bounds__(256) void score_bwd_blocked_w_kernel(const float *e1, const float *e2, const float *scores,
+                                                                  const float *lse, const int *nvalid, const int *labels,
+                                                                  const float *pair_weight, const float *gscale, int C, int N,
+                                                                  int SB_BLK, float *de1, float *de2) {
+    score_bwd_blocked_body<true, LAB, true>(e1, e2, scores, lse, nullptr, nvalid, labels, gscale, C, N, SB_BLK, de1, de2, pair_weight);
 }
 
 // triplet_loss pieces on a given score tensor (module-level API): one workgroup per pair.
@@ -850,6 +873,38 @@ static int launch_score_bwd(const float *e1, const float *e2, const float *score
     return 0;
 }
 
+// The weighted launches: form, geometry and LDS by the rules of launch_score_bwd<true> above, restated (that function is not touched);
+// LAB picks the labelled body and its N ints of LDS.
+template <bool LAB>
+static int launch_score_bwd_w(const float *e1, const float *e2, const float *scores, const float *lse, const int *nvalid,
+                              const int *labels, const float *pair_weight, const float *gscale, int B, int C, int N, float *de1,
+                              float *de2, hipStream_t st) {
+    const bool stage = score_bwd_lds_bytes(C, N, true) <= 160 * 1024 && (N <= 64 || (long long)B * CSPLIT >= 256);
+    const int csplit = (long long)B * CSPLIT < 256 ? CSPLIT_SMALL : CSPLIT;
+    const int lds = score_bwd_lds_bytes(C, N, stage, stage ? csplit : CSPLIT);
+    FGNN_CHECK(lds <= 160 * 1024, "score backward: C*N=%d too large for LDS staging", C * N);
+    const int lab_bytes = LAB ? N * (int)sizeof(int) : 0;
+    if (stage) {
+        FGNN_CHECK(lds + lab_bytes <= 160 * 1024, "score backward: C*N=%d too large for LDS staging with labels", C * N);
+        if (lds + lab_bytes > 64 * 1024)
+            (void)hipFuncSetAttribute((const void *)score_bwd_w_kernel<LAB>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + lab_bytes);
+        hipLaunchKernelGGL((score_bwd_w_kernel<LAB>), dim3(B, csplit), dim3(256), lds + lab_bytes, st, e1, e2, scores, lse, nvalid, labels,
+                           pair_weight, gscale, C, N, de1, de2);
+    } else {
+        const int cper = (C + CSPLIT - 1) / CSPLIT;
+        const int SB_BLK = (long long)B * CSPLIT * ((N + 63) / 64) >= 512 ? 64 : 16;
+        const int big = (N + 1) * SB_BLK > N * (SB_BLK + 1) ? (N + 1) * SB_BLK : N * (SB_BLK + 1);
+        const int lds2 = (2 * cper * N + big) * (int)sizeof(float) + lab_bytes;
+        FGNN_CHECK(lds2 <= 160 * 1024, "score backward: N=%d too large for the blocked LDS staging", N);
+        if (lds2 > 64 * 1024)
+            (void)hipFuncSetAttribute((const void *)score_bwd_blocked_w_kernel<LAB>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
+        hipLaunchKernelGGL((score_bwd_blocked_w_kernel<LAB>), dim3(B, CSPLIT, (N + SB_BLK - 1) / SB_BLK), dim3(256), lds2, st, e1, e2,
+                           scores, lse, nvalid, labels, pair_weight, gscale, C, N, SB_BLK, de1, de2);
+    }
+    FGNN_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int fgnn_score_row_blocks(int B, int N) {
     // few large pairs: more row blocks than FGNN_SCORE_SPLIT so that the launch fills the chip (8 rows per workgroup)
     if (B * FGNN_SCORE_SPLIT >= 512) return FGNN_SCORE_SPLIT;
@@ -901,6 +956,15 @@ extern "C" int fgnn_score_ce_bwd_labels(const float *e1, const float *e2, const 
                                         void *stream) {
     FGNN_CHECK(e1 && e2 && scores && lse && labels && gscale && de1 && de2 && B > 0, "fgnn_score_ce_bwd_labels: bad arguments");
     return launch_score_bwd<true>(e1, e2, scores, lse, nullptr, nvalid, gscale, B, C, N, de1, de2, (hipStream_t)stream, labels);
+}
+
+extern "C" int fgnn_score_ce_bwd_w(const float *e1, const float *e2, const float *scores, const float *lse, const int *nvalid,
+                                   const int *labels, const float *pair_weight, const float *gscale, int B, int C, int N, float *de1,
+                                   float *de2, void *stream) {
+    FGNN_CHECK(e1 && e2 && scores && lse && pair_weight && gscale && de1 && de2 && B > 0 && C > 0 && N > 0, "fgnn_score_ce_bwd_w: bad arguments");
+    if (labels)
+        return launch_score_bwd_w<true>(e1, e2, scores, lse, nvalid, labels, pair_weight, gscale, B, C, N, de1, de2, (hipStream_t)stream);
+    return launch_score_bwd_w<false>(e1, e2, scores, lse, nvalid, nullptr, pair_weight, gscale, B, C, N, de1, de2, (hipStream_t)stream);
 }
 
 extern "C" int fgnn_score_bwd(const float *e1, const float *e2, const float *dscores, const int *nvalid, int B, int C,

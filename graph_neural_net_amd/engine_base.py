@@ -50,6 +50,7 @@ class EngineBase:
         self._loss_target = None
         self._loss_scale_dev = None      # 1 / sum(n) as a device scalar: assigned by the caller that keeps the normaliser on the device
         self.labels = None               # (B, N) int32 targets of the cross-entropy (forward(labels=...)); None: the identity
+        self.weights = None              # (B,) fp32 per-pair loss weights (forward(weights=...)); None: the unweighted launches
 
     # ------------------------------------------------------------------ helpers
     def _nv(self):
@@ -113,6 +114,18 @@ class EngineBase:
             labels = labels_tensor(labels, self.B, self.N, self.device)
         self.labels = labels
 
+    def _adopt_weights(self, weights):
+        """weights= of forward / step: None (the unweighted launches), or (B,) per-pair weights w_b >= 0.  A contiguous fp32 tensor
+        on the engine's device is read in place by the weighted loss sum and the weighted score backward, like nvalid and labels."""
+        if weights is not None:
+            if not torch.is_tensor(weights):
+                weights = torch.as_tensor(weights, dtype=torch.float32)
+            if tuple(weights.shape) != (self.B,):
+                raise ValueError('%s: weights must have shape (%d,), got %s' % (type(self).__name__, self.B, tuple(weights.shape)))
+            if weights.dtype != torch.float32 or weights.device != torch.device(self.device) or not weights.is_contiguous():
+                weights = weights.to(device=self.device, dtype=torch.float32).contiguous()
+        self.weights = weights
+
     def _check_bits(self, bits):
         """bits: (G, N, ceil(N/32)) contiguous 32-bit words of the bit-packed adjacency on the GPU."""
         words = (self.N + 31) // 32
@@ -135,17 +148,30 @@ class EngineBase:
         return ((C.c_void_p * 3)(*[self._w(params, o) for o in rec['w']]), (C.c_void_p * 3)(*[self._w(params, o) for o in rec['b']]))
 
     # ------------------------------------------------------------------ forward
-    def forward(self, params, x, nvalid=None, total_nodes=None, defer_loss=False, loss_out=None, bits=None, labels=None, **embed_kw):
+    def forward(self, params, x, nvalid=None, total_nodes=None, defer_loss=False, loss_out=None, bits=None, labels=None, weights=None,
+                **embed_kw):
         """Siamese forward on the stacked batch x = cat(x1, x2) (or its bit-packed adjacency, see embed): returns
         (scores, loss).
         labels: (B, N) integer tensor, labels[b, i] = the column row i of pair b should match (planted.py; -1 in the padding):
         the cross-entropy is taken against them instead of the identity, and the following backward()
         differentiates that loss.  A live row whose label lies outside [0, n_b) has no target: no loss, no gradient.  The
         normaliser stays the node count.  None: the label-less launches, as before.
+        weights: (B,) fp32 per-pair loss weights w_b >= 0: loss = sum over the pairs with w_b != 0 of
+        w_b * CE_b, one fgnn_pair_loss_w launch right after the scoring (the gradient-finalize launch carries no loss job then,
+        whatever defer_loss says), and the following backward() differentiates that loss.  A pair with w_b == 0 is switched off by a
+        select: NaN or inf in its scores reach neither loss nor gradient.  The weights carry the reduction, so total_nodes must be
+        left out or 1: the normaliser D of a reduction (fgnn_pair_weights) is applied by the caller (FgnnTrainer: as Adam's gradient
+        scale, after the all-reduce).  None: the launches of the unweighted step, unchanged.
         defer_loss: leave the final sum of the per-pair losses to the gradient-finalize launch of the
         following backward() (one launch less per training step); `loss` is valid after that.
         embed_kw: keywords of the engine's own embed()."""
         self._adopt_labels(labels)
+        self._adopt_weights(weights)
+        if self.weights is not None:
+            if total_nodes is not None and float(total_nodes) != 1.0:
+                raise ValueError('%s.forward: weights carry the reduction; total_nodes must be None or 1 (got %r)'
+                                 % (type(self).__name__, total_nodes))
+            total_nodes = 1.0
         self.embed(params, x, nvalid, bits=bits, **embed_kw)
         B, N = self.B, self.N
         st = _lib.stream_ptr()
@@ -159,9 +185,12 @@ class EngineBase:
         else:
             _lib.call('fgnn_score_ce_fwd_blocks_labels', _lib.ptr(e1), _lib.ptr(e2), self._nv(), _lib.ptr(self.labels), B, 32, N,
                       self.score_blocks, _lib.ptr(self.scores), _lib.ptr(self.lse), _lib.ptr(self.pair_loss), st)
-        self._loss_pending = bool(defer_loss)
+        self._loss_pending = bool(defer_loss) and self.weights is None
         self._loss_target = self.loss if loss_out is None else loss_out     # 1-element fp32 device tensor
-        if not defer_loss:
+        if self.weights is not None:
+            _lib.call('fgnn_pair_loss_w', _lib.ptr(self.pair_loss), self.score_blocks, _lib.ptr(self.weights), B,
+                      _lib.ptr(self._loss_target), st)
+        elif not defer_loss:
             _lib.call('fgnn_sum_scale', _lib.ptr(self.pair_loss), B * self.score_blocks, 1, 1.0 / self.total_nodes,
                       _lib.ptr(self._loss_target), st)
         return self.scores, self._loss_target
@@ -198,7 +227,8 @@ class EngineBase:
     def backward(self, params, grads, grad_scale=1.0, gscale_dev=None, **kw):
         """Backward of loss*grad_scale after forward(); fills the flat `grads` buffer (the fp32 engine's finalize=False: everything
         but the last launch, see its backward_from_dE).
-        After forward(labels=...) the gradient is that of the labelled loss (the labels are read again, in place).
+        After forward(labels=...) the gradient is that of the labelled loss (the labels are read again, in place); after
+        forward(weights=...) that of the weighted loss (fgnn_score_ce_bwd_w, labelled or not; the weights are read again, in place).
         gscale_dev: a 1-element fp32 DEVICE tensor that holds grad_scale / total_nodes (replaces both): the normaliser of a ragged
         batch then never visits the host, and a captured step stays valid when the next batch has another node count.
         kw: keywords of the engine's own backward_from_dE() (finalize=, hook=)."""
@@ -211,7 +241,11 @@ class EngineBase:
         else:
             self._set_gscale(grad_scale / self.total_nodes)
         e1, e2 = self.E[:B], self.E[B:]
-        if self.labels is None:
+        if self.weights is not None:
+            _lib.call('fgnn_score_ce_bwd_w', _lib.ptr(e1), _lib.ptr(e2), _lib.ptr(self.scores), _lib.ptr(self.lse), self._nv(),
+                      _lib.ptr(self.labels), _lib.ptr(self.weights), _lib.ptr(gs_t), B, 32, N, _lib.ptr(W['dE'][:B]),
+                      _lib.ptr(W['dE'][B:]), st)
+        elif self.labels is None:
             _lib.call('fgnn_score_ce_bwd', _lib.ptr(e1), _lib.ptr(e2), _lib.ptr(self.scores), _lib.ptr(self.lse),
                       self._nv(), _lib.ptr(gs_t), B, 32, N, _lib.ptr(W['dE'][:B]), _lib.ptr(W['dE'][B:]), st)
         else:
@@ -264,10 +298,11 @@ class EngineBase:
                       self.G if graphs is None else graphs, 32, st)
         return grads
 
-    def step(self, params, grads, x, nvalid=None, total_nodes=None, loss_out=None, bits=None, labels=None):
-        """One training step's model work: forward + loss + backward.  (x / bits / an int32 device nvalid / int32 device labels are
-        read in place by both passes: see embed() and forward().)"""
-        scores, loss = self.forward(params, x, nvalid, total_nodes, defer_loss=True, loss_out=loss_out, bits=bits, labels=labels)
+    def step(self, params, grads, x, nvalid=None, total_nodes=None, loss_out=None, bits=None, labels=None, weights=None):
+        """One training step's model work: forward + loss + backward.  (x / bits / an int32 device nvalid / int32 device labels /
+        fp32 device weights are read in place by both passes: see embed() and forward().)"""
+        wkw = {} if weights is None else {'weights': weights}
+        scores, loss = self.forward(params, x, nvalid, total_nodes, defer_loss=True, loss_out=loss_out, bits=bits, labels=labels, **wkw)
         self.backward(params, grads)
         return scores, loss
 

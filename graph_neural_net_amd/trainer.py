@@ -18,7 +18,7 @@ class FgnnTrainer:
     INPUT_CHECK_EVERY = 128     # input_form='tensor_representation': the device verdict is read back on every k-th train_step (0: never)
 
     def __init__(self, layout, params_flat, lr=1e-3, capture=False, precision='fp32', collective='auto', block1=None,
-                 input_form='dense', max_grad_norm=None, skip_nonfinite=False):
+                 input_form='dense', max_grad_norm=None, skip_nonfinite=False, loss_reduction='mean'):
         """capture=True: constant-shape steps are captured in a HIP graph and replayed -- the launch overhead of ~40 kernels
         per step disappears.  With more than one rank the gradient all-reduce is recorded INSIDE that graph when the backend
         can be captured (RCCL: model work -> all-reduce -> fused Adam is one replay, no host launch on the critical path;
@@ -40,7 +40,15 @@ class FgnnTrainer:
         step: the eager one, the one-graph captured step and the optimizer graph of the gloo fallback; `grad_norm` and
         `skipped_steps` stay on the device and no step reads them.  It runs AFTER the all-reduce, on a buffer that is bit-identical
         on every rank, and its sums have a fixed order, so every rank takes the same clip and skip decision without another
-        collective.  The defaults (None, False) leave every launch sequence and captured graph as it was."""
+        collective.  The defaults (None, False) leave every launch sequence and captured graph as it was.
+        loss_reduction: 'mean' (the sum of the cross-entropies over the node count, toolbox/losses.py:27-34) or 'mean_of_mean' (the
+        average over the graphs of the per-graph mean, toolbox/losses.py:14-15; on ragged batches another loss).  'mean_of_mean'
+        runs every step as a weighted step: w_b = 1 / n_b, normalised by the number of non-empty pairs of the
+        global batch.  With 'mean', a step without weights= and live= issues the launches it always did."""
+        if loss_reduction not in ('mean', 'mean_of_mean'):
+            raise ValueError('Unknown loss_reduction parameters {}'.format(loss_reduction))
+        self.loss_reduction = loss_reduction
+        self._pw = {}               # B -> buffers of the eager weighted step
         if input_form not in ('dense', 'tensor_representation'):
             raise ValueError('input_form must be "dense" or "tensor_representation" (got %r)' % (input_form,))
         self.input_form = input_form
@@ -100,9 +108,12 @@ class FgnnTrainer:
                                'original_features_num 2 or 32 and in_features = out_features = 32; 16-bit (model.half()) takes '
                                'original_features_num, in_features and out_features up to 32; depth_of_mlp = 3 in 16-bit')
         net._bind_flat()
+        from .losses import triplet_loss
+        loss = getattr(model, 'loss', None)
+        rkw = {'loss_reduction': loss.loss_reduction} if isinstance(loss, triplet_loss) else {}
         tr = cls(lay, net._flat if pad is None else net._engine_params(), lr=model.lr if lr is None else lr, capture=capture,
                  precision=precision, input_form=getattr(net, 'input_form', 'dense'), max_grad_norm=max_grad_norm,
-                 skip_nonfinite=skip_nonfinite)
+                 skip_nonfinite=skip_nonfinite, **rkw)
         if pad is not None:
             tr._module = net
         return tr
@@ -155,6 +166,46 @@ class FgnnTrainer:
         self._sync_module()
         return (self._loss_sum / self._nodes).reshape(())
 
+    # ------------------------------------------------------------------ per-pair loss weights
+    def _weighted(self, weights, live):
+        """does this step run the weighted launches?  ('mean' without weights= and live=: no, the step is the one it always was)"""
+        return self.loss_reduction != 'mean' or weights is not None or live is not None
+
+    def _user_weights(self, weights, B):
+        """weights= of the train steps -> None or a (B,) fp32 device tensor"""
+        if weights is None:
+            return None
+        w = torch.as_tensor(weights, dtype=torch.float32).to(self.params.device).contiguous()
+        if tuple(w.shape) != (B,):
+            raise ValueError('FgnnTrainer: weights must have shape (%d,), got %s' % (B, tuple(w.shape)))
+        return w
+
+    def _set_live(self, buf, live, B):
+        """live= of the train steps into the int32[1] device buffer the weight kernel reads: an int (host) or a 1-element device
+        tensor; None: B"""
+        if torch.is_tensor(live):
+            buf.copy_(live.reshape(1))
+        else:
+            buf.fill_(B if live is None else max(0, min(B, int(live))))
+
+    def _launch_pair_weights(self, nvalid, live_buf, user, B, N, w_out):
+        """ONE launch: w_out <- the weights of self.loss_reduction on this rank's pairs, self._nodes <- their normaliser D (the
+        all-reduce sums it over the ranks, set_grad_scale_reciprocal applies 1 / D: no further collective)"""
+        from . import _lib
+        _lib.call('fgnn_pair_weights', _lib.ptr(nvalid), _lib.ptr(live_buf), 1 if self.loss_reduction == 'mean_of_mean' else 0,
+                  _lib.ptr(user), B, N, _lib.ptr(w_out), _lib.ptr(self._nodes), _lib.stream_ptr())
+        return w_out
+
+    def _pair_weights(self, B, N, nvalid, live, weights):
+        """the eager weighted step's weights: (B,) fp32 device tensor; self._nodes holds D afterwards.  nvalid: (B,) or None."""
+        pw = self._pw.get(B)
+        if pw is None:
+            dev = self.params.device
+            pw = self._pw[B] = {'w': torch.empty(B, dtype=torch.float32, device=dev), 'live': torch.empty(1, dtype=torch.int32, device=dev)}
+        self._set_live(pw['live'], live, B)
+        nv = None if nvalid is None else nvalid.to(device=self.params.device, dtype=torch.int32).contiguous()
+        return self._launch_pair_weights(nv, pw['live'], self._user_weights(weights, B), B, N, pw['w'])
+
     # ------------------------------------------------------------------ ragged batches, bucketed by size
     @staticmethod
     def bucket_by_size(sizes, granule=16):
@@ -166,7 +217,7 @@ class FgnnTrainer:
             buckets.setdefault(-(-int(n) // granule) * granule, []).append(i)
         return sorted(buckets.items())
 
-    def prepare_ragged(self, xs, ys, granule=None, labels=None):
+    def prepare_ragged(self, xs, ys, granule=None, labels=None, weights=None):
         """Stage a ragged list of pairs (xs[i], ys[i]: (c0, n_i, n_i) tensors): one stacked, zero-padded
         (2 * pairs, c0, npad, npad) device tensor + vertex counts per size bucket.  This is loader work (pad / stack / copy):
         done once per batch, off the step's critical path.  -> dict for model_step_prepared.
@@ -175,11 +226,15 @@ class FgnnTrainer:
         1.77 / 6.09 ms with buckets of 32); granule=g: one engine pass per size class ceil(n / g) * g (bounded workspace for
         very mixed batches).
         labels: None, or one integer array per pair (labels[i][r] = the vertex of ys[i] that vertex r of xs[i] matches, at most n_i
-        entries): they follow their pairs into the buckets as (pairs, npad) int32 tensors, -1 in the padding."""
+        entries): they follow their pairs into the buckets as (pairs, npad) int32 tensors, -1 in the padding.
+        weights: None, or one loss weight per pair: they follow their pairs as (pairs,) fp32 tensors, 0 for the
+        pairs a bucket is filled up with; every bucket then runs the weighted launches."""
         dev = self.params.device
         sizes = [int(x.shape[-1]) for x in xs]
         if labels is not None and len(labels) != len(xs):
             raise ValueError('FgnnTrainer.prepare_ragged: %d label arrays for %d pairs' % (len(labels), len(xs)))
+        if weights is not None and len(weights) != len(xs):
+            raise ValueError('FgnnTrainer.prepare_ragged: %d weights for %d pairs' % (len(weights), len(xs)))
         if granule is None:
             granule = -(-max(sizes) // 16) * 16        # one bucket; rounded up so that engines are shared between batches
         buckets = []
@@ -193,6 +248,9 @@ class FgnnTrainer:
             ns = [sizes[i] for i in idx] + [0] * (cnt - len(idx))
             nv = torch.tensor(ns * 2, dtype=torch.int32, device=dev)
             buckets.append({'npad': npad, 'idx': idx, 'pairs': cnt, 'x': x, 'nvalid': nv})
+            if weights is not None:
+                buckets[-1]['weights'] = torch.tensor([float(weights[i]) for i in idx] + [0.0] * (cnt - len(idx)), dtype=torch.float32,
+                                                      device=dev)
             if labels is not None:
                 import numpy as np
                 from .metrics import labels_tensor
@@ -204,6 +262,8 @@ class FgnnTrainer:
         gradients and losses of the buckets are summed.
         total_nodes=None: normalised by this batch's own node count (the single-process result);
         total_nodes=1.0: the UN-normalised sums (the data-parallel step normalises after its all-reduce).
+        A batch staged with weights: every bucket's loss and gradient are the weighted sums (the weights carry the reduction, so
+        total_nodes is not applied to them).
         Returns (loss, [scores_i of shape (n_i, n_i)] or None); self.grads holds the gradient sum."""
         sizes = batch['sizes']
         total = float(sum(sizes)) if total_nodes is None else float(total_nodes)
@@ -215,7 +275,9 @@ class FgnnTrainer:
             # the first bucket writes self.grads, the others go through the scratch vector and are added
             dst = self.grads if first else self._grad_tmp()
             kw = {'labels': b['labels']} if b.get('labels') is not None else {}
-            sc, l = eng.step(self.params, dst, b['x'], nvalid=b['nvalid'], total_nodes=total, **kw)
+            if b.get('weights') is not None:
+                kw['weights'] = b['weights']
+            sc, l = eng.step(self.params, dst, b['x'], nvalid=b['nvalid'], total_nodes=1.0 if 'weights' in kw else total, **kw)
             if not first:
                 self.grads += dst
             first = False
@@ -230,35 +292,79 @@ class FgnnTrainer:
             self._gtmp = torch.empty_like(self.grads)
         return self._gtmp
 
-    def model_step_ragged(self, xs, ys, granule=None, total_nodes=None, labels=None):
+    def model_step_ragged(self, xs, ys, granule=None, total_nodes=None, labels=None, weights=None):
         """prepare_ragged + model_step_prepared in one call.  Returns (loss, [scores_i of shape (n_i, n_i)])."""
-        return self.model_step_prepared(self.prepare_ragged(xs, ys, granule, labels), total_nodes)
+        return self.model_step_prepared(self.prepare_ragged(xs, ys, granule, labels, weights), total_nodes)
 
-    def train_step_ragged(self, xs, ys, granule=None, labels=None):
-        """labels: per-pair integer arrays (prepare_ragged): the loss is the cross-entropy against them (train_step)."""
-        loss, scores = self.model_step_ragged(xs, ys, granule, total_nodes=1.0, labels=labels)
+    def ragged_weights(self, sizes, weights=None, live=None):
+        """The per-pair weights and the normaliser D of self.loss_reduction for a list of pairs of the given sizes, on the host (where
+        the sizes already are): what fgnn_pair_weights computes on the device.  weights: optional per-pair factors; live: the pairs
+        from position `live` on are switched off (None: all count).  -> ([w_i], D)"""
+        import numpy as np
+        n = len(sizes)
+        live = n if live is None else max(0, min(n, int(live)))
+        u = np.ones(n, dtype=np.float32) if weights is None else np.asarray(weights, dtype=np.float32).reshape(n)
+        w, D = np.zeros(n, dtype=np.float32), 0.0
+        for i, size in enumerate(sizes):
+            if i >= live or (self.loss_reduction == 'mean_of_mean' and size <= 0):
+                continue
+            if self.loss_reduction == 'mean_of_mean':
+                w[i] = np.float32(1.0 / size) * u[i]
+                D += float(u[i])
+            else:
+                w[i] = u[i]
+                D += float(size) * float(u[i])
+        return [float(v) for v in w], D
+
+    def train_step_ragged(self, xs, ys, granule=None, labels=None, weights=None, live=None):
+        """labels: per-pair integer arrays (prepare_ragged): the loss is the cross-entropy against them (train_step).
+        weights, live: see train_step; the per-bucket weights are built on the host (ragged_weights)."""
+        sizes = [int(x.shape[-1]) for x in xs]
+        if self._weighted(weights, live):
+            w, D = self.ragged_weights(sizes, weights, live)
+            loss, scores = self.model_step_ragged(xs, ys, granule, total_nodes=1.0, labels=labels, weights=w)
+        else:
+            D = float(sum(sizes))
+            loss, scores = self.model_step_ragged(xs, ys, granule, total_nodes=1.0, labels=labels)
         self._loss_sum.copy_(loss.reshape(1))
-        self._nodes.fill_(float(sum(int(x.shape[-1]) for x in xs)))
+        self._nodes.fill_(D)
         return self._reduce_and_update(), scores
 
     # ------------------------------------------------------------------ captured constant-shape step
-    def _captured_step(self, x1, x2, bits=False, labels=None):
+    def _captured_step(self, x1, x2, bits=False, labels=None, weights=None, live=None, weighted=False):
         """bits: x1, x2 are (B, N, ceil(N / 32)) int32 words of bit-packed adjacency instead of (B, c0, N, N) tensors.
         labels: (B, N) int32 device tensor or None.  A labelled step is a graph of its own (the key says which): its labels live in
-        a static buffer that every call copies into, like xs, so one trainer can hold and alternate both."""
+        a static buffer that every call copies into, like xs, so one trainer can hold and alternate both.
+        weighted (weights: (B,) fp32 device tensor or None; live: int, 1-element device tensor or None): the weighted step is a graph
+        of its own as well (key: 'weights').  It holds the fgnn_pair_weights launch; the caller's weights (None: ones) and live
+        (None: B) live in static device buffers, so ONE graph serves every step of an epoch, the short last one included."""
         B, N = x1.shape[0], x1.shape[-2 if bits else -1]
         world = dp.world_size()
         key = (B, N, 'bits') if bits else (B, N)
         if labels is not None:
             key = key + ('labels',)
+        if weighted:
+            key = key + ('weights',)
         st = self._graphs.get(key)
         if st is None:
             eng = self._engine(2 * B, N, False)
             xs = torch.cat([x1, x2]).contiguous().clone()
             lab = None if labels is None else labels.clone()
             lkw = {} if lab is None else {'labels': lab}
-            step = ((lambda: eng.step(self.params, self.grads, None, total_nodes=1.0, loss_out=self._loss_sum, bits=xs, **lkw)) if bits else
-                    (lambda: eng.step(self.params, self.grads, xs, total_nodes=1.0, loss_out=self._loss_sum, **lkw)))
+            wst = None
+            if weighted:
+                dev = self.params.device
+                wst = {'user': torch.ones(B, dtype=torch.float32, device=dev), 'live': torch.full((1,), B, dtype=torch.int32, device=dev),
+                       'w': torch.zeros(B, dtype=torch.float32, device=dev)}
+                lkw['weights'] = wst['w']
+            model = ((lambda: eng.step(self.params, self.grads, None, total_nodes=1.0, loss_out=self._loss_sum, bits=xs, **lkw)) if bits else
+                     (lambda: eng.step(self.params, self.grads, xs, total_nodes=1.0, loss_out=self._loss_sum, **lkw)))
+            if weighted:
+                def step():
+                    self._launch_pair_weights(None, wst['live'], wst['user'], B, N, wst['w'])
+                    return model()
+            else:
+                step = model
             self.opt.sync_hyper_parameters(grad_scale=None)
             # two eager steps on a side stream (allocations, kernel attributes); they do not touch the optimizer
             side = torch.cuda.Stream()
@@ -316,8 +422,8 @@ class FgnnTrainer:
                 with torch.cuda.graph(g_opt):
                     self.opt.step_dev(self.grads)
             self.opt.t = t0                               # a capture does not execute an update
-            st = self._graphs[key] = (xs, g_model, g_opt, scores, B, lab)
-        xs, g_model, g_opt, scores, B, lab = st
+            st = self._graphs[key] = (xs, g_model, g_opt, scores, B, lab, wst)
+        xs, g_model, g_opt, scores, B, lab, wst = st
         if tuple(x1.shape[1:]) != tuple(xs.shape[1:]) or tuple(x2.shape) != tuple(x1.shape):
             raise RuntimeError('FgnnTrainer: the captured step of (B, N) = (%d, %d) was recorded for batches of shape %s per side, got %s / '
                                '%s; a trainer captures one channel count per (B, N)' % (B, N, (B,) + tuple(xs.shape[1:]),
@@ -327,6 +433,12 @@ class FgnnTrainer:
             xs[B:].copy_(x2)
         if lab is not None and labels.data_ptr() != lab.data_ptr():
             lab.copy_(labels)
+        if wst is not None:
+            if weights is None:
+                wst['user'].fill_(1.0)
+            else:
+                wst['user'].copy_(weights)
+            self._set_live(wst['live'], live, B)
         self._nodes.fill_(float(B * N))
         if g_opt is None:
             self.opt.sync_hyper_parameters(grad_scale=None)
@@ -367,12 +479,12 @@ class FgnnTrainer:
         from .metrics import labels_tensor
         return labels_tensor(labels, B, N, self.params.device)
 
-    def train_step_bits(self, bits1, bits2, nvalid=None, labels=None):
+    def train_step_bits(self, bits1, bits2, nvalid=None, labels=None, weights=None, live=None):
         """The same step with the local shard handed over as bit-packed adjacency: bits1, bits2
         (B, N, ceil(N / 32)) int32 device tensors, bit j of row i = W[i][j] (synthetic.pack_adjacency / the loader's packing); the
         tensor representation of loaders/data_generator.py:118-125 is built inside block 1's kernels, and with block1='structured'
         block 1 runs on the class tables of csrc/block1_struct.hip.  nvalid: (B,) int32 for ragged batches (padded to N).
-        labels: see train_step."""
+        labels, weights, live: see train_step."""
         if bits1.dim() != 3 or bits1.shape != bits2.shape or bits1.dtype not in (torch.int32, torch.uint32) or not bits1.is_cuda:
             raise RuntimeError('FgnnTrainer.train_step_bits: expected two (B, N, ceil(N/32)) int32 device tensors, got %s %s / %s %s'
                                % (tuple(bits1.shape), bits1.dtype, tuple(bits2.shape), bits2.dtype))
@@ -380,35 +492,46 @@ class FgnnTrainer:
         if bits1.shape[2] != (N + 31) // 32:
             raise RuntimeError('FgnnTrainer.train_step_bits: %d words per row for N = %d (expected %d)' % (bits1.shape[2], N, (N + 31) // 32))
         labels = self._labels(labels, B, N)
+        weighted = self._weighted(weights, live)
         if self.capture and nvalid is None:
+            if weighted:
+                return self._captured_step(bits1, bits2, bits=True, labels=labels, weights=self._user_weights(weights, B), live=live,
+                                           weighted=True)
             return self._captured_step(bits1, bits2, bits=True, labels=labels)
         eng = self._engine(2 * B, N, nvalid is not None)
         b = torch.cat([bits1, bits2]).contiguous()
         nv = None if nvalid is None else torch.cat([nvalid, nvalid]).to(torch.int32)
-        if nvalid is None:
+        lkw = {} if labels is None else {'labels': labels}
+        if weighted:
+            lkw['weights'] = self._pair_weights(B, N, nvalid, live, weights)        # (self._nodes <- D)
+        elif nvalid is None:
             self._nodes.fill_(float(B * N))
         else:
             self._nodes.copy_(nvalid.sum().to(torch.float32).reshape(1))
-        lkw = {} if labels is None else {'labels': labels}
         scores, _ = eng.step(self.params, self.grads, None, nvalid=nv, total_nodes=1.0, loss_out=self._loss_sum, bits=b, **lkw)
         return self._reduce_and_update(), scores
 
-    def train_epoch(self, generator, sampler, epoch, batch_size, permute=False):
+    def train_epoch(self, generator, sampler, epoch, batch_size, permute=False, exact_last=False):
         """One epoch over a fixed dataset of on-device pairs, in the sampler's order (the reference's shuffled DataLoader over
         num_examples_train pairs): per step ``train_step_bits(*generator.bits(index=sampler.batch_index(epoch, step, batch_size)))``.
         generator: pairgen.PairGenerator; sampler: sampler.EpochSampler (its rank and world size are this process's).  The loop reads
         nothing back (a ragged generator's vertex counts stay on the device as well).  Returns the (steps,) device tensor of the
         per-step losses of the global batch.
         permute=True: the pairs come relabelled (``generator.bits(index=..., permute=True)``) and the step trains on the
-        cross-entropy against their planted labels (train_step_bits(labels=...))."""
+        cross-entropy against their planted labels (train_step_bits(labels=...)).
+        exact_last=True: every example trains exactly once per epoch -- the positions with which a short last step is filled (they
+        wrap to examples the epoch has already shown) are switched off (train_step_bits(live=sampler.live_count(...)), DESIGN.md
+        section 14); every step then runs the weighted launches.  A rank whose last step has no live pair still takes part in the
+        all-reduce, with a zero gradient.  False (default): the filled step trains its repeats, as before."""
         steps = sampler.steps_per_epoch(batch_size)
         losses = torch.empty(steps, dtype=torch.float32, device=self.params.device)
         for step in range(steps):
+            xkw = {'live': sampler.live_count(step, batch_size)} if exact_last else {}
             if permute:
                 b1, b2, nv, lab = generator.bits(index=sampler.batch_index(epoch, step, batch_size), permute=True)
-                loss, _ = self.train_step_bits(b1, b2, nv, labels=lab)
+                loss, _ = self.train_step_bits(b1, b2, nv, labels=lab, **xkw)
             else:
-                loss, _ = self.train_step_bits(*generator.bits(index=sampler.batch_index(epoch, step, batch_size)))
+                loss, _ = self.train_step_bits(*generator.bits(index=sampler.batch_index(epoch, step, batch_size)), **xkw)
             losses[step].copy_(loss)
         return losses
 
@@ -532,7 +655,7 @@ class FgnnTrainer:
             meter.allreduce_()
         return meter
 
-    def fit(self, train_gen, train_sampler, val_gen, val_sampler, epochs, batch_size, scheduler=None, permute=False):
+    def fit(self, train_gen, train_sampler, val_gen, val_sampler, epochs, batch_size, scheduler=None, permute=False, exact_last=False):
         """The reference's training loop around its scheduler (models/trainers.py:92-104): per epoch train_epoch, evaluate, ONE host
         read (the validation record), scheduler.step(val_loss).  scheduler=None: optim.ReduceLROnPlateau with the reference's
         settings, driving self.opt.lr (the next step pushes a changed rate to the device).  Returns the per-epoch history: dicts
@@ -540,31 +663,38 @@ class FgnnTrainer:
         rate the NEXT epoch runs with).
         permute=True: training and validation run on planted pairs (train_epoch(permute=True), evaluate(permute=True,
         loss_on_labels=True)): 'val_loss' (what the scheduler sees), 'val_acc' and 'val_acc_max' all refer to the labels, and the
-        Hungarian accuracy is free of the identity tie bias."""
+        Hungarian accuracy is free of the identity tie bias.
+        exact_last: handed to train_epoch."""
         if scheduler is None:
             from .optim import ReduceLROnPlateau
             scheduler = ReduceLROnPlateau(self.opt)
         history = []
+        xkw = {'exact_last': True} if exact_last else {}
         for epoch in range(int(epochs)):
             if permute:
-                losses = self.train_epoch(train_gen, train_sampler, epoch, batch_size, permute=True)
+                losses = self.train_epoch(train_gen, train_sampler, epoch, batch_size, permute=True, **xkw)
                 res = self.evaluate(val_gen, val_sampler, batch_size, epoch=epoch, permute=True, loss_on_labels=True).result()
             else:
-                losses = self.train_epoch(train_gen, train_sampler, epoch, batch_size)
+                losses = self.train_epoch(train_gen, train_sampler, epoch, batch_size, **xkw)
                 res = self.evaluate(val_gen, val_sampler, batch_size, epoch=epoch).result()
             scheduler.step(res['loss'])
             history.append({'epoch': epoch, 'train_losses': losses, 'val_loss': res['loss'], 'val_acc': res['acc'],
                             'val_acc_max': res['acc_max'], 'lr': self.opt.lr})
         return history
 
-    def train_step(self, x1, x2, nvalid=None, labels=None):
+    def train_step(self, x1, x2, nvalid=None, labels=None, weights=None, live=None):
         """x1, x2: (B, c0, N, N) local shard on the GPU (precision='bf16' with a 32-channel layout: any 1..32 channels, e.g. the four
         spectral ones; the engine's input conversion zero-fills the rest).  Returns (loss of the global batch as a device
         scalar, scores of the local shard).
         labels: None (the identity, the reference's target), or what metrics.labels_tensor takes -- a (B, N) integer tensor with
         labels[b, i] = the vertex of x2[b] that vertex i of x1[b] matches (-1: no target), or a list of B integer arrays: the loss is
         the cross-entropy against them (normalised by the node count as before).  An int32 device tensor is
-        read in place by the eager step and copied into the captured step's static buffer."""
+        read in place by the eager step and copied into the captured step's static buffer.
+        weights: None, or (B,) per-pair factors u_b >= 0 multiplied into the weights of the reduction.  live: None, or the number of
+        leading pairs of the shard that count (an int, or a 1-element int32 device tensor): the others are fillers, switched off by
+        a select -- they add nothing to loss, gradient and normaliser, whatever their scores hold (EpochSampler.live_count; a rank
+        may pass 0).  With either, or with loss_reduction='mean_of_mean', the step runs the weighted launches (DESIGN.md section
+        15): the loss returned is sum_b w_b CE_b / D over the global batch.  A global step must have a pair that counts (D > 0)."""
         if self.input_form == 'tensor_representation' and x1.dim() == 4 and x1.shape[1] == 2 and self.layout.c0 == 2 \
                 and x1.dtype == torch.float32 and x1.shape == x2.shape:
             from . import _lib
@@ -583,21 +713,31 @@ class FgnnTrainer:
                 self._tr_calls += 1
                 if first or (self.INPUT_CHECK_EVERY and self._tr_calls % self.INPUT_CHECK_EVERY == 0):
                     self.check_input_form()
-                out = self.train_step_bits(w[:B], w[B:], nvalid=nv, **({} if labels is None else {'labels': labels}))
+                xkw = {} if labels is None else {'labels': labels}
+                if weights is not None:
+                    xkw['weights'] = weights
+                if live is not None:
+                    xkw['live'] = live
+                out = self.train_step_bits(w[:B], w[B:], nvalid=nv, **xkw)
                 if first and (B, N, 'bits') in self._graphs:        # from now on pack straight into the captured step's input words
                     self._tr[(B, N)] = self._graphs[(B, N, 'bits')][0]
                 return out
         labels = self._labels(labels, x1.shape[0], x1.shape[-1])
+        weighted = self._weighted(weights, live)
         if self.capture and nvalid is None:
+            if weighted:
+                return self._captured_step(x1, x2, labels=labels, weights=self._user_weights(weights, x1.shape[0]), live=live, weighted=True)
             return self._captured_step(x1, x2, labels=labels)
         B, _, N, _ = x1.shape
         eng = self._engine(2 * B, N, nvalid is not None)
         x = torch.cat([x1, x2]).contiguous()
         nv = None if nvalid is None else torch.cat([nvalid, nvalid])
-        if nvalid is None:
+        lkw = {} if labels is None else {'labels': labels}
+        if weighted:
+            lkw['weights'] = self._pair_weights(B, N, nvalid, live, weights)        # (self._nodes <- D)
+        elif nvalid is None:
             self._nodes.fill_(float(B * N))
         else:
             self._nodes.copy_(nvalid.sum().to(torch.float32).reshape(1))     # device-side, no host sync
-        lkw = {} if labels is None else {'labels': labels}
         scores, _ = eng.step(self.params, self.grads, x, nvalid=nv, total_nodes=1.0, loss_out=self._loss_sum, **lkw)
         return self._reduce_and_update(), scores

@@ -335,6 +335,34 @@ int fgnn_ce_fwd_labels(const float *scores, const int *nvalid, const int *labels
 int fgnn_ce_bwd_labels(const float *scores, const float *lse, const int *nvalid, const int *labels, const float *gscale, int B, int N,
                        float *dscores, void *stream);
 
+/* ---- per-pair loss weights in the fused step: triplet_loss('mean_of_mean'), an exact short last batch, or any
+ * weighting of the caller's.  pair_weight: (B,) fp32 on the device, w_b >= 0, read in place like nvalid and labels.
+ *     loss_sum = sum over b with w_b != 0 of w_b * CE_b           (CE_b: the sum of the pair's row-block partials, which stay unweighted)
+ *     dS_b     = w_b * gscale * (softmax_row(S_b) - target)       for w_b != 0;  exactly +0 for w_b == 0
+ * w_b == 0 is a SELECT, not a multiply: the backward treats the pair as nvalid = 0 and the loss sum steps over it, so NaN or inf in
+ * the scores / lse / partials of a filler pair reach neither the loss nor the gradient.  With w == 1 everywhere every output has the
+ * bits of the unweighted entry point: the one new operation is gs = *gscale * w_b per workgroup, and fgnn_pair_loss_w adds in the
+ * order of fgnn_sum_scale / the loss job of fgnn_grad_finalize.  No scratch, no atomics, plain vector stores; single capturable
+ * launches without a host read, allocation or synchronisation.
+ *
+ * fgnn_score_ce_bwd_w: fgnn_score_ce_bwd (labels == NULL) or fgnn_score_ce_bwd_labels with the weights; geometry, form selection
+ * and LDS are theirs (WGT instantiations of the same bodies). */
+int fgnn_score_ce_bwd_w(const float *e1, const float *e2, const float *scores, const float *lse, const int *nvalid,
+                        const int *labels /* may be NULL */, const float *pair_weight, const float *gscale, int B, int C, int N,
+                        float *de1, float *de2, void *stream);
+/* The weights of a reduction and their normaliser D, in one workgroup and a fixed order.  With n_b = nvalid[b] (NULL: N) and
+ * live = *live_dev (an int32 DEVICE scalar, clamped to [0, B]; NULL: B), u_b = user[b] (NULL: 1):
+ *     mode 0 ('mean'):          w_b = [b < live] * u_b,                  D = sum_{b < live} n_b * u_b
+ *     mode 1 ('mean_of_mean'):  w_b = [b < live and n_b > 0] / n_b * u_b, D = sum_{b < live, n_b > 0} u_b
+ * (user == NULL: D is the node count resp. the number of non-empty live pairs.)  D is summed in fp64 and written as fp32; the
+ * division is IEEE.  w_out (B,), denom_out (1,). */
+int fgnn_pair_weights(const int *nvalid, const int *live_dev, int mode, const float *user, int B, int N, float *w_out,
+                      float *denom_out, void *stream);
+/* out[0] = sum over b with w_b != 0, over the pair's row_blocks partials, of w_b * pair_loss[b * row_blocks + k]: the four-lane
+ * order of fgnn_sum_scale on the same (B * row_blocks) partials (rows r = 0, 4, 8, ... / 1, 5, ... / 2, ... / 3, ..., then
+ * (l0 + l1) + (l2 + l3)), each product rounded before it is added. */
+int fgnn_pair_loss_w(const float *pair_loss, int row_blocks, const float *pair_weight, int B, float *out, void *stream);
+
 /* triplet_loss on a given score tensor: lse (B,N), pair_loss (B) (toolbox/losses.py:27-34) */
 int fgnn_ce_fwd(const float *scores, const int *nvalid, int B, int N, float *lse, float *pair_loss, void *stream);
 /* dscores = (softmax_row(scores) - I) * (*gscale) on valid entries, 0 on padding */
