@@ -25,6 +25,7 @@ FGNN_SPECTRAL_MAX_N = 256    # include/fgnn_hip.h: largest graph of fgnn_spectra
 FGNN_SPECTRAL_MAX_POWERS = 8
 FGNN_PLANTED_MAX_N = 256      # include/fgnn_hip.h: largest graph of the fgnn_planted_perm / fgnn_relabel_* kernels
 FGNN_SCORE_SPLIT = 4
+FGNN_RANK_MAX_K = 8          # include/fgnn_hip.h: thresholds of fgnn_rank_fold, hits[] of fgnn_rank_record
 
 c_float_p = C.c_void_p   # device pointers travel as integers
 
@@ -155,6 +156,11 @@ class GuardRecord(C.Structure):       # fgnn_guard_record (csrc/grad_guard.hip);
 class EvalRecord(C.Structure):        # fgnn_eval_record (csrc/eval.hip); lives in device memory, this mirror gives the offsets
     _fields_ = [('ce_sum', C.c_double), ('nodes', C.c_longlong), ('correct_lsap', C.c_longlong), ('correct_max', C.c_longlong),
                 ('pairs', C.c_longlong), ('steps', C.c_longlong)]
+
+
+class RankRecord(C.Structure):        # fgnn_rank_record (csrc/rank.hip); lives in device memory, this mirror gives the offsets
+    _fields_ = [('rr_sum', C.c_double), ('rank_sum', C.c_longlong), ('targets', C.c_longlong), ('nodes', C.c_longlong),
+                ('pairs', C.c_longlong), ('steps', C.c_longlong), ('hits', C.c_longlong * FGNN_RANK_MAX_K)]
 
 
 MAX_GRAD_JOBS = 16
@@ -288,6 +294,8 @@ _SIGNATURES = {
     'fgnn_eval_pairs_labels': [_VP, _VP, _VP, _I, _I, _VP, _LL, _I, _VP, _VP, _VP],
     'fgnn_eval_fold': [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP],
     'fgnn_eval_fold_bins': [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP],
+    'fgnn_eval_ranks': [_VP, _LL, _I, _VP, _VP, _I, _I, _VP, _VP],
+    'fgnn_rank_fold': [_VP, _VP, _I, _I, _I, C.POINTER(C.c_int), _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP],
     # ---- bf16 path ----
     'fgnn_tiles_per_graph16': [_I, _I],
     'fgnn_to_bf16': [_VP, _VP, _I, _I, _I, _I, _VP, _LL, _LL, _VP],

@@ -9,6 +9,10 @@ have a fixed order.  Nothing is read back until ``EvalMeter.result()``.  There i
 ``BinnedEvalMeter`` is K such records side by side and ``evaluate_scores(..., bins=)`` adds every pair to the record of its bin
 (fgnn_eval_fold_bins in place of the fourth launch): the accuracy of a model across K noise levels from one pass
 (``FgnnTrainer.noise_curve``), each record with the bits ``fgnn_eval_fold`` gives for its pairs alone.
+
+``rank_scores`` gives the rank of every row's true match and the Hits@k / reciprocal-rank sums with two launches (csrc/rank.hip:
+fgnn_eval_ranks, fgnn_rank_fold) into a ``RankMeter`` or, with ``bins=``, a ``BinnedRankMeter``; ``evaluate_scores(...,
+rank_meter=)`` issues them after its own four, on the same scores, labels, ``live`` and bins.
 """
 import ctypes
 
@@ -145,7 +149,261 @@ def record_result(rec):
             'nodes': nodes, 'pairs': rec['pairs']}
 
 
-def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False, bins=None):
+class RankMeter:
+    """The device record of the rank metrics of an evaluation epoch (fgnn_rank_record, include/fgnn_hip.h) for the thresholds `ks`
+    (1 to FGNN_RANK_MAX_K positive, strictly increasing integers).  `rr_sum` (fp64), `rank_sum`, `targets`, `nodes`, `pairs`, `steps`
+    (int64) are 0-dim views of the record, `hits[q]` the view of the count for ks[q]; `mrr`, `mean_rank` and `hits_at(k)` are 0-dim
+    fp64 device tensors formed from them on the device.  `result()` is the only host synchronisation."""
+
+    FIELDS = ('rr_sum', 'rank_sum', 'targets', 'nodes', 'pairs', 'steps')
+
+    def __init__(self, device, ks=(1, 5, 10), buf=None):
+        """buf: the record's bytes when they belong to a larger buffer (a record of a BinnedRankMeter)"""
+        self.ks = check_ks(ks)
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise RuntimeError('RankMeter: device %s; the epoch record lives on the GPU (there is no CPU path)' % (device,))
+        R = _lib.RankRecord
+        self.buf = torch.zeros(ctypes.sizeof(R), dtype=torch.uint8, device=device) if buf is None else buf
+        self.rr_sum = self.buf[R.rr_sum.offset:R.rr_sum.offset + 8].view(torch.float64).reshape(())
+        for name in self.FIELDS[1:]:
+            off = getattr(R, name).offset
+            setattr(self, name, self.buf[off:off + 8].view(torch.int64).reshape(()))
+        self.hits = [self.buf[R.hits.offset + 8 * q:R.hits.offset + 8 * q + 8].view(torch.int64).reshape(()) for q in range(len(self.ks))]
+
+    def reset(self):
+        self.buf.zero_()
+        return self
+
+    @property
+    def mrr(self):
+        """rr_sum / targets: the mean reciprocal rank of everything folded so far (NaN before the first target)"""
+        return self.rr_sum / self.targets.to(torch.float64)
+
+    @property
+    def mean_rank(self):
+        return self.rank_sum.to(torch.float64) / self.targets.to(torch.float64)
+
+    def hits_at(self, k):
+        return self.hits[self.ks.index(int(k))].to(torch.float64) / self.targets.to(torch.float64)
+
+    def record(self):
+        """The record as a dict of Python numbers, 'hits' as {k: count} (one device-to-host copy)."""
+        return rank_record_dict(_lib.RankRecord.from_buffer_copy(self.buf.cpu().numpy().tobytes()), self.ks)
+
+    def result(self):
+        """{'hits@k' for every k, 'mrr', 'mean_rank', 'targets', 'nodes', 'pairs'} of the epoch (one device-to-host copy: the one
+        synchronisation)."""
+        return rank_result(self.record())
+
+    def allreduce_(self):
+        """Sum the record over the ranks: one all-reduce of 14 fp64 values (the counts are exact below 2^53)."""
+        t = pack_rank_records(self.buf, 1)
+        dp.allreduce_sum_(t)
+        unpack_rank_records_(self.buf, 1, t)
+        return self
+
+
+class BinnedRankMeter:
+    """K rank records in one device buffer, one per bin (the noise levels of FgnnTrainer.noise_curve): `meter[k]` is a RankMeter on
+    record k's bytes.  values: K labels of the bins, carried as 'noise' in the dicts of `record()` / `result()`."""
+
+    def __init__(self, device, K, ks=(1, 5, 10), values=None):
+        K = int(K)
+        if not 1 <= K <= _lib.FGNN_MAX_LEVELS:
+            raise ValueError('BinnedRankMeter: between 1 and %d records, got %d' % (_lib.FGNN_MAX_LEVELS, K))
+        if values is not None and len(values) != K:
+            raise ValueError('BinnedRankMeter: %d values for %d records' % (len(values), K))
+        self.ks = check_ks(ks)
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise RuntimeError('BinnedRankMeter: device %s; the epoch records live on the GPU (there is no CPU path)' % (device,))
+        size = ctypes.sizeof(_lib.RankRecord)
+        self.K, self.values = K, None if values is None else tuple(values)
+        self.buf = torch.zeros(K * size, dtype=torch.uint8, device=device)
+        self.meters = [RankMeter(device, ks=self.ks, buf=self.buf[k * size:(k + 1) * size]) for k in range(K)]
+
+    def __len__(self):
+        return self.K
+
+    def __getitem__(self, k):
+        return self.meters[k]
+
+    def reset(self):
+        self.buf.zero_()
+        return self
+
+    def record(self):
+        """The K records as dicts of Python numbers, with 'noise' when values were given (one device-to-host copy)."""
+        recs = (_lib.RankRecord * self.K).from_buffer_copy(self.buf.cpu().numpy().tobytes())
+        out = [rank_record_dict(r, self.ks) for r in recs]
+        if self.values is not None:
+            for r, v in zip(out, self.values):
+                r['noise'] = v
+        return out
+
+    def result(self):
+        """rank_result of every record, with 'noise' when values were given (one device-to-host copy: the one synchronisation)."""
+        out = []
+        for rec in self.record():
+            res = rank_result(rec)
+            if 'noise' in rec:
+                res['noise'] = rec['noise']
+            out.append(res)
+        return out
+
+    def allreduce_(self):
+        """Sum the records over the ranks: one all-reduce of K x 14 fp64 values (the counts are exact below 2^53)."""
+        t = pack_rank_records(self.buf, self.K)
+        dp.allreduce_sum_(t)
+        unpack_rank_records_(self.buf, self.K, t)
+        return self
+
+
+def check_ks(ks):
+    """The thresholds of a rank meter as a tuple of ints: 1 to FGNN_RANK_MAX_K of them, positive, strictly increasing."""
+    try:
+        ks = tuple(ks)
+    except TypeError:
+        raise ValueError('ks must be a sequence of integers, got %r' % (ks,))
+    if not 1 <= len(ks) <= _lib.FGNN_RANK_MAX_K:
+        raise ValueError('ks: between 1 and %d thresholds, got %d' % (_lib.FGNN_RANK_MAX_K, len(ks)))
+    if any(isinstance(k, bool) or int(k) != k for k in ks):
+        raise ValueError('ks must be integers, got %r' % (ks,))
+    ks = tuple(int(k) for k in ks)
+    if ks[0] < 1 or any(b <= a for a, b in zip(ks, ks[1:])) or ks[-1] > 0x7fffffff:
+        raise ValueError('ks must be positive and strictly increasing, got %r' % (ks,))
+    return ks
+
+
+RANK_WORDS = ctypes.sizeof(_lib.RankRecord) // 8
+
+
+def pack_rank_records(buf, K):
+    """The bytes of K rank records (a uint8 tensor on any device) -> the (K, 14) fp64 tensor of their all-reduce: rr_sum as it is,
+    the int64 counts converted (exact below 2^53).  A pure function of tensors."""
+    words = buf.view(torch.int64).view(K, RANK_WORDS)
+    rr = buf.view(torch.float64).view(K, RANK_WORDS)[:, :1]
+    return torch.cat([rr, words[:, 1:].to(torch.float64)], dim=1).contiguous()
+
+
+def unpack_rank_records_(buf, K, t):
+    """The inverse of pack_rank_records: writes the (K, 14) fp64 tensor t into the records' bytes, in place."""
+    buf.view(torch.float64).view(K, RANK_WORDS)[:, :1].copy_(t[:, :1])
+    buf.view(torch.int64).view(K, RANK_WORDS)[:, 1:].copy_(t[:, 1:].round().to(torch.int64))
+    return buf
+
+
+def rank_record_dict(rec, ks):
+    out = {name: getattr(rec, name) for name in RankMeter.FIELDS}
+    out['hits'] = {k: rec.hits[q] for q, k in enumerate(ks)}
+    return out
+
+
+def rank_result(rec):
+    """Hits@k = hits[k] / targets, MRR = rr_sum / targets, the mean rank = rank_sum / targets: ratios over the rows that have a
+    target.  An empty record gives NaN."""
+    targets = rec['targets']
+    div = (lambda a: a / targets) if targets else (lambda a: float('nan'))
+    out = {'hits@%d' % k: div(h) for k, h in rec['hits'].items()}
+    out.update({'mrr': div(rec['rr_sum']), 'mean_rank': div(rec['rank_sum']), 'targets': targets, 'nodes': rec['nodes'],
+                'pairs': rec['pairs']})
+    return out
+
+
+def read_records(meter, rank_meter):
+    """(meter.record(), rank_meter.record()) of an EvalMeter and a RankMeter from ONE device-to-host copy."""
+    raw = torch.cat([meter.buf, rank_meter.buf]).cpu().numpy().tobytes()
+    size = ctypes.sizeof(_lib.EvalRecord)
+    rec = _lib.EvalRecord.from_buffer_copy(raw[:size])
+    return ({name: getattr(rec, name) for name in EvalMeter.FIELDS},
+            rank_record_dict(_lib.RankRecord.from_buffer_copy(raw[size:]), rank_meter.ks))
+
+
+def _score_args(who, scores, nvalid, labels, live, bins):
+    """The argument forms and refusals evaluate_scores and rank_scores share -> (s fp32 contiguous, nvalid, labels, bins int32 on the
+    scores' device, B, N, live)."""
+    if isinstance(scores, MaskedTensor):
+        if nvalid is None:
+            nvalid = scores.nvalid
+        scores = scores.tensor
+    if not torch.is_tensor(scores) or scores.dim() != 3 or scores.shape[1] != scores.shape[2] or not scores.is_floating_point():
+        raise ValueError('%s: expected (B, N, N) floating-point scores, got %s'
+                         % (who, tuple(scores.shape) if torch.is_tensor(scores) else type(scores).__name__,))
+    if not scores.is_cuda:
+        raise RuntimeError('%s: scores on %s; the evaluation runs on the GPU only (there is no CPU path)' % (who, scores.device))
+    B, N, _ = scores.shape
+    if B < 1 or N < 1:
+        raise ValueError('%s: empty batch %s' % (who, tuple(scores.shape),))
+    if N > _lib.FGNN_LSAP_MAX_N:
+        raise RuntimeError('%s: at most %d vertices per graph (got %d)' % (who, _lib.FGNN_LSAP_MAX_N, N))
+    live = B if live is None else int(live)
+    if not 0 <= live <= B:
+        raise ValueError('%s: live = %d outside [0, %d]' % (who, live, B))
+    dev = scores.device
+    if nvalid is not None:
+        if not torch.is_tensor(nvalid) or tuple(nvalid.shape) != (B,) or nvalid.is_floating_point():
+            raise ValueError('%s: nvalid must be a (%d,) integer tensor' % (who, B))
+        nvalid = nvalid.to(device=dev, dtype=torch.int32).contiguous()
+    labels = labels_tensor(labels, B, N, dev)
+    if bins is not None:
+        if not torch.is_tensor(bins) or tuple(bins.shape) != (B,) or bins.is_floating_point() or bins.dtype == torch.bool:
+            raise ValueError('%s: bins must be a (%d,) integer tensor' % (who, B))
+        bins = bins.to(device=dev, dtype=torch.int32).contiguous()
+    return scores.detach().to(torch.float32).contiguous(), nvalid, labels, bins, B, N, live
+
+
+def _check_rank_meter(who, meter, bins, dev, ks=None):
+    if isinstance(meter, BinnedRankMeter) != (bins is not None):
+        raise ValueError('%s: bins= and a BinnedRankMeter as rank meter go together' % who)
+    if not isinstance(meter, (RankMeter, BinnedRankMeter)) or meter.buf.device != dev:
+        raise ValueError('%s: the rank meter must be a RankMeter (with bins=: a BinnedRankMeter) on %s' % (who, dev))
+    if ks is not None and check_ks(ks) != meter.ks:
+        raise ValueError('%s: ks = %r differ from the meter\'s %r' % (who, tuple(ks), meter.ks))
+
+
+def _rank_launches(s, nvalid, labels, bins, B, N, live, meter):
+    """fgnn_eval_ranks, fgnn_rank_fold on checked arguments (on the current stream of s's device) -> the dict of rank_scores"""
+    dev = s.device
+    nk = len(meter.ks)
+    # one zero-filled allocation for the five outputs (one fill launch instead of five): the 8-byte words first
+    words = torch.zeros(2 * B + (B * (N + nk + 1) + 1) // 2, dtype=torch.int64, device=dev)
+    rr, rank_sum = words[:B].view(torch.float64), words[B:2 * B]
+    ints = words[2 * B:].view(torch.int32)
+    rank = ints[:B * N].view(B, N)
+    hits = ints[B * N:B * (N + nk)].view(B, nk)
+    targets = ints[B * (N + nk):B * (N + nk + 1)]
+    st = _lib.stream_ptr()
+    _lib.call('fgnn_eval_ranks', _lib.ptr(s), N * N, N, _lib.ptr(nvalid), _lib.ptr(labels), B, N, _lib.ptr(rank), st)
+    _lib.call('fgnn_rank_fold', _lib.ptr(rank), _lib.ptr(nvalid), B, N, live, (ctypes.c_int * nk)(*meter.ks), nk, _lib.ptr(bins),
+              meter.K if bins is not None else 1, _lib.ptr(hits), _lib.ptr(rr), _lib.ptr(rank_sum), _lib.ptr(targets),
+              _lib.ptr(meter.buf), st)
+    return {'rank': rank, 'hits': hits, 'rr': rr, 'rank_sum': rank_sum, 'targets': targets, 'meter': meter}
+
+
+def rank_scores(scores, nvalid=None, labels=None, meter=None, live=None, bins=None, ks=None):
+    """The rank of every row's true match and its sums: scores, nvalid, labels, live, bins as evaluate_scores takes them (a
+    MaskedTensor included), with the same refusals.  rank[b, i] = 1 + the number of columns j < n_b that beat the target column
+    t = labels[b, i] (None: i) in the order of the arg-max of accuracy_max -- a larger score, NaN above every number, the smaller
+    index on ties -- so rank 1 is an arg-max hit; 0 for a row whose label lies outside [0, n_b).
+    Adds the live pairs to `meter` (a RankMeter; with bins= a BinnedRankMeter, pair b to record bins[b]; None: a fresh RankMeter of
+    ks, default (1, 5, 10)); ks, when given next to a meter, must be the meter's.  Returns the device tensors {'rank': (B, N) int32, 0
+    in the padding rows, 'hits': (B, nk) int32 rows with 1 <= rank <= ks[q], 'rr': (B,) fp64 sums of 1 / rank, 'rank_sum': (B,) int64,
+    'targets': (B,) int32 rows with a target, 'meter'}; the sums of pairs >= live are zero.
+    Two launches (fgnn_eval_ranks, fgnn_rank_fold), nothing is read back."""
+    if meter is None and bins is not None:
+        raise ValueError('rank_scores: bins= and a BinnedRankMeter as rank meter go together')
+    s, nvalid, labels, bins, B, N, live = _score_args('rank_scores', scores, nvalid, labels, live, bins)
+    if meter is None:
+        meter = RankMeter(s.device, ks=(1, 5, 10) if ks is None else ks)
+    else:
+        _check_rank_meter('rank_scores', meter, bins, s.device, ks)
+    with torch.cuda.device(s.device):
+        return _rank_launches(s, nvalid, labels, bins, B, N, live, meter)
+
+
+def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False, bins=None,
+                    rank_meter=None):
     """scores: (B, N, N) fp32 raw scores on the GPU, or a MaskedTensor of them (its vertex counts are used unless nvalid is given).
     nvalid: (B,) vertex counts in [0, N]; labels: see metrics.py (None: the identity; they enter the accuracies, never the loss).
     live: the first `live` pairs count (None: all B) -- the others, the filling of a short last step, are ignored entirely.
@@ -159,43 +417,22 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
     bins: a (B,) integer device tensor with a BinnedEvalMeter as `meter` (the two go together): live pair b is added to record
     bins[b] of the meter, a pair whose bin lies outside [0, K) to none (fgnn_eval_fold_bins as the fourth launch; the other three
     and everything returned are the same).
+    rank_meter: a RankMeter (with bins=: a BinnedRankMeter) -- the two launches of rank_scores follow on the same scores, labels,
+    live and bins and add to it; their per-pair tensors come back under 'ranks'.  None: nothing of this is launched.
     Four launches, nothing is read back."""
     if isinstance(meter, BinnedEvalMeter) != (bins is not None):
         raise ValueError('evaluate_scores: bins= and a BinnedEvalMeter as meter go together')
-    if isinstance(scores, MaskedTensor):
-        if nvalid is None:
-            nvalid = scores.nvalid
-        scores = scores.tensor
-    if not torch.is_tensor(scores) or scores.dim() != 3 or scores.shape[1] != scores.shape[2] or not scores.is_floating_point():
-        raise ValueError('evaluate_scores: expected (B, N, N) floating-point scores, got %s'
-                         % (tuple(scores.shape) if torch.is_tensor(scores) else type(scores).__name__,))
-    if not scores.is_cuda:
-        raise RuntimeError('evaluate_scores: scores on %s; the evaluation runs on the GPU only (there is no CPU path)' % (scores.device,))
-    B, N, _ = scores.shape
-    if B < 1 or N < 1:
-        raise ValueError('evaluate_scores: empty batch %s' % (tuple(scores.shape),))
-    if N > _lib.FGNN_LSAP_MAX_N:
-        raise RuntimeError('evaluate_scores: at most %d vertices per graph (got %d)' % (_lib.FGNN_LSAP_MAX_N, N))
-    live = B if live is None else int(live)
-    if not 0 <= live <= B:
-        raise ValueError('evaluate_scores: live = %d outside [0, %d]' % (live, B))
-    dev = scores.device
-    if nvalid is not None:
-        if not torch.is_tensor(nvalid) or tuple(nvalid.shape) != (B,) or nvalid.is_floating_point():
-            raise ValueError('evaluate_scores: nvalid must be a (%d,) integer tensor' % B)
-        nvalid = nvalid.to(device=dev, dtype=torch.int32).contiguous()
-    labels = labels_tensor(labels, B, N, dev)
+    s, nvalid, labels, bins, B, N, live = _score_args('evaluate_scores', scores, nvalid, labels, live, bins)
+    dev = s.device
     if bins is not None:
-        if not torch.is_tensor(bins) or tuple(bins.shape) != (B,) or bins.is_floating_point() or bins.dtype == torch.bool:
-            raise ValueError('evaluate_scores: bins must be a (%d,) integer tensor' % B)
         if meter.buf.device != dev:
             raise ValueError('evaluate_scores: meter must be a BinnedEvalMeter on %s' % (dev,))
-        bins = bins.to(device=dev, dtype=torch.int32).contiguous()
     elif meter is None:
         meter = EvalMeter(dev)
     elif not isinstance(meter, EvalMeter) or meter.buf.device != dev:
         raise ValueError('evaluate_scores: meter must be an EvalMeter on %s' % (dev,))
-    s = scores.detach().to(torch.float32).contiguous()
+    if rank_meter is not None:
+        _check_rank_meter('evaluate_scores', rank_meter, bins, dev)
     with torch.cuda.device(dev):
         i32 = dict(dtype=torch.int32, device=dev)
         cost = torch.empty(B, N, N, dtype=torch.float32, device=dev)
@@ -219,8 +456,12 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
         else:
             _lib.call('fgnn_eval_fold_bins', _lib.ptr(row_ce), _lib.ptr(row_hit), _lib.ptr(correct) if hungarian else None,
                       _lib.ptr(nvalid), B, N, live, _lib.ptr(bins), meter.K, _lib.ptr(pair_ce), _lib.ptr(pair_max), _lib.ptr(meter.buf), st)
+        ranks = None if rank_meter is None else _rank_launches(s, nvalid, labels, bins, B, N, live, rank_meter)
     n = nvalid if nvalid is not None else torch.full((B,), N, **i32)
-    return {'ce': pair_ce, 'n': n, 'correct_max': pair_max, 'correct_lsap': correct, 'assign': assign, 'meter': meter}
+    out = {'ce': pair_ce, 'n': n, 'correct_max': pair_max, 'correct_lsap': correct, 'assign': assign, 'meter': meter}
+    if ranks is not None:
+        out['ranks'] = ranks
+    return out
 
 
 def all_losses_acc(batches, model, eval_score='linear_assignment', labels=None):

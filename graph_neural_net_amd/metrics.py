@@ -77,6 +77,64 @@ def accuracy_max(weights, aggregate_score=True, labels=None):
     return (correct.to(torch.float64) / sizes.to(torch.float64)).tolist()
 
 
+def _ranks_host(blk, want):
+    """The rank of column want[i] in row i of an (n, n) block of host scores: 1 + the columns that beat it in the order of the arg-max
+    above (a larger score; NaN above every number; on equal scores, or two NaN, the smaller index) -- 0 where want[i] is no column."""
+    n = blk.shape[0]
+    want = want.to(torch.int64)
+    valid = (want >= 0) & (want < n)
+    t = want.clamp(0, max(n - 1, 0))[:, None]
+    st = blk.gather(1, t)
+    first = torch.arange(n)[None, :] < t
+    vnan, tnan = torch.isnan(blk), torch.isnan(st)
+    beats = torch.where(tnan, vnan & first, vnan | (blk > st) | ((blk == st) & first))
+    return torch.where(valid, 1 + beats.sum(1), torch.zeros_like(want)).to(torch.int32)
+
+
+def match_ranks(scores, labels=None):
+    """scores: (bs, n, n) tensor or MaskedTensor -> (bs, n) int32 ranks on the scores' device: rank[b, i] = 1 + the number of columns
+    j < n_b that beat the column row i should match (labels[b, i]; None: i) -- rank 1 is what accuracy_max counts; 0 for a row whose
+    label is no column of the graph and for the padding rows.  Host scores take a host route, device scores fgnn_eval_ranks."""
+    if isinstance(scores, MaskedTensor):
+        s, nvalid = scores.tensor, scores.nvalid
+    else:
+        s, nvalid = scores, None
+    s = s.detach()
+    B, N, _ = s.shape
+    labels = labels_tensor(labels, B, N, s.device)
+    if not s.is_cuda:
+        rank = torch.zeros(B, N, dtype=torch.int32)
+        sizes = [N] * B if nvalid is None else [min(max(int(n), 0), N) for n in nvalid.tolist()]
+        for b, n in enumerate(sizes):
+            if n:
+                rank[b, :n] = _ranks_host(s[b, :n, :n].float(), torch.arange(n) if labels is None else labels[b, :n])
+        return rank
+    s = s.to(torch.float32).contiguous()
+    nv32 = nvalid.to(device=s.device, dtype=torch.int32).contiguous() if nvalid is not None else None
+    rank = torch.zeros(B, N, dtype=torch.int32, device=s.device)
+    with torch.cuda.device(s.device):
+        _lib.call('fgnn_eval_ranks', _lib.ptr(s), N * N, N, _lib.ptr(nv32), _lib.ptr(labels), B, N, _lib.ptr(rank), _lib.stream_ptr())
+    return rank
+
+
+def hits_at_k(scores, k, labels=None, aggregate_score=True):
+    """Hits@k with the return convention of accuracy_max: (rows whose match ranks among the first k, n_vertices), or the list of
+    per-graph fractions with aggregate_score=False.  k = 1 is accuracy_max."""
+    k = int(k)
+    if k < 1:
+        raise ValueError('hits_at_k: k must be at least 1, got %d' % k)
+    rank = match_ranks(scores, labels)
+    B, N = rank.shape
+    if isinstance(scores, MaskedTensor):
+        sizes = scores.nvalid.to(device=rank.device, dtype=torch.int64).clamp(0, N)
+    else:
+        sizes = torch.full((B,), N, dtype=torch.int64, device=rank.device)
+    hits = ((rank >= 1) & (rank <= k)).sum(1)
+    if aggregate_score:
+        return int(hits.sum().item()), int(sizes.sum().item())
+    return [h / n if n else float('nan') for h, n in zip(hits.tolist(), sizes.tolist())]
+
+
 def accuracy_linear_assignment(rawscores, aggregate_score=True, labels=None):
     """rawscores: (bs, n, n) device tensor or MaskedTensor.  Minimum-cost matching on -log_softmax(scores) per graph (the
     assignment scipy.optimize.linear_sum_assignment returns, computed on the device by fgnn_lsap_accuracy: no copy of the

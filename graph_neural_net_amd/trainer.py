@@ -547,10 +547,10 @@ class FgnnTrainer:
         return scores
 
     def eval_step_bits(self, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False,
-                       bins=None):
+                       bins=None, rank_meter=None):
         """Forward-only evaluation of a batch handed over as train_step_bits takes it: the training engine's forward pass (a third of
         a step's work), then evaluation.evaluate_scores on its scores -- see there for labels, meter, live, hungarian,
-        loss_on_labels, bins and the returned per-pair device tensors.  Nothing is read back; parameters, gradients and optimizer state keep their bits."""
+        loss_on_labels, bins, rank_meter and the returned per-pair device tensors.  Nothing is read back; parameters, gradients and optimizer state keep their bits."""
         if bits1.dim() != 3 or bits1.shape != bits2.shape or bits1.dtype not in (torch.int32, torch.uint32) or not bits1.is_cuda:
             raise RuntimeError('FgnnTrainer.eval_step_bits: expected two (B, N, ceil(N/32)) int32 device tensors, got %s %s / %s %s'
                                % (tuple(bits1.shape), bits1.dtype, tuple(bits2.shape), bits2.dtype))
@@ -560,9 +560,11 @@ class FgnnTrainer:
         from .evaluation import evaluate_scores
         scores = self._eval_forward(B, N, nvalid, bits=torch.cat([bits1, bits2]).contiguous())
         return evaluate_scores(scores, nvalid=nvalid, labels=labels, meter=meter, live=live, hungarian=hungarian,
-                               **({'loss_on_labels': True} if loss_on_labels else {}), **({} if bins is None else {'bins': bins}))
+                               **({'loss_on_labels': True} if loss_on_labels else {}), **({} if bins is None else {'bins': bins}),
+                               **({} if rank_meter is None else {'rank_meter': rank_meter}))
 
-    def eval_step(self, x1, x2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False, bins=None):
+    def eval_step(self, x1, x2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False, bins=None,
+                  rank_meter=None):
         """eval_step_bits for dense batches: x1, x2 (B, c0, N, N) fp32 on the GPU, through the generic kernels (precision='bf16' with
         a 32-channel layout: any 1..32 channels, as train_step)."""
         if x1.dim() != 4 or x1.shape != x2.shape or not x1.is_cuda:
@@ -571,22 +573,28 @@ class FgnnTrainer:
         from .evaluation import evaluate_scores
         scores = self._eval_forward(x1.shape[0], x1.shape[-1], nvalid, x=torch.cat([x1, x2]).contiguous())
         return evaluate_scores(scores, nvalid=nvalid, labels=labels, meter=meter, live=live, hungarian=hungarian,
-                               **({'loss_on_labels': True} if loss_on_labels else {}), **({} if bins is None else {'bins': bins}))
+                               **({'loss_on_labels': True} if loss_on_labels else {}), **({} if bins is None else {'bins': bins}),
+                               **({} if rank_meter is None else {'rank_meter': rank_meter}))
 
-    def evaluate(self, generator, sampler, batch_size, epoch=0, hungarian=True, meter=None, permute=False, loss_on_labels=False):
+    def evaluate(self, generator, sampler, batch_size, epoch=0, hungarian=True, meter=None, permute=False, loss_on_labels=False,
+                 rank_meter=None):
         """One pass over this rank's examples of `sampler` (sampler.EpochSampler; shuffle=False is the reference's validation
         loader): per step ``eval_step_bits(*generator.bits(index=sampler.batch_index(epoch, step, batch_size)))`` with the generator's
         vertex counts and, with permute=True, its planted labels.  Every example counts exactly once: the positions with which a
         short last step is filled are masked out (live=sampler.live_count(...)).  With more than one rank the record is summed
         over the ranks at the end (one all-reduce of 6 values).  Reads nothing back; returns the meter (EvalMeter).
         loss_on_labels=True (with permute=True): the record's loss is the cross-entropy against the planted labels -- the model's
-        loss on those pairs, the one ReduceLROnPlateau should watch -- instead of the one against the identity."""
-        from .evaluation import EvalMeter
+        loss on those pairs, the one ReduceLROnPlateau should watch -- instead of the one against the identity.
+        rank_meter: a RankMeter that takes the rank of every example's true match (the planted labels with permute=True) from the
+        same steps (evaluation.rank_scores; two more launches per step) and is summed over the ranks like the meter."""
+        from .evaluation import EvalMeter, RankMeter
         B = int(batch_size)
         if meter is None:
             meter = EvalMeter(self.params.device)
         elif not isinstance(meter, EvalMeter):
             raise ValueError('FgnnTrainer.evaluate: meter must be an EvalMeter or None (got %s)' % type(meter).__name__)
+        if rank_meter is not None and not isinstance(rank_meter, RankMeter):
+            raise ValueError('FgnnTrainer.evaluate: rank_meter must be a RankMeter or None (got %s)' % type(rank_meter).__name__)
         for step in range(sampler.steps_per_epoch(B)):
             live = sampler.live_count(step, B)
             if live == 0:       # (a rank past the end of the data in the last global step)
@@ -597,9 +605,13 @@ class FgnnTrainer:
                 kw = {'loss_on_labels': True}
             else:
                 kw = {}
+            if rank_meter is not None:
+                kw['rank_meter'] = rank_meter
             self.eval_step_bits(b1, b2, nvalid=nv, labels=labels[0] if labels else None, meter=meter, live=live, hungarian=hungarian, **kw)
         if dp.world_size() > 1:
             meter.allreduce_()
+            if rank_meter is not None:
+                rank_meter.allreduce_()
         return meter
 
     @staticmethod
@@ -613,7 +625,7 @@ class FgnnTrainer:
         return e % M, e // M, sampler.live_count(step, batch_size)
 
     def noise_curve(self, generator, noises, num_examples, batch_size, hungarian=True, permute=False, loss_on_labels=False,
-                    rank=None, world_size=None, meter=None):
+                    rank=None, world_size=None, meter=None, rank_meter=None):
         """The reference's result figure (README.md, "Results": a trained model evaluated across noise levels; per level
         toolbox/metrics.py:144-166) in one pass: the first num_examples pairs of `generator` at each of the K = len(noises) noise
         levels -- the SAME parent graphs at every level, a paired design -- through full batches of mixed levels
@@ -626,8 +638,10 @@ class FgnnTrainer:
         rank for a whole curve each, or the parts of a split walked in one process -- the records stay this call's own.
         hungarian, permute, loss_on_labels: as in `evaluate`.  meter: a BinnedEvalMeter of K records to accumulate into (None: a
         fresh one whose values are the noises).  Reads nothing back: ``meter.result()``, K dicts with 'noise', 'loss', 'acc',
-        'acc_max', is the one host read.  Returns the meter."""
-        from .evaluation import BinnedEvalMeter
+        'acc_max', is the one host read.  Returns the meter.
+        rank_meter: a BinnedRankMeter of K records that takes the rank metrics of every level from the same steps; it is summed
+        over the ranks where the meter is."""
+        from .evaluation import BinnedEvalMeter, BinnedRankMeter
         from .sampler import EpochSampler
         levels = generator.levels(noises)
         K, M, B = len(levels), int(num_examples), int(batch_size)
@@ -637,6 +651,8 @@ class FgnnTrainer:
             meter = BinnedEvalMeter(self.params.device, K, values=levels.noises)
         elif not isinstance(meter, BinnedEvalMeter) or meter.K != K:
             raise ValueError('FgnnTrainer.noise_curve: meter must be a BinnedEvalMeter of %d records or None' % K)
+        if rank_meter is not None and (not isinstance(rank_meter, BinnedRankMeter) or rank_meter.K != K):
+            raise ValueError('FgnnTrainer.noise_curve: rank_meter must be a BinnedRankMeter of %d records or None' % K)
         if world_size is None:
             world_size = dp.world_size()
         if rank is None:        # (this process's rank in the split of torch.distributed; any other split has to name it)
@@ -644,6 +660,8 @@ class FgnnTrainer:
         sampler = EpochSampler(K * M, shuffle=False, rank=rank, world_size=world_size, drop_last=False, device=generator.device)
         kw = {'permute': True} if permute else {}
         ekw = {'loss_on_labels': True} if loss_on_labels else {}
+        if rank_meter is not None:
+            ekw['rank_meter'] = rank_meter
         for step in range(sampler.steps_per_epoch(B)):
             pair, level, live = self.noise_curve_batch(sampler, step, B, M)
             if live == 0:       # (a rank past the end of the examples in the last global step)
@@ -653,9 +671,12 @@ class FgnnTrainer:
                                 bins=level, **ekw)
         if dp.world_size() > 1 and sampler.world_size == dp.world_size():
             meter.allreduce_()
+            if rank_meter is not None:
+                rank_meter.allreduce_()
         return meter
 
-    def fit(self, train_gen, train_sampler, val_gen, val_sampler, epochs, batch_size, scheduler=None, permute=False, exact_last=False):
+    def fit(self, train_gen, train_sampler, val_gen, val_sampler, epochs, batch_size, scheduler=None, permute=False, exact_last=False,
+            rank_ks=None):
         """The reference's training loop around its scheduler (models/trainers.py:92-104): per epoch train_epoch, evaluate, ONE host
         read (the validation record), scheduler.step(val_loss).  scheduler=None: optim.ReduceLROnPlateau with the reference's
         settings, driving self.opt.lr (the next step pushes a changed rate to the device).  Returns the per-epoch history: dicts
@@ -664,22 +685,38 @@ class FgnnTrainer:
         permute=True: training and validation run on planted pairs (train_epoch(permute=True), evaluate(permute=True,
         loss_on_labels=True)): 'val_loss' (what the scheduler sees), 'val_acc' and 'val_acc_max' all refer to the labels, and the
         Hungarian accuracy is free of the identity tie bias.
-        exact_last: handed to train_epoch."""
+        exact_last: handed to train_epoch.
+        rank_ks: a tuple of thresholds (evaluation.RankMeter): every epoch's dict gains 'val_hits' ({k: Hits@k}) and 'val_mrr' of the
+        validation pairs, taken by the same validation steps and read with the validation record in the same single host copy."""
+        from .evaluation import EvalMeter, RankMeter, rank_result, read_records, record_result
         if scheduler is None:
             from .optim import ReduceLROnPlateau
             scheduler = ReduceLROnPlateau(self.opt)
         history = []
         xkw = {'exact_last': True} if exact_last else {}
+        rank_meter = None if rank_ks is None else RankMeter(self.params.device, ks=rank_ks)
+        ekw = {} if rank_meter is None else {'meter': EvalMeter(self.params.device), 'rank_meter': rank_meter}
         for epoch in range(int(epochs)):
+            if rank_meter is not None:
+                rank_meter.reset()
+                ekw['meter'].reset()
             if permute:
                 losses = self.train_epoch(train_gen, train_sampler, epoch, batch_size, permute=True, **xkw)
-                res = self.evaluate(val_gen, val_sampler, batch_size, epoch=epoch, permute=True, loss_on_labels=True).result()
+                meter = self.evaluate(val_gen, val_sampler, batch_size, epoch=epoch, permute=True, loss_on_labels=True, **ekw)
             else:
                 losses = self.train_epoch(train_gen, train_sampler, epoch, batch_size, **xkw)
-                res = self.evaluate(val_gen, val_sampler, batch_size, epoch=epoch).result()
+                meter = self.evaluate(val_gen, val_sampler, batch_size, epoch=epoch, **ekw)
+            if rank_meter is None:
+                res = meter.result()
+            else:
+                rec, rank_rec = read_records(meter, rank_meter)
+                res, rres = record_result(rec), rank_result(rank_rec)
             scheduler.step(res['loss'])
             history.append({'epoch': epoch, 'train_losses': losses, 'val_loss': res['loss'], 'val_acc': res['acc'],
                             'val_acc_max': res['acc_max'], 'lr': self.opt.lr})
+            if rank_meter is not None:
+                history[-1]['val_hits'] = {k: rres['hits@%d' % k] for k in rank_meter.ks}
+                history[-1]['val_mrr'] = rres['mrr']
         return history
 
     def train_step(self, x1, x2, nvalid=None, labels=None, weights=None, live=None):

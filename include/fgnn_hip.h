@@ -1001,6 +1001,42 @@ int fgnn_eval_fold_bins(const float *row_ce, const int *row_hit, const int *corr
                         int B, int N, int live, const int *bin /* (B) */, int K, double *pair_ce /* optional */,
                         int *pair_max /* optional */, fgnn_eval_record *records /* K records */, void *stream);
 
+/* Rank metrics (csrc/rank.hip): Hits@k and the mean reciprocal rank of the true match, per epoch and per bin.
+ * fgnn_eval_ranks, one pass over scores (fp32; row pitch ld >= N, pairs bstride >= N ld apart; nvalid as above, NOTHING outside
+ * the n_b x n_b corner is read): for a row i < n_b of pair b with target t = labels ? labels[b][i] : i (labels: optional int32 (B, N))
+ *   rank[b][i] = 1 + #{ j < n_b, j != t : column j beats column t }   when 0 <= t < n_b, and 0 otherwise (no target)
+ *   column j BEATS column t iff  s_j is NaN and s_t is not,  or  s_j > s_t,  or  j < t and (s_j == s_t or both are NaN)
+ * -- the order of the arg-max of fgnn_accuracy_max / fgnn_eval_pairs (first maximum on ties, NaN above every number, the first NaN
+ * wins, -0.0 == +0.0): rank == 1 exactly when row_hit of fgnn_eval_pairs is 1.  rank is int32 (B, N); rows >= n_b are not written.
+ * Integer counts: exact, whatever the order.  No limit on N beyond the launch grid.
+ * fgnn_rank_fold, for the pairs b < live (0 <= live <= B; the others are ignored entirely), with the nk thresholds ks (host memory,
+ * 1 <= nk <= FGNN_RANK_MAX_K, positive and strictly increasing; they reach the kernel by value):
+ *   pair_hits[b][q] (int32 (B, nk)) = #{i : 1 <= rank <= ks[q]}, pair_rr[b] (fp64) = sum_i 1.0 / rank, pair_rank_sum[b] (int64)
+ *   = sum_i rank, pair_targets[b] (int32) = #{i : rank >= 1}, all over the rows i < n_b with a target and each optional; lane l of
+ *   a wave adds the rows l, l + 64, ... in ascending order, the wave meets by a butterfly.  Then ONE workgroup adds the pairs to
+ *   the records in pair order, one pair at a time: pair b goes to records[bins[b]] (bins: optional int32[B] on the device, with K
+ *   contiguous records, 1 <= K <= FGNN_MAX_LEVELS; NULL: record 0, K must be 1); a pair whose bin lies outside [0, K) is added
+ *   nowhere.  rr_sum += pair_rr[b], rank_sum, targets, hits[q] likewise, nodes += n_b, pairs += 1; steps += 1 per call that added
+ *   a pair to the record.  A record that took no pair is not written.  No floating-point atomics, a fixed order: a record is
+ *   bit-identical however its examples were cut into calls, and a binned record has the bytes the plain fold gives for its pairs
+ *   alone.  hits[q] for q >= nk stay as they are.
+ * Both are single launches on `stream`: capturable, no allocation, no host copy, no synchronisation. */
+#define FGNN_RANK_MAX_K 8
+typedef struct {
+    double rr_sum;          /* sum of 1 / rank over the rows with a target of every live pair */
+    long long rank_sum;     /* sum of their ranks */
+    long long targets;      /* rows with a target */
+    long long nodes;        /* sum of n_b */
+    long long pairs;        /* live pairs folded */
+    long long steps;        /* fgnn_rank_fold calls that added a pair */
+    long long hits[FGNN_RANK_MAX_K];        /* rows with 1 <= rank <= ks[q] */
+} fgnn_rank_record;
+int fgnn_eval_ranks(const float *scores, long long bstride, int ld, const int *nvalid /* optional */, const int *labels /* optional */,
+                    int B, int N, int *rank, void *stream);
+int fgnn_rank_fold(const int *rank, const int *nvalid /* optional */, int B, int N, int live, const int *ks, int nk,
+                   const int *bins /* optional */, int K, int *pair_hits /* optional */, double *pair_rr /* optional */,
+                   long long *pair_rank_sum /* optional */, int *pair_targets /* optional */, fgnn_rank_record *records, void *stream);
+
 /* ---- test-only entry points (never on the product path; tests/ and tools/ call them) ---------------------------------------
  * fgnn_debug_mlp_fwd_masks / fgnn_debug_mlp_fwd_x3_masks: fgnn_mlp_fwd / fgnn_mlp_fwd_x3 once more -- the same tile code, the same
  * outputs, bit for bit -- that ALSO exports the ReLU decisions of the conv chain (models/layers.py:129-130), the input of the
