@@ -5,7 +5,7 @@
 // Everything here is latency work on at most 256 vertices: one wave or one small workgroup per pair, the permutation and its inverse
 // in LDS.  An inverse is built by scatter (inv[labels[i]] = i for i < n, -1 elsewhere), so a labels row that is no permutation of
 // [0, n) never indexes out of bounds: a column nobody maps to reads as an empty source (zeros).
-#include "fgnn_common.h"
+#include "fgnn_rows.h"
 #include "fgnn_philox.h"
 
 namespace {
@@ -13,8 +13,6 @@ namespace {
 constexpr int PL_MAX_N = FGNN_PLANTED_MAX_N;
 constexpr int PL_THREADS = 256;
 constexpr int PL_SLAB = 16;                // output rows per workgroup of the dense relabelling
-
-DEVI int corner_of(const int *nvalid, int b, int N) { return min(max(nvalid_of(nvalid, b, N), 0), N); }
 
 // inv[m] = i with labels[i] = m (i < n), -1 for every other m < PL_MAX_N; ends with a barrier
 DEVI void stage_inverse(int *inv, const int *labels, int n, int tid, int nthreads) {
@@ -133,8 +131,8 @@ __global__ __launch_bounds__(64) void count_matches_kernel(const int *assign, co
     if (lane == 0) correct[b] = cnt;
 }
 
-// accuracy_max_kernel (train_ops.hip) with a label row: the same arg-max -- np.argmax's order: the first maximum on ties, NaN above
-// every number (the first NaN wins), a row of -inf has column 0 -- compared with labels[i] instead of i.
+// accuracy_max_kernel (train_ops.hip) with a label row: the same arg-max -- row_argmax (fgnn_rows.h), written out here because the
+// call moves one instruction of this kernel -- compared with labels[i] instead of i.
 __global__ __launch_bounds__(256) void accuracy_max_labels_kernel(const float *scores, const int *labels, const int *nvalid, int N,
                                                                   int *correct) {
     __shared__ int red[4];

@@ -10,14 +10,13 @@
 // wave ballots: nothing assumes B symmetric), qap = sum_i popc(A'[i] & B[pi(i)]) and the trace = sum_i popc(A'[i] & Bt[pi(i)]).
 // One pair's matrices are at most 2 x 8 KB: they live in LDS.  Rows are NW in {1, 2, 4, 8} words (N <= 32 NW), zero-filled past the
 // valid corner, so nothing outside the corner is trusted.  Rows that lanes gather from at lane-dependent words have an odd pitch.
-#include "fgnn_common.h"
+#include "fgnn_rows.h"
 
 namespace {
 
 constexpr int QAP_THREADS = 256;           // 4 waves: wave w transposes rows 64 w .. 64 w + 63 (N <= 256)
 constexpr int QAP_SLAB = 64;               // rows of the cost matrix per workgroup of the improve-cost kernel
 
-DEVI int corner_of(const int *nvalid, int b, int N) { return min(max(nvalid_of(nvalid, b, N), 0), N); }
 // the bits of word w of a row that lie inside the n x n corner
 DEVI unsigned corner_mask(int w, int n) {
     const int lo = 32 * w;

@@ -8,7 +8,7 @@
 // Matrices: fp32, row pitch ld, pairs gstride floats apart (channel 0 of a (B, C, N, N) batch in place: gstride = C N N).  Only the
 // n_b x n_b corner is ever READ (it may be surrounded by NaN), rows pi(k) outside [0, n_b) count as zero rows.
 // Every reduction has a fixed order (no float atomics): results are bit-identical from run to run.
-#include "fgnn_common.h"
+#include "fgnn_rows.h"
 
 namespace {
 
@@ -17,8 +17,6 @@ constexpr int QW_ROWS = 32;                // rows of the cost matrix per workgr
 constexpr int QW_COLS = 128;               // columns per workgroup: wave w owns columns 32 w .. 32 w + 31 of them
 constexpr int QW_KC = 32;                  // k per staged chunk
 constexpr int QW_PA = QW_KC + 1;           // pitch of the A tile: lanes read it down a column (odd pitch: conflict-free)
-
-DEVI int corner_of(const int *nvalid, int b, int N) { return min(max(nvalid_of(nvalid, b, N), 0), N); }
 
 // pi_l[k] = pi(k) if it is a column of the corner, else -1, for k < n; returns 1 if this thread saw an entry that is not
 DEVI int stage_assign(int *pi_l, const int *pi, int n, int tid) {

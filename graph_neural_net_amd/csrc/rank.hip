@@ -3,22 +3,17 @@
 //   fgnn_eval_ranks : ONE pass over the scores: per valid row the rank of its target column (1 = the arg-max of eval_pairs_kernel).
 //   fgnn_rank_fold  : per-pair sums of those rows and the add into the epoch record(s), by one workgroup in a fixed order.
 // Both are plain launches on the caller's stream: capturable, no allocation, no copy, no synchronisation.
-#include "fgnn_common.h"
+#include "fgnn_rows.h"
 
 namespace {
 
 constexpr int RANK_THREADS = 256;
 
-DEVI int clamp_nv(const int *nvalid, int b, int N) {
-    const int n = nvalid ? nvalid[b] : N;
-    return n < 0 ? 0 : (n > N ? N : n);
-}
-
-// The row grouping of eval_pairs_kernel: W lanes per row (64: one wave per row; 16: four rows per wave, for rows of at most 16
-// columns); lane `sub` of a row's group counts among the columns sub, sub + W, ... those that BEAT the target column t:
+// The row grouping of eval_pairs_kernel (fgnn_rows.h); lane `sub` of a row's group counts among the columns sub, sub + W, ...
+// those that BEAT the target column t:
 //   s_j is NaN and s_t is not;  s_j > s_t;  j < t and (s_j == s_t or both are NaN)
-// -- the order of that kernel's arg-max (first maximum on ties, NaN above every number, the first NaN wins, -0.0 == +0.0), so
-// rank == 1 exactly when its row_hit is 1.  Column t itself beats nothing (s_t == s_t needs j < t).  The counts are integers: the
+// -- the order of row_argmax (first maximum on ties, NaN above every number, the first NaN wins, -0.0 == +0.0), so
+// rank == 1 exactly when that kernel's row_hit is 1.  Column t itself beats nothing (s_t == s_t needs j < t).  The counts are integers: the
 // butterfly's order is free and the result exact.
 template <int W>
 __global__ __launch_bounds__(RANK_THREADS) void eval_ranks_kernel(const float *scores, long long bstride, int ld, const int *nvalid,
@@ -53,7 +48,7 @@ struct RankKs {
     int k[FGNN_RANK_MAX_K];          // thresholds past nk are 0: no rank >= 1 lies below them
 };
 
-// The discipline of eval_fold_kernel / eval_fold_bins_kernel.  One workgroup of four waves.  Wave w takes the pairs 4 c + w of
+// The discipline of eval_fold_kernel.  One workgroup of four waves.  Wave w takes the pairs 4 c + w of
 // chunk c: lane l adds the rows l, l + 64, ... of the pair in ascending order (1.0 / rank in fp64), the wave meets by a butterfly;
 // thread r < K then owns record r and walks the chunk's pairs below `live` in pair order, one pair at a time, taking those of its
 // bin (bin == NULL: every pair is record 0's).  Every addition has its place fixed by (B, N, live) and the record it started from.
@@ -148,16 +143,10 @@ extern "C" int fgnn_eval_ranks(const float *scores, long long bstride, int ld, c
                                int *rank, void *stream) {
     FGNN_CHECK(scores && rank && B > 0 && N > 0, "fgnn_eval_ranks: bad arguments");
     FGNN_CHECK(ld >= N && bstride >= (long long)N * ld, "fgnn_eval_ranks: score strides smaller than the matrices");
-    const long long rows = (long long)B * N;
-    const int per = N <= 16 ? RANK_THREADS / 16 : RANK_THREADS / WAVE;
-    const long long wgs = (rows + per - 1) / per;
-    FGNN_CHECK(wgs <= 0x7fffffffll, "fgnn_eval_ranks: %lld rows are more than one launch takes", rows);
-    if (N <= 16)
-        hipLaunchKernelGGL(eval_ranks_kernel<16>, dim3((unsigned)wgs), dim3(RANK_THREADS), 0, (hipStream_t)stream, scores, bstride, ld,
-                           nvalid, labels, B, N, rank);
-    else
-        hipLaunchKernelGGL(eval_ranks_kernel<WAVE>, dim3((unsigned)wgs), dim3(RANK_THREADS), 0, (hipStream_t)stream, scores, bstride, ld,
-                           nvalid, labels, B, N, rank);
+    const unsigned wgs = row_group_wgs(B, N, RANK_THREADS);
+    FGNN_CHECK(wgs, "fgnn_eval_ranks: %lld rows are more than one launch takes", (long long)B * N);
+    hipLaunchKernelGGL(row_group_width(N) == 16 ? eval_ranks_kernel<16> : eval_ranks_kernel<WAVE>, dim3(wgs), dim3(RANK_THREADS), 0,
+                       (hipStream_t)stream, scores, bstride, ld, nvalid, labels, B, N, rank);
     FGNN_LAUNCH_CHECK();
     return 0;
 }

@@ -1,7 +1,7 @@
 // Training-step helpers next to the hot path: fused Adam over the flat parameter
 // buffer (models/trainers.py:92-104 uses torch.optim.Adam, amsgrad=False) and the argmax accuracy
 // metric (toolbox/metrics.py:119-141) on the device.
-#include "fgnn_common.h"
+#include "fgnn_rows.h"
 
 namespace {
 
@@ -63,36 +63,15 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float *p, const float *g,
 }
 
 // one workgroup per pair: rows i < nv with argmax_j scores[i][j] (first maximum) == i.
-// np.argmax order: NaN is the largest value (the first NaN wins), and a row of -inf still has its first column as
-// arg-max.  A lane without columns holds (-inf, INT_MAX), which loses every comparison with a real entry.
+// np.argmax order (row_argmax, fgnn_rows.h); nv is read as it is, not clamped to the corner.
 __global__ __launch_bounds__(256) void accuracy_max_kernel(const float *scores, const int *nvalid, int N, int *correct) {
     __shared__ int red[4];
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nv = nvalid_of(nvalid, b, N);
     const float *S = scores + (long long)b * N * N;
     int cnt = 0;
-    for (int i = wave; i < nv; i += 4) {
-        float best = -INFINITY;
-        int bj = 0x7fffffff;
-        for (int j = lane; j < nv; j += WAVE) {          // ascending j: an equal later value never replaces
-            const float v = S[(long long)i * N + j];
-            if (bj == 0x7fffffff || (best == best && (v > best || v != v))) {
-                best = v;
-                bj = j;
-            }
-        }
-        // wave arg-max with ties resolved towards the smaller index (np.argmax)
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ob = __shfl_xor(best, o);
-            const int oj = __shfl_xor(bj, o);
-            const bool onan = ob != ob, bnan = best != best;
-            if (onan ? (!bnan || oj < bj) : (!bnan && (ob > best || (ob == best && oj < bj)))) {
-                best = ob;
-                bj = oj;
-            }
-        }
-        if (bj == i) ++cnt;
-    }
+    for (int i = wave; i < nv; i += 4)
+        if (row_argmax<WAVE>(S + (long long)i * N, nv, lane).bj == i) ++cnt;
     if (lane == 0) red[wave] = cnt;
     __syncthreads();
     if (threadIdx.x == 0) correct[b] = red[0] + red[1] + red[2] + red[3];

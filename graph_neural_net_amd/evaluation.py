@@ -7,12 +7,14 @@ fgnn_count_matches when there are labels; fgnn_eval_fold) and adds them to an ``
 have a fixed order.  Nothing is read back until ``EvalMeter.result()``.  There is no CPU path (``_lib``).
 
 ``BinnedEvalMeter`` is K such records side by side and ``evaluate_scores(..., bins=)`` adds every pair to the record of its bin
-(fgnn_eval_fold_bins in place of the fourth launch): the accuracy of a model across K noise levels from one pass
+(fgnn_eval_fold_bins, the same kernel, as the fourth launch): the accuracy of a model across K noise levels from one pass
 (``FgnnTrainer.noise_curve``), each record with the bits ``fgnn_eval_fold`` gives for its pairs alone.
 
 ``rank_scores`` gives the rank of every row's true match and the Hits@k / reciprocal-rank sums with two launches (csrc/rank.hip:
 fgnn_eval_ranks, fgnn_rank_fold) into a ``RankMeter`` or, with ``bins=``, a ``BinnedRankMeter``; ``evaluate_scores(...,
 rank_meter=)`` issues them after its own four, on the same scores, labels, ``live`` and bins.
+
+The four meters are one thing -- records of one ctypes struct in one device buffer (``_Records``) -- with two record types.
 """
 import ctypes
 
@@ -24,28 +26,136 @@ from .masked import MaskedTensor
 from .metrics import labels_tensor
 
 
-class EvalMeter:
-    """The device record of an evaluation epoch (fgnn_eval_record, include/fgnn_hip.h).  `ce_sum` (fp64), `nodes`, `correct_lsap`,
-    `correct_max`, `pairs`, `steps` (int64) are 0-dim views of the record; `loss`, `acc`, `acc_max` are 0-dim fp64 device tensors
-    formed from them on the device.  `result()` is the only host synchronisation."""
+def pack_records(buf, K, words):
+    """The bytes of K records of `words` 8-byte words each (a uint8 tensor on any device) -> the (K, words) fp64 tensor of their
+    all-reduce: word 0, an fp64 sum, as it is, the int64 counts converted (exact below 2^53).  A pure function of tensors."""
+    counts = buf.view(torch.int64).view(K, words)[:, 1:]
+    return torch.cat([buf.view(torch.float64).view(K, words)[:, :1], counts.to(torch.float64)], dim=1).contiguous()
 
-    FIELDS = ('ce_sum', 'nodes', 'correct_lsap', 'correct_max', 'pairs', 'steps')
 
-    def __init__(self, device, buf=None):
-        """buf: the record's bytes when they belong to a larger buffer (a record of a BinnedEvalMeter)"""
+def unpack_records_(buf, K, t):
+    """The inverse of pack_records: writes the (K, words) fp64 tensor t into the records' bytes, in place."""
+    words = t.shape[1]
+    buf.view(torch.float64).view(K, words)[:, :1].copy_(t[:, :1])
+    buf.view(torch.int64).view(K, words)[:, 1:].copy_(t[:, 1:].round().to(torch.int64))
+    return buf
+
+
+def _read(*meters):
+    """ONE device-to-host copy of several meters' bytes -> per meter the ctypes array of its records"""
+    bufs = [m.buf for m in meters]
+    raw = (bufs[0] if len(bufs) == 1 else torch.cat(bufs)).cpu().numpy().tobytes()
+    out, at = [], 0
+    for m in meters:
+        n = m.buf.numel()
+        out.append((m.RECORD * (n // ctypes.sizeof(m.RECORD))).from_buffer_copy(raw[at:at + n]))
+        at += n
+    return out
+
+
+class _Records:
+    """What the four meters share: records of one ctypes struct (RECORD: word 0 an fp64 sum, every other word an int64 count) in one
+    device buffer `buf`, read with one device-to-host copy and summed over the ranks with one all-reduce.  A plain meter is one
+    record, its FIELDS 0-dim views of `buf`; a binned meter (_BinnedRecords) is K of them side by side.  A record type adds
+    `_dict` (a ctypes record -> a dict of Python numbers) and `_result` (that dict -> the epoch's figures)."""
+    RECORD, FIELDS, NOUN = None, (), 'record lives'
+
+    def _open(self, device, K=1, buf=None):
+        """The device refusal, then K zeroed records -- or `buf`, the bytes of one record of a binned meter.  -> the device"""
         device = torch.device(device)
         if device.type != 'cuda':
-            raise RuntimeError('EvalMeter: device %s; the epoch record lives on the GPU (there is no CPU path)' % (device,))
-        R = _lib.EvalRecord
-        self.buf = torch.zeros(ctypes.sizeof(R), dtype=torch.uint8, device=device) if buf is None else buf
-        self.ce_sum = self.buf[R.ce_sum.offset:R.ce_sum.offset + 8].view(torch.float64).reshape(())
-        for name in self.FIELDS[1:]:
-            off = getattr(R, name).offset
-            setattr(self, name, self.buf[off:off + 8].view(torch.int64).reshape(()))
+            raise RuntimeError('%s: device %s; the epoch %s on the GPU (there is no CPU path)' % (type(self).__name__, device, self.NOUN))
+        self.buf = torch.zeros(K * ctypes.sizeof(self.RECORD), dtype=torch.uint8, device=device) if buf is None else buf
+        for j, name in enumerate(self.FIELDS):              # (a binned meter has none: its records' fields are its meters')
+            off = getattr(self.RECORD, name).offset
+            setattr(self, name, self.buf[off:off + 8].view(torch.float64 if j == 0 else torch.int64).reshape(()))
+        return device
 
     def reset(self):
         self.buf.zero_()
         return self
+
+    def record(self):
+        """The record as a dict of Python numbers (one device-to-host copy)."""
+        return self._dict(_read(self)[0][0])
+
+    def result(self):
+        """The figures of the epoch (one device-to-host copy: the one synchronisation)."""
+        return self._result(self.record())
+
+    def allreduce_(self):
+        """Sum the records over the ranks: one all-reduce of one fp64 value per 8-byte word (the counts are exact below 2^53)."""
+        words = ctypes.sizeof(self.RECORD) // 8
+        K = self.buf.numel() // (8 * words)
+        t = pack_records(self.buf, K, words)
+        dp.allreduce_sum_(t)
+        unpack_records_(self.buf, K, t)
+        return self
+
+
+class _BinnedRecords(_Records):
+    """K records in one device buffer, one per bin (the noise levels of FgnnTrainer.noise_curve): `meter[k]` is a plain meter of
+    class PLAIN on record k's bytes.  values: K labels of the bins, carried as 'noise' in the dicts of `record()` / `result()`."""
+    PLAIN, FIELDS, NOUN = None, (), 'records live'
+
+    @classmethod
+    def _check_bins(cls, K, values):
+        K = int(K)
+        if not 1 <= K <= _lib.FGNN_MAX_LEVELS:
+            raise ValueError('%s: between 1 and %d records, got %d' % (cls.__name__, _lib.FGNN_MAX_LEVELS, K))
+        if values is not None and len(values) != K:
+            raise ValueError('%s: %d values for %d records' % (cls.__name__, len(values), K))
+        return K
+
+    def _open_bins(self, device, K, values, **own):
+        device = self._open(device, K)
+        size = ctypes.sizeof(self.RECORD)
+        self.K, self.values = K, None if values is None else tuple(values)
+        self.meters = [self.PLAIN(device, buf=self.buf[k * size:(k + 1) * size], **own) for k in range(K)]
+
+    def __len__(self):
+        return self.K
+
+    def __getitem__(self, k):
+        return self.meters[k]
+
+    def record(self):
+        """The K records as dicts of Python numbers, with 'noise' when values were given (one device-to-host copy)."""
+        out = [m._dict(r) for m, r in zip(self.meters, _read(self)[0])]
+        for rec, v in zip(out, self.values or ()):
+            rec['noise'] = v
+        return out
+
+    def result(self):
+        """The figures of every record, with 'noise' when values were given (one device-to-host copy: the one synchronisation)."""
+        out = [m._result(rec) for m, rec in zip(self.meters, self.record())]
+        for res, v in zip(out, self.values or ()):
+            res['noise'] = v
+        return out
+
+
+def record_result(rec):
+    """The reference's figures from a record: loss = ce_sum / nodes (toolbox/losses.py:27-34), acc = matches / nodes
+    (toolbox/metrics.py:107-114).  An empty record gives NaN, the 0 / 0 of the reference."""
+    nodes = rec['nodes']
+    div = (lambda a: a / nodes) if nodes else (lambda a: float('nan'))
+    return {'loss': div(rec['ce_sum']), 'acc': div(rec['correct_lsap']), 'acc_max': div(rec['correct_max']),
+            'nodes': nodes, 'pairs': rec['pairs']}
+
+
+class EvalMeter(_Records):
+    """The device record of an evaluation epoch (fgnn_eval_record, include/fgnn_hip.h).  `ce_sum` (fp64), `nodes`, `correct_lsap`,
+    `correct_max`, `pairs`, `steps` (int64) are 0-dim views of the record; `loss`, `acc`, `acc_max` are 0-dim fp64 device tensors
+    formed from them on the device.  `result()`, {'loss', 'acc', 'acc_max', 'nodes', 'pairs'}, is the only host synchronisation."""
+    RECORD, FIELDS = _lib.EvalRecord, ('ce_sum', 'nodes', 'correct_lsap', 'correct_max', 'pairs', 'steps')
+    _result = staticmethod(record_result)
+
+    def __init__(self, device, buf=None):
+        """buf: the record's bytes when they belong to a larger buffer (a record of a BinnedEvalMeter)"""
+        self._open(device, buf=buf)
+
+    def _dict(self, rec):
+        return {name: getattr(rec, name) for name in self.FIELDS}
 
     @property
     def loss(self):
@@ -60,204 +170,14 @@ class EvalMeter:
     def acc_max(self):
         return self.correct_max.to(torch.float64) / self.nodes.to(torch.float64)
 
-    def record(self):
-        """The record as a dict of Python numbers (one device-to-host copy)."""
-        raw = self.buf.cpu().numpy().tobytes()
-        rec = _lib.EvalRecord.from_buffer_copy(raw)
-        return {name: getattr(rec, name) for name in self.FIELDS}
 
-    def result(self):
-        """{'loss', 'acc', 'acc_max', 'nodes', 'pairs'} of the epoch (one device-to-host copy: the one synchronisation)."""
-        return record_result(self.record())
-
-    def allreduce_(self):
-        """Sum the record over the ranks: one all-reduce of 6 fp64 values (the counts are exact below 2^53)."""
-        t = torch.stack([self.ce_sum] + [getattr(self, n).to(torch.float64) for n in self.FIELDS[1:]])
-        dp.allreduce_sum_(t)
-        self.ce_sum.copy_(t[0])
-        for k, name in enumerate(self.FIELDS[1:], 1):
-            getattr(self, name).copy_(t[k].round().to(torch.int64))
-        return self
-
-
-class BinnedEvalMeter:
-    """K epoch records in one device buffer, one per bin (the noise levels of FgnnTrainer.noise_curve): `meter[k]` is an EvalMeter
-    on record k's bytes (`loss`, `acc`, `acc_max` as device tensors, `record()`, `result()`).  values: K labels of the bins, carried
-    as 'noise' in the dicts of `record()` / `result()`."""
+class BinnedEvalMeter(_BinnedRecords):
+    """K epoch records, one per bin: `meter[k]` is an EvalMeter (`loss`, `acc`, `acc_max` as device tensors, `record()`,
+    `result()`); see _BinnedRecords."""
+    PLAIN, RECORD = EvalMeter, _lib.EvalRecord
 
     def __init__(self, device, K, values=None):
-        K = int(K)
-        if not 1 <= K <= _lib.FGNN_MAX_LEVELS:
-            raise ValueError('BinnedEvalMeter: between 1 and %d records, got %d' % (_lib.FGNN_MAX_LEVELS, K))
-        if values is not None and len(values) != K:
-            raise ValueError('BinnedEvalMeter: %d values for %d records' % (len(values), K))
-        device = torch.device(device)
-        if device.type != 'cuda':
-            raise RuntimeError('BinnedEvalMeter: device %s; the epoch records live on the GPU (there is no CPU path)' % (device,))
-        size = ctypes.sizeof(_lib.EvalRecord)
-        self.K, self.values = K, None if values is None else tuple(values)
-        self.buf = torch.zeros(K * size, dtype=torch.uint8, device=device)
-        self.meters = [EvalMeter(device, buf=self.buf[k * size:(k + 1) * size]) for k in range(K)]
-
-    def __len__(self):
-        return self.K
-
-    def __getitem__(self, k):
-        return self.meters[k]
-
-    def reset(self):
-        self.buf.zero_()
-        return self
-
-    def record(self):
-        """The K records as dicts of Python numbers, with 'noise' when values were given (one device-to-host copy)."""
-        raw = self.buf.cpu().numpy().tobytes()
-        recs = (_lib.EvalRecord * self.K).from_buffer_copy(raw)
-        out = [{name: getattr(r, name) for name in EvalMeter.FIELDS} for r in recs]
-        if self.values is not None:
-            for r, v in zip(out, self.values):
-                r['noise'] = v
-        return out
-
-    def result(self):
-        """record_result of every record, with 'noise' when values were given (one device-to-host copy: the one synchronisation)."""
-        out = []
-        for rec in self.record():
-            res = record_result(rec)
-            if 'noise' in rec:
-                res['noise'] = rec['noise']
-            out.append(res)
-        return out
-
-    def allreduce_(self):
-        """Sum the records over the ranks: one all-reduce of K x 6 fp64 values (the counts are exact below 2^53)."""
-        words = self.buf.view(torch.int64).view(self.K, len(EvalMeter.FIELDS))
-        ce = self.buf.view(torch.float64).view(self.K, len(EvalMeter.FIELDS))[:, :1]
-        t = torch.cat([ce, words[:, 1:].to(torch.float64)], dim=1).contiguous()
-        dp.allreduce_sum_(t)
-        ce.copy_(t[:, :1])
-        words[:, 1:].copy_(t[:, 1:].round().to(torch.int64))
-        return self
-
-
-def record_result(rec):
-    """The reference's figures from a record: loss = ce_sum / nodes (toolbox/losses.py:27-34), acc = matches / nodes
-    (toolbox/metrics.py:107-114).  An empty record gives NaN, the 0 / 0 of the reference."""
-    nodes = rec['nodes']
-    div = (lambda a: a / nodes) if nodes else (lambda a: float('nan'))
-    return {'loss': div(rec['ce_sum']), 'acc': div(rec['correct_lsap']), 'acc_max': div(rec['correct_max']),
-            'nodes': nodes, 'pairs': rec['pairs']}
-
-
-class RankMeter:
-    """The device record of the rank metrics of an evaluation epoch (fgnn_rank_record, include/fgnn_hip.h) for the thresholds `ks`
-    (1 to FGNN_RANK_MAX_K positive, strictly increasing integers).  `rr_sum` (fp64), `rank_sum`, `targets`, `nodes`, `pairs`, `steps`
-    (int64) are 0-dim views of the record, `hits[q]` the view of the count for ks[q]; `mrr`, `mean_rank` and `hits_at(k)` are 0-dim
-    fp64 device tensors formed from them on the device.  `result()` is the only host synchronisation."""
-
-    FIELDS = ('rr_sum', 'rank_sum', 'targets', 'nodes', 'pairs', 'steps')
-
-    def __init__(self, device, ks=(1, 5, 10), buf=None):
-        """buf: the record's bytes when they belong to a larger buffer (a record of a BinnedRankMeter)"""
-        self.ks = check_ks(ks)
-        device = torch.device(device)
-        if device.type != 'cuda':
-            raise RuntimeError('RankMeter: device %s; the epoch record lives on the GPU (there is no CPU path)' % (device,))
-        R = _lib.RankRecord
-        self.buf = torch.zeros(ctypes.sizeof(R), dtype=torch.uint8, device=device) if buf is None else buf
-        self.rr_sum = self.buf[R.rr_sum.offset:R.rr_sum.offset + 8].view(torch.float64).reshape(())
-        for name in self.FIELDS[1:]:
-            off = getattr(R, name).offset
-            setattr(self, name, self.buf[off:off + 8].view(torch.int64).reshape(()))
-        self.hits = [self.buf[R.hits.offset + 8 * q:R.hits.offset + 8 * q + 8].view(torch.int64).reshape(()) for q in range(len(self.ks))]
-
-    def reset(self):
-        self.buf.zero_()
-        return self
-
-    @property
-    def mrr(self):
-        """rr_sum / targets: the mean reciprocal rank of everything folded so far (NaN before the first target)"""
-        return self.rr_sum / self.targets.to(torch.float64)
-
-    @property
-    def mean_rank(self):
-        return self.rank_sum.to(torch.float64) / self.targets.to(torch.float64)
-
-    def hits_at(self, k):
-        return self.hits[self.ks.index(int(k))].to(torch.float64) / self.targets.to(torch.float64)
-
-    def record(self):
-        """The record as a dict of Python numbers, 'hits' as {k: count} (one device-to-host copy)."""
-        return rank_record_dict(_lib.RankRecord.from_buffer_copy(self.buf.cpu().numpy().tobytes()), self.ks)
-
-    def result(self):
-        """{'hits@k' for every k, 'mrr', 'mean_rank', 'targets', 'nodes', 'pairs'} of the epoch (one device-to-host copy: the one
-        synchronisation)."""
-        return rank_result(self.record())
-
-    def allreduce_(self):
-        """Sum the record over the ranks: one all-reduce of 14 fp64 values (the counts are exact below 2^53)."""
-        t = pack_rank_records(self.buf, 1)
-        dp.allreduce_sum_(t)
-        unpack_rank_records_(self.buf, 1, t)
-        return self
-
-
-class BinnedRankMeter:
-    """K rank records in one device buffer, one per bin (the noise levels of FgnnTrainer.noise_curve): `meter[k]` is a RankMeter on
-    record k's bytes.  values: K labels of the bins, carried as 'noise' in the dicts of `record()` / `result()`."""
-
-    def __init__(self, device, K, ks=(1, 5, 10), values=None):
-        K = int(K)
-        if not 1 <= K <= _lib.FGNN_MAX_LEVELS:
-            raise ValueError('BinnedRankMeter: between 1 and %d records, got %d' % (_lib.FGNN_MAX_LEVELS, K))
-        if values is not None and len(values) != K:
-            raise ValueError('BinnedRankMeter: %d values for %d records' % (len(values), K))
-        self.ks = check_ks(ks)
-        device = torch.device(device)
-        if device.type != 'cuda':
-            raise RuntimeError('BinnedRankMeter: device %s; the epoch records live on the GPU (there is no CPU path)' % (device,))
-        size = ctypes.sizeof(_lib.RankRecord)
-        self.K, self.values = K, None if values is None else tuple(values)
-        self.buf = torch.zeros(K * size, dtype=torch.uint8, device=device)
-        self.meters = [RankMeter(device, ks=self.ks, buf=self.buf[k * size:(k + 1) * size]) for k in range(K)]
-
-    def __len__(self):
-        return self.K
-
-    def __getitem__(self, k):
-        return self.meters[k]
-
-    def reset(self):
-        self.buf.zero_()
-        return self
-
-    def record(self):
-        """The K records as dicts of Python numbers, with 'noise' when values were given (one device-to-host copy)."""
-        recs = (_lib.RankRecord * self.K).from_buffer_copy(self.buf.cpu().numpy().tobytes())
-        out = [rank_record_dict(r, self.ks) for r in recs]
-        if self.values is not None:
-            for r, v in zip(out, self.values):
-                r['noise'] = v
-        return out
-
-    def result(self):
-        """rank_result of every record, with 'noise' when values were given (one device-to-host copy: the one synchronisation)."""
-        out = []
-        for rec in self.record():
-            res = rank_result(rec)
-            if 'noise' in rec:
-                res['noise'] = rec['noise']
-            out.append(res)
-        return out
-
-    def allreduce_(self):
-        """Sum the records over the ranks: one all-reduce of K x 14 fp64 values (the counts are exact below 2^53)."""
-        t = pack_rank_records(self.buf, self.K)
-        dp.allreduce_sum_(t)
-        unpack_rank_records_(self.buf, self.K, t)
-        return self
+        self._open_bins(device, self._check_bins(K, values), values)
 
 
 def check_ks(ks):
@@ -274,24 +194,6 @@ def check_ks(ks):
     if ks[0] < 1 or any(b <= a for a, b in zip(ks, ks[1:])) or ks[-1] > 0x7fffffff:
         raise ValueError('ks must be positive and strictly increasing, got %r' % (ks,))
     return ks
-
-
-RANK_WORDS = ctypes.sizeof(_lib.RankRecord) // 8
-
-
-def pack_rank_records(buf, K):
-    """The bytes of K rank records (a uint8 tensor on any device) -> the (K, 14) fp64 tensor of their all-reduce: rr_sum as it is,
-    the int64 counts converted (exact below 2^53).  A pure function of tensors."""
-    words = buf.view(torch.int64).view(K, RANK_WORDS)
-    rr = buf.view(torch.float64).view(K, RANK_WORDS)[:, :1]
-    return torch.cat([rr, words[:, 1:].to(torch.float64)], dim=1).contiguous()
-
-
-def unpack_rank_records_(buf, K, t):
-    """The inverse of pack_rank_records: writes the (K, 14) fp64 tensor t into the records' bytes, in place."""
-    buf.view(torch.float64).view(K, RANK_WORDS)[:, :1].copy_(t[:, :1])
-    buf.view(torch.int64).view(K, RANK_WORDS)[:, 1:].copy_(t[:, 1:].round().to(torch.int64))
-    return buf
 
 
 def rank_record_dict(rec, ks):
@@ -311,13 +213,60 @@ def rank_result(rec):
     return out
 
 
-def read_records(meter, rank_meter):
-    """(meter.record(), rank_meter.record()) of an EvalMeter and a RankMeter from ONE device-to-host copy."""
-    raw = torch.cat([meter.buf, rank_meter.buf]).cpu().numpy().tobytes()
-    size = ctypes.sizeof(_lib.EvalRecord)
-    rec = _lib.EvalRecord.from_buffer_copy(raw[:size])
-    return ({name: getattr(rec, name) for name in EvalMeter.FIELDS},
-            rank_record_dict(_lib.RankRecord.from_buffer_copy(raw[size:]), rank_meter.ks))
+class RankMeter(_Records):
+    """The device record of the rank metrics of an evaluation epoch (fgnn_rank_record, include/fgnn_hip.h) for the thresholds `ks`
+    (1 to FGNN_RANK_MAX_K positive, strictly increasing integers).  `rr_sum` (fp64), `rank_sum`, `targets`, `nodes`, `pairs`, `steps`
+    (int64) are 0-dim views of the record, `hits[q]` the view of the count for ks[q]; `mrr`, `mean_rank` and `hits_at(k)` are 0-dim
+    fp64 device tensors formed from them on the device.  `record()` has 'hits' as {k: count}; `result()`, {'hits@k' for every k,
+    'mrr', 'mean_rank', 'targets', 'nodes', 'pairs'}, is the only host synchronisation."""
+    RECORD, FIELDS = _lib.RankRecord, ('rr_sum', 'rank_sum', 'targets', 'nodes', 'pairs', 'steps')
+    _result = staticmethod(rank_result)
+
+    def __init__(self, device, ks=(1, 5, 10), buf=None):
+        """buf: the record's bytes when they belong to a larger buffer (a record of a BinnedRankMeter)"""
+        self.ks = check_ks(ks)
+        self._open(device, buf=buf)
+        off = _lib.RankRecord.hits.offset
+        self.hits = [self.buf[off + 8 * q:off + 8 * q + 8].view(torch.int64).reshape(()) for q in range(len(self.ks))]
+
+    def _dict(self, rec):
+        return rank_record_dict(rec, self.ks)
+
+    @property
+    def mrr(self):
+        """rr_sum / targets: the mean reciprocal rank of everything folded so far (NaN before the first target)"""
+        return self.rr_sum / self.targets.to(torch.float64)
+
+    @property
+    def mean_rank(self):
+        return self.rank_sum.to(torch.float64) / self.targets.to(torch.float64)
+
+    def hits_at(self, k):
+        return self.hits[self.ks.index(int(k))].to(torch.float64) / self.targets.to(torch.float64)
+
+
+class BinnedRankMeter(_BinnedRecords):
+    """K rank records, one per bin: `meter[k]` is a RankMeter of the same `ks`; see _BinnedRecords."""
+    PLAIN, RECORD = RankMeter, _lib.RankRecord
+
+    def __init__(self, device, K, ks=(1, 5, 10), values=None):
+        K = self._check_bins(K, values)
+        self.ks = check_ks(ks)
+        self._open_bins(device, K, values, ks=self.ks)
+
+
+RANK_WORDS = ctypes.sizeof(_lib.RankRecord) // 8
+unpack_rank_records_ = unpack_records_
+
+
+def pack_rank_records(buf, K):
+    """pack_records of K rank records -> (K, 14) fp64"""
+    return pack_records(buf, K, RANK_WORDS)
+
+
+def read_records(*meters):
+    """(meter.record(), rank_meter.record(), ...) of plain meters -- an EvalMeter and a RankMeter -- from ONE device-to-host copy."""
+    return tuple(m._dict(recs[0]) for m, recs in zip(meters, _read(*meters)))
 
 
 def _score_args(who, scores, nvalid, labels, live, bins):
@@ -353,11 +302,12 @@ def _score_args(who, scores, nvalid, labels, live, bins):
     return scores.detach().to(torch.float32).contiguous(), nvalid, labels, bins, B, N, live
 
 
-def _check_rank_meter(who, meter, bins, dev, ks=None):
-    if isinstance(meter, BinnedRankMeter) != (bins is not None):
-        raise ValueError('%s: bins= and a BinnedRankMeter as rank meter go together' % who)
-    if not isinstance(meter, (RankMeter, BinnedRankMeter)) or meter.buf.device != dev:
-        raise ValueError('%s: the rank meter must be a RankMeter (with bins=: a BinnedRankMeter) on %s' % (who, dev))
+def _check_meter(who, what, binned, meter, bins, dev, ks=None):
+    """meter: a `binned` meter with bins=, else one of its PLAIN class, on dev (what: 'meter' or 'rank meter' in the messages)"""
+    if isinstance(meter, binned) != (bins is not None):
+        raise ValueError('%s: bins= and a %s as %s go together' % (who, binned.__name__, what))
+    if not isinstance(meter, (binned.PLAIN, binned)) or meter.buf.device != dev:
+        raise ValueError('%s: the %s must be of class %s (with bins=: %s) on %s' % (who, what, binned.PLAIN.__name__, binned.__name__, dev))
     if ks is not None and check_ks(ks) != meter.ks:
         raise ValueError('%s: ks = %r differ from the meter\'s %r' % (who, tuple(ks), meter.ks))
 
@@ -397,7 +347,7 @@ def rank_scores(scores, nvalid=None, labels=None, meter=None, live=None, bins=No
     if meter is None:
         meter = RankMeter(s.device, ks=(1, 5, 10) if ks is None else ks)
     else:
-        _check_rank_meter('rank_scores', meter, bins, s.device, ks)
+        _check_meter('rank_scores', 'rank meter', BinnedRankMeter, meter, bins, s.device, ks)
     with torch.cuda.device(s.device):
         return _rank_launches(s, nvalid, labels, bins, B, N, live, meter)
 
@@ -424,15 +374,12 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
         raise ValueError('evaluate_scores: bins= and a BinnedEvalMeter as meter go together')
     s, nvalid, labels, bins, B, N, live = _score_args('evaluate_scores', scores, nvalid, labels, live, bins)
     dev = s.device
-    if bins is not None:
-        if meter.buf.device != dev:
-            raise ValueError('evaluate_scores: meter must be a BinnedEvalMeter on %s' % (dev,))
-    elif meter is None:
+    if meter is None:
         meter = EvalMeter(dev)
-    elif not isinstance(meter, EvalMeter) or meter.buf.device != dev:
-        raise ValueError('evaluate_scores: meter must be an EvalMeter on %s' % (dev,))
+    else:
+        _check_meter('evaluate_scores', 'meter', BinnedEvalMeter, meter, bins, dev)
     if rank_meter is not None:
-        _check_rank_meter('evaluate_scores', rank_meter, bins, dev)
+        _check_meter('evaluate_scores', 'rank meter', BinnedRankMeter, rank_meter, bins, dev)
     with torch.cuda.device(dev):
         i32 = dict(dtype=torch.int32, device=dev)
         cost = torch.empty(B, N, N, dtype=torch.float32, device=dev)
@@ -443,19 +390,19 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
         correct = torch.zeros(B, **i32)
         assign = None
         st = _lib.stream_ptr()
-        _lib.call('fgnn_eval_pairs_labels' if loss_on_labels and labels is not None else 'fgnn_eval_pairs', _lib.ptr(s), _lib.ptr(nvalid), _lib.ptr(labels), B, N, _lib.ptr(cost), N * N, N,
-                  _lib.ptr(row_ce), _lib.ptr(row_hit), st)
+        _lib.call('fgnn_eval_pairs_labels' if loss_on_labels and labels is not None else 'fgnn_eval_pairs', _lib.ptr(s), _lib.ptr(nvalid),
+                  _lib.ptr(labels), B, N, _lib.ptr(cost), N * N, N, _lib.ptr(row_ce), _lib.ptr(row_hit), st)
         if hungarian:
             assign = torch.empty(B, N, **i32)
             _lib.call('fgnn_lsap_accuracy', _lib.ptr(cost), N * N, N, _lib.ptr(nvalid), B, N, _lib.ptr(correct), _lib.ptr(assign), st)
             if labels is not None:
                 _lib.call('fgnn_count_matches', _lib.ptr(assign), _lib.ptr(labels), _lib.ptr(nvalid), B, N, _lib.ptr(correct), st)
+        rows = (_lib.ptr(row_ce), _lib.ptr(row_hit), _lib.ptr(correct) if hungarian else None, _lib.ptr(nvalid), B, N, live)
+        sums = (_lib.ptr(pair_ce), _lib.ptr(pair_max), _lib.ptr(meter.buf), st)
         if bins is None:
-            _lib.call('fgnn_eval_fold', _lib.ptr(row_ce), _lib.ptr(row_hit), _lib.ptr(correct) if hungarian else None, _lib.ptr(nvalid),
-                      B, N, live, _lib.ptr(pair_ce), _lib.ptr(pair_max), _lib.ptr(meter.buf), st)
+            _lib.call('fgnn_eval_fold', *rows, *sums)
         else:
-            _lib.call('fgnn_eval_fold_bins', _lib.ptr(row_ce), _lib.ptr(row_hit), _lib.ptr(correct) if hungarian else None,
-                      _lib.ptr(nvalid), B, N, live, _lib.ptr(bins), meter.K, _lib.ptr(pair_ce), _lib.ptr(pair_max), _lib.ptr(meter.buf), st)
+            _lib.call('fgnn_eval_fold_bins', *rows, _lib.ptr(bins), meter.K, *sums)
         ranks = None if rank_meter is None else _rank_launches(s, nvalid, labels, bins, B, N, live, rank_meter)
     n = nvalid if nvalid is not None else torch.full((B,), N, **i32)
     out = {'ce': pair_ce, 'n': n, 'correct_max': pair_max, 'correct_lsap': correct, 'assign': assign, 'meter': meter}

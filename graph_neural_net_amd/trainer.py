@@ -479,18 +479,24 @@ class FgnnTrainer:
         from .metrics import labels_tensor
         return labels_tensor(labels, B, N, self.params.device)
 
+    @staticmethod
+    def _bits_shape(who, bits1, bits2):
+        """The shape check of a bit-packed pair of batches (who: the calling method, for the message) -> (B, N)"""
+        if bits1.dim() != 3 or bits1.shape != bits2.shape or bits1.dtype not in (torch.int32, torch.uint32) or not bits1.is_cuda:
+            raise RuntimeError('FgnnTrainer.%s: expected two (B, N, ceil(N/32)) int32 device tensors, got %s %s / %s %s'
+                               % (who, tuple(bits1.shape), bits1.dtype, tuple(bits2.shape), bits2.dtype))
+        B, N = bits1.shape[0], bits1.shape[1]
+        if bits1.shape[2] != (N + 31) // 32:
+            raise RuntimeError('FgnnTrainer.%s: %d words per row for N = %d (expected %d)' % (who, bits1.shape[2], N, (N + 31) // 32))
+        return B, N
+
     def train_step_bits(self, bits1, bits2, nvalid=None, labels=None, weights=None, live=None):
         """The same step with the local shard handed over as bit-packed adjacency: bits1, bits2
         (B, N, ceil(N / 32)) int32 device tensors, bit j of row i = W[i][j] (synthetic.pack_adjacency / the loader's packing); the
         tensor representation of loaders/data_generator.py:118-125 is built inside block 1's kernels, and with block1='structured'
         block 1 runs on the class tables of csrc/block1_struct.hip.  nvalid: (B,) int32 for ragged batches (padded to N).
         labels, weights, live: see train_step."""
-        if bits1.dim() != 3 or bits1.shape != bits2.shape or bits1.dtype not in (torch.int32, torch.uint32) or not bits1.is_cuda:
-            raise RuntimeError('FgnnTrainer.train_step_bits: expected two (B, N, ceil(N/32)) int32 device tensors, got %s %s / %s %s'
-                               % (tuple(bits1.shape), bits1.dtype, tuple(bits2.shape), bits2.dtype))
-        B, N = bits1.shape[0], bits1.shape[1]
-        if bits1.shape[2] != (N + 31) // 32:
-            raise RuntimeError('FgnnTrainer.train_step_bits: %d words per row for N = %d (expected %d)' % (bits1.shape[2], N, (N + 31) // 32))
+        B, N = self._bits_shape('train_step_bits', bits1, bits2)
         labels = self._labels(labels, B, N)
         weighted = self._weighted(weights, live)
         if self.capture and nvalid is None:
@@ -526,12 +532,9 @@ class FgnnTrainer:
         steps = sampler.steps_per_epoch(batch_size)
         losses = torch.empty(steps, dtype=torch.float32, device=self.params.device)
         for step in range(steps):
-            xkw = {'live': sampler.live_count(step, batch_size)} if exact_last else {}
-            if permute:
-                b1, b2, nv, lab = generator.bits(index=sampler.batch_index(epoch, step, batch_size), permute=True)
-                loss, _ = self.train_step_bits(b1, b2, nv, labels=lab, **xkw)
-            else:
-                loss, _ = self.train_step_bits(*generator.bits(index=sampler.batch_index(epoch, step, batch_size)), **xkw)
+            b1, b2, nv, *lab = generator.bits(index=sampler.batch_index(epoch, step, batch_size), permute=permute)
+            loss, _ = self.train_step_bits(b1, b2, nv, labels=lab[0] if lab else None,
+                                           live=sampler.live_count(step, batch_size) if exact_last else None)
             losses[step].copy_(loss)
         return losses
 
@@ -546,22 +549,19 @@ class FgnnTrainer:
         scores, _ = eng.forward(self.params, x, nvalid=nv, total_nodes=1.0, defer_loss=False, loss_out=self._eval_loss, bits=bits)
         return scores
 
+    def _eval_tail(self, B, N, nvalid, x=None, bits=None, **options):
+        """The stacked batch -> its scores -> evaluation.evaluate_scores with the step's options"""
+        from .evaluation import evaluate_scores
+        return evaluate_scores(self._eval_forward(B, N, nvalid, x=x, bits=bits), nvalid=nvalid, **options)
+
     def eval_step_bits(self, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False,
                        bins=None, rank_meter=None):
         """Forward-only evaluation of a batch handed over as train_step_bits takes it: the training engine's forward pass (a third of
         a step's work), then evaluation.evaluate_scores on its scores -- see there for labels, meter, live, hungarian,
         loss_on_labels, bins, rank_meter and the returned per-pair device tensors.  Nothing is read back; parameters, gradients and optimizer state keep their bits."""
-        if bits1.dim() != 3 or bits1.shape != bits2.shape or bits1.dtype not in (torch.int32, torch.uint32) or not bits1.is_cuda:
-            raise RuntimeError('FgnnTrainer.eval_step_bits: expected two (B, N, ceil(N/32)) int32 device tensors, got %s %s / %s %s'
-                               % (tuple(bits1.shape), bits1.dtype, tuple(bits2.shape), bits2.dtype))
-        B, N = bits1.shape[0], bits1.shape[1]
-        if bits1.shape[2] != (N + 31) // 32:
-            raise RuntimeError('FgnnTrainer.eval_step_bits: %d words per row for N = %d (expected %d)' % (bits1.shape[2], N, (N + 31) // 32))
-        from .evaluation import evaluate_scores
-        scores = self._eval_forward(B, N, nvalid, bits=torch.cat([bits1, bits2]).contiguous())
-        return evaluate_scores(scores, nvalid=nvalid, labels=labels, meter=meter, live=live, hungarian=hungarian,
-                               **({'loss_on_labels': True} if loss_on_labels else {}), **({} if bins is None else {'bins': bins}),
-                               **({} if rank_meter is None else {'rank_meter': rank_meter}))
+        B, N = self._bits_shape('eval_step_bits', bits1, bits2)
+        return self._eval_tail(B, N, nvalid, bits=torch.cat([bits1, bits2]).contiguous(), labels=labels, meter=meter, live=live,
+                               hungarian=hungarian, loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter)
 
     def eval_step(self, x1, x2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False, bins=None,
                   rank_meter=None):
@@ -570,11 +570,8 @@ class FgnnTrainer:
         if x1.dim() != 4 or x1.shape != x2.shape or not x1.is_cuda:
             raise RuntimeError('FgnnTrainer.eval_step: expected two (B, c0, N, N) device tensors, got %s / %s'
                                % (tuple(x1.shape), tuple(x2.shape)))
-        from .evaluation import evaluate_scores
-        scores = self._eval_forward(x1.shape[0], x1.shape[-1], nvalid, x=torch.cat([x1, x2]).contiguous())
-        return evaluate_scores(scores, nvalid=nvalid, labels=labels, meter=meter, live=live, hungarian=hungarian,
-                               **({'loss_on_labels': True} if loss_on_labels else {}), **({} if bins is None else {'bins': bins}),
-                               **({} if rank_meter is None else {'rank_meter': rank_meter}))
+        return self._eval_tail(x1.shape[0], x1.shape[-1], nvalid, x=torch.cat([x1, x2]).contiguous(), labels=labels, meter=meter, live=live,
+                               hungarian=hungarian, loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter)
 
     def evaluate(self, generator, sampler, batch_size, epoch=0, hungarian=True, meter=None, permute=False, loss_on_labels=False,
                  rank_meter=None):
@@ -595,20 +592,21 @@ class FgnnTrainer:
             raise ValueError('FgnnTrainer.evaluate: meter must be an EvalMeter or None (got %s)' % type(meter).__name__)
         if rank_meter is not None and not isinstance(rank_meter, RankMeter):
             raise ValueError('FgnnTrainer.evaluate: rank_meter must be a RankMeter or None (got %s)' % type(rank_meter).__name__)
-        for step in range(sampler.steps_per_epoch(B)):
-            live = sampler.live_count(step, B)
-            if live == 0:       # (a rank past the end of the data in the last global step)
-                continue
-            kw = {'permute': True} if permute else {}
-            b1, b2, nv, *labels = generator.bits(index=sampler.batch_index(epoch, step, B), **kw)
-            if loss_on_labels:
-                kw = {'loss_on_labels': True}
-            else:
-                kw = {}
-            if rank_meter is not None:
-                kw['rank_meter'] = rank_meter
-            self.eval_step_bits(b1, b2, nvalid=nv, labels=labels[0] if labels else None, meter=meter, live=live, hungarian=hungarian, **kw)
-        if dp.world_size() > 1:
+        def batches():
+            for step in range(sampler.steps_per_epoch(B)):
+                live = sampler.live_count(step, B)
+                if live:        # (0: a rank past the end of the data in the last global step; its index is never made)
+                    yield live, None, {'index': sampler.batch_index(epoch, step, B), 'permute': permute}
+        return self._eval_epoch(generator, batches(), meter, rank_meter, dp.world_size() > 1, hungarian, loss_on_labels)
+
+    def _eval_epoch(self, generator, batches, meter, rank_meter, reduce, hungarian, loss_on_labels):
+        """The loop of evaluate and noise_curve.  batches: per step that has a live pair (live, bins, the keyword arguments of
+        generator.bits); reduce: sum the meters over the ranks at the end.  -> meter"""
+        for live, bins, bits_kw in batches:
+            b1, b2, nv, *labels = generator.bits(**bits_kw)
+            self.eval_step_bits(b1, b2, nvalid=nv, labels=labels[0] if labels else None, meter=meter, live=live, hungarian=hungarian,
+                                loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter)
+        if reduce:
             meter.allreduce_()
             if rank_meter is not None:
                 rank_meter.allreduce_()
@@ -658,22 +656,13 @@ class FgnnTrainer:
         if rank is None:        # (this process's rank in the split of torch.distributed; any other split has to name it)
             rank = torch.distributed.get_rank() if world_size == dp.world_size() > 1 else 0
         sampler = EpochSampler(K * M, shuffle=False, rank=rank, world_size=world_size, drop_last=False, device=generator.device)
-        kw = {'permute': True} if permute else {}
-        ekw = {'loss_on_labels': True} if loss_on_labels else {}
-        if rank_meter is not None:
-            ekw['rank_meter'] = rank_meter
-        for step in range(sampler.steps_per_epoch(B)):
-            pair, level, live = self.noise_curve_batch(sampler, step, B, M)
-            if live == 0:       # (a rank past the end of the examples in the last global step)
-                continue
-            b1, b2, nv, *labels = generator.bits(index=pair, levels=levels, level=level, **kw)
-            self.eval_step_bits(b1, b2, nvalid=nv, labels=labels[0] if labels else None, meter=meter, live=live, hungarian=hungarian,
-                                bins=level, **ekw)
-        if dp.world_size() > 1 and sampler.world_size == dp.world_size():
-            meter.allreduce_()
-            if rank_meter is not None:
-                rank_meter.allreduce_()
-        return meter
+        def batches():
+            for step in range(sampler.steps_per_epoch(B)):
+                pair, level, live = self.noise_curve_batch(sampler, step, B, M)
+                if live:        # (0: a rank past the end of the examples in the last global step)
+                    yield live, level, {'index': pair, 'levels': levels, 'level': level, 'permute': permute}
+        return self._eval_epoch(generator, batches(), meter, rank_meter, dp.world_size() > 1 and sampler.world_size == dp.world_size(),
+                                hungarian, loss_on_labels)
 
     def fit(self, train_gen, train_sampler, val_gen, val_sampler, epochs, batch_size, scheduler=None, permute=False, exact_last=False,
             rank_ks=None):
@@ -693,19 +682,15 @@ class FgnnTrainer:
             from .optim import ReduceLROnPlateau
             scheduler = ReduceLROnPlateau(self.opt)
         history = []
-        xkw = {'exact_last': True} if exact_last else {}
         rank_meter = None if rank_ks is None else RankMeter(self.params.device, ks=rank_ks)
-        ekw = {} if rank_meter is None else {'meter': EvalMeter(self.params.device), 'rank_meter': rank_meter}
+        own = None if rank_meter is None else EvalMeter(self.params.device)          # (read together with the rank meter)
         for epoch in range(int(epochs)):
             if rank_meter is not None:
                 rank_meter.reset()
-                ekw['meter'].reset()
-            if permute:
-                losses = self.train_epoch(train_gen, train_sampler, epoch, batch_size, permute=True, **xkw)
-                meter = self.evaluate(val_gen, val_sampler, batch_size, epoch=epoch, permute=True, loss_on_labels=True, **ekw)
-            else:
-                losses = self.train_epoch(train_gen, train_sampler, epoch, batch_size, **xkw)
-                meter = self.evaluate(val_gen, val_sampler, batch_size, epoch=epoch, **ekw)
+                own.reset()
+            losses = self.train_epoch(train_gen, train_sampler, epoch, batch_size, permute=permute, exact_last=exact_last)
+            meter = self.evaluate(val_gen, val_sampler, batch_size, epoch=epoch, meter=own, permute=permute, loss_on_labels=permute,
+                                  rank_meter=rank_meter)
             if rank_meter is None:
                 res = meter.result()
             else:
@@ -750,12 +735,7 @@ class FgnnTrainer:
                 self._tr_calls += 1
                 if first or (self.INPUT_CHECK_EVERY and self._tr_calls % self.INPUT_CHECK_EVERY == 0):
                     self.check_input_form()
-                xkw = {} if labels is None else {'labels': labels}
-                if weights is not None:
-                    xkw['weights'] = weights
-                if live is not None:
-                    xkw['live'] = live
-                out = self.train_step_bits(w[:B], w[B:], nvalid=nv, **xkw)
+                out = self.train_step_bits(w[:B], w[B:], nvalid=nv, labels=labels, weights=weights, live=live)
                 if first and (B, N, 'bits') in self._graphs:        # from now on pack straight into the captured step's input words
                     self._tr[(B, N)] = self._graphs[(B, N, 'bits')][0]
                 return out

@@ -137,11 +137,12 @@ def test_fit_permute_trains_and_validates_on_the_labels():
         def __init__(self):
             self.opt = type('O', (), {'lr': 1e-3})()
 
-        def train_epoch(self, generator, sampler, epoch, batch_size, permute=False):
+        def train_epoch(self, generator, sampler, epoch, batch_size, permute=False, exact_last=False):
             calls.append(('train', permute))
             return None
 
-        def evaluate(self, generator, sampler, batch_size, epoch=0, hungarian=True, meter=None, permute=False, loss_on_labels=False):
+        def evaluate(self, generator, sampler, batch_size, epoch=0, hungarian=True, meter=None, permute=False, loss_on_labels=False,
+                     rank_meter=None):
             calls.append(('eval', permute, loss_on_labels))
             return Meter()
 

@@ -101,11 +101,12 @@ class _StubTrainer(FgnnTrainer):
         self.val_losses = list(val_losses)
         self.calls = []
 
-    def train_epoch(self, generator, sampler, epoch, batch_size):
+    def train_epoch(self, generator, sampler, epoch, batch_size, permute=False, exact_last=False):
         self.calls.append(('train', generator, sampler, epoch, batch_size, self.opt.lr))
         return 'losses%d' % epoch
 
-    def evaluate(self, generator, sampler, batch_size, epoch=0, hungarian=True, meter=None, permute=False):
+    def evaluate(self, generator, sampler, batch_size, epoch=0, hungarian=True, meter=None, permute=False, loss_on_labels=False,
+                 rank_meter=None):
         self.calls.append(('eval', generator, sampler, epoch, batch_size))
         return self._Meter(self.val_losses[epoch])
 

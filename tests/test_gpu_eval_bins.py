@@ -111,6 +111,50 @@ def test_one_bin_is_the_plain_fold(N):
     assert EvalMeter(DEV, buf=binned).record()['steps'] == 3
 
 
+def _start_records(k):
+    """k records that are not zero, record j = 1 the same for every k (ce_sum is not exactly representable)"""
+    recs = (_lib.EvalRecord * k)()
+    for j in range(k):
+        q = 1 if k == 1 else j
+        recs[j].ce_sum = 0.1 + q / 3.0
+        recs[j].nodes, recs[j].correct_lsap, recs[j].correct_max, recs[j].pairs, recs[j].steps = 1000 + q, 500 + q, 400 + q, 30 + q, 7 + q
+    return torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(DEV)
+
+
+@pytest.mark.parametrize('N', [1, 64, 65])          # (a lane adds the rows l, l + 64, ...)
+@pytest.mark.parametrize('nb', [1, 4, 5, 9])          # (a chunk is four pairs)
+def test_the_plain_fold_is_the_binned_fold_at_the_shape_edges(nb, N):
+    """fgnn_eval_fold, fgnn_eval_fold_bins with K = 1 and with K = 3 and every pair in bin 1 are one kernel: the same record bytes,
+    pair_ce and pair_max from a record that is not zero; live = 0 leaves every byte, and the other bins' records always stay"""
+    g = torch.Generator().manual_seed(1000 * nb + N)
+    nv = torch.randint(1, N + 1, (nb,), generator=g, dtype=torch.int32)
+    nv[0] = N
+    nv[min(1, nb - 1)] = 0          # (ragged, one pair without vertices; with one pair, that one)
+    for nvalid in ([nv] if nb > 1 else [nv, torch.tensor([N], dtype=torch.int32)]):
+        inside = torch.arange(N)[None, :] < nvalid[:, None]
+        row_ce = torch.where(inside, torch.rand(nb, N, generator=g) * 7.0, torch.full((nb, N), NAN)).to(DEV)
+        row_hit = torch.where(inside, torch.randint(0, 2, (nb, N), generator=g, dtype=torch.int32),
+                              torch.full((nb, N), SENTINEL, dtype=torch.int32)).to(DEV)
+        correct = torch.randint(0, N + 1, (nb,), generator=g, dtype=torch.int32).to(DEV)
+        nvd = nvalid.to(DEV)
+        for live in sorted({0, nb - 1, nb}):
+            plain, one, three = _start_records(1), _start_records(1), _start_records(3)
+            assert torch.equal(plain, three[REC:2 * REC])
+            p = _fold(row_ce, row_hit, correct, nvd, live, plain)
+            q = _fold_bins(row_ce, row_hit, correct, nvd, live, torch.zeros(nb, dtype=torch.int32, device=DEV), 1, one)
+            r = _fold_bins(row_ce, row_hit, correct, nvd, live, torch.ones(nb, dtype=torch.int32, device=DEV), 3, three)
+            assert torch.equal(plain, one) and torch.equal(plain, three[REC:2 * REC]), (live, nvalid.tolist())
+            assert torch.equal(three[:REC], _start_records(3)[:REC]) and torch.equal(three[2 * REC:], _start_records(3)[2 * REC:])
+            for other in (q, r):          # (NaN / the sentinel past `live` in all three: compared as bits)
+                assert torch.equal(p[0].view(torch.int64), other[0].view(torch.int64)) and torch.equal(p[1], other[1])
+            assert bool(torch.isnan(p[0][live:]).all()) and bool((p[1][live:] == SENTINEL).all())
+            if live == 0:
+                assert torch.equal(plain, _start_records(1))
+            else:
+                rec = _lib.EvalRecord.from_buffer_copy(plain.cpu().numpy().tobytes())
+                assert (rec.pairs, rec.steps, rec.nodes) == (31 + live, 9, 1001 + int(nvalid[:live].sum()))
+
+
 @pytest.mark.parametrize('N', [17])
 def test_a_bin_outside_the_records_is_ignored(N):
     bins = list(BINS)

@@ -156,6 +156,36 @@ def test_adversarial_rows_hold_the_beats_rule(N):
         assert KS[0] == 1 and torch.equal(o['hits'][:, 0], correct), name
 
 
+@pytest.mark.parametrize('N', [16, 17, 65])
+def test_the_four_arg_max_routes_agree_on_the_adversarial_rows(N):
+    """one arg-max rule, four routes: fgnn_accuracy_max, fgnn_accuracy_max_labels, the row_hit of fgnn_eval_pairs and rank == 1 of
+    fgnn_eval_ranks count the same rows of every pair -- against the identity written out as labels, so that all four see one target"""
+    g = torch.Generator().manual_seed(N)
+    s, nv = RR.adversarial(N, g)
+    B = s.shape[0]
+    rows = torch.arange(N)[None, :] < nv.long()[:, None]
+    ident = torch.where(rows, torch.arange(N, dtype=torch.int32)[None, :], torch.full((B, N), -1, dtype=torch.int32))
+    sd, nvd, labd, rows = s.to(DEV), nv.to(DEV), ident.to(DEV), rows.to(DEV)
+    plain = torch.full((B,), SENTINEL, dtype=torch.int32, device=DEV)
+    labelled = torch.full((B,), SENTINEL, dtype=torch.int32, device=DEV)
+    _lib.call('fgnn_accuracy_max', _lib.ptr(sd), _lib.ptr(nvd), B, N, _lib.ptr(plain), _lib.stream_ptr())
+    _lib.call('fgnn_accuracy_max_labels', _lib.ptr(sd), _lib.ptr(labd), _lib.ptr(nvd), B, N, _lib.ptr(labelled), _lib.stream_ptr())
+    hits = []
+    for lab in (None, labd):
+        for entry in ('fgnn_eval_pairs', 'fgnn_eval_pairs_labels')[:1 if lab is None else 2]:
+            cost = torch.empty(B, N, N, dtype=torch.float32, device=DEV)
+            row_ce = torch.empty(B, N, dtype=torch.float32, device=DEV)
+            row_hit = torch.full((B, N), SENTINEL, dtype=torch.int32, device=DEV)
+            _lib.call(entry, _lib.ptr(sd), _lib.ptr(nvd), _lib.ptr(lab), B, N, _lib.ptr(cost), N * N, N, _lib.ptr(row_ce), _lib.ptr(row_hit),
+                      _lib.stream_ptr())
+            hits.append(row_hit == 1)
+        hits.append(_ranks(sd, nvd, lab, B, N) == 1)
+    for h in hits[1:]:
+        assert torch.equal(h & rows, hits[0] & rows)
+    count = (hits[0] & rows).sum(1).to(torch.int32)
+    assert torch.equal(plain, count) and torch.equal(labelled, count) and int(count.sum()) > 0
+
+
 # ---------------------------------------------------------------------------------------------------------- layout and cutting
 def test_pair_alone_equals_pair_in_batch():
     N, B = 65, 9

@@ -148,8 +148,9 @@ class _CurveTrainer(FgnnTrainer):
     def __init__(self):
         self.steps = []
 
-    def eval_step_bits(self, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, bins=None, **kw):
-        self.steps.append((bits1.tolist(), bins.tolist(), live, kw))
+    def eval_step_bits(self, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False,
+                       bins=None, rank_meter=None):
+        self.steps.append((bits1.tolist(), bins.tolist(), live, (loss_on_labels, rank_meter)))
 
 
 class _CurveGenerator:
@@ -158,9 +159,9 @@ class _CurveGenerator:
     def levels(self, noises):
         return PairGenerator(20, 'ErdosRenyi', device='cpu').levels(noises)
 
-    def bits(self, index=None, levels=None, level=None, **kw):
-        assert len(levels) == 3 and kw in ({}, {'permute': True})
-        return (index, level, None) + ((index,) if kw else ())
+    def bits(self, index=None, levels=None, level=None, permute=False):
+        assert len(levels) == 3 and isinstance(permute, bool)          # (any other keyword is a TypeError)
+        return (index, level, None) + ((index,) if permute else ())
 
 
 def _curve_meter():
@@ -181,11 +182,11 @@ def test_noise_curve_loop_and_its_all_reduce(monkeypatch):
     assert tr.noise_curve(*args, meter=meter) is meter and meter.reduced == 0
     assert [s[2] for s in tr.steps] == [4, 4, 4, 3]
     seen = [(l, p) for pair, lev, live, kw in tr.steps for p, l in list(zip(pair, lev))[:live]]
-    assert seen == [(k, m) for k in range(K) for m in range(M)] and all(s[3] == {} for s in tr.steps)
+    assert seen == [(k, m) for k in range(K) for m in range(M)] and all(s[3] == (False, None) for s in tr.steps)
     # parts of a split walked in one process: nothing is reduced
     tr, meter = _CurveTrainer(), _curve_meter()
     tr.noise_curve(*args, meter=meter, rank=1, world_size=2, permute=True, loss_on_labels=True)
-    assert [s[2] for s in tr.steps] == [4, 3] and meter.reduced == 0 and all(s[3] == {'loss_on_labels': True} for s in tr.steps)
+    assert [s[2] for s in tr.steps] == [4, 3] and meter.reduced == 0 and all(s[3] == (True, None) for s in tr.steps)
     # two ranks of torch.distributed: this rank's share, one all-reduce; with world_size=1 a whole curve of its own, none
     monkeypatch.setattr(dp, 'world_size', lambda: 2)
     monkeypatch.setattr(torch.distributed, 'get_rank', lambda: 1)

@@ -8,8 +8,8 @@ import torch
 
 import rank_ref as RR
 from graph_neural_net_amd import _lib, metrics
-from graph_neural_net_amd.evaluation import (RANK_WORDS, check_ks, pack_rank_records, rank_record_dict, rank_result,
-                                             unpack_rank_records_)
+from graph_neural_net_amd.evaluation import (RANK_WORDS, check_ks, pack_rank_records, pack_records, rank_record_dict, rank_result,
+                                             unpack_rank_records_, unpack_records_)
 from graph_neural_net_amd.masked import MaskedTensor
 
 
@@ -101,6 +101,24 @@ def test_allreduce_packing_round_trips():
     assert two[2].rank_sum == 2 * recs[2].rank_sum and two[2].hits[7] == 2 * recs[2].hits[7] and two[2].rr_sum == 2 * recs[2].rr_sum
     rec = rank_record_dict(two[1], (1, 5))
     assert rec['hits'] == {1: 2000, 5: 2002} and rec['targets'] == 2 * (2 ** 52 - 1)
+    # the rank pair is the generic one at 14 words ...
+    assert torch.equal(pack_records(buf, K, RANK_WORDS), t)
+    assert unpack_records_(torch.zeros(K * 8 * RANK_WORDS, dtype=torch.uint8), K, t).numpy().tobytes() == raw
+    # ... which packs the evaluation record, 6 words, by the same rule
+    words = ctypes.sizeof(_lib.EvalRecord) // 8
+    evs = (_lib.EvalRecord * K)()
+    for j in range(K):
+        evs[j].ce_sum = 0.1 + j / 3.0
+        evs[j].nodes, evs[j].correct_lsap, evs[j].correct_max, evs[j].pairs, evs[j].steps = 2 ** 52 - j, 2 ** 52 - 7 * j - 1, 10 ** 12 + j, j, 3
+    eraw = bytes(evs)
+    et = pack_records(torch.frombuffer(bytearray(eraw), dtype=torch.uint8), K, words)
+    assert words == 6 and et.shape == (K, 6) and et.dtype == torch.float64
+    assert et[2].tolist() == [0.1 + 2 / 3.0, 2 ** 52 - 2, 2 ** 52 - 15, 10 ** 12 + 2, 2, 3]
+    assert unpack_records_(torch.zeros(K * 8 * words, dtype=torch.uint8), K, et).numpy().tobytes() == eraw
+    etwo = (_lib.EvalRecord * K).from_buffer_copy(unpack_records_(torch.zeros(K * 8 * words, dtype=torch.uint8), K, et + et).numpy().tobytes())
+    for j in range(K):
+        assert etwo[j].ce_sum == 2 * evs[j].ce_sum
+        assert all(getattr(etwo[j], n) == 2 * getattr(evs[j], n) for n in ('nodes', 'correct_lsap', 'correct_max', 'pairs', 'steps'))
     res = rank_result({'rr_sum': 3.0, 'rank_sum': 12, 'targets': 4, 'nodes': 5, 'pairs': 1, 'steps': 1, 'hits': {1: 2, 5: 4}})
     assert res == {'hits@1': 0.5, 'hits@5': 1.0, 'mrr': 0.75, 'mean_rank': 3.0, 'targets': 4, 'nodes': 5, 'pairs': 1}
     empty = rank_result({'rr_sum': 0.0, 'rank_sum': 0, 'targets': 0, 'nodes': 3, 'pairs': 1, 'steps': 1, 'hits': {1: 0}})
