@@ -142,6 +142,14 @@ class PairgenArgs(C.Structure):       # fgnn_pairgen_args (csrc/pairgen.hip)
                 ('bits1', C.c_void_p), ('bits2', C.c_void_p), ('nvalid', C.c_void_p)]
 
 
+class PairstoreArgs(C.Structure):     # fgnn_pairstore_args (csrc/pairstore.hip)
+    _fields_ = [('seed', C.c_ulonglong), ('first', C.c_longlong), ('M', C.c_longlong), ('B', C.c_int), ('N', C.c_int),
+                ('noise_model', C.c_int), ('emax', C.c_int), ('thr_noise1', C.c_ulonglong), ('thr_noise2', C.c_ulonglong),
+                ('parents', C.c_void_p), ('sizes', C.c_void_p), ('seconds', C.c_void_p), ('index', C.c_void_p),
+                ('level_thr', C.c_void_p), ('level', C.c_void_p), ('K', C.c_int),
+                ('bits1', C.c_void_p), ('bits2', C.c_void_p), ('nvalid', C.c_void_p)]
+
+
 FGNN_GUARD_MAX_PARTS = 64         # include/fgnn_hip.h
 FGNN_GUARD_SKIP_NONFINITE = 1     # mode bit
 FGNN_GUARD_NONFINITE = 1          # flags bit
@@ -273,6 +281,8 @@ _SIGNATURES = {
     'fgnn_pairgen': [C.POINTER(PairgenArgs), _VP],
     'fgnn_pairgen_indexed': [C.POINTER(PairgenArgs), _VP, _VP],
     'fgnn_pairgen_levels': [C.POINTER(PairgenArgs), _VP, _VP, _I, _VP, _VP],
+    'fgnn_pairstore_supported': [_I, _I],
+    'fgnn_pairstore_gather': [C.POINTER(PairstoreArgs), _VP],
     'fgnn_epoch_index': [C.c_ulonglong, C.c_ulonglong, _LL, _LL, _LL, _VP, _VP],
     'fgnn_qap_objective': [_VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP],
     'fgnn_qap_improve_cost': [_VP, _VP, _VP, _VP, _I, _I, _VP, _LL, _I, _VP],

@@ -94,7 +94,99 @@ class NoiseLevels:
         return len(self.noises)
 
 
-class PairGenerator:
+class PairSource:
+    """What the epoch loops take as their `generator` (FgnnTrainer.train_epoch / evaluate / fit / noise_curve): the selection and
+    level arguments, ``levels``, and ``dense`` / ``spectral`` over ``bits``.  A subclass has `n_vertices`, `edge_density`, `seed`,
+    `device` and ``bits(first, count, index, permute, levels, level)``: ``PairGenerator`` below, ``pairstore.PairStore``."""
+
+    def _selection(self, first, count, index):
+        """(first, count, None) of a contiguous range, or (0, len(index), index as a contiguous int64 tensor on the device)."""
+        if index is None:
+            if first is None or count is None:
+                raise ValueError('give either (first, count) or index=')
+            first, count = int(first), int(count)
+            if first < 0 or count < 0:
+                raise ValueError('first and count must be >= 0, got %d, %d' % (first, count))
+            return first, count, None
+        if first is not None or count is not None:
+            raise ValueError('give either (first, count) or index=, not both')
+        if not torch.is_tensor(index):
+            index = torch.tensor(index, dtype=torch.int64)
+        if index.dim() != 1 or index.dtype != torch.int64:
+            raise ValueError('index must be a 1-D int64 tensor, got shape %s, %s' % (tuple(index.shape), index.dtype))
+        return 0, index.numel(), index.to(self.device).contiguous()
+
+    def levels(self, noises):
+        """The NoiseLevels of this generator's edge density for `noises` (1 to 64 values in [0, 1]): the `levels=` of bits / dense /
+        spectral.  `self.noise` does not enter it."""
+        return NoiseLevels(noises, self.edge_density, self.device)
+
+    def _need_gpu(self):
+        if self.device.type != 'cuda':
+            raise RuntimeError('%s: device %s; the pairs are made on the GPU only (there is no CPU path)'
+                               % (type(self).__name__, self.device))
+
+    def _level(self, levels, level, count):
+        """level= as a contiguous (count,) int32 tensor on the device (never read on the host), or None without levels"""
+        if levels is None and level is None:
+            return None
+        if levels is None or level is None:
+            raise ValueError('levels= (PairGenerator.levels) and level= (one level number per pair) go together')
+        if not isinstance(levels, NoiseLevels) or levels.edge_density != self.edge_density or not same_device(levels.table.device, self.device):
+            raise ValueError('levels must come from the levels() of this generator (edge density %r, device %s)'
+                             % (self.edge_density, self.device))
+        if not torch.is_tensor(level):
+            level = torch.tensor(level, dtype=torch.int32)
+        if level.dim() != 1 or level.numel() != count or level.is_floating_point() or level.dtype == torch.bool:
+            raise ValueError('level must be a (%d,) integer tensor, got shape %s, %s' % (count, tuple(level.shape), level.dtype))
+        return level.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def _planted(self, b1, b2, nv, first, count, index):
+        """permute=True: side 2 relabelled by the planted permutation of each pair -> (bits1, bits2, nvalid, labels)"""
+        N = self.n_vertices
+        if index is None:
+            labels = planted_permutation(self.seed, N, first, count, nvalid=nv, device=self.device)
+        else:
+            labels = planted_permutation(self.seed, N, index=index, nvalid=nv, device=self.device)
+        return b1, relabel_bits(b2, labels, nv), nv, labels
+
+    @staticmethod
+    def _levels_kw(levels, level):
+        return {} if levels is None and level is None else {'levels': levels, 'level': level}
+
+    def dense(self, first=None, count=None, index=None, permute=False, levels=None, level=None):
+        """The reference's collate structures for the same pairs: ({'input': x1}, {'input': x2}) with (count, 2, N, N) fp32
+        tensor representations (collate_fn_pair_explore) for a constant vertex count, else two MaskedTensors padded to the
+        largest n_i of the batch (collate_fn_pair; one host sync for that size).  permute=True: side 2 is the representation of
+        the relabelled graph and the (count, N) labels are appended to the return value.  levels, level: as in `bits`."""
+        b1, b2, nv, *labels = self.bits(first, count, index, permute, **self._levels_kw(levels, level))
+        count = b1.shape[0]
+        N = self.n_vertices
+        x1, x2 = expand_adjacency(b1, N, nv), expand_adjacency(b2, N, nv)
+        if nv is None:
+            return ({'input': x1}, {'input': x2}, *labels)
+        n = int(nv.max().item()) if count else 0
+        x1, x2 = x1[:, :, :n, :n].contiguous(), x2[:, :, :n, :n].contiguous()
+        return (MaskedTensor(x1, nv, (2, 3), 'N'), MaskedTensor(x2, nv, (2, 3), 'M'), *labels)
+
+    def spectral(self, first=None, count=None, n_powers=4, index=None, permute=False, levels=None, level=None):
+        """The twin of `dense` for the reference's ``QAP_spectralGenerator`` (loaders/data_generator.py:221-277): the same pairs as
+        `bits`, each side as the n_powers channels L, L^2, ... of ``spectral.spectral_features`` (one launch per side, straight from
+        the bit rows; an isolated vertex gives a zero row and column where the reference gives NaN).  ({'input': F1}, {'input': F2})
+        with (count, n_powers, N, N) fp32 tensors for a constant vertex count, else two MaskedTensors written directly at the
+        largest n_i of the batch (one host sync for that size), with the names and masked dims of `dense`.  permute=True: side 2 is
+        computed from the relabelled bit rows and the (count, N) labels are appended to the return value.  levels, level: as in
+        `bits`."""
+        b1, b2, nv, *labels = self.bits(first, count, index, permute, **self._levels_kw(levels, level))
+        count = b1.shape[0]
+        if nv is None:
+            return ({'input': spectral_features(b1, None, n_powers)}, {'input': spectral_features(b2, None, n_powers)}, *labels)
+        n = max(int(nv.max().item()), 1) if count else 1
+        f1, f2 = spectral_features(b1, nv, n_powers, n_out=n), spectral_features(b2, nv, n_powers, n_out=n)
+        return (MaskedTensor(f1, nv, (2, 3), 'N'), MaskedTensor(f2, nv, (2, 3), 'M'), *labels)
+
+
+class PairGenerator(PairSource):
     """On-device twin of the reference's ``QAP_Generator`` (the ``data.train`` / ``data.test`` parameters)."""
 
     def __init__(self, n_vertices, generative_model='Regular', noise_model='ErdosRenyi', edge_density=0.2, noise=0.1,
@@ -141,47 +233,6 @@ class PairGenerator:
                    edge_density=cfg['edge_density'], noise=cfg['noise'], vertex_proba=cfg.get('vertex_proba', 1.0),
                    seed=seed, **kw)
 
-    def _selection(self, first, count, index):
-        """(first, count, None) of a contiguous range, or (0, len(index), index as a contiguous int64 tensor on the device)."""
-        if index is None:
-            if first is None or count is None:
-                raise ValueError('give either (first, count) or index=')
-            first, count = int(first), int(count)
-            if first < 0 or count < 0:
-                raise ValueError('first and count must be >= 0, got %d, %d' % (first, count))
-            return first, count, None
-        if first is not None or count is not None:
-            raise ValueError('give either (first, count) or index=, not both')
-        if not torch.is_tensor(index):
-            index = torch.tensor(index, dtype=torch.int64)
-        if index.dim() != 1 or index.dtype != torch.int64:
-            raise ValueError('index must be a 1-D int64 tensor, got shape %s, %s' % (tuple(index.shape), index.dtype))
-        return 0, index.numel(), index.to(self.device).contiguous()
-
-    def levels(self, noises):
-        """The NoiseLevels of this generator's edge density for `noises` (1 to 64 values in [0, 1]): the `levels=` of bits / dense /
-        spectral.  `self.noise` does not enter it."""
-        return NoiseLevels(noises, self.edge_density, self.device)
-
-    def _need_gpu(self):
-        if self.device.type != 'cuda':
-            raise RuntimeError('PairGenerator: device %s; the generator runs on the GPU only (there is no CPU path)' % (self.device,))
-
-    def _level(self, levels, level, count):
-        """level= as a contiguous (count,) int32 tensor on the device (never read on the host), or None without levels"""
-        if levels is None and level is None:
-            return None
-        if levels is None or level is None:
-            raise ValueError('levels= (PairGenerator.levels) and level= (one level number per pair) go together')
-        if not isinstance(levels, NoiseLevels) or levels.edge_density != self.edge_density or not same_device(levels.table.device, self.device):
-            raise ValueError('levels must come from the levels() of this generator (edge density %r, device %s)'
-                             % (self.edge_density, self.device))
-        if not torch.is_tensor(level):
-            level = torch.tensor(level, dtype=torch.int32)
-        if level.dim() != 1 or level.numel() != count or level.is_floating_point() or level.dtype == torch.bool:
-            raise ValueError('level must be a (%d,) integer tensor, got shape %s, %s' % (count, tuple(level.shape), level.dtype))
-        return level.to(device=self.device, dtype=torch.int32).contiguous()
-
     def bits(self, first=None, count=None, index=None, permute=False, levels=None, level=None):
         """Pairs first .. first + count - 1, or the pairs index[0], index[1], ... (a 1-D int64 tensor, or a list; moved to the device
         if it is not there; any order, duplicates allowed) -> (bits1, bits2, nvalid): (count, N, ceil(N/32)) int32 device tensors
@@ -220,44 +271,5 @@ class PairGenerator:
                 else:
                     _lib.call('fgnn_pairgen_indexed', C.byref(a), _lib.ptr(index), _lib.stream_ptr())
             if permute:
-                if index is None:
-                    labels = planted_permutation(self.seed, N, first, count, nvalid=nv, device=self.device)
-                else:
-                    labels = planted_permutation(self.seed, N, index=index, nvalid=nv, device=self.device)
-                return b1, relabel_bits(b2, labels, nv), nv, labels
+                return self._planted(b1, b2, nv, first, count, index)
         return b1, b2, nv
-
-    @staticmethod
-    def _levels_kw(levels, level):
-        return {} if levels is None and level is None else {'levels': levels, 'level': level}
-
-    def dense(self, first=None, count=None, index=None, permute=False, levels=None, level=None):
-        """The reference's collate structures for the same pairs: ({'input': x1}, {'input': x2}) with (count, 2, N, N) fp32
-        tensor representations (collate_fn_pair_explore) for a constant vertex count, else two MaskedTensors padded to the
-        largest n_i of the batch (collate_fn_pair; one host sync for that size).  permute=True: side 2 is the representation of
-        the relabelled graph and the (count, N) labels are appended to the return value.  levels, level: as in `bits`."""
-        b1, b2, nv, *labels = self.bits(first, count, index, permute, **self._levels_kw(levels, level))
-        count = b1.shape[0]
-        N = self.n_vertices
-        x1, x2 = expand_adjacency(b1, N, nv), expand_adjacency(b2, N, nv)
-        if nv is None:
-            return ({'input': x1}, {'input': x2}, *labels)
-        n = int(nv.max().item()) if count else 0
-        x1, x2 = x1[:, :, :n, :n].contiguous(), x2[:, :, :n, :n].contiguous()
-        return (MaskedTensor(x1, nv, (2, 3), 'N'), MaskedTensor(x2, nv, (2, 3), 'M'), *labels)
-
-    def spectral(self, first=None, count=None, n_powers=4, index=None, permute=False, levels=None, level=None):
-        """The twin of `dense` for the reference's ``QAP_spectralGenerator`` (loaders/data_generator.py:221-277): the same pairs as
-        `bits`, each side as the n_powers channels L, L^2, ... of ``spectral.spectral_features`` (one launch per side, straight from
-        the bit rows; an isolated vertex gives a zero row and column where the reference gives NaN).  ({'input': F1}, {'input': F2})
-        with (count, n_powers, N, N) fp32 tensors for a constant vertex count, else two MaskedTensors written directly at the
-        largest n_i of the batch (one host sync for that size), with the names and masked dims of `dense`.  permute=True: side 2 is
-        computed from the relabelled bit rows and the (count, N) labels are appended to the return value.  levels, level: as in
-        `bits`."""
-        b1, b2, nv, *labels = self.bits(first, count, index, permute, **self._levels_kw(levels, level))
-        count = b1.shape[0]
-        if nv is None:
-            return ({'input': spectral_features(b1, None, n_powers)}, {'input': spectral_features(b2, None, n_powers)}, *labels)
-        n = max(int(nv.max().item()), 1) if count else 1
-        f1, f2 = spectral_features(b1, nv, n_powers, n_out=n), spectral_features(b2, nv, n_powers, n_out=n)
-        return (MaskedTensor(f1, nv, (2, 3), 'N'), MaskedTensor(f2, nv, (2, 3), 'M'), *labels)

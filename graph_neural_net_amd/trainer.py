@@ -520,7 +520,7 @@ class FgnnTrainer:
     def train_epoch(self, generator, sampler, epoch, batch_size, permute=False, exact_last=False):
         """One epoch over a fixed dataset of on-device pairs, in the sampler's order (the reference's shuffled DataLoader over
         num_examples_train pairs): per step ``train_step_bits(*generator.bits(index=sampler.batch_index(epoch, step, batch_size)))``.
-        generator: pairgen.PairGenerator; sampler: sampler.EpochSampler (its rank and world size are this process's).  The loop reads
+        generator: pairgen.PairGenerator or pairstore.PairStore; sampler: sampler.EpochSampler (its rank and world size are this process's).  The loop reads
         nothing back (a ragged generator's vertex counts stay on the device as well).  Returns the (steps,) device tensor of the
         per-step losses of the global batch.
         permute=True: the pairs come relabelled (``generator.bits(index=..., permute=True)``) and the step trains on the

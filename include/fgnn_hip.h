@@ -818,6 +818,43 @@ int fgnn_pairgen_indexed(const fgnn_pairgen_args *args, const long long *index, 
 int fgnn_pairgen_levels(const fgnn_pairgen_args *args, const long long *index /* NULL: args->first + b */,
                         const unsigned long long *level_thr /* (K, 2) */, int K, const int *level /* (B) */, void *stream);
 
+/* ---- stored graphs (csrc/pairstore.hip; graph_neural_net_amd/pairstore.py) -----------------------------------------------------
+ * A store is M graphs in the wire format above, resident in device memory: parents (M, N, ceil(N/32)) words, symmetric, zero
+ * diagonal, rows / columns >= n_k and padding bits zero; sizes (optional, int32[M]) = n_k in [0, N], NULL when every graph has N
+ * vertices; seconds (optional, the shape of parents): a stored second side.  One launch writes the batch (bits1, bits2, nvalid) of
+ * fgnn_pairgen_indexed: workgroup b takes example k = index[b] (int64[B] on the device), or first + b when index is NULL.  bits1 is
+ * parents[k], nvalid n_k, and bits2
+ *   with seconds: seconds[k] as it is (seed, noise_model, emax, the thresholds and the levels are not used; levels are refused);
+ *   without: the noisy copy that pairgen_kernel's noise stage makes of that parent for pair (seed, k) at this N and n_k -- streams
+ *     2 / 3, positions i N + j (ErdosRenyi), o and o 2m + i (EdgeSwap), the thresholds below -- so a store filled with a generator's
+ *     parents returns that generator's pairs bit for bit.  EdgeSwap keeps the parent's edge list in LDS: emax >= the largest edge
+ *     count of a stored parent (at most N (N - 1) / 2).
+ * level_thr, K, level: as in fgnn_pairgen_levels (all NULL / 0: thr_noise1 / thr_noise2 of the arguments hold for every pair).
+ * Caller errors that the host cannot see are handled as fgnn_pairgen_indexed handles a negative index -- the empty graph, nvalid = 0,
+ * nothing outside the arguments' extents read: k outside [0, M), a level outside [0, K), a parent with more than emax edges. */
+typedef struct {
+    unsigned long long seed;            /* Philox key of the noise */
+    long long first;                    /* example of workgroup 0 when index is NULL */
+    long long M;                        /* stored graphs */
+    int B, N;                           /* pairs of the launch, padded size (1 <= N <= FGNN_PAIRGEN_MAX_N) */
+    int noise_model;                    /* FGNN_PAIRGEN_ERDOS_RENYI / FGNN_PAIRGEN_EDGE_SWAP */
+    int emax;                           /* EdgeSwap: largest edge count of a stored parent */
+    unsigned long long thr_noise1;      /* as in fgnn_pairgen_args */
+    unsigned long long thr_noise2;
+    const unsigned *parents;            /* (M, N, ceil(N/32)) */
+    const int *sizes;                   /* optional (M) */
+    const unsigned *seconds;            /* optional (M, N, ceil(N/32)) */
+    const long long *index;             /* optional (B) */
+    const unsigned long long *level_thr; /* optional (K, 2) */
+    const int *level;                   /* optional (B) */
+    int K;
+    unsigned *bits1, *bits2;            /* out (B, N, ceil(N/32)) */
+    int *nvalid;                        /* optional out (B) */
+} fgnn_pairstore_args;
+/* 1 if (N, noise_model) is a shape fgnn_pairstore_gather runs */
+int fgnn_pairstore_supported(int N, int noise_model);
+int fgnn_pairstore_gather(const fgnn_pairstore_args *args, void *stream);
+
 /* ---- the order of a shuffled epoch (csrc/pairgen.hip; graph_neural_net_amd/sampler.py) ---------------------------------------
  * out[i] = pi((first_pos + i) mod M) for i < count, with pi the permutation of [0, M) that (seed, epoch) select: a balanced Feistel
  * network on 2 h bits (h = max(1, ceil(ceil(log2 M) / 2))), FGNN_EPOCH_ROUNDS rounds, walked along its cycle until the value is
