@@ -171,6 +171,12 @@ class RankRecord(C.Structure):        # fgnn_rank_record (csrc/rank.hip); lives 
                 ('pairs', C.c_longlong), ('steps', C.c_longlong), ('hits', C.c_longlong * FGNN_RANK_MAX_K)]
 
 
+class QapRecord(C.Structure):         # fgnn_qap_record (csrc/qap_fold.hip); lives in device memory, this mirror gives the offsets
+    _fields_ = [('ratio_sum', C.c_double)] + [(name, C.c_longlong) for name in (
+        'ratio_pairs', 'qap_sum', 'planted_sum', 'correct', 'refined_sum', 'refined_correct', 'recovered', 'exact', 'improved',
+        'unmatched', 'nodes', 'pairs', 'steps')]
+
+
 MAX_GRAD_JOBS = 16
 MAX_PACK_JOBS = 24
 _VP, _LL, _I, _F = C.c_void_p, C.c_longlong, C.c_int, C.c_float
@@ -306,6 +312,8 @@ _SIGNATURES = {
     'fgnn_eval_fold_bins': [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP],
     'fgnn_eval_ranks': [_VP, _LL, _I, _VP, _VP, _I, _I, _VP, _VP],
     'fgnn_rank_fold': [_VP, _VP, _I, _I, _I, C.POINTER(C.c_int), _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP],
+    'fgnn_qap_fold': [_VP] * 7 + [_I, _I, _I] + [_VP] * 5,
+    'fgnn_qap_fold_bins': [_VP] * 7 + [_I, _I, _I, _VP, _I] + [_VP] * 5,
     # ---- bf16 path ----
     'fgnn_tiles_per_graph16': [_I, _I],
     'fgnn_to_bf16': [_VP, _VP, _I, _I, _I, _I, _VP, _LL, _LL, _VP],

@@ -14,7 +14,13 @@ have a fixed order.  Nothing is read back until ``EvalMeter.result()``.  There i
 fgnn_eval_ranks, fgnn_rank_fold) into a ``RankMeter`` or, with ``bins=``, a ``BinnedRankMeter``; ``evaluate_scores(...,
 rank_meter=)`` issues them after its own four, on the same scores, labels, ``live`` and bins.
 
-The four meters are one thing -- records of one ctypes struct in one device buffer (``_Records``) -- with two record types.
+``decode_scores`` is the epoch form of the reference's ``all_acc_qap(val_loader, ...)`` / ``all_greedy_losses_acc``
+(toolbox/metrics.py:168-223): the Hungarian matching, its QAP objective and the planted one on the pairs' bit words (csrc/qap.hip),
+optionally the greedy refinement, and fgnn_qap_fold (csrc/qap_fold.hip) into a ``QapMeter`` or, with ``bins=``, a
+``BinnedQapMeter``; ``evaluate_scores(..., qap_meter=, bits=, refine=)`` issues it after its own launches on the assignment its
+solver launch wrote.  0/1 graphs only; the real-weighted decode stays per batch.
+
+The six meters are one thing -- records of one ctypes struct in one device buffer (``_Records``) -- with three record types.
 """
 import ctypes
 
@@ -255,6 +261,96 @@ class BinnedRankMeter(_BinnedRecords):
         self._open_bins(device, K, values, ks=self.ks)
 
 
+def qap_result(rec):
+    """The decode figures of an epoch from a QapRecord dict: 'acc' = correct / nodes (the accuracy of all_acc_qap's matching),
+    'qap_ratio' = qap_sum / planted_sum (the recovered objective over the planted one, the figure quoted across noise levels),
+    'mean_ratio' = ratio_sum / ratio_pairs (the mean of the per-pair ratios), 'recovered' and 'exact' as fractions of the pairs,
+    'unmatched', 'nodes', 'pairs'; and, when a refinement was folded (rec['refined'], which a meter's record carries):
+    'refined_acc' = refined_correct / nodes, 'refined_qap_ratio' = refined_sum / planted_sum, 'improved' as a fraction of the
+    pairs.  An empty denominator gives NaN."""
+    div = lambda a, b: a / b if b else float('nan')
+    out = {'acc': div(rec['correct'], rec['nodes']), 'qap_ratio': div(rec['qap_sum'], rec['planted_sum']),
+           'mean_ratio': div(rec['ratio_sum'], rec['ratio_pairs']), 'recovered': div(rec['recovered'], rec['pairs']),
+           'exact': div(rec['exact'], rec['pairs']), 'unmatched': rec['unmatched'], 'nodes': rec['nodes'], 'pairs': rec['pairs']}
+    if rec.get('refined'):
+        out.update({'refined_acc': div(rec['refined_correct'], rec['nodes']),
+                    'refined_qap_ratio': div(rec['refined_sum'], rec['planted_sum']), 'improved': div(rec['improved'], rec['pairs'])})
+    return out
+
+
+class QapMeter(_Records):
+    """The device record of a decode epoch (fgnn_qap_record, include/fgnn_hip.h): the reference's all_acc_qap(val_loader, ...) and
+    all_greedy_losses_acc (toolbox/metrics.py:168-223) over a whole loader, for 0/1 graphs on the bit-word path (the real-weighted
+    decode, qap.py's weighted=True, stays per batch).  Every field of the record is a 0-dim view of it (`ratio_sum` fp64, the
+    others int64); `acc`, `qap_ratio`, `mean_ratio`, `refined_acc`, `refined_qap_ratio` are 0-dim fp64 device tensors formed from
+    them on the device.  `refined` (host) says whether a refinement was folded since the last reset; `record()` carries it and
+    `result()` (qap_result) is the only host synchronisation."""
+    RECORD, FIELDS = _lib.QapRecord, tuple(name for name, _ in _lib.QapRecord._fields_)
+    _result = staticmethod(qap_result)
+
+    def __init__(self, device, buf=None):
+        """buf: the record's bytes when they belong to a larger buffer (a record of a BinnedQapMeter)"""
+        self.refined = False
+        self._open(device, buf=buf)
+
+    def reset(self):
+        self.refined = False
+        return super().reset()
+
+    def _mark_refined(self):
+        self.refined = True
+
+    def _dict(self, rec):
+        out = {name: getattr(rec, name) for name in self.FIELDS}
+        out['refined'] = self.refined
+        return out
+
+    def _over(self, a, b):
+        return a.to(torch.float64) / b.to(torch.float64)
+
+    @property
+    def acc(self):
+        """correct / nodes of everything folded so far (NaN before the first node)"""
+        return self._over(self.correct, self.nodes)
+
+    @property
+    def qap_ratio(self):
+        return self._over(self.qap_sum, self.planted_sum)
+
+    @property
+    def mean_ratio(self):
+        return self.ratio_sum / self.ratio_pairs.to(torch.float64)
+
+    @property
+    def refined_acc(self):
+        return self._over(self.refined_correct, self.nodes)
+
+    @property
+    def refined_qap_ratio(self):
+        return self._over(self.refined_sum, self.planted_sum)
+
+
+class BinnedQapMeter(_BinnedRecords):
+    """K decode records, one per bin: `meter[k]` is a QapMeter; see _BinnedRecords."""
+    PLAIN, RECORD = QapMeter, _lib.QapRecord
+
+    def __init__(self, device, K, values=None):
+        self._open_bins(device, self._check_bins(K, values), values)
+
+    @property
+    def refined(self):
+        return self.meters[0].refined
+
+    def reset(self):
+        for m in self.meters:
+            m.refined = False
+        return super().reset()
+
+    def _mark_refined(self):
+        for m in self.meters:
+            m.refined = True
+
+
 RANK_WORDS = ctypes.sizeof(_lib.RankRecord) // 8
 unpack_rank_records_ = unpack_records_
 
@@ -265,7 +361,8 @@ def pack_rank_records(buf, K):
 
 
 def read_records(*meters):
-    """(meter.record(), rank_meter.record(), ...) of plain meters -- an EvalMeter and a RankMeter -- from ONE device-to-host copy."""
+    """(meter.record(), rank_meter.record(), ...) of plain meters -- an EvalMeter, a RankMeter, a QapMeter -- from ONE device-to-host
+    copy."""
     return tuple(m._dict(recs[0]) for m, recs in zip(meters, _read(*meters)))
 
 
@@ -352,8 +449,93 @@ def rank_scores(scores, nvalid=None, labels=None, meter=None, live=None, bins=No
         return _rank_launches(s, nvalid, labels, bins, B, N, live, meter)
 
 
+def _check_refine(who, refine):
+    if isinstance(refine, bool) or int(refine) != refine or refine < 0:
+        raise ValueError('%s: refine must be an integer >= 0 (rounds of greedy_qap), got %r' % (who, refine))
+    return int(refine)
+
+
+def _bits_args(who, bits, B, N, dev):
+    """bits: (bits1, bits2), each (B, N, ceil(N/32)) int32 bit words on dev -> the two, contiguous"""
+    if bits is None or len(bits) != 2:
+        raise ValueError('%s: the decode needs bits=(bits1, bits2), the two graphs as bit words' % who)
+    want = (B, N, (N + 31) // 32)
+    for t in bits:
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != want or t.device != dev:
+            raise ValueError('%s: bit words must be %s int32 tensors on %s, got %s'
+                             % (who, want, dev, (tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else type(t).__name__))
+    if N > _lib.FGNN_QAP_MAX_N:
+        raise RuntimeError('%s: at most %d vertices per graph (got %d)' % (who, _lib.FGNN_QAP_MAX_N, N))
+    return bits[0].contiguous(), bits[1].contiguous()
+
+
+def _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine):
+    """qap.objective_bits (once more on the labels), qap.greedy_bits with refine > 0, then fgnn_qap_fold(_bins), on checked
+    arguments (on the current stream of the bit words' device) -> the dict of decode_scores"""
+    from . import qap
+    dev = b1.device
+    obj = qap.objective_bits(b1, b2, assign, nvalid, raw=True)
+    q, planted = obj[0], obj[1]
+    if labels is not None:          # (as all_acc_qap: planted is the objective of the labels' matching)
+        planted = qap.objective_bits(b1, b2, labels, nvalid, raw=True)[0]
+    perm = refined = None
+    if refine > 0:
+        g = qap.greedy_bits(b1, b2, assign, refine, nvalid, labels, raw=True)
+        perm, refined = g['perm'], g['s_best2']
+        meter._mark_refined()
+    # one zero-filled allocation for the three per-pair outputs: the 8-byte words first
+    words = torch.zeros(2 * B, dtype=torch.int64, device=dev)
+    ratio, ints = words[:B].view(torch.float64), words[B:].view(torch.int32)
+    correct, refined_correct = ints[:B], ints[B:]
+    pairs = (_lib.ptr(assign), _lib.ptr(perm), _lib.ptr(labels), _lib.ptr(q), _lib.ptr(planted), _lib.ptr(refined), _lib.ptr(nvalid),
+             B, N, live)
+    outs = (_lib.ptr(correct), _lib.ptr(refined_correct), _lib.ptr(ratio), _lib.ptr(meter.buf), _lib.stream_ptr())
+    if bins is None:
+        _lib.call('fgnn_qap_fold', *pairs, *outs)
+    else:
+        _lib.call('fgnn_qap_fold_bins', *pairs, _lib.ptr(bins), meter.K, *outs)
+    return {'assign': assign, 'qap': q, 'planted': planted, 'correct': correct, 'ratio': ratio, 'perm': perm, 'refined': refined,
+            'refined_correct': None if perm is None else refined_correct, 'meter': meter}
+
+
+def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, bins=None, refine=0, assign=None):
+    """The reference's all_acc_qap / all_greedy_losses_acc (toolbox/metrics.py:168-223) of a batch, added to an epoch record.
+    scores, nvalid, labels, live, bins: as evaluate_scores takes them, with the same refusals; bits1, bits2: the two graphs as
+    (B, N, ceil(N/32)) int32 bit words on the scores' device (PairGenerator.bits, synthetic.pack_adjacency).  0/1 graphs only: the
+    real-weighted decode (qap.all_acc_qap / greedy_qap with weighted=True, fp32 objectives) stays per batch and has no record.
+    The chain: the Hungarian matching of the scores (metrics.lsap_device, the route of qap.all_acc_qap) unless `assign`, a (B, N)
+    int32 device tensor of matched columns, is handed in; qap.objective_bits for qap and planted, once more on the labels when
+    there are any (planted is then the objective of the labels' matching); with refine = T > 0 the T rounds of qap.greedy_bits
+    from that matching; then fgnn_qap_fold, which adds the live pairs to `meter` (a QapMeter; with bins= a BinnedQapMeter, pair b
+    to record bins[b]; None: a fresh QapMeter).
+    Returns the device tensors {'assign': (B, N) int32, 'qap', 'planted': (B,) int32, 'correct': (B,) int32 rows where assign is the
+    row's target, 'ratio': (B,) fp64 qap / planted (0 for an unmatched pair or planted <= 0), 'perm': (B, N) int32 and 'refined':
+    (B,) int32 of the refinement (None without) -- refined is 2 s_best, trace(A P B P^T) of perm, the unit of qap --
+    'refined_correct': (B,) int32 (None without), 'meter'}; correct, ratio and refined_correct of pairs >= live are zero.
+    Nothing is read back."""
+    if meter is None and bins is not None:
+        raise ValueError('decode_scores: bins= and a BinnedQapMeter as meter go together')
+    refine = _check_refine('decode_scores', refine)
+    s, nvalid, labels, bins, B, N, live = _score_args('decode_scores', scores, nvalid, labels, live, bins)
+    dev = s.device
+    b1, b2 = _bits_args('decode_scores', (bits1, bits2), B, N, dev)
+    if meter is None:
+        meter = QapMeter(dev)
+    else:
+        _check_meter('decode_scores', 'meter', BinnedQapMeter, meter, bins, dev)
+    if assign is not None:
+        if not torch.is_tensor(assign) or tuple(assign.shape) != (B, N) or assign.is_floating_point() or assign.device != dev:
+            raise ValueError('decode_scores: assign must be a (%d, %d) integer tensor on %s' % (B, N, dev))
+        assign = assign.to(torch.int32).contiguous()
+    with torch.cuda.device(dev):
+        if assign is None:
+            from .metrics import lsap_device
+            assign = lsap_device(s, nvalid, want_assign=True)[1]
+        return _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine)
+
+
 def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False, bins=None,
-                    rank_meter=None):
+                    rank_meter=None, qap_meter=None, bits=None, refine=0):
     """scores: (B, N, N) fp32 raw scores on the GPU, or a MaskedTensor of them (its vertex counts are used unless nvalid is given).
     nvalid: (B,) vertex counts in [0, N]; labels: see metrics.py (None: the identity; they enter the accuracies, never the loss).
     live: the first `live` pairs count (None: all B) -- the others, the filling of a short last step, are ignored entirely.
@@ -369,9 +551,20 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
     and everything returned are the same).
     rank_meter: a RankMeter (with bins=: a BinnedRankMeter) -- the two launches of rank_scores follow on the same scores, labels,
     live and bins and add to it; their per-pair tensors come back under 'ranks'.  None: nothing of this is launched.
+    qap_meter: a QapMeter (with bins=: a BinnedQapMeter of the meter's K) with bits=(bits1, bits2), the two graphs as bit words --
+    the chain of decode_scores follows on the assignment of the solver launch made here (the solver does not run twice, so
+    hungarian=False is refused), with refine rounds of greedy refinement, on the same labels, live and bins; its per-pair tensors
+    come back under 'decode'.  0/1 graphs only (see decode_scores).  None: nothing of this is launched.
     Four launches, nothing is read back."""
     if isinstance(meter, BinnedEvalMeter) != (bins is not None):
         raise ValueError('evaluate_scores: bins= and a BinnedEvalMeter as meter go together')
+    if qap_meter is None:
+        if bits is not None or refine:
+            raise ValueError('evaluate_scores: bits= and refine= belong to a qap_meter')
+    else:
+        if not hungarian:
+            raise ValueError('evaluate_scores: a qap_meter decodes the matching of the Hungarian solver; it needs hungarian=True')
+        refine = _check_refine('evaluate_scores', refine)
     s, nvalid, labels, bins, B, N, live = _score_args('evaluate_scores', scores, nvalid, labels, live, bins)
     dev = s.device
     if meter is None:
@@ -380,6 +573,11 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
         _check_meter('evaluate_scores', 'meter', BinnedEvalMeter, meter, bins, dev)
     if rank_meter is not None:
         _check_meter('evaluate_scores', 'rank meter', BinnedRankMeter, rank_meter, bins, dev)
+    if qap_meter is not None:
+        _check_meter('evaluate_scores', 'qap meter', BinnedQapMeter, qap_meter, bins, dev)
+        if bins is not None and qap_meter.K != meter.K:
+            raise ValueError('evaluate_scores: the qap meter has %d records, the meter %d' % (qap_meter.K, meter.K))
+        bits = _bits_args('evaluate_scores', bits, B, N, dev)
     with torch.cuda.device(dev):
         i32 = dict(dtype=torch.int32, device=dev)
         cost = torch.empty(B, N, N, dtype=torch.float32, device=dev)
@@ -404,10 +602,13 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
         else:
             _lib.call('fgnn_eval_fold_bins', *rows, _lib.ptr(bins), meter.K, *sums)
         ranks = None if rank_meter is None else _rank_launches(s, nvalid, labels, bins, B, N, live, rank_meter)
+        decode = None if qap_meter is None else _decode_launches(*bits, assign, nvalid, labels, bins, B, N, live, qap_meter, refine)
     n = nvalid if nvalid is not None else torch.full((B,), N, **i32)
     out = {'ce': pair_ce, 'n': n, 'correct_max': pair_max, 'correct_lsap': correct, 'assign': assign, 'meter': meter}
     if ranks is not None:
         out['ranks'] = ranks
+    if decode is not None:
+        out['decode'] = decode
     return out
 
 

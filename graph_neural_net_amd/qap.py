@@ -91,20 +91,24 @@ def _on_host(adj1, n):
     return not adj1.is_cuda or n > _lib.FGNN_QAP_MAX_N
 
 
-def objective_bits(b1, b2, assign, nv):
-    """fgnn_qap_objective on bit words -> dict of (B,) int64 device tensors; never synchronises."""
+def objective_bits(b1, b2, assign, nv, raw=False):
+    """fgnn_qap_objective on bit words -> dict of (B,) int64 device tensors; never synchronises.  raw=True: the (4, B) int32 tensor
+    the kernel wrote (qap, planted, na, nb), as fgnn_qap_fold reads it."""
     B, N, _ = b1.shape
     a = assign.to(dtype=torch.int32).contiguous()
     out = torch.empty(4, B, dtype=torch.int32, device=b1.device)
     _lib.call('fgnn_qap_objective', _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(a), _lib.ptr(nv), B, N, _lib.ptr(out[0]), _lib.ptr(out[1]),
               _lib.ptr(out[2]), _lib.ptr(out[3]), _lib.stream_ptr())
+    if raw:
+        return out
     out = out.to(torch.int64)
     return {'qap': out[0], 'planted': out[1], 'na': out[2], 'nb': out[3]}
 
 
-def greedy_bits(b1, b2, assign, T, nv, labels=None):
+def greedy_bits(b1, b2, assign, T, nv, labels=None, raw=False):
     """fgnn_greedy_qap (fgnn_greedy_qap_labels with (B, N) int32 device labels) on bit words -> the dict of `greedy_qap`; never
-    synchronises."""
+    synchronises.  raw=True: the int32 tensors the launch sequence wrote, {'s_best2' (= 2 s_best), 'acc_best', 'T_best', 'perm'},
+    as fgnn_qap_fold reads them, without the launch for na / nb."""
     B, N, _ = b1.shape
     dev = b1.device
     a = assign.to(dtype=torch.int32).contiguous()
@@ -119,6 +123,8 @@ def greedy_bits(b1, b2, assign, T, nv, labels=None):
     else:
         _lib.call('fgnn_greedy_qap_labels', _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(a), _lib.ptr(labels), _lib.ptr(nv), B, N, int(T),
                   _lib.ptr(ws), nbytes, _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.ptr(perm), _lib.stream_ptr())
+    if raw:
+        return {'s_best2': out[0], 'acc_best': out[1], 'T_best': out[2], 'perm': perm}
     _lib.call('fgnn_qap_objective', _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(a), _lib.ptr(nv), B, N, None, None, _lib.ptr(sums[0]),
               _lib.ptr(sums[1]), _lib.stream_ptr())
     return {'s_best': out[0].to(torch.float64) / 2, 'na': sums[0].to(torch.float64) / 2, 'nb': sums[1].to(torch.float64) / 2,

@@ -549,19 +549,25 @@ class FgnnTrainer:
         scores, _ = eng.forward(self.params, x, nvalid=nv, total_nodes=1.0, defer_loss=False, loss_out=self._eval_loss, bits=bits)
         return scores
 
-    def _eval_tail(self, B, N, nvalid, x=None, bits=None, **options):
-        """The stacked batch -> its scores -> evaluation.evaluate_scores with the step's options"""
+    def _eval_tail(self, B, N, nvalid, x=None, bits=None, pair_bits=None, **options):
+        """The stacked batch -> its scores -> evaluation.evaluate_scores with the step's options (pair_bits: its bits=, the two
+        graphs' bit words for a qap_meter)"""
         from .evaluation import evaluate_scores
+        if pair_bits is not None:
+            options['bits'] = pair_bits
         return evaluate_scores(self._eval_forward(B, N, nvalid, x=x, bits=bits), nvalid=nvalid, **options)
 
     def eval_step_bits(self, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False,
-                       bins=None, rank_meter=None):
+                       bins=None, rank_meter=None, qap_meter=None, refine=0):
         """Forward-only evaluation of a batch handed over as train_step_bits takes it: the training engine's forward pass (a third of
         a step's work), then evaluation.evaluate_scores on its scores -- see there for labels, meter, live, hungarian,
-        loss_on_labels, bins, rank_meter and the returned per-pair device tensors.  Nothing is read back; parameters, gradients and optimizer state keep their bits."""
+        loss_on_labels, bins, rank_meter and the returned per-pair device tensors.  Nothing is read back; parameters, gradients and optimizer state keep their bits.
+        qap_meter (a QapMeter; with bins= a BinnedQapMeter), refine: the decode chain of evaluation.decode_scores on the bit words
+        handed in here and the solver's assignment (0/1 graphs only; needs hungarian=True).  None: nothing of it is launched."""
         B, N = self._bits_shape('eval_step_bits', bits1, bits2)
+        decode = {} if qap_meter is None and not refine else {'qap_meter': qap_meter, 'pair_bits': (bits1, bits2), 'refine': refine}
         return self._eval_tail(B, N, nvalid, bits=torch.cat([bits1, bits2]).contiguous(), labels=labels, meter=meter, live=live,
-                               hungarian=hungarian, loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter)
+                               hungarian=hungarian, loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter, **decode)
 
     def eval_step(self, x1, x2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False, bins=None,
                   rank_meter=None):
@@ -574,7 +580,7 @@ class FgnnTrainer:
                                hungarian=hungarian, loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter)
 
     def evaluate(self, generator, sampler, batch_size, epoch=0, hungarian=True, meter=None, permute=False, loss_on_labels=False,
-                 rank_meter=None):
+                 rank_meter=None, qap_meter=None, refine=0):
         """One pass over this rank's examples of `sampler` (sampler.EpochSampler; shuffle=False is the reference's validation
         loader): per step ``eval_step_bits(*generator.bits(index=sampler.batch_index(epoch, step, batch_size)))`` with the generator's
         vertex counts and, with permute=True, its planted labels.  Every example counts exactly once: the positions with which a
@@ -583,8 +589,12 @@ class FgnnTrainer:
         loss_on_labels=True (with permute=True): the record's loss is the cross-entropy against the planted labels -- the model's
         loss on those pairs, the one ReduceLROnPlateau should watch -- instead of the one against the identity.
         rank_meter: a RankMeter that takes the rank of every example's true match (the planted labels with permute=True) from the
-        same steps (evaluation.rank_scores; two more launches per step) and is summed over the ranks like the meter."""
-        from .evaluation import EvalMeter, RankMeter
+        same steps (evaluation.rank_scores; two more launches per step) and is summed over the ranks like the meter.
+        qap_meter: a QapMeter that takes the decode of every example from the same steps -- the accuracy of the Hungarian
+        matching, its QAP objective against the planted one and, with refine = T > 0, the same after T rounds of greedy refinement
+        (evaluation.decode_scores on the steps' bit words and the solver's assignment; the reference's all_acc_qap(val_loader, ...)
+        and all_greedy_losses_acc; 0/1 graphs only) -- and is summed over the ranks like the meter.  Needs hungarian=True."""
+        from .evaluation import EvalMeter, QapMeter, RankMeter
         B = int(batch_size)
         if meter is None:
             meter = EvalMeter(self.params.device)
@@ -592,24 +602,32 @@ class FgnnTrainer:
             raise ValueError('FgnnTrainer.evaluate: meter must be an EvalMeter or None (got %s)' % type(meter).__name__)
         if rank_meter is not None and not isinstance(rank_meter, RankMeter):
             raise ValueError('FgnnTrainer.evaluate: rank_meter must be a RankMeter or None (got %s)' % type(rank_meter).__name__)
+        if qap_meter is not None and not isinstance(qap_meter, QapMeter):
+            raise ValueError('FgnnTrainer.evaluate: qap_meter must be a QapMeter or None (got %s)' % type(qap_meter).__name__)
         def batches():
             for step in range(sampler.steps_per_epoch(B)):
                 live = sampler.live_count(step, B)
                 if live:        # (0: a rank past the end of the data in the last global step; its index is never made)
                     yield live, None, {'index': sampler.batch_index(epoch, step, B), 'permute': permute}
-        return self._eval_epoch(generator, batches(), meter, rank_meter, dp.world_size() > 1, hungarian, loss_on_labels)
+        return self._eval_epoch(generator, batches(), meter, rank_meter, dp.world_size() > 1, hungarian, loss_on_labels, qap_meter,
+                                refine)
 
-    def _eval_epoch(self, generator, batches, meter, rank_meter, reduce, hungarian, loss_on_labels):
+    def _eval_epoch(self, generator, batches, meter, rank_meter, reduce, hungarian, loss_on_labels, qap_meter=None, refine=0):
         """The loop of evaluate and noise_curve.  batches: per step that has a live pair (live, bins, the keyword arguments of
         generator.bits); reduce: sum the meters over the ranks at the end.  -> meter"""
+        if qap_meter is None and refine:
+            raise ValueError('FgnnTrainer: refine= belongs to a qap_meter')
+        decode = {} if qap_meter is None else {'qap_meter': qap_meter, 'refine': refine}
         for live, bins, bits_kw in batches:
             b1, b2, nv, *labels = generator.bits(**bits_kw)
             self.eval_step_bits(b1, b2, nvalid=nv, labels=labels[0] if labels else None, meter=meter, live=live, hungarian=hungarian,
-                                loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter)
+                                loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter, **decode)
         if reduce:
             meter.allreduce_()
             if rank_meter is not None:
                 rank_meter.allreduce_()
+            if qap_meter is not None:
+                qap_meter.allreduce_()
         return meter
 
     @staticmethod
@@ -623,7 +641,7 @@ class FgnnTrainer:
         return e % M, e // M, sampler.live_count(step, batch_size)
 
     def noise_curve(self, generator, noises, num_examples, batch_size, hungarian=True, permute=False, loss_on_labels=False,
-                    rank=None, world_size=None, meter=None, rank_meter=None):
+                    rank=None, world_size=None, meter=None, rank_meter=None, qap_meter=None, refine=0):
         """The reference's result figure (README.md, "Results": a trained model evaluated across noise levels; per level
         toolbox/metrics.py:144-166) in one pass: the first num_examples pairs of `generator` at each of the K = len(noises) noise
         levels -- the SAME parent graphs at every level, a paired design -- through full batches of mixed levels
@@ -638,8 +656,10 @@ class FgnnTrainer:
         fresh one whose values are the noises).  Reads nothing back: ``meter.result()``, K dicts with 'noise', 'loss', 'acc',
         'acc_max', is the one host read.  Returns the meter.
         rank_meter: a BinnedRankMeter of K records that takes the rank metrics of every level from the same steps; it is summed
-        over the ranks where the meter is."""
-        from .evaluation import BinnedEvalMeter, BinnedRankMeter
+        over the ranks where the meter is.
+        qap_meter: a BinnedQapMeter of K records that takes the decode of every level (see `evaluate`; refine: its rounds of
+        greedy refinement) from the same steps -- the QAP ratio across noise levels; it is summed over the ranks where the meter is."""
+        from .evaluation import BinnedEvalMeter, BinnedQapMeter, BinnedRankMeter
         from .sampler import EpochSampler
         levels = generator.levels(noises)
         K, M, B = len(levels), int(num_examples), int(batch_size)
@@ -651,6 +671,8 @@ class FgnnTrainer:
             raise ValueError('FgnnTrainer.noise_curve: meter must be a BinnedEvalMeter of %d records or None' % K)
         if rank_meter is not None and (not isinstance(rank_meter, BinnedRankMeter) or rank_meter.K != K):
             raise ValueError('FgnnTrainer.noise_curve: rank_meter must be a BinnedRankMeter of %d records or None' % K)
+        if qap_meter is not None and (not isinstance(qap_meter, BinnedQapMeter) or qap_meter.K != K):
+            raise ValueError('FgnnTrainer.noise_curve: qap_meter must be a BinnedQapMeter of %d records or None' % K)
         if world_size is None:
             world_size = dp.world_size()
         if rank is None:        # (this process's rank in the split of torch.distributed; any other split has to name it)
@@ -662,10 +684,10 @@ class FgnnTrainer:
                 if live:        # (0: a rank past the end of the examples in the last global step)
                     yield live, level, {'index': pair, 'levels': levels, 'level': level, 'permute': permute}
         return self._eval_epoch(generator, batches(), meter, rank_meter, dp.world_size() > 1 and sampler.world_size == dp.world_size(),
-                                hungarian, loss_on_labels)
+                                hungarian, loss_on_labels, qap_meter, refine)
 
     def fit(self, train_gen, train_sampler, val_gen, val_sampler, epochs, batch_size, scheduler=None, permute=False, exact_last=False,
-            rank_ks=None):
+            rank_ks=None, decode_refine=None):
         """The reference's training loop around its scheduler (models/trainers.py:92-104): per epoch train_epoch, evaluate, ONE host
         read (the validation record), scheduler.step(val_loss).  scheduler=None: optim.ReduceLROnPlateau with the reference's
         settings, driving self.opt.lr (the next step pushes a changed rate to the device).  Returns the per-epoch history: dicts
@@ -676,32 +698,46 @@ class FgnnTrainer:
         Hungarian accuracy is free of the identity tie bias.
         exact_last: handed to train_epoch.
         rank_ks: a tuple of thresholds (evaluation.RankMeter): every epoch's dict gains 'val_hits' ({k: Hits@k}) and 'val_mrr' of the
-        validation pairs, taken by the same validation steps and read with the validation record in the same single host copy."""
-        from .evaluation import EvalMeter, RankMeter, rank_result, read_records, record_result
+        validation pairs, taken by the same validation steps and read with the validation record in the same single host copy.
+        decode_refine: an integer T >= 0 (evaluation.QapMeter; 0/1 graphs only): every epoch's dict gains 'val_qap_ratio' (the
+        objective of the Hungarian matching over the planted one, summed over the validation pairs), 'val_recovered' (the fraction
+        of pairs whose matching reaches the planted objective) and, for T > 0, 'val_refined_acc' (the accuracy after T rounds of
+        greedy refinement), taken by the same validation steps and read in the same single host copy."""
+        from .evaluation import EvalMeter, QapMeter, RankMeter, _check_refine, qap_result, rank_result, read_records, record_result
         if scheduler is None:
             from .optim import ReduceLROnPlateau
             scheduler = ReduceLROnPlateau(self.opt)
         history = []
         rank_meter = None if rank_ks is None else RankMeter(self.params.device, ks=rank_ks)
-        own = None if rank_meter is None else EvalMeter(self.params.device)          # (read together with the rank meter)
+        if decode_refine is not None:
+            decode_refine = _check_refine('FgnnTrainer.fit', decode_refine)
+        qap_meter = None if decode_refine is None else QapMeter(self.params.device)
+        extra = [m for m in (rank_meter, qap_meter) if m is not None]
+        own = EvalMeter(self.params.device) if extra else None                       # (read together with the other meters)
+        decode = {} if qap_meter is None else {'qap_meter': qap_meter, 'refine': decode_refine}
         for epoch in range(int(epochs)):
-            if rank_meter is not None:
-                rank_meter.reset()
-                own.reset()
+            for m in extra + [own] * bool(extra):
+                m.reset()
             losses = self.train_epoch(train_gen, train_sampler, epoch, batch_size, permute=permute, exact_last=exact_last)
             meter = self.evaluate(val_gen, val_sampler, batch_size, epoch=epoch, meter=own, permute=permute, loss_on_labels=permute,
-                                  rank_meter=rank_meter)
-            if rank_meter is None:
+                                  rank_meter=rank_meter, **decode)
+            if not extra:
                 res = meter.result()
             else:
-                rec, rank_rec = read_records(meter, rank_meter)
-                res, rres = record_result(rec), rank_result(rank_rec)
+                rec, *others = read_records(meter, *extra)
+                res, others = record_result(rec), dict(zip(map(id, extra), others))
             scheduler.step(res['loss'])
             history.append({'epoch': epoch, 'train_losses': losses, 'val_loss': res['loss'], 'val_acc': res['acc'],
                             'val_acc_max': res['acc_max'], 'lr': self.opt.lr})
             if rank_meter is not None:
+                rres = rank_result(others[id(rank_meter)])
                 history[-1]['val_hits'] = {k: rres['hits@%d' % k] for k in rank_meter.ks}
                 history[-1]['val_mrr'] = rres['mrr']
+            if qap_meter is not None:
+                qres = qap_result(others[id(qap_meter)])
+                history[-1]['val_qap_ratio'], history[-1]['val_recovered'] = qres['qap_ratio'], qres['recovered']
+                if decode_refine > 0:
+                    history[-1]['val_refined_acc'] = qres['refined_acc']
         return history
 
     def train_step(self, x1, x2, nvalid=None, labels=None, weights=None, live=None):

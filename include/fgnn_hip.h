@@ -1074,6 +1074,56 @@ int fgnn_rank_fold(const int *rank, const int *nvalid /* optional */, int B, int
                    const int *bins /* optional */, int K, int *pair_hits /* optional */, double *pair_rr /* optional */,
                    long long *pair_rank_sum /* optional */, int *pair_targets /* optional */, fgnn_rank_record *records, void *stream);
 
+/* Decode epochs (csrc/qap_fold.hip): the reference's all_acc_qap(val_loader, ...) and all_greedy_losses_acc over a whole loader
+ * (toolbox/metrics.py:168-223), per epoch and per bin, from what the decode launches leave on the device.  0/1 graphs only: qap,
+ * planted and refined are the int32 values of the bit-word entry points above (the fp32 objectives of fgnn_qapw_* have no fold).
+ * fgnn_qap_fold, for the pairs b < live (0 <= live <= B; the others are ignored entirely); all inputs int32 on the device:
+ *   assign  (B, N): the matching, as fgnn_lsap_accuracy writes it;  qap, planted (B): as fgnn_qap_objective writes them (planted may
+ *   be the qap of the labels' matching instead);  perm (B, N) and refined (B): perm_best and s_best2 of fgnn_greedy_qap -- s_best2 =
+ *   trace(A P B P^T) = 2 s_best IS the qap of perm whenever A or B is symmetric, so it is stored as it comes and refined_sum /
+ *   planted_sum reads like qap_sum / planted_sum; the two are optional and go together;  labels (B, N) optional;  nvalid (B)
+ *   optional (n_b clamped to [0, N]).  target(b, i) = labels ? labels[b][i] : i, and none when that lies outside [0, n_b).
+ *   Per pair: pair_correct[b] = #{i < n_b : assign[b][i] == target(b, i)}, pair_refined_correct[b] the same of perm (0 without),
+ *   pair_ratio[b] (fp64) = (double)qap / (double)planted, the IEEE quotient, when qap >= 0 and planted > 0, else 0; each optional.
+ *   Lane l of a wave counts the rows l, l + 64, ...; the wave meets by a butterfly.  Then ONE workgroup adds the pairs to the
+ *   record in pair order, one pair at a time:
+ *     nodes += n_b, pairs += 1, correct += pair_correct, exact += [pair_correct == n_b], refined_correct += pair_refined_correct;
+ *     a pair with qap < 0 (the solver found no finite matching) then adds unmatched += 1 and nothing else; every other pair
+ *     qap_sum += qap, planted_sum += planted, recovered += [qap >= planted], with planted > 0: ratio_sum += pair_ratio,
+ *     ratio_pairs += 1, and with perm: refined_sum += refined, improved += [refined > qap];
+ *   steps += 1 per call that added a pair.  Without perm the three refinement fields are not touched.  A record that took no pair
+ *   is not written.  No floating-point atomics, a fixed order: a record is bit-identical from run to run and does not depend on
+ *   how its examples were cut into calls.  The record lives in device memory, zero-initialised (and reset) by its owner.
+ * fgnn_qap_fold_bins: the same kernel with K contiguous records (1 <= K <= FGNN_MAX_LEVELS): record k receives the pairs b < live
+ *   with bin[b] == k (int32[B] on the device) in ascending b and ends with the bytes fgnn_qap_fold leaves after folding just those
+ *   pairs into the same starting record; a pair whose bin lies outside [0, K) is added nowhere; the per-pair outputs are those of
+ *   fgnn_qap_fold.
+ * Both are single launches on `stream`: capturable, no allocation, no host copy, no synchronisation. */
+typedef struct {
+    double ratio_sum;           /* sum of qap / planted over the matched pairs with planted > 0 */
+    long long ratio_pairs;      /* how many pairs entered ratio_sum */
+    long long qap_sum;          /* sum of qap over the matched pairs */
+    long long planted_sum;      /* sum of planted over the matched pairs */
+    long long correct;          /* rows with assign == target */
+    long long refined_sum;      /* sum of refined (s_best2: the unit of qap) over the matched pairs */
+    long long refined_correct;  /* rows with perm == target */
+    long long recovered;        /* matched pairs with qap >= planted */
+    long long exact;            /* pairs with every row correct */
+    long long improved;         /* matched pairs with refined > qap */
+    long long unmatched;        /* pairs with qap < 0 */
+    long long nodes;            /* sum of n_b */
+    long long pairs;            /* live pairs folded */
+    long long steps;            /* fold calls that added a pair */
+} fgnn_qap_record;
+int fgnn_qap_fold(const int *assign, const int *perm /* optional */, const int *labels /* optional */, const int *qap, const int *planted,
+                  const int *refined /* with perm */, const int *nvalid /* optional */, int B, int N, int live,
+                  int *pair_correct /* optional */, int *pair_refined_correct /* optional */, double *pair_ratio /* optional */,
+                  fgnn_qap_record *meter, void *stream);
+int fgnn_qap_fold_bins(const int *assign, const int *perm /* optional */, const int *labels /* optional */, const int *qap,
+                       const int *planted, const int *refined /* with perm */, const int *nvalid /* optional */, int B, int N, int live,
+                       const int *bin /* (B) */, int K, int *pair_correct /* optional */, int *pair_refined_correct /* optional */,
+                       double *pair_ratio /* optional */, fgnn_qap_record *records /* K records */, void *stream);
+
 /* ---- test-only entry points (never on the product path; tests/ and tools/ call them) ---------------------------------------
  * fgnn_debug_mlp_fwd_masks / fgnn_debug_mlp_fwd_x3_masks: fgnn_mlp_fwd / fgnn_mlp_fwd_x3 once more -- the same tile code, the same
  * outputs, bit for bit -- that ALSO exports the ReLU decisions of the conv chain (models/layers.py:129-130), the input of the
