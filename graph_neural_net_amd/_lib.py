@@ -306,6 +306,7 @@ _SIGNATURES = {
     'fgnn_count_matches': [_VP, _VP, _VP, _I, _I, _VP, _VP],
     'fgnn_accuracy_max_labels': [_VP, _VP, _VP, _I, _I, _VP, _VP],
     'fgnn_spectral_features': [_VP, _VP, _I, _I, _I, _VP, _I, _VP],
+    'fgnn_spectral_slab16': [_VP, _VP, _I, _I, _I, _I, _I, _VP, _LL, _VP],
     'fgnn_eval_pairs': [_VP, _VP, _VP, _I, _I, _VP, _LL, _I, _VP, _VP, _VP],
     'fgnn_eval_pairs_labels': [_VP, _VP, _VP, _I, _I, _VP, _LL, _I, _VP, _VP, _VP],
     'fgnn_eval_fold': [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP],

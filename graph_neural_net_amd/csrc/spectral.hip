@@ -15,63 +15,18 @@
 // panel is written from the accumulators after a barrier, so ONE panel in LDS is enough (the accumulators are the second buffer):
 // 42 KB at N = 256.  The D fragment has the column on the lane, so each store instruction writes two 128-byte row segments.
 // Loads and stores go through per-graph buffer descriptors: lanes outside the tensors take an out-of-range offset.
-#include "fgnn_common.h"
+#include "fgnn_spectral.h"      // the panel code, shared with spectral_slab.hip
 
 namespace {
-
-constexpr int SP_THREADS = 256;            // 4 waves; thread t stages row t of W (N <= 256)
-constexpr int SP_ROWS = 32;                // rows of a panel
-
-// the bits of word w of a row that lie inside the n x n corner
-DEVI unsigned corner_mask(int w, int n) {
-    const int lo = 32 * w;
-    return n >= lo + 32 ? 0xffffffffu : (n > lo ? (1u << (n - lo)) - 1u : 0u);
-}
-DEVI rsrc_t make_rsrc(const void *p, long long bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
-
-// one power of one column block: acc += panel (32 x K, scaled by s_k) @ W[0 .. K)[32 jb .. 32 jb + 31]
-template <int NW, int P>
-DEVI void panel_times_w(f32x16 &acc, const float *panel, const unsigned *wl, int K, int jb, int lane) {
-    const int j = lane & 31, h = lane >> 5;
-    const float *a = panel + j * P + h;
-    const unsigned *w = wl + h * NW + jb;
-    for (int k0 = 0; k0 < K; k0 += 32) {        // K is a multiple of 32
-#pragma unroll
-        for (int k = k0; k < k0 + 32; k += 2) acc = mfma32(a[k], (float)((w[k * NW] >> j) & 1u), acc);
-    }
-}
-// the same for two column blocks sharing the A operand
-template <int NW, int P>
-DEVI void panel_times_w2(f32x16 &acc0, f32x16 &acc1, const float *panel, const unsigned *wl, int K, int jb0, int jb1, int lane) {
-    const int j = lane & 31, h = lane >> 5;
-    const float *a = panel + j * P + h;
-    const unsigned *w = wl + h * NW;
-    for (int k0 = 0; k0 < K; k0 += 32) {
-#pragma unroll
-        for (int k = k0; k < k0 + 32; k += 2) {
-            const float av = a[k];
-            acc0 = mfma32(av, (float)((w[k * NW + jb0] >> j) & 1u), acc0);
-            acc1 = mfma32(av, (float)((w[k * NW + jb1] >> j) & 1u), acc1);
-        }
-    }
-}
 
 // grid: G * ceil(Nout / 32) workgroups, workgroup b = (graph b / panels, panel b % panels).  NW = words per staged row (N <= 32 NW).
 template <int NW>
 __global__ __launch_bounds__(SP_THREADS) void spectral_kernel(const unsigned *bits, const int *nvalid, int G, int N, int n_powers,
                                                               float *out, int Nout, int panels) {
-    constexpr int NP = 32 * NW, P = NP + 1, NACC = NW > 4 ? 2 : 1;       // P odd: the 32 rows a half-wave reads at one k are 32 banks
-    __shared__ unsigned wl[NP * NW];           // rows of W, zero outside the corner
-    __shared__ float sl[NP];                   // s_k, zero for k >= n and for isolated vertices
-    __shared__ float panel[SP_ROWS * P];       // F_p[i0 + i][k] s_k
+    __shared__ SpLds<NW> L;
     const int g = blockIdx.x / panels, i0 = (blockIdx.x - g * panels) * SP_ROWS, tid = threadIdx.x;
-    const int wv = tid >> 6, lane = tid & 63, j = lane & 31, h = lane >> 5;
-    const int W = (N + 31) >> 5;
-    const rsrc_t nv_r = make_rsrc(nvalid, nvalid ? (long long)G * 4 : 0);
-    const int nv = __builtin_amdgcn_raw_buffer_load_b32(nv_r, 0, g * 4, 0);
-    const int n = nvalid ? min(max(nv, 0), N) : N;
+    const int lane = tid & 63, j = lane & 31, h = lane >> 5;
+    const int n = sp_nvalid(nvalid, G, g, N);
     const long long plane = (long long)Nout * Nout;
     const rsrc_t out_r = make_rsrc(out + (long long)g * n_powers * plane, (long long)n_powers * plane * 4);
     const int plane4 = (int)plane * 4;
@@ -83,78 +38,19 @@ __global__ __launch_bounds__(SP_THREADS) void spectral_kernel(const unsigned *bi
                 __builtin_amdgcn_raw_buffer_store_b32(0u, out_r, (i0 + r < Nout) ? off + (i0 + r) * Nout * 4 : OOB_OFF, p * plane4, 0);
         return;
     }
-
-    // ---- stage W (masked to the corner) and s
-    {
-        const rsrc_t bits_r = make_rsrc(bits + (long long)g * N * W, (long long)N * W * 4);
-        int deg = 0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            const unsigned v = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(bits_r, (tid < N && w < W) ? (tid * W + w) * 4 : OOB_OFF, 0, 0)
-                               & (tid < n ? corner_mask(w, n) : 0u);
-            if (tid < NP) wl[tid * NW + w] = v;
-            deg += __popc(v);
-        }
-        if (tid < NP) sl[tid] = deg > 0 ? 1.0f / __builtin_sqrtf((float)deg) : 0.0f;
-    }
-    __syncthreads();
-
-    const int nb = (n + 31) >> 5, K = 32 * nb;  // live column blocks; the contraction runs over whole words (zeros past n)
-    int jb[NACC];
-    bool live[NACC];
-    float sj[NACC];
-    f32x16 acc[NACC];
-#pragma unroll
-    for (int a = 0; a < NACC; ++a) {
-        jb[a] = wv + 4 * a;
-        live[a] = jb[a] < nb;                   // uniform per wave
-        const int jc = live[a] ? jb[a] : 0;
-        sj[a] = live[a] ? sl[32 * jc + j] : 0.0f;
-        // power 1 before its column scale: s_i w_ij, in the D layout (register r of half h = row (r & 3) + 8 (r >> 2) + 4 h)
+    sp_stage<NW>(L, bits, g, N, n, tid);
+    // F_p -> HBM (column blocks up to Nout; zeros where the block is past the corner)
+    sp_powers<NW>(L, n, i0, n_powers, tid, [&](int p, int jb, const f32x16 &f) {
+        const int col = 32 * jb + j;
+        const int off = col < Nout ? col * 4 : OOB_OFF;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int i = i0 + ch_of(r, h);
-            const unsigned bit = (wl[i * NW + jc] >> j) & 1u;
-            acc[a][r] = (live[a] && bit) ? sl[i] : 0.0f;
+            const float v = f[r];               // (a copy: __builtin_bit_cast applied to the vector element itself reads element 0)
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), out_r, i < Nout ? off + i * Nout * 4 : OOB_OFF,
+                                                  p * plane4, 0);
         }
-    }
-
-    for (int p = 0; p < n_powers; ++p) {
-        if (p > 0) {
-            if (NACC == 2 && live[NACC - 1]) {
-                panel_times_w2<NW, P>(acc[0], acc[NACC - 1], panel, wl, K, jb[0], jb[NACC - 1], lane);
-            } else if (live[0]) {
-                panel_times_w<NW, P>(acc[0], panel, wl, K, jb[0], lane);
-            }
-        }
-        // F_p = acc s_j -> HBM (column blocks up to Nout; zeros where the block is past the corner); acc <- F_p s_j, the next A operand
-#pragma unroll
-        for (int a = 0; a < NACC; ++a) {
-            const int col = 32 * jb[a] + j;
-            const int off = col < Nout ? col * 4 : OOB_OFF;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int i = i0 + ch_of(r, h);
-                const float v = acc[a][r] * sj[a];
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), out_r, i < Nout ? off + i * Nout * 4 : OOB_OFF,
-                                                      p * plane4, 0);
-                acc[a][r] = v * sj[a];
-            }
-        }
-        if (p + 1 == n_powers) break;
-        __syncthreads();                        // every wave has read the panel of this power
-#pragma unroll
-        for (int a = 0; a < NACC; ++a) {
-            if (live[a]) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    panel[ch_of(r, h) * P + 32 * jb[a] + j] = acc[a][r];
-                    acc[a][r] = 0.0f;
-                }
-            }
-        }
-        __syncthreads();
-    }
+    });
 }
 
 template <int NW>

@@ -213,6 +213,8 @@ class FgnnEngine(EngineBase):
                          if self.ranges is not None and self.MM_ORDER and 64 < N <= 256 else None)
         self.x = None
         self.xdeg = None          # row sums of a bit-packed adjacency input (embed(..., bits=...))
+        self.xspec = {}           # n_powers -> ((G, n_powers, N, N) spectral features of embed(..., spectral=...), their zero-padded
+                                  # (G, 32, N, N) image on the 32-channel layout or None): persistent, allocated at first use
         # LDS operand images of every MLP launch, re-packed once per step (fgnn_pack_operands)
         self._packs = {}
         self._pack_entry = 'fgnn_pack_x3_operands' if self.x3 else 'fgnn_pack_operands'      # EngineBase.pack_operands
@@ -313,11 +315,23 @@ class FgnnEngine(EngineBase):
             args.xdeg = self.xdeg.data_ptr()
 
     # ------------------------------------------------------------------ forward
-    def embed(self, params, x, nvalid=None, bits=None, pack=True):
+    def _check_spectral_channels(self, n_powers):
+        c0 = self.layout.c0
+        if n_powers > c0 or (n_powers != c0 and c0 != 32):
+            raise RuntimeError('FgnnEngine.embed: spectral= with %d powers does not fit original_features_num = %d: the fp32 kernels take '
+                               'their input at the layout\'s width -- a 2-channel layout takes exactly 2 powers, the 32-channel layout '
+                               'any number (zero-padded)' % (n_powers, c0))
+
+    def embed(self, params, x=None, nvalid=None, bits=None, pack=True, spectral=None):
         """x: (G, c0, N, N) contiguous device tensor -- or bits: (G, N, ceil(N/32)) int32 words of the bit-packed
         adjacency (bit j of row i = W[i][j], the format of inputs.expand_adjacency / synthetic.pack_adjacency): the
         (2, N, N) representation of loaders/data_generator.py:118-125 is then built inside block 1's kernels and never
         exists in HBM.  Fills self.E / self.idx.
+        spectral: (bits, n_powers) -- the same stacked words as the source of the spectral features L, ..., L^n_powers
+        : one fgnn_spectral_features launch writes them into a persistent (G, n_powers, N, N) buffer of the engine, and the step
+        goes on exactly as if that buffer had been handed in as x (n_powers = layout.c0).  The fp32 kernels read their input at the
+        layout's width, so on the 32-channel layout the powers are then copied (one launch) into the first channels of a persistent
+        zero-filled (G, 32, N, N) buffer, the input a narrow model runs zero-padded on.  Replaces x and bits=; generic block 1 only.
         LIFETIME: x / bits, and an nvalid handed over as a contiguous int32 device tensor of G entries, are read IN PLACE -- by this
         forward AND by the backward that follows it (block 1's backward re-reads the input; every backward kernel reads nvalid): the
         caller must leave them untouched until backward() has been issued (stream order is enough).  Any other nvalid (host list,
@@ -328,7 +342,21 @@ class FgnnEngine(EngineBase):
         if self.ranges is not None:
             _lib.call('fgnn_ragged_tile_ranges_order', _lib.ptr(self.nvalid), self.G, self.N, _lib.ptr(self.ranges),
                       _lib.ptr(self.mm_order) if self.mm_order is not None else None, st, tag='fgnn_ragged_tile_ranges')
-        if bits is not None:
+        if spectral is not None:
+            sbits, n_powers = self._check_spectral(x, bits, spectral)
+            buf = self.xspec.get(n_powers)      # persistent per n_powers: a captured step keeps its addresses
+            if buf is None:
+                f32 = dict(dtype=torch.float32, device=self.device)
+                # the 32-channel layout: the fp32 kernels read a 32-channel slab, so the powers are copied into the first channels of
+                # a zero-filled one (the input a narrow model runs zero-padded on); its other channels are never written again
+                buf = self.xspec[n_powers] = (torch.empty(self.G, n_powers, self.N, self.N, **f32),
+                                              torch.zeros(self.G, L.c0, self.N, self.N, **f32) if n_powers < L.c0 else None)
+            feat, padded = buf
+            _lib.call('fgnn_spectral_features', _lib.ptr(sbits), self._nv(), self.G, self.N, n_powers, _lib.ptr(feat), self.N, st)
+            if padded is not None:
+                padded[:, :n_powers].copy_(feat)
+            self.x, self.xbits = (feat if padded is None else padded), None
+        elif bits is not None:
             if x is not None or L.c0 != 2 or L.depth != 3:
                 raise RuntimeError('FgnnEngine.embed: bits= replaces x and needs original_features_num = 2, depth_of_mlp = 3')
             self._check_bits(bits)

@@ -115,17 +115,27 @@ class FgnnEngineBF16(EngineBase):
             self._gn_finalize(params, k, js)
 
     # ------------------------------------------------------------------ forward
-    def embed(self, params, x, nvalid=None, bits=None):
+    def _check_spectral_channels(self, n_powers):
+        if n_powers > self.layout.c0:
+            raise RuntimeError('FgnnEngineBF16.embed: spectral= with %d powers needs an input slab of at least that many channels; this '
+                               'layout has original_features_num = %d (use the 32-channel layout)' % (n_powers, self.layout.c0))
+
+    def embed(self, params, x=None, nvalid=None, bits=None, spectral=None):
         """x: (G, c, N, N) contiguous fp32 device tensor with c <= layout.c0 (2: 0/1 adjacency + degrees, exact in bf16 for N <= 256;
         32-channel layouts take any 1..32 channels, e.g. the four spectral ones: one launch, fgnn_to_bf16_pad, rounds them into the
         32-channel slab and writes the missing channels as zeros -- no fp32 staging buffer) -- or bits:
         (G, N, ceil(N/32)) int32 words of the bit-packed adjacency (the input form of FgnnEngine.embed(bits=...)); with
-        block1='structured' block 1 then runs on the class tables (csrc/block1_struct.hip).
+        block1='structured' block 1 then runs on the class tables (csrc/block1_struct.hip) -- or spectral: (bits, n_powers), the same
+        stacked words read as the source of the spectral features L, ..., L^n_powers (n_powers <= layout.c0): ONE launch,
+        fgnn_spectral_slab16, writes the whole input slab (the fp32 features never exist in HBM) and the step goes on as after
+        fgnn_to_bf16_pad; its bytes are those of embed(x=spectral_features(bits, nvalid, n_powers)).  Generic block 1 only.
         LIFETIME: as FgnnEngine.embed -- bits and an int32 device nvalid of G entries are read in place by this forward and by the
         backward after it; leave them untouched until backward() has been issued."""
         L = self.layout
         self._adopt_nvalid(nvalid)
-        if bits is not None:
+        if spectral is not None:
+            sbits, n_powers = self._check_spectral(x, bits, spectral)
+        elif bits is not None:
             if x is not None:
                 raise RuntimeError('FgnnEngineBF16.embed: pass x or bits, not both')
             self._check_bits(bits)
@@ -139,7 +149,10 @@ class FgnnEngineBF16(EngineBase):
         st = _lib.stream_ptr()
         if self.ranges is not None:
             _lib.call('fgnn_ragged_tile_ranges16', _lib.ptr(self.nvalid), self.G, self.N, self.ldr, _lib.ptr(self.ranges), st)
-        if bits is None and x.shape[1] == L.c0 == 2:
+        if spectral is not None:
+            _lib.call('fgnn_spectral_slab16', _lib.ptr(sbits), self._nv(), self.G, self.N, n_powers, L.c0, self.ldr, _lib.ptr(self.x16),
+                      self.ldp, st)
+        elif bits is None and x.shape[1] == L.c0 == 2:
             _lib.call('fgnn_to_bf16', _lib.ptr(x), self._nv(), self.G, 2, self.N, self.ldr, _lib.ptr(self.x16),
                       2 * self.ldp, self.ldp, st)
         elif bits is None:      # fewer channels than the slab, or the 32-channel slab: convert and zero-fill in one pass

@@ -134,6 +134,28 @@ class EngineBase:
             raise RuntimeError('%s.embed: expected contiguous 32-bit words %s on the GPU, got %s %s'
                                % (type(self).__name__, (self.G, self.N, words), tuple(bits.shape), bits.dtype))
 
+    def _check_spectral(self, x, bits, spectral):
+        """spectral=(bits, n_powers) of embed / forward / step: the stacked (G, N, ceil(N/32)) bit words whose spectral features
+        L, L^2, ..., L^n_powers are block 1's input (csrc/spectral.hip) -> (bits, n_powers), checked.  Replaces x and bits=."""
+        who = type(self).__name__
+        if x is not None or bits is not None:
+            raise RuntimeError('%s.embed: pass x, bits= or spectral=, not two of them' % who)
+        try:
+            sbits, n_powers = spectral
+            n_powers = int(n_powers)
+        except (TypeError, ValueError):
+            raise RuntimeError('%s.embed: spectral= takes (bits, n_powers), got %r' % (who, spectral)) from None
+        if self.struct1:
+            raise RuntimeError("%s.embed: spectral= runs the generic block 1; this engine was built with block1='structured', which "
+                               'serves the 2-channel tensor representation of bits= only' % who)
+        if not 1 <= n_powers <= _lib.FGNN_SPECTRAL_MAX_POWERS:
+            raise RuntimeError('%s.embed: spectral= takes 1 to %d powers, got %d' % (who, _lib.FGNN_SPECTRAL_MAX_POWERS, n_powers))
+        if self.N > _lib.FGNN_SPECTRAL_MAX_N:
+            raise RuntimeError('%s.embed: spectral= handles N <= %d (got %d)' % (who, _lib.FGNN_SPECTRAL_MAX_N, self.N))
+        self._check_spectral_channels(n_powers)
+        self._check_bits(sbits)
+        return sbits, n_powers
+
     # ------------------------------------------------------------------ block 1 on its structured input (csrc/block1_struct.hip)
     def _struct_ws(self):
         if self._struct is None:
@@ -148,8 +170,8 @@ class EngineBase:
         return ((C.c_void_p * 3)(*[self._w(params, o) for o in rec['w']]), (C.c_void_p * 3)(*[self._w(params, o) for o in rec['b']]))
 
     # ------------------------------------------------------------------ forward
-    def forward(self, params, x, nvalid=None, total_nodes=None, defer_loss=False, loss_out=None, bits=None, labels=None, weights=None,
-                **embed_kw):
+    def forward(self, params, x=None, nvalid=None, total_nodes=None, defer_loss=False, loss_out=None, bits=None, labels=None, weights=None,
+                spectral=None, **embed_kw):
         """Siamese forward on the stacked batch x = cat(x1, x2) (or its bit-packed adjacency, see embed): returns
         (scores, loss).
         labels: (B, N) integer tensor, labels[b, i] = the column row i of pair b should match (planted.py; -1 in the padding):
@@ -162,6 +184,8 @@ class EngineBase:
         select: NaN or inf in its scores reach neither loss nor gradient.  The weights carry the reduction, so total_nodes must be
         left out or 1: the normaliser D of a reduction (fgnn_pair_weights) is applied by the caller (FgnnTrainer: as Adam's gradient
         scale, after the all-reduce).  None: the launches of the unweighted step, unchanged.
+        spectral: (bits, n_powers) -- block 1's input is the spectral features L, ..., L^n_powers of the stacked bit words, computed
+        by the engine (see embed); replaces x and bits=.  None: the launches of a forward without it, unchanged.
         defer_loss: leave the final sum of the per-pair losses to the gradient-finalize launch of the
         following backward() (one launch less per training step); `loss` is valid after that.
         embed_kw: keywords of the engine's own embed()."""
@@ -172,6 +196,8 @@ class EngineBase:
                 raise ValueError('%s.forward: weights carry the reduction; total_nodes must be None or 1 (got %r)'
                                  % (type(self).__name__, total_nodes))
             total_nodes = 1.0
+        if spectral is not None:
+            embed_kw['spectral'] = spectral
         self.embed(params, x, nvalid, bits=bits, **embed_kw)
         B, N = self.B, self.N
         st = _lib.stream_ptr()
@@ -298,10 +324,13 @@ class EngineBase:
                       self.G if graphs is None else graphs, 32, st)
         return grads
 
-    def step(self, params, grads, x, nvalid=None, total_nodes=None, loss_out=None, bits=None, labels=None, weights=None):
-        """One training step's model work: forward + loss + backward.  (x / bits / an int32 device nvalid / int32 device labels /
-        fp32 device weights are read in place by both passes: see embed() and forward().)"""
+    def step(self, params, grads, x=None, nvalid=None, total_nodes=None, loss_out=None, bits=None, labels=None, weights=None,
+             spectral=None):
+        """One training step's model work: forward + loss + backward.  (x / bits / the bit words of spectral= / an int32 device nvalid /
+        int32 device labels / fp32 device weights are read in place by both passes: see embed() and forward().)"""
         wkw = {} if weights is None else {'weights': weights}
+        if spectral is not None:
+            wkw['spectral'] = spectral
         scores, loss = self.forward(params, x, nvalid, total_nodes, defer_loss=True, loss_out=loss_out, bits=bits, labels=labels, **wkw)
         self.backward(params, grads)
         return scores, loss

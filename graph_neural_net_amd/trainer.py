@@ -331,16 +331,19 @@ class FgnnTrainer:
         return self._reduce_and_update(), scores
 
     # ------------------------------------------------------------------ captured constant-shape step
-    def _captured_step(self, x1, x2, bits=False, labels=None, weights=None, live=None, weighted=False):
+    def _captured_step(self, x1, x2, bits=False, labels=None, weights=None, live=None, weighted=False, spectral=None):
         """bits: x1, x2 are (B, N, ceil(N / 32)) int32 words of bit-packed adjacency instead of (B, c0, N, N) tensors.
+        spectral: None, or n_powers -- x1, x2 are bit words as well, and the step takes their spectral features as its input
+        (engine.step(spectral=...)): a graph of its own, key (B, N, 'spectral', n_powers); its static input is the stacked words, as
+        for 'bits', and the feature launch rides inside the graph.
         labels: (B, N) int32 device tensor or None.  A labelled step is a graph of its own (the key says which): its labels live in
         a static buffer that every call copies into, like xs, so one trainer can hold and alternate both.
         weighted (weights: (B,) fp32 device tensor or None; live: int, 1-element device tensor or None): the weighted step is a graph
         of its own as well (key: 'weights').  It holds the fgnn_pair_weights launch; the caller's weights (None: ones) and live
         (None: B) live in static device buffers, so ONE graph serves every step of an epoch, the short last one included."""
-        B, N = x1.shape[0], x1.shape[-2 if bits else -1]
+        B, N = x1.shape[0], x1.shape[-2 if (bits or spectral is not None) else -1]
         world = dp.world_size()
-        key = (B, N, 'bits') if bits else (B, N)
+        key = (B, N, 'spectral', spectral) if spectral is not None else (B, N, 'bits') if bits else (B, N)
         if labels is not None:
             key = key + ('labels',)
         if weighted:
@@ -357,7 +360,10 @@ class FgnnTrainer:
                 wst = {'user': torch.ones(B, dtype=torch.float32, device=dev), 'live': torch.full((1,), B, dtype=torch.int32, device=dev),
                        'w': torch.zeros(B, dtype=torch.float32, device=dev)}
                 lkw['weights'] = wst['w']
-            model = ((lambda: eng.step(self.params, self.grads, None, total_nodes=1.0, loss_out=self._loss_sum, bits=xs, **lkw)) if bits else
+            if spectral is not None:
+                lkw['spectral'] = (xs, spectral)
+            model = ((lambda: eng.step(self.params, self.grads, None, total_nodes=1.0, loss_out=self._loss_sum, **lkw)) if spectral is not None else
+                     (lambda: eng.step(self.params, self.grads, None, total_nodes=1.0, loss_out=self._loss_sum, bits=xs, **lkw)) if bits else
                      (lambda: eng.step(self.params, self.grads, xs, total_nodes=1.0, loss_out=self._loss_sum, **lkw)))
             if weighted:
                 def step():
@@ -496,28 +502,68 @@ class FgnnTrainer:
         tensor representation of loaders/data_generator.py:118-125 is built inside block 1's kernels, and with block1='structured'
         block 1 runs on the class tables of csrc/block1_struct.hip.  nvalid: (B,) int32 for ragged batches (padded to N).
         labels, weights, live: see train_step."""
-        B, N = self._bits_shape('train_step_bits', bits1, bits2)
+        return self._train_step_words('train_step_bits', bits1, bits2, nvalid, labels, weights, live, None)
+
+    def _check_features(self, who, n_powers):
+        """The layout checks of the spectral steps and loops (before any launch) -> n_powers"""
+        from . import _lib
+        n_powers = int(n_powers)
+        if not 1 <= n_powers <= _lib.FGNN_SPECTRAL_MAX_POWERS:
+            raise ValueError('FgnnTrainer.%s: n_powers must be in [1, %d], got %d' % (who, _lib.FGNN_SPECTRAL_MAX_POWERS, n_powers))
+        c0 = self.layout.c0
+        if n_powers > c0 or (self.precision == 'fp32' and n_powers != c0 and c0 != 32):
+            raise RuntimeError('FgnnTrainer.%s: %d spectral channels do not fit this layout (original_features_num = %d: n_powers <= '
+                               'it; an fp32 2-channel layout takes exactly 2)' % (who, n_powers, c0))
+        if self.block1 == 'structured':
+            raise RuntimeError("FgnnTrainer.%s: spectral features run the generic block 1; this trainer was built with "
+                               "block1='structured' (the 2-channel tensor representation only)" % who)
+        return n_powers
+
+    def train_step_spectral(self, bits1, bits2, nvalid=None, n_powers=4, labels=None, weights=None, live=None):
+        """The twin of train_step_bits for the reference's second dataset class (QAP_spectralGenerator): the same bit words, but the
+        step's input is their spectral features L, L^2, ..., L^n_powers (spectral.spectral_features), computed by the engine
+        (engine.step(spectral=...)) -- bf16: one fgnn_spectral_slab16 launch straight into block 1's input slab; fp32: one
+        fgnn_spectral_features launch into the engine's own buffer.  Bit-identical to train_step on the features of
+        ``generator.spectral`` (fp32 on the 32-channel layout: zero-padded to its 32 channels, the input a narrow model runs on).  The
+        layout needs original_features_num >= n_powers (an fp32 2-channel layout: exactly 2 powers) and the generic block 1.
+        With capture=True the step is a graph of its own, keyed (B, N, 'spectral', n_powers) (+ 'labels' / 'weights'): its static
+        input is the stacked words, the feature launch rides inside the graph.  nvalid, labels, weights, live: see train_step_bits."""
+        n_powers = self._check_features('train_step_spectral', n_powers)
+        return self._train_step_words('train_step_spectral', bits1, bits2, nvalid, labels, weights, live, n_powers)
+
+    def _train_step_words(self, who, bits1, bits2, nvalid, labels, weights, live, n_powers):
+        """train_step_bits (n_powers None) / train_step_spectral: one body, the engine keyword differs"""
+        B, N = self._bits_shape(who, bits1, bits2)
         labels = self._labels(labels, B, N)
         weighted = self._weighted(weights, live)
         if self.capture and nvalid is None:
             if weighted:
                 return self._captured_step(bits1, bits2, bits=True, labels=labels, weights=self._user_weights(weights, B), live=live,
-                                           weighted=True)
-            return self._captured_step(bits1, bits2, bits=True, labels=labels)
+                                           weighted=True, spectral=n_powers)
+            return self._captured_step(bits1, bits2, bits=True, labels=labels, spectral=n_powers)
         eng = self._engine(2 * B, N, nvalid is not None)
         b = torch.cat([bits1, bits2]).contiguous()
         nv = None if nvalid is None else torch.cat([nvalid, nvalid]).to(torch.int32)
         lkw = {} if labels is None else {'labels': labels}
+        lkw.update({'bits': b} if n_powers is None else {'spectral': (b, n_powers)})
         if weighted:
             lkw['weights'] = self._pair_weights(B, N, nvalid, live, weights)        # (self._nodes <- D)
         elif nvalid is None:
             self._nodes.fill_(float(B * N))
         else:
             self._nodes.copy_(nvalid.sum().to(torch.float32).reshape(1))
-        scores, _ = eng.step(self.params, self.grads, None, nvalid=nv, total_nodes=1.0, loss_out=self._loss_sum, bits=b, **lkw)
+        scores, _ = eng.step(self.params, self.grads, None, nvalid=nv, total_nodes=1.0, loss_out=self._loss_sum, **lkw)
         return self._reduce_and_update(), scores
 
-    def train_epoch(self, generator, sampler, epoch, batch_size, permute=False, exact_last=False):
+    def _features(self, who, features, n_powers):
+        """features= / n_powers= of the epoch loops -> None (the tensor representation: the bits steps) or the checked n_powers"""
+        if features is None:
+            return None
+        if features != 'spectral':
+            raise ValueError("FgnnTrainer.%s: features must be None or 'spectral' (got %r)" % (who, features))
+        return self._check_features(who, n_powers)
+
+    def train_epoch(self, generator, sampler, epoch, batch_size, permute=False, exact_last=False, features=None, n_powers=4):
         """One epoch over a fixed dataset of on-device pairs, in the sampler's order (the reference's shuffled DataLoader over
         num_examples_train pairs): per step ``train_step_bits(*generator.bits(index=sampler.batch_index(epoch, step, batch_size)))``.
         generator: pairgen.PairGenerator or pairstore.PairStore; sampler: sampler.EpochSampler (its rank and world size are this process's).  The loop reads
@@ -528,34 +574,39 @@ class FgnnTrainer:
         exact_last=True: every example trains exactly once per epoch -- the positions with which a short last step is filled (they
         wrap to examples the epoch has already shown) are switched off (train_step_bits(live=sampler.live_count(...)), DESIGN.md
         section 14); every step then runs the weighted launches.  A rank whose last step has no live pair still takes part in the
-        all-reduce, with a zero gradient.  False (default): the filled step trains its repeats, as before."""
+        all-reduce, with a zero gradient.  False (default): the filled step trains its repeats, as before.
+        features='spectral' (the reference's QAP_spectralGenerator): the same ``generator.bits(...)`` words go to
+        train_step_spectral(n_powers=n_powers) -- the hand-written loop over ``generator.spectral(index=...)`` and train_step, bit
+        for bit, without the fp32 features between two launches.  None (default): the loop above, launch for launch."""
+        spec = self._features('train_epoch', features, n_powers)
         steps = sampler.steps_per_epoch(batch_size)
         losses = torch.empty(steps, dtype=torch.float32, device=self.params.device)
         for step in range(steps):
             b1, b2, nv, *lab = generator.bits(index=sampler.batch_index(epoch, step, batch_size), permute=permute)
-            loss, _ = self.train_step_bits(b1, b2, nv, labels=lab[0] if lab else None,
-                                           live=sampler.live_count(step, batch_size) if exact_last else None)
+            kw = {'labels': lab[0] if lab else None, 'live': sampler.live_count(step, batch_size) if exact_last else None}
+            loss, _ = self.train_step_bits(b1, b2, nv, **kw) if spec is None else self.train_step_spectral(b1, b2, nv, spec, **kw)
             losses[step].copy_(loss)
         return losses
 
     # ------------------------------------------------------------------ validation / test epochs (evaluation.py)
-    def _eval_forward(self, B, N, nvalid, x=None, bits=None):
+    def _eval_forward(self, B, N, nvalid, x=None, bits=None, spectral=None):
         """EngineBase.forward of the training engine for (B, N) on the stacked batch: raw scores only.  Its loss sum goes to a buffer
         of this method's own; gradients, the collective's buffer, the optimizer and the captured graphs are not touched."""
         if getattr(self, '_eval_loss', None) is None:
             self._eval_loss = torch.zeros(1, dtype=torch.float32, device=self.params.device)
         eng = self._engine(2 * B, N, nvalid is not None)
         nv = None if nvalid is None else torch.cat([nvalid, nvalid]).to(torch.int32)
-        scores, _ = eng.forward(self.params, x, nvalid=nv, total_nodes=1.0, defer_loss=False, loss_out=self._eval_loss, bits=bits)
+        skw = {} if spectral is None else {'spectral': spectral}
+        scores, _ = eng.forward(self.params, x, nvalid=nv, total_nodes=1.0, defer_loss=False, loss_out=self._eval_loss, bits=bits, **skw)
         return scores
 
-    def _eval_tail(self, B, N, nvalid, x=None, bits=None, pair_bits=None, **options):
+    def _eval_tail(self, B, N, nvalid, x=None, bits=None, pair_bits=None, spectral=None, **options):
         """The stacked batch -> its scores -> evaluation.evaluate_scores with the step's options (pair_bits: its bits=, the two
         graphs' bit words for a qap_meter)"""
         from .evaluation import evaluate_scores
         if pair_bits is not None:
             options['bits'] = pair_bits
-        return evaluate_scores(self._eval_forward(B, N, nvalid, x=x, bits=bits), nvalid=nvalid, **options)
+        return evaluate_scores(self._eval_forward(B, N, nvalid, x=x, bits=bits, spectral=spectral), nvalid=nvalid, **options)
 
     def eval_step_bits(self, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False,
                        bins=None, rank_meter=None, qap_meter=None, refine=0):
@@ -564,10 +615,30 @@ class FgnnTrainer:
         loss_on_labels, bins, rank_meter and the returned per-pair device tensors.  Nothing is read back; parameters, gradients and optimizer state keep their bits.
         qap_meter (a QapMeter; with bins= a BinnedQapMeter), refine: the decode chain of evaluation.decode_scores on the bit words
         handed in here and the solver's assignment (0/1 graphs only; needs hungarian=True).  None: nothing of it is launched."""
-        B, N = self._bits_shape('eval_step_bits', bits1, bits2)
+        return self._eval_step_words('eval_step_bits', bits1, bits2, nvalid, None, labels=labels, meter=meter, live=live,
+                                     hungarian=hungarian, loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter,
+                                     qap_meter=qap_meter, refine=refine)
+
+    def eval_step_spectral(self, bits1, bits2, nvalid=None, n_powers=4, labels=None, meter=None, live=None, hungarian=True,
+                           loss_on_labels=False, bins=None, rank_meter=None, qap_meter=None, refine=0):
+        """The twin of eval_step_bits for spectral input: the forward pass runs on the features L, ..., L^n_powers of the bit words
+        (engine.forward(spectral=...), as train_step_spectral), everything after the scores is eval_step_bits'.
+        qap_meter, refine: the decode runs on the BIT WORDS handed in here -- the QAP objective on the adjacency W, not on the
+        normalised L the model sees.  On regular graphs L = W / d, so the ratio to the planted objective is the one the reference
+        reports for its spectral pairs; the reference's literal decode on channel 0 of the features stays what
+        ``match(..., weighted=True)`` computes per batch."""
+        n_powers = self._check_features('eval_step_spectral', n_powers)
+        return self._eval_step_words('eval_step_spectral', bits1, bits2, nvalid, n_powers, labels=labels, meter=meter, live=live,
+                                     hungarian=hungarian, loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter,
+                                     qap_meter=qap_meter, refine=refine)
+
+    def _eval_step_words(self, who, bits1, bits2, nvalid, n_powers, qap_meter=None, refine=0, **options):
+        """eval_step_bits (n_powers None) / eval_step_spectral: one body, the engine keyword differs"""
+        B, N = self._bits_shape(who, bits1, bits2)
         decode = {} if qap_meter is None and not refine else {'qap_meter': qap_meter, 'pair_bits': (bits1, bits2), 'refine': refine}
-        return self._eval_tail(B, N, nvalid, bits=torch.cat([bits1, bits2]).contiguous(), labels=labels, meter=meter, live=live,
-                               hungarian=hungarian, loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter, **decode)
+        b = torch.cat([bits1, bits2]).contiguous()
+        src = {'bits': b} if n_powers is None else {'spectral': (b, n_powers)}
+        return self._eval_tail(B, N, nvalid, **src, **options, **decode)
 
     def eval_step(self, x1, x2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False, bins=None,
                   rank_meter=None):
@@ -580,7 +651,7 @@ class FgnnTrainer:
                                hungarian=hungarian, loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter)
 
     def evaluate(self, generator, sampler, batch_size, epoch=0, hungarian=True, meter=None, permute=False, loss_on_labels=False,
-                 rank_meter=None, qap_meter=None, refine=0):
+                 rank_meter=None, qap_meter=None, refine=0, features=None, n_powers=4):
         """One pass over this rank's examples of `sampler` (sampler.EpochSampler; shuffle=False is the reference's validation
         loader): per step ``eval_step_bits(*generator.bits(index=sampler.batch_index(epoch, step, batch_size)))`` with the generator's
         vertex counts and, with permute=True, its planted labels.  Every example counts exactly once: the positions with which a
@@ -593,8 +664,11 @@ class FgnnTrainer:
         qap_meter: a QapMeter that takes the decode of every example from the same steps -- the accuracy of the Hungarian
         matching, its QAP objective against the planted one and, with refine = T > 0, the same after T rounds of greedy refinement
         (evaluation.decode_scores on the steps' bit words and the solver's assignment; the reference's all_acc_qap(val_loader, ...)
-        and all_greedy_losses_acc; 0/1 graphs only) -- and is summed over the ranks like the meter.  Needs hungarian=True."""
+        and all_greedy_losses_acc; 0/1 graphs only) -- and is summed over the ranks like the meter.  Needs hungarian=True.
+        features='spectral', n_powers: the steps are eval_step_spectral on the same words (the decode of a qap_meter stays on the
+        adjacency, see there).  None: eval_step_bits, as before."""
         from .evaluation import EvalMeter, QapMeter, RankMeter
+        spec = self._features('evaluate', features, n_powers)
         B = int(batch_size)
         if meter is None:
             meter = EvalMeter(self.params.device)
@@ -610,18 +684,22 @@ class FgnnTrainer:
                 if live:        # (0: a rank past the end of the data in the last global step; its index is never made)
                     yield live, None, {'index': sampler.batch_index(epoch, step, B), 'permute': permute}
         return self._eval_epoch(generator, batches(), meter, rank_meter, dp.world_size() > 1, hungarian, loss_on_labels, qap_meter,
-                                refine)
+                                refine, spec)
 
-    def _eval_epoch(self, generator, batches, meter, rank_meter, reduce, hungarian, loss_on_labels, qap_meter=None, refine=0):
+    def _eval_epoch(self, generator, batches, meter, rank_meter, reduce, hungarian, loss_on_labels, qap_meter=None, refine=0, spec=None):
         """The loop of evaluate and noise_curve.  batches: per step that has a live pair (live, bins, the keyword arguments of
-        generator.bits); reduce: sum the meters over the ranks at the end.  -> meter"""
+        generator.bits); reduce: sum the meters over the ranks at the end; spec: None or the n_powers of spectral steps.  -> meter"""
         if qap_meter is None and refine:
             raise ValueError('FgnnTrainer: refine= belongs to a qap_meter')
         decode = {} if qap_meter is None else {'qap_meter': qap_meter, 'refine': refine}
         for live, bins, bits_kw in batches:
             b1, b2, nv, *labels = generator.bits(**bits_kw)
-            self.eval_step_bits(b1, b2, nvalid=nv, labels=labels[0] if labels else None, meter=meter, live=live, hungarian=hungarian,
-                                loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter, **decode)
+            kw = dict(nvalid=nv, labels=labels[0] if labels else None, meter=meter, live=live, hungarian=hungarian,
+                      loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter, **decode)
+            if spec is None:
+                self.eval_step_bits(b1, b2, **kw)
+            else:
+                self.eval_step_spectral(b1, b2, n_powers=spec, **kw)
         if reduce:
             meter.allreduce_()
             if rank_meter is not None:
@@ -641,7 +719,7 @@ class FgnnTrainer:
         return e % M, e // M, sampler.live_count(step, batch_size)
 
     def noise_curve(self, generator, noises, num_examples, batch_size, hungarian=True, permute=False, loss_on_labels=False,
-                    rank=None, world_size=None, meter=None, rank_meter=None, qap_meter=None, refine=0):
+                    rank=None, world_size=None, meter=None, rank_meter=None, qap_meter=None, refine=0, features=None, n_powers=4):
         """The reference's result figure (README.md, "Results": a trained model evaluated across noise levels; per level
         toolbox/metrics.py:144-166) in one pass: the first num_examples pairs of `generator` at each of the K = len(noises) noise
         levels -- the SAME parent graphs at every level, a paired design -- through full batches of mixed levels
@@ -658,8 +736,10 @@ class FgnnTrainer:
         rank_meter: a BinnedRankMeter of K records that takes the rank metrics of every level from the same steps; it is summed
         over the ranks where the meter is.
         qap_meter: a BinnedQapMeter of K records that takes the decode of every level (see `evaluate`; refine: its rounds of
-        greedy refinement) from the same steps -- the QAP ratio across noise levels; it is summed over the ranks where the meter is."""
+        greedy refinement) from the same steps -- the QAP ratio across noise levels; it is summed over the ranks where the meter is.
+        features='spectral', n_powers: as in `evaluate`."""
         from .evaluation import BinnedEvalMeter, BinnedQapMeter, BinnedRankMeter
+        spec = self._features('noise_curve', features, n_powers)
         from .sampler import EpochSampler
         levels = generator.levels(noises)
         K, M, B = len(levels), int(num_examples), int(batch_size)
@@ -684,10 +764,10 @@ class FgnnTrainer:
                 if live:        # (0: a rank past the end of the examples in the last global step)
                     yield live, level, {'index': pair, 'levels': levels, 'level': level, 'permute': permute}
         return self._eval_epoch(generator, batches(), meter, rank_meter, dp.world_size() > 1 and sampler.world_size == dp.world_size(),
-                                hungarian, loss_on_labels, qap_meter, refine)
+                                hungarian, loss_on_labels, qap_meter, refine, spec)
 
     def fit(self, train_gen, train_sampler, val_gen, val_sampler, epochs, batch_size, scheduler=None, permute=False, exact_last=False,
-            rank_ks=None, decode_refine=None):
+            rank_ks=None, decode_refine=None, features=None, n_powers=4):
         """The reference's training loop around its scheduler (models/trainers.py:92-104): per epoch train_epoch, evaluate, ONE host
         read (the validation record), scheduler.step(val_loss).  scheduler=None: optim.ReduceLROnPlateau with the reference's
         settings, driving self.opt.lr (the next step pushes a changed rate to the device).  Returns the per-epoch history: dicts
@@ -702,7 +782,10 @@ class FgnnTrainer:
         decode_refine: an integer T >= 0 (evaluation.QapMeter; 0/1 graphs only): every epoch's dict gains 'val_qap_ratio' (the
         objective of the Hungarian matching over the planted one, summed over the validation pairs), 'val_recovered' (the fraction
         of pairs whose matching reaches the planted objective) and, for T > 0, 'val_refined_acc' (the accuracy after T rounds of
-        greedy refinement), taken by the same validation steps and read in the same single host copy."""
+        greedy refinement), taken by the same validation steps and read in the same single host copy.
+        features='spectral', n_powers: training and validation run on the spectral features of the generators' pairs (train_epoch /
+        evaluate with the same arguments)."""
+        fkw = {} if features is None else {'features': features, 'n_powers': self._features('fit', features, n_powers)}
         from .evaluation import EvalMeter, QapMeter, RankMeter, _check_refine, qap_result, rank_result, read_records, record_result
         if scheduler is None:
             from .optim import ReduceLROnPlateau
@@ -718,9 +801,9 @@ class FgnnTrainer:
         for epoch in range(int(epochs)):
             for m in extra + [own] * bool(extra):
                 m.reset()
-            losses = self.train_epoch(train_gen, train_sampler, epoch, batch_size, permute=permute, exact_last=exact_last)
+            losses = self.train_epoch(train_gen, train_sampler, epoch, batch_size, permute=permute, exact_last=exact_last, **fkw)
             meter = self.evaluate(val_gen, val_sampler, batch_size, epoch=epoch, meter=own, permute=permute, loss_on_labels=permute,
-                                  rank_meter=rank_meter, **decode)
+                                  rank_meter=rank_meter, **decode, **fkw)
             if not extra:
                 res = meter.result()
             else:

@@ -987,6 +987,15 @@ int fgnn_greedy_qapw_labels(const float *a1, const float *a2, long long gstride,
 #define FGNN_SPECTRAL_MAX_N 256
 #define FGNN_SPECTRAL_MAX_POWERS 8
 int fgnn_spectral_features(const unsigned *bits, const int *nvalid, int G, int N, int n_powers, float *out, int Nout, void *stream);
+/* The same features straight into the bf16 input slab of block 1 (csrc/spectral_slab.hip): y is the (G, CP, ldp) slab of
+ * fgnn_to_bf16_pad (CP = 2 or 32, row pitch ldr a multiple of 8, channel stride ldp a multiple of 64, y 16-byte aligned),
+ * 1 <= n_powers <= min(CP, FGNN_SPECTRAL_MAX_POWERS).  ONE launch writes every byte of the slab: channel p < n_powers = the
+ * round-to-nearest-even bf16 of the fp32 value fgnn_spectral_features computes for L^(p+1) (the chain stays in fp32; rounding happens
+ * on the way out only); channels >= n_powers, the ragged padding, the pitch columns j >= N and the tail of every channel up to ldp:
+ * exact +0.  The slab is byte-identical to fgnn_to_bf16_pad(fgnn_spectral_features(bits, nvalid, ..., Nout = N), ...).
+ * No workspace, no copy to the host, no synchronisation: capturable. */
+int fgnn_spectral_slab16(const unsigned *bits, const int *nvalid, int G, int N, int n_powers, int CP, int ldr, void *y, long long ldp,
+                         void *stream);
 
 /* ---- evaluation (csrc/eval.hip): what the reference's all_losses_acc (toolbox/metrics.py:144-166) and the val_loss behind its
  * ReduceLROnPlateau (models/trainers.py:78-104) take from a batch of raw scores, kept on the device ---------------------------
