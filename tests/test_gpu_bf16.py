@@ -191,7 +191,7 @@ def test_matmul16_entry_points_agree(N):
         return t.view(G, Cc, ldp)[:, :, :N * ldr].reshape(G, Cc, N, ldr)[..., :N].float().cpu()
     # the kernel normalises with one fma, y = R(z a + (beta - mean a)); torch rounds twice, so an operand may differ by one
     # bf16 ulp here and there: the product is compared in L2 (the element-wise half-ulp check with exact operands is
-    # tests/diag/gpu_mm16_kernel_check.py)
+    # test_random_operands_element_wise in tests/test_gpu_matmul16_exact.py)
     ya = (dense(za) * 0.8 + (beta_a.cpu().view(1, Cc, 1, 1) - 1.5 * 0.8)).to(torch.bfloat16).float()
     yb = (dense(zb) * 1.3 + (beta_b.cpu().view(1, Cc, 1, 1) + 0.7 * 1.3)).to(torch.bfloat16).float()
     m_ref = torch.matmul(ya.double(), yb.double()).float()
