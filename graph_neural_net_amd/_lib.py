@@ -295,6 +295,7 @@ _SIGNATURES = {
     'fgnn_greedy_qap_ws_bytes': [_I, _I],
     'fgnn_greedy_qap': [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
     'fgnn_greedy_qap_labels': [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
+    'fgnn_qap_2opt': [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP],
     'fgnn_qapw_objective': [_VP, _VP, _LL, _I, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP],
     'fgnn_qapw_improve_cost': [_VP, _VP, _LL, _I, _VP, _VP, _I, _I, _VP, _LL, _I, _VP],
     'fgnn_greedy_qapw_ws_bytes': [_I, _I],

@@ -16,9 +16,10 @@ rank_meter=)`` issues them after its own four, on the same scores, labels, ``liv
 
 ``decode_scores`` is the epoch form of the reference's ``all_acc_qap(val_loader, ...)`` / ``all_greedy_losses_acc``
 (toolbox/metrics.py:168-223): the Hungarian matching, its QAP objective and the planted one on the pairs' bit words (csrc/qap.hip),
-optionally the greedy refinement, and fgnn_qap_fold (csrc/qap_fold.hip) into a ``QapMeter`` or, with ``bins=``, a
-``BinnedQapMeter``; ``evaluate_scores(..., qap_meter=, bits=, refine=)`` issues it after its own launches on the assignment its
-solver launch wrote.  0/1 graphs only; the real-weighted decode stays per batch.
+optionally the greedy refinement and, with ``two_opt=True``, the pairwise-exchange search after it (csrc/qap_2opt.hip), and
+fgnn_qap_fold (csrc/qap_fold.hip) into a ``QapMeter`` or, with ``bins=``, a ``BinnedQapMeter``; ``evaluate_scores(..., qap_meter=,
+bits=, refine=, two_opt=)`` issues it after its own launches on the assignment its solver launch wrote.  0/1 graphs only; the
+real-weighted decode stays per batch.
 
 The six meters are one thing -- records of one ctypes struct in one device buffer (``_Records``) -- with three record types.
 """
@@ -469,9 +470,9 @@ def _bits_args(who, bits, B, N, dev):
     return bits[0].contiguous(), bits[1].contiguous()
 
 
-def _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine):
-    """qap.objective_bits (once more on the labels), qap.greedy_bits with refine > 0, then fgnn_qap_fold(_bins), on checked
-    arguments (on the current stream of the bit words' device) -> the dict of decode_scores"""
+def _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt=False):
+    """qap.objective_bits (once more on the labels), qap.greedy_bits with refine > 0, qap.two_opt_bits with two_opt, then
+    fgnn_qap_fold(_bins), on checked arguments (on the current stream of the bit words' device) -> the dict of decode_scores"""
     from . import qap
     dev = b1.device
     obj = qap.objective_bits(b1, b2, assign, nvalid, raw=True)
@@ -482,6 +483,11 @@ def _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, re
     if refine > 0:
         g = qap.greedy_bits(b1, b2, assign, refine, nvalid, labels, raw=True)
         perm, refined = g['perm'], g['s_best2']
+        meter._mark_refined()
+    swaps = status = None
+    if two_opt:                     # from the last matching of the chain; its objective IS qap's sum, whatever the symmetry
+        t = qap.two_opt_bits(b1, b2, assign if perm is None else perm, nvalid, raw=True)
+        perm, refined, swaps, status = t['perm'], t['qap'], t['swaps'], t['status']
         meter._mark_refined()
     # one zero-filled allocation for the three per-pair outputs: the 8-byte words first
     words = torch.zeros(2 * B, dtype=torch.int64, device=dev)
@@ -495,10 +501,17 @@ def _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, re
     else:
         _lib.call('fgnn_qap_fold_bins', *pairs, _lib.ptr(bins), meter.K, *outs)
     return {'assign': assign, 'qap': q, 'planted': planted, 'correct': correct, 'ratio': ratio, 'perm': perm, 'refined': refined,
-            'refined_correct': None if perm is None else refined_correct, 'meter': meter}
+            'refined_correct': None if perm is None else refined_correct, 'meter': meter, 'swaps': swaps, 'status': status}
 
 
-def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, bins=None, refine=0, assign=None):
+def _check_two_opt(who, two_opt):
+    if not isinstance(two_opt, bool):
+        raise ValueError('%s: two_opt must be True or False, got %r' % (who, two_opt))
+    return two_opt
+
+
+def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, bins=None, refine=0, assign=None,
+                  two_opt=False):
     """The reference's all_acc_qap / all_greedy_losses_acc (toolbox/metrics.py:168-223) of a batch, added to an epoch record.
     scores, nvalid, labels, live, bins: as evaluate_scores takes them, with the same refusals; bits1, bits2: the two graphs as
     (B, N, ceil(N/32)) int32 bit words on the scores' device (PairGenerator.bits, synthetic.pack_adjacency).  0/1 graphs only: the
@@ -506,16 +519,22 @@ def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, li
     The chain: the Hungarian matching of the scores (metrics.lsap_device, the route of qap.all_acc_qap) unless `assign`, a (B, N)
     int32 device tensor of matched columns, is handed in; qap.objective_bits for qap and planted, once more on the labels when
     there are any (planted is then the objective of the labels' matching); with refine = T > 0 the T rounds of qap.greedy_bits
-    from that matching; then fgnn_qap_fold, which adds the live pairs to `meter` (a QapMeter; with bins= a BinnedQapMeter, pair b
-    to record bins[b]; None: a fresh QapMeter).
+    from that matching; with two_opt=True the pairwise-exchange search of qap.two_opt_bits (one launch, no limit on its exchanges)
+    from the refinement's matching, or from the first one when refine = 0; then fgnn_qap_fold, which adds the live pairs to `meter`
+    (a QapMeter; with bins= a BinnedQapMeter, pair b to record bins[b]; None: a fresh QapMeter).  The fold takes the matching and
+    objective of the LAST stage that ran as perm / refined, so 'refined_acc', 'refined_qap_ratio' and 'improved' of the meter
+    describe the final matching of the chain.
     Returns the device tensors {'assign': (B, N) int32, 'qap', 'planted': (B,) int32, 'correct': (B,) int32 rows where assign is the
     row's target, 'ratio': (B,) fp64 qap / planted (0 for an unmatched pair or planted <= 0), 'perm': (B, N) int32 and 'refined':
-    (B,) int32 of the refinement (None without) -- refined is 2 s_best, trace(A P B P^T) of perm, the unit of qap --
-    'refined_correct': (B,) int32 (None without), 'meter'}; correct, ratio and refined_correct of pairs >= live are zero.
+    (B,) int32 of the refinement (None without) -- refined is 2 s_best, trace(A P B P^T) of perm, the unit of qap; after two_opt it
+    is the qap of perm itself, sum_{i,k} A[i,k] B[perm(i),perm(k)], -1 where the search was handed no permutation --
+    'refined_correct': (B,) int32 (None without), 'meter', 'swaps', 'status': (B,) int32 of qap.two_opt_bits (None without
+    two_opt)}; correct, ratio and refined_correct of pairs >= live are zero.
     Nothing is read back."""
     if meter is None and bins is not None:
         raise ValueError('decode_scores: bins= and a BinnedQapMeter as meter go together')
     refine = _check_refine('decode_scores', refine)
+    two_opt = _check_two_opt('decode_scores', two_opt)
     s, nvalid, labels, bins, B, N, live = _score_args('decode_scores', scores, nvalid, labels, live, bins)
     dev = s.device
     b1, b2 = _bits_args('decode_scores', (bits1, bits2), B, N, dev)
@@ -531,11 +550,11 @@ def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, li
         if assign is None:
             from .metrics import lsap_device
             assign = lsap_device(s, nvalid, want_assign=True)[1]
-        return _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine)
+        return _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt)
 
 
 def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False, bins=None,
-                    rank_meter=None, qap_meter=None, bits=None, refine=0):
+                    rank_meter=None, qap_meter=None, bits=None, refine=0, two_opt=False):
     """scores: (B, N, N) fp32 raw scores on the GPU, or a MaskedTensor of them (its vertex counts are used unless nvalid is given).
     nvalid: (B,) vertex counts in [0, N]; labels: see metrics.py (None: the identity; they enter the accuracies, never the loss).
     live: the first `live` pairs count (None: all B) -- the others, the filling of a short last step, are ignored entirely.
@@ -553,18 +572,21 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
     live and bins and add to it; their per-pair tensors come back under 'ranks'.  None: nothing of this is launched.
     qap_meter: a QapMeter (with bins=: a BinnedQapMeter of the meter's K) with bits=(bits1, bits2), the two graphs as bit words --
     the chain of decode_scores follows on the assignment of the solver launch made here (the solver does not run twice, so
-    hungarian=False is refused), with refine rounds of greedy refinement, on the same labels, live and bins; its per-pair tensors
-    come back under 'decode'.  0/1 graphs only (see decode_scores).  None: nothing of this is launched.
+    hungarian=False is refused), with refine rounds of greedy refinement and, with two_opt=True, the pairwise-exchange search
+    after them, on the same labels, live and bins; its per-pair tensors come back under 'decode'.  0/1 graphs only (see decode_scores).  None: nothing of this is launched.
     Four launches, nothing is read back."""
     if isinstance(meter, BinnedEvalMeter) != (bins is not None):
         raise ValueError('evaluate_scores: bins= and a BinnedEvalMeter as meter go together')
     if qap_meter is None:
         if bits is not None or refine:
             raise ValueError('evaluate_scores: bits= and refine= belong to a qap_meter')
+        if two_opt:
+            raise ValueError('evaluate_scores: two_opt= belongs to a qap_meter')
     else:
         if not hungarian:
             raise ValueError('evaluate_scores: a qap_meter decodes the matching of the Hungarian solver; it needs hungarian=True')
         refine = _check_refine('evaluate_scores', refine)
+        two_opt = _check_two_opt('evaluate_scores', two_opt)
     s, nvalid, labels, bins, B, N, live = _score_args('evaluate_scores', scores, nvalid, labels, live, bins)
     dev = s.device
     if meter is None:
@@ -602,7 +624,9 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
         else:
             _lib.call('fgnn_eval_fold_bins', *rows, _lib.ptr(bins), meter.K, *sums)
         ranks = None if rank_meter is None else _rank_launches(s, nvalid, labels, bins, B, N, live, rank_meter)
-        decode = None if qap_meter is None else _decode_launches(*bits, assign, nvalid, labels, bins, B, N, live, qap_meter, refine)
+        decode = None
+        if qap_meter is not None:
+            decode = _decode_launches(*bits, assign, nvalid, labels, bins, B, N, live, qap_meter, refine, two_opt)
     n = nvalid if nvalid is not None else torch.full((B,), N, **i32)
     out = {'ce': pair_ce, 'n': n, 'correct_max': pair_max, 'correct_lsap': correct, 'assign': assign, 'meter': meter}
     if ranks is not None:

@@ -38,6 +38,11 @@ instead of the identity (``planted.py``; a (B, N) integer tensor with labels[b, 
 of per-graph arrays): ``acc`` and ``acc_best`` count ``assign[i] == labels[i]`` and ``planted`` is the objective of the labels'
 matching, ``qap_objective(adj1, adj2, labels)['qap']`` -- for the identity that is ``sum A * B``.  On ``greedy_qap`` this is an
 extension: the reference's has no such parameter, its label is ``arange``.  ``labels=None`` changes nothing.
+
+``two_opt`` (``csrc/qap_2opt.hip``; not in the reference) polishes a matching by pairwise exchanges until no exchange of two
+vertices raises qap: the algorithm, scan order and evaluation count of ``scipy.optimize.quadratic_assignment(A, B, method='2opt',
+options={'maximize': True, 'partial_guess': ...})``, so perm, qap and nit are SciPy's, from one launch for the whole batch.  Its
+host route is a numpy restatement with the same delta evaluation, not a call into SciPy.  0/1 graphs only.
 """
 import numpy as np
 import torch
@@ -129,6 +134,32 @@ def greedy_bits(b1, b2, assign, T, nv, labels=None, raw=False):
               _lib.ptr(sums[1]), _lib.stream_ptr())
     return {'s_best': out[0].to(torch.float64) / 2, 'na': sums[0].to(torch.float64) / 2, 'nb': sums[1].to(torch.float64) / 2,
             'acc_best': out[1].to(torch.int64), 'T_best': out[2].to(torch.int64), 'perm': perm}
+
+
+def _check_max_swaps(max_swaps):
+    if max_swaps is None:
+        return -1
+    if isinstance(max_swaps, bool) or int(max_swaps) != max_swaps or not 0 <= max_swaps < 2 ** 31:
+        raise ValueError('two_opt: max_swaps must be None or an integer >= 0, got %r' % (max_swaps,))
+    return int(max_swaps)
+
+
+def two_opt_bits(b1, b2, assign, nv, max_swaps=None, raw=False):
+    """fgnn_qap_2opt on bit words, from the matching `assign` -> {'perm': (B, N) int32, 'qap', 'swaps', 'nit', 'status': (B,) int64}
+    device tensors (see `two_opt`); never synchronises.  raw=True: the tensors as the launch wrote them -- qap, swaps, status int32
+    (qap as fgnn_qap_fold reads it), nit int64."""
+    B, N, _ = b1.shape
+    dev = b1.device
+    a = assign.to(dtype=torch.int32).contiguous()
+    perm = torch.empty(B, N, dtype=torch.int32, device=dev)
+    out = torch.empty(3, B, dtype=torch.int32, device=dev)
+    nit = torch.empty(B, dtype=torch.int64, device=dev)
+    _lib.call('fgnn_qap_2opt', _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(a), _lib.ptr(nv), B, N, _check_max_swaps(max_swaps), _lib.ptr(perm),
+              _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(nit), _lib.ptr(out[2]), _lib.stream_ptr())
+    if raw:
+        return {'perm': perm, 'qap': out[0], 'swaps': out[1], 'nit': nit, 'status': out[2]}
+    out = out.to(torch.int64)
+    return {'perm': perm, 'qap': out[0], 'swaps': out[1], 'nit': nit, 'status': out[2]}
 
 
 def _chan0_ok(x):
@@ -234,6 +265,38 @@ def greedy_qap(adj1, adj2, assign, T=10, nvalid=None, weighted=False, labels=Non
         return _greedy_host(adj1, adj2, assign, T, nvalid, labels)
     b1, b2, nv, flag = _device_inputs(adj1, adj2, nvalid)
     out = greedy_bits(b1, b2, assign, T, nv, labels)
+    if flag is not None:
+        raise_if_bad(flag)
+    return out
+
+
+def two_opt(adj1, adj2, assign, nvalid=None, labels=None, max_swaps=None, weighted=False):
+    """Pairwise-exchange local search from `assign` for every pair of the batch: SciPy's ``quadratic_assignment(A, B,
+    method='2opt', options={'maximize': True, 'partial_guess': [[i, assign[i]]]})``.  The pairs (i, j), i <= j, are scanned in the
+    order (0,0), (0,1), .., (0,n-1), (1,1), ..; the first pair whose exchange raises qap = sum_{i,k} A[i,k] B[pi(i),pi(k)] is applied
+    and the scan starts over; a scan that finds none ends the search.  adj1, adj2, nvalid, labels: as `greedy_qap` takes them.
+    -> dict of tensors on the inputs' device: perm (B, N) int32, the polished matching (-1 in the padding), and per pair (int64)
+    qap = the objective of perm, qap0 = the objective of `assign`, acc = the rows of perm that meet `labels` (the identity without),
+    swaps = the exchanges applied, nit = the evaluations SciPy counts (an applied pair adds its 1-based scan position, the last scan
+    n (n + 1) / 2), status: 0 a local optimum, 1 stopped after `max_swaps` exchanges (None: no limit; perm / qap are the state
+    reached, nit has no last scan), 2 `assign` is no permutation of the pair's [0, n_b) -- perm is then `assign`, qap -1, swaps and
+    nit 0.  The device route is three launches (the search itself is one) and, with bit words, never synchronises; the host route
+    (tensors not on the GPU, N > 256) is the same algorithm in numpy with the same integers.  0/1 graphs only."""
+    if weighted:
+        raise NotImplementedError('two_opt: weighted=True is not supported -- the exchange search runs on 0/1 adjacency (bit words '
+                                  'or a tensor representation) only')
+    ms = _check_max_swaps(max_swaps)
+    labels = labels_tensor(labels, assign.shape[0], assign.shape[1], adj1.device)
+    if _on_host(adj1, adj1.shape[-2]):
+        return _two_opt_host(adj1, adj2, assign, nvalid, labels, ms)
+    b1, b2, nv, flag = _device_inputs(adj1, adj2, nvalid)
+    B, N, _ = b1.shape
+    a = assign.to(device=b1.device, dtype=torch.int32).contiguous()
+    out = two_opt_bits(b1, b2, a, nv, max_swaps)
+    out['qap0'] = objective_bits(b1, b2, a, nv)['qap']
+    if labels is None:
+        labels = torch.arange(N, dtype=torch.int32, device=b1.device).expand(B, N).contiguous()
+    out['acc'] = count_matches(out['perm'], labels, nv).to(torch.int64)
     if flag is not None:
         raise_if_bad(flag)
     return out
@@ -357,6 +420,62 @@ def _greedy_host(adj1, adj2, assign, T, nvalid, labels=None):
     return {'s_best': torch.from_numpy(s2).to(torch.float64) / 2, 'na': torch.from_numpy(na).to(torch.float64) / 2,
             'nb': torch.from_numpy(nb).to(torch.float64) / 2, 'acc_best': torch.from_numpy(acc_b), 'T_best': torch.from_numpy(t_b),
             'perm': torch.from_numpy(perm)}
+
+
+def _two_opt_pair(A, Bm, pi, max_swaps):
+    """The exchange search of one pair -> (perm, qap, swaps, nit, status).  With Bp = B[pi][:, pi], R = A Bp^T and X = A^T Bp the gain
+    of exchanging i and j is R[i,j] + R[j,i] - R[i,i] - R[j,j] (rows i, j) + X[i,j] + X[j,i] - X[i,i] - X[j,j] (columns i, j) +
+    (A[i,i] + A[j,j] - A[i,j] - A[j,i]) (Bp[i,i] + Bp[j,j] - Bp[i,j] - Bp[j,i]) (the four crossings): all gains of a round are two
+    matrix products (in float64, exact: every entry is an integer <= n), and the first positive one in row-major order above the
+    diagonal is the pair SciPy's scan accepts."""
+    n = len(pi)
+    if n == 0:
+        return pi, 0, 0, 0, 0
+    pi = pi.copy()
+    A = A.astype(np.float64)
+    Bp = Bm[np.ix_(pi, pi)].astype(np.float64)
+    dA = np.diag(A)
+    da = dA[:, None] + dA[None, :] - A - A.T
+    upper = np.triu(np.ones((n, n), dtype=bool), 1)
+    swaps, nit, status = 0, 0, 1
+    for _ in range(n * n if max_swaps < 0 else min(max_swaps, n * n)):
+        R, X, dB = A @ Bp.T, A.T @ Bp, np.diag(Bp)
+        own = np.diag(R) + np.diag(X)
+        gain = R + R.T + X + X.T - own[:, None] - own[None, :] + da * (dB[:, None] + dB[None, :] - Bp - Bp.T)
+        hit = np.flatnonzero((gain > 0) & upper)
+        if hit.size == 0:
+            nit += n * (n + 1) // 2
+            status = 0
+            break
+        i, j = divmod(int(hit[0]), n)
+        nit += i * n - i * (i - 1) // 2 + (j - i) + 1
+        swaps += 1
+        pi[[i, j]] = pi[[j, i]]
+        Bp[[i, j], :] = Bp[[j, i], :]
+        Bp[:, [i, j]] = Bp[:, [j, i]]
+    return pi, int((A * Bp).sum()), swaps, nit, status
+
+
+def _two_opt_host(adj1, adj2, assign, nvalid, labels, max_swaps):
+    B, N = adj1.shape[0], adj1.shape[-2]
+    sizes = _sizes(nvalid, B, N)
+    lab = _label_rows(labels, sizes)
+    As, Bs = _adjacency_host(adj1, sizes), _adjacency_host(adj2, sizes)
+    pis = assign.detach().cpu().numpy().astype(np.int64)
+    out = np.zeros((6, B), dtype=np.int64)                         # qap, qap0, acc, swaps, nit, status
+    perm = np.full((B, N), -1, dtype=np.int32)
+    for b, n in enumerate(sizes):
+        pi0 = pis[b, :n]
+        inside = bool(((pi0 >= 0) & (pi0 < n)).all())
+        q0 = _qap_of(As[b], Bs[b], pi0) if inside else -1
+        if inside and len(set(pi0.tolist())) == n:
+            pi, q, swaps, nit, status = _two_opt_pair(As[b], Bs[b], pi0, max_swaps)
+        else:
+            pi, q, swaps, nit, status = pi0, -1, 0, 0, 2
+        perm[b, :n] = pi
+        out[:, b] = (q, q0, int((pi == lab[b]).sum()), swaps, nit, status)
+    t = torch.from_numpy(out)
+    return {'perm': torch.from_numpy(perm), 'qap': t[0], 'qap0': t[1], 'acc': t[2], 'swaps': t[3], 'nit': t[4], 'status': t[5]}
 
 
 def _all_acc_qap_host(scores, adj1, adj2, nvalid, labels=None):

@@ -133,7 +133,7 @@ class Siamese_Node_Exp(nn.Module):
             return MaskedTensor(scores, nvalid, (1, 2), x1.base_name)
         return scores
 
-    def match(self, x1, x2, refine=0, weighted=False, labels=None):
+    def match(self, x1, x2, refine=0, weighted=False, labels=None, two_opt=False):
         """Decode a batch: the eager forward under no_grad (no `.grad` is touched), the Hungarian matching of -log_softmax(scores)
         and the reference's evaluation of it (toolbox/metrics.py:168-193 all_acc_qap), all on the device (qap.py).  Takes what
         `forward` takes.  Returns a dict: scores ((bs, n, n) tensor or MaskedTensor), assign ((bs, n) int32: the matched column of
@@ -150,7 +150,14 @@ class Siamese_Node_Exp(nn.Module):
         labels (planted.py; a (bs, n) integer tensor, labels[b, i] = the vertex of x2 that vertex i of x1 is, or the reference's list
         of per-graph arrays; wider rows, such as a generator's (bs, N) labels beside a ragged batch cropped to its largest graph, are
         cut to n): acc and acc_best count the matches with the labels instead of the fixed points, and planted is the objective of
-        the labels' matching.  None: the identity, as before."""
+        the labels' matching.  None: the identity, as before.
+
+        two_opt=True ends the decode in the pairwise-exchange search of qap.two_opt (one launch), started from the refinement's perm,
+        or from assign when refine = 0: the dict gains -- as qap.two_opt names them -- perm (the polished matching, in place of the
+        refinement's), qap_2opt (its objective, in the unit of qap), acc_2opt (its rows that meet the labels, or the identity), swaps,
+        nit and status.  0/1 batches only: with weighted=True it is refused."""
+        if two_opt and weighted:
+            raise NotImplementedError('match: two_opt=True runs on 0/1 adjacency only, not with weighted=True')
         a1, a2 = _unwrap_input(x1), _unwrap_input(x2)
         with torch.no_grad():
             scores = self(a1, a2)
@@ -180,6 +187,11 @@ class Siamese_Node_Exp(nn.Module):
             out = {'scores': scores, 'assign': assign, 'acc': correct.to(torch.int64), 'qap': obj['qap'], 'planted': obj['planted']}
             if refine:
                 out.update(qap.greedy_bits(b1, b2, assign, int(refine), nv, labels))
+            if two_opt:
+                t = qap.two_opt_bits(b1, b2, out.get('perm', assign), nv)
+                target = labels if labels is not None else torch.arange(s.shape[-1], dtype=torch.int32, device=dev).expand_as(assign).contiguous()
+                out.update({'perm': t['perm'], 'qap_2opt': t['qap'], 'acc_2opt': count_matches(t['perm'], target, nv).to(torch.int64),
+                            'swaps': t['swaps'], 'nit': t['nit'], 'status': t['status']})
         self._raise_if_not_representation({'flag': flag})
         return out
 

@@ -932,6 +932,25 @@ int fgnn_greedy_qap(const unsigned *bits1, const unsigned *bits2, const int *ass
 int fgnn_greedy_qap_labels(const unsigned *bits1, const unsigned *bits2, const int *assign0, const int *labels, const int *nvalid, int B,
                            int N, int T, void *ws, long long ws_bytes, int *s_best2, int *acc_best, int *t_best,
                            int *perm_best /* optional */, void *stream);
+/* fgnn_qap_2opt (csrc/qap_2opt.hip): pairwise-exchange local search from `assign`, one workgroup per pair, the whole search in ONE
+ * launch.  The semantics are those of scipy.optimize.quadratic_assignment(A, B, method='2opt', options={'maximize': True,
+ * 'partial_guess': [[i, assign[i]]]}) (scipy/optimize/_qap.py, _quadratic_assignment_2opt): the objective is
+ * S(p) = sum_{i,k} A[i,k] B[p(i),p(k)] on the corner (the qap of fgnn_qap_objective); the pairs (i, j), i <= j, are scanned in the
+ * order (0,0), (0,1), .., (0,n-1), (1,1), ..; the first pair whose exchange p(i) <-> p(j) gives a strictly larger S is applied and
+ * the scan restarts at (0,0); the search ends after a scan without an improving pair.  "First improving pair in scan order" is the
+ * minimum scan position among the pairs with a positive gain, so a round is all gains in parallel and one min-reduction; perm,
+ * qap, swaps and nit equal the serial algorithm's.  No symmetry and no zero diagonal is assumed of A or B.  The round loop is a
+ * counted loop of min(max_swaps, n_b n_b) rounds (max_swaps < 0: no limit of the caller's): every exchange raises an integer
+ * S <= n_b^2 by at least 1, so on valid input the bound does not bind by itself, and no input can make the kernel spin.
+ * Outputs per pair (all required):
+ *   perm (B, N) int32: the matching, -1 past the corner;  qap int32: S(perm);  swaps int32: the exchanges applied;
+ *   nit int64: the evaluations SciPy counts -- an applied pair (i, j) adds its 1-based scan position i n - i (i - 1) / 2 + (j - i) + 1,
+ *   the last, fruitless scan n (n + 1) / 2;
+ *   status int32: 0 a local optimum; 1 stopped after max_swaps exchanges (perm / qap the state reached, nit without a last scan);
+ *   2 `assign` is no permutation of [0, n_b) (an entry outside, or a duplicate): perm = assign (-1 past the corner), qap = -1,
+ *   swaps = nit = 0.  A pair with n_b = 0: status 0, qap = 0, nit = 0. */
+int fgnn_qap_2opt(const unsigned *bits1, const unsigned *bits2, const int *assign, const int *nvalid, int B, int N, int max_swaps,
+                  int *perm, int *qap, int *swaps, long long *nit, int *status, void *stream);
 
 /* ---- decoding a matching on real-weighted pairs (csrc/qap_weighted.hip): the fp32 twin of the section above, for what the
  * reference's all_acc_qap / greedy_qap take besides 0/1 adjacency -- a spectral L = D^-1/2 W D^-1/2, any weighted graph ---------
