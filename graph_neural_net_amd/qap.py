@@ -43,6 +43,9 @@ extension: the reference's has no such parameter, its label is ``arange``.  ``la
 vertices raises qap: the algorithm, scan order and evaluation count of ``scipy.optimize.quadratic_assignment(A, B, method='2opt',
 options={'maximize': True, 'partial_guess': ...})``, so perm, qap and nit are SciPy's, from one launch for the whole batch.  Its
 host route is a numpy restatement with the same delta evaluation, not a call into SciPy.  0/1 graphs only.
+
+``two_opt_weighted`` (``csrc/qap_2opt_weighted.hip``) is that search on real-weighted pairs, from the `perm` (or `assign`) that
+``match(..., weighted=True)`` or ``greedy_qap(weighted=True)`` return; see its docstring.
 """
 import numpy as np
 import torch
@@ -225,6 +228,49 @@ def greedy_weighted(adj1, adj2, assign, T, nv, labels=None):
 
 def _on_host_weighted(adj1, n):
     return not adj1.is_cuda or n > _lib.FGNN_QAPW_MAX_N
+
+
+def two_opt_weighted(adj1, adj2, assign, nvalid=None, labels=None, max_swaps=None):
+    """`two_opt` on real-weighted pairs (``csrc/qap_2opt_weighted.hip``): the same scan, acceptance of the first improving pair and
+    evaluation count, from `assign`, on what `weighted_views` takes -- (B, N, N) float matrices or (B, C, N, N) batches whose
+    channel 0 is used as is (a spectral L of ``PairGenerator.spectral``, any weighted graph).  nvalid, labels, max_swaps: as `two_opt`
+    takes them.  -> dict of tensors on the inputs' device: perm (B, N) int32 (-1 in the padding); qap, qap0 (B,) float32, exactly
+    ``objective_weighted(adj1, adj2, perm)['qap']`` resp. that of `assign` -- fresh fixed-order sums, not accumulated gains -- with
+    qap = -1 where status == 2; acc, swaps, nit, status (B,) int64 as `two_opt` defines them.
+
+    The gain of an exchange is one fp32 fmaf chain in the difference-of-products form, accepted iff > 0.  On integer
+    or dyadic weights whose partial sums stay below 2^24 units every gain is exact: perm, swaps and nit are SciPy's.  On general real
+    weights the trajectory is the kernel's own, bit-identical from run to run, and the default bound of n_b^2 exchanges can bind:
+    that is status 1, not an error.  The device route is the search launch, two objective launches and one count; it never
+    synchronises.  CPU tensors and N > 256 take a host route in numpy float64 with the same scan and the same nit; there qap and
+    qap0 are float64.
+
+    ``qap.two_opt(weighted=True)`` and ``match(weighted=True, two_opt=True)`` still refuse; the chain on weighted pairs is
+        out = model.match(x1, x2, refine=T, weighted=True)
+        polished = qap.two_opt_weighted(x1, x2, out.get('perm', out['assign']), labels=...)"""
+    ms = _check_max_swaps(max_swaps)
+    labels = labels_tensor(labels, assign.shape[0], assign.shape[1], adj1.device)
+    if _on_host_weighted(adj1, adj1.shape[-1]):
+        return _two_opt_host_w(adj1, adj2, assign, nvalid, labels, ms)
+    x1, x2, gs, ld = weighted_views(adj1, adj2)
+    B, N = x1.shape[0], x1.shape[-1]
+    dev = x1.device
+    nv = _nv32(nvalid, dev)
+    a = assign.to(device=dev, dtype=torch.int32).contiguous()
+    nbytes = _lib.load().fgnn_qapw_2opt_ws_bytes(B, N)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    perm = torch.empty(B, N, dtype=torch.int32, device=dev)
+    o32 = torch.empty(2, B, dtype=torch.int32, device=dev)
+    nit = torch.empty(B, dtype=torch.int64, device=dev)
+    _lib.call('fgnn_qapw_2opt', _lib.ptr(x1), _lib.ptr(x2), gs, ld, _lib.ptr(a), _lib.ptr(nv), B, N, ms, _lib.ptr(ws), nbytes,
+              _lib.ptr(perm), _lib.ptr(o32[0]), _lib.ptr(nit), _lib.ptr(o32[1]), _lib.stream_ptr())
+    o64 = o32.to(torch.int64)
+    qap = objective_weighted(x1, x2, perm, nv)['qap']
+    if labels is None:
+        labels = torch.arange(N, dtype=torch.int32, device=dev).expand(B, N).contiguous()
+    return {'perm': perm, 'qap': torch.where(o64[1] == 2, torch.full_like(qap, -1.0), qap),
+            'qap0': objective_weighted(x1, x2, a, nv)['qap'], 'acc': count_matches(perm, labels, nv).to(torch.int64),
+            'swaps': o64[0], 'nit': nit, 'status': o64[1]}
 
 
 def qap_objective(adj1, adj2, assign, nvalid=None, weighted=False):
@@ -563,6 +609,68 @@ def _greedy_host_w(adj1, adj2, assign, T, nvalid, labels=None):
         s_b[b], acc_b[b], t_b[b] = best, acc_best, t_best
     return {'s_best': torch.from_numpy(s_b), 'na': torch.from_numpy(na), 'nb': torch.from_numpy(nb), 'acc_best': torch.from_numpy(acc_b),
             'T_best': torch.from_numpy(t_b), 'perm': torch.from_numpy(perm)}
+
+
+def _gains_of_row_w(A, Bp, i):
+    """float64 gains of exchanging i with j = i + 1 .. n - 1, in the kernel's difference-of-products form (terms k = i, j left out)"""
+    n = len(A)
+    js = np.arange(i + 1, n)
+    rows = (A[i][None, :] - A[js]) * (Bp[js] - Bp[i][None, :])
+    cols = (A[:, i][None, :] - A[:, js].T) * (Bp[:, js].T - Bp[:, i][None, :])
+    for t in (rows, cols):
+        t[:, i] = 0.0
+        t[js - i - 1, js] = 0.0
+    dA, dB = np.diag(A), np.diag(Bp)
+    cross = (dA[i] - dA[js]) * (dB[js] - dB[i]) + (A[i, js] - A[js, i]) * (Bp[js, i] - Bp[i, js])
+    return rows.sum(1) + cols.sum(1) + cross
+
+
+def _two_opt_pair_w(A, Bm, pi, max_swaps):
+    """The exchange search of one real-weighted pair -> (perm, qap, swaps, nit, status): the scan, the counted loop (n^2 rounds
+    without a limit) and the nit of the kernel, the gains in float64"""
+    n = len(pi)
+    if n == 0:
+        return pi, 0.0, 0, 0, 0
+    pi = pi.copy()
+    Bp = Bm[np.ix_(pi, pi)]
+    swaps, nit, status = 0, 0, 1
+    for _ in range(n * n if max_swaps < 0 else min(max_swaps, n * n)):
+        for i in range(n - 1):
+            hit = np.flatnonzero(_gains_of_row_w(A, Bp, i) > 0)
+            if hit.size:
+                break
+        else:
+            nit += n * (n + 1) // 2
+            status = 0
+            break
+        j = i + 1 + int(hit[0])
+        nit += i * n - i * (i - 1) // 2 + (j - i) + 1
+        swaps += 1
+        pi[[i, j]] = pi[[j, i]]
+        Bp = Bm[np.ix_(pi, pi)]
+    return pi, float((A * Bp).sum()), swaps, nit, status
+
+
+def _two_opt_host_w(adj1, adj2, assign, nvalid, labels, max_swaps):
+    B, N = adj1.shape[0], adj1.shape[-1]
+    sizes = _sizes(nvalid, B, N)
+    lab = _label_rows(labels, sizes)
+    As, Bs = _matrices_host_w(adj1, sizes), _matrices_host_w(adj2, sizes)
+    pis = assign.detach().cpu().numpy().astype(np.int64)
+    q, out = np.zeros((2, B), dtype=np.float64), np.zeros((4, B), dtype=np.int64)      # qap, qap0; acc, swaps, nit, status
+    perm = np.full((B, N), -1, dtype=np.int32)
+    for b, n in enumerate(sizes):
+        pi0 = pis[b, :n]
+        inside = bool(((pi0 >= 0) & (pi0 < n)).all())
+        q[1, b] = (As[b] * Bs[b][np.ix_(pi0, pi0)]).sum() if inside else -1.0
+        if inside and len(set(pi0.tolist())) == n:
+            pi, q[0, b], swaps, nit, status = _two_opt_pair_w(As[b], Bs[b], pi0, max_swaps)
+        else:
+            pi, q[0, b], swaps, nit, status = pi0, -1.0, 0, 0, 2
+        perm[b, :n] = pi
+        out[:, b] = (int((pi == lab[b]).sum()), swaps, nit, status)
+    t, tq = torch.from_numpy(out), torch.from_numpy(q)
+    return {'perm': torch.from_numpy(perm), 'qap': tq[0], 'qap0': tq[1], 'acc': t[0], 'swaps': t[1], 'nit': t[2], 'status': t[3]}
 
 
 def _all_acc_qap_host_w(scores, adj1, adj2, nvalid, labels=None):

@@ -991,6 +991,24 @@ int fgnn_greedy_qapw(const float *a1, const float *a2, long long gstride, int ld
 int fgnn_greedy_qapw_labels(const float *a1, const float *a2, long long gstride, int ld, const int *assign0, const int *labels,
                             const int *nvalid, int B, int N, int T, void *ws, long long ws_bytes, float *s_best, int *acc_best,
                             int *t_best, int *perm_best /* optional */, void *stream);
+/* fgnn_qapw_2opt (csrc/qap_2opt_weighted.hip): the pairwise-exchange local search of fgnn_qap_2opt on real-weighted pairs, one
+ * workgroup per pair, the whole search in ONE launch.  Addressing and input contract are those of the fgnn_qapw_* entry points
+ * above; scan order, acceptance of the first improving pair, perm (-1 past the corner), swaps, nit (the same closed formulas) and
+ * status (0 a local optimum, 1 stopped at the exchange bound, 2 `assign` is no permutation of the corner: perm = assign, swaps =
+ * nit = 0) are those of fgnn_qap_2opt.  There is no qap output: fgnn_qapw_objective on perm is the objective, a fresh sum.
+ * With Bp[a][k] = B[p(a)][p(k)] the gain of exchanging i < j is
+ *     sum_{k != i,j} (A[i,k] - A[j,k]) (Bp[j,k] - Bp[i,k]) + sum_{k != i,j} (A[k,i] - A[k,j]) (Bp[k,j] - Bp[k,i])
+ *     + (A[i,i] - A[j,j]) (Bp[j,j] - Bp[i,i]) + (A[i,j] - A[j,i]) (Bp[j,i] - Bp[i,j]),
+ * one fp32 fmaf chain per pair (k ascending, row term before column term, then the two crossings) that depends on (A, Bp, i, j)
+ * only; no gain state is carried between rounds; the gain of undoing an exchange is the exact negative of the gain that made it.
+ * A pair is accepted iff its fp32 gain is > 0.  On integer or dyadic weights whose partial sums stay below 2^24 units every gain is
+ * exact and perm, swaps, nit are SciPy's; on general real weights the trajectory is the kernel's own, the same from run to run.
+ * The round loop is a counted loop of max_swaps rounds (max_swaps < 0: n_b n_b); with real weights that default bound can bind
+ * (status 1).  N <= 128: A and Bp live in LDS and ws may be NULL / 0 bytes; 128 < N <= 256: Bp lives in ws
+ * (fgnn_qapw_2opt_ws_bytes(B, N) bytes, 16-byte aligned), A is read in place. */
+long long fgnn_qapw_2opt_ws_bytes(int B, int N);
+int fgnn_qapw_2opt(const float *a1, const float *a2, long long gstride, int ld, const int *assign, const int *nvalid, int B, int N,
+                   int max_swaps, void *ws, long long ws_bytes, int *perm, int *swaps, long long *nit, int *status, void *stream);
 
 /* ---- spectral input features (csrc/spectral.hip; loaders/data_generator.py:221-232 make_laplacian / make_spectral_feature, the
  * input of QAP_spectralGenerator) ---------------------------------------------------------------------------------------------
