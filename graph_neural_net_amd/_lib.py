@@ -303,6 +303,8 @@ _SIGNATURES = {
     'fgnn_greedy_qapw_labels': [_VP, _VP, _LL, _I, _VP, _VP, _VP, _I, _I, _I, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
     'fgnn_qapw_2opt_ws_bytes': [_I, _I],
     'fgnn_qapw_2opt': [_VP, _VP, _LL, _I, _VP, _VP, _I, _I, _I, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
+    'fgnn_qapw_faq_ws_bytes': [_I, _I],
+    'fgnn_qapw_faq': [_VP, _VP, _LL, _I, _VP, _VP, _VP, _I, _I, _I, _F, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
     'fgnn_planted_perm': [C.c_ulonglong, _LL, _VP, _VP, _I, _I, _VP, _VP],
     'fgnn_relabel_bits': [_VP, _VP, _VP, _I, _I, _VP, _VP],
     'fgnn_relabel_dense': [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP],
@@ -345,7 +347,8 @@ _SIGNATURES = {
     'fgnn_mlp_bwd16_pair': [C.POINTER(MlpBwd16Args), C.POINTER(MlpBwd16Args), _VP],
 }
 _RESTYPES = {'fgnn_last_error': C.c_char_p, 'fgnn_block1_struct_ws_floats': C.c_longlong, 'fgnn_greedy_qap_ws_bytes': C.c_longlong,
-             'fgnn_greedy_qapw_ws_bytes': C.c_longlong, 'fgnn_qapw_2opt_ws_bytes': C.c_longlong}
+             'fgnn_greedy_qapw_ws_bytes': C.c_longlong, 'fgnn_qapw_2opt_ws_bytes': C.c_longlong,
+             'fgnn_qapw_faq_ws_bytes': C.c_longlong}
 EXPORTS = tuple(_SIGNATURES)
 
 _lib = None

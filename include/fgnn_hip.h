@@ -1009,6 +1009,31 @@ int fgnn_greedy_qapw_labels(const float *a1, const float *a2, long long gstride,
 long long fgnn_qapw_2opt_ws_bytes(int B, int N);
 int fgnn_qapw_2opt(const float *a1, const float *a2, long long gstride, int ld, const int *assign, const int *nvalid, int B, int N,
                    int max_swaps, void *ws, long long ws_bytes, int *perm, int *swaps, long long *nit, int *status, void *stream);
+/* fgnn_qapw_faq (csrc/qap_faq.hip): the Fast Approximate QAP algorithm -- Frank-Wolfe on f(P) = tr(A^T P B P^T) over the doubly
+ * stochastic matrices, scipy.optimize.quadratic_assignment(method='faq', options={'maximize': True}) without seeds or shuffling --
+ * for every pair, as a chain of launches on `stream` with scratch from ws (fgnn_qapw_faq_ws_bytes bytes, 16-byte aligned): no
+ * allocation, no host copy, no synchronisation, capturable.  Addressing and input contract are those of the fgnn_qapw_* entry
+ * points above; nothing outside a pair's corner is read, in a1, a2 and p0 alike.  The start is p0 ((B, N, N) fp32, optional; that
+ * it is doubly stochastic is NOT checked), the permutation matrix of assign0 ((B, N) int32, optional), or with neither the
+ * barycenter, every entry 1 / n_b; at most one of the two may be given.  A round:
+ *     G = A P B^T + A^T P B          two launches on v_mfma_f32_32x32x2_f32, operands staged through LDS: T = P [B^T | B], then
+ *                                    -G = -([A | A^T] [T0; T1]) into the layout fgnn_lsap_accuracy reads; every entry of T is an fmaf
+ *                                    chain of n_b terms, every entry of G one of 2 n_b terms; G is fresh from P in every round
+ *     q = argmax_Q <G, Q>            the solver of fgnn_lsap_accuracy on -G
+ *     a = <G, P> / 2 - <G, Q> + f(Q), b = <G, Q> - 2 f(Q)      (R = P - Q: f(Q + x R) = f(Q) + b x + a x^2), fp64 sums in a fixed order
+ *     x = -b / (2 a) if a < 0 and 0 <= -b / (2 a) <= 1, else 1 if -(a + b) < 0, else 0;  P' = x P + (1 - x) Q, formed in fp64 and
+ *                                    rounded once to fp32;  the pair stops when ||P - P'||_F / sqrt(n_b) < tol, keeping P'
+ * Always maxiter rounds of 4 launches are issued; a pair that has met tol is frozen by a done flag in the workspace: the round's
+ * kernels leave it at once and the solver sees n_b = 0 for it.  Then perm = argmax_Q <P, Q> by the same solver on -P.
+ * Outputs: perm (B, N) int32, -1 past the corner; nit int32 = the rounds performed (>= 1, as SciPy counts them); status int32: 0
+ * stopped on tol, 1 maxiter reached, 2 n_b = 0, assign0 no permutation of [0, n_b), or the solver found no assignment (a NaN inside
+ * the corner) -- perm is then assign0 (or -1 without) and nit 0; p_out (optional, (B, N, N) fp32) = the last P, zero around the
+ * corner.  There is no objective output: fgnn_qapw_objective on perm is the objective, a fresh sum.  Results are bit-identical
+ * from run to run, and a pair's do not depend on the batch around it.  maxiter > 0, tol > 0. */
+long long fgnn_qapw_faq_ws_bytes(int B, int N);
+int fgnn_qapw_faq(const float *a1, const float *a2, long long gstride, int ld, const float *p0 /* optional, (B,N,N) */,
+                  const int *assign0 /* optional, (B,N) */, const int *nvalid, int B, int N, int maxiter, float tol, void *ws,
+                  long long ws_bytes, int *perm, int *nit, int *status, float *p_out /* optional, (B,N,N) */, void *stream);
 
 /* ---- spectral input features (csrc/spectral.hip; loaders/data_generator.py:221-232 make_laplacian / make_spectral_feature, the
  * input of QAP_spectralGenerator) ---------------------------------------------------------------------------------------------
