@@ -21,6 +21,7 @@ FGNN_LSAP_MAX_N = 2048       # include/fgnn_hip.h: largest graph of fgnn_lsap_ac
 FGNN_MAX_LEVELS = 64         # include/fgnn_hip.h: noise levels of fgnn_pairgen_levels, records of fgnn_eval_fold_bins
 FGNN_QAP_MAX_N = 256         # include/fgnn_hip.h: largest graph of the fgnn_qap_* / fgnn_greedy_qap kernels
 FGNN_QAPW_MAX_N = 256        # include/fgnn_hip.h: largest graph of the fgnn_qapw_* / fgnn_greedy_qapw kernels (fp32 weights)
+FGNN_SINKHORN_LDS_MAX_N = 192   # include/fgnn_hip.h: largest graph whose scores fgnn_sinkhorn keeps in LDS
 FGNN_SPECTRAL_MAX_N = 256    # include/fgnn_hip.h: largest graph of fgnn_spectral_features
 FGNN_SPECTRAL_MAX_POWERS = 8
 FGNN_PLANTED_MAX_N = 256      # include/fgnn_hip.h: largest graph of the fgnn_planted_perm / fgnn_relabel_* kernels
@@ -305,6 +306,7 @@ _SIGNATURES = {
     'fgnn_qapw_2opt': [_VP, _VP, _LL, _I, _VP, _VP, _I, _I, _I, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
     'fgnn_qapw_faq_ws_bytes': [_I, _I],
     'fgnn_qapw_faq': [_VP, _VP, _LL, _I, _VP, _VP, _VP, _I, _I, _I, _F, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
+    'fgnn_sinkhorn': [_VP, _LL, _I, _VP, _I, _I, _F, _I, _VP, _VP, _VP, _VP],
     'fgnn_planted_perm': [C.c_ulonglong, _LL, _VP, _VP, _I, _I, _VP, _VP],
     'fgnn_relabel_bits': [_VP, _VP, _VP, _I, _I, _VP, _VP],
     'fgnn_relabel_dense': [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP],

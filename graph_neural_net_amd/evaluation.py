@@ -19,7 +19,8 @@ rank_meter=)`` issues them after its own four, on the same scores, labels, ``liv
 optionally the greedy refinement and, with ``two_opt=True``, the pairwise-exchange search after it (csrc/qap_2opt.hip), and
 fgnn_qap_fold (csrc/qap_fold.hip) into a ``QapMeter`` or, with ``bins=``, a ``BinnedQapMeter``; ``evaluate_scores(..., qap_meter=,
 bits=, refine=, two_opt=)`` issues it after its own launches on the assignment its solver launch wrote.  0/1 graphs only; the
-real-weighted decode stays per batch.
+real-weighted decode stays per batch.  ``faq=`` puts the Fast Approximate QAP chain (csrc/qap_faq.hip) between the Hungarian
+matching and the refinement, started from the Sinkhorn projection of the scores (csrc/sinkhorn.hip) or from the barycenter.
 
 The six meters are one thing -- records of one ctypes struct in one device buffer (``_Records``) -- with three record types.
 """
@@ -470,9 +471,58 @@ def _bits_args(who, bits, B, N, dev):
     return bits[0].contiguous(), bits[1].contiguous()
 
 
-def _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt=False):
-    """qap.objective_bits (once more on the labels), qap.greedy_bits with refine > 0, qap.two_opt_bits with two_opt, then
-    fgnn_qap_fold(_bins), on checked arguments (on the current stream of the bit words' device) -> the dict of decode_scores"""
+FAQ_DEFAULTS = {'P0': 'scores', 'maxiter': 30, 'tol': 0.03, 'tau': 1.0, 'iters': 20}
+
+
+def _check_faq(who, faq):
+    """faq= of the decode: None (off), True (FAQ_DEFAULTS) or a dict of some of its keys -> None or the full dict, checked"""
+    if faq is None:
+        return None
+    if faq is True:
+        faq = {}
+    if not isinstance(faq, dict):
+        raise ValueError('%s: faq must be None, True or a dict with keys from %s, got %r' % (who, sorted(FAQ_DEFAULTS), faq))
+    unknown = sorted(set(faq) - set(FAQ_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError('%s: faq has unknown key(s) %s; the keys are %s' % (who, unknown, sorted(FAQ_DEFAULTS)))
+    from .qap import check_sinkhorn
+    o = dict(FAQ_DEFAULTS, **faq)
+    if o['P0'] not in ('scores', 'barycenter'):
+        raise ValueError("%s: faq['P0'] is 'scores' or 'barycenter', got %r" % (who, o['P0']))
+    if isinstance(o['maxiter'], bool) or not isinstance(o['maxiter'], (int, np.integer)) or o['maxiter'] <= 0:
+        raise ValueError("%s: faq['maxiter'] must be a positive integer, got %r" % (who, o['maxiter']))
+    if isinstance(o['tol'], bool) or not isinstance(o['tol'], (int, float, np.floating, np.integer)) or not o['tol'] > 0:
+        raise ValueError("%s: faq['tol'] must be a positive float, got %r" % (who, o['tol']))
+    o['tau'], o['iters'] = check_sinkhorn('%s: faq' % who, o['tau'], o['iters'])
+    o['maxiter'], o['tol'] = int(o['maxiter']), float(o['tol'])
+    return o
+
+
+def _faq_launches(b1, b2, s, assign, q, nvalid, B, N, faq):
+    """The FAQ stage of the decode, on checked arguments: fgnn_sinkhorn on the scores (P0 'scores'), fgnn_expand_adjacency on both
+    sides, the fgnn_qapw_faq chain, the objective of its perm, and the select -- where the chain reports status 2 the stage keeps
+    `assign` and its objective `q`.  Every buffer is allocated before the first launch; nothing is read back.
+    -> {'perm', 'qap', 'faq_perm', 'faq_qap', 'faq_nit', 'faq_status', 'sinkhorn_err'}"""
+    from . import qap
+    dev = b1.device
+    x = torch.empty(2, B, 2, N, N, dtype=torch.float32, device=dev)
+    p0 = err = None
+    if faq['P0'] == 'scores':
+        sk = qap.sinkhorn_device(s, nvalid, faq['tau'], faq['iters'])
+        p0, err = sk['P'], sk['err']
+    for side, bits in enumerate((b1, b2)):
+        _lib.call('fgnn_expand_adjacency', _lib.ptr(bits), _lib.ptr(nvalid), B, N, _lib.ptr(x[side]), _lib.stream_ptr())
+    out = qap.faq_weighted(x[0], x[1], nvalid, p0, None, faq['maxiter'], faq['tol'])
+    fq = qap.objective_bits(b1, b2, out['perm'], nvalid, raw=True)[0]
+    failed = out['status'] == 2
+    return {'perm': torch.where(failed[:, None], assign, out['perm']), 'qap': torch.where(failed, q, fq), 'faq_perm': out['perm'],
+            'faq_qap': fq, 'faq_nit': out['nit'], 'faq_status': out['status'], 'sinkhorn_err': err}
+
+
+def _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt=False, faq=None, scores=None):
+    """qap.objective_bits (once more on the labels), _faq_launches with faq (on `scores`), qap.greedy_bits with refine > 0,
+    qap.two_opt_bits with two_opt, then fgnn_qap_fold(_bins), on checked arguments (on the current stream of the bit words' device)
+    -> the dict of decode_scores"""
     from . import qap
     dev = b1.device
     obj = qap.objective_bits(b1, b2, assign, nvalid, raw=True)
@@ -480,8 +530,13 @@ def _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, re
     if labels is not None:          # (as all_acc_qap: planted is the objective of the labels' matching)
         planted = qap.objective_bits(b1, b2, labels, nvalid, raw=True)[0]
     perm = refined = None
+    stage = dict.fromkeys(('faq_perm', 'faq_qap', 'faq_nit', 'faq_status', 'sinkhorn_err'))
+    if faq is not None:
+        stage = _faq_launches(b1, b2, scores, assign, q, nvalid, B, N, faq)
+        perm, refined = stage.pop('perm'), stage.pop('qap')
+        meter._mark_refined()
     if refine > 0:
-        g = qap.greedy_bits(b1, b2, assign, refine, nvalid, labels, raw=True)
+        g = qap.greedy_bits(b1, b2, assign if perm is None else perm, refine, nvalid, labels, raw=True)
         perm, refined = g['perm'], g['s_best2']
         meter._mark_refined()
     swaps = status = None
@@ -501,7 +556,7 @@ def _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, re
     else:
         _lib.call('fgnn_qap_fold_bins', *pairs, _lib.ptr(bins), meter.K, *outs)
     return {'assign': assign, 'qap': q, 'planted': planted, 'correct': correct, 'ratio': ratio, 'perm': perm, 'refined': refined,
-            'refined_correct': None if perm is None else refined_correct, 'meter': meter, 'swaps': swaps, 'status': status}
+            'refined_correct': None if perm is None else refined_correct, 'meter': meter, 'swaps': swaps, 'status': status, **stage}
 
 
 def _check_two_opt(who, two_opt):
@@ -511,7 +566,7 @@ def _check_two_opt(who, two_opt):
 
 
 def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, bins=None, refine=0, assign=None,
-                  two_opt=False):
+                  two_opt=False, faq=None):
     """The reference's all_acc_qap / all_greedy_losses_acc (toolbox/metrics.py:168-223) of a batch, added to an epoch record.
     scores, nvalid, labels, live, bins: as evaluate_scores takes them, with the same refusals; bits1, bits2: the two graphs as
     (B, N, ceil(N/32)) int32 bit words on the scores' device (PairGenerator.bits, synthetic.pack_adjacency).  0/1 graphs only: the
@@ -530,11 +585,22 @@ def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, li
     is the qap of perm itself, sum_{i,k} A[i,k] B[perm(i),perm(k)], -1 where the search was handed no permutation --
     'refined_correct': (B,) int32 (None without), 'meter', 'swaps', 'status': (B,) int32 of qap.two_opt_bits (None without
     two_opt)}; correct, ratio and refined_correct of pairs >= live are zero.
+    faq: None (off), True or a dict with keys from {'P0': 'scores' | 'barycenter', 'maxiter': 30, 'tol': 0.03, 'tau': 1.0,
+    'iters': 20} (True: these defaults with P0 'scores'; an unknown key raises ValueError) -- the Fast Approximate QAP stage, after
+    the Hungarian matching and before refine and two_opt: with 'scores' the Sinkhorn projection of the scores the solver saw
+    (qap.sinkhorn: tau, iters; one launch) is the start P0, else the barycenter; fgnn_expand_adjacency on both sides' words; the
+    chain of qap.faq (maxiter, tol); qap.objective_bits of its perm; and a select on the device: where the chain reports status 2
+    the stage's matching and objective are `assign` and its qap.  refine and two_opt then start from the stage's matching, and the
+    fold takes the last stage that ran, as above.  The dict gains 'faq_perm' (B, N) int32, 'faq_qap', 'faq_nit', 'faq_status' (B,)
+    int32 as the chain left them (faq_qap: the objective of faq_perm, -1 where it holds no matching) and 'sinkhorn_err' (B,) fp32
+    (None with the barycenter); all None without faq.  With {'P0': 'barycenter'} and `assign` handed in the scores do not enter
+    the stage's matching: the classical-baseline epoch.
     Nothing is read back."""
     if meter is None and bins is not None:
         raise ValueError('decode_scores: bins= and a BinnedQapMeter as meter go together')
     refine = _check_refine('decode_scores', refine)
     two_opt = _check_two_opt('decode_scores', two_opt)
+    faq = _check_faq('decode_scores', faq)
     s, nvalid, labels, bins, B, N, live = _score_args('decode_scores', scores, nvalid, labels, live, bins)
     dev = s.device
     b1, b2 = _bits_args('decode_scores', (bits1, bits2), B, N, dev)
@@ -550,11 +616,11 @@ def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, li
         if assign is None:
             from .metrics import lsap_device
             assign = lsap_device(s, nvalid, want_assign=True)[1]
-        return _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt)
+        return _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt, faq, s)
 
 
 def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False, bins=None,
-                    rank_meter=None, qap_meter=None, bits=None, refine=0, two_opt=False):
+                    rank_meter=None, qap_meter=None, bits=None, refine=0, two_opt=False, faq=None):
     """scores: (B, N, N) fp32 raw scores on the GPU, or a MaskedTensor of them (its vertex counts are used unless nvalid is given).
     nvalid: (B,) vertex counts in [0, N]; labels: see metrics.py (None: the identity; they enter the accuracies, never the loss).
     live: the first `live` pairs count (None: all B) -- the others, the filling of a short last step, are ignored entirely.
@@ -574,6 +640,7 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
     the chain of decode_scores follows on the assignment of the solver launch made here (the solver does not run twice, so
     hungarian=False is refused), with refine rounds of greedy refinement and, with two_opt=True, the pairwise-exchange search
     after them, on the same labels, live and bins; its per-pair tensors come back under 'decode'.  0/1 graphs only (see decode_scores).  None: nothing of this is launched.
+    faq (with a qap_meter): the Fast Approximate QAP stage of decode_scores, started from these scores or from the barycenter.
     Four launches, nothing is read back."""
     if isinstance(meter, BinnedEvalMeter) != (bins is not None):
         raise ValueError('evaluate_scores: bins= and a BinnedEvalMeter as meter go together')
@@ -582,11 +649,14 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
             raise ValueError('evaluate_scores: bits= and refine= belong to a qap_meter')
         if two_opt:
             raise ValueError('evaluate_scores: two_opt= belongs to a qap_meter')
+        if faq is not None:
+            raise ValueError('evaluate_scores: faq= belongs to a qap_meter')
     else:
         if not hungarian:
             raise ValueError('evaluate_scores: a qap_meter decodes the matching of the Hungarian solver; it needs hungarian=True')
         refine = _check_refine('evaluate_scores', refine)
         two_opt = _check_two_opt('evaluate_scores', two_opt)
+        faq = _check_faq('evaluate_scores', faq)
     s, nvalid, labels, bins, B, N, live = _score_args('evaluate_scores', scores, nvalid, labels, live, bins)
     dev = s.device
     if meter is None:
@@ -626,7 +696,7 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
         ranks = None if rank_meter is None else _rank_launches(s, nvalid, labels, bins, B, N, live, rank_meter)
         decode = None
         if qap_meter is not None:
-            decode = _decode_launches(*bits, assign, nvalid, labels, bins, B, N, live, qap_meter, refine, two_opt)
+            decode = _decode_launches(*bits, assign, nvalid, labels, bins, B, N, live, qap_meter, refine, two_opt, faq, s)
     n = nvalid if nvalid is not None else torch.full((B,), N, **i32)
     out = {'ce': pair_ce, 'n': n, 'correct_max': pair_max, 'correct_lsap': correct, 'assign': assign, 'meter': meter}
     if ranks is not None:

@@ -50,11 +50,16 @@ host route is a numpy restatement with the same delta evaluation, not a call int
 ``faq`` (``csrc/qap_faq.hip``; not in the reference, whose paper compares against it) is SciPy's other -- and default -- method, the
 Fast Approximate QAP algorithm: Frank-Wolfe on the relaxed objective, needing no model and no starting matching; ``two_opt`` /
 ``two_opt_weighted`` on its `perm` is SciPy's documented recipe.  See its docstring.
+
+``sinkhorn`` (``csrc/sinkhorn.hip``) turns a batch of scores into doubly stochastic matrices with one launch -- the start ``faq``
+takes from a model (``faq(..., P0=sinkhorn(scores)['P'])``), and the first step of the ``faq=`` stage of
+``evaluation.decode_scores``.
 """
 import numpy as np
 import torch
 
 from . import _lib
+from .masked import MaskedTensor
 from .metrics import count_matches, labels_tensor, lsap_device
 
 NOT_A_REPRESENTATION = ('the batch is NOT the tensor representation of a 0/1 adjacency (channel 0 in {0, 1}, channel 1 = '
@@ -370,6 +375,68 @@ def faq(adj1, adj2, nvalid=None, labels=None, P0='barycenter', maxiter=30, tol=0
     out['acc'] = count_matches(out['perm'], labels, nv).to(torch.int64)
     if flag is not None:
         raise_if_bad(flag)
+    return out
+
+
+def check_sinkhorn(who, tau, iters):
+    """tau > 0 (finite), iters an integer >= 1, else ValueError -> (float tau, int iters)"""
+    if isinstance(tau, bool) or not isinstance(tau, (int, float, np.floating, np.integer)) or not 0 < tau < float('inf'):
+        raise ValueError("%s: 'tau' must be a positive finite number, got %r" % (who, tau))
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 1:
+        raise ValueError("%s: 'iters' must be an integer >= 1, got %r" % (who, iters))
+    return float(tau), int(iters)
+
+
+def sinkhorn_device(s, nv, tau, iters):
+    """fgnn_sinkhorn on (B, N, N) fp32 device scores (read in place when the rows are contiguous, pitched views included) ->
+    {'P': (B, N, N) fp32, 'err': (B,) fp32, 'status': (B,) int32} as the launch wrote them; never synchronises."""
+    B, N = s.shape[0], s.shape[-1]
+    dev = s.device
+    if not _chan0_ok(s):
+        s = s.contiguous()
+    P = torch.empty(B, N, N, dtype=torch.float32, device=dev)
+    err = torch.empty(B, dtype=torch.float32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.call('fgnn_sinkhorn', _lib.ptr(s), s.stride(0) if B > 1 else N * s.stride(-2), s.stride(-2), _lib.ptr(nv), B, N, tau, iters,
+              _lib.ptr(P), _lib.ptr(err), _lib.ptr(status), _lib.stream_ptr())
+    return {'P': P, 'err': err, 'status': status}
+
+
+def sinkhorn(scores, nvalid=None, tau=1.0, iters=20):
+    """Sinkhorn normalisation of every pair's scores (``csrc/sinkhorn.hip``): with Z = scores / tau on the n_b x n_b corner and
+    f = g = 0, `iters` times f_i = -LSE_j(Z_ij + g_j), then g_j = -LSE_i(Z_ij + f_i); P_ij = exp(Z_ij + f_i + g_j) on the corner,
+    exactly 0 around it.  The columns of P sum to 1 (g came last), the rows within `err`.  The start ``faq`` takes from a model:
+    ``faq(b1, b2, nvalid, P0=sinkhorn(scores, nvalid)['P'])``.
+    scores: a (B, N, N) floating-point tensor or a MaskedTensor of one (its vertex counts are used unless nvalid is given); nvalid:
+    a (B,) integer tensor of vertex counts, clamped to [0, N].  Nothing outside a pair's corner is read.  tau <= 0 and iters < 1
+    raise ValueError.
+    -> {'P': (B, N, N) fp32, 'err': (B,) fp32 = max_i |sum_j P_ij - 1|, 'status': (B,) int64} on the scores' device.  -inf scores are
+    legal and give P = 0 there.  status 1 marks a degenerate pair -- a NaN or a +inf in the corner, a row or a column without a
+    finite entry, or n_b = 0: its P is 1 / n_b on the corner (the barycenter, so a following `faq` always has a valid start) and
+    its err 0.  Every other pair has status 0.
+    The device route is ONE launch, in fp32 with max-subtracted LSEs in a fixed order: bit-identical from run to run, a pair's
+    result independent of the batch around it; it never synchronises.  CPU tensors and N > 256 take a host route, the same
+    recurrence in numpy float64; there P and err are float64.  (The degenerate test looks at Z: scores whose quotient by tau
+    overflows fp32 count as +inf on the device.)"""
+    tau, iters = check_sinkhorn('sinkhorn', tau, iters)
+    if isinstance(scores, MaskedTensor):
+        if nvalid is None:
+            nvalid = scores.nvalid
+        scores = scores.tensor.rename(None)
+    if not torch.is_tensor(scores) or scores.dim() != 3 or scores.shape[1] != scores.shape[2] or not scores.is_floating_point():
+        raise ValueError('sinkhorn: expected (B, N, N) floating-point scores, got %s'
+                         % (tuple(scores.shape) if torch.is_tensor(scores) else type(scores).__name__,))
+    B, N = scores.shape[0], scores.shape[-1]
+    if B < 1 or N < 1:
+        raise ValueError('sinkhorn: empty batch %s' % (tuple(scores.shape),))
+    if nvalid is not None and (not torch.is_tensor(nvalid) or tuple(nvalid.shape) != (B,) or nvalid.is_floating_point()):
+        raise ValueError('sinkhorn: nvalid must be a (%d,) integer tensor' % B)
+    scores = scores.detach()
+    if _on_host(scores, N):
+        return _sinkhorn_host(scores, nvalid, tau, iters)
+    with torch.cuda.device(scores.device):
+        out = sinkhorn_device(scores.to(torch.float32), _nv32(nvalid, scores.device), tau, iters)
+    out['status'] = out['status'].to(torch.int64)
     return out
 
 
@@ -841,6 +908,34 @@ def _faq_host(adj1, adj2, nvalid, labels, p0, assign0, maxiter, tol, weighted, r
     if return_P:
         res['P'] = torch.from_numpy(Ps)
     return res
+
+
+def _sinkhorn_host(scores, nvalid, tau, iters):
+    B, N = scores.shape[0], scores.shape[-1]
+    sizes = _sizes(nvalid, B, N)
+    S = scores.cpu().double().numpy()
+    P, err, status = np.zeros((B, N, N)), np.zeros(B), np.zeros(B, dtype=np.int64)
+    for b, n in enumerate(sizes):
+        Z = S[b, :n, :n] / tau
+        finite = np.isfinite(Z)
+        if n == 0 or bool((np.isnan(Z) | (Z == np.inf)).any()) or not finite.any(1).all() or not finite.any(0).all():
+            status[b] = 1
+            if n:
+                P[b, :n, :n] = 1.0 / n
+            continue
+        f, g = np.zeros(n), np.zeros(n)
+        with np.errstate(divide='ignore'):                         # (log 0 never happens: every sum holds its maximum's exp(0))
+            for _ in range(iters):
+                X = Z + g[None, :]
+                m = X.max(1)
+                f = -(m + np.log(np.exp(X - m[:, None]).sum(1)))
+                X = Z + f[:, None]
+                m = X.max(0)
+                g = -(m + np.log(np.exp(X - m[None, :]).sum(0)))
+        P[b, :n, :n] = np.exp(Z + f[:, None] + g[None, :])
+        err[b] = np.abs(P[b, :n, :n].sum(1) - 1.0).max()
+    dev = scores.device
+    return {'P': torch.from_numpy(P).to(dev), 'err': torch.from_numpy(err).to(dev), 'status': torch.from_numpy(status).to(dev)}
 
 
 def _all_acc_qap_host_w(scores, adj1, adj2, nvalid, labels=None):

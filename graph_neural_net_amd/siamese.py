@@ -133,7 +133,7 @@ class Siamese_Node_Exp(nn.Module):
             return MaskedTensor(scores, nvalid, (1, 2), x1.base_name)
         return scores
 
-    def match(self, x1, x2, refine=0, weighted=False, labels=None, two_opt=False):
+    def match(self, x1, x2, refine=0, weighted=False, labels=None, two_opt=False, faq=None):
         """Decode a batch: the eager forward under no_grad (no `.grad` is touched), the Hungarian matching of -log_softmax(scores)
         and the reference's evaluation of it (toolbox/metrics.py:168-193 all_acc_qap), all on the device (qap.py).  Takes what
         `forward` takes.  Returns a dict: scores ((bs, n, n) tensor or MaskedTensor), assign ((bs, n) int32: the matched column of
@@ -155,9 +155,20 @@ class Siamese_Node_Exp(nn.Module):
         two_opt=True ends the decode in the pairwise-exchange search of qap.two_opt (one launch), started from the refinement's perm,
         or from assign when refine = 0: the dict gains -- as qap.two_opt names them -- perm (the polished matching, in place of the
         refinement's), qap_2opt (its objective, in the unit of qap), acc_2opt (its rows that meet the labels, or the identity), swaps,
-        nit and status.  0/1 batches only: with weighted=True it is refused."""
+        nit and status.  0/1 batches only: with weighted=True it is refused.
+
+        faq (None, True or the dict evaluation.decode_scores takes) runs the Fast Approximate QAP stage after the Hungarian matching
+        and before refine and two_opt, which then start from its matching: the Sinkhorn projection of the scores (or the barycenter)
+        as the start, the chain of qap.faq, and where that chain reports status 2 the stage keeps assign.  The dict gains perm (the
+        stage's matching, until a later stage replaces it), qap_faq and acc_faq (int64: its objective in the unit of qap, its rows
+        that meet the labels or the identity), faq_perm, faq_nit, faq_status (as the chain left them) and sinkhorn_err (None with the
+        barycenter).  0/1 batches only: with weighted=True it is refused."""
         if two_opt and weighted:
             raise NotImplementedError('match: two_opt=True runs on 0/1 adjacency only, not with weighted=True')
+        if faq is not None and weighted:
+            raise NotImplementedError('match: faq= runs on 0/1 adjacency only, not with weighted=True')
+        from .evaluation import _check_faq, _faq_launches
+        faq = _check_faq('match', faq)
         a1, a2 = _unwrap_input(x1), _unwrap_input(x2)
         with torch.no_grad():
             scores = self(a1, a2)
@@ -185,11 +196,17 @@ class Siamese_Node_Exp(nn.Module):
             if labels is not None:
                 correct, obj['planted'] = count_matches(assign, labels, nv), qap.objective_bits(b1, b2, labels, nv)['qap']
             out = {'scores': scores, 'assign': assign, 'acc': correct.to(torch.int64), 'qap': obj['qap'], 'planted': obj['planted']}
+            if faq is not None or two_opt:
+                target = labels if labels is not None else torch.arange(s.shape[-1], dtype=torch.int32, device=dev).expand_as(assign).contiguous()
+            if faq is not None:
+                st = _faq_launches(b1, b2, s.detach().float(), assign, obj['qap'].to(torch.int32), nv, s.shape[0], s.shape[-1], faq)
+                out.update({'perm': st['perm'], 'qap_faq': st['qap'].to(torch.int64),
+                            'acc_faq': count_matches(st['perm'], target, nv).to(torch.int64), 'faq_perm': st['faq_perm'],
+                            'faq_nit': st['faq_nit'], 'faq_status': st['faq_status'], 'sinkhorn_err': st['sinkhorn_err']})
             if refine:
-                out.update(qap.greedy_bits(b1, b2, assign, int(refine), nv, labels))
+                out.update(qap.greedy_bits(b1, b2, out.get('perm', assign), int(refine), nv, labels))
             if two_opt:
                 t = qap.two_opt_bits(b1, b2, out.get('perm', assign), nv)
-                target = labels if labels is not None else torch.arange(s.shape[-1], dtype=torch.int32, device=dev).expand_as(assign).contiguous()
                 out.update({'perm': t['perm'], 'qap_2opt': t['qap'], 'acc_2opt': count_matches(t['perm'], target, nv).to(torch.int64),
                             'swaps': t['swaps'], 'nit': t['nit'], 'status': t['status']})
         self._raise_if_not_representation({'flag': flag})

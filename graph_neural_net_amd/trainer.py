@@ -609,37 +609,41 @@ class FgnnTrainer:
         return evaluate_scores(self._eval_forward(B, N, nvalid, x=x, bits=bits, spectral=spectral), nvalid=nvalid, **options)
 
     def eval_step_bits(self, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False,
-                       bins=None, rank_meter=None, qap_meter=None, refine=0, two_opt=False):
+                       bins=None, rank_meter=None, qap_meter=None, refine=0, two_opt=False, faq=None):
         """Forward-only evaluation of a batch handed over as train_step_bits takes it: the training engine's forward pass (a third of
         a step's work), then evaluation.evaluate_scores on its scores -- see there for labels, meter, live, hungarian,
         loss_on_labels, bins, rank_meter and the returned per-pair device tensors.  Nothing is read back; parameters, gradients and optimizer state keep their bits.
         qap_meter (a QapMeter; with bins= a BinnedQapMeter), refine: the decode chain of evaluation.decode_scores on the bit words
         handed in here and the solver's assignment (0/1 graphs only; needs hungarian=True).  None: nothing of it is launched.
         two_opt=True (with a qap_meter): the chain ends in the pairwise-exchange search of qap.two_opt_bits, one more launch, and the
-        meter's refined figures describe its matching."""
+        meter's refined figures describe its matching.
+        faq (with a qap_meter): None, True or the dict of evaluation.decode_scores -- the Fast Approximate QAP stage between the
+        Hungarian matching and the refinement, started from the Sinkhorn projection of this step's scores or from the barycenter."""
         return self._eval_step_words('eval_step_bits', bits1, bits2, nvalid, None, labels=labels, meter=meter, live=live,
                                      hungarian=hungarian, loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter,
-                                     qap_meter=qap_meter, refine=refine, two_opt=two_opt)
+                                     qap_meter=qap_meter, refine=refine, two_opt=two_opt, faq=faq)
 
     def eval_step_spectral(self, bits1, bits2, nvalid=None, n_powers=4, labels=None, meter=None, live=None, hungarian=True,
-                           loss_on_labels=False, bins=None, rank_meter=None, qap_meter=None, refine=0, two_opt=False):
+                           loss_on_labels=False, bins=None, rank_meter=None, qap_meter=None, refine=0, two_opt=False, faq=None):
         """The twin of eval_step_bits for spectral input: the forward pass runs on the features L, ..., L^n_powers of the bit words
         (engine.forward(spectral=...), as train_step_spectral), everything after the scores is eval_step_bits'.
-        qap_meter, refine, two_opt: the decode runs on the BIT WORDS handed in here -- the QAP objective on the adjacency W, not on the
+        qap_meter, refine, two_opt, faq: the decode runs on the BIT WORDS handed in here -- the QAP objective on the adjacency W, not on the
         normalised L the model sees.  On regular graphs L = W / d, so the ratio to the planted objective is the one the reference
         reports for its spectral pairs; the reference's literal decode on channel 0 of the features stays what
         ``match(..., weighted=True)`` computes per batch."""
         n_powers = self._check_features('eval_step_spectral', n_powers)
         return self._eval_step_words('eval_step_spectral', bits1, bits2, nvalid, n_powers, labels=labels, meter=meter, live=live,
                                      hungarian=hungarian, loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter,
-                                     qap_meter=qap_meter, refine=refine, two_opt=two_opt)
+                                     qap_meter=qap_meter, refine=refine, two_opt=two_opt, faq=faq)
 
-    def _eval_step_words(self, who, bits1, bits2, nvalid, n_powers, qap_meter=None, refine=0, two_opt=False, **options):
+    def _eval_step_words(self, who, bits1, bits2, nvalid, n_powers, qap_meter=None, refine=0, two_opt=False, faq=None, **options):
         """eval_step_bits (n_powers None) / eval_step_spectral: one body, the engine keyword differs"""
         B, N = self._bits_shape(who, bits1, bits2)
         decode = {} if qap_meter is None and not refine else {'qap_meter': qap_meter, 'pair_bits': (bits1, bits2), 'refine': refine}
         if two_opt is not False:
             decode = dict(decode, qap_meter=qap_meter, two_opt=two_opt)
+        if faq is not None:
+            decode = dict(decode, qap_meter=qap_meter, faq=faq)
         b = torch.cat([bits1, bits2]).contiguous()
         src = {'bits': b} if n_powers is None else {'spectral': (b, n_powers)}
         return self._eval_tail(B, N, nvalid, **src, **options, **decode)
@@ -655,7 +659,7 @@ class FgnnTrainer:
                                hungarian=hungarian, loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter)
 
     def evaluate(self, generator, sampler, batch_size, epoch=0, hungarian=True, meter=None, permute=False, loss_on_labels=False,
-                 rank_meter=None, qap_meter=None, refine=0, features=None, n_powers=4, two_opt=False):
+                 rank_meter=None, qap_meter=None, refine=0, features=None, n_powers=4, two_opt=False, faq=None):
         """One pass over this rank's examples of `sampler` (sampler.EpochSampler; shuffle=False is the reference's validation
         loader): per step ``eval_step_bits(*generator.bits(index=sampler.batch_index(epoch, step, batch_size)))`` with the generator's
         vertex counts and, with permute=True, its planted labels.  Every example counts exactly once: the positions with which a
@@ -671,6 +675,8 @@ class FgnnTrainer:
         and all_greedy_losses_acc; 0/1 graphs only) -- and is summed over the ranks like the meter.  Needs hungarian=True.
         two_opt=True (with a qap_meter): every step's chain ends in the pairwise-exchange search (evaluation.decode_scores), and the
         meter's 'refined_acc', 'refined_qap_ratio' and 'improved' describe the matching it leaves.
+        faq (with a qap_meter): None, True or the dict of evaluation.decode_scores -- every step's chain runs the Fast Approximate
+        QAP stage after the Hungarian matching; the refined figures describe the last stage of the chain that ran.
         features='spectral', n_powers: the steps are eval_step_spectral on the same words (the decode of a qap_meter stays on the
         adjacency, see there).  None: eval_step_bits, as before."""
         from .evaluation import EvalMeter, QapMeter, RankMeter
@@ -690,19 +696,23 @@ class FgnnTrainer:
                 if live:        # (0: a rank past the end of the data in the last global step; its index is never made)
                     yield live, None, {'index': sampler.batch_index(epoch, step, B), 'permute': permute}
         return self._eval_epoch(generator, batches(), meter, rank_meter, dp.world_size() > 1, hungarian, loss_on_labels, qap_meter,
-                                refine, spec, two_opt)
+                                refine, spec, two_opt, faq)
 
     def _eval_epoch(self, generator, batches, meter, rank_meter, reduce, hungarian, loss_on_labels, qap_meter=None, refine=0, spec=None,
-                    two_opt=False):
+                    two_opt=False, faq=None):
         """The loop of evaluate and noise_curve.  batches: per step that has a live pair (live, bins, the keyword arguments of
         generator.bits); reduce: sum the meters over the ranks at the end; spec: None or the n_powers of spectral steps.  -> meter"""
         if qap_meter is None and refine:
             raise ValueError('FgnnTrainer: refine= belongs to a qap_meter')
         if qap_meter is None and two_opt:
             raise ValueError('FgnnTrainer: two_opt= belongs to a qap_meter')
+        if qap_meter is None and faq is not None:
+            raise ValueError('FgnnTrainer: faq= belongs to a qap_meter')
         decode = {} if qap_meter is None else {'qap_meter': qap_meter, 'refine': refine}
         if two_opt is not False:
             decode['two_opt'] = two_opt
+        if faq is not None:
+            decode['faq'] = faq
         for live, bins, bits_kw in batches:
             b1, b2, nv, *labels = generator.bits(**bits_kw)
             kw = dict(nvalid=nv, labels=labels[0] if labels else None, meter=meter, live=live, hungarian=hungarian,
@@ -731,7 +741,7 @@ class FgnnTrainer:
 
     def noise_curve(self, generator, noises, num_examples, batch_size, hungarian=True, permute=False, loss_on_labels=False,
                     rank=None, world_size=None, meter=None, rank_meter=None, qap_meter=None, refine=0, features=None, n_powers=4,
-                    two_opt=False):
+                    two_opt=False, faq=None):
         """The reference's result figure (README.md, "Results": a trained model evaluated across noise levels; per level
         toolbox/metrics.py:144-166) in one pass: the first num_examples pairs of `generator` at each of the K = len(noises) noise
         levels -- the SAME parent graphs at every level, a paired design -- through full batches of mixed levels
@@ -748,7 +758,7 @@ class FgnnTrainer:
         rank_meter: a BinnedRankMeter of K records that takes the rank metrics of every level from the same steps; it is summed
         over the ranks where the meter is.
         qap_meter: a BinnedQapMeter of K records that takes the decode of every level (see `evaluate`; refine: its rounds of
-        greedy refinement; two_opt: the pairwise-exchange search at its end) from the same steps -- the QAP ratio across noise
+        greedy refinement; two_opt: the pairwise-exchange search at its end; faq: the Fast Approximate QAP stage before them) from the same steps -- the QAP ratio across noise
         levels; it is summed over the ranks where the meter is.
         features='spectral', n_powers: as in `evaluate`."""
         from .evaluation import BinnedEvalMeter, BinnedQapMeter, BinnedRankMeter
@@ -777,10 +787,10 @@ class FgnnTrainer:
                 if live:        # (0: a rank past the end of the examples in the last global step)
                     yield live, level, {'index': pair, 'levels': levels, 'level': level, 'permute': permute}
         return self._eval_epoch(generator, batches(), meter, rank_meter, dp.world_size() > 1 and sampler.world_size == dp.world_size(),
-                                hungarian, loss_on_labels, qap_meter, refine, spec, two_opt)
+                                hungarian, loss_on_labels, qap_meter, refine, spec, two_opt, faq)
 
     def fit(self, train_gen, train_sampler, val_gen, val_sampler, epochs, batch_size, scheduler=None, permute=False, exact_last=False,
-            rank_ks=None, decode_refine=None, features=None, n_powers=4, decode_two_opt=False):
+            rank_ks=None, decode_refine=None, features=None, n_powers=4, decode_two_opt=False, decode_faq=None):
         """The reference's training loop around its scheduler (models/trainers.py:92-104): per epoch train_epoch, evaluate, ONE host
         read (the validation record), scheduler.step(val_loss).  scheduler=None: optim.ReduceLROnPlateau with the reference's
         settings, driving self.opt.lr (the next step pushes a changed rate to the device).  Returns the per-epoch history: dicts
@@ -799,10 +809,13 @@ class FgnnTrainer:
         decode_two_opt=True (with decode_refine, which may be 0): the validation decode ends in the pairwise-exchange search
         (evaluate(two_opt=True)); 'val_refined_acc' is then reported for every T and describes the matching the search leaves, and
         'val_refined_qap_ratio' is its objective over the planted one.
+        decode_faq (with decode_refine, which may be 0): None, True or the dict of evaluation.decode_scores -- the validation decode
+        runs the Fast Approximate QAP stage (evaluate(faq=...)); 'val_refined_acc' and 'val_refined_qap_ratio' are then reported
+        for every T, as with decode_two_opt, and describe the last stage of the chain.
         features='spectral', n_powers: training and validation run on the spectral features of the generators' pairs (train_epoch /
         evaluate with the same arguments)."""
         fkw = {} if features is None else {'features': features, 'n_powers': self._features('fit', features, n_powers)}
-        from .evaluation import EvalMeter, QapMeter, RankMeter, _check_refine, qap_result, rank_result, read_records, record_result
+        from .evaluation import EvalMeter, QapMeter, RankMeter, _check_faq, _check_refine, qap_result, rank_result, read_records, record_result
         if scheduler is None:
             from .optim import ReduceLROnPlateau
             scheduler = ReduceLROnPlateau(self.opt)
@@ -812,12 +825,17 @@ class FgnnTrainer:
             decode_refine = _check_refine('FgnnTrainer.fit', decode_refine)
         if decode_two_opt and decode_refine is None:
             raise ValueError('FgnnTrainer.fit: decode_two_opt= belongs to a decode_refine (which may be 0)')
+        if decode_faq is not None and decode_refine is None:
+            raise ValueError('FgnnTrainer.fit: decode_faq= belongs to a decode_refine (which may be 0)')
+        decode_faq = _check_faq('FgnnTrainer.fit', decode_faq)
         qap_meter = None if decode_refine is None else QapMeter(self.params.device)
         extra = [m for m in (rank_meter, qap_meter) if m is not None]
         own = EvalMeter(self.params.device) if extra else None                       # (read together with the other meters)
         decode = {} if qap_meter is None else {'qap_meter': qap_meter, 'refine': decode_refine}
         if decode_two_opt is not False:
             decode['two_opt'] = decode_two_opt
+        if decode_faq is not None:
+            decode['faq'] = decode_faq
         for epoch in range(int(epochs)):
             for m in extra + [own] * bool(extra):
                 m.reset()
@@ -839,9 +857,9 @@ class FgnnTrainer:
             if qap_meter is not None:
                 qres = qap_result(others[id(qap_meter)])
                 history[-1]['val_qap_ratio'], history[-1]['val_recovered'] = qres['qap_ratio'], qres['recovered']
-                if decode_refine > 0 or decode_two_opt:
+                if decode_refine > 0 or decode_two_opt or decode_faq is not None:
                     history[-1]['val_refined_acc'] = qres['refined_acc']
-                if decode_two_opt:
+                if decode_two_opt or decode_faq is not None:
                     history[-1]['val_refined_qap_ratio'] = qres['refined_qap_ratio']
         return history
 

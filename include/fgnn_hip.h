@@ -1035,6 +1035,26 @@ int fgnn_qapw_faq(const float *a1, const float *a2, long long gstride, int ld, c
                   const int *assign0 /* optional, (B,N) */, const int *nvalid, int B, int N, int maxiter, float tol, void *ws,
                   long long ws_bytes, int *perm, int *nit, int *status, float *p_out /* optional, (B,N,N) */, void *stream);
 
+/* ---- Sinkhorn normalisation of scores (csrc/sinkhorn.hip): the doubly stochastic start fgnn_qapw_faq takes from a model's scores,
+ * one workgroup per pair, the whole iteration in ONE launch, in the log domain --------------------------------------------------
+ * S: B pairs of (N, N) fp32 scores, row pitch ld >= N, pairs pair_stride >= N ld floats apart.  nvalid (optional, int32[B]): pair b
+ * is the n_b x n_b corner (n_b clamped to [0, N]); nothing outside it is read (it may hold NaN).  tau > 0 (finite), iters >= 1.
+ * With Z = S / tau (a correctly rounded fp32 division), f = 0, g = 0, `iters` times:
+ *     f_i = -LSE_j(Z_ij + g_j) over j < n_b,  then  g_j = -LSE_i(Z_ij + f_i) over i < n_b          (every LSE max-subtracted)
+ * Outputs (all required): P (B, N, N) fp32, contiguous: P_ij = exp((Z_ij + f_i) + g_j) on the corner and exactly 0.0f around it --
+ * every element is written; the columns of the corner sum to 1 up to rounding (g came last);  err[b] fp32 = max_i |sum_j P_ij - 1|,
+ * the row sums of the P written, added in a fixed order;  status[b] int32.  -inf entries are legal and give P = 0 there.
+ * A pair is degenerate -- status 1, P = 1 / n_b on the corner (the barycenter of fgnn_qapw_faq; nothing for n_b = 0), err = 0 -- if
+ * its corner of Z holds a NaN or a +inf, or it has a row or a column without a finite entry, or n_b = 0; every other pair has
+ * status 0.  So a following fgnn_qapw_faq always has a valid p0.
+ * Every reduction has a fixed order that depends on n_b and N only (no float atomics): the output is bit-identical from run to
+ * run, and a pair's does not depend on B or on its place in the batch.  N <= FGNN_QAP_MAX_N.  Z is resident in LDS for
+ * N <= FGNN_SINKHORN_LDS_MAX_N (192 x 192 floats = 144 KiB of the CU's 160 KiB, plus 9.5 KiB of vectors); above, S is re-read in
+ * place in every pass.  No workspace, no allocation, no host copy, no synchronisation: capturable. */
+#define FGNN_SINKHORN_LDS_MAX_N 192
+int fgnn_sinkhorn(const float *S, long long pair_stride, int ld, const int *nvalid /* optional */, int B, int N, float tau, int iters,
+                  float *P, float *err, int *status, void *stream);
+
 /* ---- spectral input features (csrc/spectral.hip; loaders/data_generator.py:221-232 make_laplacian / make_spectral_feature, the
  * input of QAP_spectralGenerator) ---------------------------------------------------------------------------------------------
  * bits: (G, N, ceil(N/32)) words, bit j of word row i = W[i][j] (the layout of fgnn_expand_adjacency); nvalid (optional, int32[G]):
