@@ -21,6 +21,7 @@ FGNN_LSAP_MAX_N = 2048       # include/fgnn_hip.h: largest graph of fgnn_lsap_ac
 FGNN_MAX_LEVELS = 64         # include/fgnn_hip.h: noise levels of fgnn_pairgen_levels, records of fgnn_eval_fold_bins
 FGNN_QAP_MAX_N = 256         # include/fgnn_hip.h: largest graph of the fgnn_qap_* / fgnn_greedy_qap kernels
 FGNN_QAPW_MAX_N = 256        # include/fgnn_hip.h: largest graph of the fgnn_qapw_* / fgnn_greedy_qapw kernels (fp32 weights)
+FGNN_SEED_MAX_N = 256        # include/fgnn_hip.h: largest graph of the fgnn_seed_* kernels
 FGNN_SINKHORN_LDS_MAX_N = 192   # include/fgnn_hip.h: largest graph whose scores fgnn_sinkhorn keeps in LDS
 FGNN_SPECTRAL_MAX_N = 256    # include/fgnn_hip.h: largest graph of fgnn_spectral_features
 FGNN_SPECTRAL_MAX_POWERS = 8
@@ -307,6 +308,13 @@ _SIGNATURES = {
     'fgnn_qapw_faq_ws_bytes': [_I, _I],
     'fgnn_qapw_faq': [_VP, _VP, _LL, _I, _VP, _VP, _VP, _I, _I, _I, _F, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
     'fgnn_sinkhorn': [_VP, _LL, _I, _VP, _I, _I, _F, _I, _VP, _VP, _VP, _VP],
+    'fgnn_seed_index': [_VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    'fgnn_seed_gather': [_VP, _LL, _I, _VP, _VP, _VP, _I, _I, _VP, _VP],
+    'fgnn_seed_const': [_VP, _VP, _LL, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP],
+    'fgnn_qapw_faq_seeded_ws_bytes': [_I, _I],
+    'fgnn_qapw_faq_seeded': [_VP, _VP, _LL, _I, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _F, _VP, _LL, _VP, _VP, _VP, _VP, _VP, _VP],
+    'fgnn_qap_2opt_seeded': [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP],
+    'fgnn_reveal_seeds': [C.c_ulonglong, _LL, _VP, _VP, _VP, _I, _I, _I, _VP, _VP],
     'fgnn_planted_perm': [C.c_ulonglong, _LL, _VP, _VP, _I, _I, _VP, _VP],
     'fgnn_relabel_bits': [_VP, _VP, _VP, _I, _I, _VP, _VP],
     'fgnn_relabel_dense': [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP],
@@ -350,7 +358,7 @@ _SIGNATURES = {
 }
 _RESTYPES = {'fgnn_last_error': C.c_char_p, 'fgnn_block1_struct_ws_floats': C.c_longlong, 'fgnn_greedy_qap_ws_bytes': C.c_longlong,
              'fgnn_greedy_qapw_ws_bytes': C.c_longlong, 'fgnn_qapw_2opt_ws_bytes': C.c_longlong,
-             'fgnn_qapw_faq_ws_bytes': C.c_longlong}
+             'fgnn_qapw_faq_ws_bytes': C.c_longlong, 'fgnn_qapw_faq_seeded_ws_bytes': C.c_longlong}
 EXPORTS = tuple(_SIGNATURES)
 
 _lib = None

@@ -166,7 +166,59 @@ __global__ __launch_bounds__(256) void accuracy_max_labels_kernel(const float *s
     if (threadIdx.x == 0) correct[b] = red[0] + red[1] + red[2] + red[3];
 }
 
+// One wave per pair: min(count, n) rows of labels, uniform without replacement -- the top `cnt` steps of planted_perm_kernel's
+// Fisher-Yates on the identity, on stream FGNN_SEEDS_STREAM: for k = n-1 .. n-cnt, j = (u32_k (k + 1)) >> 32, swap p[k], p[j]; the
+// rows revealed are p[n-cnt .. n-1].  seeds[i] = labels[i] on them, -1 on every other entry.
+__global__ __launch_bounds__(64) void reveal_seeds_kernel(unsigned long long seed, long long first, const long long *index,
+                                                          const int *labels, const int *nvalid, int N, int count, int *seeds) {
+    __shared__ int p[PL_MAX_N], chosen[PL_MAX_N];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const long long k = index ? index[b] : first + b;
+    int *out = seeds + (long long)b * N;
+    if (k < 0) {                 // a caller error, as in planted_perm_kernel: nothing revealed (wave-uniform exit)
+        for (int i = lane; i < N; i += 64) out[i] = -1;
+        return;
+    }
+    const int n = corner_of(nvalid, b, N), low = n - min(max(count, 0), n), last = max(low, 1);
+    const Pair pr{seed, (unsigned long long)k};
+    for (int i = lane; i < n; i += 64) {
+        p[i] = i;
+        chosen[i] = 0;
+    }
+    __syncthreads();
+    for (int top = n - 1; top >= last; top -= 64) {
+        const int i = top - lane;
+        const int rj = i >= last ? below(pr.draw(FGNN_SEEDS_STREAM, (unsigned long long)i), i + 1) : 0;
+        const int cnt = min(64, top - last + 1);
+        for (int l = 0; l < cnt; ++l) {
+            const int ii = top - l, j = __builtin_amdgcn_readlane(rj, l);
+            const int pi = uni(p[ii]), pj = uni(p[j]);
+            if (lane == 0) {
+                p[ii] = pj;
+                p[j] = pi;
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = low + lane; i < n; i += 64) chosen[p[i]] = 1;
+    __syncthreads();
+    for (int i = lane; i < N; i += 64) out[i] = (i < n && chosen[i]) ? labels[(long long)b * N + i] : -1;
+}
+
 }  // namespace
+
+extern "C" int fgnn_reveal_seeds(unsigned long long seed, long long first, const long long *index, const int *labels, const int *nvalid,
+                                 int B, int N, int count, int *seeds, void *stream) {
+    FGNN_CHECK(B >= 0 && N >= 1 && N <= FGNN_PLANTED_MAX_N, "fgnn_reveal_seeds: B=%d, N=%d (1 <= N <= %d)", B, N, FGNN_PLANTED_MAX_N);
+    FGNN_CHECK(index || first >= 0, "fgnn_reveal_seeds: first=%lld < 0", first);
+    FGNN_CHECK(count >= 0, "fgnn_reveal_seeds: count=%d < 0", count);
+    if (B == 0) return 0;
+    FGNN_CHECK(labels && seeds, "fgnn_reveal_seeds: NULL labels or output");
+    hipLaunchKernelGGL(reveal_seeds_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, seed, first, index, labels, nvalid, N, count,
+                       seeds);
+    FGNN_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" int fgnn_planted_perm(unsigned long long seed, long long first, const long long *index, const int *nvalid, int B, int N,
                                  int *labels, void *stream) {

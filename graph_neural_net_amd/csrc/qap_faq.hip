@@ -267,6 +267,195 @@ __global__ __launch_bounds__(FQ_THREADS) void faq_finish_kernel(const float *P, 
 constexpr long long WS_ALIGN = 256;
 long long ws_round(long long x) { return (x + WS_ALIGN - 1) / WS_ALIGN * WS_ALIGN; }
 
+// ---- seeds (fgnn_qapw_faq_seeded): the chain above on the free block A22, B22 with n_b := u_b, the seeds' constant term C in the
+// gradient, G = C + A22 P B22^T + A22^T P B22, and its linear term in the line search.  The kernels above run as they are wherever
+// the seeds change nothing (the start, the first product, -P, the outputs of the free block); the three below are the seeded
+// forms of the second product and of the step, and the way in and out of free coordinates.
+
+// One workgroup per pair: what the start needs in free coordinates.  ok = the seeds are valid and assign0 (if given) holds them on
+// every seeded row; ueff = u_b for such a pair, else 0 (the chain above then freezes it); assign_s[r] = the rank among the free
+// columns of assign0[free_a[r]], -1 where that is no free column (the start refuses the pair: status 2).
+__global__ __launch_bounds__(FQ_THREADS) void faq_seed_start_kernel(const int *seeds, const int *assign0, const int *nvalid, int N,
+                                                                    const int *free_a, const int *free_b, const int *nfree,
+                                                                    const int *valid, int *ok, int *ueff, int *assign_s) {
+    __shared__ int col_rank[FGNN_QAPW_MAX_N];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = corner_of(nvalid, b, N), good = valid[b], u = good ? min(max(nfree[b], 0), n) : 0;
+    const long long o = (long long)b * N;
+    int bad = 0;
+    if (assign0) {
+        for (int k = tid; k < N; k += FQ_THREADS) col_rank[k] = -1;
+        __syncthreads();
+        for (int c = tid; c < u; c += FQ_THREADS) col_rank[free_b[o + c]] = c;
+        __syncthreads();
+        for (int k = tid; k < n; k += FQ_THREADS) {
+            const int s = seeds[o + k];
+            bad |= s >= 0 && assign0[o + k] != s;
+        }
+        for (int r = tid; r < N; r += FQ_THREADS) {
+            int v = -1;
+            if (r < u) {
+                const int p = assign0[o + free_a[o + r]];
+                if (p >= 0 && p < n) v = col_rank[p];
+            }
+            assign_s[o + r] = v;
+        }
+    }
+    bad = __syncthreads_or(bad);
+    if (tid == 0) {
+        ok[b] = good && !bad;
+        ueff[b] = good && !bad ? u : 0;
+    }
+}
+
+// faq_grad_kernel with the constant term: cost = -(chain + C), C added once, in the epilogue, to the finished fmaf chain.
+__global__ __launch_bounds__(FQ_THREADS) void faq_grad_seeded_kernel(const float *a1, long long gstride, int ld, const float *T,
+                                                                     const float *C, const int *nvc, const int *done, int N, float *cost) {
+    __shared__ float a_l[FQ_ROWS * FQ_PA];
+    __shared__ float b_l[FQ_KC * FQ_PB];
+    const int b = blockIdx.z, i0 = blockIdx.x * FQ_ROWS, c0 = blockIdx.y * FQ_COLS, tid = threadIdx.x;
+    if (done[b]) return;                        // uniform
+    const int n = nvc[b];
+    if (i0 >= n || c0 >= n) return;             // uniform
+    const float *A = a1 + (long long)b * gstride, *T0 = T + (long long)b * 2 * N * N, *T1 = T0 + (long long)N * N;
+    const int wv = tid >> 6, lane = tid & 63, h = lane >> 5, c = lane & 31;
+    const bool live = c0 + 32 * wv < n;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    tile_product<false, false>(acc, a_l, b_l, A, ld, T0, N, n, i0, c0, tid, live);
+    tile_product<true, false>(acc, a_l, b_l, A, ld, T1, N, n, i0, c0, tid, live);
+    const int gj = c0 + 32 * wv + c;
+    if (!live || gj >= n) return;
+    float *out = cost + (long long)b * N * N + gj;
+    const float *Cb = C + (long long)b * N * N + gj;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int gi = i0 + ch_of(r, h);
+        if (gi < n) out[(long long)gi * N] = -(acc[r] + Cb[(long long)gi * N]);
+    }
+}
+
+// faq_step_kernel with the linear term.  f(P) = q(P) + <C, P> with q(P) = tr(A22^T P B22 P^T), whose gradient is G - C, so
+// <G - C, P> = 2 q(P), and with R = P - Q: f(Q + x R) = f(Q) + b x + a x^2,
+//     a = (<G,P> - <C,P>) / 2 - (<G,Q> - <C,Q>) + q(Q),   b = (<G,Q> - <C,Q>) - 2 q(Q) + <C,P> - <C,Q>
+// (SciPy's a and b21 + b12 + b22a + b22b).  With C = 0 every sum and both coefficients have the bits of faq_step_kernel's.
+__global__ __launch_bounds__(FQ_THREADS) void faq_step_seeded_kernel(const float *a1, const float *a2, long long gstride, int ld,
+                                                                     const float *cost, const float *C, const int *q, const int *nvc,
+                                                                     int N, float tol, float *P, int *nvw, int *done, int *nit,
+                                                                     int *status) {
+    __shared__ int q_l[FGNN_QAPW_MAX_N];
+    __shared__ double red[FQ_THREADS / 64];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (done[b]) return;                        // uniform
+    const int n = nvc[b];
+    int bad = 0;
+    for (int k = tid; k < n; k += FQ_THREADS) {
+        const int p = q[(long long)b * N + k];
+        const bool ok = p >= 0 && p < n;
+        q_l[k] = ok ? p : 0;
+        bad |= !ok;
+    }
+    if (__syncthreads_or(bad)) {
+        if (tid == 0) {
+            done[b] = 1;
+            nvw[b] = 0;
+            nit[b] = 0;
+            status[b] = 2;
+        }
+        return;
+    }
+    const float *A = a1 + (long long)b * gstride, *Bm = a2 + (long long)b * gstride, *Gb = cost + (long long)b * N * N;
+    const float *Cb = C + (long long)b * N * N;
+    float *Pb = P + (long long)b * N * N;
+    double gp = 0.0, gq = 0.0, fq = 0.0, cp = 0.0, cq = 0.0;       // <G, P>, <G, Q>, q(Q), <C, P>, <C, Q>
+    for (int idx = tid; idx < n * n; idx += FQ_THREADS) {
+        const int i = idx / n, k = idx - i * n, qi = q_l[i];
+        const double g = -(double)Gb[(long long)i * N + k], cc = (double)Cb[(long long)i * N + k];
+        const double p = (double)Pb[(long long)i * N + k];
+        gp += g * p;
+        cp += cc * p;
+        if (k == qi) {
+            gq += g;
+            cq += cc;
+        }
+        fq += (double)A[(long long)i * ld + k] * (double)Bm[(long long)qi * ld + q_l[k]];
+    }
+    gp = block_sum(gp, red, tid);
+    gq = block_sum(gq, red, tid);
+    fq = block_sum(fq, red, tid);
+    cp = block_sum(cp, red, tid);
+    cq = block_sum(cq, red, tid);
+    const double a = 0.5 * (gp - cp) - (gq - cq) + fq, bb = (gq - cq) - 2.0 * fq + cp - cq;
+    double alpha;
+    if (a < 0.0 && 0.0 <= -bb / (2.0 * a) && -bb / (2.0 * a) <= 1.0) alpha = -bb / (2.0 * a);
+    else alpha = -(a + bb) < 0.0 ? 1.0 : 0.0;
+    double ss = 0.0;
+    for (int idx = tid; idx < n * n; idx += FQ_THREADS) {
+        const int i = idx / n, k = idx - i * n;
+        const double p = (double)Pb[(long long)i * N + k];
+        const float p1 = (float)(alpha * p + (1.0 - alpha) * (k == q_l[i] ? 1.0 : 0.0));
+        const double d = p - (double)p1;
+        ss += d * d;
+        Pb[(long long)i * N + k] = p1;
+    }
+    ss = block_sum(ss, red, tid);
+    if (tid == 0) {
+        nit[b] += 1;
+        if (sqrt(ss) / sqrt((double)n) < (double)tol) {
+            done[b] = 1;
+            nvw[b] = 0;
+            status[b] = 0;
+        }
+    }
+}
+
+// One workgroup per pair: out of free coordinates.  perm_s holds the free block's assignment as faq_finish_kernel left it.
+//   invalid seeds: perm = -1, nit 0, status 2;   assign0 against the seeds, or refused / no assignment (status 2 above): perm =
+//   assign0 (or -1), nit 0, status 2;   u_b = 0 < n_b: perm = seeds, nit 0, status 0;   n_b = 0: status 2, as without seeds;
+//   else perm[free_a[r]] = free_b[perm_s[r]] and perm[i] = seeds[i] on the seeded rows.  -1 past the corner.
+__global__ __launch_bounds__(FQ_THREADS) void faq_seed_finish_kernel(const int *seeds, const int *assign0, const int *nvalid, int N,
+                                                                     const int *free_a, const int *free_b, const int *nfree,
+                                                                     const int *nseed, const int *valid, const int *ok,
+                                                                     const int *perm_s, int *perm, int *nit, int *status,
+                                                                     int *seeded) {
+    __shared__ int row_rank[FGNN_QAPW_MAX_N];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = corner_of(nvalid, b, N), good = valid[b], agreed = ok[b], u = agreed ? min(max(nfree[b], 0), n) : 0;
+    const long long o = (long long)b * N;
+    const int st = status[b];
+    const bool trivial = agreed && u == 0 && n > 0, failed = !agreed || (!trivial && st == 2);
+    for (int k = tid; k < N; k += FQ_THREADS) row_rank[k] = -1;
+    __syncthreads();                             // (every thread has read status[b])
+    for (int r = tid; r < u; r += FQ_THREADS) row_rank[free_a[o + r]] = r;
+    __syncthreads();
+    for (int k = tid; k < N; k += FQ_THREADS) {
+        int v = -1;
+        if (k < n) {
+            const int s = seeds[o + k];
+            if (failed) {
+                v = (good && assign0) ? assign0[o + k] : -1;
+            } else if (s >= 0) {
+                v = s;
+            } else {
+                const int r = row_rank[k], c = r >= 0 ? perm_s[o + r] : -1;
+                v = (c >= 0 && c < u) ? free_b[o + c] : -1;
+            }
+        }
+        perm[o + k] = v;
+    }
+    if (tid == 0) {
+        if (failed) {
+            status[b] = 2;
+            nit[b] = 0;
+        } else if (trivial) {
+            status[b] = 0;
+            nit[b] = 0;
+        }
+        if (seeded) seeded[b] = nseed[b];
+    }
+}
+
 }  // namespace
 
 extern "C" long long fgnn_qapw_faq_ws_bytes(int B, int N) {
@@ -317,6 +506,80 @@ extern "C" int fgnn_qapw_faq(const float *a1, const float *a2, long long gstride
     FGNN_LAUNCH_CHECK();
     if ((rc = fgnn_lsap_accuracy(cost, bs, N, nvc, B, N, correct, perm, stream))) return rc;
     hipLaunchKernelGGL(faq_finish_kernel, dim3(B), dim3(FQ_THREADS), 0, st, P, assign0, nvc, N, perm, nit, status, p_out);
+    FGNN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" long long fgnn_qapw_faq_seeded_ws_bytes(int B, int N) {
+    if (B <= 0 || N <= 0) return 0;
+    // the chain's own workspace; A22, B22, C, the gathered p0; free_a, free_b, seed_a, seed_b, assign_s, perm_s; nfree, nseed, valid, ok, ueff
+    return fgnn_qapw_faq_ws_bytes(B, N) + 4 * ws_round((long long)B * N * N * 4) + 6 * ws_round((long long)B * N * 4) +
+           5 * ws_round((long long)B * 4);
+}
+
+extern "C" int fgnn_qapw_faq_seeded(const float *a1, const float *a2, long long gstride, int ld, const int *seeds, const float *p0,
+                                    int p0_free, const int *assign0, const int *nvalid, int B, int N, int maxiter, float tol, void *ws,
+                                    long long ws_bytes, int *perm, int *nit, int *status, int *seeded, float *p_out, void *stream) {
+    FGNN_CHECK(a1 && a2 && seeds && ws && perm && nit && status && B > 0 && N > 0, "fgnn_qapw_faq_seeded: bad arguments");
+    FGNN_CHECK(!(p0 && assign0), "fgnn_qapw_faq_seeded: at most one of p0 and assign0");
+    FGNN_CHECK(maxiter > 0 && tol > 0.f, "fgnn_qapw_faq_seeded: maxiter and tol must be positive (got %d, %g)", maxiter, (double)tol);
+    FGNN_CHECK(N <= FGNN_QAPW_MAX_N, "fgnn_qapw_faq_seeded: at most %d vertices per graph (got %d)", FGNN_QAPW_MAX_N, N);
+    FGNN_CHECK(B <= FQ_MAX_B, "fgnn_qapw_faq_seeded: at most %d pairs per call (got %d)", FQ_MAX_B, B);
+    FGNN_CHECK(ld >= N && gstride >= (long long)N * ld, "fgnn_qapw_faq_seeded: ld / gstride smaller than the matrices");
+    FGNN_CHECK(ws_bytes >= fgnn_qapw_faq_seeded_ws_bytes(B, N) && ((uintptr_t)ws & 15) == 0,
+               "fgnn_qapw_faq_seeded: the workspace needs %lld bytes, 16-byte aligned (got %lld)", fgnn_qapw_faq_seeded_ws_bytes(B, N),
+               ws_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    const long long mat = ws_round((long long)B * N * N * 4), vec = ws_round((long long)B * 4), lst = ws_round((long long)B * N * 4);
+    char *p = (char *)ws;
+    float *P = (float *)p;
+    p += mat;
+    float *T = (float *)p;
+    p += 2 * mat;
+    float *cost = (float *)p;
+    p += mat;
+    int *q = (int *)p;
+    p += lst;
+    int *nvc = (int *)p, *nvw = (int *)(p + vec), *done = (int *)(p + 2 * vec), *correct = (int *)(p + 3 * vec);
+    p += 4 * vec;
+    float *A22 = (float *)p, *B22 = (float *)(p + mat), *C = (float *)(p + 2 * mat), *P0 = (float *)(p + 3 * mat);
+    p += 4 * mat;
+    int *free_a = (int *)p, *free_b = (int *)(p + lst), *seed_a = (int *)(p + 2 * lst), *seed_b = (int *)(p + 3 * lst);
+    int *assign_s = (int *)(p + 4 * lst), *perm_s = (int *)(p + 5 * lst);
+    p += 6 * lst;
+    int *nfree = (int *)p, *nseed = (int *)(p + vec), *valid = (int *)(p + 2 * vec), *ok = (int *)(p + 3 * vec), *ueff = (int *)(p + 4 * vec);
+    const long long bs = (long long)N * N;
+    const dim3 tiles((N + FQ_ROWS - 1) / FQ_ROWS, (N + FQ_COLS - 1) / FQ_COLS, B);
+    int rc;
+    if ((rc = fgnn_seed_index(seeds, nvalid, B, N, nfree, nseed, free_a, free_b, seed_a, seed_b, valid, stream))) return rc;
+    hipLaunchKernelGGL(faq_seed_start_kernel, dim3(B), dim3(FQ_THREADS), 0, st, seeds, assign0, nvalid, N, free_a, free_b, nfree, valid, ok,
+                       ueff, assign_s);
+    FGNN_LAUNCH_CHECK();
+    if ((rc = fgnn_seed_gather(a1, gstride, ld, free_a, free_a, ueff, B, N, A22, stream))) return rc;
+    if ((rc = fgnn_seed_gather(a2, gstride, ld, free_b, free_b, ueff, B, N, B22, stream))) return rc;
+    if (p0 && !p0_free && (rc = fgnn_seed_gather(p0, bs, N, free_a, free_b, ueff, B, N, P0, stream))) return rc;
+    if ((rc = fgnn_seed_const(a1, a2, gstride, ld, free_a, free_b, seed_a, seed_b, ueff, nseed, B, N, C, stream))) return rc;
+    hipLaunchKernelGGL(faq_init_kernel, dim3(B), dim3(FQ_THREADS), 0, st, p0 ? (p0_free ? p0 : P0) : nullptr, assign0 ? assign_s : nullptr, ueff, N, P, nvc,
+                       nvw, done, nit, status);
+    FGNN_LAUNCH_CHECK();
+    for (int it = 0; it < maxiter; ++it) {
+        hipLaunchKernelGGL(faq_pb_kernel, dim3(tiles.x, 2 * tiles.y, B), dim3(FQ_THREADS), 0, st, B22, bs, N, P, nvc, done, N, T);
+        FGNN_LAUNCH_CHECK();
+        hipLaunchKernelGGL(faq_grad_seeded_kernel, tiles, dim3(FQ_THREADS), 0, st, A22, bs, N, T, C, nvc, done, N, cost);
+        FGNN_LAUNCH_CHECK();
+        if ((rc = fgnn_lsap_accuracy(cost, bs, N, nvw, B, N, correct, q, stream))) return rc;
+        hipLaunchKernelGGL(faq_step_seeded_kernel, dim3(B), dim3(FQ_THREADS), 0, st, A22, B22, bs, N, cost, C, q, nvc, N, tol, P, nvw, done,
+                           nit, status);
+        FGNN_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(faq_neg_p_kernel, dim3(N, B), dim3(64), 0, st, P, nvc, N, cost);
+    FGNN_LAUNCH_CHECK();
+    if ((rc = fgnn_lsap_accuracy(cost, bs, N, nvc, B, N, correct, perm_s, stream))) return rc;
+    hipLaunchKernelGGL(faq_finish_kernel, dim3(B), dim3(FQ_THREADS), 0, st, P, assign0 ? assign_s : nullptr, nvc, N, perm_s, nit, status,
+                       p_out);
+    FGNN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(faq_seed_finish_kernel, dim3(B), dim3(FQ_THREADS), 0, st, seeds, assign0, nvalid, N, free_a, free_b, nfree, nseed,
+                       valid, ok, perm_s, perm, nit, status, seeded);
     FGNN_LAUNCH_CHECK();
     return 0;
 }

@@ -498,28 +498,42 @@ def _check_faq(who, faq):
     return o
 
 
-def _faq_launches(b1, b2, s, assign, q, nvalid, B, N, faq):
+def _faq_launches(b1, b2, s, assign, q, nvalid, B, N, faq, seeds=None):
     """The FAQ stage of the decode, on checked arguments: fgnn_sinkhorn on the scores (P0 'scores'), fgnn_expand_adjacency on both
     sides, the fgnn_qapw_faq chain, the objective of its perm, and the select -- where the chain reports status 2 the stage keeps
     `assign` and its objective `q`.  Every buffer is allocated before the first launch; nothing is read back.
-    -> {'perm', 'qap', 'faq_perm', 'faq_qap', 'faq_nit', 'faq_status', 'sinkhorn_err'}"""
+    With seeds: fgnn_seed_index and fgnn_seed_gather first, so that Sinkhorn runs on the free block of the scores with n_b := u_b,
+    and the fgnn_qapw_faq_seeded chain from that start, already in free coordinates.
+    -> {'perm', 'qap', 'faq_perm', 'faq_qap', 'faq_nit', 'faq_status', 'sinkhorn_err'} (+ 'seeded' with seeds)"""
     from . import qap
     dev = b1.device
     x = torch.empty(2, B, 2, N, N, dtype=torch.float32, device=dev)
     p0 = err = None
     if faq['P0'] == 'scores':
-        sk = qap.sinkhorn_device(s, nvalid, faq['tau'], faq['iters'])
+        if seeds is None:
+            sk = qap.sinkhorn_device(s, nvalid, faq['tau'], faq['iters'])
+        else:
+            ix = qap.seed_index_device(seeds, nvalid)
+            u = torch.where(ix['valid'] != 0, ix['nfree'], torch.zeros_like(ix['nfree']))
+            sk = qap.sinkhorn_device(qap.seed_gather_device(s, ix['free_a'], ix['free_b'], u), u, faq['tau'], faq['iters'])
         p0, err = sk['P'], sk['err']
     for side, bits in enumerate((b1, b2)):
         _lib.call('fgnn_expand_adjacency', _lib.ptr(bits), _lib.ptr(nvalid), B, N, _lib.ptr(x[side]), _lib.stream_ptr())
-    out = qap.faq_weighted(x[0], x[1], nvalid, p0, None, faq['maxiter'], faq['tol'])
+    if seeds is None:
+        out = qap.faq_weighted(x[0], x[1], nvalid, p0, None, faq['maxiter'], faq['tol'])
+    else:
+        out = qap.faq_weighted_seeded(x[0], x[1], seeds, nvalid, p0, None, faq['maxiter'], faq['tol'], p0_free=True)
     fq = qap.objective_bits(b1, b2, out['perm'], nvalid, raw=True)[0]
     failed = out['status'] == 2
-    return {'perm': torch.where(failed[:, None], assign, out['perm']), 'qap': torch.where(failed, q, fq), 'faq_perm': out['perm'],
-            'faq_qap': fq, 'faq_nit': out['nit'], 'faq_status': out['status'], 'sinkhorn_err': err}
+    res = {'perm': torch.where(failed[:, None], assign, out['perm']), 'qap': torch.where(failed, q, fq), 'faq_perm': out['perm'],
+           'faq_qap': fq, 'faq_nit': out['nit'], 'faq_status': out['status'], 'sinkhorn_err': err}
+    if seeds is not None:
+        res['seeded'] = out['seeded']
+    return res
 
 
-def _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt=False, faq=None, scores=None):
+def _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt=False, faq=None, scores=None,
+                     seeds=None):
     """qap.objective_bits (once more on the labels), _faq_launches with faq (on `scores`), qap.greedy_bits with refine > 0,
     qap.two_opt_bits with two_opt, then fgnn_qap_fold(_bins), on checked arguments (on the current stream of the bit words' device)
     -> the dict of decode_scores"""
@@ -532,7 +546,7 @@ def _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, re
     perm = refined = None
     stage = dict.fromkeys(('faq_perm', 'faq_qap', 'faq_nit', 'faq_status', 'sinkhorn_err'))
     if faq is not None:
-        stage = _faq_launches(b1, b2, scores, assign, q, nvalid, B, N, faq)
+        stage = _faq_launches(b1, b2, scores, assign, q, nvalid, B, N, faq, seeds)
         perm, refined = stage.pop('perm'), stage.pop('qap')
         meter._mark_refined()
     if refine > 0:
@@ -541,7 +555,7 @@ def _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, re
         meter._mark_refined()
     swaps = status = None
     if two_opt:                     # from the last matching of the chain; its objective IS qap's sum, whatever the symmetry
-        t = qap.two_opt_bits(b1, b2, assign if perm is None else perm, nvalid, raw=True)
+        t = qap.two_opt_bits(b1, b2, assign if perm is None else perm, nvalid, raw=True, seeds=seeds)
         perm, refined, swaps, status = t['perm'], t['qap'], t['swaps'], t['status']
         meter._mark_refined()
     # one zero-filled allocation for the three per-pair outputs: the 8-byte words first
@@ -565,8 +579,21 @@ def _check_two_opt(who, two_opt):
     return two_opt
 
 
+def _check_decode_seeds(who, seeds, B, N, dev, faq, refine):
+    """seeds= of the decode -> (B, N) int32 on dev or None; seeds need the faq= stage and exclude refine"""
+    if seeds is None:
+        return None
+    from . import qap
+    seeds = qap.check_seeds(who, seeds, B, N, dev)
+    if faq is None:
+        raise ValueError('%s: seeds= needs the faq= stage (the Hungarian matching knows no fixed rows)' % who)
+    if refine > 0:
+        raise ValueError("%s: seeds= and refine > 0 do not go together (the reference's greedy_qap knows no fixed rows)" % who)
+    return seeds
+
+
 def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, bins=None, refine=0, assign=None,
-                  two_opt=False, faq=None):
+                  two_opt=False, faq=None, seeds=None):
     """The reference's all_acc_qap / all_greedy_losses_acc (toolbox/metrics.py:168-223) of a batch, added to an epoch record.
     scores, nvalid, labels, live, bins: as evaluate_scores takes them, with the same refusals; bits1, bits2: the two graphs as
     (B, N, ceil(N/32)) int32 bit words on the scores' device (PairGenerator.bits, synthetic.pack_adjacency).  0/1 graphs only: the
@@ -595,6 +622,12 @@ def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, li
     int32 as the chain left them (faq_qap: the objective of faq_perm, -1 where it holds no matching) and 'sinkhorn_err' (B,) fp32
     (None with the barycenter); all None without faq.  With {'P0': 'barycenter'} and `assign` handed in the scores do not enter
     the stage's matching: the classical-baseline epoch.
+    seeds: None or a (B, N) integer tensor of known matches (qap.faq: seeds[b, i] = j fixes row i, -1 leaves it free;
+    planted.reveal_seeds draws one from labels).  Seeds need the faq= stage and exclude refine > 0 (ValueError otherwise): with P0
+    'scores' Sinkhorn runs on the free block of the scores (fgnn_seed_index, fgnn_seed_gather, n_b := u_b), the seeded chain
+    fgnn_qapw_faq_seeded follows, and two_opt=True runs fgnn_qap_2opt_seeded, so 'faq_perm' and 'perm' hold every seed.  The
+    Hungarian stage ('assign', 'correct') stays unseeded; the fold and the meters are unchanged.  The dict gains 'seeded' (B,) int32
+    = m_b.  seeds=None issues the launches and returns the keys it always did.
     Nothing is read back."""
     if meter is None and bins is not None:
         raise ValueError('decode_scores: bins= and a BinnedQapMeter as meter go together')
@@ -604,6 +637,7 @@ def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, li
     s, nvalid, labels, bins, B, N, live = _score_args('decode_scores', scores, nvalid, labels, live, bins)
     dev = s.device
     b1, b2 = _bits_args('decode_scores', (bits1, bits2), B, N, dev)
+    seeds = _check_decode_seeds('decode_scores', seeds, B, N, dev, faq, refine)
     if meter is None:
         meter = QapMeter(dev)
     else:
@@ -616,7 +650,7 @@ def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, li
         if assign is None:
             from .metrics import lsap_device
             assign = lsap_device(s, nvalid, want_assign=True)[1]
-        return _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt, faq, s)
+        return _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt, faq, s, seeds)
 
 
 def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False, bins=None,

@@ -22,6 +22,7 @@ from .masked import MaskedTensor
 
 MAX_N = _lib.FGNN_PLANTED_MAX_N
 STREAM = 7                    # include/fgnn_hip.h: FGNN_PLANTED_STREAM
+SEEDS_STREAM = 8              # include/fgnn_hip.h: FGNN_SEEDS_STREAM (reveal_seeds)
 
 
 def check_labels(labels, B, N, what='labels'):
@@ -75,6 +76,40 @@ def planted_permutation(seed, N, first=None, count=None, index=None, nvalid=None
         if count:
             _lib.call('fgnn_planted_perm', seed, first, _lib.ptr(index), _lib.ptr(nv), count, N, _lib.ptr(labels), _lib.stream_ptr())
     return labels
+
+
+def reveal_seeds(labels, nvalid, count, seed, first=0, index=None):
+    """A seed vector for ``qap.faq`` / ``qap.two_opt`` / ``match`` (``seeds=``) from planted labels: per pair min(count, n_b) rows
+    keep their label, chosen uniformly without replacement; every other entry is -1.  labels: (B, N) integer tensor on the GPU;
+    nvalid: (B,) vertex counts or None.  The choice depends on (seed, pair index) only -- pair b is first + b, or index[b] -- and
+    is drawn from Philox stream 8 of the pair (SEEDS_STREAM), next to the permutation's stream 7: the first `count` steps of
+    `planted_permutation`'s Fisher-Yates.  -> (B, N) int32 device tensor.  Enqueued on the current stream."""
+    if not torch.is_tensor(labels) or labels.dim() != 2:
+        raise ValueError('reveal_seeds: labels must be a (B, N) integer tensor')
+    B, N = labels.shape
+    check_labels(labels, B, N)
+    if not labels.is_cuda:
+        raise RuntimeError('reveal_seeds: labels are on %s; the seeds are drawn on the GPU only (there is no CPU path)' % (labels.device,))
+    if not 1 <= N <= MAX_N:
+        raise ValueError('reveal_seeds: 1 to %d vertices per graph, got %d' % (MAX_N, N))
+    count, seed, first = int(count), int(seed), int(first)
+    if count < 0 or first < 0 or not 0 <= seed < 1 << 64:
+        raise ValueError('reveal_seeds: count and first must be >= 0 and seed in [0, 2^64), got %d, %d, %d' % (count, first, seed))
+    dev = labels.device
+    if index is not None:
+        if not torch.is_tensor(index):
+            index = torch.tensor(index, dtype=torch.int64)
+        if index.dim() != 1 or index.dtype != torch.int64 or index.numel() != B:
+            raise ValueError('reveal_seeds: index must be a (%d,) int64 tensor' % B)
+        index = index.to(dev).contiguous()
+    lab = labels.to(dtype=torch.int32).contiguous()
+    nv = _nv32(nvalid, B, dev)
+    out = torch.empty(B, N, dtype=torch.int32, device=dev)
+    if B:
+        with torch.cuda.device(dev):
+            _lib.call('fgnn_reveal_seeds', seed, first, _lib.ptr(index), _lib.ptr(lab), _lib.ptr(nv), B, N, min(count, N), _lib.ptr(out),
+                      _lib.stream_ptr())
+    return out
 
 
 def relabel_bits(bits, labels, nvalid=None):

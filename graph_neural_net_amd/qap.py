@@ -156,18 +156,23 @@ def _check_max_swaps(max_swaps):
     return int(max_swaps)
 
 
-def two_opt_bits(b1, b2, assign, nv, max_swaps=None, raw=False):
+def two_opt_bits(b1, b2, assign, nv, max_swaps=None, raw=False, seeds=None):
     """fgnn_qap_2opt on bit words, from the matching `assign` -> {'perm': (B, N) int32, 'qap', 'swaps', 'nit', 'status': (B,) int64}
     device tensors (see `two_opt`); never synchronises.  raw=True: the tensors as the launch wrote them -- qap, swaps, status int32
-    (qap as fgnn_qap_fold reads it), nit int64."""
+    (qap as fgnn_qap_fold reads it), nit int64.  seeds ((B, N) int32 on the device): fgnn_qap_2opt_seeded instead."""
     B, N, _ = b1.shape
     dev = b1.device
     a = assign.to(dtype=torch.int32).contiguous()
     perm = torch.empty(B, N, dtype=torch.int32, device=dev)
     out = torch.empty(3, B, dtype=torch.int32, device=dev)
     nit = torch.empty(B, dtype=torch.int64, device=dev)
-    _lib.call('fgnn_qap_2opt', _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(a), _lib.ptr(nv), B, N, _check_max_swaps(max_swaps), _lib.ptr(perm),
-              _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(nit), _lib.ptr(out[2]), _lib.stream_ptr())
+    if seeds is None:
+        _lib.call('fgnn_qap_2opt', _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(a), _lib.ptr(nv), B, N, _check_max_swaps(max_swaps),
+                  _lib.ptr(perm), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(nit), _lib.ptr(out[2]), _lib.stream_ptr())
+    else:
+        _lib.call('fgnn_qap_2opt_seeded', _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(a), _lib.ptr(seeds), _lib.ptr(nv), B, N,
+                  _check_max_swaps(max_swaps), _lib.ptr(perm), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(nit), _lib.ptr(out[2]),
+                  _lib.stream_ptr())
     if raw:
         return {'perm': perm, 'qap': out[0], 'swaps': out[1], 'nit': nit, 'status': out[2]}
     out = out.to(torch.int64)
@@ -252,7 +257,7 @@ def two_opt_weighted(adj1, adj2, assign, nvalid=None, labels=None, max_swaps=Non
     weights the trajectory is the kernel's own, bit-identical from run to run, and the default bound of n_b^2 exchanges can bind:
     that is status 1, not an error.  The device route is the search launch, two objective launches and one count; it never
     synchronises.  CPU tensors and N > 256 take a host route in numpy float64 with the same scan and the same nit; there qap and
-    qap0 are float64.
+    qap0 are float64.  There is no ``seeds`` argument here: fixed rows are supported by `two_opt` (0/1 pairs) and `faq` only.
 
     ``qap.two_opt(weighted=True)`` and ``match(weighted=True, two_opt=True)`` still refuse; the chain on weighted pairs is
         out = model.match(x1, x2, refine=T, weighted=True)
@@ -320,7 +325,91 @@ def faq_weighted(adj1, adj2, nv, p0=None, assign0=None, maxiter=30, tol=0.03, re
     return res
 
 
-def faq(adj1, adj2, nvalid=None, labels=None, P0='barycenter', maxiter=30, tol=0.03, weighted=False, return_P=False, **options):
+def check_seeds(who, seeds, B, N, dev):
+    """seeds= of `faq` / `two_opt` / the decode -> (B, N) int32 tensor on `dev` (None passes)"""
+    if seeds is None:
+        return None
+    if isinstance(seeds, np.ndarray):
+        seeds = torch.from_numpy(seeds)
+    if (not torch.is_tensor(seeds) or seeds.is_floating_point() or seeds.dtype == torch.bool or seeds.is_complex()
+            or tuple(seeds.shape) != (B, N)):
+        raise ValueError('%s: seeds must be a (%d, %d) integer tensor (seeds[b, i] = j fixes vertex i to vertex j, -1 leaves it free), '
+                         'got %s' % (who, B, N, tuple(seeds.shape) if torch.is_tensor(seeds) else type(seeds).__name__))
+    return seeds.detach().to(device=dev, dtype=torch.int32).contiguous()
+
+
+def seeds_from_partial_match(partial_match, B, N, device=None):
+    """SciPy's form -> a seed vector: `partial_match` is a list of B arrays of shape (m_b, 2) (or None / empty for a pair without
+    seeds), each row [i, j] fixing vertex i of graph 1 to vertex j of graph 2 -> (B, N) int32 tensor on `device`, -1 on free rows.
+    Entries outside [0, N) and rows named twice raise ValueError; whether a pair's seeds are valid for ITS n_b (a target beyond
+    n_b, a target shared by two rows) is the solvers' verdict: status 2."""
+    if len(partial_match) != B:
+        raise ValueError('seeds_from_partial_match: expected %d arrays, got %d' % (B, len(partial_match)))
+    out = np.full((B, N), -1, dtype=np.int32)
+    for b, pm in enumerate(partial_match):
+        if pm is None:
+            continue
+        pm = np.asarray(pm.detach().cpu() if torch.is_tensor(pm) else pm)
+        if pm.size == 0:
+            continue
+        if pm.ndim != 2 or pm.shape[1] != 2 or not np.issubdtype(pm.dtype, np.integer):
+            raise ValueError('seeds_from_partial_match: pair %d: expected an (m, 2) integer array, got %s %s' % (b, pm.shape, pm.dtype))
+        if (pm < 0).any() or (pm >= N).any():
+            raise ValueError('seeds_from_partial_match: pair %d: entries must lie in [0, %d)' % (b, N))
+        if len(set(pm[:, 0].tolist())) != len(pm):
+            raise ValueError('seeds_from_partial_match: pair %d names a row twice' % b)
+        out[b, pm[:, 0]] = pm[:, 1]
+    t = torch.from_numpy(out)
+    return t.to(device) if device is not None else t
+
+
+def seed_index_device(seeds, nv):
+    """fgnn_seed_index on (B, N) int32 device seeds -> {'nfree', 'nseed', 'valid': (B,) int32, 'free_a', 'free_b', 'seed_a', 'seed_b':
+    (B, N) int32} as the launch wrote them; never synchronises."""
+    B, N = seeds.shape
+    cnt = torch.empty(3, B, dtype=torch.int32, device=seeds.device)
+    lists = torch.empty(4, B, N, dtype=torch.int32, device=seeds.device)
+    _lib.call('fgnn_seed_index', _lib.ptr(seeds), _lib.ptr(nv), B, N, _lib.ptr(cnt[0]), _lib.ptr(cnt[1]), _lib.ptr(lists[0]),
+              _lib.ptr(lists[1]), _lib.ptr(lists[2]), _lib.ptr(lists[3]), _lib.ptr(cnt[2]), _lib.stream_ptr())
+    return {'nfree': cnt[0], 'nseed': cnt[1], 'valid': cnt[2], 'free_a': lists[0], 'free_b': lists[1], 'seed_a': lists[2],
+            'seed_b': lists[3]}
+
+
+def seed_gather_device(x, rows, cols, nfree):
+    """fgnn_seed_gather on (B, N, N) fp32 device matrices (rows contiguous, pitched views included) -> (B, N, N) fp32: the
+    (rows, cols) block in the nfree x nfree corner, exact zeros around it; never synchronises."""
+    B, N = x.shape[0], x.shape[-1]
+    if not _chan0_ok(x):
+        x = x.contiguous()
+    out = torch.empty(B, N, N, dtype=torch.float32, device=x.device)
+    _lib.call('fgnn_seed_gather', _lib.ptr(x), x.stride(0) if B > 1 else N * x.stride(-2), x.stride(-2), _lib.ptr(rows), _lib.ptr(cols),
+              _lib.ptr(nfree), B, N, _lib.ptr(out), _lib.stream_ptr())
+    return out
+
+
+def faq_weighted_seeded(adj1, adj2, seeds, nv, p0=None, assign0=None, maxiter=30, tol=0.03, return_P=False, p0_free=False):
+    """fgnn_qapw_faq_seeded on what `weighted_views` takes and (B, N) int32 device seeds -> the dict of `faq_weighted` plus 'seeded'
+    (B,) int32 = m_b; 'P' is the last iterate in free coordinates (the u_b x u_b corner); never synchronises.  p0_free: p0 is
+    already in free coordinates (its u_b x u_b corner is the start)."""
+    x1, x2, gs, ld = weighted_views(adj1, adj2)
+    B, N = x1.shape[0], x1.shape[-1]
+    dev = x1.device
+    nbytes = _lib.load().fgnn_qapw_faq_seeded_ws_bytes(B, N)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    perm = torch.empty(B, N, dtype=torch.int32, device=dev)
+    out = torch.empty(3, B, dtype=torch.int32, device=dev)
+    P = torch.empty(B, N, N, dtype=torch.float32, device=dev) if return_P else None
+    _lib.call('fgnn_qapw_faq_seeded', _lib.ptr(x1), _lib.ptr(x2), gs, ld, _lib.ptr(seeds), _lib.ptr(p0), int(bool(p0_free)), _lib.ptr(assign0),
+              _lib.ptr(nv), B, N, int(maxiter), float(tol), _lib.ptr(ws), nbytes, _lib.ptr(perm), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]),
+              _lib.ptr(P), _lib.stream_ptr())
+    res = {'perm': perm, 'nit': out[0], 'status': out[1], 'seeded': out[2]}
+    if return_P:
+        res['P'] = P
+    return res
+
+
+def faq(adj1, adj2, nvalid=None, labels=None, P0='barycenter', maxiter=30, tol=0.03, weighted=False, return_P=False, seeds=None,
+        **options):
     """The Fast Approximate QAP algorithm for every pair of the batch: SciPy's ``quadratic_assignment(A, B, method='faq',
     options={'maximize': True, 'P0': ..., 'maxiter': ..., 'tol': ...})`` -- Frank-Wolfe on f(P) = tr(A^T P B P^T) over the doubly
     stochastic matrices (each round: the gradient G = A P B^T + A^T P B, the assignment q that maximises <G, Q>, an exact line
@@ -343,7 +432,18 @@ def faq(adj1, adj2, nvalid=None, labels=None, P0='barycenter', maxiter=30, tol=0
     words or weighted input it never synchronises (dense 0/1 input: the one read of the verdict flag, as everywhere).  G is an fp32
     product on the matrix cores, the line search fp64 sums over it, P fp32: on data where every iterate is exactly representable
     the trajectory is the float64 one, else it is the kernel's own, bit-identical from run to run.  CPU tensors and N > 256 take a
-    host route in numpy float64 that restates SciPy's loop operation for operation; there a weighted qap and P are float64."""
+    host route in numpy float64 that restates SciPy's loop operation for operation; there a weighted qap and P are float64.
+
+    seeds (the project's spelling of SciPy's partial_match, which keeps raising; `seeds_from_partial_match` converts): a (B, N)
+    integer tensor, seeds[b, i] = j fixes vertex i of graph 1 to vertex j of graph 2 and -1 leaves row i free, the convention of
+    `labels`; rows at or beyond n_b are ignored.  Pair b then has m_b seeds and u_b = n_b - m_b free vertices, and the algorithm is
+    SciPy's seeded one: Frank-Wolfe on the free block with the seeds' constant term in the gradient (``csrc/qap_seeds.hip``,
+    fgnn_qapw_faq_seeded).  P0: 'barycenter' (1 / u_b), a (B, N) matching that holds every seed, or a (B, N, N) float tensor whose
+    (free rows x free columns) block is the start.  The dict gains seeded (B,) int64 = m_b; perm[i] == seeds[i] on every seeded
+    row; acc counts all rows; nit, status as above over the free block, and: a seed outside [0, n_b) or shared by two rows -- status
+    2, perm -1, nit 0; a matching P0 against a seed -- status 2, perm = P0; u_b = 0 < n_b -- perm = seeds, nit 0, status 0.  With
+    return_P, P is the last iterate IN FREE COORDINATES: the u_b x u_b corner of (B, N, N), rows / columns the ascending free ones.
+    seeds=None issues the launches and returns the keys it always did."""
     if options:
         raise ValueError('faq: unsupported option(s) %s -- seeds (partial_match), shuffle_input and rng are not implemented'
                          % ', '.join(sorted(options)))
@@ -354,21 +454,30 @@ def faq(adj1, adj2, nvalid=None, labels=None, P0='barycenter', maxiter=30, tol=0
     B, N = adj1.shape[0], adj1.shape[-2]
     labels = labels_tensor(labels, B, N, adj1.device)
     p0, assign0 = _faq_start(P0, B, N, adj1.device)
+    seeds = check_seeds('faq', seeds, B, N, adj1.device)
     if (_on_host_weighted if weighted else _on_host)(adj1, N):
-        return _faq_host(adj1, adj2, nvalid, labels, p0, assign0, int(maxiter), tol, weighted, return_P)
+        return _faq_host(adj1, adj2, nvalid, labels, p0, assign0, int(maxiter), tol, weighted, return_P, seeds)
     dev = adj1.device
+
+    def run(x1, x2, nv):
+        if seeds is None:
+            return faq_weighted(x1, x2, nv, p0, assign0, maxiter, tol, return_P)
+        return faq_weighted_seeded(x1, x2, seeds, nv, p0, assign0, maxiter, tol, return_P)
+
     if weighted:
         nv, flag = _nv32(nvalid, dev), None
-        out = faq_weighted(adj1, adj2, nv, p0, assign0, maxiter, tol, return_P)
+        out = run(adj1, adj2, nv)
         q = objective_weighted(adj1, adj2, out['perm'], nv)['qap']
     else:
         b1, b2, nv, flag = _device_inputs(adj1, adj2, nvalid)
         x = torch.empty(2, B, 2, N, N, dtype=torch.float32, device=dev)
         for side, bits in enumerate((b1, b2)):
             _lib.call('fgnn_expand_adjacency', _lib.ptr(bits), _lib.ptr(nv), B, N, _lib.ptr(x[side]), _lib.stream_ptr())
-        out = faq_weighted(x[0], x[1], nv, p0, assign0, maxiter, tol, return_P)
+        out = run(x[0], x[1], nv)
         q = objective_bits(b1, b2, out['perm'], nv)['qap']
     out['status'], out['nit'] = out['status'].to(torch.int64), out['nit'].to(torch.int64)
+    if seeds is not None:
+        out['seeded'] = out['seeded'].to(torch.int64)
     out['qap'] = torch.where(out['status'] == 2, torch.full_like(q, -1), q)
     if labels is None:
         labels = torch.arange(N, dtype=torch.int32, device=dev).expand(B, N).contiguous()
@@ -483,7 +592,7 @@ def greedy_qap(adj1, adj2, assign, T=10, nvalid=None, weighted=False, labels=Non
     return out
 
 
-def two_opt(adj1, adj2, assign, nvalid=None, labels=None, max_swaps=None, weighted=False):
+def two_opt(adj1, adj2, assign, nvalid=None, labels=None, max_swaps=None, weighted=False, seeds=None):
     """Pairwise-exchange local search from `assign` for every pair of the batch: SciPy's ``quadratic_assignment(A, B,
     method='2opt', options={'maximize': True, 'partial_guess': [[i, assign[i]]]})``.  The pairs (i, j), i <= j, are scanned in the
     order (0,0), (0,1), .., (0,n-1), (1,1), ..; the first pair whose exchange raises qap = sum_{i,k} A[i,k] B[pi(i),pi(k)] is applied
@@ -494,18 +603,22 @@ def two_opt(adj1, adj2, assign, nvalid=None, labels=None, max_swaps=None, weight
     n (n + 1) / 2), status: 0 a local optimum, 1 stopped after `max_swaps` exchanges (None: no limit; perm / qap are the state
     reached, nit has no last scan), 2 `assign` is no permutation of the pair's [0, n_b) -- perm is then `assign`, qap -1, swaps and
     nit 0.  The device route is three launches (the search itself is one) and, with bit words, never synchronises; the host route
-    (tensors not on the GPU, N > 256) is the same algorithm in numpy with the same integers.  0/1 graphs only."""
+    (tensors not on the GPU, N > 256) is the same algorithm in numpy with the same integers.  0/1 graphs only.
+    seeds (see `faq`): a (B, N) integer tensor of fixed rows -- SciPy's partial_match.  Only the free rows are exchanged, scanned as
+    SciPy's combinations_with_replacement(i_free, 2): with f free rows and r(i) the rank of row i among them an applied pair adds
+    r(i) f - r(i) (r(i) - 1) / 2 + (r(j) - r(i)) + 1 to nit, the last scan f (f + 1) / 2.  `assign` must hold every seed, else status 2."""
     if weighted:
         raise NotImplementedError('two_opt: weighted=True is not supported -- the exchange search runs on 0/1 adjacency (bit words '
                                   'or a tensor representation) only')
     ms = _check_max_swaps(max_swaps)
     labels = labels_tensor(labels, assign.shape[0], assign.shape[1], adj1.device)
+    seeds = check_seeds('two_opt', seeds, assign.shape[0], assign.shape[1], adj1.device)
     if _on_host(adj1, adj1.shape[-2]):
-        return _two_opt_host(adj1, adj2, assign, nvalid, labels, ms)
+        return _two_opt_host(adj1, adj2, assign, nvalid, labels, ms, seeds)
     b1, b2, nv, flag = _device_inputs(adj1, adj2, nvalid)
     B, N, _ = b1.shape
     a = assign.to(device=b1.device, dtype=torch.int32).contiguous()
-    out = two_opt_bits(b1, b2, a, nv, max_swaps)
+    out = two_opt_bits(b1, b2, a, nv, max_swaps, seeds=seeds)
     out['qap0'] = objective_bits(b1, b2, a, nv)['qap']
     if labels is None:
         labels = torch.arange(N, dtype=torch.int32, device=b1.device).expand(B, N).contiguous()
@@ -635,8 +748,9 @@ def _greedy_host(adj1, adj2, assign, T, nvalid, labels=None):
             'perm': torch.from_numpy(perm)}
 
 
-def _two_opt_pair(A, Bm, pi, max_swaps):
-    """The exchange search of one pair -> (perm, qap, swaps, nit, status).  With Bp = B[pi][:, pi], R = A Bp^T and X = A^T Bp the gain
+def _two_opt_pair(A, Bm, pi, max_swaps, free=None):
+    """The exchange search of one pair -> (perm, qap, swaps, nit, status).  free (a boolean mask of the rows that may move; None:
+    all): SciPy's scan over combinations_with_replacement(i_free, 2), positions counted among the free rows.  With Bp = B[pi][:, pi], R = A Bp^T and X = A^T Bp the gain
     of exchanging i and j is R[i,j] + R[j,i] - R[i,i] - R[j,j] (rows i, j) + X[i,j] + X[j,i] - X[i,i] - X[j,j] (columns i, j) +
     (A[i,i] + A[j,j] - A[i,j] - A[j,i]) (Bp[i,i] + Bp[j,j] - Bp[i,j] - Bp[j,i]) (the four crossings): all gains of a round are two
     matrix products (in float64, exact: every entry is an integer <= n), and the first positive one in row-major order above the
@@ -650,6 +764,10 @@ def _two_opt_pair(A, Bm, pi, max_swaps):
     dA = np.diag(A)
     da = dA[:, None] + dA[None, :] - A - A.T
     upper = np.triu(np.ones((n, n), dtype=bool), 1)
+    f, rank = n, np.arange(n)
+    if free is not None:
+        upper &= free[:, None] & free[None, :]
+        f, rank = int(free.sum()), np.cumsum(free) - 1
     swaps, nit, status = 0, 0, 1
     for _ in range(n * n if max_swaps < 0 else min(max_swaps, n * n)):
         R, X, dB = A @ Bp.T, A.T @ Bp, np.diag(Bp)
@@ -657,11 +775,12 @@ def _two_opt_pair(A, Bm, pi, max_swaps):
         gain = R + R.T + X + X.T - own[:, None] - own[None, :] + da * (dB[:, None] + dB[None, :] - Bp - Bp.T)
         hit = np.flatnonzero((gain > 0) & upper)
         if hit.size == 0:
-            nit += n * (n + 1) // 2
+            nit += f * (f + 1) // 2
             status = 0
             break
         i, j = divmod(int(hit[0]), n)
-        nit += i * n - i * (i - 1) // 2 + (j - i) + 1
+        ri, rj = int(rank[i]), int(rank[j])
+        nit += ri * f - ri * (ri - 1) // 2 + (rj - ri) + 1
         swaps += 1
         pi[[i, j]] = pi[[j, i]]
         Bp[[i, j], :] = Bp[[j, i], :]
@@ -669,7 +788,7 @@ def _two_opt_pair(A, Bm, pi, max_swaps):
     return pi, int((A * Bp).sum()), swaps, nit, status
 
 
-def _two_opt_host(adj1, adj2, assign, nvalid, labels, max_swaps):
+def _two_opt_host(adj1, adj2, assign, nvalid, labels, max_swaps, seeds=None):
     B, N = adj1.shape[0], adj1.shape[-2]
     sizes = _sizes(nvalid, B, N)
     lab = _label_rows(labels, sizes)
@@ -681,8 +800,13 @@ def _two_opt_host(adj1, adj2, assign, nvalid, labels, max_swaps):
         pi0 = pis[b, :n]
         inside = bool(((pi0 >= 0) & (pi0 < n)).all())
         q0 = _qap_of(As[b], Bs[b], pi0) if inside else -1
+        free = None
+        if seeds is not None:
+            sd = seeds[b, :n].detach().cpu().numpy().astype(np.int64)
+            free = sd < 0
+            inside = inside and bool((pi0[~free] == sd[~free]).all())
         if inside and len(set(pi0.tolist())) == n:
-            pi, q, swaps, nit, status = _two_opt_pair(As[b], Bs[b], pi0, max_swaps)
+            pi, q, swaps, nit, status = _two_opt_pair(As[b], Bs[b], pi0, max_swaps, free)
         else:
             pi, q, swaps, nit, status = pi0, -1, 0, 0, 2
         perm[b, :n] = pi
@@ -870,7 +994,107 @@ def _faq_pair(A, Bm, P, maxiter, tol):
     return col, nit, P, stop
 
 
-def _faq_host(adj1, adj2, nvalid, labels, p0, assign0, maxiter, tol, weighted, return_P):
+def _seed_lists(sd, n):
+    """one pair's seeds -> (valid, free_a, free_b, seed_a, seed_b): ascending free rows / columns (SciPy's setdiff1d), seeded rows
+    ascending; valid = every target inside [0, n) and none shared"""
+    seed_a = np.flatnonzero(sd >= 0)
+    seed_b = sd[seed_a]
+    valid = bool((seed_b < n).all()) and len(set(seed_b.tolist())) == len(seed_b)
+    free_a = np.flatnonzero(sd < 0)
+    free_b = np.setdiff1d(np.arange(n), seed_b) if valid else np.zeros(0, dtype=np.int64)
+    return valid, free_a, free_b, seed_a, seed_b
+
+
+def _faq_pair_seeded(A, Bm, lists, P, maxiter, tol):
+    """SciPy's _quadratic_assignment_faq (maximize=True, no shuffling) with partial_match on one pair, operation for operation, from
+    the start P on the free block -> (perm over all rows, nit, P, whether it stopped on tol)."""
+    from scipy.optimize import linear_sum_assignment
+    _, free_a, free_b, seed_a, seed_b = lists
+    n, m = len(A), len(seed_a)
+    u = n - m
+    perm_A, perm_B = np.concatenate([seed_a, free_a]), np.concatenate([seed_b, free_b])
+    XA, XB = A[perm_A][:, perm_A], Bm[perm_B][:, perm_B]
+    A12, A21, A22 = XA[:m, m:], XA[m:, :m], XA[m:, m:]
+    B12, B21, B22 = XB[:m, m:], XB[m:, :m], XB[m:, m:]
+    const_sum = A21 @ B21.T + A12.T @ B12
+    nit, stop = 0, False
+    for nit in range(1, maxiter + 1):
+        grad = const_sum + A22 @ P @ B22.T + A22.T @ P @ B22
+        _, cols = linear_sum_assignment(grad, maximize=True)
+        Q = np.eye(u)[cols]
+        R = P - Q
+        b21 = ((R.T @ A21) * B21).sum()
+        b12 = ((R.T @ A12.T) * B12.T).sum()
+        AR22, BR22 = A22.T @ R, B22 @ R.T
+        b22a = (AR22 * B22.T[cols]).sum()
+        b22b = (A22 * BR22[cols]).sum()
+        a = (AR22.T * BR22).sum()
+        b = b21 + b12 + b22a + b22b
+        if -a > 0 and 0 <= -b / (2 * a) <= 1:
+            alpha = -b / (2 * a)
+        else:
+            alpha = np.argmin([0, -(b + a)])
+        P1 = alpha * P + (1 - alpha) * Q
+        stop = bool(np.linalg.norm(P - P1) / np.sqrt(u) < tol)
+        P = P1
+        if stop:
+            break
+    _, col = linear_sum_assignment(P, maximize=True)
+    perm = np.concatenate((np.arange(m), col + m))
+    out = np.zeros(n, dtype=np.int64)
+    out[perm_A] = perm_B[perm]
+    return out, nit, P, stop
+
+
+def _faq_host_seeded(As, Bs, sizes, lab, seeds, starts, pis, maxiter, tol, weighted, return_P, N):
+    B = len(sizes)
+    sds = seeds.detach().cpu().numpy().astype(np.int64)
+    q = np.zeros(B, dtype=np.float64 if weighted else np.int64)
+    out = np.zeros((4, B), dtype=np.int64)                         # acc, nit, status, seeded
+    perm = np.full((B, N), -1, dtype=np.int32)
+    Ps = np.zeros((B, N, N))
+    for b, n in enumerate(sizes):
+        A, Bm, sd = As[b].astype(np.float64), Bs[b].astype(np.float64), sds[b, :n]
+        lists = _seed_lists(sd, n)
+        valid, free_a, free_b, seed_a, seed_b = lists
+        u = len(free_a)
+        pi0 = pis[b, :n] if pis is not None else None
+        pi, nit, status = np.full(n, -1), 0, 2
+        if valid and n > 0:
+            agreed = pi0 is None or bool((pi0[seed_a] == seed_b).all())
+            if not agreed:
+                pi = pi0
+            elif u == 0:
+                pi, status = sd.copy(), 0
+            else:
+                ok = pi0 is None or (bool(((pi0 >= 0) & (pi0 < n)).all()) and len(set(pi0.tolist())) == n)
+                if ok:
+                    if starts is not None:
+                        P = starts[b][np.ix_(free_a, free_b)]
+                    elif pi0 is not None:
+                        P = np.eye(u)[np.searchsorted(free_b, pi0[free_a])]
+                    else:
+                        P = np.ones((u, u)) / u
+                    A22, B22 = A[np.ix_(free_a, free_a)], Bm[np.ix_(free_b, free_b)]
+                    with np.errstate(invalid='ignore', divide='ignore'):
+                        ok = bool(np.isfinite(A22 @ P @ B22.T + A22.T @ P @ B22).all())
+                if ok:
+                    pi, nit, P, stopped = _faq_pair_seeded(A, Bm, lists, P, maxiter, tol)
+                    Ps[b, :u, :u] = P
+                    status = 0 if stopped else 1
+                elif pi0 is not None:
+                    pi = pi0
+        q[b] = (As[b] * Bs[b][pi][:, pi]).sum() if status != 2 else -1
+        perm[b, :n] = pi
+        out[:, b] = (int((pi == lab[b]).sum()), nit, status, len(seed_a))
+    t = torch.from_numpy(out)
+    res = {'perm': torch.from_numpy(perm), 'qap': torch.from_numpy(q), 'acc': t[0], 'nit': t[1], 'status': t[2], 'seeded': t[3]}
+    if return_P:
+        res['P'] = torch.from_numpy(Ps)
+    return res
+
+
+def _faq_host(adj1, adj2, nvalid, labels, p0, assign0, maxiter, tol, weighted, return_P, seeds=None):
     B, N = adj1.shape[0], adj1.shape[-2]
     sizes = _sizes(nvalid, B, N)
     lab = _label_rows(labels, sizes)
@@ -880,6 +1104,8 @@ def _faq_host(adj1, adj2, nvalid, labels, p0, assign0, maxiter, tol, weighted, r
         As, Bs = _adjacency_host(adj1, sizes), _adjacency_host(adj2, sizes)
     starts = p0.detach().cpu().double().numpy() if p0 is not None else None
     pis = assign0.detach().cpu().numpy().astype(np.int64) if assign0 is not None else None
+    if seeds is not None:
+        return _faq_host_seeded(As, Bs, sizes, lab, seeds, starts, pis, maxiter, tol, weighted, return_P, N)
     q = np.zeros(B, dtype=np.float64 if weighted else np.int64)
     out = np.zeros((3, B), dtype=np.int64)                         # acc, nit, status
     perm = np.full((B, N), -1, dtype=np.int32)

@@ -133,7 +133,7 @@ class Siamese_Node_Exp(nn.Module):
             return MaskedTensor(scores, nvalid, (1, 2), x1.base_name)
         return scores
 
-    def match(self, x1, x2, refine=0, weighted=False, labels=None, two_opt=False, faq=None):
+    def match(self, x1, x2, refine=0, weighted=False, labels=None, two_opt=False, faq=None, seeds=None):
         """Decode a batch: the eager forward under no_grad (no `.grad` is touched), the Hungarian matching of -log_softmax(scores)
         and the reference's evaluation of it (toolbox/metrics.py:168-193 all_acc_qap), all on the device (qap.py).  Takes what
         `forward` takes.  Returns a dict: scores ((bs, n, n) tensor or MaskedTensor), assign ((bs, n) int32: the matched column of
@@ -162,13 +162,23 @@ class Siamese_Node_Exp(nn.Module):
         as the start, the chain of qap.faq, and where that chain reports status 2 the stage keeps assign.  The dict gains perm (the
         stage's matching, until a later stage replaces it), qap_faq and acc_faq (int64: its objective in the unit of qap, its rows
         that meet the labels or the identity), faq_perm, faq_nit, faq_status (as the chain left them) and sinkhorn_err (None with the
-        barycenter).  0/1 batches only: with weighted=True it is refused."""
+        barycenter).  0/1 batches only: with weighted=True it is refused.
+
+        seeds (None or a (bs, n) integer tensor of known matches: seeds[b, i] = j fixes vertex i of x1 to vertex j of x2, -1 leaves
+        it free; wider rows are cut to n like labels; planted.reveal_seeds draws one): the anchors of seeded graph matching.  They
+        need the faq= stage and exclude refine > 0 (ValueError otherwise).  Sinkhorn then runs on the free block of the scores, the
+        seeded chain of qap.faq(seeds=) follows and two_opt=True runs the seeded exchange search, so faq_perm and perm hold every
+        seed; assign and acc, the Hungarian stage, stay unseeded.  The dict gains seeded (int32: the seeds per pair)."""
         if two_opt and weighted:
             raise NotImplementedError('match: two_opt=True runs on 0/1 adjacency only, not with weighted=True')
         if faq is not None and weighted:
             raise NotImplementedError('match: faq= runs on 0/1 adjacency only, not with weighted=True')
         from .evaluation import _check_faq, _faq_launches
         faq = _check_faq('match', faq)
+        if seeds is not None and faq is None:
+            raise ValueError('match: seeds= needs the faq= stage (the Hungarian matching knows no fixed rows)')
+        if seeds is not None and refine:
+            raise ValueError("match: seeds= and refine > 0 do not go together (the reference's greedy_qap knows no fixed rows)")
         a1, a2 = _unwrap_input(x1), _unwrap_input(x2)
         with torch.no_grad():
             scores = self(a1, a2)
@@ -180,6 +190,9 @@ class Siamese_Node_Exp(nn.Module):
             if torch.is_tensor(labels) and labels.dim() == 2 and labels.shape[1] > s.shape[-1]:
                 labels = labels[:, :s.shape[-1]]
             labels = labels_tensor(labels, s.shape[0], s.shape[-1], dev)
+            if torch.is_tensor(seeds) and seeds.dim() == 2 and seeds.shape[1] > s.shape[-1]:
+                seeds = seeds[:, :s.shape[-1]]
+            seeds = qap.check_seeds('match', seeds, s.shape[0], s.shape[-1], dev)
             if weighted:
                 correct, assign = lsap_device(s, nv, want_assign=True)
                 obj = qap.objective_weighted(t1, t2, assign, nv)
@@ -199,14 +212,17 @@ class Siamese_Node_Exp(nn.Module):
             if faq is not None or two_opt:
                 target = labels if labels is not None else torch.arange(s.shape[-1], dtype=torch.int32, device=dev).expand_as(assign).contiguous()
             if faq is not None:
-                st = _faq_launches(b1, b2, s.detach().float(), assign, obj['qap'].to(torch.int32), nv, s.shape[0], s.shape[-1], faq)
+                st = _faq_launches(b1, b2, s.detach().float(), assign, obj['qap'].to(torch.int32), nv, s.shape[0], s.shape[-1], faq,
+                                   seeds)
+                if seeds is not None:
+                    out['seeded'] = st['seeded']
                 out.update({'perm': st['perm'], 'qap_faq': st['qap'].to(torch.int64),
                             'acc_faq': count_matches(st['perm'], target, nv).to(torch.int64), 'faq_perm': st['faq_perm'],
                             'faq_nit': st['faq_nit'], 'faq_status': st['faq_status'], 'sinkhorn_err': st['sinkhorn_err']})
             if refine:
                 out.update(qap.greedy_bits(b1, b2, out.get('perm', assign), int(refine), nv, labels))
             if two_opt:
-                t = qap.two_opt_bits(b1, b2, out.get('perm', assign), nv)
+                t = qap.two_opt_bits(b1, b2, out.get('perm', assign), nv, seeds=seeds)
                 out.update({'perm': t['perm'], 'qap_2opt': t['qap'], 'acc_2opt': count_matches(t['perm'], target, nv).to(torch.int64),
                             'swaps': t['swaps'], 'nit': t['nit'], 'status': t['status']})
         self._raise_if_not_representation({'flag': flag})

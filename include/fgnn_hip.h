@@ -890,6 +890,13 @@ int fgnn_epoch_index(unsigned long long seed, unsigned long long epoch, long lon
 #define FGNN_PLANTED_MAX_N 256
 int fgnn_planted_perm(unsigned long long seed, long long first, const long long *index /* optional */, const int *nvalid /* optional */,
                       int B, int N, int *labels, void *stream);
+/* fgnn_reveal_seeds: a seed vector (see the seeds section below) from labels: min(count, n_b) rows of pair b keep their label, every
+ * other entry is -1.  The rows are uniform without replacement and a function of (seed, pair index) only (first / index as above):
+ * the first min(count, n_b) steps of fgnn_planted_perm's Fisher-Yates from the top on the identity, with the draws of pair stream
+ * FGNN_SEEDS_STREAM; the rows revealed are p[n_b - count .. n_b - 1]. */
+#define FGNN_SEEDS_STREAM 8
+int fgnn_reveal_seeds(unsigned long long seed, long long first, const long long *index /* optional */, const int *labels,
+                      const int *nvalid /* optional */, int B, int N, int count, int *seeds, void *stream);
 int fgnn_relabel_bits(const unsigned *in, const int *labels, const int *nvalid, int B, int N, unsigned *out, void *stream);
 int fgnn_relabel_dense(const float *in, const int *labels, const int *nvalid, int B, int C, int ld, int NL, float *out, void *stream);
 int fgnn_count_matches(const int *assign, const int *labels, const int *nvalid, int B, int N, int *correct, void *stream);
@@ -951,6 +958,14 @@ int fgnn_greedy_qap_labels(const unsigned *bits1, const unsigned *bits2, const i
  *   swaps = nit = 0.  A pair with n_b = 0: status 0, qap = 0, nit = 0. */
 int fgnn_qap_2opt(const unsigned *bits1, const unsigned *bits2, const int *assign, const int *nvalid, int B, int N, int max_swaps,
                   int *perm, int *qap, int *swaps, long long *nit, int *status, void *stream);
+/* fgnn_qap_2opt_seeded: fgnn_qap_2opt over the free rows only -- SciPy's scan over combinations_with_replacement(i_free, 2) with
+ * partial_match.  seeds: (B, N) int32 as the seeds section below describes (a negative entry: the row is free).  With f the number
+ * of free rows and r(i) the rank of row i among them, an applied pair (i, j) adds r(i) f - r(i) (r(i) - 1) / 2 + (r(j) - r(i)) + 1 to
+ * nit and the last, fruitless scan f (f + 1) / 2; the round bound stays min(max_swaps, n_b n_b).  `assign` must be a permutation of
+ * [0, n_b) that holds every seed, else status 2 (perm = assign, qap = -1, swaps = nit = 0).  Everything else as fgnn_qap_2opt; the
+ * rank table lives in LDS beside the bit matrices. */
+int fgnn_qap_2opt_seeded(const unsigned *bits1, const unsigned *bits2, const int *assign, const int *seeds, const int *nvalid, int B, int N,
+                         int max_swaps, int *perm, int *qap, int *swaps, long long *nit, int *status, void *stream);
 
 /* ---- decoding a matching on real-weighted pairs (csrc/qap_weighted.hip): the fp32 twin of the section above, for what the
  * reference's all_acc_qap / greedy_qap take besides 0/1 adjacency -- a spectral L = D^-1/2 W D^-1/2, any weighted graph ---------
@@ -1034,6 +1049,48 @@ long long fgnn_qapw_faq_ws_bytes(int B, int N);
 int fgnn_qapw_faq(const float *a1, const float *a2, long long gstride, int ld, const float *p0 /* optional, (B,N,N) */,
                   const int *assign0 /* optional, (B,N) */, const int *nvalid, int B, int N, int maxiter, float tol, void *ws,
                   long long ws_bytes, int *perm, int *nit, int *status, float *p_out /* optional, (B,N,N) */, void *stream);
+
+/* ---- seeds: known matches for the QAP solvers (csrc/qap_seeds.hip; SciPy's partial_match, seeded graph matching) ----------------
+ * seeds: (B, N) int32; seeds[b][i] = j >= 0 fixes vertex i of graph 1 to vertex j of graph 2, a negative entry leaves row i free
+ * (the convention of labels); rows i >= n_b are ignored.  Pair b has m_b seeds and u_b = n_b - m_b free vertices; free rows and
+ * free columns are taken in ascending order (SciPy's setdiff1d), seeded rows in ascending order of the row.  A pair is INVALID if a
+ * seed lies outside [0, n_b) or two rows share one.  N <= FGNN_SEED_MAX_N; B <= 65535 for the gather and the constant term.  No
+ * entry point allocates, copies to the host or synchronises; none uses an atomic: all are capturable and bit-identical from run to run.
+ *
+ * fgnn_seed_index: one workgroup per pair -> nfree[b] = u_b and nseed[b] = m_b (rows counted, whether the pair is valid or not),
+ *   valid[b] (1 / 0), and four (B, N) int32 lists, -1 past their ends and all -1 for an invalid pair: free_a, free_b (the free rows
+ *   and columns, ascending), seed_a (the seeded rows, ascending) and seed_b[s] = seeds[seed_a[s]].
+ * fgnn_seed_gather: out[b][r][c] = in[b][rows[b][r]][cols[b][c]] for r, c < nfree[b] (clamped to [0, N]) and an exact 0.0f in every
+ *   other entry of the contiguous (B, N, N) out; in has the gstride / ld addressing of the fgnn_qapw_* entry points.  Pure data
+ *   movement, bit-exact: A22 (free_a, free_a), B22 (free_b, free_b), a float P0 or scores (free_a, free_b).  An index outside
+ *   [0, N) reads as zero.
+ * fgnn_seed_const: SciPy's const_sum = A21 B21^T + A12^T B12 on the free block, into the contiguous (B, N, N) out (zero around it):
+ *   C[r][c] = sum_s A[fa r][sa s] B[fb c][sb s] + A[sa s][fa r] B[sb s][fb c], one fp32 fmaf chain per entry from 0, s ascending, the
+ *   row term before the column term.  No symmetry and no zero diagonal is assumed. */
+#define FGNN_SEED_MAX_N 256
+int fgnn_seed_index(const int *seeds, const int *nvalid /* optional */, int B, int N, int *nfree, int *nseed, int *free_a, int *free_b,
+                    int *seed_a, int *seed_b, int *valid, void *stream);
+int fgnn_seed_gather(const float *in, long long gstride, int ld, const int *rows, const int *cols, const int *nfree, int B, int N,
+                     float *out, void *stream);
+int fgnn_seed_const(const float *a1, const float *a2, long long gstride, int ld, const int *free_a, const int *free_b, const int *seed_a,
+                    const int *seed_b, const int *nfree, const int *nseed, int B, int N, float *out, void *stream);
+/* fgnn_qapw_faq_seeded (csrc/qap_faq.hip): fgnn_qapw_faq with seeds -- SciPy's method='faq' with partial_match -- as one chain of
+ * launches: fgnn_seed_index, the gathers of A22 and B22 (and of p0's free block), fgnn_seed_const, then the rounds of fgnn_qapw_faq
+ * on A22 / B22 with n_b := u_b, the gradient G = C + A22 P B22^T + A22^T P B22 and the line search
+ *     a = (<G,P> - <C,P>) / 2 - (<G,Q> - <C,Q>) + q(Q),  b = (<G,Q> - <C,Q>) - 2 q(Q) + <C,P> - <C,Q>,   q(Q) = tr(A22^T Q B22 Q^T)
+ * (fp64 sums in a fixed order; the stop test is over sqrt(u_b)).  C enters the second gradient launch in its EPILOGUE: every entry
+ * of G is the finished fmaf chain of 2 u_b terms plus C, one more rounding.  With no seeds C = 0 and every bit is fgnn_qapw_faq's.
+ * The start: the barycenter 1 / u_b; assign0, which must hold every seed; or p0 ((B, N, N) fp32, contiguous): its (free_a, free_b) block, or with p0_free != 0 its u_b x u_b corner as it is
+ * (a start already in free coordinates: Sinkhorn on the gathered scores).  The assignment of
+ * the last P is scattered back: perm[free_a[r]] = free_b[q[r]], perm[i] = seeds[i] on seeded rows, -1 past the corner.
+ * status as fgnn_qapw_faq, and: invalid seeds -> status 2, perm = -1, nit 0; assign0 against a seed -> status 2, perm = assign0,
+ * nit 0; u_b = 0 < n_b with valid seeds -> perm = seeds, nit 0, status 0.  seeded (optional, int32[B]) = m_b.  p_out (optional) = the
+ * last P IN FREE COORDINATES: the u_b x u_b corner of (B, N, N), zero around it.  ws: fgnn_qapw_faq_seeded_ws_bytes bytes. */
+long long fgnn_qapw_faq_seeded_ws_bytes(int B, int N);
+int fgnn_qapw_faq_seeded(const float *a1, const float *a2, long long gstride, int ld, const int *seeds, const float *p0 /* optional */,
+                         int p0_free, const int *assign0 /* optional */, const int *nvalid, int B, int N, int maxiter, float tol, void *ws,
+                         long long ws_bytes, int *perm, int *nit, int *status, int *seeded /* optional */,
+                         float *p_out /* optional, (B,N,N) */, void *stream);
 
 /* ---- Sinkhorn normalisation of scores (csrc/sinkhorn.hip): the doubly stochastic start fgnn_qapw_faq takes from a model's scores,
  * one workgroup per pair, the whole iteration in ONE launch, in the log domain --------------------------------------------------
