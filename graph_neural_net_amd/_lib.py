@@ -179,6 +179,12 @@ class QapRecord(C.Structure):         # fgnn_qap_record (csrc/qap_fold.hip); liv
         'unmatched', 'nodes', 'pairs', 'steps')]
 
 
+class SeedRecord(C.Structure):        # fgnn_seed_record (csrc/seed_select.hip); lives in device memory, this mirror gives the offsets
+    _fields_ = [(name, C.c_longlong) for name in (
+        'seeds', 'seed_correct', 'free_nodes', 'free_correct', 'free_refined_correct', 'clean_pairs', 'exact_free', 'nodes', 'pairs',
+        'steps')]
+
+
 MAX_GRAD_JOBS = 16
 MAX_PACK_JOBS = 24
 _VP, _LL, _I, _F = C.c_void_p, C.c_longlong, C.c_int, C.c_float
@@ -330,6 +336,9 @@ _SIGNATURES = {
     'fgnn_rank_fold': [_VP, _VP, _I, _I, _I, C.POINTER(C.c_int), _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP],
     'fgnn_qap_fold': [_VP] * 7 + [_I, _I, _I] + [_VP] * 5,
     'fgnn_qap_fold_bins': [_VP] * 7 + [_I, _I, _I, _VP, _I] + [_VP] * 5,
+    'fgnn_confident_seeds': [_VP, _LL, _I, _VP, _I, _I, _I, _F, _VP, _VP, _VP, _VP],
+    'fgnn_seed_fold': [_VP] * 5 + [_I, _I, _I, _VP, _VP],
+    'fgnn_seed_fold_bins': [_VP] * 5 + [_I, _I, _I, _VP, _I, _VP, _VP],
     # ---- bf16 path ----
     'fgnn_tiles_per_graph16': [_I, _I],
     'fgnn_to_bf16': [_VP, _VP, _I, _I, _I, _I, _VP, _LL, _LL, _VP],

@@ -22,7 +22,10 @@ bits=, refine=, two_opt=)`` issues it after its own launches on the assignment i
 real-weighted decode stays per batch.  ``faq=`` puts the Fast Approximate QAP chain (csrc/qap_faq.hip) between the Hungarian
 matching and the refinement, started from the Sinkhorn projection of the scores (csrc/sinkhorn.hip) or from the barycenter.
 
-The six meters are one thing -- records of one ctypes struct in one device buffer (``_Records``) -- with three record types.
+``seeds=`` of the decode takes known matches -- a tensor, or a spec that draws them from the scores themselves (csrc/seed_select.hip:
+fgnn_confident_seeds) -- and ``seed_meter=`` a ``SeedMeter`` / ``BinnedSeedMeter`` that says what the seeds were worth.
+
+The eight meters are one thing -- records of one ctypes struct in one device buffer (``_Records``) -- with four record types.
 """
 import ctypes
 
@@ -67,6 +70,7 @@ class _Records:
     record, its FIELDS 0-dim views of `buf`; a binned meter (_BinnedRecords) is K of them side by side.  A record type adds
     `_dict` (a ctypes record -> a dict of Python numbers) and `_result` (that dict -> the epoch's figures)."""
     RECORD, FIELDS, NOUN = None, (), 'record lives'
+    HEAD_FP64 = True            # word 0 is an fp64 sum (False: every word is an int64 count)
 
     def _open(self, device, K=1, buf=None):
         """The device refusal, then K zeroed records -- or `buf`, the bytes of one record of a binned meter.  -> the device"""
@@ -76,7 +80,7 @@ class _Records:
         self.buf = torch.zeros(K * ctypes.sizeof(self.RECORD), dtype=torch.uint8, device=device) if buf is None else buf
         for j, name in enumerate(self.FIELDS):              # (a binned meter has none: its records' fields are its meters')
             off = getattr(self.RECORD, name).offset
-            setattr(self, name, self.buf[off:off + 8].view(torch.float64 if j == 0 else torch.int64).reshape(()))
+            setattr(self, name, self.buf[off:off + 8].view(torch.float64 if j == 0 and self.HEAD_FP64 else torch.int64).reshape(()))
         return device
 
     def reset(self):
@@ -95,6 +99,11 @@ class _Records:
         """Sum the records over the ranks: one all-reduce of one fp64 value per 8-byte word (the counts are exact below 2^53)."""
         words = ctypes.sizeof(self.RECORD) // 8
         K = self.buf.numel() // (8 * words)
+        if not self.HEAD_FP64:
+            t = self.buf.view(torch.int64).to(torch.float64)
+            dp.allreduce_sum_(t)
+            self.buf.view(torch.int64).copy_(t.round().to(torch.int64))
+            return self
         t = pack_records(self.buf, K, words)
         dp.allreduce_sum_(t)
         unpack_records_(self.buf, K, t)
@@ -353,6 +362,58 @@ class BinnedQapMeter(_BinnedRecords):
             m.refined = True
 
 
+def seed_result(rec):
+    """The seed figures of an epoch from a SeedRecord dict: 'seed_precision' = seed_correct / seeds, 'seeds_per_pair' = seeds / pairs,
+    'free_acc' = free_correct / free_nodes and 'free_refined_acc' = free_refined_correct / free_nodes (the rows WITHOUT a seed that
+    the first and the final matching handed to the fold got right), 'clean' (pairs whose every seed is right) and 'exact_free'
+    (pairs whose every free row of the final matching is right) as fractions of the pairs, 'seeds', 'free_nodes', 'nodes', 'pairs'.
+    An empty denominator gives NaN."""
+    div = lambda a, b: a / b if b else float('nan')
+    return {'seed_precision': div(rec['seed_correct'], rec['seeds']), 'seeds_per_pair': div(rec['seeds'], rec['pairs']),
+            'free_acc': div(rec['free_correct'], rec['free_nodes']),
+            'free_refined_acc': div(rec['free_refined_correct'], rec['free_nodes']), 'clean': div(rec['clean_pairs'], rec['pairs']),
+            'exact_free': div(rec['exact_free'], rec['pairs']), 'seeds': rec['seeds'], 'free_nodes': rec['free_nodes'],
+            'nodes': rec['nodes'], 'pairs': rec['pairs']}
+
+
+class SeedMeter(_Records):
+    """The device record of the seeds of a decode epoch (fgnn_seed_record, include/fgnn_hip.h): how many rows were seeded, how many
+    of the seeds were right, and what the matchings recovered on the rows that were NOT given -- the figure the QapMeter cannot
+    give, because fgnn_qap_fold counts a seeded row as a hit.  Every field is a 0-dim int64 view of the record; `seed_precision`,
+    `free_acc` and `free_refined_acc` are 0-dim fp64 device tensors formed from them on the device.  `result()` (seed_result) is
+    the only host synchronisation."""
+    RECORD, FIELDS, HEAD_FP64 = _lib.SeedRecord, tuple(name for name, _ in _lib.SeedRecord._fields_), False
+    _result = staticmethod(seed_result)
+
+    def __init__(self, device, buf=None):
+        """buf: the record's bytes when they belong to a larger buffer (a record of a BinnedSeedMeter)"""
+        self._open(device, buf=buf)
+
+    def _dict(self, rec):
+        return {name: getattr(rec, name) for name in self.FIELDS}
+
+    @property
+    def seed_precision(self):
+        """seed_correct / seeds of everything folded so far (NaN before the first seed)"""
+        return self.seed_correct.to(torch.float64) / self.seeds.to(torch.float64)
+
+    @property
+    def free_acc(self):
+        return self.free_correct.to(torch.float64) / self.free_nodes.to(torch.float64)
+
+    @property
+    def free_refined_acc(self):
+        return self.free_refined_correct.to(torch.float64) / self.free_nodes.to(torch.float64)
+
+
+class BinnedSeedMeter(_BinnedRecords):
+    """K seed records, one per bin: `meter[k]` is a SeedMeter; see _BinnedRecords."""
+    PLAIN, RECORD, HEAD_FP64 = SeedMeter, _lib.SeedRecord, False
+
+    def __init__(self, device, K, values=None):
+        self._open_bins(device, self._check_bins(K, values), values)
+
+
 RANK_WORDS = ctypes.sizeof(_lib.RankRecord) // 8
 unpack_rank_records_ = unpack_records_
 
@@ -532,22 +593,39 @@ def _faq_launches(b1, b2, s, assign, q, nvalid, B, N, faq, seeds=None):
     return res
 
 
+def seed_fold(seed_meter, seeds, first, final, nvalid, labels, bins, B, N, live):
+    """fgnn_seed_fold(_bins) on checked (B, N) int32 device tensors: seeds (None: every row free), `first` (the matching the seeds
+    went into) and `final` (the last matching of the chain, or None) against labels (None: the identity) into seed_meter"""
+    pairs = (_lib.ptr(seeds), _lib.ptr(first), _lib.ptr(final), _lib.ptr(labels), _lib.ptr(nvalid), B, N, live)
+    if bins is None:
+        _lib.call('fgnn_seed_fold', *pairs, _lib.ptr(seed_meter.buf), _lib.stream_ptr())
+    else:
+        _lib.call('fgnn_seed_fold_bins', *pairs, _lib.ptr(bins), seed_meter.K, _lib.ptr(seed_meter.buf), _lib.stream_ptr())
+
+
 def _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt=False, faq=None, scores=None,
-                     seeds=None):
-    """qap.objective_bits (once more on the labels), _faq_launches with faq (on `scores`), qap.greedy_bits with refine > 0,
-    qap.two_opt_bits with two_opt, then fgnn_qap_fold(_bins), on checked arguments (on the current stream of the bit words' device)
+                     seeds=None, seed_meter=None):
+    """qap.objective_bits (once more on the labels), fgnn_confident_seeds on `scores` when seeds is a spec, _faq_launches with faq
+    (on `scores`), qap.greedy_bits with refine > 0, qap.two_opt_bits with two_opt, then fgnn_qap_fold(_bins) and, with a
+    seed_meter, fgnn_seed_fold(_bins), on checked arguments (on the current stream of the bit words' device)
     -> the dict of decode_scores"""
     from . import qap
     dev = b1.device
+    nseeds = None
+    if isinstance(seeds, dict):     # a spec: the seeds come from the scores the solver saw
+        picked = qap.confident_seeds_device(scores, nvalid, seeds['count'], seeds['min_margin'])
+        seeds, nseeds = picked['seeds'], picked['nseeds']
     obj = qap.objective_bits(b1, b2, assign, nvalid, raw=True)
     q, planted = obj[0], obj[1]
     if labels is not None:          # (as all_acc_qap: planted is the objective of the labels' matching)
         planted = qap.objective_bits(b1, b2, labels, nvalid, raw=True)[0]
     perm = refined = None
+    first = assign
     stage = dict.fromkeys(('faq_perm', 'faq_qap', 'faq_nit', 'faq_status', 'sinkhorn_err'))
     if faq is not None:
         stage = _faq_launches(b1, b2, scores, assign, q, nvalid, B, N, faq, seeds)
         perm, refined = stage.pop('perm'), stage.pop('qap')
+        first = perm
         meter._mark_refined()
     if refine > 0:
         g = qap.greedy_bits(b1, b2, assign if perm is None else perm, refine, nvalid, labels, raw=True)
@@ -569,6 +647,11 @@ def _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, re
         _lib.call('fgnn_qap_fold', *pairs, *outs)
     else:
         _lib.call('fgnn_qap_fold_bins', *pairs, _lib.ptr(bins), meter.K, *outs)
+    if seed_meter is not None:
+        seed_fold(seed_meter, seeds, first, perm, nvalid, labels, bins, B, N, live)
+        stage['seed_meter'] = seed_meter
+    if seeds is not None:
+        stage['seeds'], stage['nseeds'] = seeds, stage['seeded'] if nseeds is None else nseeds
     return {'assign': assign, 'qap': q, 'planted': planted, 'correct': correct, 'ratio': ratio, 'perm': perm, 'refined': refined,
             'refined_correct': None if perm is None else refined_correct, 'meter': meter, 'swaps': swaps, 'status': status, **stage}
 
@@ -579,12 +662,45 @@ def _check_two_opt(who, two_opt):
     return two_opt
 
 
+SEED_SPEC_DEFAULTS = {'from': 'scores', 'count': None, 'min_margin': 0.0}
+
+
+def seed_spec(who, seeds):
+    """seeds= as a spec -- 'scores' or a dict with keys from {'from': 'scores', 'count': None, 'min_margin': 0.0} -> the checked
+    {'count': int (-1: no cap), 'min_margin': float} of qap.confident_seeds_device; None when seeds is neither (a tensor, None)"""
+    if isinstance(seeds, str):
+        seeds = {'from': seeds}
+    elif not isinstance(seeds, dict):
+        return None
+    unknown = sorted(set(seeds) - set(SEED_SPEC_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError('%s: seeds has unknown key(s) %s; the keys are %s' % (who, unknown, sorted(SEED_SPEC_DEFAULTS)))
+    o = dict(SEED_SPEC_DEFAULTS, **seeds)
+    if o['from'] != 'scores':
+        raise ValueError("%s: seeds['from'] is 'scores', got %r" % (who, o['from']))
+    from .qap import check_confident
+    count, min_margin = check_confident('%s: seeds' % who, o['count'], o['min_margin'])
+    return {'count': count, 'min_margin': min_margin}
+
+
+def _check_seed_meter(who, seed_meter, bins, dev, K=None):
+    if seed_meter is None:
+        return
+    _check_meter(who, 'seed meter', BinnedSeedMeter, seed_meter, bins, dev)
+    if bins is not None and K is not None and seed_meter.K != K:
+        raise ValueError('%s: the seed meter has %d records, the meter %d' % (who, seed_meter.K, K))
+
+
 def _check_decode_seeds(who, seeds, B, N, dev, faq, refine):
-    """seeds= of the decode -> (B, N) int32 on dev or None; seeds need the faq= stage and exclude refine"""
+    """seeds= of the decode -> (B, N) int32 on dev, the checked spec of seed_spec, or None; seeds need the faq= stage and exclude
+    refine"""
     if seeds is None:
         return None
     from . import qap
-    seeds = qap.check_seeds(who, seeds, B, N, dev)
+    spec = seed_spec(who, seeds)
+    if spec is not None and N > _lib.FGNN_SEED_MAX_N:
+        raise RuntimeError('%s: seeds from the scores take at most %d vertices per graph (got %d)' % (who, _lib.FGNN_SEED_MAX_N, N))
+    seeds = qap.check_seeds(who, seeds, B, N, dev) if spec is None else spec
     if faq is None:
         raise ValueError('%s: seeds= needs the faq= stage (the Hungarian matching knows no fixed rows)' % who)
     if refine > 0:
@@ -593,7 +709,7 @@ def _check_decode_seeds(who, seeds, B, N, dev, faq, refine):
 
 
 def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, bins=None, refine=0, assign=None,
-                  two_opt=False, faq=None, seeds=None):
+                  two_opt=False, faq=None, seeds=None, seed_meter=None):
     """The reference's all_acc_qap / all_greedy_losses_acc (toolbox/metrics.py:168-223) of a batch, added to an epoch record.
     scores, nvalid, labels, live, bins: as evaluate_scores takes them, with the same refusals; bits1, bits2: the two graphs as
     (B, N, ceil(N/32)) int32 bit words on the scores' device (PairGenerator.bits, synthetic.pack_adjacency).  0/1 graphs only: the
@@ -628,6 +744,15 @@ def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, li
     fgnn_qapw_faq_seeded follows, and two_opt=True runs fgnn_qap_2opt_seeded, so 'faq_perm' and 'perm' hold every seed.  The
     Hungarian stage ('assign', 'correct') stays unseeded; the fold and the meters are unchanged.  The dict gains 'seeded' (B,) int32
     = m_b.  seeds=None issues the launches and returns the keys it always did.
+    seeds may also be a spec -- 'scores', or {'from': 'scores', 'count': k, 'min_margin': x} (an unknown key or 'from' raises
+    ValueError) -- the seeds the model's own scores give: one fgnn_confident_seeds launch (qap.confident_seeds: rows whose best
+    column picks them back with margin >= x, the k clearest of them) on the scores the solver saw, its output going where a seed
+    tensor goes.  The rules are the same: the faq= stage, no refine.  With any seeds the dict gains 'seeds' (B, N) int32 and
+    'nseeds' (B,) int32.
+    seed_meter: a SeedMeter (with bins= a BinnedSeedMeter of the meter's K) -- fgnn_seed_fold(_bins) runs after fgnn_qap_fold with
+    the same labels, live and bins and adds, per live pair, the seeds that are right and the rows WITHOUT a seed that the faq stage's
+    matching (without faq: assign) and the final `perm` of the chain got right; it comes back under 'seed_meter'.  The QapMeter and
+    its fold are untouched: they count a seeded row as a hit.
     Nothing is read back."""
     if meter is None and bins is not None:
         raise ValueError('decode_scores: bins= and a BinnedQapMeter as meter go together')
@@ -642,6 +767,7 @@ def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, li
         meter = QapMeter(dev)
     else:
         _check_meter('decode_scores', 'meter', BinnedQapMeter, meter, bins, dev)
+    _check_seed_meter('decode_scores', seed_meter, bins, dev, meter.K if bins is not None else None)
     if assign is not None:
         if not torch.is_tensor(assign) or tuple(assign.shape) != (B, N) or assign.is_floating_point() or assign.device != dev:
             raise ValueError('decode_scores: assign must be a (%d, %d) integer tensor on %s' % (B, N, dev))
@@ -650,11 +776,11 @@ def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, li
         if assign is None:
             from .metrics import lsap_device
             assign = lsap_device(s, nvalid, want_assign=True)[1]
-        return _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt, faq, s, seeds)
+        return _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt, faq, s, seeds, seed_meter)
 
 
 def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False, bins=None,
-                    rank_meter=None, qap_meter=None, bits=None, refine=0, two_opt=False, faq=None):
+                    rank_meter=None, qap_meter=None, bits=None, refine=0, two_opt=False, faq=None, seeds=None, seed_meter=None):
     """scores: (B, N, N) fp32 raw scores on the GPU, or a MaskedTensor of them (its vertex counts are used unless nvalid is given).
     nvalid: (B,) vertex counts in [0, N]; labels: see metrics.py (None: the identity; they enter the accuracies, never the loss).
     live: the first `live` pairs count (None: all B) -- the others, the filling of a short last step, are ignored entirely.
@@ -675,6 +801,8 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
     hungarian=False is refused), with refine rounds of greedy refinement and, with two_opt=True, the pairwise-exchange search
     after them, on the same labels, live and bins; its per-pair tensors come back under 'decode'.  0/1 graphs only (see decode_scores).  None: nothing of this is launched.
     faq (with a qap_meter): the Fast Approximate QAP stage of decode_scores, started from these scores or from the barycenter.
+    seeds, seed_meter (with a qap_meter): a (B, N) seed tensor or the spec of decode_scores ('scores', or a dict), and a SeedMeter
+    (with bins=: a BinnedSeedMeter) -- both are handed to the decode, with its refusals: seeds need faq= and exclude refine > 0.
     Four launches, nothing is read back."""
     if isinstance(meter, BinnedEvalMeter) != (bins is not None):
         raise ValueError('evaluate_scores: bins= and a BinnedEvalMeter as meter go together')
@@ -685,6 +813,8 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
             raise ValueError('evaluate_scores: two_opt= belongs to a qap_meter')
         if faq is not None:
             raise ValueError('evaluate_scores: faq= belongs to a qap_meter')
+        if seeds is not None or seed_meter is not None:
+            raise ValueError('evaluate_scores: seeds= and seed_meter= belong to a qap_meter')
     else:
         if not hungarian:
             raise ValueError('evaluate_scores: a qap_meter decodes the matching of the Hungarian solver; it needs hungarian=True')
@@ -704,6 +834,8 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
         if bins is not None and qap_meter.K != meter.K:
             raise ValueError('evaluate_scores: the qap meter has %d records, the meter %d' % (qap_meter.K, meter.K))
         bits = _bits_args('evaluate_scores', bits, B, N, dev)
+        seeds = _check_decode_seeds('evaluate_scores', seeds, B, N, dev, faq, refine)
+        _check_seed_meter('evaluate_scores', seed_meter, bins, dev, meter.K if bins is not None else None)
     with torch.cuda.device(dev):
         i32 = dict(dtype=torch.int32, device=dev)
         cost = torch.empty(B, N, N, dtype=torch.float32, device=dev)
@@ -730,7 +862,8 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
         ranks = None if rank_meter is None else _rank_launches(s, nvalid, labels, bins, B, N, live, rank_meter)
         decode = None
         if qap_meter is not None:
-            decode = _decode_launches(*bits, assign, nvalid, labels, bins, B, N, live, qap_meter, refine, two_opt, faq, s)
+            decode = _decode_launches(*bits, assign, nvalid, labels, bins, B, N, live, qap_meter, refine, two_opt, faq, s, seeds,
+                                      seed_meter)
     n = nvalid if nvalid is not None else torch.full((B,), N, **i32)
     out = {'ce': pair_ce, 'n': n, 'correct_max': pair_max, 'correct_lsap': correct, 'assign': assign, 'meter': meter}
     if ranks is not None:

@@ -54,6 +54,9 @@ Fast Approximate QAP algorithm: Frank-Wolfe on the relaxed objective, needing no
 ``sinkhorn`` (``csrc/sinkhorn.hip``) turns a batch of scores into doubly stochastic matrices with one launch -- the start ``faq``
 takes from a model (``faq(..., P0=sinkhorn(scores)['P'])``), and the first step of the ``faq=`` stage of
 ``evaluation.decode_scores``.
+
+``confident_seeds`` (``csrc/seed_select.hip``) takes a seed vector for ``faq(seeds=)`` / ``two_opt(seeds=)`` from the scores themselves:
+the rows whose best column picks them back with a clear margin; ``seeds='scores'`` on the decode runs it on the scores the solver saw.
 """
 import numpy as np
 import torch
@@ -547,6 +550,71 @@ def sinkhorn(scores, nvalid=None, tau=1.0, iters=20):
         out = sinkhorn_device(scores.to(torch.float32), _nv32(nvalid, scores.device), tau, iters)
     out['status'] = out['status'].to(torch.int64)
     return out
+
+
+def check_confident(who, count, min_margin):
+    """count: None or an integer >= 0; min_margin: a number >= 0 (no NaN), else ValueError -> (int count, -1 for None; float)"""
+    if count is None:
+        count = -1
+    elif isinstance(count, bool) or not isinstance(count, (int, np.integer)) or count < 0:
+        raise ValueError("%s: 'count' must be None or an integer >= 0, got %r" % (who, count))
+    if isinstance(min_margin, bool) or not isinstance(min_margin, (int, float, np.floating, np.integer)) or not min_margin >= 0:
+        raise ValueError("%s: 'min_margin' must be a number >= 0, got %r" % (who, min_margin))
+    return min(int(count), 0x7fffffff), float(np.float32(min_margin))
+
+
+def confident_seeds_device(s, nv, count=-1, min_margin=0.0, return_margin=False):
+    """fgnn_confident_seeds on (B, N, N) fp32 device scores (read in place when the rows are contiguous, pitched views included) ->
+    {'seeds': (B, N) int32, 'nseeds': (B,) int32 (+ 'margin': (B, N) fp32)} as the launch wrote them; never synchronises."""
+    B, N = s.shape[0], s.shape[-1]
+    dev = s.device
+    if not _chan0_ok(s):
+        s = s.contiguous()
+    seeds = torch.empty(B, N, dtype=torch.int32, device=dev)
+    nseeds = torch.empty(B, dtype=torch.int32, device=dev)
+    margin = torch.empty(B, N, dtype=torch.float32, device=dev) if return_margin else None
+    _lib.call('fgnn_confident_seeds', _lib.ptr(s), s.stride(0) if B > 1 else N * s.stride(-2), s.stride(-2), _lib.ptr(nv), B, N, count,
+              min_margin, _lib.ptr(seeds), _lib.ptr(nseeds), _lib.ptr(margin), _lib.stream_ptr())
+    out = {'seeds': seeds, 'nseeds': nseeds}
+    if return_margin:
+        out['margin'] = margin
+    return out
+
+
+def confident_seeds(scores, nvalid=None, count=None, min_margin=0.0, return_margin=False):
+    """Seeds from a model's own scores (``csrc/seed_select.hip``): the rows whose best column picks them back, with a clear margin.
+    Per pair, on the n_b x n_b corner: c_i is the arg-max column of row i, m_i = s[i, c_i] - (the largest value among the other
+    columns of row i), one float32 subtraction (+inf for n_b = 1); r_j is the arg-max row of column j; ties take the smaller index
+    in both.  A row that holds a NaN, or whose maximum is not finite, has m_i = -inf and is never a candidate; a column that holds a
+    NaN has no r_j.  Row i is a candidate iff r_{c_i} == i and m_i >= min_margin; of the candidates the `count` first in (margin
+    descending, row ascending) order are kept (None: all of them).  Mutual best makes the targets distinct, so the result is always
+    a valid seed vector for ``faq(seeds=)``, ``two_opt(seeds=)`` and the decode.
+    scores: a (B, N, N) floating-point tensor or a MaskedTensor of one (its vertex counts are used unless nvalid is given);
+    nvalid: a (B,) integer tensor, clamped to [0, N].  Nothing outside a pair's corner is read.  count negative or no integer,
+    min_margin negative or NaN, scores of another rank or dtype: ValueError.
+    -> {'seeds': (B, N) int32, c_i on the kept rows and -1 everywhere else, 'nseeds': (B,) int32} and with return_margin 'margin':
+    (B, N) float32, m_i on the corner's rows and 0 in the padding, on the scores' device.
+    The device route is ONE launch that reads the scores in place (a strided view with contiguous rows included), bit-identical
+    from run to run, a pair's result independent of the batch; it never synchronises.  CPU tensors and N > 256 take the same rule
+    restated in numpy, with the margin in float32 arithmetic: the two routes agree exactly."""
+    count, min_margin = check_confident('confident_seeds', count, min_margin)
+    if isinstance(scores, MaskedTensor):
+        if nvalid is None:
+            nvalid = scores.nvalid
+        scores = scores.tensor.rename(None)
+    if not torch.is_tensor(scores) or scores.dim() != 3 or scores.shape[1] != scores.shape[2] or not scores.is_floating_point():
+        raise ValueError('confident_seeds: expected (B, N, N) floating-point scores, got %s'
+                         % (tuple(scores.shape) if torch.is_tensor(scores) else type(scores).__name__,))
+    B, N = scores.shape[0], scores.shape[-1]
+    if B < 1 or N < 1:
+        raise ValueError('confident_seeds: empty batch %s' % (tuple(scores.shape),))
+    if nvalid is not None and (not torch.is_tensor(nvalid) or tuple(nvalid.shape) != (B,) or nvalid.is_floating_point()):
+        raise ValueError('confident_seeds: nvalid must be a (%d,) integer tensor' % B)
+    scores = scores.detach()
+    if not scores.is_cuda or N > _lib.FGNN_SEED_MAX_N:
+        return _confident_seeds_host(scores, nvalid, count, min_margin, return_margin)
+    with torch.cuda.device(scores.device):
+        return confident_seeds_device(scores.to(torch.float32), _nv32(nvalid, scores.device), count, min_margin, return_margin)
 
 
 def qap_objective(adj1, adj2, assign, nvalid=None, weighted=False):
@@ -1162,6 +1230,41 @@ def _sinkhorn_host(scores, nvalid, tau, iters):
         err[b] = np.abs(P[b, :n, :n].sum(1) - 1.0).max()
     dev = scores.device
     return {'P': torch.from_numpy(P).to(dev), 'err': torch.from_numpy(err).to(dev), 'status': torch.from_numpy(status).to(dev)}
+
+
+def _confident_seeds_host(scores, nvalid, count, min_margin, return_margin):
+    """The rule of fgnn_confident_seeds in numpy: float32 scores, one float32 subtraction per margin, np.argmax's first maximum"""
+    B, N = scores.shape[0], scores.shape[-1]
+    S = scores.to(torch.float32).cpu().numpy()
+    seeds = np.full((B, N), -1, dtype=np.int32)
+    nseeds = np.zeros(B, dtype=np.int32)
+    margin = np.zeros((B, N), dtype=np.float32)
+    neg = np.float32(-np.inf)
+    for b, n in enumerate(_sizes(nvalid, B, N)):
+        if n == 0:
+            continue
+        s = S[b, :n, :n]
+        nan = np.isnan(s)
+        z = np.where(nan, neg, s)                                  # a NaN never wins; its row and column are struck below
+        c, r = z.argmax(1), z.argmax(0)
+        best = z[np.arange(n), c]
+        rest = z.copy()
+        rest[np.arange(n), c] = neg
+        with np.errstate(invalid='ignore', over='ignore'):
+            m = (best - rest.max(1)).astype(np.float32) if n > 1 else np.full(n, np.inf, dtype=np.float32)
+        m[nan.any(1) | ~np.isfinite(best)] = neg
+        r = np.where(nan.any(0), -1, r)
+        cand = (r[c] == np.arange(n)) & (m >= np.float32(min_margin))
+        order = [i for i in sorted(range(n), key=lambda i: (-m[i], i)) if cand[i]]      # margin descending, row ascending
+        keep = np.array(order if count < 0 else order[:count], dtype=np.int64)
+        seeds[b, keep] = c[keep]
+        nseeds[b] = len(keep)
+        margin[b, :n] = m
+    dev = scores.device
+    out = {'seeds': torch.from_numpy(seeds).to(dev), 'nseeds': torch.from_numpy(nseeds).to(dev)}
+    if return_margin:
+        out['margin'] = torch.from_numpy(margin).to(dev)
+    return out
 
 
 def _all_acc_qap_host_w(scores, adj1, adj2, nvalid, labels=None):

@@ -133,7 +133,7 @@ class Siamese_Node_Exp(nn.Module):
             return MaskedTensor(scores, nvalid, (1, 2), x1.base_name)
         return scores
 
-    def match(self, x1, x2, refine=0, weighted=False, labels=None, two_opt=False, faq=None, seeds=None):
+    def match(self, x1, x2, refine=0, weighted=False, labels=None, two_opt=False, faq=None, seeds=None, seed_meter=None):
         """Decode a batch: the eager forward under no_grad (no `.grad` is touched), the Hungarian matching of -log_softmax(scores)
         and the reference's evaluation of it (toolbox/metrics.py:168-193 all_acc_qap), all on the device (qap.py).  Takes what
         `forward` takes.  Returns a dict: scores ((bs, n, n) tensor or MaskedTensor), assign ((bs, n) int32: the matched column of
@@ -168,13 +168,21 @@ class Siamese_Node_Exp(nn.Module):
         it free; wider rows are cut to n like labels; planted.reveal_seeds draws one): the anchors of seeded graph matching.  They
         need the faq= stage and exclude refine > 0 (ValueError otherwise).  Sinkhorn then runs on the free block of the scores, the
         seeded chain of qap.faq(seeds=) follows and two_opt=True runs the seeded exchange search, so faq_perm and perm hold every
-        seed; assign and acc, the Hungarian stage, stay unseeded.  The dict gains seeded (int32: the seeds per pair)."""
+        seed; assign and acc, the Hungarian stage, stay unseeded.  The dict gains seeded (int32: the seeds per pair).
+        seeds may also be a spec -- 'scores', or {'from': 'scores', 'count': k, 'min_margin': x} -- the seeds the model's own scores
+        give (qap.confident_seeds: rows whose best column picks them back with margin >= x, the k clearest; one launch on the scores
+        the solver saw), under the same rules.  With any seeds the dict gains seeds ((bs, n) int32) and nseeds ((bs,) int32).
+        seed_meter (an evaluation.SeedMeter, with faq=): the seeds that are right and the rows without a seed that the faq stage's
+        and the final matching got right are added to it (fgnn_seed_fold, against the labels or the identity)."""
         if two_opt and weighted:
             raise NotImplementedError('match: two_opt=True runs on 0/1 adjacency only, not with weighted=True')
         if faq is not None and weighted:
             raise NotImplementedError('match: faq= runs on 0/1 adjacency only, not with weighted=True')
-        from .evaluation import _check_faq, _faq_launches
+        from .evaluation import SeedMeter, _check_faq, _faq_launches, seed_fold, seed_spec
         faq = _check_faq('match', faq)
+        spec = seed_spec('match', seeds)
+        if seed_meter is not None and (not isinstance(seed_meter, SeedMeter) or faq is None):
+            raise ValueError('match: seed_meter must be a SeedMeter and needs the faq= stage')
         if seeds is not None and faq is None:
             raise ValueError('match: seeds= needs the faq= stage (the Hungarian matching knows no fixed rows)')
         if seeds is not None and refine:
@@ -192,7 +200,15 @@ class Siamese_Node_Exp(nn.Module):
             labels = labels_tensor(labels, s.shape[0], s.shape[-1], dev)
             if torch.is_tensor(seeds) and seeds.dim() == 2 and seeds.shape[1] > s.shape[-1]:
                 seeds = seeds[:, :s.shape[-1]]
-            seeds = qap.check_seeds('match', seeds, s.shape[0], s.shape[-1], dev)
+            nseeds = None
+            if spec is None:
+                seeds = qap.check_seeds('match', seeds, s.shape[0], s.shape[-1], dev)
+            else:
+                if s.shape[-1] > qap._lib.FGNN_SEED_MAX_N:
+                    raise RuntimeError('match: seeds from the scores take at most %d vertices per graph (got %d)'
+                                       % (qap._lib.FGNN_SEED_MAX_N, s.shape[-1]))
+                picked = qap.confident_seeds_device(s.detach().float(), nv, spec['count'], spec['min_margin'])
+                seeds, nseeds = picked['seeds'], picked['nseeds']
             if weighted:
                 correct, assign = lsap_device(s, nv, want_assign=True)
                 obj = qap.objective_weighted(t1, t2, assign, nv)
@@ -216,6 +232,7 @@ class Siamese_Node_Exp(nn.Module):
                                    seeds)
                 if seeds is not None:
                     out['seeded'] = st['seeded']
+                    out['seeds'], out['nseeds'] = seeds, st['seeded'] if nseeds is None else nseeds
                 out.update({'perm': st['perm'], 'qap_faq': st['qap'].to(torch.int64),
                             'acc_faq': count_matches(st['perm'], target, nv).to(torch.int64), 'faq_perm': st['faq_perm'],
                             'faq_nit': st['faq_nit'], 'faq_status': st['faq_status'], 'sinkhorn_err': st['sinkhorn_err']})
@@ -225,6 +242,8 @@ class Siamese_Node_Exp(nn.Module):
                 t = qap.two_opt_bits(b1, b2, out.get('perm', assign), nv, seeds=seeds)
                 out.update({'perm': t['perm'], 'qap_2opt': t['qap'], 'acc_2opt': count_matches(t['perm'], target, nv).to(torch.int64),
                             'swaps': t['swaps'], 'nit': t['nit'], 'status': t['status']})
+            if seed_meter is not None:
+                seed_fold(seed_meter, seeds, st['perm'], out['perm'], nv, labels, None, s.shape[0], s.shape[-1], s.shape[0])
         self._raise_if_not_representation({'flag': flag})
         return out
 

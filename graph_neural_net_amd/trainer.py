@@ -609,7 +609,7 @@ class FgnnTrainer:
         return evaluate_scores(self._eval_forward(B, N, nvalid, x=x, bits=bits, spectral=spectral), nvalid=nvalid, **options)
 
     def eval_step_bits(self, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False,
-                       bins=None, rank_meter=None, qap_meter=None, refine=0, two_opt=False, faq=None):
+                       bins=None, rank_meter=None, qap_meter=None, refine=0, two_opt=False, faq=None, seeds=None, seed_meter=None):
         """Forward-only evaluation of a batch handed over as train_step_bits takes it: the training engine's forward pass (a third of
         a step's work), then evaluation.evaluate_scores on its scores -- see there for labels, meter, live, hungarian,
         loss_on_labels, bins, rank_meter and the returned per-pair device tensors.  Nothing is read back; parameters, gradients and optimizer state keep their bits.
@@ -618,25 +618,30 @@ class FgnnTrainer:
         two_opt=True (with a qap_meter): the chain ends in the pairwise-exchange search of qap.two_opt_bits, one more launch, and the
         meter's refined figures describe its matching.
         faq (with a qap_meter): None, True or the dict of evaluation.decode_scores -- the Fast Approximate QAP stage between the
-        Hungarian matching and the refinement, started from the Sinkhorn projection of this step's scores or from the barycenter."""
+        Hungarian matching and the refinement, started from the Sinkhorn projection of this step's scores or from the barycenter.
+        seeds, seed_meter (with a qap_meter and faq): a (B, N) seed tensor or the spec of evaluation.decode_scores -- 'scores' draws
+        the seeds from this step's scores (qap.confident_seeds) -- and a SeedMeter (with bins= a BinnedSeedMeter); both go to the
+        decode, which refuses seeds without faq= and with refine > 0."""
         return self._eval_step_words('eval_step_bits', bits1, bits2, nvalid, None, labels=labels, meter=meter, live=live,
                                      hungarian=hungarian, loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter,
-                                     qap_meter=qap_meter, refine=refine, two_opt=two_opt, faq=faq)
+                                     qap_meter=qap_meter, refine=refine, two_opt=two_opt, faq=faq, seeds=seeds, seed_meter=seed_meter)
 
     def eval_step_spectral(self, bits1, bits2, nvalid=None, n_powers=4, labels=None, meter=None, live=None, hungarian=True,
-                           loss_on_labels=False, bins=None, rank_meter=None, qap_meter=None, refine=0, two_opt=False, faq=None):
+                           loss_on_labels=False, bins=None, rank_meter=None, qap_meter=None, refine=0, two_opt=False, faq=None,
+                           seeds=None, seed_meter=None):
         """The twin of eval_step_bits for spectral input: the forward pass runs on the features L, ..., L^n_powers of the bit words
         (engine.forward(spectral=...), as train_step_spectral), everything after the scores is eval_step_bits'.
-        qap_meter, refine, two_opt, faq: the decode runs on the BIT WORDS handed in here -- the QAP objective on the adjacency W, not on the
+        qap_meter, refine, two_opt, faq, seeds, seed_meter: the decode runs on the BIT WORDS handed in here -- the QAP objective on the adjacency W, not on the
         normalised L the model sees.  On regular graphs L = W / d, so the ratio to the planted objective is the one the reference
         reports for its spectral pairs; the reference's literal decode on channel 0 of the features stays what
         ``match(..., weighted=True)`` computes per batch."""
         n_powers = self._check_features('eval_step_spectral', n_powers)
         return self._eval_step_words('eval_step_spectral', bits1, bits2, nvalid, n_powers, labels=labels, meter=meter, live=live,
                                      hungarian=hungarian, loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter,
-                                     qap_meter=qap_meter, refine=refine, two_opt=two_opt, faq=faq)
+                                     qap_meter=qap_meter, refine=refine, two_opt=two_opt, faq=faq, seeds=seeds, seed_meter=seed_meter)
 
-    def _eval_step_words(self, who, bits1, bits2, nvalid, n_powers, qap_meter=None, refine=0, two_opt=False, faq=None, **options):
+    def _eval_step_words(self, who, bits1, bits2, nvalid, n_powers, qap_meter=None, refine=0, two_opt=False, faq=None, seeds=None,
+                         seed_meter=None, **options):
         """eval_step_bits (n_powers None) / eval_step_spectral: one body, the engine keyword differs"""
         B, N = self._bits_shape(who, bits1, bits2)
         decode = {} if qap_meter is None and not refine else {'qap_meter': qap_meter, 'pair_bits': (bits1, bits2), 'refine': refine}
@@ -644,6 +649,10 @@ class FgnnTrainer:
             decode = dict(decode, qap_meter=qap_meter, two_opt=two_opt)
         if faq is not None:
             decode = dict(decode, qap_meter=qap_meter, faq=faq)
+        if seeds is not None:
+            decode = dict(decode, qap_meter=qap_meter, seeds=seeds)
+        if seed_meter is not None:
+            decode = dict(decode, qap_meter=qap_meter, seed_meter=seed_meter)
         b = torch.cat([bits1, bits2]).contiguous()
         src = {'bits': b} if n_powers is None else {'spectral': (b, n_powers)}
         return self._eval_tail(B, N, nvalid, **src, **options, **decode)
@@ -659,7 +668,8 @@ class FgnnTrainer:
                                hungarian=hungarian, loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter)
 
     def evaluate(self, generator, sampler, batch_size, epoch=0, hungarian=True, meter=None, permute=False, loss_on_labels=False,
-                 rank_meter=None, qap_meter=None, refine=0, features=None, n_powers=4, two_opt=False, faq=None):
+                 rank_meter=None, qap_meter=None, refine=0, features=None, n_powers=4, two_opt=False, faq=None, seeds=None,
+                 seed_meter=None):
         """One pass over this rank's examples of `sampler` (sampler.EpochSampler; shuffle=False is the reference's validation
         loader): per step ``eval_step_bits(*generator.bits(index=sampler.batch_index(epoch, step, batch_size)))`` with the generator's
         vertex counts and, with permute=True, its planted labels.  Every example counts exactly once: the positions with which a
@@ -677,9 +687,13 @@ class FgnnTrainer:
         meter's 'refined_acc', 'refined_qap_ratio' and 'improved' describe the matching it leaves.
         faq (with a qap_meter): None, True or the dict of evaluation.decode_scores -- every step's chain runs the Fast Approximate
         QAP stage after the Hungarian matching; the refined figures describe the last stage of the chain that ran.
+        seeds (with a qap_meter and faq): what eval_step_bits takes -- 'scores' or the spec dict: every step's seeds come from its own
+        scores -- or an integer k: every step reveals k rows of the planted labels,
+        ``planted.reveal_seeds(labels, nvalid, k, generator.seed, index=...)`` with the step's example indices (needs permute=True,
+        ValueError otherwise).  seed_meter: a SeedMeter that takes every step's seed fold and is summed over the ranks like the meter.
         features='spectral', n_powers: the steps are eval_step_spectral on the same words (the decode of a qap_meter stays on the
         adjacency, see there).  None: eval_step_bits, as before."""
-        from .evaluation import EvalMeter, QapMeter, RankMeter
+        from .evaluation import EvalMeter, QapMeter, RankMeter, SeedMeter
         spec = self._features('evaluate', features, n_powers)
         B = int(batch_size)
         if meter is None:
@@ -690,16 +704,18 @@ class FgnnTrainer:
             raise ValueError('FgnnTrainer.evaluate: rank_meter must be a RankMeter or None (got %s)' % type(rank_meter).__name__)
         if qap_meter is not None and not isinstance(qap_meter, QapMeter):
             raise ValueError('FgnnTrainer.evaluate: qap_meter must be a QapMeter or None (got %s)' % type(qap_meter).__name__)
+        if seed_meter is not None and not isinstance(seed_meter, SeedMeter):
+            raise ValueError('FgnnTrainer.evaluate: seed_meter must be a SeedMeter or None (got %s)' % type(seed_meter).__name__)
         def batches():
             for step in range(sampler.steps_per_epoch(B)):
                 live = sampler.live_count(step, B)
                 if live:        # (0: a rank past the end of the data in the last global step; its index is never made)
                     yield live, None, {'index': sampler.batch_index(epoch, step, B), 'permute': permute}
         return self._eval_epoch(generator, batches(), meter, rank_meter, dp.world_size() > 1, hungarian, loss_on_labels, qap_meter,
-                                refine, spec, two_opt, faq)
+                                refine, spec, two_opt, faq, seeds, seed_meter)
 
     def _eval_epoch(self, generator, batches, meter, rank_meter, reduce, hungarian, loss_on_labels, qap_meter=None, refine=0, spec=None,
-                    two_opt=False, faq=None):
+                    two_opt=False, faq=None, seeds=None, seed_meter=None):
         """The loop of evaluate and noise_curve.  batches: per step that has a live pair (live, bins, the keyword arguments of
         generator.bits); reduce: sum the meters over the ranks at the end; spec: None or the n_powers of spectral steps.  -> meter"""
         if qap_meter is None and refine:
@@ -713,8 +729,24 @@ class FgnnTrainer:
             decode['two_opt'] = two_opt
         if faq is not None:
             decode['faq'] = faq
+        if qap_meter is None and (seeds is not None or seed_meter is not None):
+            raise ValueError('FgnnTrainer: seeds= and seed_meter= belong to a qap_meter')
+        reveal = None
+        if seeds is not None and not isinstance(seeds, (str, dict)) and not torch.is_tensor(seeds):
+            if isinstance(seeds, bool) or not hasattr(seeds, '__index__') or seeds < 0:
+                raise ValueError("FgnnTrainer: seeds must be a seed tensor, 'scores', a spec dict or an integer >= 0, got %r" % (seeds,))
+            reveal = int(seeds)
+        elif seeds is not None:
+            decode['seeds'] = seeds
+        if seed_meter is not None:
+            decode['seed_meter'] = seed_meter
         for live, bins, bits_kw in batches:
+            if reveal is not None and not bits_kw.get('permute'):
+                raise ValueError('FgnnTrainer: an integer seeds= reveals rows of the planted labels; it needs permute=True')
             b1, b2, nv, *labels = generator.bits(**bits_kw)
+            if reveal is not None:
+                from .planted import reveal_seeds
+                decode['seeds'] = reveal_seeds(labels[0], nv, reveal, generator.seed, index=bits_kw['index'])
             kw = dict(nvalid=nv, labels=labels[0] if labels else None, meter=meter, live=live, hungarian=hungarian,
                       loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter, **decode)
             if spec is None:
@@ -727,6 +759,8 @@ class FgnnTrainer:
                 rank_meter.allreduce_()
             if qap_meter is not None:
                 qap_meter.allreduce_()
+            if seed_meter is not None:
+                seed_meter.allreduce_()
         return meter
 
     @staticmethod
@@ -741,7 +775,7 @@ class FgnnTrainer:
 
     def noise_curve(self, generator, noises, num_examples, batch_size, hungarian=True, permute=False, loss_on_labels=False,
                     rank=None, world_size=None, meter=None, rank_meter=None, qap_meter=None, refine=0, features=None, n_powers=4,
-                    two_opt=False, faq=None):
+                    two_opt=False, faq=None, seeds=None, seed_meter=None):
         """The reference's result figure (README.md, "Results": a trained model evaluated across noise levels; per level
         toolbox/metrics.py:144-166) in one pass: the first num_examples pairs of `generator` at each of the K = len(noises) noise
         levels -- the SAME parent graphs at every level, a paired design -- through full batches of mixed levels
@@ -760,8 +794,10 @@ class FgnnTrainer:
         qap_meter: a BinnedQapMeter of K records that takes the decode of every level (see `evaluate`; refine: its rounds of
         greedy refinement; two_opt: the pairwise-exchange search at its end; faq: the Fast Approximate QAP stage before them) from the same steps -- the QAP ratio across noise
         levels; it is summed over the ranks where the meter is.
+        seeds: as in `evaluate` (an integer k reveals the same rows of a pair at every level: the choice depends on the pair's index
+        alone); seed_meter: a BinnedSeedMeter of K records, summed over the ranks where the meter is.
         features='spectral', n_powers: as in `evaluate`."""
-        from .evaluation import BinnedEvalMeter, BinnedQapMeter, BinnedRankMeter
+        from .evaluation import BinnedEvalMeter, BinnedQapMeter, BinnedRankMeter, BinnedSeedMeter
         spec = self._features('noise_curve', features, n_powers)
         from .sampler import EpochSampler
         levels = generator.levels(noises)
@@ -776,6 +812,8 @@ class FgnnTrainer:
             raise ValueError('FgnnTrainer.noise_curve: rank_meter must be a BinnedRankMeter of %d records or None' % K)
         if qap_meter is not None and (not isinstance(qap_meter, BinnedQapMeter) or qap_meter.K != K):
             raise ValueError('FgnnTrainer.noise_curve: qap_meter must be a BinnedQapMeter of %d records or None' % K)
+        if seed_meter is not None and (not isinstance(seed_meter, BinnedSeedMeter) or seed_meter.K != K):
+            raise ValueError('FgnnTrainer.noise_curve: seed_meter must be a BinnedSeedMeter of %d records or None' % K)
         if world_size is None:
             world_size = dp.world_size()
         if rank is None:        # (this process's rank in the split of torch.distributed; any other split has to name it)
@@ -787,10 +825,10 @@ class FgnnTrainer:
                 if live:        # (0: a rank past the end of the examples in the last global step)
                     yield live, level, {'index': pair, 'levels': levels, 'level': level, 'permute': permute}
         return self._eval_epoch(generator, batches(), meter, rank_meter, dp.world_size() > 1 and sampler.world_size == dp.world_size(),
-                                hungarian, loss_on_labels, qap_meter, refine, spec, two_opt, faq)
+                                hungarian, loss_on_labels, qap_meter, refine, spec, two_opt, faq, seeds, seed_meter)
 
     def fit(self, train_gen, train_sampler, val_gen, val_sampler, epochs, batch_size, scheduler=None, permute=False, exact_last=False,
-            rank_ks=None, decode_refine=None, features=None, n_powers=4, decode_two_opt=False, decode_faq=None):
+            rank_ks=None, decode_refine=None, features=None, n_powers=4, decode_two_opt=False, decode_faq=None, decode_seeds=None):
         """The reference's training loop around its scheduler (models/trainers.py:92-104): per epoch train_epoch, evaluate, ONE host
         read (the validation record), scheduler.step(val_loss).  scheduler=None: optim.ReduceLROnPlateau with the reference's
         settings, driving self.opt.lr (the next step pushes a changed rate to the device).  Returns the per-epoch history: dicts
@@ -812,15 +850,22 @@ class FgnnTrainer:
         decode_faq (with decode_refine, which may be 0): None, True or the dict of evaluation.decode_scores -- the validation decode
         runs the Fast Approximate QAP stage (evaluate(faq=...)); 'val_refined_acc' and 'val_refined_qap_ratio' are then reported
         for every T, as with decode_two_opt, and describe the last stage of the chain.
+        decode_seeds (with decode_faq; decode_refine may be left out and is then 0): what evaluate(seeds=...) takes -- 'scores', the spec dict, or an integer
+        k with permute=True -- the validation decode is seeded, and every epoch's dict gains 'val_seed_precision' (the seeds that
+        are right over the seeds) and 'val_free_acc' (the rows without a seed the seeded stage got right over those rows), from a
+        SeedMeter read in the same single host copy.
         features='spectral', n_powers: training and validation run on the spectral features of the generators' pairs (train_epoch /
         evaluate with the same arguments)."""
         fkw = {} if features is None else {'features': features, 'n_powers': self._features('fit', features, n_powers)}
-        from .evaluation import EvalMeter, QapMeter, RankMeter, _check_faq, _check_refine, qap_result, rank_result, read_records, record_result
+        from .evaluation import (EvalMeter, QapMeter, RankMeter, SeedMeter, _check_faq, _check_refine, qap_result, rank_result,
+                                 read_records, record_result, seed_result)
         if scheduler is None:
             from .optim import ReduceLROnPlateau
             scheduler = ReduceLROnPlateau(self.opt)
         history = []
         rank_meter = None if rank_ks is None else RankMeter(self.params.device, ks=rank_ks)
+        if decode_seeds is not None and decode_refine is None:       # (seeds exclude refine > 0: theirs is the decode without rounds)
+            decode_refine = 0
         if decode_refine is not None:
             decode_refine = _check_refine('FgnnTrainer.fit', decode_refine)
         if decode_two_opt and decode_refine is None:
@@ -828,14 +873,19 @@ class FgnnTrainer:
         if decode_faq is not None and decode_refine is None:
             raise ValueError('FgnnTrainer.fit: decode_faq= belongs to a decode_refine (which may be 0)')
         decode_faq = _check_faq('FgnnTrainer.fit', decode_faq)
+        if decode_seeds is not None and decode_faq is None:
+            raise ValueError('FgnnTrainer.fit: decode_seeds= needs decode_faq= (seeds need the faq stage of the decode)')
         qap_meter = None if decode_refine is None else QapMeter(self.params.device)
-        extra = [m for m in (rank_meter, qap_meter) if m is not None]
+        seed_meter = None if decode_seeds is None else SeedMeter(self.params.device)
+        extra = [m for m in (rank_meter, qap_meter, seed_meter) if m is not None]
         own = EvalMeter(self.params.device) if extra else None                       # (read together with the other meters)
         decode = {} if qap_meter is None else {'qap_meter': qap_meter, 'refine': decode_refine}
         if decode_two_opt is not False:
             decode['two_opt'] = decode_two_opt
         if decode_faq is not None:
             decode['faq'] = decode_faq
+        if decode_seeds is not None:
+            decode.update(seeds=decode_seeds, seed_meter=seed_meter)
         for epoch in range(int(epochs)):
             for m in extra + [own] * bool(extra):
                 m.reset()
@@ -861,6 +911,9 @@ class FgnnTrainer:
                     history[-1]['val_refined_acc'] = qres['refined_acc']
                 if decode_two_opt or decode_faq is not None:
                     history[-1]['val_refined_qap_ratio'] = qres['refined_qap_ratio']
+            if seed_meter is not None:
+                sres = seed_result(others[id(seed_meter)])
+                history[-1]['val_seed_precision'], history[-1]['val_free_acc'] = sres['seed_precision'], sres['free_acc']
         return history
 
     def train_step(self, x1, x2, nvalid=None, labels=None, weights=None, live=None):

@@ -1272,6 +1272,60 @@ int fgnn_qap_fold_bins(const int *assign, const int *perm /* optional */, const 
                        const int *bin /* (B) */, int K, int *pair_correct /* optional */, int *pair_refined_correct /* optional */,
                        double *pair_ratio /* optional */, fgnn_qap_record *records /* K records */, void *stream);
 
+/* ---- confident seeds (csrc/seed_select.hip): a seed vector for the seeded solvers from a model's own scores, and its meter ------
+ * fgnn_confident_seeds.  scores: B pairs of (N, N) fp32, row pitch ld >= N, pairs bstride >= N ld floats apart; nvalid (optional,
+ * int32[B]): pair b is the n x n corner, n = n_b clamped to [0, N]; NOTHING outside the corner is read (it may hold NaN).
+ * N <= FGNN_SEED_MAX_N.  Per pair:
+ *   rows     c_i = the arg-max column of row i over [0, n), top2_i = the largest value among the OTHER columns, m_i = s[i][c_i] -
+ *            top2_i, one fp32 subtraction (+inf for n = 1, and wherever top2_i is -inf).  A row that holds a NaN anywhere in its
+ *            corner, or whose maximum is not finite, is never a candidate: m_i = -inf.
+ *   columns  r_j = the arg-max row of column j over [0, n); a column that holds a NaN has none.
+ *   ties     the smaller index, in both passes; -0.0 == +0.0 (the order of fgnn_accuracy_max and fgnn_eval_ranks).
+ *   row i is a CANDIDATE iff r_{c_i} == i and m_i >= min_margin (min_margin >= 0, no NaN).  Mutual best makes the targets distinct
+ *   and puts them inside [0, n): the output is always a valid seed vector for fgnn_seed_index.
+ *   candidate i is KEPT iff fewer than `count` candidates come before it (count < 0: no cap); k comes before i when m_k > m_i, or
+ *   m_k == m_i and k < i.  The rank is a count over the candidates, so nothing depends on a sort's or an atomic's order.
+ * Outputs: seeds (B, N) int32 = c_i on kept rows and -1 in every other entry of the N, the padding rows included; nseeds int32[B] =
+ * the kept rows; margin (optional, (B, N) fp32) = m_i for i < n and 0 in the padding.  n = 0: all -1, nseeds 0.
+ * One launch with one workgroup per pair; the matrix is read once (row reads coalesced along j feed the row and the column pass),
+ * every reduction has a fixed order: bit-identical from run to run, a pair's result independent of the batch around it.  No
+ * workspace, no allocation, no host copy, no synchronisation: capturable.
+ *
+ * fgnn_seed_fold, for the pairs b < live (0 <= live <= B; the others are ignored entirely); all inputs int32 on the device: seeds
+ * (B, N) optional (NULL: every row is free); assign (B, N): the first matching; perm (B, N) optional: the final matching of the
+ * decode chain; labels (B, N) optional; nvalid (B) optional.  target(b, i) = labels ? labels[b][i] : i, none outside [0, n_b).
+ * A row i < n_b is SEEDED when seeds[b][i] >= 0, else FREE.  Per pair, m = the seeded rows, then ONE workgroup adds the pairs to the
+ * record in pair order:
+ *   seeds += m, seed_correct += #{seeded i : seeds[b][i] == target}, free_nodes += n_b - m,
+ *   free_correct += #{free i : assign[b][i] == target}, free_refined_correct += #{free i : perm[b][i] == target} (with perm; without
+ *   it the field is not touched), clean_pairs += [every seed is right], exact_free += [every free row of perm -- of assign without
+ *   perm -- is right], nodes += n_b, pairs += 1; steps += 1 per call that added a pair.  A record that took no pair is not written.
+ *   Integer sums: a record does not depend on how its examples were cut into calls.
+ * fgnn_seed_fold_bins: the same kernel with K contiguous records (1 <= K <= FGNN_MAX_LEVELS): record k receives the pairs b < live
+ *   with bin[b] == k and ends with the bytes fgnn_seed_fold leaves after folding just those pairs into the same starting record; a
+ *   pair whose bin lies outside [0, K) is added nowhere.
+ * Both are single launches on `stream`: capturable, no allocation, no host copy, no synchronisation. */
+typedef struct {
+    long long seeds;                /* seeded rows */
+    long long seed_correct;         /* seeded rows whose seed is the row's target */
+    long long free_nodes;           /* rows without a seed */
+    long long free_correct;         /* free rows with assign == target */
+    long long free_refined_correct; /* free rows with perm == target */
+    long long clean_pairs;          /* pairs whose every seed is right */
+    long long exact_free;           /* pairs whose every free row of the final matching is right */
+    long long nodes;                /* sum of n_b */
+    long long pairs;                /* live pairs folded */
+    long long steps;                /* fold calls that added a pair */
+} fgnn_seed_record;
+int fgnn_confident_seeds(const float *scores, long long bstride, int ld, const int *nvalid /* optional */, int B, int N,
+                         int count /* < 0: no cap */, float min_margin, int *seeds, int *nseeds, float *margin /* optional, (B,N) */,
+                         void *stream);
+int fgnn_seed_fold(const int *seeds /* optional */, const int *assign, const int *perm /* optional */, const int *labels /* optional */,
+                   const int *nvalid /* optional */, int B, int N, int live, fgnn_seed_record *meter, void *stream);
+int fgnn_seed_fold_bins(const int *seeds /* optional */, const int *assign, const int *perm /* optional */,
+                        const int *labels /* optional */, const int *nvalid /* optional */, int B, int N, int live,
+                        const int *bin /* (B) */, int K, fgnn_seed_record *records /* K records */, void *stream);
+
 /* ---- test-only entry points (never on the product path; tests/ and tools/ call them) ---------------------------------------
  * fgnn_debug_mlp_fwd_masks / fgnn_debug_mlp_fwd_x3_masks: fgnn_mlp_fwd / fgnn_mlp_fwd_x3 once more -- the same tile code, the same
  * outputs, bit for bit -- that ALSO exports the ReLU decisions of the conv chain (models/layers.py:129-130), the input of the
