@@ -17,12 +17,19 @@
 // The pairs i < j are taken QAP_THREADS at a time in scan order (a pair (i,i) never improves: it only counts in nit), and the
 // workgroup meets every OPT_PER of them per thread: the first meeting that holds an improving pair holds the first one.
 // Rows have an odd pitch: lanes read rows j at lane-dependent words.
+//
+// Seeds (fgnn_qap_2opt_seeded) are the SEEDED instantiation of the same kernel body: the search over the free rows only, SciPy's
+// scan over combinations_with_replacement(i_free, 2).  fr[r] = the r-th free row (ascending) is the rank table, f their number:
+// the scan walks the rank pairs (ri, rj), ri < rj, in the order above with n := f and exchanges rows fr[ri], fr[rj]; ascending
+// ranks are ascending rows, so the smallest key (ri << 8) | rj is still the first improving pair of SciPy's scan, and its 1-based
+// position is ri f - ri (ri - 1) / 2 + (rj - ri) + 1.  Without seeds f = n and the rank of a row is the row, at compile time: no
+// table exists and none is read.  The gains, the exchange and the round bound n^2 do not know about seeds.
 #include "fgnn_qap_bits.h"
+#include "fgnn_qap_search.h"
 
 namespace {
 
 constexpr int OPT_PER = 4;                     // pairs per thread between two meetings of the workgroup
-constexpr unsigned OPT_NONE = 0xffffffffu;     // no improving pair (a real key is (i << 8) | j < 2^16)
 
 template <int NW>
 DEVI int exchange_gain(const unsigned *a, const unsigned *at, const unsigned *bp, const unsigned *bpt, const int *row_s, const int *col_s,
@@ -40,16 +47,17 @@ DEVI int exchange_gain(const unsigned *a, const unsigned *at, const unsigned *bp
     return g + da * db;
 }
 
-// One workgroup per pair.  LDS (NW = 8): five matrices of 256 x 9 words (the fifth stages B and Bt for the gather) + 4 KB = 50 KB.
-template <int NW>
+// One workgroup per pair.  LDS (NW = 8): five matrices of 256 x 9 words (the fifth stages B and Bt for the gather) + 4 KB = 50 KB;
+// SEEDED adds the rank table (1 KB).  seeds is not read when !SEEDED (it comes last: the other arguments keep their places).
+template <int NW, bool SEEDED>
 __global__ __launch_bounds__(QAP_THREADS) void qap_2opt_kernel(const unsigned *bits1, const unsigned *bits2, const int *assign,
                                                                const int *nvalid, int N, int max_swaps, int *perm, int *qap, int *swaps,
-                                                               long long *nit, int *status) {
+                                                               long long *nit, int *status, const int *seeds) {
     constexpr int P = NW | 1, R = 32 * NW, WAVES = QAP_THREADS / 64;
     __shared__ unsigned a_l[R * P], at_l[R * P], bp_l[R * P], bpt_l[R * P], stage[R * P];
-    __shared__ int pl[R], cnt[R], row_s[R], col_s[R];
+    __shared__ int pl[R], cnt[R], row_s[R], col_s[R], fr[SEEDED ? R : 1];
     __shared__ unsigned red[2][WAVES];
-    __shared__ int sum_s[WAVES];
+    __shared__ int sum_s[WAVES], free_s[SEEDED ? WAVES : 1];
     __shared__ int bad_s;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int n = corner_of(nvalid, b, N), W = (N + 31) >> 5;
@@ -57,28 +65,34 @@ __global__ __launch_bounds__(QAP_THREADS) void qap_2opt_kernel(const unsigned *b
     const int *pi = assign + (long long)b * N;
     int *po = perm + (long long)b * N;
 
-    // pl = assign on the corner (-1 past it), refused unless it is a permutation of [0, n)
-    for (int m = tid; m < R; m += QAP_THREADS) {
-        pl[m] = -1;
-        cnt[m] = 0;
-    }
-    if (tid == 0) bad_s = 0;
-    __syncthreads();
-    for (int k = tid; k < n; k += QAP_THREADS) {
-        const int p = pi[k];
-        if (p >= 0 && p < n) {
-            pl[k] = p;
-            atomicAdd(&cnt[p], 1);
-        } else {
-            bad_s = 1;
+    // pl = assign on the corner (-1 past it), refused unless it is a permutation of [0, n) -- that holds every seed
+    load_start<QAP_THREADS>(pl, cnt, &bad_s, pi, n, R, tid);
+    int nfree = n;                              // the rows the scan walks, and the row of a scan rank
+    const auto row_of = [&](int rank) {
+        if constexpr (SEEDED) return fr[rank];
+        else return rank;
+    };
+    if constexpr (SEEDED) {
+        const int sd = tid < n ? seeds[(long long)b * N + tid] : 0;    // (n <= QAP_THREADS: thread t owns row t)
+        const bool is_free = tid < n && sd < 0;
+        if (tid < n && sd >= 0 && pl[tid] != sd) bad_s = 1;
+        // the rank table: ballot and prefix counts, the waves in order
+        const unsigned long long fm = __ballot(is_free);
+        if ((tid & 63) == 0) free_s[tid >> 6] = __popcll(fm);
+        __syncthreads();
+        int rank = __popcll(fm & ((1ull << (tid & 63)) - 1ull));
+        nfree = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) {
+            rank += w < (tid >> 6) ? free_s[w] : 0;
+            nfree += free_s[w];
         }
+        if (is_free) fr[rank] = tid;
     }
-    __syncthreads();
-    for (int m = tid; m < n; m += QAP_THREADS)
-        if (cnt[m] != 1) bad_s = 1;
+    const int f = nfree;
     __syncthreads();
     if (bad_s) {                                // uniform
-        for (int k = tid; k < N; k += QAP_THREADS) po[k] = k < n ? pi[k] : -1;
+        refuse_start<QAP_THREADS>(po, pi, n, N, tid);
         if (tid == 0) {
             qap[b] = -1;
             swaps[b] = 0;
@@ -117,43 +131,39 @@ __global__ __launch_bounds__(QAP_THREADS) void qap_2opt_kernel(const unsigned *b
     }
 
     // The rounds: a counted loop.  Every exchange raises S <= n^2 by at least 1, so n^2 rounds end any search on their own.
-    const int pairs = n * (n - 1) / 2;
+    const int pairs = f * (f - 1) / 2;
     const int bound = max_swaps < 0 ? n * n : min(max_swaps, n * n);
     int done = 0, st = n == 0 ? 0 : 1, par = 0;
     long long evals = 0;
     for (int round = 0; round < bound; ++round) {
         __syncthreads();                        // Bp, Bpt, row_s, col_s of this round
-        unsigned best = OPT_NONE;
-        int i = 0, j = 1 + tid;                 // pair number tid of the scan without its (i,i)
+        unsigned best = SEARCH_NONE;
+        int i = 0, j = 1 + tid;                 // (rank) pair number tid of the scan without its (i,i)
         for (int base = 0; base < pairs; base += OPT_PER * QAP_THREADS) {       // uniform
-            unsigned key = OPT_NONE;
+            unsigned key = SEARCH_NONE;
 #pragma unroll
             for (int c = 0; c < OPT_PER; ++c) {
-                while (j >= n && i < n - 1) {   // past the end of row i: on into the next row
+                while (j >= f && i < f - 1) {   // past the end of row i: on into the next row
                     ++i;
-                    j += i + 1 - n;
+                    j += i + 1 - f;
                 }
-                if (i < n - 1) {
-                    if (exchange_gain<NW>(a_l, at_l, bp_l, bpt_l, row_s, col_s, i, j) > 0) key = min(key, (unsigned)((i << 8) | j));
+                if (i < f - 1) {
+                    if (exchange_gain<NW>(a_l, at_l, bp_l, bpt_l, row_s, col_s, row_of(i), row_of(j)) > 0)
+                        key = min(key, (unsigned)((i << 8) | j));
                     j += QAP_THREADS;
                 }
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) key = min(key, (unsigned)__shfl_xor((int)key, o));
-            if ((tid & 63) == 0) red[par][tid >> 6] = key;
-            __syncthreads();
-#pragma unroll
-            for (int w = 0; w < WAVES; ++w) best = min(best, red[par][w]);
+            best = first_key<WAVES>(key, best, red[par], tid);
             par ^= 1;                           // (the next meeting writes the other half: no second barrier)
-            if (best != OPT_NONE) break;        // uniform
+            if (best != SEARCH_NONE) break;     // uniform
         }
-        if (best == OPT_NONE) {                 // a whole scan without an improving pair
-            evals += (long long)n * (n + 1) / 2;
+        if (best == SEARCH_NONE) {              // a whole scan without an improving pair
+            evals += full_scan(f);
             st = 0;
             break;
         }
-        const int bi = (int)(best >> 8), bj = (int)(best & 255u);
-        evals += (long long)bi * n - (long long)bi * (bi - 1) / 2 + (bj - bi) + 1;
+        const int ri = (int)(best >> 8), rj = (int)(best & 255u), bi = row_of(ri), bj = row_of(rj);
+        evals += scan_position(ri, rj, f);
         ++done;
         // rows bi, bj of Bp and Bpt change places, then bits bi, bj of every row
         if (tid < 2 * NW) {
@@ -208,204 +218,30 @@ __global__ __launch_bounds__(QAP_THREADS) void qap_2opt_kernel(const unsigned *b
     }
 }
 
-template <int NW>
-int launch_2opt(const unsigned *bits1, const unsigned *bits2, const int *assign, const int *nvalid, int B, int N, int max_swaps, int *perm,
-                int *qap, int *swaps, long long *nit, int *status, hipStream_t st) {
-    hipLaunchKernelGGL((qap_2opt_kernel<NW>), dim3(B), dim3(QAP_THREADS), 0, st, bits1, bits2, assign, nvalid, N, max_swaps, perm, qap, swaps,
-                       nit, status);
+template <int NW, bool SEEDED>
+int launch_2opt(const unsigned *bits1, const unsigned *bits2, const int *assign, const int *seeds, const int *nvalid, int B, int N,
+                int max_swaps, int *perm, int *qap, int *swaps, long long *nit, int *status, hipStream_t st) {
+    hipLaunchKernelGGL((qap_2opt_kernel<NW, SEEDED>), dim3(B), dim3(QAP_THREADS), 0, st, bits1, bits2, assign, nvalid, N, max_swaps, perm,
+                       qap, swaps, nit, status, seeds);
     FGNN_LAUNCH_CHECK();
     return 0;
 }
 
-// ---- seeds (fgnn_qap_2opt_seeded): the search above over the free rows only, SciPy's scan over
-// combinations_with_replacement(i_free, 2).  fr[r] = the r-th free row (ascending) is the rank table, f their number: the scan
-// walks the rank pairs (ri, rj), ri < rj, in the order above with n := f and exchanges rows fr[ri], fr[rj]; ascending ranks are
-// ascending rows, so the smallest key (ri << 8) | rj is still the first improving pair of SciPy's scan, and its 1-based position is
-// ri f - ri (ri - 1) / 2 + (rj - ri) + 1.  The gains, the exchange and the round bound n^2 are those of qap_2opt_kernel.
-template <int NW>
-__global__ __launch_bounds__(QAP_THREADS) void qap_2opt_seeded_kernel(const unsigned *bits1, const unsigned *bits2, const int *assign,
-                                                                      const int *seeds, const int *nvalid, int N, int max_swaps,
-                                                                      int *perm, int *qap, int *swaps, long long *nit, int *status) {
-    constexpr int P = NW | 1, R = 32 * NW, WAVES = QAP_THREADS / 64;
-    __shared__ unsigned a_l[R * P], at_l[R * P], bp_l[R * P], bpt_l[R * P], stage[R * P];
-    __shared__ int pl[R], cnt[R], row_s[R], col_s[R], fr[R];
-    __shared__ unsigned red[2][WAVES];
-    __shared__ int sum_s[WAVES], free_s[WAVES];
-    __shared__ int bad_s;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int n = corner_of(nvalid, b, N), W = (N + 31) >> 5;
-    const unsigned *A = bits1 + (long long)b * N * W, *Bm = bits2 + (long long)b * N * W;
-    const int *pi = assign + (long long)b * N;
-    int *po = perm + (long long)b * N;
-
-    // pl = assign on the corner (-1 past it), refused unless it is a permutation of [0, n) that holds every seed
-    for (int m = tid; m < R; m += QAP_THREADS) {
-        pl[m] = -1;
-        cnt[m] = 0;
-    }
-    if (tid == 0) bad_s = 0;
-    __syncthreads();
-    const int sd = tid < n ? seeds[(long long)b * N + tid] : 0;        // (n <= QAP_THREADS: thread t owns row t)
-    const bool is_free = tid < n && sd < 0;
-    if (tid < n) {
-        const int p = pi[tid];
-        if (p >= 0 && p < n) {
-            pl[tid] = p;
-            atomicAdd(&cnt[p], 1);
-        } else {
-            bad_s = 1;
-        }
-        if (sd >= 0 && p != sd) bad_s = 1;
-    }
-    // the rank table: ballot and prefix counts, the waves in order
-    const unsigned long long fm = __ballot(is_free);
-    if ((tid & 63) == 0) free_s[tid >> 6] = __popcll(fm);
-    __syncthreads();
-    for (int m = tid; m < n; m += QAP_THREADS)
-        if (cnt[m] != 1) bad_s = 1;
-    int f = 0, rank = __popcll(fm & ((1ull << (tid & 63)) - 1ull));
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-        rank += w < (tid >> 6) ? free_s[w] : 0;
-        f += free_s[w];
-    }
-    if (is_free) fr[rank] = tid;
-    __syncthreads();
-    if (bad_s) {                                // uniform
-        for (int k = tid; k < N; k += QAP_THREADS) po[k] = k < n ? pi[k] : -1;
-        if (tid == 0) {
-            qap[b] = -1;
-            swaps[b] = 0;
-            nit[b] = 0;
-            status[b] = 2;
-        }
-        return;
-    }
-
-    stage_rows<NW>(a_l, P, A, 0, R, n, W, tid);
-    stage_transposed<NW>(at_l, P, A, n, W, tid);
-    stage_rows<NW>(stage, P, Bm, 0, R, n, W, tid);
-    __syncthreads();
-    for (int idx = tid; idx < n * NW; idx += QAP_THREADS) {
-        const int r = idx / NW, w = idx - r * NW;
-        bp_l[r * P + w] = permuted_word(stage + pl[r] * P, pl, w);
-    }
-    __syncthreads();
-    stage_transposed<NW>(stage, P, Bm, n, W, tid);
-    __syncthreads();
-    for (int idx = tid; idx < n * NW; idx += QAP_THREADS) {
-        const int r = idx / NW, w = idx - r * NW;
-        bpt_l[r * P + w] = permuted_word(stage + pl[r] * P, pl, w);
-    }
-    __syncthreads();
-    for (int r = tid; r < n; r += QAP_THREADS) {
-        int rs = 0, cs = 0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            rs += __popc(a_l[r * P + w] & bp_l[r * P + w]);
-            cs += __popc(at_l[r * P + w] & bpt_l[r * P + w]);
-        }
-        row_s[r] = rs;
-        col_s[r] = cs;
-    }
-
-    const int pairs = f * (f - 1) / 2;
-    const int bound = max_swaps < 0 ? n * n : min(max_swaps, n * n);
-    int done = 0, st = n == 0 ? 0 : 1, par = 0;
-    long long evals = 0;
-    for (int round = 0; round < bound; ++round) {
-        __syncthreads();
-        unsigned best = OPT_NONE;
-        int i = 0, j = 1 + tid;                 // rank pair number tid of the scan without its (i,i)
-        for (int base = 0; base < pairs; base += OPT_PER * QAP_THREADS) {       // uniform
-            unsigned key = OPT_NONE;
-#pragma unroll
-            for (int c = 0; c < OPT_PER; ++c) {
-                while (j >= f && i < f - 1) {
-                    ++i;
-                    j += i + 1 - f;
-                }
-                if (i < f - 1) {
-                    if (exchange_gain<NW>(a_l, at_l, bp_l, bpt_l, row_s, col_s, fr[i], fr[j]) > 0) key = min(key, (unsigned)((i << 8) | j));
-                    j += QAP_THREADS;
-                }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) key = min(key, (unsigned)__shfl_xor((int)key, o));
-            if ((tid & 63) == 0) red[par][tid >> 6] = key;
-            __syncthreads();
-#pragma unroll
-            for (int w = 0; w < WAVES; ++w) best = min(best, red[par][w]);
-            par ^= 1;
-            if (best != OPT_NONE) break;        // uniform
-        }
-        if (best == OPT_NONE) {
-            evals += (long long)f * (f + 1) / 2;
-            st = 0;
-            break;
-        }
-        const int ri = (int)(best >> 8), rj = (int)(best & 255u), bi = fr[ri], bj = fr[rj];
-        evals += (long long)ri * f - (long long)ri * (ri - 1) / 2 + (rj - ri) + 1;
-        ++done;
-        if (tid < 2 * NW) {
-            unsigned *m = tid < NW ? bp_l : bpt_l;
-            const int w = tid & (NW - 1);
-            const unsigned x = m[bi * P + w];
-            m[bi * P + w] = m[bj * P + w];
-            m[bj * P + w] = x;
-        }
-        if (tid == QAP_THREADS - 1) {
-            const int x = pl[bi];
-            pl[bi] = pl[bj];
-            pl[bj] = x;
-        }
-        __syncthreads();
-        const int wi = bi >> 5, si = bi & 31, wj = bj >> 5, sj = bj & 31;
-        for (int r = tid; r < n; r += QAP_THREADS) {
-            unsigned *rows[2] = {bp_l + r * P, bpt_l + r * P};
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const unsigned d = ((rows[q][wi] >> si) ^ (rows[q][wj] >> sj)) & 1u;
-                rows[q][wi] ^= d << si;
-                rows[q][wj] ^= d << sj;
-            }
-            int rs = 0, cs = 0;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                rs += __popc(a_l[r * P + w] & bp_l[r * P + w]);
-                cs += __popc(at_l[r * P + w] & bpt_l[r * P + w]);
-            }
-            row_s[r] = rs;
-            col_s[r] = cs;
-        }
-    }
-    __syncthreads();
-
-    for (int k = tid; k < N; k += QAP_THREADS) po[k] = k < n ? pl[k] : -1;
-    int s = 0;
-    for (int r = tid; r < n; r += QAP_THREADS) s += row_s[r];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((tid & 63) == 0) sum_s[tid >> 6] = s;
-    __syncthreads();
-    if (tid == 0) {
-        int total = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) total += sum_s[w];
-        qap[b] = total;
-        swaps[b] = done;
-        nit[b] = evals;
-        status[b] = st;
-    }
-}
-
-template <int NW>
-int launch_2opt_seeded(const unsigned *bits1, const unsigned *bits2, const int *assign, const int *seeds, const int *nvalid, int B, int N,
-                       int max_swaps, int *perm, int *qap, int *swaps, long long *nit, int *status, hipStream_t st) {
-    hipLaunchKernelGGL((qap_2opt_seeded_kernel<NW>), dim3(B), dim3(QAP_THREADS), 0, st, bits1, bits2, assign, seeds, nvalid, N, max_swaps,
-                       perm, qap, swaps, nit, status);
-    FGNN_LAUNCH_CHECK();
-    return 0;
+// both entry points: `who` names the one in the messages; seeds (may be NULL: the unseeded search) picks the instantiation
+int two_opt(const char *who, const unsigned *bits1, const unsigned *bits2, const int *assign, const int *seeds, const int *nvalid, int B,
+            int N, int max_swaps, int *perm, int *qap, int *swaps, long long *nit, int *status, void *stream) {
+    FGNN_CHECK(bits1 && bits2 && assign && perm && qap && swaps && nit && status && B > 0 && N > 0, "%s: bad arguments", who);
+    FGNN_CHECK(N <= FGNN_QAP_MAX_N, "%s: at most %d vertices per graph (got %d)", who, FGNN_QAP_MAX_N, N);
+    hipStream_t st = (hipStream_t)stream;
+    const auto launch = [&](auto nw) {
+        constexpr int NW = decltype(nw)::value;
+        return seeds ? launch_2opt<NW, true>(bits1, bits2, assign, seeds, nvalid, B, N, max_swaps, perm, qap, swaps, nit, status, st)
+                     : launch_2opt<NW, false>(bits1, bits2, assign, seeds, nvalid, B, N, max_swaps, perm, qap, swaps, nit, status, st);
+    };
+    if (N <= 32) return launch(std::integral_constant<int, 1>());
+    if (N <= 64) return launch(std::integral_constant<int, 2>());
+    if (N <= 128) return launch(std::integral_constant<int, 4>());
+    return launch(std::integral_constant<int, 8>());
 }
 
 }  // namespace
@@ -413,23 +249,11 @@ int launch_2opt_seeded(const unsigned *bits1, const unsigned *bits2, const int *
 extern "C" int fgnn_qap_2opt_seeded(const unsigned *bits1, const unsigned *bits2, const int *assign, const int *seeds, const int *nvalid,
                                     int B, int N, int max_swaps, int *perm, int *qap, int *swaps, long long *nit, int *status,
                                     void *stream) {
-    FGNN_CHECK(bits1 && bits2 && assign && seeds && perm && qap && swaps && nit && status && B > 0 && N > 0,
-               "fgnn_qap_2opt_seeded: bad arguments");
-    FGNN_CHECK(N <= FGNN_QAP_MAX_N, "fgnn_qap_2opt_seeded: at most %d vertices per graph (got %d)", FGNN_QAP_MAX_N, N);
-    hipStream_t st = (hipStream_t)stream;
-    if (N <= 32) return launch_2opt_seeded<1>(bits1, bits2, assign, seeds, nvalid, B, N, max_swaps, perm, qap, swaps, nit, status, st);
-    if (N <= 64) return launch_2opt_seeded<2>(bits1, bits2, assign, seeds, nvalid, B, N, max_swaps, perm, qap, swaps, nit, status, st);
-    if (N <= 128) return launch_2opt_seeded<4>(bits1, bits2, assign, seeds, nvalid, B, N, max_swaps, perm, qap, swaps, nit, status, st);
-    return launch_2opt_seeded<8>(bits1, bits2, assign, seeds, nvalid, B, N, max_swaps, perm, qap, swaps, nit, status, st);
+    FGNN_CHECK(seeds, "fgnn_qap_2opt_seeded: bad arguments");
+    return two_opt("fgnn_qap_2opt_seeded", bits1, bits2, assign, seeds, nvalid, B, N, max_swaps, perm, qap, swaps, nit, status, stream);
 }
 
 extern "C" int fgnn_qap_2opt(const unsigned *bits1, const unsigned *bits2, const int *assign, const int *nvalid, int B, int N, int max_swaps,
                              int *perm, int *qap, int *swaps, long long *nit, int *status, void *stream) {
-    FGNN_CHECK(bits1 && bits2 && assign && perm && qap && swaps && nit && status && B > 0 && N > 0, "fgnn_qap_2opt: bad arguments");
-    FGNN_CHECK(N <= FGNN_QAP_MAX_N, "fgnn_qap_2opt: at most %d vertices per graph (got %d)", FGNN_QAP_MAX_N, N);
-    hipStream_t st = (hipStream_t)stream;
-    if (N <= 32) return launch_2opt<1>(bits1, bits2, assign, nvalid, B, N, max_swaps, perm, qap, swaps, nit, status, st);
-    if (N <= 64) return launch_2opt<2>(bits1, bits2, assign, nvalid, B, N, max_swaps, perm, qap, swaps, nit, status, st);
-    if (N <= 128) return launch_2opt<4>(bits1, bits2, assign, nvalid, B, N, max_swaps, perm, qap, swaps, nit, status, st);
-    return launch_2opt<8>(bits1, bits2, assign, nvalid, B, N, max_swaps, perm, qap, swaps, nit, status, st);
+    return two_opt("fgnn_qap_2opt", bits1, bits2, assign, nullptr, nvalid, B, N, max_swaps, perm, qap, swaps, nit, status, stream);
 }

@@ -21,11 +21,10 @@
 //
 // N <= 128: A and Bp live in LDS with an odd pitch (lanes read rows j at lane-dependent offsets), three sizes (32, 64, 128 rows) so
 // that small pairs share a CU.  128 < N <= 256: Bp lives in the caller's workspace (N x N floats per pair), A is read in place.
-#include "fgnn_rows.h"
+#include "fgnn_qap_search.h"
 
 namespace {
 
-constexpr unsigned OPTW_NONE = 0xffffffffu;    // no improving pair (a real key is (i << 8) | j < 2^16)
 constexpr int OPTW_LDS_MAX_N = 128;            // beyond: Bp in the workspace
 constexpr long long OPTW_WS_ALIGN = 256;
 constexpr int OPTW_MAX_B = 65535;              // pairs ride on a grid dimension
@@ -60,27 +59,10 @@ __global__ __launch_bounds__(T) void qapw_2opt_kernel(const float *a1, const flo
     int *po = perm + (long long)b * N;
 
     // pl = assign on the corner (-1 past it), refused unless it is a permutation of [0, n)
-    for (int m = tid; m < R; m += T) {
-        pl[m] = -1;
-        cnt[m] = 0;
-    }
-    if (tid == 0) bad_s = 0;
-    __syncthreads();
-    for (int k = tid; k < n; k += T) {
-        const int p = pi[k];
-        if (p >= 0 && p < n) {
-            pl[k] = p;
-            atomicAdd(&cnt[p], 1);
-        } else {
-            bad_s = 1;
-        }
-    }
-    __syncthreads();
-    for (int m = tid; m < n; m += T)
-        if (cnt[m] != 1) bad_s = 1;
+    load_start<T>(pl, cnt, &bad_s, pi, n, R, tid);
     __syncthreads();
     if (bad_s) {                                // uniform
-        for (int k = tid; k < N; k += T) po[k] = k < n ? pi[k] : -1;
+        refuse_start<T>(po, pi, n, N, tid);
         if (tid == 0) {
             swaps[b] = 0;
             nit[b] = 0;
@@ -114,10 +96,10 @@ __global__ __launch_bounds__(T) void qapw_2opt_kernel(const float *a1, const flo
     long long evals = 0;
     for (int round = 0; round < bound; ++round) {
         __syncthreads();                        // Bp of this round
-        unsigned best = OPTW_NONE;
+        unsigned best = SEARCH_NONE;
         int i = 0, j = 1 + tid;                 // pair number tid of the scan without its (i,i)
         for (int base = 0; base < pairs; base += T) {       // uniform: T pairs in scan order between two meetings
-            unsigned key = OPTW_NONE;
+            unsigned key = SEARCH_NONE;
             while (j >= n && i < n - 1) {       // past the end of row i: on into the next row
                 ++i;
                 j += i + 1 - n;
@@ -126,22 +108,17 @@ __global__ __launch_bounds__(T) void qapw_2opt_kernel(const float *a1, const flo
                 if (exchange_gain(a, pa, bp, pb, n, i, j) > 0.f) key = (unsigned)((i << 8) | j);
                 j += T;
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) key = min(key, (unsigned)__shfl_xor((int)key, o));
-            if ((tid & 63) == 0) red[par][tid >> 6] = key;
-            __syncthreads();
-#pragma unroll
-            for (int w = 0; w < WAVES; ++w) best = min(best, red[par][w]);
+            best = first_key<WAVES>(key, best, red[par], tid);
             par ^= 1;                           // (the next meeting writes the other half: no second barrier)
-            if (best != OPTW_NONE) break;       // uniform
+            if (best != SEARCH_NONE) break;     // uniform
         }
-        if (best == OPTW_NONE) {                // a whole scan without an improving pair
-            evals += (long long)n * (n + 1) / 2;
+        if (best == SEARCH_NONE) {              // a whole scan without an improving pair
+            evals += full_scan(n);
             st = 0;
             break;
         }
         const int bi = (int)(best >> 8), bj = (int)(best & 255u);
-        evals += (long long)bi * n - (long long)bi * (bi - 1) / 2 + (bj - bi) + 1;
+        evals += scan_position(bi, bj, n);
         ++done;
         // rows bi, bj of Bp change places, then columns bi, bj
         for (int k = tid; k < n; k += T) {

@@ -12,6 +12,11 @@
 // and the matching is the assignment that maximises the last P.  Matrices: fp32, row pitch ld, pairs gstride floats apart; only
 // the corner is ever READ (it may be surrounded by NaN), in a1, a2 and p0 alike.  Every reduction has a fixed order (no float
 // atomics): results are bit-identical from run to run, and a pair's bits do not depend on the batch it sits in.
+//
+// Seeds (fgnn_qapw_faq_seeded, further down) are the same chain on the free block: one faq_chain() issues the launches of both
+// entry points on one workspace layout (FaqWs), and the two kernels that know the seeds' constant term C, faq_grad_kernel and
+// faq_step_kernel, are templates on SEEDED -- one body each, the reads of C and the sums over it under `if constexpr`, so the
+// unseeded instantiations do exactly the work written above.
 #include "fgnn_rows.h"
 
 namespace {
@@ -87,8 +92,10 @@ __global__ __launch_bounds__(FQ_THREADS) void faq_pb_kernel(const float *a2, lon
 
 // cost[b] = -G = -([A | A^T] [T0; T1]) on the corner, in the layout the solver reads (row pitch N, pairs N N apart): one fmaf chain
 // per entry, the n terms of A T0 (k ascending) and then the n terms of A^T T1.  grid (ceil(N / 32), ceil(N / 128), B).
-__global__ __launch_bounds__(FQ_THREADS) void faq_grad_kernel(const float *a1, long long gstride, int ld, const float *T, const int *nvc,
-                                                              const int *done, int N, float *cost) {
+// SEEDED: cost = -(chain + C), the seeds' constant term added once, in the epilogue, to the finished chain; else C is not read.
+template <bool SEEDED>
+__global__ __launch_bounds__(FQ_THREADS) void faq_grad_kernel(const float *a1, long long gstride, int ld, const float *T, const float *C,
+                                                              const int *nvc, const int *done, int N, float *cost) {
     __shared__ float a_l[FQ_ROWS * FQ_PA];
     __shared__ float b_l[FQ_KC * FQ_PB];
     const int b = blockIdx.z, i0 = blockIdx.x * FQ_ROWS, c0 = blockIdx.y * FQ_COLS, tid = threadIdx.x;
@@ -109,7 +116,9 @@ __global__ __launch_bounds__(FQ_THREADS) void faq_grad_kernel(const float *a1, l
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int gi = i0 + ch_of(r, h);
-        if (gi < n) out[(long long)gi * N] = -acc[r];
+        if (gi >= n) continue;
+        if constexpr (SEEDED) out[(long long)gi * N] = -(acc[r] + C[(long long)b * N * N + gj + (long long)gi * N]);
+        else out[(long long)gi * N] = -acc[r];
     }
 }
 
@@ -166,9 +175,14 @@ __global__ __launch_bounds__(FQ_THREADS) void faq_init_kernel(const float *p0, c
 
 // One workgroup per pair: the line search, the update and the stop test of one round.  cost holds -G, q the solver's assignment.
 // Thread t takes the corner's elements t, t + 256, ... (row-major) in both passes; the sums are fp64, folded in a fixed order.
+// SEEDED: the linear term.  f(P) = q(P) + <C, P> with q(P) = tr(A22^T P B22 P^T), whose gradient is G - C, so <G - C, P> = 2 q(P),
+// and with R = P - Q: f(Q + x R) = f(Q) + b x + a x^2,
+//     a = (<G,P> - <C,P>) / 2 - (<G,Q> - <C,Q>) + q(Q),   b = (<G,Q> - <C,Q>) - 2 q(Q) + <C,P> - <C,Q>
+// (SciPy's a and b21 + b12 + b22a + b22b): two more sums.  Without seeds C is not read and the three sums are all there is.
+template <bool SEEDED>
 __global__ __launch_bounds__(FQ_THREADS) void faq_step_kernel(const float *a1, const float *a2, long long gstride, int ld,
-                                                              const float *cost, const int *q, const int *nvc, int N, float tol, float *P,
-                                                              int *nvw, int *done, int *nit, int *status) {
+                                                              const float *cost, const float *C, const int *q, const int *nvc, int N,
+                                                              float tol, float *P, int *nvw, int *done, int *nit, int *status) {
     __shared__ int q_l[FGNN_QAPW_MAX_N];
     __shared__ double red[FQ_THREADS / 64];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -190,20 +204,30 @@ __global__ __launch_bounds__(FQ_THREADS) void faq_step_kernel(const float *a1, c
         }
         return;
     }
-    const float *A = a1 + (long long)b * gstride, *Bm = a2 + (long long)b * gstride, *Cb = cost + (long long)b * N * N;
+    const float *A = a1 + (long long)b * gstride, *Bm = a2 + (long long)b * gstride, *Gb = cost + (long long)b * N * N;
     float *Pb = P + (long long)b * N * N;
-    double gp = 0.0, gq = 0.0, fq = 0.0;        // <G, P>, <G, Q>, f(Q)
+    double gp = 0.0, gq = 0.0, fq = 0.0, cp = 0.0, cq = 0.0;       // <G, P>, <G, Q>, f(Q) (seeded: q(Q)); seeded: <C, P>, <C, Q>
     for (int idx = tid; idx < n * n; idx += FQ_THREADS) {
         const int i = idx / n, k = idx - i * n, qi = q_l[i];
-        const double g = -(double)Cb[(long long)i * N + k];
-        gp += g * (double)Pb[(long long)i * N + k];
+        const double g = -(double)Gb[(long long)i * N + k], p = (double)Pb[(long long)i * N + k];
+        gp += g * p;
         if (k == qi) gq += g;
+        if constexpr (SEEDED) {
+            const double cc = (double)C[(long long)b * N * N + (long long)i * N + k];
+            cp += cc * p;
+            if (k == qi) cq += cc;
+        }
         fq += (double)A[(long long)i * ld + k] * (double)Bm[(long long)qi * ld + q_l[k]];
     }
     gp = block_sum(gp, red, tid);
     gq = block_sum(gq, red, tid);
     fq = block_sum(fq, red, tid);
-    const double a = 0.5 * gp - gq + fq, bb = gq - 2.0 * fq;
+    double a = 0.5 * gp - gq + fq, bb = gq - 2.0 * fq;
+    if constexpr (SEEDED) {
+        cp = block_sum(cp, red, tid);
+        cq = block_sum(cq, red, tid);
+        a = 0.5 * (gp - cp) - (gq - cq) + fq, bb = (gq - cq) - 2.0 * fq + cp - cq;
+    }
     double alpha;
     if (a < 0.0 && 0.0 <= -bb / (2.0 * a) && -bb / (2.0 * a) <= 1.0) alpha = -bb / (2.0 * a);
     else alpha = -(a + bb) < 0.0 ? 1.0 : 0.0;
@@ -269,8 +293,8 @@ long long ws_round(long long x) { return (x + WS_ALIGN - 1) / WS_ALIGN * WS_ALIG
 
 // ---- seeds (fgnn_qapw_faq_seeded): the chain above on the free block A22, B22 with n_b := u_b, the seeds' constant term C in the
 // gradient, G = C + A22 P B22^T + A22^T P B22, and its linear term in the line search.  The kernels above run as they are wherever
-// the seeds change nothing (the start, the first product, -P, the outputs of the free block); the three below are the seeded
-// forms of the second product and of the step, and the way in and out of free coordinates.
+// the seeds change nothing (the start, the first product, -P, the outputs of the free block); the second product and the step run
+// in their SEEDED instantiation; the two kernels below are the way in and out of free coordinates.
 
 // One workgroup per pair: what the start needs in free coordinates.  ok = the seeds are valid and assign0 (if given) holds them on
 // every seeded row; ueff = u_b for such a pair, else 0 (the chain above then freezes it); assign_s[r] = the rank among the free
@@ -305,108 +329,6 @@ __global__ __launch_bounds__(FQ_THREADS) void faq_seed_start_kernel(const int *s
     if (tid == 0) {
         ok[b] = good && !bad;
         ueff[b] = good && !bad ? u : 0;
-    }
-}
-
-// faq_grad_kernel with the constant term: cost = -(chain + C), C added once, in the epilogue, to the finished fmaf chain.
-__global__ __launch_bounds__(FQ_THREADS) void faq_grad_seeded_kernel(const float *a1, long long gstride, int ld, const float *T,
-                                                                     const float *C, const int *nvc, const int *done, int N, float *cost) {
-    __shared__ float a_l[FQ_ROWS * FQ_PA];
-    __shared__ float b_l[FQ_KC * FQ_PB];
-    const int b = blockIdx.z, i0 = blockIdx.x * FQ_ROWS, c0 = blockIdx.y * FQ_COLS, tid = threadIdx.x;
-    if (done[b]) return;                        // uniform
-    const int n = nvc[b];
-    if (i0 >= n || c0 >= n) return;             // uniform
-    const float *A = a1 + (long long)b * gstride, *T0 = T + (long long)b * 2 * N * N, *T1 = T0 + (long long)N * N;
-    const int wv = tid >> 6, lane = tid & 63, h = lane >> 5, c = lane & 31;
-    const bool live = c0 + 32 * wv < n;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    tile_product<false, false>(acc, a_l, b_l, A, ld, T0, N, n, i0, c0, tid, live);
-    tile_product<true, false>(acc, a_l, b_l, A, ld, T1, N, n, i0, c0, tid, live);
-    const int gj = c0 + 32 * wv + c;
-    if (!live || gj >= n) return;
-    float *out = cost + (long long)b * N * N + gj;
-    const float *Cb = C + (long long)b * N * N + gj;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int gi = i0 + ch_of(r, h);
-        if (gi < n) out[(long long)gi * N] = -(acc[r] + Cb[(long long)gi * N]);
-    }
-}
-
-// faq_step_kernel with the linear term.  f(P) = q(P) + <C, P> with q(P) = tr(A22^T P B22 P^T), whose gradient is G - C, so
-// <G - C, P> = 2 q(P), and with R = P - Q: f(Q + x R) = f(Q) + b x + a x^2,
-//     a = (<G,P> - <C,P>) / 2 - (<G,Q> - <C,Q>) + q(Q),   b = (<G,Q> - <C,Q>) - 2 q(Q) + <C,P> - <C,Q>
-// (SciPy's a and b21 + b12 + b22a + b22b).  With C = 0 every sum and both coefficients have the bits of faq_step_kernel's.
-__global__ __launch_bounds__(FQ_THREADS) void faq_step_seeded_kernel(const float *a1, const float *a2, long long gstride, int ld,
-                                                                     const float *cost, const float *C, const int *q, const int *nvc,
-                                                                     int N, float tol, float *P, int *nvw, int *done, int *nit,
-                                                                     int *status) {
-    __shared__ int q_l[FGNN_QAPW_MAX_N];
-    __shared__ double red[FQ_THREADS / 64];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    if (done[b]) return;                        // uniform
-    const int n = nvc[b];
-    int bad = 0;
-    for (int k = tid; k < n; k += FQ_THREADS) {
-        const int p = q[(long long)b * N + k];
-        const bool ok = p >= 0 && p < n;
-        q_l[k] = ok ? p : 0;
-        bad |= !ok;
-    }
-    if (__syncthreads_or(bad)) {
-        if (tid == 0) {
-            done[b] = 1;
-            nvw[b] = 0;
-            nit[b] = 0;
-            status[b] = 2;
-        }
-        return;
-    }
-    const float *A = a1 + (long long)b * gstride, *Bm = a2 + (long long)b * gstride, *Gb = cost + (long long)b * N * N;
-    const float *Cb = C + (long long)b * N * N;
-    float *Pb = P + (long long)b * N * N;
-    double gp = 0.0, gq = 0.0, fq = 0.0, cp = 0.0, cq = 0.0;       // <G, P>, <G, Q>, q(Q), <C, P>, <C, Q>
-    for (int idx = tid; idx < n * n; idx += FQ_THREADS) {
-        const int i = idx / n, k = idx - i * n, qi = q_l[i];
-        const double g = -(double)Gb[(long long)i * N + k], cc = (double)Cb[(long long)i * N + k];
-        const double p = (double)Pb[(long long)i * N + k];
-        gp += g * p;
-        cp += cc * p;
-        if (k == qi) {
-            gq += g;
-            cq += cc;
-        }
-        fq += (double)A[(long long)i * ld + k] * (double)Bm[(long long)qi * ld + q_l[k]];
-    }
-    gp = block_sum(gp, red, tid);
-    gq = block_sum(gq, red, tid);
-    fq = block_sum(fq, red, tid);
-    cp = block_sum(cp, red, tid);
-    cq = block_sum(cq, red, tid);
-    const double a = 0.5 * (gp - cp) - (gq - cq) + fq, bb = (gq - cq) - 2.0 * fq + cp - cq;
-    double alpha;
-    if (a < 0.0 && 0.0 <= -bb / (2.0 * a) && -bb / (2.0 * a) <= 1.0) alpha = -bb / (2.0 * a);
-    else alpha = -(a + bb) < 0.0 ? 1.0 : 0.0;
-    double ss = 0.0;
-    for (int idx = tid; idx < n * n; idx += FQ_THREADS) {
-        const int i = idx / n, k = idx - i * n;
-        const double p = (double)Pb[(long long)i * N + k];
-        const float p1 = (float)(alpha * p + (1.0 - alpha) * (k == q_l[i] ? 1.0 : 0.0));
-        const double d = p - (double)p1;
-        ss += d * d;
-        Pb[(long long)i * N + k] = p1;
-    }
-    ss = block_sum(ss, red, tid);
-    if (tid == 0) {
-        nit[b] += 1;
-        if (sqrt(ss) / sqrt((double)n) < (double)tol) {
-            done[b] = 1;
-            nvw[b] = 0;
-            status[b] = 0;
-        }
     }
 }
 
@@ -456,130 +378,124 @@ __global__ __launch_bounds__(FQ_THREADS) void faq_seed_finish_kernel(const int *
     }
 }
 
-}  // namespace
+// The workspace of a call: the chain's own part, then what only the seeded entry point uses (null without seeds).
+struct FaqWs {
+    float *P, *T, *cost;                        // the iterate, the two products, -G (then -P)
+    int *q, *nvc, *nvw, *done, *correct;
+    float *A22, *B22, *C, *P0;                  // the free blocks, the constant term, the gathered p0
+    int *free_a, *free_b, *seed_a, *seed_b, *assign_s, *perm_s;
+    int *nfree, *nseed, *valid, *ok, *ueff;
+    long long bytes;
+};
 
-extern "C" long long fgnn_qapw_faq_ws_bytes(int B, int N) {
-    if (B <= 0 || N <= 0) return 0;
-    // P, T (two products), cost; q; nvc, nvw, done, correct
-    return 4 * ws_round((long long)B * N * N * 4) + ws_round((long long)B * N * 4) + 4 * ws_round((long long)B * 4);
+// (ws may be NULL: only `bytes` is then of use)
+FaqWs faq_carve(void *ws, int B, int N, bool seeded) {
+    const long long mat = ws_round((long long)B * N * N * 4), lst = ws_round((long long)B * N * 4), vec = ws_round((long long)B * 4);
+    uintptr_t p = (uintptr_t)ws;
+    const auto take = [&p](long long bytes) {
+        const uintptr_t at = p;
+        p += bytes;
+        return at;
+    };
+    FaqWs w = {};
+    w.P = (float *)take(mat), w.T = (float *)take(2 * mat), w.cost = (float *)take(mat);
+    w.q = (int *)take(lst);
+    w.nvc = (int *)take(vec), w.nvw = (int *)take(vec), w.done = (int *)take(vec), w.correct = (int *)take(vec);
+    if (seeded) {
+        w.A22 = (float *)take(mat), w.B22 = (float *)take(mat), w.C = (float *)take(mat), w.P0 = (float *)take(mat);
+        w.free_a = (int *)take(lst), w.free_b = (int *)take(lst), w.seed_a = (int *)take(lst), w.seed_b = (int *)take(lst);
+        w.assign_s = (int *)take(lst), w.perm_s = (int *)take(lst);
+        w.nfree = (int *)take(vec), w.nseed = (int *)take(vec), w.valid = (int *)take(vec), w.ok = (int *)take(vec), w.ueff = (int *)take(vec);
+    }
+    w.bytes = (long long)(p - (uintptr_t)ws);
+    return w;
 }
 
-extern "C" int fgnn_qapw_faq(const float *a1, const float *a2, long long gstride, int ld, const float *p0, const int *assign0,
-                             const int *nvalid, int B, int N, int maxiter, float tol, void *ws, long long ws_bytes, int *perm, int *nit,
-                             int *status, float *p_out, void *stream) {
-    FGNN_CHECK(a1 && a2 && ws && perm && nit && status && B > 0 && N > 0, "fgnn_qapw_faq: bad arguments");
-    FGNN_CHECK(!(p0 && assign0), "fgnn_qapw_faq: at most one of p0 and assign0");
-    FGNN_CHECK(maxiter > 0 && tol > 0.f, "fgnn_qapw_faq: maxiter and tol must be positive (got %d, %g)", maxiter, (double)tol);
-    FGNN_CHECK(N <= FGNN_QAPW_MAX_N, "fgnn_qapw_faq: at most %d vertices per graph (got %d)", FGNN_QAPW_MAX_N, N);
-    FGNN_CHECK(B <= FQ_MAX_B, "fgnn_qapw_faq: at most %d pairs per call (got %d)", FQ_MAX_B, B);
-    FGNN_CHECK(ld >= N && gstride >= (long long)N * ld, "fgnn_qapw_faq: ld / gstride smaller than the matrices");
-    FGNN_CHECK(ws_bytes >= fgnn_qapw_faq_ws_bytes(B, N) && ((uintptr_t)ws & 15) == 0,
-               "fgnn_qapw_faq: the workspace needs %lld bytes, 16-byte aligned (got %lld)", fgnn_qapw_faq_ws_bytes(B, N), ws_bytes);
+// what both entry points check; `who` names the entry point in the messages
+int faq_check(const char *who, bool pointers, const float *p0, const int *assign0, long long gstride, int ld, int B, int N, int maxiter,
+              float tol, const void *ws, long long ws_bytes, long long need) {
+    FGNN_CHECK(pointers && B > 0 && N > 0, "%s: bad arguments", who);
+    FGNN_CHECK(!(p0 && assign0), "%s: at most one of p0 and assign0", who);
+    FGNN_CHECK(maxiter > 0 && tol > 0.f, "%s: maxiter and tol must be positive (got %d, %g)", who, maxiter, (double)tol);
+    FGNN_CHECK(N <= FGNN_QAPW_MAX_N, "%s: at most %d vertices per graph (got %d)", who, FGNN_QAPW_MAX_N, N);
+    FGNN_CHECK(B <= FQ_MAX_B, "%s: at most %d pairs per call (got %d)", who, FQ_MAX_B, B);
+    FGNN_CHECK(ld >= N && gstride >= (long long)N * ld, "%s: ld / gstride smaller than the matrices", who);
+    FGNN_CHECK(ws_bytes >= need && ((uintptr_t)ws & 15) == 0, "%s: the workspace needs %lld bytes, 16-byte aligned (got %lld)", who, need,
+               ws_bytes);
+    return 0;
+}
+
+// The chain on the corners nvalid names: init, maxiter x (the two products, the assignment, the step), -P, the last assignment,
+// the outputs.  C (may be NULL: no seeds) is the constant term of the gradient and picks the instantiations of the two kernels
+// that know it.
+int faq_chain(const float *a1, const float *a2, long long gstride, int ld, const float *C, const float *p0, const int *assign0,
+              const int *nvalid, int B, int N, int maxiter, float tol, const FaqWs &w, int *perm, int *nit, int *status, float *p_out,
+              void *stream) {
     hipStream_t st = (hipStream_t)stream;
-    const long long mat = ws_round((long long)B * N * N * 4), vec = ws_round((long long)B * 4);
-    char *p = (char *)ws;
-    float *P = (float *)p;
-    p += mat;
-    float *T = (float *)p;
-    p += 2 * mat;
-    float *cost = (float *)p;
-    p += mat;
-    int *q = (int *)p;
-    p += ws_round((long long)B * N * 4);
-    int *nvc = (int *)p, *nvw = (int *)(p + vec), *done = (int *)(p + 2 * vec), *correct = (int *)(p + 3 * vec);
     const long long bs = (long long)N * N;
     const dim3 tiles((N + FQ_ROWS - 1) / FQ_ROWS, (N + FQ_COLS - 1) / FQ_COLS, B);
     int rc;
-    hipLaunchKernelGGL(faq_init_kernel, dim3(B), dim3(FQ_THREADS), 0, st, p0, assign0, nvalid, N, P, nvc, nvw, done, nit, status);
+    hipLaunchKernelGGL(faq_init_kernel, dim3(B), dim3(FQ_THREADS), 0, st, p0, assign0, nvalid, N, w.P, w.nvc, w.nvw, w.done, nit, status);
     FGNN_LAUNCH_CHECK();
     for (int it = 0; it < maxiter; ++it) {
-        hipLaunchKernelGGL(faq_pb_kernel, dim3(tiles.x, 2 * tiles.y, B), dim3(FQ_THREADS), 0, st, a2, gstride, ld, P, nvc, done, N, T);
+        hipLaunchKernelGGL(faq_pb_kernel, dim3(tiles.x, 2 * tiles.y, B), dim3(FQ_THREADS), 0, st, a2, gstride, ld, w.P, w.nvc, w.done, N, w.T);
         FGNN_LAUNCH_CHECK();
-        hipLaunchKernelGGL(faq_grad_kernel, tiles, dim3(FQ_THREADS), 0, st, a1, gstride, ld, T, nvc, done, N, cost);
+        hipLaunchKernelGGL(C ? faq_grad_kernel<true> : faq_grad_kernel<false>, tiles, dim3(FQ_THREADS), 0, st, a1, gstride, ld, w.T, C, w.nvc,
+                           w.done, N, w.cost);
         FGNN_LAUNCH_CHECK();
-        if ((rc = fgnn_lsap_accuracy(cost, bs, N, nvw, B, N, correct, q, stream))) return rc;      // a frozen pair: n = 0, no work
-        hipLaunchKernelGGL(faq_step_kernel, dim3(B), dim3(FQ_THREADS), 0, st, a1, a2, gstride, ld, cost, q, nvc, N, tol, P, nvw, done, nit,
-                           status);
+        if ((rc = fgnn_lsap_accuracy(w.cost, bs, N, w.nvw, B, N, w.correct, w.q, stream))) return rc;      // a frozen pair: n = 0, no work
+        hipLaunchKernelGGL(C ? faq_step_kernel<true> : faq_step_kernel<false>, dim3(B), dim3(FQ_THREADS), 0, st, a1, a2, gstride, ld, w.cost, C,
+                           w.q, w.nvc, N, tol, w.P, w.nvw, w.done, nit, status);
         FGNN_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(faq_neg_p_kernel, dim3(N, B), dim3(64), 0, st, P, nvc, N, cost);
+    hipLaunchKernelGGL(faq_neg_p_kernel, dim3(N, B), dim3(64), 0, st, w.P, w.nvc, N, w.cost);
     FGNN_LAUNCH_CHECK();
-    if ((rc = fgnn_lsap_accuracy(cost, bs, N, nvc, B, N, correct, perm, stream))) return rc;
-    hipLaunchKernelGGL(faq_finish_kernel, dim3(B), dim3(FQ_THREADS), 0, st, P, assign0, nvc, N, perm, nit, status, p_out);
+    if ((rc = fgnn_lsap_accuracy(w.cost, bs, N, w.nvc, B, N, w.correct, perm, stream))) return rc;
+    hipLaunchKernelGGL(faq_finish_kernel, dim3(B), dim3(FQ_THREADS), 0, st, w.P, assign0, w.nvc, N, perm, nit, status, p_out);
     FGNN_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" long long fgnn_qapw_faq_seeded_ws_bytes(int B, int N) {
-    if (B <= 0 || N <= 0) return 0;
-    // the chain's own workspace; A22, B22, C, the gathered p0; free_a, free_b, seed_a, seed_b, assign_s, perm_s; nfree, nseed, valid, ok, ueff
-    return fgnn_qapw_faq_ws_bytes(B, N) + 4 * ws_round((long long)B * N * N * 4) + 6 * ws_round((long long)B * N * 4) +
-           5 * ws_round((long long)B * 4);
+}  // namespace
+
+extern "C" long long fgnn_qapw_faq_ws_bytes(int B, int N) { return B <= 0 || N <= 0 ? 0 : faq_carve(nullptr, B, N, false).bytes; }
+
+extern "C" int fgnn_qapw_faq(const float *a1, const float *a2, long long gstride, int ld, const float *p0, const int *assign0,
+                             const int *nvalid, int B, int N, int maxiter, float tol, void *ws, long long ws_bytes, int *perm, int *nit,
+                             int *status, float *p_out, void *stream) {
+    if (int rc = faq_check("fgnn_qapw_faq", a1 && a2 && ws && perm && nit && status, p0, assign0, gstride, ld, B, N, maxiter, tol, ws,
+                           ws_bytes, fgnn_qapw_faq_ws_bytes(B, N)))
+        return rc;
+    return faq_chain(a1, a2, gstride, ld, nullptr, p0, assign0, nvalid, B, N, maxiter, tol, faq_carve(ws, B, N, false), perm, nit, status,
+                     p_out, stream);
 }
+
+extern "C" long long fgnn_qapw_faq_seeded_ws_bytes(int B, int N) { return B <= 0 || N <= 0 ? 0 : faq_carve(nullptr, B, N, true).bytes; }
 
 extern "C" int fgnn_qapw_faq_seeded(const float *a1, const float *a2, long long gstride, int ld, const int *seeds, const float *p0,
                                     int p0_free, const int *assign0, const int *nvalid, int B, int N, int maxiter, float tol, void *ws,
                                     long long ws_bytes, int *perm, int *nit, int *status, int *seeded, float *p_out, void *stream) {
-    FGNN_CHECK(a1 && a2 && seeds && ws && perm && nit && status && B > 0 && N > 0, "fgnn_qapw_faq_seeded: bad arguments");
-    FGNN_CHECK(!(p0 && assign0), "fgnn_qapw_faq_seeded: at most one of p0 and assign0");
-    FGNN_CHECK(maxiter > 0 && tol > 0.f, "fgnn_qapw_faq_seeded: maxiter and tol must be positive (got %d, %g)", maxiter, (double)tol);
-    FGNN_CHECK(N <= FGNN_QAPW_MAX_N, "fgnn_qapw_faq_seeded: at most %d vertices per graph (got %d)", FGNN_QAPW_MAX_N, N);
-    FGNN_CHECK(B <= FQ_MAX_B, "fgnn_qapw_faq_seeded: at most %d pairs per call (got %d)", FQ_MAX_B, B);
-    FGNN_CHECK(ld >= N && gstride >= (long long)N * ld, "fgnn_qapw_faq_seeded: ld / gstride smaller than the matrices");
-    FGNN_CHECK(ws_bytes >= fgnn_qapw_faq_seeded_ws_bytes(B, N) && ((uintptr_t)ws & 15) == 0,
-               "fgnn_qapw_faq_seeded: the workspace needs %lld bytes, 16-byte aligned (got %lld)", fgnn_qapw_faq_seeded_ws_bytes(B, N),
-               ws_bytes);
-    hipStream_t st = (hipStream_t)stream;
-    const long long mat = ws_round((long long)B * N * N * 4), vec = ws_round((long long)B * 4), lst = ws_round((long long)B * N * 4);
-    char *p = (char *)ws;
-    float *P = (float *)p;
-    p += mat;
-    float *T = (float *)p;
-    p += 2 * mat;
-    float *cost = (float *)p;
-    p += mat;
-    int *q = (int *)p;
-    p += lst;
-    int *nvc = (int *)p, *nvw = (int *)(p + vec), *done = (int *)(p + 2 * vec), *correct = (int *)(p + 3 * vec);
-    p += 4 * vec;
-    float *A22 = (float *)p, *B22 = (float *)(p + mat), *C = (float *)(p + 2 * mat), *P0 = (float *)(p + 3 * mat);
-    p += 4 * mat;
-    int *free_a = (int *)p, *free_b = (int *)(p + lst), *seed_a = (int *)(p + 2 * lst), *seed_b = (int *)(p + 3 * lst);
-    int *assign_s = (int *)(p + 4 * lst), *perm_s = (int *)(p + 5 * lst);
-    p += 6 * lst;
-    int *nfree = (int *)p, *nseed = (int *)(p + vec), *valid = (int *)(p + 2 * vec), *ok = (int *)(p + 3 * vec), *ueff = (int *)(p + 4 * vec);
-    const long long bs = (long long)N * N;
-    const dim3 tiles((N + FQ_ROWS - 1) / FQ_ROWS, (N + FQ_COLS - 1) / FQ_COLS, B);
     int rc;
-    if ((rc = fgnn_seed_index(seeds, nvalid, B, N, nfree, nseed, free_a, free_b, seed_a, seed_b, valid, stream))) return rc;
-    hipLaunchKernelGGL(faq_seed_start_kernel, dim3(B), dim3(FQ_THREADS), 0, st, seeds, assign0, nvalid, N, free_a, free_b, nfree, valid, ok,
-                       ueff, assign_s);
+    if ((rc = faq_check("fgnn_qapw_faq_seeded", a1 && a2 && seeds && ws && perm && nit && status, p0, assign0, gstride, ld, B, N, maxiter,
+                        tol, ws, ws_bytes, fgnn_qapw_faq_seeded_ws_bytes(B, N))))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const FaqWs w = faq_carve(ws, B, N, true);
+    // into free coordinates: the index lists, the free blocks A22, B22 (and p0's), the constant term
+    if ((rc = fgnn_seed_index(seeds, nvalid, B, N, w.nfree, w.nseed, w.free_a, w.free_b, w.seed_a, w.seed_b, w.valid, stream))) return rc;
+    hipLaunchKernelGGL(faq_seed_start_kernel, dim3(B), dim3(FQ_THREADS), 0, st, seeds, assign0, nvalid, N, w.free_a, w.free_b, w.nfree,
+                       w.valid, w.ok, w.ueff, w.assign_s);
     FGNN_LAUNCH_CHECK();
-    if ((rc = fgnn_seed_gather(a1, gstride, ld, free_a, free_a, ueff, B, N, A22, stream))) return rc;
-    if ((rc = fgnn_seed_gather(a2, gstride, ld, free_b, free_b, ueff, B, N, B22, stream))) return rc;
-    if (p0 && !p0_free && (rc = fgnn_seed_gather(p0, bs, N, free_a, free_b, ueff, B, N, P0, stream))) return rc;
-    if ((rc = fgnn_seed_const(a1, a2, gstride, ld, free_a, free_b, seed_a, seed_b, ueff, nseed, B, N, C, stream))) return rc;
-    hipLaunchKernelGGL(faq_init_kernel, dim3(B), dim3(FQ_THREADS), 0, st, p0 ? (p0_free ? p0 : P0) : nullptr, assign0 ? assign_s : nullptr, ueff, N, P, nvc,
-                       nvw, done, nit, status);
-    FGNN_LAUNCH_CHECK();
-    for (int it = 0; it < maxiter; ++it) {
-        hipLaunchKernelGGL(faq_pb_kernel, dim3(tiles.x, 2 * tiles.y, B), dim3(FQ_THREADS), 0, st, B22, bs, N, P, nvc, done, N, T);
-        FGNN_LAUNCH_CHECK();
-        hipLaunchKernelGGL(faq_grad_seeded_kernel, tiles, dim3(FQ_THREADS), 0, st, A22, bs, N, T, C, nvc, done, N, cost);
-        FGNN_LAUNCH_CHECK();
-        if ((rc = fgnn_lsap_accuracy(cost, bs, N, nvw, B, N, correct, q, stream))) return rc;
-        hipLaunchKernelGGL(faq_step_seeded_kernel, dim3(B), dim3(FQ_THREADS), 0, st, A22, B22, bs, N, cost, C, q, nvc, N, tol, P, nvw, done,
-                           nit, status);
-        FGNN_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(faq_neg_p_kernel, dim3(N, B), dim3(64), 0, st, P, nvc, N, cost);
-    FGNN_LAUNCH_CHECK();
-    if ((rc = fgnn_lsap_accuracy(cost, bs, N, nvc, B, N, correct, perm_s, stream))) return rc;
-    hipLaunchKernelGGL(faq_finish_kernel, dim3(B), dim3(FQ_THREADS), 0, st, P, assign0 ? assign_s : nullptr, nvc, N, perm_s, nit, status,
-                       p_out);
-    FGNN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(faq_seed_finish_kernel, dim3(B), dim3(FQ_THREADS), 0, st, seeds, assign0, nvalid, N, free_a, free_b, nfree, nseed,
-                       valid, ok, perm_s, perm, nit, status, seeded);
+    if ((rc = fgnn_seed_gather(a1, gstride, ld, w.free_a, w.free_a, w.ueff, B, N, w.A22, stream))) return rc;
+    if ((rc = fgnn_seed_gather(a2, gstride, ld, w.free_b, w.free_b, w.ueff, B, N, w.B22, stream))) return rc;
+    if (p0 && !p0_free && (rc = fgnn_seed_gather(p0, (long long)N * N, N, w.free_a, w.free_b, w.ueff, B, N, w.P0, stream))) return rc;
+    if ((rc = fgnn_seed_const(a1, a2, gstride, ld, w.free_a, w.free_b, w.seed_a, w.seed_b, w.ueff, w.nseed, B, N, w.C, stream))) return rc;
+    // the chain on the free block, its matching in free coordinates
+    if ((rc = faq_chain(w.A22, w.B22, (long long)N * N, N, w.C, p0 ? (p0_free ? p0 : w.P0) : nullptr, assign0 ? w.assign_s : nullptr, w.ueff,
+                        B, N, maxiter, tol, w, w.perm_s, nit, status, p_out, stream)))
+        return rc;
+    hipLaunchKernelGGL(faq_seed_finish_kernel, dim3(B), dim3(FQ_THREADS), 0, st, seeds, assign0, nvalid, N, w.free_a, w.free_b, w.nfree,
+                       w.nseed, w.valid, w.ok, w.perm_s, perm, nit, status, seeded);
     FGNN_LAUNCH_CHECK();
     return 0;
 }

@@ -583,7 +583,7 @@ def _faq_launches(b1, b2, s, assign, q, nvalid, B, N, faq, seeds=None):
     if seeds is None:
         out = qap.faq_weighted(x[0], x[1], nvalid, p0, None, faq['maxiter'], faq['tol'])
     else:
-        out = qap.faq_weighted_seeded(x[0], x[1], seeds, nvalid, p0, None, faq['maxiter'], faq['tol'], p0_free=True)
+        out = qap.faq_weighted(x[0], x[1], nvalid, p0, None, faq['maxiter'], faq['tol'], seeds=seeds, p0_free=True)
     fq = qap.objective_bits(b1, b2, out['perm'], nvalid, raw=True)[0]
     failed = out['status'] == 2
     res = {'perm': torch.where(failed[:, None], assign, out['perm']), 'qap': torch.where(failed, q, fq), 'faq_perm': out['perm'],

@@ -188,6 +188,36 @@ def _chan0_ok(x):
             and x.data_ptr() % 4 == 0)
 
 
+def _pitched(x):
+    """(B, N, N) fp32 device matrices -> (x, gstride, ld): read in place when the rows are contiguous (pitched views included),
+    else copied"""
+    if not _chan0_ok(x):
+        x = x.contiguous()
+    return x, x.stride(0) if x.shape[0] > 1 else x.shape[-1] * x.stride(-2), x.stride(-2)
+
+
+def _labels_or_identity(labels, B, N, dev):
+    if labels is None:
+        return torch.arange(N, dtype=torch.int32, device=dev).expand(B, N).contiguous()
+    return labels
+
+
+def _finish_solver(out, q, labels, nv, flag):
+    """The tail `faq`, `two_opt` and `two_opt_weighted` share: status, nit (and seeded) widened to int64 where the launch wrote
+    int32; qap = q with -1 where status == 2 (q None: the launch wrote qap itself); acc against labels or the identity; the one
+    read of a dense input's verdict flag."""
+    for k in ('status', 'nit', 'seeded'):
+        if k in out:
+            out[k] = out[k].to(torch.int64)
+    if q is not None:
+        out['qap'] = torch.where(out['status'] == 2, torch.full_like(q, -1), q)
+    B, N = out['perm'].shape
+    out['acc'] = count_matches(out['perm'], _labels_or_identity(labels, B, N, out['perm'].device), nv).to(torch.int64)
+    if flag is not None:
+        raise_if_bad(flag)
+    return out
+
+
 def weighted_views(adj1, adj2):
     """-> (x1, x2, gstride, ld): fp32 device tensors whose data_ptr() is channel 0 of pair 0 (row pitch ld, pairs gstride floats apart,
     the same on both sides).  A contiguous fp32 (B, N, N) or (B, C, N, N) batch passes in place; anything else has its channel 0 copied."""
@@ -282,12 +312,8 @@ def two_opt_weighted(adj1, adj2, assign, nvalid=None, labels=None, max_swaps=Non
     _lib.call('fgnn_qapw_2opt', _lib.ptr(x1), _lib.ptr(x2), gs, ld, _lib.ptr(a), _lib.ptr(nv), B, N, ms, _lib.ptr(ws), nbytes,
               _lib.ptr(perm), _lib.ptr(o32[0]), _lib.ptr(nit), _lib.ptr(o32[1]), _lib.stream_ptr())
     o64 = o32.to(torch.int64)
-    qap = objective_weighted(x1, x2, perm, nv)['qap']
-    if labels is None:
-        labels = torch.arange(N, dtype=torch.int32, device=dev).expand(B, N).contiguous()
-    return {'perm': perm, 'qap': torch.where(o64[1] == 2, torch.full_like(qap, -1.0), qap),
-            'qap0': objective_weighted(x1, x2, a, nv)['qap'], 'acc': count_matches(perm, labels, nv).to(torch.int64),
-            'swaps': o64[0], 'nit': nit, 'status': o64[1]}
+    out = {'perm': perm, 'qap0': objective_weighted(x1, x2, a, nv)['qap'], 'swaps': o64[0], 'nit': nit, 'status': o64[1]}
+    return _finish_solver(out, objective_weighted(x1, x2, perm, nv)['qap'], labels, nv, None)
 
 
 def _faq_start(P0, B, N, dev):
@@ -307,25 +333,6 @@ def _faq_start(P0, B, N, dev):
     if tuple(P0.shape) != (B, N, N):
         raise ValueError('faq: a matrix P0 must have shape (%d, %d, %d), got %s' % (B, N, N, tuple(P0.shape)))
     return P0.detach().to(device=dev, dtype=torch.float32).contiguous(), None
-
-
-def faq_weighted(adj1, adj2, nv, p0=None, assign0=None, maxiter=30, tol=0.03, return_P=False):
-    """fgnn_qapw_faq on what `weighted_views` takes -> {'perm' (B, N) int32, 'nit', 'status' (B,) int32, + 'P' (B, N, N) fp32 with
-    return_P} device tensors as the launch chain wrote them; never synchronises."""
-    x1, x2, gs, ld = weighted_views(adj1, adj2)
-    B, N = x1.shape[0], x1.shape[-1]
-    dev = x1.device
-    nbytes = _lib.load().fgnn_qapw_faq_ws_bytes(B, N)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    perm = torch.empty(B, N, dtype=torch.int32, device=dev)
-    out = torch.empty(2, B, dtype=torch.int32, device=dev)
-    P = torch.empty(B, N, N, dtype=torch.float32, device=dev) if return_P else None
-    _lib.call('fgnn_qapw_faq', _lib.ptr(x1), _lib.ptr(x2), gs, ld, _lib.ptr(p0), _lib.ptr(assign0), _lib.ptr(nv), B, N, int(maxiter),
-              float(tol), _lib.ptr(ws), nbytes, _lib.ptr(perm), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(P), _lib.stream_ptr())
-    res = {'perm': perm, 'nit': out[0], 'status': out[1]}
-    if return_P:
-        res['P'] = P
-    return res
 
 
 def check_seeds(who, seeds, B, N, dev):
@@ -382,30 +389,33 @@ def seed_gather_device(x, rows, cols, nfree):
     """fgnn_seed_gather on (B, N, N) fp32 device matrices (rows contiguous, pitched views included) -> (B, N, N) fp32: the
     (rows, cols) block in the nfree x nfree corner, exact zeros around it; never synchronises."""
     B, N = x.shape[0], x.shape[-1]
-    if not _chan0_ok(x):
-        x = x.contiguous()
+    x, gs, ld = _pitched(x)
     out = torch.empty(B, N, N, dtype=torch.float32, device=x.device)
-    _lib.call('fgnn_seed_gather', _lib.ptr(x), x.stride(0) if B > 1 else N * x.stride(-2), x.stride(-2), _lib.ptr(rows), _lib.ptr(cols),
+    _lib.call('fgnn_seed_gather', _lib.ptr(x), gs, ld, _lib.ptr(rows), _lib.ptr(cols),
               _lib.ptr(nfree), B, N, _lib.ptr(out), _lib.stream_ptr())
     return out
 
 
-def faq_weighted_seeded(adj1, adj2, seeds, nv, p0=None, assign0=None, maxiter=30, tol=0.03, return_P=False, p0_free=False):
-    """fgnn_qapw_faq_seeded on what `weighted_views` takes and (B, N) int32 device seeds -> the dict of `faq_weighted` plus 'seeded'
-    (B,) int32 = m_b; 'P' is the last iterate in free coordinates (the u_b x u_b corner); never synchronises.  p0_free: p0 is
-    already in free coordinates (its u_b x u_b corner is the start)."""
+def faq_weighted(adj1, adj2, nv, p0=None, assign0=None, maxiter=30, tol=0.03, return_P=False, seeds=None, p0_free=False):
+    """fgnn_qapw_faq on what `weighted_views` takes -> {'perm' (B, N) int32, 'nit', 'status' (B,) int32, + 'P' (B, N, N) fp32 with
+    return_P} device tensors as the launch chain wrote them; never synchronises.  seeds ((B, N) int32 on the device):
+    fgnn_qapw_faq_seeded instead, and the dict gains 'seeded' (B,) int32 = m_b; 'P' is then the last iterate in free coordinates (the
+    u_b x u_b corner).  p0_free (with seeds): p0 is already in free coordinates (its u_b x u_b corner is the start)."""
     x1, x2, gs, ld = weighted_views(adj1, adj2)
     B, N = x1.shape[0], x1.shape[-1]
     dev = x1.device
-    nbytes = _lib.load().fgnn_qapw_faq_seeded_ws_bytes(B, N)
+    entry = 'fgnn_qapw_faq' if seeds is None else 'fgnn_qapw_faq_seeded'
+    nbytes = getattr(_lib.load(), entry + '_ws_bytes')(B, N)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     perm = torch.empty(B, N, dtype=torch.int32, device=dev)
-    out = torch.empty(3, B, dtype=torch.int32, device=dev)
+    out = torch.empty(2 if seeds is None else 3, B, dtype=torch.int32, device=dev)
     P = torch.empty(B, N, N, dtype=torch.float32, device=dev) if return_P else None
-    _lib.call('fgnn_qapw_faq_seeded', _lib.ptr(x1), _lib.ptr(x2), gs, ld, _lib.ptr(seeds), _lib.ptr(p0), int(bool(p0_free)), _lib.ptr(assign0),
-              _lib.ptr(nv), B, N, int(maxiter), float(tol), _lib.ptr(ws), nbytes, _lib.ptr(perm), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]),
-              _lib.ptr(P), _lib.stream_ptr())
-    res = {'perm': perm, 'nit': out[0], 'status': out[1], 'seeded': out[2]}
+    start = (_lib.ptr(p0),) if seeds is None else (_lib.ptr(seeds), _lib.ptr(p0), int(bool(p0_free)))
+    _lib.call(entry, _lib.ptr(x1), _lib.ptr(x2), gs, ld, *start, _lib.ptr(assign0), _lib.ptr(nv), B, N, int(maxiter), float(tol),
+              _lib.ptr(ws), nbytes, _lib.ptr(perm), *(_lib.ptr(o) for o in out), _lib.ptr(P), _lib.stream_ptr())
+    res = {'perm': perm, 'nit': out[0], 'status': out[1]}
+    if seeds is not None:
+        res['seeded'] = out[2]
     if return_P:
         res['P'] = P
     return res
@@ -461,33 +471,36 @@ def faq(adj1, adj2, nvalid=None, labels=None, P0='barycenter', maxiter=30, tol=0
     if (_on_host_weighted if weighted else _on_host)(adj1, N):
         return _faq_host(adj1, adj2, nvalid, labels, p0, assign0, int(maxiter), tol, weighted, return_P, seeds)
     dev = adj1.device
-
-    def run(x1, x2, nv):
-        if seeds is None:
-            return faq_weighted(x1, x2, nv, p0, assign0, maxiter, tol, return_P)
-        return faq_weighted_seeded(x1, x2, seeds, nv, p0, assign0, maxiter, tol, return_P)
-
     if weighted:
         nv, flag = _nv32(nvalid, dev), None
-        out = run(adj1, adj2, nv)
+        out = faq_weighted(adj1, adj2, nv, p0, assign0, maxiter, tol, return_P, seeds)
         q = objective_weighted(adj1, adj2, out['perm'], nv)['qap']
     else:
         b1, b2, nv, flag = _device_inputs(adj1, adj2, nvalid)
         x = torch.empty(2, B, 2, N, N, dtype=torch.float32, device=dev)
         for side, bits in enumerate((b1, b2)):
             _lib.call('fgnn_expand_adjacency', _lib.ptr(bits), _lib.ptr(nv), B, N, _lib.ptr(x[side]), _lib.stream_ptr())
-        out = run(x[0], x[1], nv)
+        out = faq_weighted(x[0], x[1], nv, p0, assign0, maxiter, tol, return_P, seeds)
         q = objective_bits(b1, b2, out['perm'], nv)['qap']
-    out['status'], out['nit'] = out['status'].to(torch.int64), out['nit'].to(torch.int64)
-    if seeds is not None:
-        out['seeded'] = out['seeded'].to(torch.int64)
-    out['qap'] = torch.where(out['status'] == 2, torch.full_like(q, -1), q)
-    if labels is None:
-        labels = torch.arange(N, dtype=torch.int32, device=dev).expand(B, N).contiguous()
-    out['acc'] = count_matches(out['perm'], labels, nv).to(torch.int64)
-    if flag is not None:
-        raise_if_bad(flag)
-    return out
+    return _finish_solver(out, q, labels, nv, flag)
+
+
+def _scores_arg(who, scores, nvalid):
+    """scores=, nvalid= of `sinkhorn` / `confident_seeds`: a MaskedTensor unwrapped (its vertex counts stand in for a missing nvalid),
+    anything but (B, N, N) floating-point scores and a (B,) integer nvalid refused -> (detached scores, nvalid)"""
+    if isinstance(scores, MaskedTensor):
+        if nvalid is None:
+            nvalid = scores.nvalid
+        scores = scores.tensor.rename(None)
+    if not torch.is_tensor(scores) or scores.dim() != 3 or scores.shape[1] != scores.shape[2] or not scores.is_floating_point():
+        raise ValueError('%s: expected (B, N, N) floating-point scores, got %s'
+                         % (who, tuple(scores.shape) if torch.is_tensor(scores) else type(scores).__name__))
+    B, N = scores.shape[0], scores.shape[-1]
+    if B < 1 or N < 1:
+        raise ValueError('%s: empty batch %s' % (who, tuple(scores.shape)))
+    if nvalid is not None and (not torch.is_tensor(nvalid) or tuple(nvalid.shape) != (B,) or nvalid.is_floating_point()):
+        raise ValueError('%s: nvalid must be a (%d,) integer tensor' % (who, B))
+    return scores.detach(), nvalid
 
 
 def check_sinkhorn(who, tau, iters):
@@ -504,12 +517,11 @@ def sinkhorn_device(s, nv, tau, iters):
     {'P': (B, N, N) fp32, 'err': (B,) fp32, 'status': (B,) int32} as the launch wrote them; never synchronises."""
     B, N = s.shape[0], s.shape[-1]
     dev = s.device
-    if not _chan0_ok(s):
-        s = s.contiguous()
+    s, gs, ld = _pitched(s)
     P = torch.empty(B, N, N, dtype=torch.float32, device=dev)
     err = torch.empty(B, dtype=torch.float32, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
-    _lib.call('fgnn_sinkhorn', _lib.ptr(s), s.stride(0) if B > 1 else N * s.stride(-2), s.stride(-2), _lib.ptr(nv), B, N, tau, iters,
+    _lib.call('fgnn_sinkhorn', _lib.ptr(s), gs, ld, _lib.ptr(nv), B, N, tau, iters,
               _lib.ptr(P), _lib.ptr(err), _lib.ptr(status), _lib.stream_ptr())
     return {'P': P, 'err': err, 'status': status}
 
@@ -531,19 +543,8 @@ def sinkhorn(scores, nvalid=None, tau=1.0, iters=20):
     recurrence in numpy float64; there P and err are float64.  (The degenerate test looks at Z: scores whose quotient by tau
     overflows fp32 count as +inf on the device.)"""
     tau, iters = check_sinkhorn('sinkhorn', tau, iters)
-    if isinstance(scores, MaskedTensor):
-        if nvalid is None:
-            nvalid = scores.nvalid
-        scores = scores.tensor.rename(None)
-    if not torch.is_tensor(scores) or scores.dim() != 3 or scores.shape[1] != scores.shape[2] or not scores.is_floating_point():
-        raise ValueError('sinkhorn: expected (B, N, N) floating-point scores, got %s'
-                         % (tuple(scores.shape) if torch.is_tensor(scores) else type(scores).__name__,))
-    B, N = scores.shape[0], scores.shape[-1]
-    if B < 1 or N < 1:
-        raise ValueError('sinkhorn: empty batch %s' % (tuple(scores.shape),))
-    if nvalid is not None and (not torch.is_tensor(nvalid) or tuple(nvalid.shape) != (B,) or nvalid.is_floating_point()):
-        raise ValueError('sinkhorn: nvalid must be a (%d,) integer tensor' % B)
-    scores = scores.detach()
+    scores, nvalid = _scores_arg('sinkhorn', scores, nvalid)
+    N = scores.shape[-1]
     if _on_host(scores, N):
         return _sinkhorn_host(scores, nvalid, tau, iters)
     with torch.cuda.device(scores.device):
@@ -568,12 +569,11 @@ def confident_seeds_device(s, nv, count=-1, min_margin=0.0, return_margin=False)
     {'seeds': (B, N) int32, 'nseeds': (B,) int32 (+ 'margin': (B, N) fp32)} as the launch wrote them; never synchronises."""
     B, N = s.shape[0], s.shape[-1]
     dev = s.device
-    if not _chan0_ok(s):
-        s = s.contiguous()
+    s, gs, ld = _pitched(s)
     seeds = torch.empty(B, N, dtype=torch.int32, device=dev)
     nseeds = torch.empty(B, dtype=torch.int32, device=dev)
     margin = torch.empty(B, N, dtype=torch.float32, device=dev) if return_margin else None
-    _lib.call('fgnn_confident_seeds', _lib.ptr(s), s.stride(0) if B > 1 else N * s.stride(-2), s.stride(-2), _lib.ptr(nv), B, N, count,
+    _lib.call('fgnn_confident_seeds', _lib.ptr(s), gs, ld, _lib.ptr(nv), B, N, count,
               min_margin, _lib.ptr(seeds), _lib.ptr(nseeds), _lib.ptr(margin), _lib.stream_ptr())
     out = {'seeds': seeds, 'nseeds': nseeds}
     if return_margin:
@@ -598,19 +598,8 @@ def confident_seeds(scores, nvalid=None, count=None, min_margin=0.0, return_marg
     from run to run, a pair's result independent of the batch; it never synchronises.  CPU tensors and N > 256 take the same rule
     restated in numpy, with the margin in float32 arithmetic: the two routes agree exactly."""
     count, min_margin = check_confident('confident_seeds', count, min_margin)
-    if isinstance(scores, MaskedTensor):
-        if nvalid is None:
-            nvalid = scores.nvalid
-        scores = scores.tensor.rename(None)
-    if not torch.is_tensor(scores) or scores.dim() != 3 or scores.shape[1] != scores.shape[2] or not scores.is_floating_point():
-        raise ValueError('confident_seeds: expected (B, N, N) floating-point scores, got %s'
-                         % (tuple(scores.shape) if torch.is_tensor(scores) else type(scores).__name__,))
-    B, N = scores.shape[0], scores.shape[-1]
-    if B < 1 or N < 1:
-        raise ValueError('confident_seeds: empty batch %s' % (tuple(scores.shape),))
-    if nvalid is not None and (not torch.is_tensor(nvalid) or tuple(nvalid.shape) != (B,) or nvalid.is_floating_point()):
-        raise ValueError('confident_seeds: nvalid must be a (%d,) integer tensor' % B)
-    scores = scores.detach()
+    scores, nvalid = _scores_arg('confident_seeds', scores, nvalid)
+    N = scores.shape[-1]
     if not scores.is_cuda or N > _lib.FGNN_SEED_MAX_N:
         return _confident_seeds_host(scores, nvalid, count, min_margin, return_margin)
     with torch.cuda.device(scores.device):
@@ -684,16 +673,10 @@ def two_opt(adj1, adj2, assign, nvalid=None, labels=None, max_swaps=None, weight
     if _on_host(adj1, adj1.shape[-2]):
         return _two_opt_host(adj1, adj2, assign, nvalid, labels, ms, seeds)
     b1, b2, nv, flag = _device_inputs(adj1, adj2, nvalid)
-    B, N, _ = b1.shape
     a = assign.to(device=b1.device, dtype=torch.int32).contiguous()
     out = two_opt_bits(b1, b2, a, nv, max_swaps, seeds=seeds)
     out['qap0'] = objective_bits(b1, b2, a, nv)['qap']
-    if labels is None:
-        labels = torch.arange(N, dtype=torch.int32, device=b1.device).expand(B, N).contiguous()
-    out['acc'] = count_matches(out['perm'], labels, nv).to(torch.int64)
-    if flag is not None:
-        raise_if_bad(flag)
-    return out
+    return _finish_solver(out, None, labels, nv, flag)
 
 
 def all_acc_qap(scores, adj1, adj2, nvalid=None, weighted=False, labels=None):

@@ -88,24 +88,33 @@ def test_first_iteration_equals_scipy_exactly(n, kind):
 
 # ------------------------------------------------------------------------------------------- 2. one round from a known P
 CASES = ((5, 2), (33, 1), (50, 10), (65, 31))
+# u = 132 > FQ_COLS = 128: the seeded gradient and step across the second column block.  (n, m, the pair's generator seed): the cap
+# tol < 1e-3 |best| at the end of the test binds at this size (the tolerance grows with gamma_(3 u)), and these seeds are the ones
+# of 0 .. 119 that keep the most room under it, evaluated in float64 with P1 from the host update: 0.945 / 0.960 (sym / dir) of
+# the cap for (136, 4, 20), 0.959 / 0.983 for (133, 1, 89)
+WIDE = ((136, 4, 20), (133, 1, 89))
 
 
 @pytest.mark.parametrize('symmetric', [True, False], ids=['sym', 'dir'])
 def test_one_round_from_a_known_P(symmetric):
-    N = 72
-    pairs = [R.real_pair(n, b, symmetric) for b, (n, m) in enumerate(CASES)]
+    for N, cases in ((72, [(n, m, b) for b, (n, m) in enumerate(CASES)]), (136, WIDE)):
+        _one_round_from_a_known_P(N, cases, symmetric)
+
+
+def _one_round_from_a_known_P(N, cases, symmetric):
+    pairs = [R.real_pair(n, s, symmetric) for n, m, s in cases]
     As, Bs = [p[0] for p in pairs], [p[1] for p in pairs]
-    sds = [S.seed_vector(n, m, b) for b, (n, m) in enumerate(CASES)]
-    starts, P0 = [], torch.full((len(CASES), N, N), float('nan'))
-    for b, (n, m) in enumerate(CASES):
+    sds = [S.seed_vector(n, m, s) for n, m, s in cases]
+    starts, P0 = [], torch.full((len(cases), N, N), float('nan'))
+    for b, (n, m, s) in enumerate(cases):
         free_a, free_b, _, _ = S.lists_of(sds[b], n)
-        starts.append(R.interior_start(n - m, b))
+        starts.append(R.interior_start(n - m, s))
         P0[b][np.ix_(free_a, free_b)] = torch.from_numpy(starts[b]).float()
     out = qap.faq(_dense(As, N, 5), _dense(Bs, N, 6), nvalid=_nv(As), P0=P0.to(DEV), weighted=True, maxiter=1, return_P=True,
                   seeds=_seeds(sds, N))
-    assert out['nit'].cpu().tolist() == [1] * len(CASES) and out['seeded'].cpu().tolist() == [m for _, m in CASES]
+    assert out['nit'].cpu().tolist() == [1] * len(cases) and out['seeded'].cpu().tolist() == [m for _, m, _ in cases]
     _holds(out['perm'], sds)
-    for b, (n, m) in enumerate(CASES):
+    for b, (n, m, _) in enumerate(cases):
         u = n - m
         A22, B22, C, Cabs = S.blocks(As[b], Bs[b], sds[b])
         P = starts[b]
@@ -280,9 +289,62 @@ def test_two_opt_seeded_equals_host_and_scipy(n):
     assert out['perm'][0, :n].cpu().tolist() == p.tolist()
 
 
+def _planted_pair(n, b):
+    """-> (A, B, q): pair b of the batches below relabelled by a known q, B[q(i), q(k)] = (the noisy copy of A)[i, k]; b = 2 is
+    directed with loops"""
+    rng = np.random.default_rng(500 * n + b)
+    if b < 2:
+        A, M = R.zero_one_pair(n, b, 'ErdosRenyi' if b == 1 else 'Regular')
+    else:
+        A = (rng.random((n, n)) < 0.3).astype(np.float64)
+        M = np.where(rng.random((n, n)) < 0.1, (rng.random((n, n)) < 0.3).astype(np.float64), A)
+    q = rng.permutation(n)
+    B = np.zeros_like(A)
+    B[np.ix_(q, q)] = M
+    return A, B, q
+
+
+@pytest.mark.parametrize('n', [65, 129])
+def test_two_opt_seeded_across_waves_equals_host(n):
+    """n > 64: the rank table's prefix crosses waves (and, with N > 128, the NW = 8 form; n = 65 runs NW = 4).  m = 0, 3, n - 1 seeds
+    on the planted matching; seeded and free rows at index >= 64, and at n = 129 at index 128: pair 0 has every row free, pair 1 seeds
+    rows 2, 70 (n = 65: 40) and n - 1, pair 2 leaves only row n - 1 free.  The starts are the planted matching with three
+    transpositions of free rows (none in pair 2), so the host route ends after a few rounds.  Host route only: SciPy is compared
+    at the sizes of the test above."""
+    trio = [_planted_pair(n, b) for b in range(3)]
+    As, Bs = [t[0] for t in trio], [t[1] for t in trio]
+    held = ([], [2, 70 if n > 70 else 40, n - 1], list(range(n - 1)))
+    sds, starts = [], []
+    for (_, _, q), rows in zip(trio, held):
+        sd = np.full(n, -1, dtype=np.int64)
+        sd[rows] = q[rows]
+        fr = np.flatnonzero(sd < 0)
+        p = q.copy()
+        if len(fr) > 1:
+            for i, j in ((fr[0], fr[-1]), (fr[1], fr[len(fr) // 2]), (fr[5], fr[6])):
+                p[[i, j]] = p[[j, i]]
+        sds.append(sd)
+        starts.append(p)
+    assert sds[0][n - 1] < 0 and sds[1][n - 1] >= 0 and sds[2][n - 1] < 0 and sds[1][n - 2] < 0
+    for N in (n, n + 5):
+        x1, x2, nv = _bits(As, N), _bits(Bs, N), torch.full((3,), n, dtype=torch.int32, device=DEV)
+        dev = qap.two_opt(x1, x2, _rows(starts, N), nvalid=nv, seeds=_seeds(sds, N))
+        host = qap.two_opt(x1.cpu(), x2.cpu(), _rows(starts, N).cpu(), nvalid=nv.cpu(), seeds=_seeds(sds, N).cpu())
+        for k in ('perm', 'qap', 'qap0', 'acc', 'swaps', 'nit', 'status'):
+            assert dev[k].cpu().tolist() == host[k].tolist(), (k, N)
+        _holds(dev['perm'], sds)
+        assert dev['status'].cpu().tolist() == [0] * 3
+        assert int(dev['swaps'][0]) > 0 and int(dev['swaps'][1]) > 0 and int(dev['swaps'][2]) == 0 and int(dev['nit'][2]) == 1
+        # all -1 seeds: the unseeded search, bit for bit
+        free = qap.two_opt(x1, x2, _rows(starts, N), nvalid=nv, seeds=torch.full((3, N), -1, dtype=torch.int32, device=DEV))
+        plain = qap.two_opt(x1, x2, _rows(starts, N), nvalid=nv)
+        assert set(free) == set(plain) and all(torch.equal(free[k], plain[k]) for k in plain)
+        assert int(plain['swaps'].max()) > 0
+
+
 # --------------------------------------------------------------------------------------------- 7. the unseeded path, bit for bit
-def test_free_seeds_are_the_unseeded_chain_bit_for_bit():
-    N, sizes = 64, (50, 33, 32, 16, 5, 2, 1)
+def _free_seeds_are_the_unseeded_chain(N, sizes):
+    """plain, seeds=None and all -1 seeds: equal bytes on every key -> (x1, x2, nv) of the batch"""
     pairs = [R.real_pair(n, 40 + b) for b, n in enumerate(sizes)]
     As, Bs = [p[0] for p in pairs], [p[1] for p in pairs]
     x1, x2, nv = _dense(As, N, 10), _dense(Bs, N, 11), _nv(As)
@@ -297,6 +359,13 @@ def test_free_seeds_are_the_unseeded_chain_bit_for_bit():
         assert torch.equal(plain[k], seeded[k]), k
     assert all(torch.equal(seeded[k], again[k]) for k in seeded)
     assert int(plain['nit'].max()) > 1 and seeded['seeded'].cpu().tolist() == [0] * len(sizes)
+    return x1, x2, nv
+
+
+def test_free_seeds_are_the_unseeded_chain_bit_for_bit():
+    _free_seeds_are_the_unseeded_chain(136, (136, 130, 129))          # n > FQ_COLS = 128: the second column block
+    N, sizes = 64, (50, 33, 32, 16, 5, 2, 1)
+    x1, x2, nv = _free_seeds_are_the_unseeded_chain(N, sizes)
     # with seeds: run to run, and a pair's result does not depend on the batch around it
     sds = [S.seed_vector(n, n // 4, b) for b, n in enumerate(sizes)]
     seeds = _seeds(sds, N)
@@ -318,12 +387,12 @@ def test_seeded_chain_is_capturable():
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
-        eager = qap.faq_weighted_seeded(x1, x2, seeds, None, maxiter=3)
+        eager = qap.faq_weighted(x1, x2, None, seeds=seeds, maxiter=3)
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
-        cap = qap.faq_weighted_seeded(x1, x2, seeds, None, maxiter=3)
+        cap = qap.faq_weighted(x1, x2, None, seeds=seeds, maxiter=3)
     graph.replay()
     torch.cuda.synchronize()
     assert all(torch.equal(eager[k], cap[k]) for k in eager)

@@ -4,9 +4,11 @@ ErdosRenyi noise 0.1, 32 relabelled pairs as bit-packed adjacency (seed 1), 8 se
 (a) the seeded chain against the unseeded one (qap.faq with and without seeds=; the seeded one works on u = N - 8 vertices and pays
     the set-up launches), with the default tol and with a tol no pair meets;
 (b) the three set-up launches alone: fgnn_seed_index, fgnn_seed_gather (one of A22 / B22), fgnn_seed_const;
-(c) the unseeded qap.faq and qap.two_opt of THIS library and, with --parent-lib, of the parent commit's build (a second process
-    that loads it through FGNN_LIB and runs the same windows): the unseeded entry points were not touched, so the expectation is
-    no change beyond the spread;
+(c) the four solver entry points -- qap.faq and qap.two_opt, each without and with seeds= -- of THIS library and, with
+    --parent-lib, of the parent commit's build: each build is then timed in a fresh process of its own (the parent's loaded
+    through FGNN_LIB) that runs nothing but these windows, so that both meet the same allocator and runtime state.  Per variant
+    `vs_parent` holds this library's median minus the parent's beside the larger of the two spreads: a median further above the
+    parent's than that margin is a regression;
 (d) quality: free vertices recovered with and without the seeds.
 
 Protocol (tools/time_pairgen_indexed.py): device events on one stream, warm-up, then WINDOWS = 7 rounds in which the variants take
@@ -36,13 +38,16 @@ def pairs_of(N):
     return gen.bits(0, B, permute=True)
 
 
-def unseeded(N, reps):
-    """the entry points every build has: qap.faq and qap.two_opt without seeds"""
-    from graph_neural_net_amd import qap
+def solvers(N, reps):
+    """leg (c): qap.faq and qap.two_opt without and with seeds=, the seeded two_opt from the seeded faq's matching"""
+    from graph_neural_net_amd import planted, qap
     from time_pairgen_indexed import alternate, row
     b1, b2, _, labels = pairs_of(N)
-    start = qap.faq(b1, b2)['perm']
-    return row(alternate({'faq': lambda: qap.faq(b1, b2), 'two_opt': lambda: qap.two_opt(b1, b2, start)}, reps))
+    seeds = planted.reveal_seeds(labels, None, SEEDS, seed=1)
+    start, start_seeded = qap.faq(b1, b2)['perm'], qap.faq(b1, b2, seeds=seeds)['perm']
+    return row(alternate({'faq': lambda: qap.faq(b1, b2), 'two_opt': lambda: qap.two_opt(b1, b2, start),
+                          'faq_seeded': lambda: qap.faq(b1, b2, seeds=seeds),
+                          'two_opt_seeded': lambda: qap.two_opt(b1, b2, start_seeded, seeds=seeds)}, reps))
 
 
 def one_size(N, reps):
@@ -82,26 +87,35 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--sizes', default='50,200')
     ap.add_argument('--parent-lib', default=None, help="the parent commit's libfgnn_hip.so, for leg (c)")
-    ap.add_argument('--unseeded-only', action='store_true', help='leg (c) of the library FGNN_LIB names; prints one JSON line')
+    ap.add_argument('--solvers-only', action='store_true', help='leg (c) of the library FGNN_LIB names; prints one JSON line')
     ap.add_argument('--out', default=None)
     o = ap.parse_args()
     sizes = list(map(int, o.sizes.split(',')))
     reps = {n: o.reps if n <= 64 else max(2, o.reps // 2) for n in sizes}
-    if o.unseeded_only:
+    if o.solvers_only:
         _lib.load(allow_missing=True)
-        print(json.dumps({str(n): unseeded(n, reps[n]) for n in sizes}))
+        print(json.dumps({str(n): solvers(n, reps[n]) for n in sizes}))
         return
     from time_pairgen_indexed import WINDOWS
     res = {'tool': 'time_seeds', 'windows': WINDOWS, 'sizes': []}
     for n in sizes:
         res['sizes'].append(one_size(n, reps[n]))
-        res['sizes'][-1]['unseeded_this_library'] = unseeded(n, reps[n])
-    if o.parent_lib:                 # a fresh process: a library is loaded once per process
-        cmd = [sys.executable, os.path.abspath(__file__), '--unseeded-only', '--reps', str(o.reps), '--sizes', o.sizes]
-        out = subprocess.run(cmd, env=dict(os.environ, FGNN_LIB=os.path.abspath(o.parent_lib)), check=True, capture_output=True, text=True)
-        parent = json.loads(out.stdout.strip().splitlines()[-1])
+        res['sizes'][-1]['solvers_this_library'] = solvers(n, reps[n])
+    if o.parent_lib:                 # fresh processes: a library is loaded once per process, and both builds meet the same conditions
+        def fresh(lib):
+            cmd = [sys.executable, os.path.abspath(__file__), '--solvers-only', '--reps', str(o.reps), '--sizes', o.sizes]
+            env = dict(os.environ, FGNN_LIB=os.path.abspath(lib)) if lib else {k: v for k, v in os.environ.items() if k != 'FGNN_LIB'}
+            out = subprocess.run(cmd, env=env, check=True, capture_output=True, text=True)
+            return json.loads(out.stdout.strip().splitlines()[-1])
+
+        this, parent = fresh(None), fresh(o.parent_lib)
         for s in res['sizes']:
-            s['unseeded_parent_library'] = parent[str(s['n_vertices'])]
+            ours, theirs = this[str(s['n_vertices'])], parent[str(s['n_vertices'])]
+            s['solvers_this_library'], s['solvers_parent_library'] = ours, theirs
+            s['vs_parent'] = {k: {'delta_us': round(ours[k]['us'] - theirs[k]['us'], 2),
+                                  'margin_us': max(ours[k]['spread_us'], theirs[k]['spread_us'])} for k in ours}
+            for v in s['vs_parent'].values():
+                v['within'] = v['delta_us'] <= v['margin_us']
     line = json.dumps(res)
     if o.out:
         os.makedirs(os.path.dirname(os.path.abspath(o.out)), exist_ok=True)
