@@ -23,6 +23,9 @@ FGNN_QAP_MAX_N = 256         # include/fgnn_hip.h: largest graph of the fgnn_qap
 FGNN_QAPW_MAX_N = 256        # include/fgnn_hip.h: largest graph of the fgnn_qapw_* / fgnn_greedy_qapw kernels (fp32 weights)
 FGNN_SEED_MAX_N = 256        # include/fgnn_hip.h: largest graph of the fgnn_seed_* kernels
 FGNN_SINKHORN_LDS_MAX_N = 192   # include/fgnn_hip.h: largest graph whose scores fgnn_sinkhorn keeps in LDS
+FGNN_RESTART_STREAM = 9      # include/fgnn_hip.h: the pair stream of fgnn_faq_restart_starts
+FGNN_RESTART_MAX_R = 64      # include/fgnn_hip.h: restarts per pair
+FGNN_RESTART_MAX_STARTS = 65535   # include/fgnn_hip.h: B R of one call (the pairs of one fgnn_qapw_faq call)
 FGNN_SPECTRAL_MAX_N = 256    # include/fgnn_hip.h: largest graph of fgnn_spectral_features
 FGNN_SPECTRAL_MAX_POWERS = 8
 FGNN_PLANTED_MAX_N = 256      # include/fgnn_hip.h: largest graph of the fgnn_planted_perm / fgnn_relabel_* kernels
@@ -339,6 +342,9 @@ _SIGNATURES = {
     'fgnn_confident_seeds': [_VP, _LL, _I, _VP, _I, _I, _I, _F, _VP, _VP, _VP, _VP],
     'fgnn_seed_fold': [_VP] * 5 + [_I, _I, _I, _VP, _VP],
     'fgnn_seed_fold_bins': [_VP] * 5 + [_I, _I, _I, _VP, _I, _VP, _VP],
+    'fgnn_faq_restart_starts': [_VP, _VP, _VP, C.c_ulonglong, _I, _I, _I, _VP, _VP],
+    'fgnn_qap_best_of_i64': [_VP] * 5 + [_I, _I, _I] + [_VP] * 6,
+    'fgnn_qap_best_of_f32': [_VP] * 5 + [_I, _I, _I] + [_VP] * 6,
     # ---- bf16 path ----
     'fgnn_tiles_per_graph16': [_I, _I],
     'fgnn_to_bf16': [_VP, _VP, _I, _I, _I, _I, _VP, _LL, _LL, _VP],

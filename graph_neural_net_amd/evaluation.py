@@ -533,21 +533,30 @@ def _bits_args(who, bits, B, N, dev):
 
 
 FAQ_DEFAULTS = {'P0': 'scores', 'maxiter': 30, 'tol': 0.03, 'tau': 1.0, 'iters': 20}
+FAQ_RESTART_DEFAULTS = {'restarts': 1, 'seed': 0, 'polish': False, 'index': None}      # qap.faq's restarts=, seed=, polish=, pair_index=
 
 
 def _check_faq(who, faq):
-    """faq= of the decode: None (off), True (FAQ_DEFAULTS) or a dict of some of its keys -> None or the full dict, checked"""
+    """faq= of the decode: None (off), True (FAQ_DEFAULTS) or a dict of some of its keys and of FAQ_RESTART_DEFAULTS' -> None or
+    the full dict, checked"""
     if faq is None:
         return None
     if faq is True:
         faq = {}
+    keys = dict(FAQ_DEFAULTS, **FAQ_RESTART_DEFAULTS)
     if not isinstance(faq, dict):
-        raise ValueError('%s: faq must be None, True or a dict with keys from %s, got %r' % (who, sorted(FAQ_DEFAULTS), faq))
-    unknown = sorted(set(faq) - set(FAQ_DEFAULTS), key=str)
+        raise ValueError('%s: faq must be None, True or a dict with keys from %s, got %r' % (who, sorted(keys), faq))
+    unknown = sorted(set(faq) - set(keys), key=str)
     if unknown:
-        raise ValueError('%s: faq has unknown key(s) %s; the keys are %s' % (who, unknown, sorted(FAQ_DEFAULTS)))
-    from .qap import check_sinkhorn
-    o = dict(FAQ_DEFAULTS, **faq)
+        raise ValueError('%s: faq has unknown key(s) %s; the keys are %s' % (who, unknown, sorted(keys)))
+    from .qap import _check_restarts, check_sinkhorn
+    o = dict(keys, **faq)
+    o['restarts'], o['seed'] = _check_restarts('%s: faq' % who, o['restarts'], o['seed'])
+    if not isinstance(o['polish'], bool):
+        raise ValueError("%s: faq['polish'] must be True or False, got %r" % (who, o['polish']))
+    if o['index'] is not None and (not torch.is_tensor(o['index']) or o['index'].dim() != 1 or o['index'].is_floating_point()
+                                   or not o['index'].is_cuda):
+        raise ValueError("%s: faq['index'] must be a (B,) integer device tensor of pair indices" % who)
     if o['P0'] not in ('scores', 'barycenter'):
         raise ValueError("%s: faq['P0'] is 'scores' or 'barycenter', got %r" % (who, o['P0']))
     if isinstance(o['maxiter'], bool) or not isinstance(o['maxiter'], (int, np.integer)) or o['maxiter'] <= 0:
@@ -565,21 +574,56 @@ def _faq_launches(b1, b2, s, assign, q, nvalid, B, N, faq, seeds=None):
     `assign` and its objective `q`.  Every buffer is allocated before the first launch; nothing is read back.
     With seeds: fgnn_seed_index and fgnn_seed_gather first, so that Sinkhorn runs on the free block of the scores with n_b := u_b,
     and the fgnn_qapw_faq_seeded chain from that start, already in free coordinates.
-    -> {'perm', 'qap', 'faq_perm', 'faq_qap', 'faq_nit', 'faq_status', 'sinkhorn_err'} (+ 'seeded' with seeds)"""
+    With faq['restarts'] = R > 1 or faq['polish'] (qap.faq's restarts): that start -- the Sinkhorn matrix or the barycenter -- is the
+    base of fgnn_faq_restart_starts (pair indices faq['index'], else the position in the batch), the sides are replicated R-fold,
+    the chain runs once on the B R problems, qap.objective_bits (with polish qap.two_opt_bits, seeded with seeds) scores them and
+    fgnn_qap_best_of picks; the select then works on the winner.  Restart 0 is the start the stage always had.
+    -> {'perm', 'qap', 'faq_perm', 'faq_qap', 'faq_nit', 'faq_status', 'sinkhorn_err', 'faq_restart'} (+ 'seeded' with seeds);
+    faq_restart is None without restarts"""
     from . import qap
     dev = b1.device
+    R = faq['restarts']
+    restarted = R > 1 or faq['polish']
+    if restarted and B * R > _lib.FGNN_RESTART_MAX_STARTS:
+        raise ValueError('decode: at most %d starts per call (got %d pairs x %d restarts)' % (_lib.FGNN_RESTART_MAX_STARTS, B, R))
+    if faq['index'] is not None and tuple(faq['index'].shape) != (B,):
+        raise ValueError("decode: faq['index'] must hold %d pair indices, got %s" % (B, tuple(faq['index'].shape)))
     x = torch.empty(2, B, 2, N, N, dtype=torch.float32, device=dev)
-    p0 = err = None
+    p0 = err = u = None
+    if seeds is not None and (restarted or faq['P0'] == 'scores'):
+        ix = qap.seed_index_device(seeds, nvalid)
+        u = torch.where(ix['valid'] != 0, ix['nfree'], torch.zeros_like(ix['nfree']))
     if faq['P0'] == 'scores':
         if seeds is None:
             sk = qap.sinkhorn_device(s, nvalid, faq['tau'], faq['iters'])
         else:
-            ix = qap.seed_index_device(seeds, nvalid)
-            u = torch.where(ix['valid'] != 0, ix['nfree'], torch.zeros_like(ix['nfree']))
             sk = qap.sinkhorn_device(qap.seed_gather_device(s, ix['free_a'], ix['free_b'], u), u, faq['tau'], faq['iters'])
         p0, err = sk['P'], sk['err']
     for side, bits in enumerate((b1, b2)):
         _lib.call('fgnn_expand_adjacency', _lib.ptr(bits), _lib.ptr(nvalid), B, N, _lib.ptr(x[side]), _lib.stream_ptr())
+    if restarted:
+        def rep(t):
+            return t.repeat_interleave(R, 0) if t is not None else None
+        index = faq['index'].to(torch.int64).contiguous() if faq['index'] is not None else None
+        starts = qap.random_starts_device(p0, nvalid if seeds is None else u, index, faq['seed'], B, N, R, dev)
+        b1r, b2r, nvr, sdr = rep(b1), rep(b2), rep(nvalid), rep(seeds)
+        run = qap.faq_weighted(rep(x[0, :, 0]), rep(x[1, :, 0]), nvr, starts, None, faq['maxiter'], faq['tol'], seeds=sdr,
+                               p0_free=seeds is not None)
+        if faq['polish']:
+            t = qap.two_opt_bits(b1r, b2r, run['perm'], nvr, seeds=sdr)
+            best = qap.best_of_device(t['qap'], run['status'], run['nit'], t['perm'], R, t['status'].to(torch.int32))
+        else:
+            best = qap.best_of_device(qap.objective_bits(b1r, b2r, run['perm'], nvr)['qap'], run['status'], run['nit'], run['perm'], R)
+        out = {'perm': best['perm'], 'nit': best['nit'], 'status': best['status']}
+        if seeds is not None:
+            out['seeded'] = run['seeded'].view(B, R)[:, 0].contiguous()
+        fq = best['qap'].to(torch.int32)
+        failed = out['status'] == 2
+        res = {'perm': torch.where(failed[:, None], assign, out['perm']), 'qap': torch.where(failed, q, fq), 'faq_perm': out['perm'],
+               'faq_qap': fq, 'faq_nit': out['nit'], 'faq_status': out['status'], 'sinkhorn_err': err, 'faq_restart': best['restart']}
+        if seeds is not None:
+            res['seeded'] = out['seeded']
+        return res
     if seeds is None:
         out = qap.faq_weighted(x[0], x[1], nvalid, p0, None, faq['maxiter'], faq['tol'])
     else:
@@ -587,7 +631,7 @@ def _faq_launches(b1, b2, s, assign, q, nvalid, B, N, faq, seeds=None):
     fq = qap.objective_bits(b1, b2, out['perm'], nvalid, raw=True)[0]
     failed = out['status'] == 2
     res = {'perm': torch.where(failed[:, None], assign, out['perm']), 'qap': torch.where(failed, q, fq), 'faq_perm': out['perm'],
-           'faq_qap': fq, 'faq_nit': out['nit'], 'faq_status': out['status'], 'sinkhorn_err': err}
+           'faq_qap': fq, 'faq_nit': out['nit'], 'faq_status': out['status'], 'sinkhorn_err': err, 'faq_restart': None}
     if seeds is not None:
         res['seeded'] = out['seeded']
     return res
@@ -621,7 +665,7 @@ def _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, re
         planted = qap.objective_bits(b1, b2, labels, nvalid, raw=True)[0]
     perm = refined = None
     first = assign
-    stage = dict.fromkeys(('faq_perm', 'faq_qap', 'faq_nit', 'faq_status', 'sinkhorn_err'))
+    stage = dict.fromkeys(('faq_perm', 'faq_qap', 'faq_nit', 'faq_status', 'sinkhorn_err', 'faq_restart'))
     if faq is not None:
         stage = _faq_launches(b1, b2, scores, assign, q, nvalid, B, N, faq, seeds)
         perm, refined = stage.pop('perm'), stage.pop('qap')
@@ -738,6 +782,14 @@ def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, li
     int32 as the chain left them (faq_qap: the objective of faq_perm, -1 where it holds no matching) and 'sinkhorn_err' (B,) fp32
     (None with the barycenter); all None without faq.  With {'P0': 'barycenter'} and `assign` handed in the scores do not enter
     the stage's matching: the classical-baseline epoch.
+    The faq dict also takes qap.faq's restarts: 'restarts': R in [1, 64], 'seed', 'polish': True / False, and 'index', a (B,) integer
+    device tensor of pair indices (default: the position in the batch).  With R > 1 (or polish) the stage's start -- the Sinkhorn
+    matrix of the scores or the barycenter -- is the base of R starts per pair (fgnn_faq_restart_starts: restart 0 is that start,
+    the others its mean with a random doubly stochastic matrix drawn from (seed, index[b], k)), the chain runs once on the B R
+    problems, and fgnn_qap_best_of keeps each pair's best matching -- by qap.objective_bits, with polish by qap.two_opt_bits'
+    objective after the exchange search on all of them -- before the select; 'faq_perm', 'faq_qap', 'faq_nit', 'faq_status' are the
+    winner's and the dict gains 'faq_restart' (B,) int32, its k (None without restarts).  {'restarts': 1} issues the launches it
+    always did.  {'P0': 'randomized'} stays refused.
     seeds: None or a (B, N) integer tensor of known matches (qap.faq: seeds[b, i] = j fixes row i, -1 leaves it free;
     planted.reveal_seeds draws one from labels).  Seeds need the faq= stage and exclude refine > 0 (ValueError otherwise): with P0
     'scores' Sinkhorn runs on the free block of the scores (fgnn_seed_index, fgnn_seed_gather, n_b := u_b), the seeded chain

@@ -421,8 +421,156 @@ def faq_weighted(adj1, adj2, nv, p0=None, assign0=None, maxiter=30, tol=0.03, re
     return res
 
 
+def _check_restarts(who, restarts, seed):
+    if isinstance(restarts, bool) or not isinstance(restarts, (int, np.integer)) or not 1 <= restarts <= _lib.FGNN_RESTART_MAX_R:
+        raise ValueError("%s: 'restarts' must be an integer in [1, %d], got %r" % (who, _lib.FGNN_RESTART_MAX_R, restarts))
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
+        raise ValueError("%s: 'seed' must be an integer in [0, 2^64), got %r" % (who, seed))
+    return int(restarts), int(seed)
+
+
+def _check_pair_index(who, pair_index, B, dev):
+    """pair_index= -> (B,) int64 tensor on dev (None passes: the position in the batch)"""
+    if pair_index is None:
+        return None
+    if isinstance(pair_index, np.ndarray):
+        pair_index = torch.from_numpy(pair_index)
+    if (not torch.is_tensor(pair_index) or pair_index.is_floating_point() or pair_index.dtype == torch.bool or pair_index.is_complex()
+            or tuple(pair_index.shape) != (B,)):
+        raise ValueError('%s: pair_index must be a (%d,) integer tensor' % (who, B))
+    return pair_index.detach().to(device=dev, dtype=torch.int64).contiguous()
+
+
+def random_starts_device(base, n, pair_index, seed, B, N, R, device):
+    """fgnn_faq_restart_starts -> (B R, N, N) fp32 on `device`, pair-major; base (B, N, N) fp32 contiguous or None, n (B,) int32 or
+    None, pair_index (B,) int64 or None, all on `device`; never synchronises."""
+    starts = torch.empty(B * R, N, N, dtype=torch.float32, device=device)
+    _lib.call('fgnn_faq_restart_starts', _lib.ptr(base), _lib.ptr(n), _lib.ptr(pair_index), seed, B, N, R, _lib.ptr(starts),
+              _lib.stream_ptr())
+    return starts
+
+
+def random_starts(nvalid_or_B, N, restarts, seed=0, base=None, pair_index=None, device=None):
+    """R = `restarts` starts per pair for `faq` (``csrc/qap_restarts.hip``) -> (B, R, N, N).  Start 0 of pair b is `base`'s n_b x n_b
+    corner as it is, or the barycenter 1 / n_b; start k >= 1 is (base + K_k) / 2 with K_k = SciPy's ``_doubly_stochastic(U_k)`` --
+    SciPy's ``P0='randomized'`` start when base is the barycenter -- and U_k[i, j] = ((u32 >> 8) + 1) 2^-24, u32 raw draw
+    (k << 32) | (i << 16) | j of Philox pair stream 9 of pair p = pair_index[b] (b without) under `seed`.  So a start depends on
+    (seed, p, k, n_b, base) only, not on B, R or the padded N.  Zeros outside the corner; n_b = 0: zeros; n_b = 1: K = [[1]].
+    nvalid_or_B: a (B,) integer tensor of corner sides (clamped to [0, N]) or the integer B (every corner N x N); base: None or a
+    (B, N, N) float tensor; pair_index: None or a (B,) integer tensor; device: where the result goes (default: base's, else
+    nvalid's, else the CPU).  The device route is ONE launch, fp64 sums in a fixed order rounded to fp32 once, bit-identical from
+    run to run; it never synchronises.  The CPU and N > 256 take the same rule in numpy float64 and return float64."""
+    R, seed = _check_restarts('random_starts', restarts, seed)
+    if torch.is_tensor(nvalid_or_B):
+        nvalid = nvalid_or_B
+        if nvalid.dim() != 1 or nvalid.is_floating_point() or nvalid.dtype == torch.bool:
+            raise ValueError('random_starts: nvalid must be a (B,) integer tensor')
+        B = nvalid.shape[0]
+    else:
+        if isinstance(nvalid_or_B, bool) or not isinstance(nvalid_or_B, (int, np.integer)) or nvalid_or_B < 1:
+            raise ValueError('random_starts: expected a (B,) integer tensor of vertex counts or a batch size >= 1, got %r' % (nvalid_or_B,))
+        nvalid, B = None, int(nvalid_or_B)
+    if isinstance(N, bool) or not isinstance(N, (int, np.integer)) or N < 1 or B < 1:
+        raise ValueError('random_starts: empty batch (B = %r, N = %r)' % (B, N))
+    if base is not None and (not torch.is_tensor(base) or not base.is_floating_point() or tuple(base.shape) != (B, N, N)):
+        raise ValueError('random_starts: base must be a (%d, %d, %d) float tensor' % (B, N, N))
+    if device is None:
+        device = base.device if base is not None else nvalid.device if nvalid is not None else 'cpu'
+    device = torch.device(device)
+    pair_index = _check_pair_index('random_starts', pair_index, B, device)
+    if device.type != 'cuda' or N > _lib.FGNN_QAP_MAX_N:
+        sizes = _sizes(nvalid, B, N)
+        b64 = base.detach().cpu().double().numpy() if base is not None else None
+        pidx = pair_index.cpu().tolist() if pair_index is not None else list(range(B))
+        out = np.zeros((B, R, N, N))
+        for b, n in enumerate(sizes):
+            out[b, :, :n, :n] = _restart_starts_pair(seed, pidx[b], R, n, b64[b, :n, :n] if b64 is not None else None)
+        return torch.from_numpy(out).to(device)
+    if B * R > _lib.FGNN_RESTART_MAX_STARTS:
+        raise ValueError('random_starts: at most %d starts per call (got %d x %d)' % (_lib.FGNN_RESTART_MAX_STARTS, B, R))
+    with torch.cuda.device(device):
+        b32 = base.detach().to(device=device, dtype=torch.float32).contiguous() if base is not None else None
+        return random_starts_device(b32, _nv32(nvalid, device), pair_index, seed, B, N, R, device).view(B, R, N, N)
+
+
+def best_of_device(q, status, nit, perm, R, veto=None):
+    """fgnn_qap_best_of_i64 / _f32 on pair-major results of B R problems -- q (B R,) int64 or fp32, status, nit, veto (B R,) int32,
+    perm (B R, N) int32 -> {'perm' (B, N) int32, 'qap' (B,) as q, 'nit', 'status', 'restart' (B,) int32}; never synchronises."""
+    BR, N = perm.shape
+    B, dev = BR // R, perm.device
+    entry = 'fgnn_qap_best_of_f32' if q.dtype == torch.float32 else 'fgnn_qap_best_of_i64'
+    q, status, nit, perm = q.contiguous(), status.contiguous(), nit.contiguous(), perm.contiguous()
+    veto = veto.contiguous() if veto is not None else None
+    perm_o = torch.empty(B, N, dtype=torch.int32, device=dev)
+    q_o = torch.empty(B, dtype=q.dtype, device=dev)
+    o32 = torch.empty(3, B, dtype=torch.int32, device=dev)
+    _lib.call(entry, _lib.ptr(q), _lib.ptr(status), _lib.ptr(veto), _lib.ptr(nit), _lib.ptr(perm), B, N, R, _lib.ptr(perm_o),
+              _lib.ptr(q_o), _lib.ptr(o32[0]), _lib.ptr(o32[1]), _lib.ptr(o32[2]), _lib.stream_ptr())
+    return {'perm': perm_o, 'qap': q_o, 'nit': o32[0], 'status': o32[1], 'restart': o32[2]}
+
+
+def _faq_restarts(adj1, adj2, nvalid, labels, p0, maxiter, tol, weighted, seeds, R, seed, pair_index, polish, return_all):
+    """The restarted chain of `faq` on the device: the starts, the inputs R-fold, ONE chain on B R problems, their objectives, the
+    exchange search with polish, and the choice."""
+    B, N = adj1.shape[0], adj1.shape[-2]
+    dev = adj1.device
+    if B * R > _lib.FGNN_RESTART_MAX_STARTS:
+        raise ValueError('faq: at most %d starts per call (got %d pairs x %d restarts)' % (_lib.FGNN_RESTART_MAX_STARTS, B, R))
+
+    def rep(t):
+        return t.repeat_interleave(R, 0) if t is not None else None
+
+    with torch.cuda.device(dev):
+        if weighted:
+            nv, flag = _nv32(nvalid, dev), None
+            x1, x2 = weighted_views(adj1, adj2)[:2]
+            b1 = b2 = None
+        else:
+            b1, b2, nv, flag = _device_inputs(adj1, adj2, nvalid)
+            x = torch.empty(2, B, 2, N, N, dtype=torch.float32, device=dev)
+            for side, bits in enumerate((b1, b2)):
+                _lib.call('fgnn_expand_adjacency', _lib.ptr(bits), _lib.ptr(nv), B, N, _lib.ptr(x[side]), _lib.stream_ptr())
+            x1, x2 = x[0, :, 0], x[1, :, 0]
+            b1, b2 = rep(b1), rep(b2)
+        side, base = nv, p0
+        if seeds is not None:           # the starts live on the free block: its side, and the base gathered into free coordinates
+            ix = seed_index_device(seeds, nv)
+            side = torch.where(ix['valid'] != 0, ix['nfree'], torch.zeros_like(ix['nfree']))
+            base = seed_gather_device(p0, ix['free_a'], ix['free_b'], side) if p0 is not None else None
+        starts = random_starts_device(base, side, pair_index, seed, B, N, R, dev)
+        x1, x2, nvr, sdr = rep(x1), rep(x2), rep(nv), rep(seeds)
+        out = faq_weighted(x1, x2, nvr, starts, None, maxiter, tol, False, sdr, p0_free=seeds is not None)
+        perm, veto, extra = out['perm'], None, {}
+        if polish:
+            if weighted:
+                t = two_opt_weighted(x1, x2, perm, nvalid=nvr)
+            else:
+                t = two_opt_bits(b1, b2, perm, nvr, seeds=sdr)
+            perm, q, veto = t['perm'], t['qap'], t['status'].to(torch.int32)
+        elif weighted:
+            q = objective_weighted(x1, x2, perm, nvr)['qap']
+        else:
+            q = objective_bits(b1, b2, perm, nvr)['qap']
+        res = best_of_device(q, out['status'], out['nit'], perm, R, veto)
+        pick = res['restart'].to(torch.int64)[:, None]
+        if polish:
+            res['swaps'] = t['swaps'].view(B, R).gather(1, pick)[:, 0]
+            res['status_2opt'] = t['status'].view(B, R).gather(1, pick)[:, 0]
+        if seeds is not None:
+            res['seeded'] = out['seeded'].view(B, R)[:, 0]
+        if return_all:
+            st = out['status'].view(B, R).to(torch.int64)
+            dead = (st == 2) | (veto.view(B, R) == 2 if veto is not None else False)
+            extra = {'all_qap': torch.where(dead, torch.full_like(q.view(B, R), -1), q.view(B, R)), 'all_nit': out['nit'].view(B, R).to(torch.int64),
+                     'all_status': st, 'all_perm': perm.view(B, R, N)}
+        res['restart'] = res['restart'].to(torch.int64)
+        res = _finish_solver(res, res['qap'], labels, nv, flag)
+        res.update(extra)
+        return res
+
+
 def faq(adj1, adj2, nvalid=None, labels=None, P0='barycenter', maxiter=30, tol=0.03, weighted=False, return_P=False, seeds=None,
-        **options):
+        restarts=1, seed=0, pair_index=None, polish=False, return_all=False, **options):
     """The Fast Approximate QAP algorithm for every pair of the batch: SciPy's ``quadratic_assignment(A, B, method='faq',
     options={'maximize': True, 'P0': ..., 'maxiter': ..., 'tol': ...})`` -- Frank-Wolfe on f(P) = tr(A^T P B P^T) over the doubly
     stochastic matrices (each round: the gradient G = A P B^T + A^T P B, the assignment q that maximises <G, Q>, an exact line
@@ -456,7 +604,25 @@ def faq(adj1, adj2, nvalid=None, labels=None, P0='barycenter', maxiter=30, tol=0
     row; acc counts all rows; nit, status as above over the free block, and: a seed outside [0, n_b) or shared by two rows -- status
     2, perm -1, nit 0; a matching P0 against a seed -- status 2, perm = P0; u_b = 0 < n_b -- perm = seeds, nit 0, status 0.  With
     return_P, P is the last iterate IN FREE COORDINATES: the u_b x u_b corner of (B, N, N), rows / columns the ascending free ones.
-    seeds=None issues the launches and returns the keys it always did."""
+    seeds=None issues the launches and returns the keys it always did.
+
+    restarts = R in [1, 64] (the project's spelling of SciPy's randomized starts; ``P0='randomized'`` and ``rng=`` keep raising):
+    every pair is solved from the R starts of `random_starts` -- start 0 is P0 itself ('barycenter' or a (B, N, N) float matrix; a
+    (B, N) matching raises ValueError, as return_P with R > 1 does), start k >= 1 is (P0 + K_k) / 2 with K_k a random doubly
+    stochastic matrix drawn from (seed, pair_index[b], k) -- pair_index: a (B,) integer tensor, default the position in the batch --
+    and the best result is kept.  With seeds the starts live on the free block (side u_b; a matrix P0's free block is the base):
+    restart k >= 1 from the barycenter is SciPy's seeded randomized start.  The device route builds the starts with one launch
+    (fgnn_faq_restart_starts), replicates the inputs R-fold, runs the chain ONCE on the B R problems, takes the objective of every
+    matching, and fgnn_qap_best_of picks per pair, without a host read: among the restarts whose status is not 2 the largest
+    objective wins, a NaN never, ties go to the smallest k; without a candidate restart 0's results stand (status 2).  B R <= 65535.
+    The dict gains restart (B,) int64, the winner's k; perm, qap, nit, status, acc (and seeded) are the winner's.  return_all=True adds
+    all_qap, all_nit, all_status (B, R) and all_perm (B, R, N): every restart's results, restart k's being what ``faq(P0=starts[:, k])``
+    returns.  polish=True runs the exchange search on all B R matchings before the choice -- `two_opt` (seeded with seeds) on 0/1
+    pairs, `two_opt_weighted` on weighted ones -- and chooses by the polished objective; a restart whose search reports status 2 is
+    no candidate; perm and qap (and all_perm, all_qap) are the polished ones, nit and status the chain's, and the dict gains swaps and
+    status_2opt of the winner.  polish with weighted and seeds raises ValueError: `two_opt_weighted` takes no seeds.  The host route
+    (CPU, N > 256) is the same in numpy float64, per restart the SciPy call with that P0.  restarts=1 without polish and return_all
+    issues the launches and returns the keys it always did."""
     if options:
         raise ValueError('faq: unsupported option(s) %s -- seeds (partial_match), shuffle_input and rng are not implemented'
                          % ', '.join(sorted(options)))
@@ -468,7 +634,22 @@ def faq(adj1, adj2, nvalid=None, labels=None, P0='barycenter', maxiter=30, tol=0
     labels = labels_tensor(labels, B, N, adj1.device)
     p0, assign0 = _faq_start(P0, B, N, adj1.device)
     seeds = check_seeds('faq', seeds, B, N, adj1.device)
-    if (_on_host_weighted if weighted else _on_host)(adj1, N):
+    R, seed = _check_restarts('faq', restarts, seed)
+    pair_index = _check_pair_index('faq', pair_index, B, adj1.device)
+    if not isinstance(polish, bool) or not isinstance(return_all, bool):
+        raise ValueError("faq: 'polish' and 'return_all' are True or False, got %r, %r" % (polish, return_all))
+    on_host = (_on_host_weighted if weighted else _on_host)(adj1, N)
+    if R > 1 or polish or return_all:
+        if assign0 is not None:
+            raise ValueError("faq: with restarts, polish or return_all P0 is 'barycenter' or a (B, N, N) matrix -- a matching has no "
+                             'interior to perturb')
+        if return_P:
+            raise ValueError('faq: return_P goes with a single start (restarts=1, no polish, no return_all)')
+        if polish and weighted and seeds is not None:
+            raise ValueError('faq: polish=True with weighted=True and seeds is not supported -- two_opt_weighted takes no seeds')
+        route = _faq_restarts_host if on_host else _faq_restarts
+        return route(adj1, adj2, nvalid, labels, p0, int(maxiter), tol, weighted, seeds, R, seed, pair_index, polish, return_all)
+    if on_host:
         return _faq_host(adj1, adj2, nvalid, labels, p0, assign0, int(maxiter), tol, weighted, return_P, seeds)
     dev = adj1.device
     if weighted:
@@ -1184,6 +1365,119 @@ def _faq_host(adj1, adj2, nvalid, labels, p0, assign0, maxiter, tol, weighted, r
     res = {'perm': torch.from_numpy(perm), 'qap': torch.from_numpy(q), 'acc': t[0], 'nit': t[1], 'status': t[2]}
     if return_P:
         res['P'] = torch.from_numpy(Ps)
+    return res
+
+
+_PHILOX_M = (0xD2E7470EE14C6C93, 0xCA5A826395121157)
+_PHILOX_W = (0x9E3779B97F4A7C15, 0xBB67AE8584CAA73B)
+_MASK64 = (1 << 64) - 1
+
+
+def _mulhilo64(m, x):
+    """the constant m times a uint64 array -> (high, low) 64-bit halves, by 32-bit limbs"""
+    lo32, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    m0, m1 = np.uint64(m & 0xFFFFFFFF), np.uint64(m >> 32)
+    x0, x1 = x & lo32, x >> s32
+    p00, p01, p10, p11 = m0 * x0, m0 * x1, m1 * x0, m1 * x1
+    mid = (p00 >> s32) + (p01 & lo32) + (p10 & lo32)
+    return p11 + (p01 >> s32) + (p10 >> s32) + (mid >> s32), (mid << s32) | (p00 & lo32)
+
+
+def pair_stream_draws(seed, pair, stream, pos):
+    """The host twin of ``csrc/fgnn_philox.h``: raw 32-bit draws (int64) at the positions `pos` of pair stream `stream` of pair `pair`
+    -- word pos & 7 (low half first) of Philox4x64-10 at counter (pos >> 3, pair, stream, 0) under key (seed, 0)."""
+    pos = np.asarray(pos, dtype=np.uint64).reshape(-1)
+    c = [pos >> np.uint64(3), np.full_like(pos, int(pair) & _MASK64), np.full_like(pos, stream), np.zeros_like(pos)]
+    k0, k1 = int(seed) & _MASK64, 0
+    with np.errstate(over='ignore'):
+        for r in range(10):
+            if r:
+                k0, k1 = (k0 + _PHILOX_W[0]) & _MASK64, (k1 + _PHILOX_W[1]) & _MASK64
+            hi0, lo0 = _mulhilo64(_PHILOX_M[0], c[0])
+            hi1, lo1 = _mulhilo64(_PHILOX_M[1], c[2])
+            c = [hi1 ^ c[1] ^ np.uint64(k0), lo1, hi0 ^ c[3] ^ np.uint64(k1), lo0]
+    w = (pos & np.uint64(7)).astype(np.int64)
+    word = np.stack(c)[w >> 1, np.arange(len(pos))]
+    return ((word >> (np.uint64(32) * (w & 1).astype(np.uint64))) & np.uint64(0xFFFFFFFF)).astype(np.int64)
+
+
+def _doubly_stochastic(P, tol=1e-3):
+    """SciPy's _doubly_stochastic (scipy/optimize/_qap.py), operation for operation: Sinkhorn-Knopp in the linear domain; the first
+    test runs on the unscaled P"""
+    c = 1 / P.sum(axis=0)
+    r = 1 / (P @ c)
+    P_eps = P
+    for _ in range(1000):
+        if (np.abs(P_eps.sum(axis=1) - 1) < tol).all() and (np.abs(P_eps.sum(axis=0) - 1) < tol).all():
+            break
+        c = 1 / (r @ P)
+        r = 1 / (P @ c)
+        P_eps = r[:, None] * P * c
+    return P_eps
+
+
+def _restart_starts_pair(seed, p, R, n, base):
+    """the R starts of pair p on an n x n corner, numpy float64 (`random_starts` states the rule); base: (n, n) float64 or None"""
+    out = np.zeros((R, n, n))
+    if n == 0:
+        return out
+    J = base if base is not None else np.ones((n, n)) / n
+    out[0] = J
+    i, j = np.divmod(np.arange(n * n, dtype=np.int64), n)
+    for k in range(1, R):
+        u32 = pair_stream_draws(seed, p, _lib.FGNN_RESTART_STREAM, (k << 32) | (i << 16) | j)
+        U = (((u32 >> 8) + 1).astype(np.float64) * 2.0 ** -24).reshape(n, n)
+        out[k] = (J + (_doubly_stochastic(U) if n > 1 else np.ones((1, 1)))) / 2
+    return out
+
+
+def _best_of_host(q, status, veto=None):
+    """the rule of fgnn_qap_best_of on (B, R) numpy arrays -> (B,) winners"""
+    B, R = q.shape
+    win = np.zeros(B, dtype=np.int64)
+    for b in range(B):
+        best = -1
+        for k in range(R):
+            if status[b, k] == 2 or (veto is not None and veto[b, k] == 2) or q[b, k] != q[b, k]:
+                continue
+            if best < 0 or q[b, k] > q[b, best]:
+                best = k
+        win[b] = max(best, 0)
+    return win
+
+
+def _faq_restarts_host(adj1, adj2, nvalid, labels, p0, maxiter, tol, weighted, seeds, R, seed, pair_index, polish, return_all):
+    B, N = adj1.shape[0], adj1.shape[-2]
+    sizes = _sizes(nvalid, B, N)
+    pidx = pair_index.cpu().tolist() if pair_index is not None else list(range(B))
+    b64 = p0.detach().cpu().double().numpy() if p0 is not None else None
+    sds = seeds.detach().cpu().numpy().astype(np.int64) if seeds is not None else None
+    starts = np.zeros((B, R, N, N))                                 # in full coordinates, as _faq_host takes a matrix P0
+    for b, n in enumerate(sizes):
+        rows = cols = np.arange(n)
+        if sds is not None:
+            valid, rows, cols = _seed_lists(sds[b, :n], n)[:3]
+            if not valid:
+                continue
+        base = b64[b][np.ix_(rows, cols)] if b64 is not None else None
+        starts[b][:, rows[:, None], cols[None, :]] = _restart_starts_pair(seed, pidx[b], R, len(rows), base)
+    runs = [_faq_host(adj1, adj2, nvalid, labels, torch.from_numpy(starts[:, k]), None, maxiter, tol, weighted, False, seeds)
+            for k in range(R)]
+    veto = None
+    if polish:
+        ms = _check_max_swaps(None)
+        for k, run in enumerate(runs):
+            t = (_two_opt_host_w(adj1, adj2, run['perm'], nvalid, labels, ms) if weighted
+                 else _two_opt_host(adj1, adj2, run['perm'], nvalid, labels, ms, seeds))
+            runs[k] = dict(run, perm=t['perm'], qap=t['qap'], acc=t['acc'], swaps=t['swaps'], status_2opt=t['status'])
+        veto = np.stack([run['status_2opt'].numpy() for run in runs], 1)
+    allr = {key: torch.stack([run[key] for run in runs], 1) for key in runs[0]}
+    win = torch.from_numpy(_best_of_host(allr['qap'].numpy(), allr['status'].numpy(), veto))
+    res = {key: (v.gather(1, win[:, None, None].expand(B, 1, N))[:, 0] if v.dim() == 3 else v.gather(1, win[:, None])[:, 0])
+           for key, v in allr.items()}
+    res['restart'] = win
+    if return_all:
+        res.update({'all_qap': allr['qap'], 'all_nit': allr['nit'], 'all_status': allr['status'], 'all_perm': allr['perm']})
     return res
 
 

@@ -162,7 +162,10 @@ class Siamese_Node_Exp(nn.Module):
         as the start, the chain of qap.faq, and where that chain reports status 2 the stage keeps assign.  The dict gains perm (the
         stage's matching, until a later stage replaces it), qap_faq and acc_faq (int64: its objective in the unit of qap, its rows
         that meet the labels or the identity), faq_perm, faq_nit, faq_status (as the chain left them) and sinkhorn_err (None with the
-        barycenter).  0/1 batches only: with weighted=True it is refused.
+        barycenter).  0/1 batches only: with weighted=True it is refused.  With {'restarts': R, 'seed': ..} (and 'polish', 'index':
+        qap.faq's random restarts, as evaluation.decode_scores takes them) the chain runs from R starts per pair -- the stage's own
+        start and R - 1 perturbations of it -- and the best matching is kept on the device; the pair index is the position in the
+        batch unless 'index' says otherwise.  The dict gains faq_restart ((bs,) int32, the winner's restart; None without restarts).
 
         seeds (None or a (bs, n) integer tensor of known matches: seeds[b, i] = j fixes vertex i of x1 to vertex j of x2, -1 leaves
         it free; wider rows are cut to n like labels; planted.reveal_seeds draws one): the anchors of seeded graph matching.  They
@@ -235,7 +238,8 @@ class Siamese_Node_Exp(nn.Module):
                     out['seeds'], out['nseeds'] = seeds, st['seeded'] if nseeds is None else nseeds
                 out.update({'perm': st['perm'], 'qap_faq': st['qap'].to(torch.int64),
                             'acc_faq': count_matches(st['perm'], target, nv).to(torch.int64), 'faq_perm': st['faq_perm'],
-                            'faq_nit': st['faq_nit'], 'faq_status': st['faq_status'], 'sinkhorn_err': st['sinkhorn_err']})
+                            'faq_nit': st['faq_nit'], 'faq_status': st['faq_status'], 'sinkhorn_err': st['sinkhorn_err'],
+                            'faq_restart': st['faq_restart']})
             if refine:
                 out.update(qap.greedy_bits(b1, b2, out.get('perm', assign), int(refine), nv, labels))
             if two_opt:

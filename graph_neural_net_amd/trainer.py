@@ -740,7 +740,11 @@ class FgnnTrainer:
             decode['seeds'] = seeds
         if seed_meter is not None:
             decode['seed_meter'] = seed_meter
+        # restarts draw from (seed, pair index, k): hand the step's dataset indices over, so the record does not depend on the batching
+        restart_index = isinstance(faq, dict) and faq.get('restarts', 1) != 1 and faq.get('index') is None
         for live, bins, bits_kw in batches:
+            if restart_index:
+                decode['faq'] = dict(faq, index=bits_kw['index'])
             if reveal is not None and not bits_kw.get('permute'):
                 raise ValueError('FgnnTrainer: an integer seeds= reveals rows of the planted labels; it needs permute=True')
             b1, b2, nv, *labels = generator.bits(**bits_kw)

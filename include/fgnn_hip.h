@@ -1326,6 +1326,39 @@ int fgnn_seed_fold_bins(const int *seeds /* optional */, const int *assign, cons
                         const int *labels /* optional */, const int *nvalid /* optional */, int B, int N, int live,
                         const int *bin /* (B) */, int K, fgnn_seed_record *records /* K records */, void *stream);
 
+/* ---- random restarts for the FAQ chain (csrc/qap_restarts.hip): R starts per pair, and the best of R results ---------------------
+ * fgnn_faq_restart_starts writes starts (B R, N, N) fp32, pair-major (start b R + k is restart k of pair b), in ONE launch with one
+ * workgroup per start.  base: (B, N, N) fp32 contiguous, or NULL for the barycenter 1 / n_b; n (optional, int32[B]): the side of
+ * pair b's live corner, clamped to [0, N] -- nvalid, or with seeds nfree of fgnn_seed_index and base in free coordinates (what
+ * fgnn_qapw_faq_seeded takes with p0_free); pair_index (optional, int64[B]): the pair's index p, b without.  Per (b, k):
+ *   k = 0   base's corner bit for bit, or (float)(1.0 / n_b);
+ *   k >= 1  (base + K_k) / 2, K_k = SciPy's _doubly_stochastic(U_k) (scipy/optimize/_qap.py; its randomized start when base is
+ *           the barycenter): c = 1 / colsum(U), r = 1 / (U c), then c = 1 / (r U), r = 1 / (U c) until every row and column sum of
+ *           r_i U_ij c_j lies within 1e-3 of 1, at most 1000 times; SciPy's first test runs on the unscaled U (then K = U): kept.
+ *           U_k[i][j] = ((u32 >> 8) + 1) 2^-24, in (0, 1] and exact in fp32, u32 = raw draw t = (k << 32) | (i << 16) | j of pair
+ *           stream FGNN_RESTART_STREAM of pair p under `seed` (the pair streams of fgnn_pairgen).  n_b = 1: K = [[1]].
+ * Sums, r and c are fp64 in an order fixed by n_b alone; the start is rounded to fp32 once.  A start is a function of (seed, p, k,
+ * n_b, base's corner) only -- not of B, R or N -- and bit-identical from run to run.  Outside the corner: exact zeros; n_b = 0: all
+ * zeros.  Nothing outside base's corner is read.  U stays in the output buffer and two fp64 N-vectors (with two sums' worth more)
+ * in LDS: there is no LDS-resident form and hence no size threshold.  N <= FGNN_QAP_MAX_N, 1 <= R <= FGNN_RESTART_MAX_R, B R <=
+ * FGNN_RESTART_MAX_STARTS (the pairs of one fgnn_qapw_faq call).
+ *
+ * fgnn_qap_best_of_i64 / fgnn_qap_best_of_f32 (int64 objectives of 0/1 graphs, fp32 of weighted ones): qap, status, nit (B R) and
+ * perm (B R, N) int32, pair-major as above; veto (optional, int32[B R]): a second status.  Per pair, the CANDIDATES are the
+ * restarts k with status != 2, veto != 2 and an objective that is no NaN; the largest objective wins, ties go to the smallest k;
+ * without a candidate restart 0 stands in.  perm_out (B, N), qap_out, nit_out, status_out (B) are the winner's entries copied as
+ * they are, restart_out (B) int32 its k.  One wave per pair.
+ * All three are single launches on `stream`: capturable, no workspace, no allocation, no host copy, no synchronisation. */
+#define FGNN_RESTART_STREAM 9
+#define FGNN_RESTART_MAX_R 64
+#define FGNN_RESTART_MAX_STARTS 65535
+int fgnn_faq_restart_starts(const float *base /* optional */, const int *n /* optional */, const long long *pair_index /* optional */,
+                            unsigned long long seed, int B, int N, int R, float *starts, void *stream);
+int fgnn_qap_best_of_i64(const long long *qap, const int *status, const int *veto /* optional */, const int *nit, const int *perm, int B,
+                         int N, int R, int *perm_out, long long *qap_out, int *nit_out, int *status_out, int *restart_out, void *stream);
+int fgnn_qap_best_of_f32(const float *qap, const int *status, const int *veto /* optional */, const int *nit, const int *perm, int B, int N,
+                         int R, int *perm_out, float *qap_out, int *nit_out, int *status_out, int *restart_out, void *stream);
+
 /* ---- test-only entry points (never on the product path; tests/ and tools/ call them) ---------------------------------------
  * fgnn_debug_mlp_fwd_masks / fgnn_debug_mlp_fwd_x3_masks: fgnn_mlp_fwd / fgnn_mlp_fwd_x3 once more -- the same tile code, the same
  * outputs, bit for bit -- that ALSO exports the ReLU decisions of the conv chain (models/layers.py:129-130), the input of the
