@@ -182,6 +182,12 @@ class QapRecord(C.Structure):         # fgnn_qap_record (csrc/qap_fold.hip); liv
         'unmatched', 'nodes', 'pairs', 'steps')]
 
 
+class QapwRecord(C.Structure):        # fgnn_qapw_record (csrc/qap_fold_weighted.hip); lives in device memory, this mirror gives the offsets
+    _fields_ = [(name, C.c_double) for name in ('ratio_sum', 'qap_sum', 'planted_sum', 'refined_sum')] + [
+        (name, C.c_longlong) for name in ('ratio_pairs', 'correct', 'refined_correct', 'recovered', 'exact', 'improved', 'unmatched',
+                                          'nodes', 'pairs', 'steps')]
+
+
 class SeedRecord(C.Structure):        # fgnn_seed_record (csrc/seed_select.hip); lives in device memory, this mirror gives the offsets
     _fields_ = [(name, C.c_longlong) for name in (
         'seeds', 'seed_correct', 'free_nodes', 'free_correct', 'free_refined_correct', 'clean_pairs', 'exact_free', 'nodes', 'pairs',
@@ -314,6 +320,7 @@ _SIGNATURES = {
     'fgnn_greedy_qapw_labels': [_VP, _VP, _LL, _I, _VP, _VP, _VP, _I, _I, _I, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
     'fgnn_qapw_2opt_ws_bytes': [_I, _I],
     'fgnn_qapw_2opt': [_VP, _VP, _LL, _I, _VP, _VP, _I, _I, _I, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
+    'fgnn_qapw_2opt_seeded': [_VP, _VP, _LL, _I, _VP, _VP, _VP, _I, _I, _I, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
     'fgnn_qapw_faq_ws_bytes': [_I, _I],
     'fgnn_qapw_faq': [_VP, _VP, _LL, _I, _VP, _VP, _VP, _I, _I, _I, _F, _VP, _LL, _VP, _VP, _VP, _VP, _VP],
     'fgnn_sinkhorn': [_VP, _LL, _I, _VP, _I, _I, _F, _I, _VP, _VP, _VP, _VP],
@@ -339,6 +346,8 @@ _SIGNATURES = {
     'fgnn_rank_fold': [_VP, _VP, _I, _I, _I, C.POINTER(C.c_int), _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP],
     'fgnn_qap_fold': [_VP] * 7 + [_I, _I, _I] + [_VP] * 5,
     'fgnn_qap_fold_bins': [_VP] * 7 + [_I, _I, _I, _VP, _I] + [_VP] * 5,
+    'fgnn_qapw_fold': [_VP] * 7 + [_I, _I, _I] + [_VP] * 5,
+    'fgnn_qapw_fold_bins': [_VP] * 7 + [_I, _I, _I, _VP, _I] + [_VP] * 5,
     'fgnn_confident_seeds': [_VP, _LL, _I, _VP, _I, _I, _I, _F, _VP, _VP, _VP, _VP],
     'fgnn_seed_fold': [_VP] * 5 + [_I, _I, _I, _VP, _VP],
     'fgnn_seed_fold_bins': [_VP] * 5 + [_I, _I, _I, _VP, _I, _VP, _VP],

@@ -19,8 +19,9 @@ rank_meter=)`` issues them after its own four, on the same scores, labels, ``liv
 optionally the greedy refinement and, with ``two_opt=True``, the pairwise-exchange search after it (csrc/qap_2opt.hip), and
 fgnn_qap_fold (csrc/qap_fold.hip) into a ``QapMeter`` or, with ``bins=``, a ``BinnedQapMeter``; ``evaluate_scores(..., qap_meter=,
 bits=, refine=, two_opt=)`` issues it after its own launches on the assignment its solver launch wrote.  0/1 graphs only; the
-real-weighted decode stays per batch.  ``faq=`` puts the Fast Approximate QAP chain (csrc/qap_faq.hip) between the Hungarian
-matching and the refinement, started from the Sinkhorn projection of the scores (csrc/sinkhorn.hip) or from the barycenter.
+real-weighted decode is ``decode_scores_weighted`` (a ``WeightedQapMeter``).  ``faq=`` puts the Fast Approximate QAP chain
+(csrc/qap_faq.hip) between the Hungarian matching and the refinement, started from the Sinkhorn projection of the scores
+(csrc/sinkhorn.hip) or from the barycenter.
 
 ``seeds=`` of the decode takes known matches -- a tensor, or a spec that draws them from the scores themselves (csrc/seed_select.hip:
 fgnn_confident_seeds) -- and ``seed_meter=`` a ``SeedMeter`` / ``BinnedSeedMeter`` that says what the seeds were worth.
@@ -37,18 +38,19 @@ from .masked import MaskedTensor
 from .metrics import labels_tensor
 
 
-def pack_records(buf, K, words):
+def pack_records(buf, K, words, head=1):
     """The bytes of K records of `words` 8-byte words each (a uint8 tensor on any device) -> the (K, words) fp64 tensor of their
-    all-reduce: word 0, an fp64 sum, as it is, the int64 counts converted (exact below 2^53).  A pure function of tensors."""
-    counts = buf.view(torch.int64).view(K, words)[:, 1:]
-    return torch.cat([buf.view(torch.float64).view(K, words)[:, :1], counts.to(torch.float64)], dim=1).contiguous()
+    all-reduce: the first `head` words, fp64 sums (one, word 0, in every record but fgnn_qapw_record, which has four), as they are,
+    the int64 counts converted (exact below 2^53).  A pure function of tensors."""
+    counts = buf.view(torch.int64).view(K, words)[:, head:]
+    return torch.cat([buf.view(torch.float64).view(K, words)[:, :head], counts.to(torch.float64)], dim=1).contiguous()
 
 
-def unpack_records_(buf, K, t):
+def unpack_records_(buf, K, t, head=1):
     """The inverse of pack_records: writes the (K, words) fp64 tensor t into the records' bytes, in place."""
     words = t.shape[1]
-    buf.view(torch.float64).view(K, words)[:, :1].copy_(t[:, :1])
-    buf.view(torch.int64).view(K, words)[:, 1:].copy_(t[:, 1:].round().to(torch.int64))
+    buf.view(torch.float64).view(K, words)[:, :head].copy_(t[:, :head])
+    buf.view(torch.int64).view(K, words)[:, head:].copy_(t[:, head:].round().to(torch.int64))
     return buf
 
 
@@ -71,6 +73,7 @@ class _Records:
     `_dict` (a ctypes record -> a dict of Python numbers) and `_result` (that dict -> the epoch's figures)."""
     RECORD, FIELDS, NOUN = None, (), 'record lives'
     HEAD_FP64 = True            # word 0 is an fp64 sum (False: every word is an int64 count)
+    HEAD_WORDS = 1              # with HEAD_FP64: how many leading words are fp64 sums
 
     def _open(self, device, K=1, buf=None):
         """The device refusal, then K zeroed records -- or `buf`, the bytes of one record of a binned meter.  -> the device"""
@@ -80,7 +83,8 @@ class _Records:
         self.buf = torch.zeros(K * ctypes.sizeof(self.RECORD), dtype=torch.uint8, device=device) if buf is None else buf
         for j, name in enumerate(self.FIELDS):              # (a binned meter has none: its records' fields are its meters')
             off = getattr(self.RECORD, name).offset
-            setattr(self, name, self.buf[off:off + 8].view(torch.float64 if j == 0 and self.HEAD_FP64 else torch.int64).reshape(()))
+            fp64 = self.HEAD_FP64 and j < self.HEAD_WORDS
+            setattr(self, name, self.buf[off:off + 8].view(torch.float64 if fp64 else torch.int64).reshape(()))
         return device
 
     def reset(self):
@@ -104,9 +108,9 @@ class _Records:
             dp.allreduce_sum_(t)
             self.buf.view(torch.int64).copy_(t.round().to(torch.int64))
             return self
-        t = pack_records(self.buf, K, words)
+        t = pack_records(self.buf, K, words, self.HEAD_WORDS)
         dp.allreduce_sum_(t)
-        unpack_records_(self.buf, K, t)
+        unpack_records_(self.buf, K, t, self.HEAD_WORDS)
         return self
 
 
@@ -292,8 +296,8 @@ def qap_result(rec):
 class QapMeter(_Records):
     """The device record of a decode epoch (fgnn_qap_record, include/fgnn_hip.h): the reference's all_acc_qap(val_loader, ...) and
     all_greedy_losses_acc (toolbox/metrics.py:168-223) over a whole loader, for 0/1 graphs on the bit-word path (the real-weighted
-    decode, qap.py's weighted=True, stays per batch).  Every field of the record is a 0-dim view of it (`ratio_sum` fp64, the
-    others int64); `acc`, `qap_ratio`, `mean_ratio`, `refined_acc`, `refined_qap_ratio` are 0-dim fp64 device tensors formed from
+    decode, qap.py's weighted=True, has its own meter, WeightedQapMeter).  Every field of the record is a 0-dim view of it
+    (`ratio_sum` fp64, the others int64); `acc`, `qap_ratio`, `mean_ratio`, `refined_acc`, `refined_qap_ratio` are 0-dim fp64 device tensors formed from
     them on the device.  `refined` (host) says whether a refinement was folded since the last reset; `record()` carries it and
     `result()` (qap_result) is the only host synchronisation."""
     RECORD, FIELDS = _lib.QapRecord, tuple(name for name, _ in _lib.QapRecord._fields_)
@@ -356,6 +360,54 @@ class BinnedQapMeter(_BinnedRecords):
         for m in self.meters:
             m.refined = False
         return super().reset()
+
+    def _mark_refined(self):
+        for m in self.meters:
+            m.refined = True
+
+
+class WeightedQapMeter(_Records):
+    """The device record of a decode epoch on REAL-weighted pairs (fgnn_qapw_record, include/fgnn_hip.h; csrc/qap_fold_weighted.hip):
+    what QapMeter is for 0/1 graphs, over the fp32 objectives of csrc/qap_weighted.hip.  `ratio_sum`, `qap_sum`, `planted_sum`,
+    `refined_sum` are 0-dim fp64 views of the record, the ten counts int64; `unmatched` counts the pairs whose matching leaves the
+    corner (a weighted objective may be negative, so its sign marks nothing).  The derived tensors, `refined`, `record()` and
+    `result()` (qap_result: the same keys) are QapMeter's.  A class of its own: decode_scores refuses it, decode_scores_weighted
+    refuses a QapMeter."""
+    RECORD, FIELDS, HEAD_WORDS = _lib.QapwRecord, tuple(name for name, _ in _lib.QapwRecord._fields_), 4
+    _result = staticmethod(qap_result)
+
+    def __init__(self, device, buf=None):
+        """buf: the record's bytes when they belong to a larger buffer (a record of a BinnedWeightedQapMeter)"""
+        self.refined = False
+        self._open(device, buf=buf)
+
+    def reset(self):
+        self.refined = False
+        return _Records.reset(self)
+
+    def _mark_refined(self):
+        self.refined = True
+
+    _dict, _over = QapMeter._dict, QapMeter._over
+    acc, qap_ratio, mean_ratio = QapMeter.acc, QapMeter.qap_ratio, QapMeter.mean_ratio
+    refined_acc, refined_qap_ratio = QapMeter.refined_acc, QapMeter.refined_qap_ratio
+
+
+class BinnedWeightedQapMeter(_BinnedRecords):
+    """K weighted decode records, one per bin: `meter[k]` is a WeightedQapMeter; see _BinnedRecords."""
+    PLAIN, RECORD, HEAD_WORDS = WeightedQapMeter, _lib.QapwRecord, 4
+
+    def __init__(self, device, K, values=None):
+        self._open_bins(device, self._check_bins(K, values), values)
+
+    @property
+    def refined(self):
+        return self.meters[0].refined
+
+    def reset(self):
+        for m in self.meters:
+            m.refined = False
+        return _Records.reset(self)
 
     def _mark_refined(self):
         for m in self.meters:
@@ -757,7 +809,8 @@ def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, li
     """The reference's all_acc_qap / all_greedy_losses_acc (toolbox/metrics.py:168-223) of a batch, added to an epoch record.
     scores, nvalid, labels, live, bins: as evaluate_scores takes them, with the same refusals; bits1, bits2: the two graphs as
     (B, N, ceil(N/32)) int32 bit words on the scores' device (PairGenerator.bits, synthetic.pack_adjacency).  0/1 graphs only: the
-    real-weighted decode (qap.all_acc_qap / greedy_qap with weighted=True, fp32 objectives) stays per batch and has no record.
+    real-weighted decode (qap.all_acc_qap / greedy_qap with weighted=True, fp32 objectives) is decode_scores_weighted, with a
+    WeightedQapMeter.
     The chain: the Hungarian matching of the scores (metrics.lsap_device, the route of qap.all_acc_qap) unless `assign`, a (B, N)
     int32 device tensor of matched columns, is handed in; qap.objective_bits for qap and planted, once more on the labels when
     there are any (planted is then the objective of the labels' matching); with refine = T > 0 the T rounds of qap.greedy_bits
@@ -829,6 +882,173 @@ def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, li
             from .metrics import lsap_device
             assign = lsap_device(s, nvalid, want_assign=True)[1]
         return _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt, faq, s, seeds, seed_meter)
+
+
+def _faq_launches_weighted(x1, x2, s, assign, q, nvalid, B, N, faq, seeds=None):
+    """The FAQ stage of the weighted decode: the twin of _faq_launches on the fp32 views of qap.weighted_views -- no
+    fgnn_expand_adjacency, qap.faq_weighted directly on the views, qap.objective_weighted for the objectives (fp32), with polish
+    the exchange search of qap.two_opt_weighted_device (seeded with seeds) on all B R matchings, fgnn_qap_best_of_f32 for the
+    choice.  -> the keys of _faq_launches, 'qap' and 'faq_qap' float32"""
+    from . import qap
+    dev = x1.device
+    R = faq['restarts']
+    restarted = R > 1 or faq['polish']
+    if restarted and B * R > _lib.FGNN_RESTART_MAX_STARTS:
+        raise ValueError('decode: at most %d starts per call (got %d pairs x %d restarts)' % (_lib.FGNN_RESTART_MAX_STARTS, B, R))
+    if faq['index'] is not None and tuple(faq['index'].shape) != (B,):
+        raise ValueError("decode: faq['index'] must hold %d pair indices, got %s" % (B, tuple(faq['index'].shape)))
+    p0 = err = u = None
+    if seeds is not None and (restarted or faq['P0'] == 'scores'):
+        ix = qap.seed_index_device(seeds, nvalid)
+        u = torch.where(ix['valid'] != 0, ix['nfree'], torch.zeros_like(ix['nfree']))
+    if faq['P0'] == 'scores':
+        if seeds is None:
+            sk = qap.sinkhorn_device(s, nvalid, faq['tau'], faq['iters'])
+        else:
+            sk = qap.sinkhorn_device(qap.seed_gather_device(s, ix['free_a'], ix['free_b'], u), u, faq['tau'], faq['iters'])
+        p0, err = sk['P'], sk['err']
+    restart = None
+    if restarted:
+        def rep(t):
+            return t.repeat_interleave(R, 0) if t is not None else None
+        index = faq['index'].to(torch.int64).contiguous() if faq['index'] is not None else None
+        starts = qap.random_starts_device(p0, nvalid if seeds is None else u, index, faq['seed'], B, N, R, dev)
+        x1r, x2r, nvr, sdr = rep(x1), rep(x2), rep(nvalid), rep(seeds)
+        run = qap.faq_weighted(x1r, x2r, nvr, starts, None, faq['maxiter'], faq['tol'], seeds=sdr, p0_free=seeds is not None)
+        if faq['polish']:
+            t = qap.two_opt_weighted_device(x1r, x2r, N * N, N, run['perm'], nvr, -1, sdr)
+            perms, veto = t['perm'], t['status']
+        else:
+            perms, veto = run['perm'], None
+        best = qap.best_of_device(qap.objective_weighted(x1r, x2r, perms, nvr)['qap'], run['status'], run['nit'], perms, R, veto)
+        out = {'perm': best['perm'], 'nit': best['nit'], 'status': best['status']}
+        if seeds is not None:
+            out['seeded'] = run['seeded'].view(B, R)[:, 0].contiguous()
+        fq, restart = best['qap'], best['restart']
+    else:
+        out = qap.faq_weighted(x1, x2, nvalid, p0, None, faq['maxiter'], faq['tol'], seeds=seeds, p0_free=seeds is not None)
+        fq = qap.objective_weighted(x1, x2, out['perm'], nvalid)['qap']
+    failed = out['status'] == 2
+    res = {'perm': torch.where(failed[:, None], assign, out['perm']), 'qap': torch.where(failed, q, fq), 'faq_perm': out['perm'],
+           'faq_qap': fq, 'faq_nit': out['nit'], 'faq_status': out['status'], 'sinkhorn_err': err, 'faq_restart': restart}
+    if seeds is not None:
+        res['seeded'] = out['seeded']
+    return res
+
+
+def _decode_launches_weighted(x1, x2, gs, ld, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt=False, faq=None,
+                              scores=None, seeds=None, seed_meter=None):
+    """The chain of _decode_launches on the fp32 views of qap.weighted_views: qap.objective_weighted (once more on the labels),
+    fgnn_confident_seeds when seeds is a spec, _faq_launches_weighted, qap.greedy_weighted, qap.two_opt_weighted_device and a fresh
+    objective of its perm, then fgnn_qapw_fold(_bins) and, with a seed_meter, fgnn_seed_fold(_bins) -- which reads integer matchings
+    only and is reused as it is.  meter None: no fold (Siamese_Node_Exp.match_weighted).  -> the dict of decode_scores_weighted"""
+    from . import qap
+    dev = x1.device
+    nseeds = None
+    if isinstance(seeds, dict):
+        picked = qap.confident_seeds_device(scores, nvalid, seeds['count'], seeds['min_margin'])
+        seeds, nseeds = picked['seeds'], picked['nseeds']
+    obj = qap.objective_weighted(x1, x2, assign, nvalid)
+    q, planted = obj['qap'], obj['planted']
+    if labels is not None:
+        planted = qap.objective_weighted(x1, x2, labels, nvalid)['qap']
+    perm = refined = None
+    first = assign
+    mark = meter._mark_refined if meter is not None else (lambda: None)
+    stage = dict.fromkeys(('faq_perm', 'faq_qap', 'faq_nit', 'faq_status', 'sinkhorn_err', 'faq_restart'))
+    if faq is not None:
+        stage = _faq_launches_weighted(x1, x2, scores, assign, q, nvalid, B, N, faq, seeds)
+        perm, refined = stage.pop('perm'), stage.pop('qap')
+        first = perm
+        mark()
+    greedy = None
+    if refine > 0:
+        greedy = qap.greedy_weighted(x1, x2, assign if perm is None else perm, refine, nvalid, labels)
+        perm, refined = greedy['perm'], greedy['s_best'] * 2       # (an exact doubling: trace(A P B P^T), the unit of qap)
+        mark()
+    swaps = status = nit = None
+    if two_opt:
+        t = qap.two_opt_weighted_device(x1, x2, gs, ld, assign if perm is None else perm, nvalid, -1, seeds)
+        perm, swaps, status, nit = t['perm'], t['swaps'], t['status'], t['nit']
+        refined = qap.objective_weighted(x1, x2, perm, nvalid)['qap']
+        mark()
+    correct = refined_correct = ratio = None
+    if meter is not None:
+        words = torch.zeros(2 * B, dtype=torch.int64, device=dev)
+        ratio, ints = words[:B].view(torch.float64), words[B:].view(torch.int32)
+        correct, refined_correct = ints[:B], ints[B:]
+        pairs = (_lib.ptr(assign), _lib.ptr(perm), _lib.ptr(labels), _lib.ptr(q), _lib.ptr(planted), _lib.ptr(refined),
+                 _lib.ptr(nvalid), B, N, live)
+        outs = (_lib.ptr(correct), _lib.ptr(refined_correct), _lib.ptr(ratio), _lib.ptr(meter.buf), _lib.stream_ptr())
+        if bins is None:
+            _lib.call('fgnn_qapw_fold', *pairs, *outs)
+        else:
+            _lib.call('fgnn_qapw_fold_bins', *pairs, _lib.ptr(bins), meter.K, *outs)
+    if seed_meter is not None:
+        seed_fold(seed_meter, seeds, first, perm, nvalid, labels, bins, B, N, live)
+        stage['seed_meter'] = seed_meter
+    if seeds is not None:
+        stage['seeds'], stage['nseeds'] = seeds, stage['seeded'] if nseeds is None else nseeds
+    return {'assign': assign, 'qap': q, 'planted': planted, 'correct': correct, 'ratio': ratio, 'perm': perm, 'refined': refined,
+            'refined_correct': None if perm is None else refined_correct, 'meter': meter, 'swaps': swaps, 'status': status,
+            'nit': nit, 'greedy': greedy, **stage}
+
+
+def _weighted_args(who, adj1, adj2, B, N, dev):
+    """adj1, adj2 of the weighted decode -> (x1, x2, gstride, ld) of qap.weighted_views, checked against the scores' (B, N) and
+    device"""
+    from . import qap
+    for a in (adj1, adj2):
+        if not torch.is_tensor(a) or a.device != dev or a.dim() not in (3, 4) or a.shape[0] != B or tuple(a.shape[-2:]) != (N, N):
+            raise ValueError('%s: the graphs are (%d, %d, %d) or (%d, C, %d, %d) float tensors on %s, got %s'
+                             % (who, B, N, N, B, N, N, dev, (tuple(a.shape), a.device) if torch.is_tensor(a) else type(a).__name__))
+    if N > _lib.FGNN_QAPW_MAX_N:
+        raise RuntimeError('%s: at most %d vertices per graph (got %d)' % (who, _lib.FGNN_QAPW_MAX_N, N))
+    return qap.weighted_views(adj1, adj2)
+
+
+def decode_scores_weighted(scores, adj1, adj2, nvalid=None, labels=None, meter=None, live=None, bins=None, refine=0, assign=None,
+                           two_opt=False, faq=None, seeds=None, seed_meter=None):
+    """`decode_scores` on REAL-weighted pairs: the same chain, arguments, rules and messages, on what qap.weighted_views takes --
+    adj1, adj2 are (B, N, N) float matrices or (B, C, N, N) batches on the scores' device whose channel 0 is used in place (a
+    spectral L of PairGenerator.spectral, any weighted graph).  No representation check, no host read: capturable.
+    The chain: metrics.lsap_device unless `assign` is handed in; qap.objective_weighted for qap and planted, once more on the labels
+    when there are any; with faq the stage of decode_scores on fp32 -- Sinkhorn on the scores (on their free block with seeds),
+    qap.faq_weighted directly on the views, restarts through fgnn_faq_restart_starts, qap.objective_weighted, fgnn_qap_best_of_f32,
+    with 'polish' the exchange search fgnn_qapw_2opt (fgnn_qapw_2opt_seeded with seeds) on every restart, and the select on status
+    2; with refine = T > 0 qap.greedy_weighted, refined = 2 s_best, an exact doubling, the unit of qap; with two_opt=True
+    fgnn_qapw_2opt (seeded with seeds) from the last matching, refined = the fresh qap.objective_weighted of its perm; then
+    fgnn_qapw_fold(_bins) into `meter` (a WeightedQapMeter; with bins= a BinnedWeightedQapMeter; None: a fresh WeightedQapMeter) and,
+    with a seed_meter, fgnn_seed_fold(_bins), which reads integer matchings only.  Seeds need faq= and exclude refine > 0; seed
+    specs ('scores', a dict) are accepted.
+    Returns decode_scores' keys with 'qap', 'planted', 'refined', 'faq_qap' as float32 (plus 'nit', (B,) int64 of the exchange
+    search, and 'greedy', the dict of qap.greedy_weighted; None without).  A pair whose `assign` leaves its corner has the
+    sentinel qap = -1 of fgnn_qapw_objective and counts as unmatched in the fold.  Nothing is read back."""
+    who = 'decode_scores_weighted'
+    if meter is None and bins is not None:
+        raise ValueError('%s: bins= and a BinnedWeightedQapMeter as meter go together' % who)
+    refine = _check_refine(who, refine)
+    two_opt = _check_two_opt(who, two_opt)
+    faq = _check_faq(who, faq)
+    s, nvalid, labels, bins, B, N, live = _score_args(who, scores, nvalid, labels, live, bins)
+    dev = s.device
+    views = _weighted_args(who, adj1, adj2, B, N, dev)
+    seeds = _check_decode_seeds(who, seeds, B, N, dev, faq, refine)
+    if meter is None:
+        meter = WeightedQapMeter(dev)
+    else:
+        _check_meter(who, 'meter', BinnedWeightedQapMeter, meter, bins, dev)
+    _check_seed_meter(who, seed_meter, bins, dev, meter.K if bins is not None else None)
+    if assign is not None:
+        if not torch.is_tensor(assign) or tuple(assign.shape) != (B, N) or assign.is_floating_point() or assign.device != dev:
+            raise ValueError('%s: assign must be a (%d, %d) integer tensor on %s' % (who, B, N, dev))
+        assign = assign.to(torch.int32).contiguous()
+    with torch.cuda.device(dev):
+        if assign is None:
+            from .metrics import lsap_device
+            assign = lsap_device(s, nvalid, want_assign=True)[1]
+        return _decode_launches_weighted(*views, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt, faq, s, seeds,
+                                         seed_meter)
 
 
 def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False, bins=None,

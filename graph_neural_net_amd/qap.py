@@ -277,6 +277,26 @@ def _on_host_weighted(adj1, n):
     return not adj1.is_cuda or n > _lib.FGNN_QAPW_MAX_N
 
 
+def two_opt_weighted_device(x1, x2, gs, ld, a, nv, ms=-1, seeds=None):
+    """fgnn_qapw_2opt (fgnn_qapw_2opt_seeded with (B, N) int32 device seeds) on the views of `weighted_views`, from the (B, N) int32
+    contiguous matching `a` -> {'perm' (B, N) int32, 'swaps', 'status' (B,) int32, 'nit' (B,) int64} as the launch wrote them;
+    never synchronises."""
+    B, N = x1.shape[0], x1.shape[-1]
+    dev = x1.device
+    nbytes = _lib.load().fgnn_qapw_2opt_ws_bytes(B, N)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    perm = torch.empty(B, N, dtype=torch.int32, device=dev)
+    o32 = torch.empty(2, B, dtype=torch.int32, device=dev)
+    nit = torch.empty(B, dtype=torch.int64, device=dev)
+    if seeds is None:
+        _lib.call('fgnn_qapw_2opt', _lib.ptr(x1), _lib.ptr(x2), gs, ld, _lib.ptr(a), _lib.ptr(nv), B, N, ms, _lib.ptr(ws), nbytes,
+                  _lib.ptr(perm), _lib.ptr(o32[0]), _lib.ptr(nit), _lib.ptr(o32[1]), _lib.stream_ptr())
+    else:
+        _lib.call('fgnn_qapw_2opt_seeded', _lib.ptr(x1), _lib.ptr(x2), gs, ld, _lib.ptr(a), _lib.ptr(seeds), _lib.ptr(nv), B, N, ms,
+                  _lib.ptr(ws), nbytes, _lib.ptr(perm), _lib.ptr(o32[0]), _lib.ptr(nit), _lib.ptr(o32[1]), _lib.stream_ptr())
+    return {'perm': perm, 'swaps': o32[0], 'nit': nit, 'status': o32[1]}
+
+
 def two_opt_weighted(adj1, adj2, assign, nvalid=None, labels=None, max_swaps=None):
     """`two_opt` on real-weighted pairs (``csrc/qap_2opt_weighted.hip``): the same scan, acceptance of the first improving pair and
     evaluation count, from `assign`, on what `weighted_views` takes -- (B, N, N) float matrices or (B, C, N, N) batches whose
@@ -290,28 +310,43 @@ def two_opt_weighted(adj1, adj2, assign, nvalid=None, labels=None, max_swaps=Non
     weights the trajectory is the kernel's own, bit-identical from run to run, and the default bound of n_b^2 exchanges can bind:
     that is status 1, not an error.  The device route is the search launch, two objective launches and one count; it never
     synchronises.  CPU tensors and N > 256 take a host route in numpy float64 with the same scan and the same nit; there qap and
-    qap0 are float64.  There is no ``seeds`` argument here: fixed rows are supported by `two_opt` (0/1 pairs) and `faq` only.
+    qap0 are float64.
+
+    This function keeps its signature (a ``seeds`` keyword stays a TypeError, which callers and tests rely on): fixed rows are
+    `two_opt_weighted_seeded`, the same search over the free rows only.
 
     ``qap.two_opt(weighted=True)`` and ``match(weighted=True, two_opt=True)`` still refuse; the chain on weighted pairs is
+    ``model.match_weighted(x1, x2, refine=T, two_opt=True)`` (``evaluation.decode_scores_weighted``), or by hand
         out = model.match(x1, x2, refine=T, weighted=True)
         polished = qap.two_opt_weighted(x1, x2, out.get('perm', out['assign']), labels=...)"""
+    return _two_opt_weighted(adj1, adj2, assign, nvalid, labels, max_swaps, None)
+
+
+def two_opt_weighted_seeded(adj1, adj2, assign, seeds, nvalid=None, labels=None, max_swaps=None):
+    """`two_opt_weighted` with seeds: a (B, N) integer tensor as `faq` and `two_opt` take it (seeds[b, i] = j fixes row i, -1 leaves
+    it free; checked by `check_seeds`) -- the search over the free rows only (fgnn_qapw_2opt_seeded, the SEEDED instantiation of
+    the same kernel): SciPy's scan with ``partial_match`` and ``partial_guess``, positions and nit counted among the free rows; the
+    gains still sum over every vertex of the corner.  `assign` must be a permutation of the corner that holds every seed, else
+    status 2 (a seed outside [0, n_b) or shared by two rows is such a case); perm[i] == seeds[i] on every seeded row.  Everything
+    else, the keys and the host route (numpy float64, perm and nit SciPy's) included, as `two_opt_weighted`; seeds of all -1 give
+    its results key for key, seeds=None its launches."""
+    seeds = check_seeds('two_opt_weighted_seeded', seeds, assign.shape[0], assign.shape[1], adj1.device)
+    return _two_opt_weighted(adj1, adj2, assign, nvalid, labels, max_swaps, seeds)
+
+
+def _two_opt_weighted(adj1, adj2, assign, nvalid, labels, max_swaps, seeds):
     ms = _check_max_swaps(max_swaps)
     labels = labels_tensor(labels, assign.shape[0], assign.shape[1], adj1.device)
     if _on_host_weighted(adj1, adj1.shape[-1]):
-        return _two_opt_host_w(adj1, adj2, assign, nvalid, labels, ms)
+        return _two_opt_host_w(adj1, adj2, assign, nvalid, labels, ms, seeds)
     x1, x2, gs, ld = weighted_views(adj1, adj2)
     B, N = x1.shape[0], x1.shape[-1]
     dev = x1.device
     nv = _nv32(nvalid, dev)
     a = assign.to(device=dev, dtype=torch.int32).contiguous()
-    nbytes = _lib.load().fgnn_qapw_2opt_ws_bytes(B, N)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-    perm = torch.empty(B, N, dtype=torch.int32, device=dev)
-    o32 = torch.empty(2, B, dtype=torch.int32, device=dev)
-    nit = torch.empty(B, dtype=torch.int64, device=dev)
-    _lib.call('fgnn_qapw_2opt', _lib.ptr(x1), _lib.ptr(x2), gs, ld, _lib.ptr(a), _lib.ptr(nv), B, N, ms, _lib.ptr(ws), nbytes,
-              _lib.ptr(perm), _lib.ptr(o32[0]), _lib.ptr(nit), _lib.ptr(o32[1]), _lib.stream_ptr())
-    o64 = o32.to(torch.int64)
+    t = two_opt_weighted_device(x1, x2, gs, ld, a, nv, ms, seeds)
+    perm, nit = t['perm'], t['nit']
+    o64 = torch.stack([t['swaps'], t['status']]).to(torch.int64)
     out = {'perm': perm, 'qap0': objective_weighted(x1, x2, a, nv)['qap'], 'swaps': o64[0], 'nit': nit, 'status': o64[1]}
     return _finish_solver(out, objective_weighted(x1, x2, perm, nv)['qap'], labels, nv, None)
 
@@ -1148,33 +1183,38 @@ def _gains_of_row_w(A, Bp, i):
     return rows.sum(1) + cols.sum(1) + cross
 
 
-def _two_opt_pair_w(A, Bm, pi, max_swaps):
+def _two_opt_pair_w(A, Bm, pi, max_swaps, free=None):
     """The exchange search of one real-weighted pair -> (perm, qap, swaps, nit, status): the scan, the counted loop (n^2 rounds
-    without a limit) and the nit of the kernel, the gains in float64"""
+    without a limit) and the nit of the kernel, the gains in float64.  free (a boolean mask of the rows that may move; None: all):
+    SciPy's scan over combinations_with_replacement(i_free, 2), positions counted among the free rows."""
     n = len(pi)
     if n == 0:
         return pi, 0.0, 0, 0, 0
     pi = pi.copy()
     Bp = Bm[np.ix_(pi, pi)]
+    f, rank, movable = n, np.arange(n), np.ones(n, dtype=bool)
+    if free is not None:
+        f, rank, movable = int(free.sum()), np.cumsum(free) - 1, free
     swaps, nit, status = 0, 0, 1
     for _ in range(n * n if max_swaps < 0 else min(max_swaps, n * n)):
-        for i in range(n - 1):
-            hit = np.flatnonzero(_gains_of_row_w(A, Bp, i) > 0)
+        for i in np.flatnonzero(movable[:n - 1]):
+            hit = np.flatnonzero((_gains_of_row_w(A, Bp, i) > 0) & movable[i + 1:])
             if hit.size:
                 break
         else:
-            nit += n * (n + 1) // 2
+            nit += f * (f + 1) // 2
             status = 0
             break
-        j = i + 1 + int(hit[0])
-        nit += i * n - i * (i - 1) // 2 + (j - i) + 1
+        i, j = int(i), int(i) + 1 + int(hit[0])
+        ri, rj = int(rank[i]), int(rank[j])
+        nit += ri * f - ri * (ri - 1) // 2 + (rj - ri) + 1
         swaps += 1
         pi[[i, j]] = pi[[j, i]]
         Bp = Bm[np.ix_(pi, pi)]
     return pi, float((A * Bp).sum()), swaps, nit, status
 
 
-def _two_opt_host_w(adj1, adj2, assign, nvalid, labels, max_swaps):
+def _two_opt_host_w(adj1, adj2, assign, nvalid, labels, max_swaps, seeds=None):
     B, N = adj1.shape[0], adj1.shape[-1]
     sizes = _sizes(nvalid, B, N)
     lab = _label_rows(labels, sizes)
@@ -1186,8 +1226,13 @@ def _two_opt_host_w(adj1, adj2, assign, nvalid, labels, max_swaps):
         pi0 = pis[b, :n]
         inside = bool(((pi0 >= 0) & (pi0 < n)).all())
         q[1, b] = (As[b] * Bs[b][np.ix_(pi0, pi0)]).sum() if inside else -1.0
+        free = None
+        if seeds is not None:
+            sd = seeds[b, :n].detach().cpu().numpy().astype(np.int64)
+            free = sd < 0
+            inside = inside and bool((pi0[~free] == sd[~free]).all())
         if inside and len(set(pi0.tolist())) == n:
-            pi, q[0, b], swaps, nit, status = _two_opt_pair_w(As[b], Bs[b], pi0, max_swaps)
+            pi, q[0, b], swaps, nit, status = _two_opt_pair_w(As[b], Bs[b], pi0, max_swaps, free)
         else:
             pi, q[0, b], swaps, nit, status = pi0, -1.0, 0, 0, 2
         perm[b, :n] = pi

@@ -251,6 +251,74 @@ class Siamese_Node_Exp(nn.Module):
         self._raise_if_not_representation({'flag': flag})
         return out
 
+    def match_weighted(self, x1, x2, refine=0, labels=None, two_opt=False, faq=None, seeds=None, seed_meter=None):
+        """What `match` does for 0/1 batches, on REAL-weighted batches (the output of PairGenerator.spectral goes straight in: channel
+        0 of the batch is used as the matrices, in place): the eager forward under no_grad, the Hungarian matching, and the chain of
+        evaluation.decode_scores_weighted without a meter -- the faq= stage on fp32 (Sinkhorn start, seeds, restarts, polish), refine
+        rounds of qap.greedy_weighted, and with two_opt=True the exchange search fgnn_qapw_2opt (fgnn_qapw_2opt_seeded with seeds).
+        refine, labels, two_opt, faq, seeds, seed_meter: as `match` takes them, with its rules and messages (seeds need faq= and
+        exclude refine > 0; 'scores' and dict specs are accepted).  Returns `match`'s keys -- scores, assign, acc, qap, planted; with
+        faq perm, qap_faq, acc_faq, faq_perm, faq_nit, faq_status, sinkhorn_err, faq_restart (and seeded, seeds, nseeds); with refine
+        the outputs of qap.greedy_weighted; with two_opt perm, qap_2opt, acc_2opt, swaps, nit, status -- the objectives as float32.
+        With only refine the outputs equal ``match(weighted=True, refine=)`` bit for bit.  No verdict is taken and nothing
+        synchronises.  `match` itself is unchanged, its refusals of weighted=True with two_opt / faq included."""
+        from .evaluation import (SeedMeter, _check_faq, _check_refine, _check_two_opt, _decode_launches_weighted, _weighted_args,
+                                 seed_spec)
+        who = 'match_weighted'
+        refine, two_opt, faq = _check_refine(who, refine), _check_two_opt(who, two_opt), _check_faq(who, faq)
+        spec = seed_spec(who, seeds)
+        if seed_meter is not None and (not isinstance(seed_meter, SeedMeter) or faq is None):
+            raise ValueError('%s: seed_meter must be a SeedMeter and needs the faq= stage' % who)
+        if seeds is not None and faq is None:
+            raise ValueError('%s: seeds= needs the faq= stage (the Hungarian matching knows no fixed rows)' % who)
+        if seeds is not None and refine:
+            raise ValueError("%s: seeds= and refine > 0 do not go together (the reference's greedy_qap knows no fixed rows)" % who)
+        a1, a2 = _unwrap_input(x1), _unwrap_input(x2)
+        with torch.no_grad():
+            scores = self(a1, a2)
+            ragged = isinstance(scores, MaskedTensor)
+            t1, t2 = (a1.tensor.rename(None), a2.tensor.rename(None)) if ragged else (a1, a2)
+            s = scores.tensor.rename(None) if ragged else scores
+            dev, B, N = s.device, s.shape[0], s.shape[-1]
+            nv = a1.nvalid.to(device=dev, dtype=torch.int32).contiguous() if ragged else None
+            if torch.is_tensor(labels) and labels.dim() == 2 and labels.shape[1] > N:
+                labels = labels[:, :N]
+            labels = labels_tensor(labels, B, N, dev)
+            if torch.is_tensor(seeds) and seeds.dim() == 2 and seeds.shape[1] > N:
+                seeds = seeds[:, :N]
+            if spec is None:
+                seeds = qap.check_seeds(who, seeds, B, N, dev)
+            else:
+                if N > qap._lib.FGNN_SEED_MAX_N:
+                    raise RuntimeError('%s: seeds from the scores take at most %d vertices per graph (got %d)'
+                                       % (who, qap._lib.FGNN_SEED_MAX_N, N))
+                seeds = spec
+            views = _weighted_args(who, t1, t2, B, N, dev)
+            with torch.cuda.device(dev):
+                correct, assign = lsap_device(s, nv, want_assign=True)
+                if labels is not None:
+                    correct = count_matches(assign, labels, nv)
+                d = _decode_launches_weighted(*views, assign, nv, labels, None, B, N, B, None, refine, two_opt, faq, s.detach().float(),
+                                              seeds, seed_meter)
+                out = {'scores': scores, 'assign': assign, 'acc': correct.to(torch.int64), 'qap': d['qap'], 'planted': d['planted']}
+                if faq is not None or two_opt:
+                    target = labels if labels is not None else torch.arange(N, dtype=torch.int32, device=dev).expand_as(assign).contiguous()
+                if faq is not None:
+                    if seeds is not None:
+                        out.update({'seeded': d['seeded'], 'seeds': d['seeds'], 'nseeds': d['nseeds']})
+                    failed = d['faq_status'] == 2
+                    stage_perm = torch.where(failed[:, None], assign, d['faq_perm'])
+                    out.update({'perm': stage_perm, 'qap_faq': torch.where(failed, d['qap'], d['faq_qap']),
+                                'acc_faq': count_matches(stage_perm, target, nv).to(torch.int64), 'faq_perm': d['faq_perm'],
+                                'faq_nit': d['faq_nit'], 'faq_status': d['faq_status'], 'sinkhorn_err': d['sinkhorn_err'],
+                                'faq_restart': d['faq_restart']})
+                if refine:
+                    out.update(d['greedy'])
+                if two_opt:
+                    out.update({'perm': d['perm'], 'qap_2opt': d['refined'], 'acc_2opt': count_matches(d['perm'], target, nv).to(torch.int64),
+                                'swaps': d['swaps'].to(torch.int64), 'nit': d['nit'], 'status': d['status'].to(torch.int64)})
+        return out
+
     def fused_step(self, x1, x2, capture=True, metric=False, labels=None):
         """Forward of both branches + scoring + `triplet_loss` + the full backward (+ the step's metric, models/trainers.py:70-76)
         as the fused launch sequence of engine.FgnnEngine -- with capture=True ONE replayed HIP graph per (padded) batch shape,

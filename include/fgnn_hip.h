@@ -1024,6 +1024,18 @@ int fgnn_greedy_qapw_labels(const float *a1, const float *a2, long long gstride,
 long long fgnn_qapw_2opt_ws_bytes(int B, int N);
 int fgnn_qapw_2opt(const float *a1, const float *a2, long long gstride, int ld, const int *assign, const int *nvalid, int B, int N,
                    int max_swaps, void *ws, long long ws_bytes, int *perm, int *swaps, long long *nit, int *status, void *stream);
+/* fgnn_qapw_2opt_seeded: fgnn_qapw_2opt over the free rows only -- SciPy's scan over combinations_with_replacement(i_free, 2) with
+ * partial_match; the SEEDED instantiation of the same kernel body, as fgnn_qap_2opt_seeded is of the bit kernel's.  seeds: (B, N)
+ * int32 as the seeds section below describes (a negative entry: the row is free; rows at or beyond n_b are not read).  With f the
+ * number of free rows and r(i) the rank of row i among them, an applied pair (i, j) adds r(i) f - r(i) (r(i) - 1) / 2 + (r(j) - r(i))
+ * + 1 to nit and the last, fruitless scan f (f + 1) / 2; the round bound stays min(max_swaps, n_b n_b).  The gain of a pair is the
+ * chain above over ALL k < n_b: seeded rows and columns are part of the objective, they only never move.  `assign` must be a
+ * permutation of [0, n_b) that holds every seed -- so a seed outside [0, n_b), one target for two rows and a start against a seed
+ * all give status 2 (perm = assign, swaps = nit = 0).  f <= 1: status 0, perm = assign, swaps = 0, nit = f (f + 1) / 2.  Everything
+ * else, the workspace included, as fgnn_qapw_2opt; the rank table (n_b ints) lives in LDS in all four variants. */
+int fgnn_qapw_2opt_seeded(const float *a1, const float *a2, long long gstride, int ld, const int *assign, const int *seeds,
+                          const int *nvalid, int B, int N, int max_swaps, void *ws, long long ws_bytes, int *perm, int *swaps,
+                          long long *nit, int *status, void *stream);
 /* fgnn_qapw_faq (csrc/qap_faq.hip): the Fast Approximate QAP algorithm -- Frank-Wolfe on f(P) = tr(A^T P B P^T) over the doubly
  * stochastic matrices, scipy.optimize.quadratic_assignment(method='faq', options={'maximize': True}) without seeds or shuffling --
  * for every pair, as a chain of launches on `stream` with scratch from ws (fgnn_qapw_faq_ws_bytes bytes, 16-byte aligned): no
@@ -1224,7 +1236,7 @@ int fgnn_rank_fold(const int *rank, const int *nvalid /* optional */, int B, int
 
 /* Decode epochs (csrc/qap_fold.hip): the reference's all_acc_qap(val_loader, ...) and all_greedy_losses_acc over a whole loader
  * (toolbox/metrics.py:168-223), per epoch and per bin, from what the decode launches leave on the device.  0/1 graphs only: qap,
- * planted and refined are the int32 values of the bit-word entry points above (the fp32 objectives of fgnn_qapw_* have no fold).
+ * planted and refined are the int32 values of the bit-word entry points above (the fp32 objectives of fgnn_qapw_* have a fold of their own, fgnn_qapw_fold below).
  * fgnn_qap_fold, for the pairs b < live (0 <= live <= B; the others are ignored entirely); all inputs int32 on the device:
  *   assign  (B, N): the matching, as fgnn_lsap_accuracy writes it;  qap, planted (B): as fgnn_qap_objective writes them (planted may
  *   be the qap of the labels' matching instead);  perm (B, N) and refined (B): perm_best and s_best2 of fgnn_greedy_qap -- s_best2 =
@@ -1271,6 +1283,48 @@ int fgnn_qap_fold_bins(const int *assign, const int *perm /* optional */, const 
                        const int *planted, const int *refined /* with perm */, const int *nvalid /* optional */, int B, int N, int live,
                        const int *bin /* (B) */, int K, int *pair_correct /* optional */, int *pair_refined_correct /* optional */,
                        double *pair_ratio /* optional */, fgnn_qap_record *records /* K records */, void *stream);
+
+/* Decode epochs on real-weighted pairs (csrc/qap_fold_weighted.hip): the fp32-objective twins of fgnn_qap_fold(_bins), over what
+ * fgnn_qapw_objective, fgnn_greedy_qapw and fgnn_qapw_2opt leave on the device.  assign, perm, labels, nvalid, live, bin, K, the
+ * targets, the per-pair counts, the kernel's structure and the rule "a record that took no pair is not written" are those of
+ * fgnn_qap_fold; qap, planted, refined (B) are fp32 (refined: the objective of perm in the unit of qap -- 2 s_best of
+ * fgnn_greedy_qapw, an exact doubling, or fgnn_qapw_objective on perm).  What differs:
+ *   a weighted objective may be negative, so qap < 0 marks nothing: a pair is UNMATCHED iff some assign[b][i], i < n_b, lies outside
+ *   [0, n_b) (the wave counts that in its pass over the rows); it adds nodes, pairs, correct and unmatched += 1, nothing else
+ *   (not refined_correct either; it cannot be exact);
+ *   pair_ratio[b] (fp64) = (double)qap / (double)planted, the IEEE quotient of the two fp32 values converted exactly, when the pair
+ *   is matched and planted > 0, else 0; only then the pair enters ratio_sum and ratio_pairs;
+ *   recovered += [qap >= planted], improved += [refined > qap]: fp32 comparisons on the stored values;
+ *   qap_sum += (double)qap, planted_sum += (double)planted, refined_sum += (double)refined, ratio_sum += pair_ratio: fp64 additions
+ *   in pair order, each starting from the record's own value -- so a record has the same bits however its pairs were cut into calls,
+ *   and equals a sequential loop over the pairs in IEEE double bit for bit.
+ * A NaN objective is not special-cased: it fails every comparison (not recovered, not improved; a NaN planted: no ratio) and
+ * propagates into the sums it is added to.  Without perm refined_sum, refined_correct and improved are not touched. */
+typedef struct {
+    double ratio_sum;           /* sum of qap / planted over the matched pairs with planted > 0 */
+    double qap_sum;             /* sum of qap over the matched pairs */
+    double planted_sum;         /* sum of planted over the matched pairs */
+    double refined_sum;         /* sum of refined over the matched pairs */
+    long long ratio_pairs;      /* how many pairs entered ratio_sum */
+    long long correct;          /* rows with assign == target */
+    long long refined_correct;  /* rows with perm == target */
+    long long recovered;        /* matched pairs with qap >= planted */
+    long long exact;            /* pairs with every row correct */
+    long long improved;         /* matched pairs with refined > qap */
+    long long unmatched;        /* pairs with an assign entry outside [0, n_b) */
+    long long nodes;            /* sum of n_b */
+    long long pairs;            /* live pairs folded */
+    long long steps;            /* fold calls that added a pair */
+} fgnn_qapw_record;
+int fgnn_qapw_fold(const int *assign, const int *perm /* optional */, const int *labels /* optional */, const float *qap,
+                   const float *planted, const float *refined /* with perm */, const int *nvalid /* optional */, int B, int N, int live,
+                   int *pair_correct /* optional */, int *pair_refined_correct /* optional */, double *pair_ratio /* optional */,
+                   fgnn_qapw_record *meter, void *stream);
+int fgnn_qapw_fold_bins(const int *assign, const int *perm /* optional */, const int *labels /* optional */, const float *qap,
+                        const float *planted, const float *refined /* with perm */, const int *nvalid /* optional */, int B, int N,
+                        int live, const int *bin /* (B) */, int K, int *pair_correct /* optional */,
+                        int *pair_refined_correct /* optional */, double *pair_ratio /* optional */,
+                        fgnn_qapw_record *records /* K records */, void *stream);
 
 /* ---- confident seeds (csrc/seed_select.hip): a seed vector for the seeded solvers from a model's own scores, and its meter ------
  * fgnn_confident_seeds.  scores: B pairs of (N, N) fp32, row pitch ld >= N, pairs bstride >= N ld floats apart; nvalid (optional,
