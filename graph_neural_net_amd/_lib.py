@@ -23,6 +23,8 @@ FGNN_QAP_MAX_N = 256         # include/fgnn_hip.h: largest graph of the fgnn_qap
 FGNN_QAPW_MAX_N = 256        # include/fgnn_hip.h: largest graph of the fgnn_qapw_* / fgnn_greedy_qapw kernels (fp32 weights)
 FGNN_SEED_MAX_N = 256        # include/fgnn_hip.h: largest graph of the fgnn_seed_* kernels
 FGNN_SINKHORN_LDS_MAX_N = 192   # include/fgnn_hip.h: largest graph whose scores fgnn_sinkhorn keeps in LDS
+FGNN_WIGNER_PARENT_STREAM = 10   # include/fgnn_hip.h: the pair streams of fgnn_wigner_pairs
+FGNN_WIGNER_NOISE_STREAM = 11
 FGNN_RESTART_STREAM = 9      # include/fgnn_hip.h: the pair stream of fgnn_faq_restart_starts
 FGNN_RESTART_MAX_R = 64      # include/fgnn_hip.h: restarts per pair
 FGNN_RESTART_MAX_STARTS = 65535   # include/fgnn_hip.h: B R of one call (the pairs of one fgnn_qapw_faq call)
@@ -153,6 +155,14 @@ class PairstoreArgs(C.Structure):     # fgnn_pairstore_args (csrc/pairstore.hip)
                 ('parents', C.c_void_p), ('sizes', C.c_void_p), ('seconds', C.c_void_p), ('index', C.c_void_p),
                 ('level_thr', C.c_void_p), ('level', C.c_void_p), ('K', C.c_int),
                 ('bits1', C.c_void_p), ('bits2', C.c_void_p), ('nvalid', C.c_void_p)]
+
+
+class WignerArgs(C.Structure):        # fgnn_wigner_args (csrc/wigner.hip)
+    _fields_ = [('seed', C.c_ulonglong), ('first', C.c_longlong), ('B', C.c_int), ('N', C.c_int), ('thr_vertex', C.c_ulonglong),
+                ('rho', C.c_float), ('sig', C.c_float), ('scale', C.c_int), ('K', C.c_int),
+                ('index', C.c_void_p), ('level_coef', C.c_void_p), ('level', C.c_void_p),
+                ('bits1', C.c_void_p), ('bits2', C.c_void_p), ('labels', C.c_void_p),
+                ('x1', C.c_void_p), ('x2', C.c_void_p), ('nvalid', C.c_void_p)]
 
 
 FGNN_GUARD_MAX_PARTS = 64         # include/fgnn_hip.h
@@ -306,6 +316,7 @@ _SIGNATURES = {
     'fgnn_pairgen_levels': [C.POINTER(PairgenArgs), _VP, _VP, _I, _VP, _VP],
     'fgnn_pairstore_supported': [_I, _I],
     'fgnn_pairstore_gather': [C.POINTER(PairstoreArgs), _VP],
+    'fgnn_wigner_pairs': [C.POINTER(WignerArgs), _VP],
     'fgnn_epoch_index': [C.c_ulonglong, C.c_ulonglong, _LL, _LL, _LL, _VP, _VP],
     'fgnn_qap_objective': [_VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP],
     'fgnn_qap_improve_cost': [_VP, _VP, _VP, _VP, _I, _I, _VP, _LL, _I, _VP],

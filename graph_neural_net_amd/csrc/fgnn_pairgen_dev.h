@@ -14,6 +14,29 @@ constexpr int PG_THREADS = 64;
 enum { ST_SIZE = 0, ST_PARENT, ST_NOISE1, ST_NOISE2, ST_RELABEL, ST_CHAIN };
 constexpr unsigned long long THR_ONE = 1ull << 32;
 
+constexpr int MAX_SIZE_DRAWS = 64;       // n < 2 is redrawn at most this often, then n = 2 (tests/pairgen_ref.py)
+
+// The vertex count of pair `pr` (pairgen.hip, wigner.hip): N, or n ~ Binomial(N, vertex_proba) as N Bernoulli draws of stream
+// ST_SIZE; n < 2 is redrawn from the next N positions.  Called by every lane of one wave (lane: its number); wave-uniform result
+DEVI int vertex_count(const Pair &pr, int N, unsigned long long thr_vertex, int lane) {
+    int n = N;
+    if (thr_vertex < THR_ONE) {
+        n = 2;
+        for (int r = 0; r < MAX_SIZE_DRAWS; ++r) {
+            int c = 0;
+            for (int b = 0; b < N; b += PG_THREADS) {
+                const int i = b + lane;
+                c += __popcll(__ballot(i < N && pr.draw(ST_SIZE, (unsigned long long)(r * N + i)) < thr_vertex));
+            }
+            if (c >= 2) {
+                n = c;
+                break;
+            }
+        }
+    }
+    return n;
+}
+
 DEVI int bit(const unsigned *rows, int W, int i, int j) { return uni((rows[i * W + (j >> 5)] >> (j & 31)) & 1); }
 DEVI void set_edge(unsigned *rows, int W, int i, int j) {           // any lane, both directions
     atomicOr(&rows[i * W + (j >> 5)], 1u << (j & 31));

@@ -23,8 +23,6 @@
 
 namespace {
 
-constexpr int MAX_SIZE_DRAWS = 64;       // n < 2 is redrawn at most this often, then n = 2 (tests/pairgen_ref.py)
-
 DEVI void set_edge_one(unsigned *rows, int W, int i, int j) {      // one lane, both directions (LDS atomics without return)
     atomicOr(&rows[i * W + (j >> 5)], 1u << (j & 31));
     atomicOr(&rows[j * W + (i >> 5)], 1u << (i & 31));
@@ -221,21 +219,7 @@ __global__ __launch_bounds__(PG_THREADS) void pairgen_kernel(std::conditional_t<
     for (int i = lane; i < 2 * N * W; i += PG_THREADS) smem[i] = 0;
 
     // vertex count: n ~ Binomial(N, vertex_proba) as N Bernoulli draws; n < 2 redrawn from the next N positions
-    int n = N;
-    if (a.thr_vertex < THR_ONE) {
-        n = 2;
-        for (int r = 0; r < MAX_SIZE_DRAWS; ++r) {
-            int c = 0;
-            for (int b = 0; b < N; b += PG_THREADS) {
-                const int i = b + lane;
-                c += __popcll(__ballot(i < N && pr.draw(ST_SIZE, (unsigned long long)(r * N + i)) < a.thr_vertex));
-            }
-            if (c >= 2) {
-                n = c;
-                break;
-            }
-        }
-    }
+    const int n = vertex_count(pr, N, a.thr_vertex, lane);      // (fgnn_pairgen_dev.h: wigner.hip draws the same count)
     __syncthreads();
 
     if (a.family == FGNN_PAIRGEN_REGULAR)

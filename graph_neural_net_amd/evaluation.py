@@ -1052,7 +1052,8 @@ def decode_scores_weighted(scores, adj1, adj2, nvalid=None, labels=None, meter=N
 
 
 def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False, bins=None,
-                    rank_meter=None, qap_meter=None, bits=None, refine=0, two_opt=False, faq=None, seeds=None, seed_meter=None):
+                    rank_meter=None, qap_meter=None, bits=None, refine=0, two_opt=False, faq=None, seeds=None, seed_meter=None,
+                    adj=None):
     """scores: (B, N, N) fp32 raw scores on the GPU, or a MaskedTensor of them (its vertex counts are used unless nvalid is given).
     nvalid: (B,) vertex counts in [0, N]; labels: see metrics.py (None: the identity; they enter the accuracies, never the loss).
     live: the first `live` pairs count (None: all B) -- the others, the filling of a short last step, are ignored entirely.
@@ -1075,12 +1076,19 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
     faq (with a qap_meter): the Fast Approximate QAP stage of decode_scores, started from these scores or from the barycenter.
     seeds, seed_meter (with a qap_meter): a (B, N) seed tensor or the spec of decode_scores ('scores', or a dict), and a SeedMeter
     (with bins=: a BinnedSeedMeter) -- both are handed to the decode, with its refusals: seeds need faq= and exclude refine > 0.
+    adj=(x1, x2) instead of bits= (REAL-weighted pairs; the two together raise ValueError): the two graphs as (B, N, N) float
+    matrices or (B, C, N, N) batches whose channel 0 is read in place (qap.weighted_views; WignerGenerator.weighted's tensors) with a
+    WeightedQapMeter as qap_meter (with bins=: a BinnedWeightedQapMeter; a QapMeter is refused, as a WeightedQapMeter is with bits=)
+    -- the chain of decode_scores_weighted follows on the assignment of the solver launch made here, with its rules and messages
+    for refine, two_opt, faq, seeds and seed_meter; its per-pair tensors come back under 'decode'.
     Four launches, nothing is read back."""
     if isinstance(meter, BinnedEvalMeter) != (bins is not None):
         raise ValueError('evaluate_scores: bins= and a BinnedEvalMeter as meter go together')
     if qap_meter is None:
         if bits is not None or refine:
             raise ValueError('evaluate_scores: bits= and refine= belong to a qap_meter')
+        if adj is not None:
+            raise ValueError('evaluate_scores: adj= belongs to a qap_meter')
         if two_opt:
             raise ValueError('evaluate_scores: two_opt= belongs to a qap_meter')
         if faq is not None:
@@ -1090,6 +1098,9 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
     else:
         if not hungarian:
             raise ValueError('evaluate_scores: a qap_meter decodes the matching of the Hungarian solver; it needs hungarian=True')
+        if bits is not None and adj is not None:
+            raise ValueError('evaluate_scores: give the graphs as bits= (0/1, a QapMeter) or as adj= (real weights, a '
+                             'WeightedQapMeter), not both')
         refine = _check_refine('evaluate_scores', refine)
         two_opt = _check_two_opt('evaluate_scores', two_opt)
         faq = _check_faq('evaluate_scores', faq)
@@ -1102,10 +1113,15 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
     if rank_meter is not None:
         _check_meter('evaluate_scores', 'rank meter', BinnedRankMeter, rank_meter, bins, dev)
     if qap_meter is not None:
-        _check_meter('evaluate_scores', 'qap meter', BinnedQapMeter, qap_meter, bins, dev)
+        _check_meter('evaluate_scores', 'qap meter', BinnedQapMeter if adj is None else BinnedWeightedQapMeter, qap_meter, bins, dev)
         if bins is not None and qap_meter.K != meter.K:
             raise ValueError('evaluate_scores: the qap meter has %d records, the meter %d' % (qap_meter.K, meter.K))
-        bits = _bits_args('evaluate_scores', bits, B, N, dev)
+        if adj is None:
+            bits = _bits_args('evaluate_scores', bits, B, N, dev)
+        else:
+            if not isinstance(adj, (tuple, list)) or len(adj) != 2:
+                raise ValueError('evaluate_scores: adj must be the pair (x1, x2) of the two graphs')
+            views = _weighted_args('evaluate_scores', adj[0], adj[1], B, N, dev)
         seeds = _check_decode_seeds('evaluate_scores', seeds, B, N, dev, faq, refine)
         _check_seed_meter('evaluate_scores', seed_meter, bins, dev, meter.K if bins is not None else None)
     with torch.cuda.device(dev):
@@ -1134,8 +1150,12 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
         ranks = None if rank_meter is None else _rank_launches(s, nvalid, labels, bins, B, N, live, rank_meter)
         decode = None
         if qap_meter is not None:
-            decode = _decode_launches(*bits, assign, nvalid, labels, bins, B, N, live, qap_meter, refine, two_opt, faq, s, seeds,
-                                      seed_meter)
+            if adj is None:
+                decode = _decode_launches(*bits, assign, nvalid, labels, bins, B, N, live, qap_meter, refine, two_opt, faq, s, seeds,
+                                          seed_meter)
+            else:
+                decode = _decode_launches_weighted(*views, assign, nvalid, labels, bins, B, N, live, qap_meter, refine, two_opt, faq,
+                                                   s, seeds, seed_meter)
     n = nvalid if nvalid is not None else torch.full((B,), N, **i32)
     out = {'ce': pair_ce, 'n': n, 'correct_max': pair_max, 'correct_lsap': correct, 'assign': assign, 'meter': meter}
     if ranks is not None:

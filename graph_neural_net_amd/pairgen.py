@@ -23,8 +23,9 @@ Semantics follow the reference:
 
 Randomness is counter-based (Philox4x64-10 keyed by ``seed``): every draw is addressed by (pair index, stream, position), so
 pair k of a dataset is the same however a range is split into calls, devices or ranks.  Streams: 0 size, 1 parent, 2 noise-1,
-3 noise-2, 4 relabel, 5 swap chain / attachment, 7 planted permutation (``planted.py``), all with 0 in the fourth counter word;
-number 6 in that word belongs to the epoch permutation (``sampler.py``).  Probabilities are integer thresholds ``min(2^32, floor(prob * 2^32))`` compared with raw 32-bit
+3 noise-2, 4 relabel, 5 swap chain / attachment, 7 planted permutation (``planted.py``), 8 revealed seeds (``planted.reveal_seeds``),
+9 restart starts (``qap.faq``), 10 Wigner parent and 11 Wigner noise (``wigner.py``: the normals of the correlated Gaussian pairs), all
+with 0 in the fourth counter word; number 6 in that word belongs to the epoch permutation (``sampler.py``).  Probabilities are integer thresholds ``min(2^32, floor(prob * 2^32))`` compared with raw 32-bit
 draws; integers in [0, k) are ``(u32 * k) >> 32`` (``tests/pairgen_ref.py`` restates it all in numpy, bit for bit).
 
 Which pairs: a contiguous range ``(first, count)``, or any pairs by ``index=`` (an int64 tensor of dataset indices in any order,

@@ -555,13 +555,32 @@ class FgnnTrainer:
         scores, _ = eng.step(self.params, self.grads, None, nvalid=nv, total_nodes=1.0, loss_out=self._loss_sum, **lkw)
         return self._reduce_and_update(), scores
 
-    def _features(self, who, features, n_powers):
-        """features= / n_powers= of the epoch loops -> None (the tensor representation: the bits steps) or the checked n_powers"""
+    def _features(self, who, features, n_powers, generators=()):
+        """features= / n_powers= of the epoch loops -> None (the tensor representation: the bits steps), the checked n_powers
+        ('spectral'), or 'weighted' (the dense steps on ``generator.weighted``; generators: the loop's generators, checked for it)"""
         if features is None:
             return None
+        if features == 'weighted':
+            return self._check_weighted(who, generators)
         if features != 'spectral':
-            raise ValueError("FgnnTrainer.%s: features must be None or 'spectral' (got %r)" % (who, features))
+            raise ValueError("FgnnTrainer.%s: features must be None or 'spectral', or 'weighted' for real-weighted pairs (got %r)" % (who, features))
         return self._check_features(who, n_powers)
+
+    def _check_weighted(self, who, generators):
+        """The refusals of features='weighted' (before any launch) -> 'weighted'"""
+        for g in generators:
+            if not callable(getattr(g, 'weighted', None)):
+                raise ValueError("FgnnTrainer.%s: features='weighted' needs a generator with .weighted(...) (wigner.WignerGenerator), "
+                                 'got %s' % (who, type(g).__name__))
+        if self.input_form == 'tensor_representation':
+            raise ValueError("FgnnTrainer.%s: features='weighted' feeds real weights; this trainer was built with "
+                             "input_form='tensor_representation', whose 0/1 check would reject them (build it with input_form='dense')"
+                             % who)
+        c0 = self.layout.c0
+        if c0 != 2 and not (self.precision == 'bf16' and c0 == 32):
+            raise ValueError("FgnnTrainer.%s: features='weighted' feeds 2-channel tensor representations; a layout with "
+                             'original_features_num = %d does not take them (2; bf16 also 32, zero-filled)' % (who, c0))
+        return 'weighted'
 
     def train_epoch(self, generator, sampler, epoch, batch_size, permute=False, exact_last=False, features=None, n_powers=4):
         """One epoch over a fixed dataset of on-device pairs, in the sampler's order (the reference's shuffled DataLoader over
@@ -577,14 +596,22 @@ class FgnnTrainer:
         all-reduce, with a zero gradient.  False (default): the filled step trains its repeats, as before.
         features='spectral' (the reference's QAP_spectralGenerator): the same ``generator.bits(...)`` words go to
         train_step_spectral(n_powers=n_powers) -- the hand-written loop over ``generator.spectral(index=...)`` and train_step, bit
-        for bit, without the fp32 features between two launches.  None (default): the loop above, launch for launch."""
-        spec = self._features('train_epoch', features, n_powers)
+        for bit, without the fp32 features between two launches.  None (default): the loop above, launch for launch.
+        features='weighted' (real-weighted pairs; generator: wigner.WignerGenerator): per step
+        ``train_step(*generator.weighted(index=..., permute=permute))`` on the (B, 2, N, N) tensors, with the same labels and live --
+        the hand-written loop, launch for launch.  ValueError for a generator without ``.weighted``, a trainer with
+        input_form='tensor_representation' and a layout that does not take 2 channels."""
+        spec = self._features('train_epoch', features, n_powers, (generator,))
         steps = sampler.steps_per_epoch(batch_size)
         losses = torch.empty(steps, dtype=torch.float32, device=self.params.device)
+        pull = generator.weighted if spec == 'weighted' else generator.bits
         for step in range(steps):
-            b1, b2, nv, *lab = generator.bits(index=sampler.batch_index(epoch, step, batch_size), permute=permute)
+            b1, b2, nv, *lab = pull(index=sampler.batch_index(epoch, step, batch_size), permute=permute)
             kw = {'labels': lab[0] if lab else None, 'live': sampler.live_count(step, batch_size) if exact_last else None}
-            loss, _ = self.train_step_bits(b1, b2, nv, **kw) if spec is None else self.train_step_spectral(b1, b2, nv, spec, **kw)
+            if spec == 'weighted':
+                loss, _ = self.train_step(b1, b2, nv, **kw)
+            else:
+                loss, _ = self.train_step_bits(b1, b2, nv, **kw) if spec is None else self.train_step_spectral(b1, b2, nv, spec, **kw)
             losses[step].copy_(loss)
         return losses
 
@@ -658,14 +685,27 @@ class FgnnTrainer:
         return self._eval_tail(B, N, nvalid, **src, **options, **decode)
 
     def eval_step(self, x1, x2, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False, bins=None,
-                  rank_meter=None):
+                  rank_meter=None, qap_meter=None, refine=0, two_opt=False, faq=None, seeds=None, seed_meter=None):
         """eval_step_bits for dense batches: x1, x2 (B, c0, N, N) fp32 on the GPU, through the generic kernels (precision='bf16' with
-        a 32-channel layout: any 1..32 channels, as train_step)."""
+        a 32-channel layout: any 1..32 channels, as train_step).
+        qap_meter (a WeightedQapMeter; with bins= a BinnedWeightedQapMeter), refine, two_opt, faq, seeds, seed_meter: the decode chain
+        of evaluation.decode_scores_weighted on channel 0 of x1 and x2, read in place (evaluate_scores(adj=(x1, x2))), on the
+        solver's assignment -- real-weighted pairs (WignerGenerator.weighted) and any tensor representation.  Without these keywords
+        nothing of it is launched and the step is the one it always was."""
         if x1.dim() != 4 or x1.shape != x2.shape or not x1.is_cuda:
             raise RuntimeError('FgnnTrainer.eval_step: expected two (B, c0, N, N) device tensors, got %s / %s'
                                % (tuple(x1.shape), tuple(x2.shape)))
+        decode = {} if qap_meter is None and not refine else {'qap_meter': qap_meter, 'adj': (x1, x2), 'refine': refine}
+        if two_opt is not False:
+            decode = dict(decode, qap_meter=qap_meter, two_opt=two_opt)
+        if faq is not None:
+            decode = dict(decode, qap_meter=qap_meter, faq=faq)
+        if seeds is not None:
+            decode = dict(decode, qap_meter=qap_meter, seeds=seeds)
+        if seed_meter is not None:
+            decode = dict(decode, qap_meter=qap_meter, seed_meter=seed_meter)
         return self._eval_tail(x1.shape[0], x1.shape[-1], nvalid, x=torch.cat([x1, x2]).contiguous(), labels=labels, meter=meter, live=live,
-                               hungarian=hungarian, loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter)
+                               hungarian=hungarian, loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter, **decode)
 
     def evaluate(self, generator, sampler, batch_size, epoch=0, hungarian=True, meter=None, permute=False, loss_on_labels=False,
                  rank_meter=None, qap_meter=None, refine=0, features=None, n_powers=4, two_opt=False, faq=None, seeds=None,
@@ -692,9 +732,13 @@ class FgnnTrainer:
         ``planted.reveal_seeds(labels, nvalid, k, generator.seed, index=...)`` with the step's example indices (needs permute=True,
         ValueError otherwise).  seed_meter: a SeedMeter that takes every step's seed fold and is summed over the ranks like the meter.
         features='spectral', n_powers: the steps are eval_step_spectral on the same words (the decode of a qap_meter stays on the
-        adjacency, see there).  None: eval_step_bits, as before."""
-        from .evaluation import EvalMeter, QapMeter, RankMeter, SeedMeter
-        spec = self._features('evaluate', features, n_powers)
+        adjacency, see there).  None: eval_step_bits, as before.
+        features='weighted' (generator: wigner.WignerGenerator): per step ``eval_step(*generator.weighted(index=..., permute=permute))``;
+        the qap_meter is then a WeightedQapMeter and its decode the fp32 chain of evaluation.decode_scores_weighted on channel 0 of
+        the step's tensors.  The refusals of train_epoch hold."""
+        from .evaluation import EvalMeter, QapMeter, RankMeter, SeedMeter, WeightedQapMeter
+        spec = self._features('evaluate', features, n_powers, (generator,))
+        qap_class = WeightedQapMeter if spec == 'weighted' else QapMeter
         B = int(batch_size)
         if meter is None:
             meter = EvalMeter(self.params.device)
@@ -702,8 +746,8 @@ class FgnnTrainer:
             raise ValueError('FgnnTrainer.evaluate: meter must be an EvalMeter or None (got %s)' % type(meter).__name__)
         if rank_meter is not None and not isinstance(rank_meter, RankMeter):
             raise ValueError('FgnnTrainer.evaluate: rank_meter must be a RankMeter or None (got %s)' % type(rank_meter).__name__)
-        if qap_meter is not None and not isinstance(qap_meter, QapMeter):
-            raise ValueError('FgnnTrainer.evaluate: qap_meter must be a QapMeter or None (got %s)' % type(qap_meter).__name__)
+        if qap_meter is not None and not isinstance(qap_meter, qap_class):
+            raise ValueError('FgnnTrainer.evaluate: qap_meter must be a %s or None (got %s)' % (qap_class.__name__, type(qap_meter).__name__))
         if seed_meter is not None and not isinstance(seed_meter, SeedMeter):
             raise ValueError('FgnnTrainer.evaluate: seed_meter must be a SeedMeter or None (got %s)' % type(seed_meter).__name__)
         def batches():
@@ -717,7 +761,8 @@ class FgnnTrainer:
     def _eval_epoch(self, generator, batches, meter, rank_meter, reduce, hungarian, loss_on_labels, qap_meter=None, refine=0, spec=None,
                     two_opt=False, faq=None, seeds=None, seed_meter=None):
         """The loop of evaluate and noise_curve.  batches: per step that has a live pair (live, bins, the keyword arguments of
-        generator.bits); reduce: sum the meters over the ranks at the end; spec: None or the n_powers of spectral steps.  -> meter"""
+        generator.bits); reduce: sum the meters over the ranks at the end; spec: None, the n_powers of spectral steps, or 'weighted' (the
+        keyword arguments go to generator.weighted, the steps are eval_step).  -> meter"""
         if qap_meter is None and refine:
             raise ValueError('FgnnTrainer: refine= belongs to a qap_meter')
         if qap_meter is None and two_opt:
@@ -747,7 +792,7 @@ class FgnnTrainer:
                 decode['faq'] = dict(faq, index=bits_kw['index'])
             if reveal is not None and not bits_kw.get('permute'):
                 raise ValueError('FgnnTrainer: an integer seeds= reveals rows of the planted labels; it needs permute=True')
-            b1, b2, nv, *labels = generator.bits(**bits_kw)
+            b1, b2, nv, *labels = generator.weighted(**bits_kw) if spec == 'weighted' else generator.bits(**bits_kw)
             if reveal is not None:
                 from .planted import reveal_seeds
                 decode['seeds'] = reveal_seeds(labels[0], nv, reveal, generator.seed, index=bits_kw['index'])
@@ -755,6 +800,8 @@ class FgnnTrainer:
                       loss_on_labels=loss_on_labels, bins=bins, rank_meter=rank_meter, **decode)
             if spec is None:
                 self.eval_step_bits(b1, b2, **kw)
+            elif spec == 'weighted':
+                self.eval_step(b1, b2, **kw)
             else:
                 self.eval_step_spectral(b1, b2, n_powers=spec, **kw)
         if reduce:
@@ -800,9 +847,11 @@ class FgnnTrainer:
         levels; it is summed over the ranks where the meter is.
         seeds: as in `evaluate` (an integer k reveals the same rows of a pair at every level: the choice depends on the pair's index
         alone); seed_meter: a BinnedSeedMeter of K records, summed over the ranks where the meter is.
-        features='spectral', n_powers: as in `evaluate`."""
-        from .evaluation import BinnedEvalMeter, BinnedQapMeter, BinnedRankMeter, BinnedSeedMeter
-        spec = self._features('noise_curve', features, n_powers)
+        features='spectral', n_powers: as in `evaluate`.  features='weighted': as in `evaluate`, the levels being the generator's own
+        (``WignerGenerator.levels``: one (rho, sig) per level) and the qap_meter a BinnedWeightedQapMeter."""
+        from .evaluation import BinnedEvalMeter, BinnedQapMeter, BinnedRankMeter, BinnedSeedMeter, BinnedWeightedQapMeter
+        spec = self._features('noise_curve', features, n_powers, (generator,))
+        qap_class = BinnedWeightedQapMeter if spec == 'weighted' else BinnedQapMeter
         from .sampler import EpochSampler
         levels = generator.levels(noises)
         K, M, B = len(levels), int(num_examples), int(batch_size)
@@ -814,8 +863,8 @@ class FgnnTrainer:
             raise ValueError('FgnnTrainer.noise_curve: meter must be a BinnedEvalMeter of %d records or None' % K)
         if rank_meter is not None and (not isinstance(rank_meter, BinnedRankMeter) or rank_meter.K != K):
             raise ValueError('FgnnTrainer.noise_curve: rank_meter must be a BinnedRankMeter of %d records or None' % K)
-        if qap_meter is not None and (not isinstance(qap_meter, BinnedQapMeter) or qap_meter.K != K):
-            raise ValueError('FgnnTrainer.noise_curve: qap_meter must be a BinnedQapMeter of %d records or None' % K)
+        if qap_meter is not None and (not isinstance(qap_meter, qap_class) or qap_meter.K != K):
+            raise ValueError('FgnnTrainer.noise_curve: qap_meter must be a %s of %d records or None' % (qap_class.__name__, K))
         if seed_meter is not None and (not isinstance(seed_meter, BinnedSeedMeter) or seed_meter.K != K):
             raise ValueError('FgnnTrainer.noise_curve: seed_meter must be a BinnedSeedMeter of %d records or None' % K)
         if world_size is None:
@@ -859,10 +908,12 @@ class FgnnTrainer:
         are right over the seeds) and 'val_free_acc' (the rows without a seed the seeded stage got right over those rows), from a
         SeedMeter read in the same single host copy.
         features='spectral', n_powers: training and validation run on the spectral features of the generators' pairs (train_epoch /
-        evaluate with the same arguments)."""
-        fkw = {} if features is None else {'features': features, 'n_powers': self._features('fit', features, n_powers)}
-        from .evaluation import (EvalMeter, QapMeter, RankMeter, SeedMeter, _check_faq, _check_refine, qap_result, rank_result,
-                                 read_records, record_result, seed_result)
+        evaluate with the same arguments).  features='weighted': on the real-weighted pairs of two wigner.WignerGenerators;
+        decode_refine then builds a WeightedQapMeter and the same 'val_*' keys are reported."""
+        spec = self._features('fit', features, n_powers, (train_gen, val_gen))
+        fkw = {} if features is None else {'features': features} if spec == 'weighted' else {'features': features, 'n_powers': spec}
+        from .evaluation import (EvalMeter, QapMeter, RankMeter, SeedMeter, WeightedQapMeter, _check_faq, _check_refine, qap_result,
+                                 rank_result, read_records, record_result, seed_result)
         if scheduler is None:
             from .optim import ReduceLROnPlateau
             scheduler = ReduceLROnPlateau(self.opt)
@@ -879,7 +930,7 @@ class FgnnTrainer:
         decode_faq = _check_faq('FgnnTrainer.fit', decode_faq)
         if decode_seeds is not None and decode_faq is None:
             raise ValueError('FgnnTrainer.fit: decode_seeds= needs decode_faq= (seeds need the faq stage of the decode)')
-        qap_meter = None if decode_refine is None else QapMeter(self.params.device)
+        qap_meter = None if decode_refine is None else (WeightedQapMeter if spec == 'weighted' else QapMeter)(self.params.device)
         seed_meter = None if decode_seeds is None else SeedMeter(self.params.device)
         extra = [m for m in (rank_meter, qap_meter, seed_meter) if m is not None]
         own = EvalMeter(self.params.device) if extra else None                       # (read together with the other meters)

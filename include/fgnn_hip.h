@@ -855,6 +855,45 @@ typedef struct {
 int fgnn_pairstore_supported(int N, int noise_model);
 int fgnn_pairstore_gather(const fgnn_pairstore_args *args, void *stream);
 
+/* ---- correlated Gaussian (Wigner) pairs (csrc/wigner.hip; graph_neural_net_amd/wigner.py) ---------------------------------------
+ * B real-weighted pairs, both sides in one launch, as tensor representations (loaders/data_generator.py:118-125 on a real W):
+ * x1 / x2 (B, 2, N, N) fp32, channel 0 = W (symmetric, zero diagonal), channel 1 = diag(row sums of W); everything outside the
+ * n_b x n_b corner and every off-diagonal entry of channel 1 is +0.0f.  Pair b is index[b], or first + b when index is NULL.
+ *   vertex count: n_b of fgnn_pairgen for the same (seed, pair, N, thr_vertex) -- stream 0, the same redraw rule;
+ *   normals: z_s(t) for the unordered entry {i, j}, i < j, t = i N + j (N the padded size), from stream s = FGNN_WIGNER_PARENT_STREAM
+ *     / FGNN_WIGNER_NOISE_STREAM of the pair: Philox block t >> 3, 64-bit word (t & 7) >> 1 = (w0 low half, w1 high half),
+ *     u = ((w0 >> 8) + 1) 2^-24, v = (w1 >> 8) 2^-24, r = sqrtf(-2 logf(u)), z = r cospif(2 v) for even t, r sinpif(2 v) for odd t;
+ *   values: A_ij = c_b z_parent(t), B_ij = fmaf(rho, A_ij, sig (c_b z_noise(t))), c_b = 1 / sqrtf(n_b) with scale != 0, else 1;
+ *     every product is rounded on its own.  rho, sig: the arguments', or row level[b] of level_coef ((K, 2) fp32 on the device,
+ *     1 <= K <= FGNN_MAX_LEVELS) when level is given: a draw does not depend on them;
+ *   support (bits1, bits2: both or neither; (B, N, ceil(N/32)) words of the same pairs, unpermuted): A_ij is written where bit
+ *     (min, max) of bits1 is set, B_ij where that of bits2 is, +0.0f elsewhere;
+ *   labels ((B, N) int32, labels[b, i] = pi_b(i) for i < n_b): side 2 is written relabelled, x2[pi(i)][pi(j)] = B_ij; a column or
+ *     row no label < n_b maps to is written as zeros, and no label is used as an address;
+ *   row sums: fp32, of the output row as it is stored, in the order fixed in csrc/wigner.hip (per-lane column sums, xor butterfly).
+ * nvalid (optional, int32[B]) = n_b.  x1 = x2 = NULL: only nvalid is written (the vertex counts the planted permutation needs
+ * before the pairs are made).  Caller errors the host cannot see -- a negative index, a level outside [0, K) -- give the empty
+ * graph (all zeros) and nvalid = 0, as in fgnn_pairgen_indexed.  1 <= N <= FGNN_PAIRGEN_MAX_N, B <= 65535. */
+#define FGNN_WIGNER_PARENT_STREAM 10
+#define FGNN_WIGNER_NOISE_STREAM 11
+typedef struct {
+    unsigned long long seed;            /* Philox key */
+    long long first;                    /* pair of b = 0 when index is NULL */
+    int B, N;
+    unsigned long long thr_vertex;      /* as in fgnn_pairgen_args */
+    float rho, sig;                     /* (float)sqrt(1 - s^2), (float)s: used when level is NULL */
+    int scale;                          /* 1: c_b = 1 / sqrtf(n_b); 0: c_b = 1 */
+    int K;                              /* rows of level_coef */
+    const long long *index;             /* optional (B) */
+    const float *level_coef;            /* optional (K, 2): rho, sig of each level */
+    const int *level;                   /* optional (B) */
+    const unsigned *bits1, *bits2;      /* optional support (B, N, ceil(N/32)) */
+    const int *labels;                  /* optional (B, N) */
+    float *x1, *x2;                     /* out (B, 2, N, N); both NULL: nvalid only */
+    int *nvalid;                        /* optional out (B) */
+} fgnn_wigner_args;
+int fgnn_wigner_pairs(const fgnn_wigner_args *args, void *stream);
+
 /* ---- the order of a shuffled epoch (csrc/pairgen.hip; graph_neural_net_amd/sampler.py) ---------------------------------------
  * out[i] = pi((first_pos + i) mod M) for i < count, with pi the permutation of [0, M) that (seed, epoch) select: a balanced Feistel
  * network on 2 h bits (h = max(1, ceil(ceil(log2 M) / 2))), FGNN_EPOCH_ROUNDS rounds, walked along its cycle until the value is
