@@ -28,6 +28,7 @@ FGNN_WIGNER_NOISE_STREAM = 11
 FGNN_RESTART_STREAM = 9      # include/fgnn_hip.h: the pair stream of fgnn_faq_restart_starts
 FGNN_RESTART_MAX_R = 64      # include/fgnn_hip.h: restarts per pair
 FGNN_RESTART_MAX_STARTS = 65535   # include/fgnn_hip.h: B R of one call (the pairs of one fgnn_qapw_faq call)
+FGNN_GRAMPA_MAX_ITER = 1024  # include/fgnn_hip.h: rounds of one fgnn_grampa call
 FGNN_SPECTRAL_MAX_N = 256    # include/fgnn_hip.h: largest graph of fgnn_spectral_features
 FGNN_SPECTRAL_MAX_POWERS = 8
 FGNN_PLANTED_MAX_N = 256      # include/fgnn_hip.h: largest graph of the fgnn_planted_perm / fgnn_relabel_* kernels
@@ -341,6 +342,8 @@ _SIGNATURES = {
     'fgnn_qapw_faq_seeded_ws_bytes': [_I, _I],
     'fgnn_qapw_faq_seeded': [_VP, _VP, _LL, _I, _VP, _VP, _I, _VP, _VP, _I, _I, _I, _F, _VP, _LL, _VP, _VP, _VP, _VP, _VP, _VP],
     'fgnn_qap_2opt_seeded': [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP],
+    'fgnn_grampa_ws_bytes': [_I, _I],
+    'fgnn_grampa': [_VP, _VP, _LL, _I, _VP, _VP, _I, _I, _F, _I, _F, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
     'fgnn_reveal_seeds': [C.c_ulonglong, _LL, _VP, _VP, _VP, _I, _I, _I, _VP, _VP],
     'fgnn_planted_perm': [C.c_ulonglong, _LL, _VP, _VP, _I, _I, _VP, _VP],
     'fgnn_relabel_bits': [_VP, _VP, _VP, _I, _I, _VP, _VP],
@@ -393,7 +396,8 @@ _SIGNATURES = {
 }
 _RESTYPES = {'fgnn_last_error': C.c_char_p, 'fgnn_block1_struct_ws_floats': C.c_longlong, 'fgnn_greedy_qap_ws_bytes': C.c_longlong,
              'fgnn_greedy_qapw_ws_bytes': C.c_longlong, 'fgnn_qapw_2opt_ws_bytes': C.c_longlong,
-             'fgnn_qapw_faq_ws_bytes': C.c_longlong, 'fgnn_qapw_faq_seeded_ws_bytes': C.c_longlong}
+             'fgnn_qapw_faq_ws_bytes': C.c_longlong, 'fgnn_qapw_faq_seeded_ws_bytes': C.c_longlong,
+             'fgnn_grampa_ws_bytes': C.c_longlong}
 EXPORTS = tuple(_SIGNATURES)
 
 _lib = None

@@ -1165,6 +1165,77 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
     return out
 
 
+BASELINE_METHODS = ('grampa',)
+
+
+def baseline_curve(generator, noises, num_examples, batch_size, method='grampa', features=None, permute=True, meter=None,
+                   rank_meter=None, qap_meter=None, seed_meter=None, refine=0, two_opt=False, faq=None, seeds=None, **grampa_kwargs):
+    """The model-free twin of ``FgnnTrainer.noise_curve``: the curve of a spectral baseline across K = len(noises) noise levels, in
+    one pass, with the same paired design and the same cut -- the K * num_examples examples lie level-major (example e is dataset
+    pair e % num_examples at level e // num_examples) and an unshuffled EpochSampler cuts them into full batches of mixed levels;
+    the filling of a short last batch is masked out (live=).  Per batch the pairs come from ``generator.bits(index=, levels=, level=,
+    permute=)`` (features=None: a PairSource, 0/1 graphs) or ``generator.weighted(...)`` (features='weighted': a WignerGenerator),
+    the scores from ``qap.grampa(x1, x2, nvalid=, labels=, weighted=, **grampa_kwargs)`` (method='grampa', the only one), and
+    ``evaluate_scores(X, nvalid=, labels=, meter=, bins=level, live=, rank_meter=, qap_meter=, bits= / adj=, refine=, two_opt=, faq=,
+    seeds=, seed_meter=)`` folds them: the records are bit for bit those of that loop written by hand.
+    meter: a BinnedEvalMeter of K records (None: a fresh one whose values are the noises); rank_meter, qap_meter (a BinnedQapMeter,
+    with features='weighted' a BinnedWeightedQapMeter), seed_meter: binned meters of K records, with the rules of evaluate_scores
+    for refine, two_opt, faq and seeds (a tensor of seeds makes no sense across batches: 'scores' or the spec dict).
+    Nothing is read until the end: ONE device-to-host copy of all the meters' records.  -> {'meter', 'records' (K dicts with 'noise',
+    'loss', 'acc', 'acc_max', ...)} plus, for each meter given, 'rank_records' / 'qap_records' / 'seed_records', the meters' result()
+    dicts.  One process: there is no split over ranks here."""
+    from . import qap
+    from .sampler import EpochSampler
+    if method not in BASELINE_METHODS:
+        raise ValueError("baseline_curve: method must be 'grampa', got %r" % (method,))
+    if features not in (None, 'weighted'):
+        raise ValueError("baseline_curve: features must be None or 'weighted', got %r" % (features,))
+    if torch.is_tensor(seeds):
+        raise ValueError("baseline_curve: seeds must be None, 'scores' or a spec dict (one seed tensor cannot serve every batch)")
+    weighted = features == 'weighted'
+    levels = generator.levels(noises)
+    K, M, B = len(levels), int(num_examples), int(batch_size)
+    if M < 1 or B < 1:
+        raise ValueError('baseline_curve: num_examples and batch_size must be >= 1, got %d, %d' % (M, B))
+    dev = generator.device
+    if meter is None:
+        meter = BinnedEvalMeter(dev, K, values=levels.noises)
+    elif not isinstance(meter, BinnedEvalMeter) or meter.K != K:
+        raise ValueError('baseline_curve: meter must be a BinnedEvalMeter of %d records or None' % K)
+    qap_class = BinnedWeightedQapMeter if weighted else BinnedQapMeter
+    for what, m, cls in (('rank_meter', rank_meter, BinnedRankMeter), ('qap_meter', qap_meter, qap_class),
+                         ('seed_meter', seed_meter, BinnedSeedMeter)):
+        if m is not None and (not isinstance(m, cls) or m.K != K):
+            raise ValueError('baseline_curve: %s must be a %s of %d records or None' % (what, cls.__name__, K))
+    decode = {}
+    if qap_meter is not None:
+        decode = {'qap_meter': qap_meter, 'refine': refine, 'two_opt': two_opt, 'faq': faq, 'seeds': seeds, 'seed_meter': seed_meter}
+    elif refine or two_opt or faq is not None or seeds is not None or seed_meter is not None:
+        raise ValueError('baseline_curve: refine=, two_opt=, faq=, seeds= and seed_meter= belong to a qap_meter')
+    sampler = EpochSampler(K * M, shuffle=False, rank=0, world_size=1, drop_last=False, device=dev)
+    for step in range(sampler.steps_per_epoch(B)):
+        e = sampler.batch_index(0, step, B)
+        pair, level, live = e % M, e // M, sampler.live_count(step, B)
+        if not live:
+            continue
+        kw = {'index': pair, 'levels': levels, 'level': level, 'permute': permute}
+        x1, x2, nv, *labels = generator.weighted(**kw) if weighted else generator.bits(**kw)
+        labels = labels[0] if labels else None
+        X = qap.grampa(x1, x2, nvalid=nv, labels=labels, weighted=weighted, **grampa_kwargs)['X']
+        if qap_meter is not None:
+            decode['adj' if weighted else 'bits'] = (x1, x2)
+        evaluate_scores(X, nvalid=nv, labels=labels, meter=meter, live=live, bins=level, rank_meter=rank_meter, **decode)
+    extra = [(k, m) for k, m in (('rank_records', rank_meter), ('qap_records', qap_meter), ('seed_records', seed_meter)) if m is not None]
+    raws = _read(meter, *(m for _, m in extra))
+    out = {'meter': meter}
+    for key, m, recs in zip(['records'] + [k for k, _ in extra], [meter] + [m for _, m in extra], raws):
+        rows = [pm._result(pm._dict(r)) for pm, r in zip(m.meters, recs)]
+        for row, v in zip(rows, m.values or ()):
+            row['noise'] = v
+        out[key] = rows
+    return out
+
+
 def all_losses_acc(batches, model, eval_score='linear_assignment', labels=None):
     """The reference's all_losses_acc (toolbox/metrics.py:144-166) over an iterable of (data1, data2) batches as `model` takes
     them: -> (np.array of the per-batch losses ce_sum_batch / nodes_batch, np.array of the per-pair accuracies).

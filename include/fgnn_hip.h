@@ -1143,6 +1143,38 @@ int fgnn_qapw_faq_seeded(const float *a1, const float *a2, long long gstride, in
                          long long ws_bytes, int *perm, int *nit, int *status, int *seeded /* optional */,
                          float *p_out /* optional, (B,N,N) */, void *stream);
 
+/* ---- GRAMPA (csrc/grampa.hip): the spectral similarity of Fan, Mao, Wu, Xu, "Spectral graph matching and regularized quadratic
+ * relaxations" -- a SCORE producer, X = sum_ij u_i u_i^T H v_j v_j^T / ((lambda_i - mu_j)^2 + eta^2) with A = U Lambda U^T,
+ * B = V M V^T -- computed without an eigendecomposition as the solution of the symmetric positive definite system
+ *     (T^T T + eta^2 I) X = H,   T(X) = A X - X B,  T^T(S) = A^T S - S B^T       (no symmetry of A, B is assumed)
+ * by conjugate gradient, for every pair, as a chain of launches on `stream` with scratch from ws (fgnn_grampa_ws_bytes bytes,
+ * 16-byte aligned): no allocation, no host copy, no synchronisation, capturable.  Addressing and input contract are those of the
+ * fgnn_qapw_* entry points; nothing outside a pair's corner is read, in a1, a2 and rhs alike.  H = the corner of rhs ((B, N, N) fp32,
+ * contiguous) or, with rhs NULL, all ones.  From X = 0, R = P = H, r0 = rr = <H, H>, a round is three launches:
+ *     S = A P - P B                      v_mfma_f32_32x32x2_f32, operands staged through LDS: two fmaf chains of n_b terms, k
+ *                                        ascending, subtracted once
+ *     Q = A^T S - S B^T + eta^2 P        two chains, one subtraction, one fmaf with eta^2 = (float)((double)eta * eta); the block's
+ *                                        part of <P, Q> goes to its slot of a partials buffer as an fp64 value (no atomics)
+ *     pq = the slots in slot order;  alpha = (float)(rr / pq);  R = fmaf(-alpha, Q, R);  rn = <R, R> (fp64, fixed order);
+ *     res = sqrt(rn / r0);  X = fmaf(alpha, P, X);  res < tol: the pair stops, status 0;  else P = fmaf((float)(rn / rr), P, R), rr = rn
+ * Breakdown -- pq not a finite number greater than 0, or rn not finite (an inf or NaN inside a corner) -- freezes the pair with
+ * status 3 BEFORE X is updated: X stays its last iterate.  Always maxiter rounds are issued; a pair that has stopped is frozen by a
+ * done flag in the workspace and left at once by all three kernels.  Then perm = argmax_Q <X, Q> by the solver of fgnn_lsap_accuracy
+ * on -X.  standardize != 0: a prologue writes fp32 work copies of both corners, (w - m) / (sqrt(n_b) sd) off the diagonal and 0 on
+ * it, m and sd the mean and population standard deviation of the n_b (n_b - 1) off-diagonal corner entries (fp64 sums in a fixed
+ * order, the quotient fp64 and rounded once) -- the paper's (A - p) / sqrt(n p (1 - p)) with the empirical p -- and the rounds read
+ * those; a side whose sd is not a finite number > 0 (an empty or complete graph, n_b < 2) gives status 2.
+ * Outputs (all required): X (B, N, N) fp32 contiguous, exact zeros around the corner (all zeros for status 2); perm (B, N) int32, -1
+ * past the corner and everywhere for status 2; nit int32 = the rounds whose update was made; res fp32 = sqrt(<R, R> / <H, H>) of the
+ * recurrence's residual after the last update (1 before any, 0 for status 2); status int32: 0 stopped on tol, 1 maxiter reached,
+ * 2 n_b = 0, <H, H> = 0, a flat side under standardize, or no assignment found; 3 breakdown.  Every reduction has a fixed order that
+ * depends on n_b alone: results are bit-identical from run to run, and a pair's do not depend on B or on the pairs around it.
+ * 1 <= N <= FGNN_QAPW_MAX_N, B <= 65535, 1 <= maxiter <= 1024, eta > 0, tol > 0 (finite). */
+long long fgnn_grampa_ws_bytes(int B, int N);
+int fgnn_grampa(const float *a1, const float *a2, long long gstride, int ld, const float *rhs /* NULL: all ones */, const int *nvalid,
+                int B, int N, float eta, int maxiter, float tol, int standardize, void *ws, float *X, int *perm, int *nit, float *res,
+                int *status, void *stream);
+
 /* ---- Sinkhorn normalisation of scores (csrc/sinkhorn.hip): the doubly stochastic start fgnn_qapw_faq takes from a model's scores,
  * one workgroup per pair, the whole iteration in ONE launch, in the log domain --------------------------------------------------
  * S: B pairs of (N, N) fp32 scores, row pitch ld >= N, pairs pair_stride >= N ld floats apart.  nvalid (optional, int32[B]): pair b
