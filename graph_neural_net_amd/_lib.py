@@ -344,6 +344,8 @@ _SIGNATURES = {
     'fgnn_qap_2opt_seeded': [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP],
     'fgnn_grampa_ws_bytes': [_I, _I],
     'fgnn_grampa': [_VP, _VP, _LL, _I, _VP, _VP, _I, _I, _F, _I, _F, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
+    'fgnn_degree_profile_ws_bytes': [_I, _I],
+    'fgnn_degree_profile': [_VP, _VP, _LL, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
     'fgnn_reveal_seeds': [C.c_ulonglong, _LL, _VP, _VP, _VP, _I, _I, _I, _VP, _VP],
     'fgnn_planted_perm': [C.c_ulonglong, _LL, _VP, _VP, _I, _I, _VP, _VP],
     'fgnn_relabel_bits': [_VP, _VP, _VP, _I, _I, _VP, _VP],
@@ -397,7 +399,7 @@ _SIGNATURES = {
 _RESTYPES = {'fgnn_last_error': C.c_char_p, 'fgnn_block1_struct_ws_floats': C.c_longlong, 'fgnn_greedy_qap_ws_bytes': C.c_longlong,
              'fgnn_greedy_qapw_ws_bytes': C.c_longlong, 'fgnn_qapw_2opt_ws_bytes': C.c_longlong,
              'fgnn_qapw_faq_ws_bytes': C.c_longlong, 'fgnn_qapw_faq_seeded_ws_bytes': C.c_longlong,
-             'fgnn_grampa_ws_bytes': C.c_longlong}
+             'fgnn_grampa_ws_bytes': C.c_longlong, 'fgnn_degree_profile_ws_bytes': C.c_longlong}
 EXPORTS = tuple(_SIGNATURES)
 
 _lib = None

@@ -1165,17 +1165,22 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
     return out
 
 
-BASELINE_METHODS = ('grampa',)
+BASELINE_METHODS = ('grampa', 'degree_profile')
+# the keywords baseline_curve hands on to a method's function (qap.grampa, qap.degree_profile); the pairs, nvalid=, labels= and
+# weighted= are the curve's own
+_BASELINE_KWARGS = {'grampa': ('eta', 'maxiter', 'tol', 'standardize', 'rhs'), 'degree_profile': ()}
 
 
 def baseline_curve(generator, noises, num_examples, batch_size, method='grampa', features=None, permute=True, meter=None,
-                   rank_meter=None, qap_meter=None, seed_meter=None, refine=0, two_opt=False, faq=None, seeds=None, **grampa_kwargs):
-    """The model-free twin of ``FgnnTrainer.noise_curve``: the curve of a spectral baseline across K = len(noises) noise levels, in
+                   rank_meter=None, qap_meter=None, seed_meter=None, refine=0, two_opt=False, faq=None, seeds=None, **kwargs):
+    """The model-free twin of ``FgnnTrainer.noise_curve``: the curve of a model-free baseline across K = len(noises) noise levels, in
     one pass, with the same paired design and the same cut -- the K * num_examples examples lie level-major (example e is dataset
     pair e % num_examples at level e // num_examples) and an unshuffled EpochSampler cuts them into full batches of mixed levels;
     the filling of a short last batch is masked out (live=).  Per batch the pairs come from ``generator.bits(index=, levels=, level=,
     permute=)`` (features=None: a PairSource, 0/1 graphs) or ``generator.weighted(...)`` (features='weighted': a WignerGenerator),
-    the scores from ``qap.grampa(x1, x2, nvalid=, labels=, weighted=, **grampa_kwargs)`` (method='grampa', the only one), and
+    the scores from ``qap.grampa(x1, x2, nvalid=, labels=, weighted=, **kwargs)`` (method='grampa') or ``qap.degree_profile(x1, x2,
+    nvalid=, labels=, weighted=)`` (method='degree_profile', which takes no further keyword; one the method does not take raises
+    ValueError before any launch), and
     ``evaluate_scores(X, nvalid=, labels=, meter=, bins=level, live=, rank_meter=, qap_meter=, bits= / adj=, refine=, two_opt=, faq=,
     seeds=, seed_meter=)`` folds them: the records are bit for bit those of that loop written by hand.
     meter: a BinnedEvalMeter of K records (None: a fresh one whose values are the noises); rank_meter, qap_meter (a BinnedQapMeter,
@@ -1187,7 +1192,11 @@ def baseline_curve(generator, noises, num_examples, batch_size, method='grampa',
     from . import qap
     from .sampler import EpochSampler
     if method not in BASELINE_METHODS:
-        raise ValueError("baseline_curve: method must be 'grampa', got %r" % (method,))
+        raise ValueError("baseline_curve: method must be 'grampa' or 'degree_profile', got %r" % (method,))
+    stray = sorted(k for k in kwargs if k not in _BASELINE_KWARGS[method])
+    if stray:
+        raise ValueError('baseline_curve: method %r takes no keyword %s' % (method, ', '.join(repr(k) for k in stray)))
+    score_fn = qap.grampa if method == 'grampa' else qap.degree_profile
     if features not in (None, 'weighted'):
         raise ValueError("baseline_curve: features must be None or 'weighted', got %r" % (features,))
     if torch.is_tensor(seeds):
@@ -1221,7 +1230,7 @@ def baseline_curve(generator, noises, num_examples, batch_size, method='grampa',
         kw = {'index': pair, 'levels': levels, 'level': level, 'permute': permute}
         x1, x2, nv, *labels = generator.weighted(**kw) if weighted else generator.bits(**kw)
         labels = labels[0] if labels else None
-        X = qap.grampa(x1, x2, nvalid=nv, labels=labels, weighted=weighted, **grampa_kwargs)['X']
+        X = score_fn(x1, x2, nvalid=nv, labels=labels, weighted=weighted, **kwargs)['X']
         if qap_meter is not None:
             decode['adj' if weighted else 'bits'] = (x1, x2)
         evaluate_scores(X, nvalid=nv, labels=labels, meter=meter, live=live, bins=level, rank_meter=rank_meter, **decode)

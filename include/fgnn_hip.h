@@ -1175,6 +1175,38 @@ int fgnn_grampa(const float *a1, const float *a2, long long gstride, int ld, con
                 int B, int N, float eta, int maxiter, float tol, int standardize, void *ws, float *X, int *perm, int *nit, float *res,
                 int *status, void *stream);
 
+/* ---- Degree-profile matching (csrc/degree_profile.hip): the baseline of Ding, Ma, Wu, Xu, "Efficient random graph matching via
+ * degree profiles" for correlated Erdos-Renyi and Wigner pairs -- a SCORE producer without iteration, tolerance or start, O(n^2 d)
+ * work per pair -- as a chain of launches on `stream` with scratch from ws (fgnn_degree_profile_ws_bytes bytes, 16-byte aligned): no
+ * allocation, no host copy, no synchronisation, capturable.  Give EITHER a1, a2 (fp32, addressing and input contract of the
+ * fgnn_qapw_* entry points; bits1 = bits2 = NULL) OR bits1, bits2 ((B, N, ceil(N/32)) words, the layout of fgnn_qap_objective; a1 =
+ * a2 = NULL, gstride and ld unused).  Nothing outside a pair's n_b x n_b corner is read.  Every vertex gets a profile, m values
+ * sorted ascending:
+ *     fp32 input   { A[i, k] : k != i, k < n_b }, the inputs themselves; m = n_b - 1
+ *     bit input    one value per neighbour k of i (m = d_i): ((c_ik n_b (n_b - 1) - r_i S) / (n_b (n_b - 1))) / sqrt(r_i q (1 - q)) =
+ *                  (c_ik - r_i q) / sqrt(r_i q (1 - q)) with d the degrees, S their sum, q = S / (n_b (n_b - 1)), r_i = n_b - 1 - d_i,
+ *                  c_ik = d_k - 1 - |N(i) & N(k)| (popcounts of the bit rows); the numerator is formed in integers, the rest in fp64,
+ *                  rounded once to fp32; r_i = 0 gives 0.  Diagonal bits are ignored; the rows are taken as they are: the formula
+ *                  is the paper's for SYMMETRIC input only.
+ *     m = 0        the point mass at 0
+ * Z(i, j) = the 1-Wasserstein distance of profile i of side 1 (a, length m) and profile j of side 2 (b, length l) over the integer
+ * quantile grid: (1 / (m l)) sum_t len_t |a[t / l] - b[t / m]|, t over the segments of [0, m l) cut at the multiples of l and of m
+ * in ascending order (ties of break points are integer comparisons), every term an fp64 product of the length and the fp64
+ * difference, added to an fp64 sum in that order without fused multiply-add, one fp64 division: the fp64 value is the one a
+ * sequential float64 loop forms, its relative error at most (m + l) 2^-53.  X = -(float)Z on the corner, +0.0 around it.
+ * perm = argmax_Q <X, Q> by the solver of fgnn_lsap_accuracy on (float)Z.
+ * Outputs: X (B, N, N) fp32 contiguous; perm (B, N) int32, -1 past the corner; status int32: 0 computed; 2 n_b < 2, or on bit input
+ * a side whose density q is 0 or 1 (or no assignment found); 3 an inf or NaN inside an fp32 corner (the diagonal included) -- for 2
+ * and 3 X is all zeros and perm all -1, and the other pairs keep their bits.  profiles (optional, (2, B, N, N) fp32: side, pair,
+ * vertex): the sorted values, +inf behind the m-th; counts (optional, (B, 2, N) int32): m; both all +inf / 0 for a row past the
+ * corner and for a pair whose status is not 0.  Every value depends on its own pair's corner alone and no launch has atomics:
+ * results are bit-identical from run to run, and a pair's do not depend on B, on N or on the pairs around it.
+ * 1 <= N <= 256, B <= 65535. */
+long long fgnn_degree_profile_ws_bytes(int B, int N);
+int fgnn_degree_profile(const float *a1, const float *a2, long long gstride, int ld, const unsigned *bits1, const unsigned *bits2,
+                        const int *nvalid, int B, int N, void *ws, float *X, int *perm, int *status, float *profiles /* optional */,
+                        int *counts /* optional */, void *stream);
+
 /* ---- Sinkhorn normalisation of scores (csrc/sinkhorn.hip): the doubly stochastic start fgnn_qapw_faq takes from a model's scores,
  * one workgroup per pair, the whole iteration in ONE launch, in the log domain --------------------------------------------------
  * S: B pairs of (N, N) fp32 scores, row pitch ld >= N, pairs pair_stride >= N ld floats apart.  nvalid (optional, int32[B]): pair b
