@@ -19,7 +19,9 @@ rank_meter=)`` issues them after its own four, on the same scores, labels, ``liv
 optionally the greedy refinement and, with ``two_opt=True``, the pairwise-exchange search after it (csrc/qap_2opt.hip), and
 fgnn_qap_fold (csrc/qap_fold.hip) into a ``QapMeter`` or, with ``bins=``, a ``BinnedQapMeter``; ``evaluate_scores(..., qap_meter=,
 bits=, refine=, two_opt=)`` issues it after its own launches on the assignment its solver launch wrote.  0/1 graphs only; the
-real-weighted decode is ``decode_scores_weighted`` (a ``WeightedQapMeter``).  ``faq=`` puts the Fast Approximate QAP chain
+real-weighted decode is ``decode_scores_weighted`` (a ``WeightedQapMeter``; ``evaluate_scores(..., adj=)``).  The two are ONE chain
+(``_decode_launches``, ``_faq_launches``) over a pair operand, ``_BitPairs`` or ``_WeightedPairs``, which holds what differs: the
+objective, the matrices of the FAQ chain, the refinement and search wrappers, the fold entry point and the meter classes.  ``faq=`` puts the Fast Approximate QAP chain
 (csrc/qap_faq.hip) between the Hungarian matching and the refinement, started from the Sinkhorn projection of the scores
 (csrc/sinkhorn.hip) or from the barycenter.
 
@@ -33,7 +35,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib, dp
+from . import _lib, dp, qap
 from .masked import MaskedTensor
 from .metrics import labels_tensor
 
@@ -293,18 +295,14 @@ def qap_result(rec):
     return out
 
 
-class QapMeter(_Records):
-    """The device record of a decode epoch (fgnn_qap_record, include/fgnn_hip.h): the reference's all_acc_qap(val_loader, ...) and
-    all_greedy_losses_acc (toolbox/metrics.py:168-223) over a whole loader, for 0/1 graphs on the bit-word path (the real-weighted
-    decode, qap.py's weighted=True, has its own meter, WeightedQapMeter).  Every field of the record is a 0-dim view of it
-    (`ratio_sum` fp64, the others int64); `acc`, `qap_ratio`, `mean_ratio`, `refined_acc`, `refined_qap_ratio` are 0-dim fp64 device tensors formed from
-    them on the device.  `refined` (host) says whether a refinement was folded since the last reset; `record()` carries it and
-    `result()` (qap_result) is the only host synchronisation."""
-    RECORD, FIELDS = _lib.QapRecord, tuple(name for name, _ in _lib.QapRecord._fields_)
+class _QapRecords(_Records):
+    """What the 0/1 and the real-weighted decode record share: `refined` (host: whether a refinement was folded since the last
+    reset, carried by `record()`), the derived device tensors and `result()` (qap_result).  A subclass names its RECORD, FIELDS and
+    HEAD_WORDS."""
     _result = staticmethod(qap_result)
 
     def __init__(self, device, buf=None):
-        """buf: the record's bytes when they belong to a larger buffer (a record of a BinnedQapMeter)"""
+        """buf: the record's bytes when they belong to a larger buffer (a record of the binned meter)"""
         self.refined = False
         self._open(device, buf=buf)
 
@@ -345,9 +343,8 @@ class QapMeter(_Records):
         return self._over(self.refined_sum, self.planted_sum)
 
 
-class BinnedQapMeter(_BinnedRecords):
-    """K decode records, one per bin: `meter[k]` is a QapMeter; see _BinnedRecords."""
-    PLAIN, RECORD = QapMeter, _lib.QapRecord
+class _BinnedQapRecords(_BinnedRecords):
+    """K decode records, one per bin, with the `refined` of _QapRecords kept on every one of them; see _BinnedRecords."""
 
     def __init__(self, device, K, values=None):
         self._open_bins(device, self._check_bins(K, values), values)
@@ -366,52 +363,34 @@ class BinnedQapMeter(_BinnedRecords):
             m.refined = True
 
 
-class WeightedQapMeter(_Records):
+class QapMeter(_QapRecords):
+    """The device record of a decode epoch (fgnn_qap_record, include/fgnn_hip.h): the reference's all_acc_qap(val_loader, ...) and
+    all_greedy_losses_acc (toolbox/metrics.py:168-223) over a whole loader, for 0/1 graphs on the bit-word path (the real-weighted
+    decode, qap.py's weighted=True, has its own meter, WeightedQapMeter).  Every field of the record is a 0-dim view of it
+    (`ratio_sum` fp64, the others int64); `acc`, `qap_ratio`, `mean_ratio`, `refined_acc`, `refined_qap_ratio` are 0-dim fp64 device tensors formed from
+    them on the device.  `refined` (host) says whether a refinement was folded since the last reset; `record()` carries it and
+    `result()` (qap_result) is the only host synchronisation."""
+    RECORD, FIELDS = _lib.QapRecord, tuple(name for name, _ in _lib.QapRecord._fields_)
+
+
+class BinnedQapMeter(_BinnedQapRecords):
+    """K decode records, one per bin: `meter[k]` is a QapMeter; see _BinnedRecords."""
+    PLAIN, RECORD = QapMeter, _lib.QapRecord
+
+
+class WeightedQapMeter(_QapRecords):
     """The device record of a decode epoch on REAL-weighted pairs (fgnn_qapw_record, include/fgnn_hip.h; csrc/qap_fold_weighted.hip):
     what QapMeter is for 0/1 graphs, over the fp32 objectives of csrc/qap_weighted.hip.  `ratio_sum`, `qap_sum`, `planted_sum`,
     `refined_sum` are 0-dim fp64 views of the record, the ten counts int64; `unmatched` counts the pairs whose matching leaves the
     corner (a weighted objective may be negative, so its sign marks nothing).  The derived tensors, `refined`, `record()` and
-    `result()` (qap_result: the same keys) are QapMeter's.  A class of its own: decode_scores refuses it, decode_scores_weighted
+    `result()` (qap_result: the same keys) are QapMeter's (_QapRecords).  A class of its own: decode_scores refuses it, decode_scores_weighted
     refuses a QapMeter."""
     RECORD, FIELDS, HEAD_WORDS = _lib.QapwRecord, tuple(name for name, _ in _lib.QapwRecord._fields_), 4
-    _result = staticmethod(qap_result)
-
-    def __init__(self, device, buf=None):
-        """buf: the record's bytes when they belong to a larger buffer (a record of a BinnedWeightedQapMeter)"""
-        self.refined = False
-        self._open(device, buf=buf)
-
-    def reset(self):
-        self.refined = False
-        return _Records.reset(self)
-
-    def _mark_refined(self):
-        self.refined = True
-
-    _dict, _over = QapMeter._dict, QapMeter._over
-    acc, qap_ratio, mean_ratio = QapMeter.acc, QapMeter.qap_ratio, QapMeter.mean_ratio
-    refined_acc, refined_qap_ratio = QapMeter.refined_acc, QapMeter.refined_qap_ratio
 
 
-class BinnedWeightedQapMeter(_BinnedRecords):
+class BinnedWeightedQapMeter(_BinnedQapRecords):
     """K weighted decode records, one per bin: `meter[k]` is a WeightedQapMeter; see _BinnedRecords."""
     PLAIN, RECORD, HEAD_WORDS = WeightedQapMeter, _lib.QapwRecord, 4
-
-    def __init__(self, device, K, values=None):
-        self._open_bins(device, self._check_bins(K, values), values)
-
-    @property
-    def refined(self):
-        return self.meters[0].refined
-
-    def reset(self):
-        for m in self.meters:
-            m.refined = False
-        return _Records.reset(self)
-
-    def _mark_refined(self):
-        for m in self.meters:
-            m.refined = True
 
 
 def seed_result(rec):
@@ -620,28 +599,124 @@ def _check_faq(who, faq):
     return o
 
 
-def _faq_launches(b1, b2, s, assign, q, nvalid, B, N, faq, seeds=None):
-    """The FAQ stage of the decode, on checked arguments: fgnn_sinkhorn on the scores (P0 'scores'), fgnn_expand_adjacency on both
-    sides, the fgnn_qapw_faq chain, the objective of its perm, and the select -- where the chain reports status 2 the stage keeps
-    `assign` and its objective `q`.  Every buffer is allocated before the first launch; nothing is read back.
+class _BitPairs:
+    """The 0/1 pairs of a decode as bit words: what the chain (_decode_launches, _faq_launches) needs from the graphs, on checked
+    arguments.  Objectives are int32, as fgnn_qap_fold reads them.  _WeightedPairs is the same surface on fp32 matrices."""
+    FOLD, BINNED, EXTRA = 'fgnn_qap_fold', BinnedQapMeter, ()       # the fold entry point, the meters, the route's own keys
+
+    def __init__(self, b1, b2):
+        self.b1, self.b2 = b1, b2
+
+    @classmethod
+    def checked(cls, who, bits1, bits2, B, N, dev):
+        return cls(*_bits_args(who, (bits1, bits2), B, N, dev))
+
+    def objective(self, matching, nvalid):
+        """-> (qap of `matching`, planted), as the fold reads them"""
+        obj = qap.objective_bits(self.b1, self.b2, matching, nvalid, raw=True)
+        return obj[0], obj[1]
+
+    def faq_buffer(self, B, N):
+        """what faq_matrices fills (the stage allocates before its first launch)"""
+        return torch.empty(2, B, 2, N, N, dtype=torch.float32, device=self.b1.device)
+
+    def faq_matrices(self, x, nvalid):
+        """-> the two sides as the fp32 matrices the FAQ chain runs on: fgnn_expand_adjacency on both sides' words"""
+        B, N = self.b1.shape[:2]
+        for side, bits in enumerate((self.b1, self.b2)):
+            _lib.call('fgnn_expand_adjacency', _lib.ptr(bits), _lib.ptr(nvalid), B, N, _lib.ptr(x[side]), _lib.stream_ptr())
+        return x[0, :, 0], x[1, :, 0]
+
+    def repeated(self, rep, m1, m2):
+        """-> (the operand of the B R restart problems, its two FAQ matrices); rep: a tensor R-fold, pair-major"""
+        return _BitPairs(rep(self.b1), rep(self.b2)), rep(m1), rep(m2)
+
+    def candidates(self, perms, nvalid, seeds, polish):
+        """The restart candidates as the best-of choice takes them -> (their objectives, their matchings, veto): with polish the
+        exchange search on all of them, its own objective and its status as veto"""
+        if not polish:
+            return qap.objective_bits(self.b1, self.b2, perms, nvalid)['qap'], perms, None
+        t = qap.two_opt_bits(self.b1, self.b2, perms, nvalid, seeds=seeds)
+        return t['qap'], t['perm'], t['status'].to(torch.int32)
+
+    def greedy(self, matching, T, nvalid, labels):
+        """-> (perm, refined = 2 s_best, the route's 'greedy' entry)"""
+        g = qap.greedy_bits(self.b1, self.b2, matching, T, nvalid, labels, raw=True)
+        return g['perm'], g['s_best2'], None
+
+    def two_opt(self, matching, nvalid, seeds):
+        """-> (perm, refined, swaps, status, nit); the search's objective IS qap's sum, whatever the symmetry"""
+        t = qap.two_opt_bits(self.b1, self.b2, matching, nvalid, raw=True, seeds=seeds)
+        return t['perm'], t['qap'], t['swaps'], t['status'], t['nit']
+
+
+class _WeightedPairs:
+    """The real-weighted pairs of a decode as the fp32 views of qap.weighted_views: the surface of _BitPairs, objectives fp32 as
+    fgnn_qapw_fold reads them.  The FAQ chain runs on the views themselves."""
+    FOLD, BINNED, EXTRA = 'fgnn_qapw_fold', BinnedWeightedQapMeter, ('nit', 'greedy')
+
+    def __init__(self, x1, x2, gs, ld):
+        self.x1, self.x2, self.gs, self.ld = x1, x2, gs, ld
+
+    @classmethod
+    def checked(cls, who, adj1, adj2, B, N, dev):
+        return cls(*_weighted_args(who, adj1, adj2, B, N, dev))
+
+    def objective(self, matching, nvalid):
+        obj = qap.objective_weighted(self.x1, self.x2, matching, nvalid)
+        return obj['qap'], obj['planted']
+
+    def faq_buffer(self, B, N):
+        return None
+
+    def faq_matrices(self, x, nvalid):
+        return self.x1, self.x2
+
+    def repeated(self, rep, m1, m2):
+        N = self.x1.shape[-1]
+        r = _WeightedPairs(rep(m1), rep(m2), N * N, N)
+        return r, r.x1, r.x2
+
+    def candidates(self, perms, nvalid, seeds, polish):
+        veto = None
+        if polish:
+            t = qap.two_opt_weighted_device(self.x1, self.x2, self.gs, self.ld, perms, nvalid, -1, seeds)
+            perms, veto = t['perm'], t['status']
+        return self.objective(perms, nvalid)[0], perms, veto
+
+    def greedy(self, matching, T, nvalid, labels):
+        g = qap.greedy_weighted(self.x1, self.x2, matching, T, nvalid, labels)
+        return g['perm'], g['s_best'] * 2, g                     # (an exact doubling: trace(A P B P^T), the unit of qap)
+
+    def two_opt(self, matching, nvalid, seeds):
+        """(the search returns no objective: a fresh launch on its perm)"""
+        t = qap.two_opt_weighted_device(self.x1, self.x2, self.gs, self.ld, matching, nvalid, -1, seeds)
+        return t['perm'], self.objective(t['perm'], nvalid)[0], t['swaps'], t['status'], t['nit']
+
+
+def _faq_launches(pairs, s, assign, q, nvalid, B, N, faq, seeds=None):
+    """The FAQ stage of the decode, on checked arguments and the operand `pairs` (_BitPairs or _WeightedPairs): fgnn_sinkhorn on the
+    scores (P0 'scores'), the operand's FAQ matrices (0/1: fgnn_expand_adjacency on both sides; weighted: the views themselves), the
+    fgnn_qapw_faq chain, the objective of its perm, and the select -- where the chain reports status 2 the stage keeps `assign` and
+    its objective `q`.  Every buffer is allocated before the first launch; nothing is read back.
     With seeds: fgnn_seed_index and fgnn_seed_gather first, so that Sinkhorn runs on the free block of the scores with n_b := u_b,
     and the fgnn_qapw_faq_seeded chain from that start, already in free coordinates.
     With faq['restarts'] = R > 1 or faq['polish'] (qap.faq's restarts): that start -- the Sinkhorn matrix or the barycenter -- is the
-    base of fgnn_faq_restart_starts (pair indices faq['index'], else the position in the batch), the sides are replicated R-fold,
-    the chain runs once on the B R problems, qap.objective_bits (with polish qap.two_opt_bits, seeded with seeds) scores them and
-    fgnn_qap_best_of picks; the select then works on the winner.  Restart 0 is the start the stage always had.
-    -> {'perm', 'qap', 'faq_perm', 'faq_qap', 'faq_nit', 'faq_status', 'sinkhorn_err', 'faq_restart'} (+ 'seeded' with seeds);
-    faq_restart is None without restarts"""
-    from . import qap
-    dev = b1.device
+    base of fgnn_faq_restart_starts (pair indices faq['index'], else the position in the batch), the operand is replicated R-fold,
+    the chain runs once on the B R problems, the operand scores them (its objective; with polish after its exchange search, seeded
+    with seeds, on all of them) and fgnn_qap_best_of picks; the select then works on the winner.  Restart 0 is the start the stage
+    always had.
+    -> {'perm', 'qap', 'faq_perm', 'faq_qap', 'faq_nit', 'faq_status', 'sinkhorn_err', 'faq_restart'} (+ 'seeded' with seeds), 'qap'
+    and 'faq_qap' in q's dtype; faq_restart is None without restarts"""
+    dev = assign.device
     R = faq['restarts']
     restarted = R > 1 or faq['polish']
     if restarted and B * R > _lib.FGNN_RESTART_MAX_STARTS:
         raise ValueError('decode: at most %d starts per call (got %d pairs x %d restarts)' % (_lib.FGNN_RESTART_MAX_STARTS, B, R))
     if faq['index'] is not None and tuple(faq['index'].shape) != (B,):
         raise ValueError("decode: faq['index'] must hold %d pair indices, got %s" % (B, tuple(faq['index'].shape)))
-    x = torch.empty(2, B, 2, N, N, dtype=torch.float32, device=dev)
-    p0 = err = u = None
+    x = pairs.faq_buffer(B, N)
+    p0 = err = u = restart = None
     if seeds is not None and (restarted or faq['P0'] == 'scores'):
         ix = qap.seed_index_device(seeds, nvalid)
         u = torch.where(ix['valid'] != 0, ix['nfree'], torch.zeros_like(ix['nfree']))
@@ -651,39 +726,27 @@ def _faq_launches(b1, b2, s, assign, q, nvalid, B, N, faq, seeds=None):
         else:
             sk = qap.sinkhorn_device(qap.seed_gather_device(s, ix['free_a'], ix['free_b'], u), u, faq['tau'], faq['iters'])
         p0, err = sk['P'], sk['err']
-    for side, bits in enumerate((b1, b2)):
-        _lib.call('fgnn_expand_adjacency', _lib.ptr(bits), _lib.ptr(nvalid), B, N, _lib.ptr(x[side]), _lib.stream_ptr())
+    m1, m2 = pairs.faq_matrices(x, nvalid)
     if restarted:
         def rep(t):
             return t.repeat_interleave(R, 0) if t is not None else None
         index = faq['index'].to(torch.int64).contiguous() if faq['index'] is not None else None
         starts = qap.random_starts_device(p0, nvalid if seeds is None else u, index, faq['seed'], B, N, R, dev)
-        b1r, b2r, nvr, sdr = rep(b1), rep(b2), rep(nvalid), rep(seeds)
-        run = qap.faq_weighted(rep(x[0, :, 0]), rep(x[1, :, 0]), nvr, starts, None, faq['maxiter'], faq['tol'], seeds=sdr,
-                               p0_free=seeds is not None)
-        if faq['polish']:
-            t = qap.two_opt_bits(b1r, b2r, run['perm'], nvr, seeds=sdr)
-            best = qap.best_of_device(t['qap'], run['status'], run['nit'], t['perm'], R, t['status'].to(torch.int32))
-        else:
-            best = qap.best_of_device(qap.objective_bits(b1r, b2r, run['perm'], nvr)['qap'], run['status'], run['nit'], run['perm'], R)
+        pairs_r, m1, m2 = pairs.repeated(rep, m1, m2)
+        nvr, sdr = rep(nvalid), rep(seeds)
+        run = qap.faq_weighted(m1, m2, nvr, starts, None, faq['maxiter'], faq['tol'], seeds=sdr, p0_free=seeds is not None)
+        score, perms, veto = pairs_r.candidates(run['perm'], nvr, sdr, faq['polish'])
+        best = qap.best_of_device(score, run['status'], run['nit'], perms, R, veto)
         out = {'perm': best['perm'], 'nit': best['nit'], 'status': best['status']}
         if seeds is not None:
             out['seeded'] = run['seeded'].view(B, R)[:, 0].contiguous()
-        fq = best['qap'].to(torch.int32)
-        failed = out['status'] == 2
-        res = {'perm': torch.where(failed[:, None], assign, out['perm']), 'qap': torch.where(failed, q, fq), 'faq_perm': out['perm'],
-               'faq_qap': fq, 'faq_nit': out['nit'], 'faq_status': out['status'], 'sinkhorn_err': err, 'faq_restart': best['restart']}
-        if seeds is not None:
-            res['seeded'] = out['seeded']
-        return res
-    if seeds is None:
-        out = qap.faq_weighted(x[0], x[1], nvalid, p0, None, faq['maxiter'], faq['tol'])
+        fq, restart = best['qap'].to(q.dtype), best['restart']
     else:
-        out = qap.faq_weighted(x[0], x[1], nvalid, p0, None, faq['maxiter'], faq['tol'], seeds=seeds, p0_free=True)
-    fq = qap.objective_bits(b1, b2, out['perm'], nvalid, raw=True)[0]
+        out = qap.faq_weighted(m1, m2, nvalid, p0, None, faq['maxiter'], faq['tol'], seeds=seeds, p0_free=seeds is not None)
+        fq = pairs.objective(out['perm'], nvalid)[0]
     failed = out['status'] == 2
     res = {'perm': torch.where(failed[:, None], assign, out['perm']), 'qap': torch.where(failed, q, fq), 'faq_perm': out['perm'],
-           'faq_qap': fq, 'faq_nit': out['nit'], 'faq_status': out['status'], 'sinkhorn_err': err, 'faq_restart': None}
+           'faq_qap': fq, 'faq_nit': out['nit'], 'faq_status': out['status'], 'sinkhorn_err': err, 'faq_restart': restart}
     if seeds is not None:
         res['seeded'] = out['seeded']
     return res
@@ -699,57 +762,58 @@ def seed_fold(seed_meter, seeds, first, final, nvalid, labels, bins, B, N, live)
         _lib.call('fgnn_seed_fold_bins', *pairs, _lib.ptr(bins), seed_meter.K, _lib.ptr(seed_meter.buf), _lib.stream_ptr())
 
 
-def _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt=False, faq=None, scores=None,
-                     seeds=None, seed_meter=None):
-    """qap.objective_bits (once more on the labels), fgnn_confident_seeds on `scores` when seeds is a spec, _faq_launches with faq
-    (on `scores`), qap.greedy_bits with refine > 0, qap.two_opt_bits with two_opt, then fgnn_qap_fold(_bins) and, with a
-    seed_meter, fgnn_seed_fold(_bins), on checked arguments (on the current stream of the bit words' device)
-    -> the dict of decode_scores"""
-    from . import qap
-    dev = b1.device
+def _decode_launches(pairs, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt=False, faq=None, scores=None, seeds=None,
+                     seed_meter=None):
+    """The decode chain on checked arguments and the operand `pairs` (_BitPairs or _WeightedPairs), on the current stream of its
+    device: the operand's objective of `assign` (once more on the labels), fgnn_confident_seeds on `scores` when seeds is a spec,
+    _faq_launches with faq (on `scores`), the operand's greedy refinement with refine > 0, its exchange search with two_opt (the
+    weighted one with a fresh objective of its perm), then the operand's fold entry point (fgnn_qap_fold(_bins) /
+    fgnn_qapw_fold(_bins)) and, with a seed_meter, fgnn_seed_fold(_bins), which reads integer matchings only.  meter None: no fold
+    (Siamese_Node_Exp.match_weighted).  -> the dict of decode_scores / decode_scores_weighted"""
     nseeds = None
     if isinstance(seeds, dict):     # a spec: the seeds come from the scores the solver saw
         picked = qap.confident_seeds_device(scores, nvalid, seeds['count'], seeds['min_margin'])
         seeds, nseeds = picked['seeds'], picked['nseeds']
-    obj = qap.objective_bits(b1, b2, assign, nvalid, raw=True)
-    q, planted = obj[0], obj[1]
+    q, planted = pairs.objective(assign, nvalid)
     if labels is not None:          # (as all_acc_qap: planted is the objective of the labels' matching)
-        planted = qap.objective_bits(b1, b2, labels, nvalid, raw=True)[0]
-    perm = refined = None
+        planted = pairs.objective(labels, nvalid)[0]
+    perm = refined = greedy = None
     first = assign
+    mark = meter._mark_refined if meter is not None else (lambda: None)
     stage = dict.fromkeys(('faq_perm', 'faq_qap', 'faq_nit', 'faq_status', 'sinkhorn_err', 'faq_restart'))
     if faq is not None:
-        stage = _faq_launches(b1, b2, scores, assign, q, nvalid, B, N, faq, seeds)
+        stage = _faq_launches(pairs, scores, assign, q, nvalid, B, N, faq, seeds)
         perm, refined = stage.pop('perm'), stage.pop('qap')
         first = perm
-        meter._mark_refined()
+        mark()
     if refine > 0:
-        g = qap.greedy_bits(b1, b2, assign if perm is None else perm, refine, nvalid, labels, raw=True)
-        perm, refined = g['perm'], g['s_best2']
-        meter._mark_refined()
-    swaps = status = None
-    if two_opt:                     # from the last matching of the chain; its objective IS qap's sum, whatever the symmetry
-        t = qap.two_opt_bits(b1, b2, assign if perm is None else perm, nvalid, raw=True, seeds=seeds)
-        perm, refined, swaps, status = t['perm'], t['qap'], t['swaps'], t['status']
-        meter._mark_refined()
-    # one zero-filled allocation for the three per-pair outputs: the 8-byte words first
-    words = torch.zeros(2 * B, dtype=torch.int64, device=dev)
-    ratio, ints = words[:B].view(torch.float64), words[B:].view(torch.int32)
-    correct, refined_correct = ints[:B], ints[B:]
-    pairs = (_lib.ptr(assign), _lib.ptr(perm), _lib.ptr(labels), _lib.ptr(q), _lib.ptr(planted), _lib.ptr(refined), _lib.ptr(nvalid),
-             B, N, live)
-    outs = (_lib.ptr(correct), _lib.ptr(refined_correct), _lib.ptr(ratio), _lib.ptr(meter.buf), _lib.stream_ptr())
-    if bins is None:
-        _lib.call('fgnn_qap_fold', *pairs, *outs)
-    else:
-        _lib.call('fgnn_qap_fold_bins', *pairs, _lib.ptr(bins), meter.K, *outs)
+        perm, refined, greedy = pairs.greedy(assign if perm is None else perm, refine, nvalid, labels)
+        mark()
+    swaps = status = nit = None
+    if two_opt:                     # from the last matching of the chain
+        perm, refined, swaps, status, nit = pairs.two_opt(assign if perm is None else perm, nvalid, seeds)
+        mark()
+    correct = refined_correct = ratio = None
+    if meter is not None:
+        # one zero-filled allocation for the three per-pair outputs: the 8-byte words first
+        words = torch.zeros(2 * B, dtype=torch.int64, device=assign.device)
+        ratio, ints = words[:B].view(torch.float64), words[B:].view(torch.int32)
+        correct, refined_correct = ints[:B], ints[B:]
+        per_pair = (_lib.ptr(assign), _lib.ptr(perm), _lib.ptr(labels), _lib.ptr(q), _lib.ptr(planted), _lib.ptr(refined),
+                    _lib.ptr(nvalid), B, N, live)
+        outs = (_lib.ptr(correct), _lib.ptr(refined_correct), _lib.ptr(ratio), _lib.ptr(meter.buf), _lib.stream_ptr())
+        if bins is None:
+            _lib.call(pairs.FOLD, *per_pair, *outs)
+        else:
+            _lib.call(pairs.FOLD + '_bins', *per_pair, _lib.ptr(bins), meter.K, *outs)
     if seed_meter is not None:
         seed_fold(seed_meter, seeds, first, perm, nvalid, labels, bins, B, N, live)
         stage['seed_meter'] = seed_meter
     if seeds is not None:
         stage['seeds'], stage['nseeds'] = seeds, stage['seeded'] if nseeds is None else nseeds
     return {'assign': assign, 'qap': q, 'planted': planted, 'correct': correct, 'ratio': ratio, 'perm': perm, 'refined': refined,
-            'refined_correct': None if perm is None else refined_correct, 'meter': meter, 'swaps': swaps, 'status': status, **stage}
+            'refined_correct': None if perm is None else refined_correct, 'meter': meter, 'swaps': swaps, 'status': status,
+            **dict(zip(pairs.EXTRA, (nit, greedy))), **stage}           # (EXTRA: 'nit' and 'greedy' on the weighted route only)
 
 
 def _check_two_opt(who, two_opt):
@@ -802,6 +866,34 @@ def _check_decode_seeds(who, seeds, B, N, dev, faq, refine):
     if refine > 0:
         raise ValueError("%s: seeds= and refine > 0 do not go together (the reference's greedy_qap knows no fixed rows)" % who)
     return seeds
+
+
+def _decode(who, operand, g1, g2, scores, nvalid, labels, meter, live, bins, refine, assign, two_opt, faq, seeds, seed_meter):
+    """The body decode_scores (operand _BitPairs, the graphs as bit words) and decode_scores_weighted (_WeightedPairs, as float
+    matrices) share: the checks, the meter of the operand's class, the Hungarian matching unless `assign`, _decode_launches"""
+    if meter is None and bins is not None:
+        raise ValueError('%s: bins= and a %s as meter go together' % (who, operand.BINNED.__name__))
+    refine = _check_refine(who, refine)
+    two_opt = _check_two_opt(who, two_opt)
+    faq = _check_faq(who, faq)
+    s, nvalid, labels, bins, B, N, live = _score_args(who, scores, nvalid, labels, live, bins)
+    dev = s.device
+    pairs = operand.checked(who, g1, g2, B, N, dev)
+    seeds = _check_decode_seeds(who, seeds, B, N, dev, faq, refine)
+    if meter is None:
+        meter = operand.BINNED.PLAIN(dev)
+    else:
+        _check_meter(who, 'meter', operand.BINNED, meter, bins, dev)
+    _check_seed_meter(who, seed_meter, bins, dev, meter.K if bins is not None else None)
+    if assign is not None:
+        if not torch.is_tensor(assign) or tuple(assign.shape) != (B, N) or assign.is_floating_point() or assign.device != dev:
+            raise ValueError('%s: assign must be a (%d, %d) integer tensor on %s' % (who, B, N, dev))
+        assign = assign.to(torch.int32).contiguous()
+    with torch.cuda.device(dev):
+        if assign is None:
+            from .metrics import lsap_device
+            assign = lsap_device(s, nvalid, want_assign=True)[1]
+        return _decode_launches(pairs, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt, faq, s, seeds, seed_meter)
 
 
 def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, live=None, bins=None, refine=0, assign=None,
@@ -859,139 +951,8 @@ def decode_scores(scores, bits1, bits2, nvalid=None, labels=None, meter=None, li
     matching (without faq: assign) and the final `perm` of the chain got right; it comes back under 'seed_meter'.  The QapMeter and
     its fold are untouched: they count a seeded row as a hit.
     Nothing is read back."""
-    if meter is None and bins is not None:
-        raise ValueError('decode_scores: bins= and a BinnedQapMeter as meter go together')
-    refine = _check_refine('decode_scores', refine)
-    two_opt = _check_two_opt('decode_scores', two_opt)
-    faq = _check_faq('decode_scores', faq)
-    s, nvalid, labels, bins, B, N, live = _score_args('decode_scores', scores, nvalid, labels, live, bins)
-    dev = s.device
-    b1, b2 = _bits_args('decode_scores', (bits1, bits2), B, N, dev)
-    seeds = _check_decode_seeds('decode_scores', seeds, B, N, dev, faq, refine)
-    if meter is None:
-        meter = QapMeter(dev)
-    else:
-        _check_meter('decode_scores', 'meter', BinnedQapMeter, meter, bins, dev)
-    _check_seed_meter('decode_scores', seed_meter, bins, dev, meter.K if bins is not None else None)
-    if assign is not None:
-        if not torch.is_tensor(assign) or tuple(assign.shape) != (B, N) or assign.is_floating_point() or assign.device != dev:
-            raise ValueError('decode_scores: assign must be a (%d, %d) integer tensor on %s' % (B, N, dev))
-        assign = assign.to(torch.int32).contiguous()
-    with torch.cuda.device(dev):
-        if assign is None:
-            from .metrics import lsap_device
-            assign = lsap_device(s, nvalid, want_assign=True)[1]
-        return _decode_launches(b1, b2, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt, faq, s, seeds, seed_meter)
-
-
-def _faq_launches_weighted(x1, x2, s, assign, q, nvalid, B, N, faq, seeds=None):
-    """The FAQ stage of the weighted decode: the twin of _faq_launches on the fp32 views of qap.weighted_views -- no
-    fgnn_expand_adjacency, qap.faq_weighted directly on the views, qap.objective_weighted for the objectives (fp32), with polish
-    the exchange search of qap.two_opt_weighted_device (seeded with seeds) on all B R matchings, fgnn_qap_best_of_f32 for the
-    choice.  -> the keys of _faq_launches, 'qap' and 'faq_qap' float32"""
-    from . import qap
-    dev = x1.device
-    R = faq['restarts']
-    restarted = R > 1 or faq['polish']
-    if restarted and B * R > _lib.FGNN_RESTART_MAX_STARTS:
-        raise ValueError('decode: at most %d starts per call (got %d pairs x %d restarts)' % (_lib.FGNN_RESTART_MAX_STARTS, B, R))
-    if faq['index'] is not None and tuple(faq['index'].shape) != (B,):
-        raise ValueError("decode: faq['index'] must hold %d pair indices, got %s" % (B, tuple(faq['index'].shape)))
-    p0 = err = u = None
-    if seeds is not None and (restarted or faq['P0'] == 'scores'):
-        ix = qap.seed_index_device(seeds, nvalid)
-        u = torch.where(ix['valid'] != 0, ix['nfree'], torch.zeros_like(ix['nfree']))
-    if faq['P0'] == 'scores':
-        if seeds is None:
-            sk = qap.sinkhorn_device(s, nvalid, faq['tau'], faq['iters'])
-        else:
-            sk = qap.sinkhorn_device(qap.seed_gather_device(s, ix['free_a'], ix['free_b'], u), u, faq['tau'], faq['iters'])
-        p0, err = sk['P'], sk['err']
-    restart = None
-    if restarted:
-        def rep(t):
-            return t.repeat_interleave(R, 0) if t is not None else None
-        index = faq['index'].to(torch.int64).contiguous() if faq['index'] is not None else None
-        starts = qap.random_starts_device(p0, nvalid if seeds is None else u, index, faq['seed'], B, N, R, dev)
-        x1r, x2r, nvr, sdr = rep(x1), rep(x2), rep(nvalid), rep(seeds)
-        run = qap.faq_weighted(x1r, x2r, nvr, starts, None, faq['maxiter'], faq['tol'], seeds=sdr, p0_free=seeds is not None)
-        if faq['polish']:
-            t = qap.two_opt_weighted_device(x1r, x2r, N * N, N, run['perm'], nvr, -1, sdr)
-            perms, veto = t['perm'], t['status']
-        else:
-            perms, veto = run['perm'], None
-        best = qap.best_of_device(qap.objective_weighted(x1r, x2r, perms, nvr)['qap'], run['status'], run['nit'], perms, R, veto)
-        out = {'perm': best['perm'], 'nit': best['nit'], 'status': best['status']}
-        if seeds is not None:
-            out['seeded'] = run['seeded'].view(B, R)[:, 0].contiguous()
-        fq, restart = best['qap'], best['restart']
-    else:
-        out = qap.faq_weighted(x1, x2, nvalid, p0, None, faq['maxiter'], faq['tol'], seeds=seeds, p0_free=seeds is not None)
-        fq = qap.objective_weighted(x1, x2, out['perm'], nvalid)['qap']
-    failed = out['status'] == 2
-    res = {'perm': torch.where(failed[:, None], assign, out['perm']), 'qap': torch.where(failed, q, fq), 'faq_perm': out['perm'],
-           'faq_qap': fq, 'faq_nit': out['nit'], 'faq_status': out['status'], 'sinkhorn_err': err, 'faq_restart': restart}
-    if seeds is not None:
-        res['seeded'] = out['seeded']
-    return res
-
-
-def _decode_launches_weighted(x1, x2, gs, ld, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt=False, faq=None,
-                              scores=None, seeds=None, seed_meter=None):
-    """The chain of _decode_launches on the fp32 views of qap.weighted_views: qap.objective_weighted (once more on the labels),
-    fgnn_confident_seeds when seeds is a spec, _faq_launches_weighted, qap.greedy_weighted, qap.two_opt_weighted_device and a fresh
-    objective of its perm, then fgnn_qapw_fold(_bins) and, with a seed_meter, fgnn_seed_fold(_bins) -- which reads integer matchings
-    only and is reused as it is.  meter None: no fold (Siamese_Node_Exp.match_weighted).  -> the dict of decode_scores_weighted"""
-    from . import qap
-    dev = x1.device
-    nseeds = None
-    if isinstance(seeds, dict):
-        picked = qap.confident_seeds_device(scores, nvalid, seeds['count'], seeds['min_margin'])
-        seeds, nseeds = picked['seeds'], picked['nseeds']
-    obj = qap.objective_weighted(x1, x2, assign, nvalid)
-    q, planted = obj['qap'], obj['planted']
-    if labels is not None:
-        planted = qap.objective_weighted(x1, x2, labels, nvalid)['qap']
-    perm = refined = None
-    first = assign
-    mark = meter._mark_refined if meter is not None else (lambda: None)
-    stage = dict.fromkeys(('faq_perm', 'faq_qap', 'faq_nit', 'faq_status', 'sinkhorn_err', 'faq_restart'))
-    if faq is not None:
-        stage = _faq_launches_weighted(x1, x2, scores, assign, q, nvalid, B, N, faq, seeds)
-        perm, refined = stage.pop('perm'), stage.pop('qap')
-        first = perm
-        mark()
-    greedy = None
-    if refine > 0:
-        greedy = qap.greedy_weighted(x1, x2, assign if perm is None else perm, refine, nvalid, labels)
-        perm, refined = greedy['perm'], greedy['s_best'] * 2       # (an exact doubling: trace(A P B P^T), the unit of qap)
-        mark()
-    swaps = status = nit = None
-    if two_opt:
-        t = qap.two_opt_weighted_device(x1, x2, gs, ld, assign if perm is None else perm, nvalid, -1, seeds)
-        perm, swaps, status, nit = t['perm'], t['swaps'], t['status'], t['nit']
-        refined = qap.objective_weighted(x1, x2, perm, nvalid)['qap']
-        mark()
-    correct = refined_correct = ratio = None
-    if meter is not None:
-        words = torch.zeros(2 * B, dtype=torch.int64, device=dev)
-        ratio, ints = words[:B].view(torch.float64), words[B:].view(torch.int32)
-        correct, refined_correct = ints[:B], ints[B:]
-        pairs = (_lib.ptr(assign), _lib.ptr(perm), _lib.ptr(labels), _lib.ptr(q), _lib.ptr(planted), _lib.ptr(refined),
-                 _lib.ptr(nvalid), B, N, live)
-        outs = (_lib.ptr(correct), _lib.ptr(refined_correct), _lib.ptr(ratio), _lib.ptr(meter.buf), _lib.stream_ptr())
-        if bins is None:
-            _lib.call('fgnn_qapw_fold', *pairs, *outs)
-        else:
-            _lib.call('fgnn_qapw_fold_bins', *pairs, _lib.ptr(bins), meter.K, *outs)
-    if seed_meter is not None:
-        seed_fold(seed_meter, seeds, first, perm, nvalid, labels, bins, B, N, live)
-        stage['seed_meter'] = seed_meter
-    if seeds is not None:
-        stage['seeds'], stage['nseeds'] = seeds, stage['seeded'] if nseeds is None else nseeds
-    return {'assign': assign, 'qap': q, 'planted': planted, 'correct': correct, 'ratio': ratio, 'perm': perm, 'refined': refined,
-            'refined_correct': None if perm is None else refined_correct, 'meter': meter, 'swaps': swaps, 'status': status,
-            'nit': nit, 'greedy': greedy, **stage}
+    return _decode('decode_scores', _BitPairs, bits1, bits2, scores, nvalid, labels, meter, live, bins, refine, assign, two_opt, faq,
+                   seeds, seed_meter)
 
 
 def _weighted_args(who, adj1, adj2, B, N, dev):
@@ -1024,31 +985,8 @@ def decode_scores_weighted(scores, adj1, adj2, nvalid=None, labels=None, meter=N
     Returns decode_scores' keys with 'qap', 'planted', 'refined', 'faq_qap' as float32 (plus 'nit', (B,) int64 of the exchange
     search, and 'greedy', the dict of qap.greedy_weighted; None without).  A pair whose `assign` leaves its corner has the
     sentinel qap = -1 of fgnn_qapw_objective and counts as unmatched in the fold.  Nothing is read back."""
-    who = 'decode_scores_weighted'
-    if meter is None and bins is not None:
-        raise ValueError('%s: bins= and a BinnedWeightedQapMeter as meter go together' % who)
-    refine = _check_refine(who, refine)
-    two_opt = _check_two_opt(who, two_opt)
-    faq = _check_faq(who, faq)
-    s, nvalid, labels, bins, B, N, live = _score_args(who, scores, nvalid, labels, live, bins)
-    dev = s.device
-    views = _weighted_args(who, adj1, adj2, B, N, dev)
-    seeds = _check_decode_seeds(who, seeds, B, N, dev, faq, refine)
-    if meter is None:
-        meter = WeightedQapMeter(dev)
-    else:
-        _check_meter(who, 'meter', BinnedWeightedQapMeter, meter, bins, dev)
-    _check_seed_meter(who, seed_meter, bins, dev, meter.K if bins is not None else None)
-    if assign is not None:
-        if not torch.is_tensor(assign) or tuple(assign.shape) != (B, N) or assign.is_floating_point() or assign.device != dev:
-            raise ValueError('%s: assign must be a (%d, %d) integer tensor on %s' % (who, B, N, dev))
-        assign = assign.to(torch.int32).contiguous()
-    with torch.cuda.device(dev):
-        if assign is None:
-            from .metrics import lsap_device
-            assign = lsap_device(s, nvalid, want_assign=True)[1]
-        return _decode_launches_weighted(*views, assign, nvalid, labels, bins, B, N, live, meter, refine, two_opt, faq, s, seeds,
-                                         seed_meter)
+    return _decode('decode_scores_weighted', _WeightedPairs, adj1, adj2, scores, nvalid, labels, meter, live, bins, refine, assign,
+                   two_opt, faq, seeds, seed_meter)
 
 
 def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hungarian=True, loss_on_labels=False, bins=None,
@@ -1117,11 +1055,11 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
         if bins is not None and qap_meter.K != meter.K:
             raise ValueError('evaluate_scores: the qap meter has %d records, the meter %d' % (qap_meter.K, meter.K))
         if adj is None:
-            bits = _bits_args('evaluate_scores', bits, B, N, dev)
+            pairs = _BitPairs(*_bits_args('evaluate_scores', bits, B, N, dev))
         else:
             if not isinstance(adj, (tuple, list)) or len(adj) != 2:
                 raise ValueError('evaluate_scores: adj must be the pair (x1, x2) of the two graphs')
-            views = _weighted_args('evaluate_scores', adj[0], adj[1], B, N, dev)
+            pairs = _WeightedPairs.checked('evaluate_scores', adj[0], adj[1], B, N, dev)
         seeds = _check_decode_seeds('evaluate_scores', seeds, B, N, dev, faq, refine)
         _check_seed_meter('evaluate_scores', seed_meter, bins, dev, meter.K if bins is not None else None)
     with torch.cuda.device(dev):
@@ -1150,12 +1088,7 @@ def evaluate_scores(scores, nvalid=None, labels=None, meter=None, live=None, hun
         ranks = None if rank_meter is None else _rank_launches(s, nvalid, labels, bins, B, N, live, rank_meter)
         decode = None
         if qap_meter is not None:
-            if adj is None:
-                decode = _decode_launches(*bits, assign, nvalid, labels, bins, B, N, live, qap_meter, refine, two_opt, faq, s, seeds,
-                                          seed_meter)
-            else:
-                decode = _decode_launches_weighted(*views, assign, nvalid, labels, bins, B, N, live, qap_meter, refine, two_opt, faq,
-                                                   s, seeds, seed_meter)
+            decode = _decode_launches(pairs, assign, nvalid, labels, bins, B, N, live, qap_meter, refine, two_opt, faq, s, seeds, seed_meter)
     n = nvalid if nvalid is not None else torch.full((B,), N, **i32)
     out = {'ce': pair_ce, 'n': n, 'correct_max': pair_max, 'correct_lsap': correct, 'assign': assign, 'meter': meter}
     if ranks is not None:

@@ -133,6 +133,42 @@ class Siamese_Node_Exp(nn.Module):
             return MaskedTensor(scores, nvalid, (1, 2), x1.base_name)
         return scores
 
+    def _match_inputs(self, who, x1, x2, refine, labels, faq, seeds, seed_meter):
+        """What `match` and `match_weighted` (who, in the messages) do before they decode: the refusals of faq, seeds and seed_meter,
+        the eager forward under no_grad, the ragged batch unwrapped, labels and seeds cut to n and checked.
+        -> (faq checked, scores as the model returned them, s / t1 / t2 their and the two sides' plain tensors, nv (B,) int32 or None,
+        labels, seeds: a (B, n) int32 tensor, None, or the checked spec of evaluation.seed_spec, which the caller launches)"""
+        from .evaluation import SeedMeter, _check_faq, seed_spec
+        faq = _check_faq(who, faq)
+        spec = seed_spec(who, seeds)
+        if seed_meter is not None and (not isinstance(seed_meter, SeedMeter) or faq is None):
+            raise ValueError('%s: seed_meter must be a SeedMeter and needs the faq= stage' % who)
+        if seeds is not None and faq is None:
+            raise ValueError('%s: seeds= needs the faq= stage (the Hungarian matching knows no fixed rows)' % who)
+        if seeds is not None and refine:
+            raise ValueError("%s: seeds= and refine > 0 do not go together (the reference's greedy_qap knows no fixed rows)" % who)
+        a1, a2 = _unwrap_input(x1), _unwrap_input(x2)
+        with torch.no_grad():
+            scores = self(a1, a2)
+            ragged = isinstance(scores, MaskedTensor)
+            t1, t2 = (a1.tensor.rename(None), a2.tensor.rename(None)) if ragged else (a1, a2)
+            s = scores.tensor.rename(None) if ragged else scores
+            dev, B, N = s.device, s.shape[0], s.shape[-1]
+            nv = a1.nvalid.to(device=dev, dtype=torch.int32).contiguous() if ragged else None
+            if torch.is_tensor(labels) and labels.dim() == 2 and labels.shape[1] > N:
+                labels = labels[:, :N]
+            labels = labels_tensor(labels, B, N, dev)
+            if torch.is_tensor(seeds) and seeds.dim() == 2 and seeds.shape[1] > N:
+                seeds = seeds[:, :N]
+            if spec is None:
+                seeds = qap.check_seeds(who, seeds, B, N, dev)
+            else:
+                if N > qap._lib.FGNN_SEED_MAX_N:
+                    raise RuntimeError('%s: seeds from the scores take at most %d vertices per graph (got %d)'
+                                       % (who, qap._lib.FGNN_SEED_MAX_N, N))
+                seeds = spec
+        return faq, scores, s, t1, t2, nv, labels, seeds
+
     def match(self, x1, x2, refine=0, weighted=False, labels=None, two_opt=False, faq=None, seeds=None, seed_meter=None):
         """Decode a batch: the eager forward under no_grad (no `.grad` is touched), the Hungarian matching of -log_softmax(scores)
         and the reference's evaluation of it (toolbox/metrics.py:168-193 all_acc_qap), all on the device (qap.py).  Takes what
@@ -181,36 +217,13 @@ class Siamese_Node_Exp(nn.Module):
             raise NotImplementedError('match: two_opt=True runs on 0/1 adjacency only, not with weighted=True')
         if faq is not None and weighted:
             raise NotImplementedError('match: faq= runs on 0/1 adjacency only, not with weighted=True')
-        from .evaluation import SeedMeter, _check_faq, _faq_launches, seed_fold, seed_spec
-        faq = _check_faq('match', faq)
-        spec = seed_spec('match', seeds)
-        if seed_meter is not None and (not isinstance(seed_meter, SeedMeter) or faq is None):
-            raise ValueError('match: seed_meter must be a SeedMeter and needs the faq= stage')
-        if seeds is not None and faq is None:
-            raise ValueError('match: seeds= needs the faq= stage (the Hungarian matching knows no fixed rows)')
-        if seeds is not None and refine:
-            raise ValueError("match: seeds= and refine > 0 do not go together (the reference's greedy_qap knows no fixed rows)")
-        a1, a2 = _unwrap_input(x1), _unwrap_input(x2)
+        from .evaluation import _BitPairs, _faq_launches, seed_fold
+        faq, scores, s, t1, t2, nv, labels, seeds = self._match_inputs('match', x1, x2, refine, labels, faq, seeds, seed_meter)
+        dev = s.device
         with torch.no_grad():
-            scores = self(a1, a2)
-            ragged = isinstance(scores, MaskedTensor)
-            t1, t2 = (a1.tensor.rename(None), a2.tensor.rename(None)) if ragged else (a1, a2)
-            s = scores.tensor.rename(None) if ragged else scores
-            dev = s.device
-            nv = a1.nvalid.to(device=dev, dtype=torch.int32).contiguous() if ragged else None
-            if torch.is_tensor(labels) and labels.dim() == 2 and labels.shape[1] > s.shape[-1]:
-                labels = labels[:, :s.shape[-1]]
-            labels = labels_tensor(labels, s.shape[0], s.shape[-1], dev)
-            if torch.is_tensor(seeds) and seeds.dim() == 2 and seeds.shape[1] > s.shape[-1]:
-                seeds = seeds[:, :s.shape[-1]]
             nseeds = None
-            if spec is None:
-                seeds = qap.check_seeds('match', seeds, s.shape[0], s.shape[-1], dev)
-            else:
-                if s.shape[-1] > qap._lib.FGNN_SEED_MAX_N:
-                    raise RuntimeError('match: seeds from the scores take at most %d vertices per graph (got %d)'
-                                       % (qap._lib.FGNN_SEED_MAX_N, s.shape[-1]))
-                picked = qap.confident_seeds_device(s.detach().float(), nv, spec['count'], spec['min_margin'])
+            if isinstance(seeds, dict):     # a spec: the seeds come from the scores the solver will see
+                picked = qap.confident_seeds_device(s.detach().float(), nv, seeds['count'], seeds['min_margin'])
                 seeds, nseeds = picked['seeds'], picked['nseeds']
             if weighted:
                 correct, assign = lsap_device(s, nv, want_assign=True)
@@ -231,8 +244,8 @@ class Siamese_Node_Exp(nn.Module):
             if faq is not None or two_opt:
                 target = labels if labels is not None else torch.arange(s.shape[-1], dtype=torch.int32, device=dev).expand_as(assign).contiguous()
             if faq is not None:
-                st = _faq_launches(b1, b2, s.detach().float(), assign, obj['qap'].to(torch.int32), nv, s.shape[0], s.shape[-1], faq,
-                                   seeds)
+                st = _faq_launches(_BitPairs(b1, b2), s.detach().float(), assign, obj['qap'].to(torch.int32), nv, s.shape[0], s.shape[-1],
+                                   faq, seeds)
                 if seeds is not None:
                     out['seeded'] = st['seeded']
                     out['seeds'], out['nseeds'] = seeds, st['seeded'] if nseeds is None else nseeds
@@ -262,44 +275,19 @@ class Siamese_Node_Exp(nn.Module):
         the outputs of qap.greedy_weighted; with two_opt perm, qap_2opt, acc_2opt, swaps, nit, status -- the objectives as float32.
         With only refine the outputs equal ``match(weighted=True, refine=)`` bit for bit.  No verdict is taken and nothing
         synchronises.  `match` itself is unchanged, its refusals of weighted=True with two_opt / faq included."""
-        from .evaluation import (SeedMeter, _check_faq, _check_refine, _check_two_opt, _decode_launches_weighted, _weighted_args,
-                                 seed_spec)
+        from .evaluation import _WeightedPairs, _check_refine, _check_two_opt, _decode_launches
         who = 'match_weighted'
-        refine, two_opt, faq = _check_refine(who, refine), _check_two_opt(who, two_opt), _check_faq(who, faq)
-        spec = seed_spec(who, seeds)
-        if seed_meter is not None and (not isinstance(seed_meter, SeedMeter) or faq is None):
-            raise ValueError('%s: seed_meter must be a SeedMeter and needs the faq= stage' % who)
-        if seeds is not None and faq is None:
-            raise ValueError('%s: seeds= needs the faq= stage (the Hungarian matching knows no fixed rows)' % who)
-        if seeds is not None and refine:
-            raise ValueError("%s: seeds= and refine > 0 do not go together (the reference's greedy_qap knows no fixed rows)" % who)
-        a1, a2 = _unwrap_input(x1), _unwrap_input(x2)
+        refine, two_opt = _check_refine(who, refine), _check_two_opt(who, two_opt)
+        faq, scores, s, t1, t2, nv, labels, seeds = self._match_inputs(who, x1, x2, refine, labels, faq, seeds, seed_meter)
+        dev, B, N = s.device, s.shape[0], s.shape[-1]
         with torch.no_grad():
-            scores = self(a1, a2)
-            ragged = isinstance(scores, MaskedTensor)
-            t1, t2 = (a1.tensor.rename(None), a2.tensor.rename(None)) if ragged else (a1, a2)
-            s = scores.tensor.rename(None) if ragged else scores
-            dev, B, N = s.device, s.shape[0], s.shape[-1]
-            nv = a1.nvalid.to(device=dev, dtype=torch.int32).contiguous() if ragged else None
-            if torch.is_tensor(labels) and labels.dim() == 2 and labels.shape[1] > N:
-                labels = labels[:, :N]
-            labels = labels_tensor(labels, B, N, dev)
-            if torch.is_tensor(seeds) and seeds.dim() == 2 and seeds.shape[1] > N:
-                seeds = seeds[:, :N]
-            if spec is None:
-                seeds = qap.check_seeds(who, seeds, B, N, dev)
-            else:
-                if N > qap._lib.FGNN_SEED_MAX_N:
-                    raise RuntimeError('%s: seeds from the scores take at most %d vertices per graph (got %d)'
-                                       % (who, qap._lib.FGNN_SEED_MAX_N, N))
-                seeds = spec
-            views = _weighted_args(who, t1, t2, B, N, dev)
+            pairs = _WeightedPairs.checked(who, t1, t2, B, N, dev)
             with torch.cuda.device(dev):
                 correct, assign = lsap_device(s, nv, want_assign=True)
                 if labels is not None:
                     correct = count_matches(assign, labels, nv)
-                d = _decode_launches_weighted(*views, assign, nv, labels, None, B, N, B, None, refine, two_opt, faq, s.detach().float(),
-                                              seeds, seed_meter)
+                d = _decode_launches(pairs, assign, nv, labels, None, B, N, B, None, refine, two_opt, faq, s.detach().float(), seeds,
+                                     seed_meter)
                 out = {'scores': scores, 'assign': assign, 'acc': correct.to(torch.int64), 'qap': d['qap'], 'planted': d['planted']}
                 if faq is not None or two_opt:
                     target = labels if labels is not None else torch.arange(N, dtype=torch.int32, device=dev).expand_as(assign).contiguous()
